@@ -12,7 +12,12 @@ ranks itself (fresh children through torch.distributed.run, before this process 
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it is one of the ranks.  RCCL (backend "nccl") carries
 the barrier, the max-over-ranks of the time, the optional me_results all-gather and the reconstructed-picture all-gather leg.
 
-Extra legs (same JSON line, under "legs"; rank 0 unless stated): whole-picture ME with sub-pel + bi-prediction (configs[2]),
+A plain run does only what the headline needs: set-up, warm-up, the timed steps and the JSON line.  `--dump-outputs DIR` also writes
+rank 0's results of the last timed step (sad, mv and the search-centre descriptors) as DIR/<name>.npy, float64; the inputs depend on
+the arguments alone, so two builds can be compared output for output.
+
+With `--full` the same line also carries the full-pel kernel's `roofline` (its own event-timed launches), the CPU baselines (N = 1) and
+the extra legs (under "legs"; rank 0 unless stated): whole-picture ME with sub-pel + bi-prediction (configs[2]),
 transform/quantisation chains at the SURVEY 8d shapes with the reference's real quantiser rows (configs[3]), the 16x16 +-16
 SadLoopKernel workload at 856x480 (configs[0]), a 3840x2160 / 10-bit pass (configs[4]) and the recon exchange (all ranks).
 """
@@ -936,7 +941,13 @@ def main():
     ap.add_argument("--no-host-threads", action="store_true", help="skip the multi-threaded host-pointer leg (counter collection under rocprofv3 "
                                                                     "crashed inside the profiler when 20 host threads issued copies)")
     ap.add_argument("--gather-results", action="store_true", help="also gather the (sad, mv) results of every step on every rank (svthip_me_gather_results_dev, RCCL)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the full-pel kernel's roofline "
+                                                         "(its own timed launches), the per-config legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write rank 0's results of the last step "
+                                                                         "(sad, mv, search_desc) to DIR/<name>.npy as float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_baseline_worker:
         sys.exit(cpu_baseline_worker_main())
 
@@ -951,7 +962,7 @@ def main():
             sys.exit(2)
 
     cpu_worker = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the CPU baselines run in a child started NOW, before this process touches a GPU; it idles until the GPU numbers are in
         cpu_worker = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--cpu-baseline-worker"], stdin=subprocess.PIPE,
                                       stdout=subprocess.PIPE, text=True)
@@ -1036,11 +1047,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # dominant-kernel duration on this rank, HIP events on the stream the kernel runs on
-    kern_ms = ctx.fullpel_search_time_dev(*a, max(5, min(args.steps, 20)))
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything else writes these buffers; int32 values are exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, buf in (("sad", d_sad), ("mv", d_mv), ("search_desc", d_desc)):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), buf.cpu().numpy().astype(np.float64))
+
+    if args.full:
+        # dominant-kernel duration on this rank, HIP events on the stream the kernel runs on
+        kern_ms = ctx.fullpel_search_time_dev(*a, max(5, min(args.steps, 20)))
 
     legs = {}
-    if not args.no_legs:
+    if args.full and not args.no_legs:
         want = set(filter(None, args.only_legs.split(",")))
         on = lambda name: not want or name in want  # noqa: E731
         if on("recon_exchange"):
@@ -1076,13 +1094,6 @@ def main():
 
     if rank == 0:
         value = total_blocks_per_step * args.steps / elapsed
-        achieved = ALGO_BYTES_PER_BLOCK * n_blocks / (kern_ms * 1e-3) / 1e9
-        absdiff_rate = ABSDIFF_PER_BLOCK * n_blocks / (kern_ms * 1e-3)
-        rec85 = pmc_entry("fullpel85_kernel")
-        traffic = pmc_traffic_bytes(rec85)
-        if traffic is None:   # no round-3 profile in the tree: the round-2 record of the same launch
-            tr = load_profile_json("r02_pmc_traffic.json") or {}
-            traffic = pmc_traffic_bytes(tr.get("svthip::fullpel85_kernel"))
         out = {
             "metric": "64x64 SAD-search blocks/sec",
             "value": round(value, 1),
@@ -1105,21 +1116,29 @@ def main():
                        "sharding": "frame-sharded: every rank searches its contiguous superblock range (510/N, balanced to one SB) of every "
                                    "picture of the 12 x N picture batch; no data-path collective"
                                    + ("; (sad, mv) all-gathered over RCCL every step" if args.gather_results and distributed else "")},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
-                         "traffic_note": "bytes per launch of 6120 blocks = (2 x FETCH_SIZE + WRITE_SIZE) KB x 1024 from separate rocprofv3 --pmc "
-                                         "passes (profiles/*_pmc_traffic.json; FETCH_SIZE doubled as the MI355X guide prescribes for gfx950); "
-                                         "algorithmic bytes per launch = 20905 x blocks",
-                         "valu_busy": counters(rec85, kern_ms, 0)["valu_busy"],
-                         "kernel": "fullpel85_kernel", "kernel_ms": round(kern_ms, 4), "kernel_blocks": n_blocks,
-                         "algorithmic_bytes_per_block": ALGO_BYTES_PER_BLOCK,
-                         "note": "search is ~400 abs-diff per compulsory byte: VALU-bound by construction (SURVEY 8d); see valu",
-                         "valu": {"achieved_absdiff_per_s": round(absdiff_rate, 0),
-                                  "peak_absdiff_per_s": round(VALU_PEAK_ABSDIFF_PER_S, 0),
-                                  "frac": round(absdiff_rate / VALU_PEAK_ABSDIFF_PER_S, 4),
-                                  "peak_source": "measured v_qsad_pk_u16_u8 issue rate, tools/ubench_valu.hip"}},
-            "legs": legs,
         }
+        if args.full:
+            achieved = ALGO_BYTES_PER_BLOCK * n_blocks / (kern_ms * 1e-3) / 1e9
+            absdiff_rate = ABSDIFF_PER_BLOCK * n_blocks / (kern_ms * 1e-3)
+            rec85 = pmc_entry("fullpel85_kernel")
+            traffic = pmc_traffic_bytes(rec85)
+            if traffic is None:   # no round-3 profile in the tree: the round-2 record of the same launch
+                tr = load_profile_json("r02_pmc_traffic.json") or {}
+                traffic = pmc_traffic_bytes(tr.get("svthip::fullpel85_kernel"))
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
+                               "traffic_note": "bytes per launch of 6120 blocks = (2 x FETCH_SIZE + WRITE_SIZE) KB x 1024 from separate rocprofv3 --pmc "
+                                               "passes (profiles/*_pmc_traffic.json; FETCH_SIZE doubled: on gfx950 it tallies half the bytes of a wide streaming read); "
+                                               "algorithmic bytes per launch = 20905 x blocks",
+                               "valu_busy": counters(rec85, kern_ms, 0)["valu_busy"],
+                               "kernel": "fullpel85_kernel", "kernel_ms": round(kern_ms, 4), "kernel_blocks": n_blocks,
+                               "algorithmic_bytes_per_block": ALGO_BYTES_PER_BLOCK,
+                               "note": "search is ~400 abs-diff per compulsory byte: VALU-bound by construction (SURVEY 8d); see valu",
+                               "valu": {"achieved_absdiff_per_s": round(absdiff_rate, 0),
+                                        "peak_absdiff_per_s": round(VALU_PEAK_ABSDIFF_PER_S, 0),
+                                        "frac": round(absdiff_rate / VALU_PEAK_ABSDIFF_PER_S, 4),
+                                        "peak_source": "measured v_qsad_pk_u16_u8 issue rate, tools/ubench_valu.hip"}}
+            out["legs"] = legs
         if cpu_worker is not None:
             try:
                 res, _ = cpu_worker.communicate("go\n", timeout=300)
