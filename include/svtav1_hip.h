@@ -582,6 +582,97 @@ int32_t svthip_tu_batcher_read_coeffs(svthip_tu_batcher *b, uint32_t handle, int
 int32_t svthip_tu_batcher_pools(const svthip_tu_batcher *b, const int32_t **d_qcoeff, const int32_t **d_dqcoeff, const void **d_recon_scratch);
 
 /* ---------------------------------------------------------------------------------------------
+ * Coefficient rate estimation and the RD transform-type decision.
+ *
+ * svthip_coeff_rate_tables holds the fields of MdRateEstimationContext_t that the coefficient rate reads
+ * (Codec/EbMdRateEstimation.h:27-38, :110-116) with the reference's element layout: a C host fills it with four memcpy's from its
+ * own context once per picture and uploads it.  The library never builds these tables. */
+typedef struct svthip_lv_map_coeff_cost { /* LV_MAP_COEFF_COST */
+    int32_t txb_skip_cost[13][2];         /* [TXB_SKIP_CONTEXTS][2] */
+    int32_t base_eob_cost[4][3];          /* [SIG_COEF_CONTEXTS_EOB][3] */
+    int32_t base_cost[42][4];             /* [SIG_COEF_CONTEXTS][4] */
+    int32_t eob_extra_cost[22][2];        /* [EOB_COEF_CONTEXTS][2] */
+    int32_t dc_sign_cost[3][2];           /* [DC_SIGN_CONTEXTS][2] */
+    int32_t lps_cost[21][13];             /* [LEVEL_CONTEXTS][COEFF_BASE_RANGE + 1] */
+} svthip_lv_map_coeff_cost;
+
+typedef struct svthip_lv_map_eob_cost { /* LV_MAP_EOB_COST */
+    int32_t eob_cost[2][11];
+} svthip_lv_map_eob_cost;
+
+typedef struct svthip_coeff_rate_tables {
+    svthip_lv_map_coeff_cost coeffFacBits[5][2];  /* [TX_SIZES][PLANE_TYPES] */
+    svthip_lv_map_eob_cost eobFracBits[7][2];
+    int32_t interTxTypeFacBits[4][4][17];         /* [EXT_TX_SETS_INTER][EXT_TX_SIZES][CDF_SIZE(TX_TYPES)] */
+    int32_t intraTxTypeFacBits[3][4][13][17];     /* [EXT_TX_SETS_INTRA][EXT_TX_SIZES][INTRA_MODES][CDF_SIZE(TX_TYPES)] */
+} svthip_coeff_rate_tables;
+
+/* One TU of a rate launch.  coeff_offset (multiple of 4) and iscan_offset (multiple of 4) index the int32 level pool and the
+ * int16 inverse-scan pool of the fused chain (min(W,32) x min(H,32) levels, row stride min(W,32)). */
+typedef struct svthip_coeff_rate_desc {
+    uint32_t coeff_offset;
+    uint32_t iscan_offset;
+    uint8_t tx_type;
+    uint8_t plane_type;     /* 0 luma, 1 chroma */
+    uint8_t txb_skip_ctx;   /* 0..12 */
+    uint8_t dc_sign_ctx;    /* 0..2 */
+    uint8_t is_inter;       /* candidate_ptr->type == INTER_MODE */
+    uint8_t intra_mode;     /* candidate_ptr->pred_mode when intra, 0..12 */
+    uint8_t reduced_tx_set; /* reduced_tx_set_used */
+    uint8_t reserved;
+} svthip_coeff_rate_desc;
+
+/* Av1TuEstimateCoeffBits for one plane of n_tu TUs of ONE TxSize (Codec/EbRateDistortionCost.c:1350-1460): d_bits[i] =
+ * av1_cost_coeffs_txb (:496-603, nz-map contexts as av1_get_nz_map_contexts_sse2 computes them) when d_eob[i] > 0, else
+ * av1_cost_skip_txb (:485-493).  The level at scan position eob - 1 must be non-zero (what a quantiser's eob guarantees).
+ * tx_size >= 19, a level pool that is not 16-byte aligned or an iscan pool that is not 8-byte aligned are refused
+ * (SVTHIP_ERR_BAD_PARAMETER); a descriptor whose coeff_offset or iscan_offset is not a multiple of 4 gets d_bits = 0xffffffff. */
+int32_t svthip_coeff_rate_batch_dev(svthip_ctx *ctx, const svthip_coeff_rate_tables *d_tables, const int32_t *d_qcoeff,
+                                    const uint16_t *d_eob, const int16_t *d_iscan, const svthip_coeff_rate_desc *d_desc, uint32_t n_tu,
+                                    uint32_t tx_size, uint32_t *d_bits, void *stream);
+
+/* RD transform-type search through the batcher (ProductFullLoopTxSearch, Codec/EbFullLoop.c:1138-1352, with TX_TYPE_FIX, BUG_FIX
+ * and CBF_ZERO_OFF).  _set_tx_search once after _begin: d_tables on the device, iscan_offsets[tx_size * 16 + tx_type] the position
+ * of every scan in the iscan pool bound with _begin.  _add_tx_search adds one TU: one candidate per bit of type_mask, each an
+ * ordinary candidate with its own candidate handle, reconstructing into scratch.  _flush then runs the fused chain, the rate
+ * kernel on the search candidates and a decision kernel (one lane per TU), and downloads one svthip_tx_search_result per TU; a
+ * batch without search TUs launches and downloads exactly what it did before.  The winner's candidate handle keeps working with
+ * _result, _read_coeffs and _pools. */
+typedef struct svthip_tx_search_tu {
+    uint64_t lambda;        /* full_lambda */
+    uint32_t src_offset;
+    uint32_t src_stride;
+    uint32_t pred_offset;
+    uint32_t pred_stride;
+    uint32_t qparam_index;
+    uint16_t type_mask;     /* bit t: evaluate TxType t (svthip_tx_search_type_mask) */
+    uint8_t tx_size;
+    uint8_t is_inter;
+    uint8_t intra_mode;
+    uint8_t reduced_tx_set;
+    uint8_t txb_skip_ctx;
+    uint8_t dc_sign_ctx;
+    uint8_t reserved[4];
+} svthip_tx_search_tu;
+
+typedef struct svthip_tx_search_result {
+    uint64_t full_cost;     /* the winner's yFullCost */
+    uint64_t distortion[2]; /* the winner's (distortion + three_quad_energy), shifted by (MAX_TX_SCALE - tx_scale) * 2 */
+    uint64_t coeff_bits;    /* the winner's yTuCoeffBits after Av1TuCalcCostLuma */
+    uint32_t candidate;     /* the winner's candidate handle (_result, _read_coeffs) */
+    uint16_t eob;
+    uint8_t tx_type;
+    uint8_t reserved;
+} svthip_tx_search_result;
+
+int32_t svthip_tu_batcher_set_tx_search(svthip_tu_batcher *b, const svthip_coeff_rate_tables *d_tables, const uint32_t iscan_offsets[19 * 16]);
+int32_t svthip_tu_batcher_add_tx_search(svthip_tu_batcher *b, const svthip_tx_search_tu *tu, uint32_t *out_tu_handle);
+int32_t svthip_tu_batcher_tx_search_result(const svthip_tu_batcher *b, uint32_t tu_handle, svthip_tx_search_result *out);
+/* the reference's candidate mask: av1_ext_tx_used[get_ext_tx_set_type(..)], DCT_DCT only above 32x32 (EbFullLoop.c:1166-1185) and,
+ * when fast_tx_search != 0, allowed_tx_set_a (:1095, :1190-1197); DCT_DCT alone when nothing else is left */
+uint16_t svthip_tx_search_type_mask(uint32_t tx_size, int32_t is_inter, int32_t reduced_tx_set, int32_t fast_tx_search);
+
+/* ---------------------------------------------------------------------------------------------
  * Reference-layout results and host-pointer forms (what a C host that owns host memory binds).
  *
  * svthip_me_cu_result_ref has the memory layout of the reference's MeCuResults_t (Codec/EbMotionEstimationLcuResults.h:56-76) as

@@ -97,6 +97,32 @@ hipError_t launch_encode_tu(const void* src, const void* pred, void* recon, int 
                             int w, int h, const int16_t* qparams, const int16_t* iscan, int32_t* coeff, int32_t* qcoeff,
                             int32_t* dqcoeff, uint16_t* eob, uint64_t* energy, uint64_t* dist, uint32_t max_workgroups, hipStream_t s);
 
+// TxSize -> width / height (TX_4X4 .. TX_64X16, Codec/EbDefinitions.h)
+__host__ __device__ inline int tx_w(int tx_size)
+{
+    constexpr uint8_t w[19] = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64};
+    return w[tx_size];
+}
+__host__ __device__ inline int tx_h(int tx_size)
+{
+    constexpr uint8_t h[19] = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16};
+    return h[tx_size];
+}
+
+// tq_coeff_rate.hip: the rate kernel (svthip_coeff_rate_batch_dev) and the batcher's RD decision.  A search TU on the device:
+// index[t] = the position of its TxType-t candidate inside the (tx_size, t) run of the launch order (0xffffffff: not a candidate),
+// bases[tx_size * 16 + t] = where that run starts.
+struct tx_search_tu_dev {
+    uint64_t lambda;
+    uint32_t index[16];
+    uint32_t tx_size;
+    uint32_t reserved;
+};
+hipError_t launch_coeff_rate(const svthip_coeff_rate_tables* tables, const int32_t* qcoeff, const uint16_t* eob, const int16_t* iscan,
+                             const svthip_coeff_rate_desc* desc, uint32_t n_tu, int tx_size, uint32_t* bits, hipStream_t s);
+hipError_t launch_tx_decision(const tx_search_tu_dev* tus, uint32_t n_tus, const uint32_t* bases, const uint16_t* eob, const uint64_t* energy,
+                              const uint64_t* dist, const uint32_t* bits, svthip_tx_search_result* out, hipStream_t s);
+
 __global__ void fullpel209_kernel(const uint8_t* __restrict__ src_plane, uint32_t src_stride, const uint8_t* __restrict__ ref_plane,
                                   uint32_t ref_stride, const int32_t* __restrict__ desc, uint32_t n_sb, uint32_t* __restrict__ out_sad,
                                   uint32_t* __restrict__ out_mv);

@@ -536,6 +536,26 @@ int32_t svthip_encode_tu16_batch_dev(svthip_ctx* ctx, const uint16_t* d_src, con
                             d_dqcoeff, d_eob, d_three_quad_energy, d_distortion, stream);
 }
 
+int32_t svthip_coeff_rate_batch_dev(svthip_ctx* ctx, const svthip_coeff_rate_tables* d_tables, const int32_t* d_qcoeff,
+                                    const uint16_t* d_eob, const int16_t* d_iscan, const svthip_coeff_rate_desc* d_desc, uint32_t n_tu,
+                                    uint32_t tx_size, uint32_t* d_bits, void* stream)
+{
+    ENTER(ctx);
+    if (tx_size >= 19) return fail(SVTHIP_ERR_BAD_PARAMETER, "tx_size must be a TxSize 0..18%s (got %d)", "", (int)tx_size);
+    if (n_tu == 0) return SVTHIP_OK;
+    if (!d_tables || !d_qcoeff || !d_eob || !d_iscan || !d_desc || !d_bits) return fail(SVTHIP_ERR_BAD_PARAMETER, "null pointer argument%s", "");
+    // a lane loads 4 levels (16 B) and 4 inverse-scan entries (8 B) at once: the pools' bases as for the fused chain, the descriptors'
+    // offsets multiples of 4 (checked by the kernel's callers that build them; the pools here)
+    if (reinterpret_cast<uintptr_t>(d_qcoeff) & 15u) return fail(SVTHIP_ERR_BAD_PARAMETER, "level pool must be 16-byte aligned%s", "");
+    if (reinterpret_cast<uintptr_t>(d_iscan) & 7u) return fail(SVTHIP_ERR_BAD_PARAMETER, "iscan pool must be 8-byte aligned%s", "");
+    if ((reinterpret_cast<uintptr_t>(d_tables) | reinterpret_cast<uintptr_t>(d_desc) | reinterpret_cast<uintptr_t>(d_bits)) & 3u)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "tables / descriptors / output must be 4-byte aligned%s", "");
+    if (reinterpret_cast<uintptr_t>(d_eob) & 1u) return fail(SVTHIP_ERR_BAD_PARAMETER, "eob array must be 2-byte aligned%s", "");
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIP_TRY(svthip::launch_coeff_rate(d_tables, d_qcoeff, d_eob, d_iscan, d_desc, n_tu, (int)tx_size, d_bits, s));
+    return SVTHIP_OK;
+}
+
 int32_t svthip_me_hme_search_center_batch_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* cur,
                                               const svthip_pa_picture* ref, uint32_t n_jobs, const svthip_me_params* params,
                                               uint32_t list_index, const svthip_sb_origin* d_sb, uint32_t n_sb,

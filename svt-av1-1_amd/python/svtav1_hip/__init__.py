@@ -155,6 +155,16 @@ def lib() -> C.CDLL:
     L.svthip_tu_batcher_read_coeffs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.svthip_tu_batcher_pools.restype = C.c_int32
     L.svthip_tu_batcher_pools.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.svthip_coeff_rate_batch_dev.restype = C.c_int32
+    L.svthip_coeff_rate_batch_dev.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.svthip_tu_batcher_set_tx_search.restype = C.c_int32
+    L.svthip_tu_batcher_set_tx_search.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.svthip_tu_batcher_add_tx_search.restype = C.c_int32
+    L.svthip_tu_batcher_add_tx_search.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.svthip_tu_batcher_tx_search_result.restype = C.c_int32
+    L.svthip_tu_batcher_tx_search_result.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.svthip_tx_search_type_mask.restype = C.c_uint16
+    L.svthip_tx_search_type_mask.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32]
     _lib = L
     return L
 
@@ -459,6 +469,69 @@ class TuBatcher:
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
         _check(lib().svthip_tu_batcher_pools(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def set_tx_search(self, d_tables, iscan_offsets):
+        """d_tables: device address of a COEFF_RATE_TABLES_DTYPE record; iscan_offsets: [19][16] (or 304) iscan-pool offsets"""
+        off = np.ascontiguousarray(np.asarray(iscan_offsets, np.uint32).reshape(19 * 16))
+        _check(lib().svthip_tu_batcher_set_tx_search(self._h, d_tables, off.ctypes.data))
+
+    def add_tx_search(self, tu: "TxSearchTu" = None, **fields) -> int:
+        """one TU of the RD transform-type search (a TxSearchTu, or its fields as keywords); returns the TU handle"""
+        if tu is None:
+            tu = TxSearchTu(**fields)
+        h = C.c_uint32(0)
+        _check(lib().svthip_tu_batcher_add_tx_search(self._h, C.byref(tu), C.byref(h)))
+        return h.value
+
+    def tx_search_result(self, tu_handle) -> "TxSearchResult":
+        r = TxSearchResult()
+        _check(lib().svthip_tu_batcher_tx_search_result(self._h, tu_handle, C.byref(r)))
+        return r
+
+
+# ---- coefficient rate and the RD transform-type search (include/svtav1_hip.h) ----
+LV_MAP_COEFF_COST_DTYPE = np.dtype([("txb_skip_cost", "<i4", (13, 2)), ("base_eob_cost", "<i4", (4, 3)), ("base_cost", "<i4", (42, 4)),
+                                    ("eob_extra_cost", "<i4", (22, 2)), ("dc_sign_cost", "<i4", (3, 2)), ("lps_cost", "<i4", (21, 13))])
+assert LV_MAP_COEFF_COST_DTYPE.itemsize == 2116
+# svthip_coeff_rate_tables: eobFracBits is [7][2] LV_MAP_EOB_COST { eob_cost[2][11] }
+COEFF_RATE_TABLES_DTYPE = np.dtype([("coeffFacBits", LV_MAP_COEFF_COST_DTYPE, (5, 2)), ("eobFracBits", "<i4", (7, 2, 2, 11)),
+                                    ("interTxTypeFacBits", "<i4", (4, 4, 17)), ("intraTxTypeFacBits", "<i4", (3, 4, 13, 17))])
+assert COEFF_RATE_TABLES_DTYPE.itemsize == 34088
+COEFF_RATE_DESC_DTYPE = np.dtype([("coeff_offset", "<u4"), ("iscan_offset", "<u4"), ("tx_type", "u1"), ("plane_type", "u1"),
+                                  ("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("is_inter", "u1"), ("intra_mode", "u1"),
+                                  ("reduced_tx_set", "u1"), ("reserved", "u1")])
+assert COEFF_RATE_DESC_DTYPE.itemsize == 16
+
+
+class TxSearchTu(C.Structure):
+    _fields_ = [("lambda_", C.c_uint64), ("src_offset", C.c_uint32), ("src_stride", C.c_uint32), ("pred_offset", C.c_uint32),
+                ("pred_stride", C.c_uint32), ("qparam_index", C.c_uint32), ("type_mask", C.c_uint16), ("tx_size", C.c_uint8),
+                ("is_inter", C.c_uint8), ("intra_mode", C.c_uint8), ("reduced_tx_set", C.c_uint8), ("txb_skip_ctx", C.c_uint8),
+                ("dc_sign_ctx", C.c_uint8), ("reserved", C.c_uint8 * 4)]
+
+
+assert C.sizeof(TxSearchTu) == 40
+
+
+class TxSearchResult(C.Structure):
+    _fields_ = [("full_cost", C.c_uint64), ("distortion", C.c_uint64 * 2), ("coeff_bits", C.c_uint64), ("candidate", C.c_uint32),
+                ("eob", C.c_uint16), ("tx_type", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+assert C.sizeof(TxSearchResult) == 40
+
+
+def tx_search_type_mask(tx_size: int, is_inter: bool, reduced_tx_set: bool, fast_tx_search: bool) -> int:
+    """the reference's transform-type candidate mask of ProductFullLoopTxSearch (bit t = TxType t)"""
+    return int(lib().svthip_tx_search_type_mask(tx_size, int(bool(is_inter)), int(bool(reduced_tx_set)), int(bool(fast_tx_search))))
+
+
+def _coeff_rate_batch_dev(self, d_tables, d_qcoeff, d_eob, d_iscan, d_desc, n_tu, tx_size, d_bits, stream=None):
+    """Av1TuEstimateCoeffBits of n_tu TUs of one TxSize (COEFF_RATE_DESC_DTYPE descriptors, uint16 eobs) -> uint32 bits per TU"""
+    _check(lib().svthip_coeff_rate_batch_dev(self._h, d_tables, d_qcoeff, d_eob, d_iscan, d_desc, n_tu, tx_size, d_bits, stream))
+
+
+Context.coeff_rate_batch_dev = _coeff_rate_batch_dev
 
 
 CONVOLVE_COMPOUND_DESC_DTYPE = np.dtype([("src0_offset", "<u4"), ("src1_offset", "<u4"), ("dst_offset", "<u4"), ("subpel0", "u1"), ("subpel1", "u1"),

@@ -1,0 +1,132 @@
+"""Writes tests/golden/coeff_rate.npz from the reference's own coefficient-rate code (tests/golden/ref_coeff_rate_driver.c linked
+against the reference objects of the oracle build, oracle/_ref/obj_all).  Run in the build container only, where the reference
+exists: the fixture is data (rate tables, level blocks, the reference's bits and candidate masks) and is what the GPU box checks.
+
+    python tests/golden/make_golden_rate.py
+
+Contents
+  tables      int32 [4][8522]: svthip_coeff_rate_tables for base_qindex QINDICES (one per coefficient-CDF bucket)
+  levels      int16 pool of the blocks (min(W,32) x min(H,32) each, raster)
+  cases       one row per block (CASE_FIELDS), bits = Av1TuEstimateCoeffBits of the reference
+  masks       uint16 [19][2 is_inter][2 reduced][2 fast]: ProductFullLoopTxSearch's candidate masks
+The blocks' scans are those of tests/golden/quant_tables.npz (av1_scan_orders)."""
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+
+import rate_util  # noqa: E402
+import svtav1_hip  # noqa: E402
+from tq_util import RealTables  # noqa: E402
+
+QINDICES = (20, 60, 120, 200)  # av1_default_coef_probs buckets: <= 20, <= 60, <= 120, above
+CASE_FIELDS = ["level_offset", "table", "tx_size", "tx_type", "plane_type", "txb_skip_ctx", "dc_sign_ctx", "is_inter", "intra_mode",
+               "reduced_tx_set", "eob", "bits"]
+
+
+def eob_choices(n):
+    out = {0, 1, 2, n}
+    for s in rate_util.EOB_GROUP_START[1:]:
+        for e in (s - 1, s, s + 1):
+            if 0 <= e <= n:
+                out.add(e)
+    return sorted(out)
+
+
+def make_block(rng, n, iscan, eob, kind):
+    """levels with exactly `eob` scan positions in play and a non-zero level at scan position eob - 1"""
+    scan = np.argsort(iscan)
+    q = np.zeros(n, np.int64)
+    if eob == 0:
+        return q
+    pos = scan[:eob]
+    mags = {
+        "small": lambda k: rng.choice([0, 0, 1, 1, 2, 3], k),
+        "mid": lambda k: rng.choice([0, 1, 2, 3, 4, 7, 14, 15, 16, 30], k),
+        "big": lambda k: rng.choice([0, 1, 3, 15, 126, 127, 128, 129, 1000, 16384, 20000, 32767], k),
+        "dense": lambda k: rng.integers(1, 5, k),
+    }[kind](eob)
+    q[pos] = mags
+    if q[scan[eob - 1]] == 0:
+        q[scan[eob - 1]] = int(rng.choice([1, 2, 3, 17, 128]))
+    q *= np.where(rng.random(n) < 0.5, -1, 1)
+    return q
+
+
+def main():
+    rng = np.random.default_rng(2024)
+    tabs = RealTables()
+    with tempfile.TemporaryDirectory() as tmp:
+        L = rate_util.build_reference_driver(tmp)
+        tables = np.concatenate([rate_util.reference_tables(L, qi, svtav1_hip.COEFF_RATE_TABLES_DTYPE) for qi in QINDICES])
+        pool, rows = [], []
+        off = 0
+
+        def add(ti, ts, tt, q, eob, plane, skip, dcs, inter, mode, red):
+            nonlocal off
+            L.drv_init(QINDICES[ti])
+            lv = np.ascontiguousarray(q.astype(np.int32))
+            bits = int(L.drv_bits(lv.ctypes.data, eob, plane, ts, tt, skip, dcs, inter, mode, red))
+            pool.append(q.astype(np.int16))
+            rows.append((off, ti, ts, tt, plane, skip, dcs, inter, mode, red, eob, bits))
+            off += len(q)
+
+        # per size: every type the transforms support, eobs over the eob groups, all four level mixes, random contexts
+        plan = []
+        for ts in range(19):
+            w, h = svtav1_hip.TX_SIZES_WH[ts]
+            n = min(w, 32) * min(h, 32)
+            types = svtav1_hip.valid_tx_types(w, h)
+            eobs = eob_choices(n)
+            for tt in types:
+                reps = max(5, 80 // len(types))
+                for r in range(reps):
+                    eob = eobs[(r * 7 + tt) % len(eobs)] if r < reps - 1 else int(rng.integers(1, n + 1))
+                    plan.append((int(rng.integers(0, 4)), ts, tt, eob, ["small", "mid", "big", "dense"][(r + tt) % 4],
+                                 int(rng.integers(0, 2)) if r % 3 == 2 else 0, int(rng.integers(0, 13)), int(rng.integers(0, 3)),
+                                 r % 2, int(rng.integers(0, 13)), int(rng.integers(0, 2))))
+        # every eob choice of every size at least once (DCT_DCT, inter and intra)
+        for ts in range(19):
+            w, h = svtav1_hip.TX_SIZES_WH[ts]
+            n = min(w, 32) * min(h, 32)
+            for k, eob in enumerate(eob_choices(n)):
+                plan.append((k % 4, ts, 0, eob, "mid", 0, k % 13, k % 3, k % 2, (3 * k) % 13, 0))
+        # every intra mode on a size with a multi-type intra set, every context value
+        for mode in range(13):
+            for ts in (0, 1, 5, 13):
+                plan.append((mode % 4, ts, 3 if ts != 13 else 1, 5, "mid", 0, mode, mode % 3, 0, mode, mode % 2))
+        plan.sort(key=lambda p: p[0])
+        for (ti, ts, tt, eob, kind, plane, skip, dcs, inter, mode, red) in plan:
+            w, h = svtav1_hip.TX_SIZES_WH[ts]
+            n = min(w, 32) * min(h, 32)
+            o = tabs.scan_offset(ts, tt)
+            iscan = tabs.iscan_pool[o:o + n]
+            add(ti, ts, tt, make_block(rng, n, iscan, eob, kind), eob, plane, skip, dcs, inter, mode, red)
+        # DC-only blocks, positive and negative
+        for ts in (0, 2, 3):
+            n = min(svtav1_hip.TX_SIZES_WH[ts][0], 32) * min(svtav1_hip.TX_SIZES_WH[ts][1], 32)
+            for v in (5, -5, -1, 40000 // 3):
+                q = np.zeros(n, np.int64)
+                q[0] = v
+                add(1, ts, 0, q, 1, 0, 4, 1, 1, 0, 0)
+
+        masks = np.zeros((19, 2, 2, 2), np.uint16)
+        for ts in range(19):
+            for inter in (0, 1):
+                for red in (0, 1):
+                    for fast in (0, 1):
+                        masks[ts, inter, red, fast] = rate_util.reference_mask(L, ts, inter, red, fast)
+    cases = np.array(rows, dtype=[(f, "<i8") for f in CASE_FIELDS])
+    out = os.path.join(HERE, "coeff_rate.npz")
+    np.savez_compressed(out, tables=tables.view(np.int32).reshape(len(QINDICES), -1), qindices=np.array(QINDICES), levels=np.concatenate(pool),
+                        cases=cases, masks=masks)
+    print(f"wrote {out}: {len(cases)} blocks, {os.path.getsize(out)} bytes")
+
+
+if __name__ == "__main__":
+    main()
