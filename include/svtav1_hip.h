@@ -542,6 +542,81 @@ int32_t svthip_av1_highbd_convolve_batch_dev(svthip_ctx *ctx, const uint16_t *d_
                                              void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Whole-PU AV1 inter prediction: Y, Cb and Cr of a batch of prediction units of ONE luma size, each exactly what one call of
+ * av1_inter_prediction (Codec/EbInterPrediction.c:1005-2050; 16-bit twin av1_inter_prediction_hbd :2053-) writes.  Callers: mode
+ * decision's inter_pu_prediction_av1 (:4351) and EncDec (Codec/EbCodingLoop.c:3671, :3688).  Per PU the device does what the function does:
+ *   luma     clamp_mv_to_umv_border_sb(xd, mv, bwidth, bheight, 0, 0) (:80-102), then convolve[sx != 0][sy != 0][is_compound] of
+ *            bwidth x bheight (:1255-1290 list 0, :1346-1385 list 1; BI_PRED averages list 1 into list 0's 16-bit result);
+ *   chroma   if has_uv: sub8x8_inter (:1044-1127) = the block is 4 wide or 4 high and every mi of the neighbourhood (row_start..0,
+ *            col_start..0) is inter (ref_frame[0] > INTRA_FRAME).  Otherwise Cb / Cr of bwidth_uv x bheight_uv = max(4, bwidth / 2) x
+ *            max(4, bheight / 2) at ((pu_origin >> 3) << 3) / 2 with clamp (bwidth_uv, bheight_uv, 1, 1) (:1292-1344).  If sub-8x8: the
+ *            piece loop (:1129-1245): b4 = (bwidth / 2) x (bheight / 2) pieces (2x2, 2x4, 4x2, 2x8 or 8x2) covering the 4x4 / 4x8 / 8x4
+ *            chroma block, each with the vector and the reference list of the mi it maps to, clamped with (bwidth_uv, bheight_uv, 1, 1)
+ *            and the current block's edges, filters from bwidth_uv / bheight_uv (not from the piece size), single-reference rounding.
+ * Filters by av1_get_interp_filter_params_with_block_size (:985-995) of the convolved block's width / height (4-tap at <= 4).
+ *
+ * Planes: pointers at picture sample (0, 0), inside the padding; strides in samples.  Offsets of the destination are >= 0.  The library
+ * reads exactly what the reference reads: after the clamp a block may lie up to (bw + 4) samples outside the picture on any side (bw, bh =
+ * the convolved block's size: bwidth x bheight for Y, bwidth_uv x bheight_uv for Cb / Cr), plus 3 filter taps left / above and 4 right /
+ * below, and the source rows stay readable 16 bytes past the last sample needed (the over-read rule of the convolution entries).  So the
+ * reference planes need a border of at least bw + 7 (left / top) and bw + 8 samples + 16 bytes (right / bottom) around the area the
+ * mb_to_*_edge values describe: 135 / 136 luma samples for 128 x 128 blocks, 71 / 72 chroma samples.
+ *
+ * svthip_inter_pu_desc (64 bytes), field by field:
+ *   pu_origin_x/y     luma sample position of the PU in the reference pictures (av1_inter_prediction's pu_origin_x / _y)
+ *   dst_origin_x/y    luma sample position of the PU in the prediction planes (dst_origin_x / _y)
+ *   mb_to_*_edge      cu_ptr->av1xd->mb_to_left_edge / _right_edge / _top_edge / _bottom_edge, 1/8 luma sample, as the caller has them
+ *   interp_filters    packed as the reference packs it: filter_x = bits 16.., filter_y = bits 0..15 (av1_extract_interp_filter,
+ *                     convolve.h:31-34); 0 EIGHTTAP_REGULAR, 1 EIGHTTAP_SMOOTH, 2 MULTITAP_SHARP, 3 BILINEAR (the low two bits are used)
+ *   pred_direction    mv_unit->predDirection: 0 UNI_PRED_LIST_0, 1 UNI_PRED_LIST_1, 2 BI_PRED (EbDefinitions.h:2027-2029)
+ *   has_uv            blk_geom->has_uv
+ *   own_list          the list the block's own piece of a sub-8x8 chroma block takes: rf[0] == LAST_FRAME ? 0 : 1 with
+ *                     av1_set_ref_frame(rf, ref_frame_type) (the value the piece loop reads back from the mi grid, :1067-1091)
+ *   mv[list]          mv_unit->mv[list] as (row, col) = (y, x), 1/8 luma sample
+ *   nb_is_inter[k], nb_list[k], nb_mv[k]   the sub-8x8 neighbourhood, k = 0 (row -1, col -1), 1 (row -1, col 0), 2 (row 0, col -1):
+ *                     is_inter_block() of that mi, ref_frame[0] == LAST_FRAME ? 0 : 1, and mv[0] as (row, col).  Only the entries inside
+ *                     (row_start..0, col_start..0) are read: k = 0..2 for 4x4, k = 2 for 4 wide, k = 1 for 4 high blocks.
+ *
+ * width x height : the luma size, one of the 22 AV1 block sizes (4..128).  Directions may be mixed within a call.  Refused, with
+ * svthip_last_error text: a size that is not an AV1 size, a null pointer when n_pu > 0 (n_pu == 0 returns OK), a descriptor array that is
+ * not 16-byte aligned, a bit_depth other than 10 (16-bit entry).  A BI_PRED PU whose chroma goes sub-8x8 (the reference asserts
+ * !is_compound there, :1148 and :2195) is only detectable on the device: nothing is written for such a PU, the context counts it, and
+ * svthip_inter_pred_refused reports the count.  The same holds for a PU whose clamped block would start beyond the border above (edges
+ * that do not describe the PU's position).
+ * Nothing in the call synchronises with the host: the expansion of descriptors into per-plane jobs runs on the device, in a grow-only
+ * context-owned scratch slot ordered on `stream` like the other context scratch. */
+typedef struct svthip_inter_planes {
+    void *y, *cb, *cr;         /* uint8_t* (8-bit entry) or uint16_t* (high-bit-depth entry), at picture sample (0, 0) */
+    uint32_t y_stride, c_stride; /* in samples; Cb and Cr share c_stride */
+} svthip_inter_planes;
+
+typedef struct svthip_inter_pu_desc {
+    uint16_t pu_origin_x, pu_origin_y;
+    uint16_t dst_origin_x, dst_origin_y;
+    int32_t mb_to_left_edge, mb_to_right_edge, mb_to_top_edge, mb_to_bottom_edge;
+    uint32_t interp_filters;
+    uint8_t pred_direction;
+    uint8_t has_uv;
+    uint8_t own_list;
+    uint8_t reserved0;
+    int16_t mv[2][2];          /* [list][row, col] */
+    uint8_t nb_is_inter[3];
+    uint8_t nb_list[3];
+    int16_t nb_mv[3][2];       /* [k][row, col] */
+    uint8_t reserved1[6];
+} svthip_inter_pu_desc;
+
+int32_t svthip_av1_inter_pred_batch_dev(svthip_ctx *ctx, const svthip_inter_planes *ref0, const svthip_inter_planes *ref1,
+                                        const svthip_inter_planes *dst, const svthip_inter_pu_desc *d_desc, uint32_t n_pu,
+                                        uint32_t bwidth, uint32_t bheight, void *stream);
+int32_t svthip_av1_highbd_inter_pred_batch_dev(svthip_ctx *ctx, const svthip_inter_planes *ref0, const svthip_inter_planes *ref1,
+                                               const svthip_inter_planes *dst, const svthip_inter_pu_desc *d_desc, uint32_t n_pu,
+                                               uint32_t bwidth, uint32_t bheight, uint32_t bit_depth, void *stream);
+/* Synchronises with the context's last inter-prediction call and returns (then clears) how many PUs the device refused since the last
+ * query (see above) in *out_count: SVTHIP_OK when none, SVTHIP_ERR_BAD_PARAMETER with text otherwise. */
+int32_t svthip_inter_pred_refused(svthip_ctx *ctx, uint32_t *out_count);
+
+/* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one
  * transform type at a time from ProductFullLoopTxSearch (Codec/EbFullLoop.c:1138-1352: for every tx_type candidate of a TU:
  * Av1EstimateTransform -> Av1QuantizeInvQuantize -> distortion -> cost), encode_pass_tx_search (:1354-1550) and Av1EncodeLoop

@@ -43,11 +43,17 @@ __device__ __forceinline__ int filter_index(int f, int size)
 // av1_inter_prediction's BI_PRED path: av1_jnt_convolve_* with round_1 = 7, round_offset = 6144, round_bits = 4 (EbInterPrediction.c:290-528).
 // HBD: 16-bit planes holding bd-bit samples (offsets and strides in SAMPLES): av1_highbd_convolve_*_sr_c / av1_highbd_jnt_convolve_*_c
 // (:530-880), the same arithmetic with bd in the offsets.
-template <int RB, bool COMPOUND, bool HBD>
+// COUNTED (whole-PU inter prediction, ip_inter_pred.hip): the job count is read from the 16 bytes in front of the descriptor array, where
+// the device wrote it; n_blocks is only the largest possible count the grid was sized for, and workgroups past the count leave at once.
+template <int RB, bool COMPOUND, bool HBD, bool COUNTED = false>
 __global__ void __launch_bounds__(256) av1_convolve_sr_kernel(const uint8_t* __restrict__ src0, uint32_t src0_stride, const uint8_t* __restrict__ src1,
                                                               uint32_t src1_stride, uint8_t* __restrict__ dst, uint32_t dst_stride,
                                                               const uint4* __restrict__ desc, uint32_t n_blocks, int w, int h, int blocks_per_wg, int bd)
 {
+    if constexpr (COUNTED) {
+        n_blocks = __builtin_amdgcn_readfirstlane(desc[-1].x);
+        if (blockIdx.x * (uint32_t)blocks_per_wg >= n_blocks) return;
+    }
     constexpr int SB = HBD ? 2 : 1;  // bytes per sample
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     lds_u8* im = (lds_u8*)smem;  // int16 [blocks_per_wg][h + 7][w]
@@ -237,7 +243,7 @@ bool convolve_size_valid(int w, int h)
 }
 
 namespace {
-template <bool COMPOUND, bool HBD>
+template <bool COMPOUND, bool HBD, bool COUNTED = false>
 hipError_t launch_valu(const void* src0, uint32_t src0_stride, const void* src1, uint32_t src1_stride, void* dst, uint32_t dst_stride, const void* desc,
                        uint32_t n_blocks, int w, int h, int bd, hipStream_t s)
 {
@@ -246,10 +252,10 @@ hipError_t launch_valu(const void* src0, uint32_t src0_stride, const void* src1,
     const uint32_t grid = (n_blocks + per - 1) / per;
     const uint8_t *a = static_cast<const uint8_t*>(src0), *b = static_cast<const uint8_t*>(src1);
     if (h >= 8)
-        hipLaunchKernelGGL((av1_convolve_sr_kernel<8, COMPOUND, HBD>), dim3(grid), dim3(256), lds, s, a, src0_stride, b, src1_stride,
+        hipLaunchKernelGGL((av1_convolve_sr_kernel<8, COMPOUND, HBD, COUNTED>), dim3(grid), dim3(256), lds, s, a, src0_stride, b, src1_stride,
                            static_cast<uint8_t*>(dst), dst_stride, reinterpret_cast<const uint4*>(desc), n_blocks, w, h, per, bd);
     else
-        hipLaunchKernelGGL((av1_convolve_sr_kernel<4, COMPOUND, HBD>), dim3(grid), dim3(256), lds, s, a, src0_stride, b, src1_stride,
+        hipLaunchKernelGGL((av1_convolve_sr_kernel<4, COMPOUND, HBD, COUNTED>), dim3(grid), dim3(256), lds, s, a, src0_stride, b, src1_stride,
                            static_cast<uint8_t*>(dst), dst_stride, reinterpret_cast<const uint4*>(desc), n_blocks, w, h, per, bd);
     return hipGetLastError();
 }
@@ -282,6 +288,28 @@ hipError_t launch_av1_convolve_compound(const uint8_t* src0, uint32_t src0_strid
                                         uint32_t dst_stride, const svthip_convolve_compound_desc* desc, uint32_t n_blocks, int w, int h, hipStream_t s)
 {
     return launch_valu<true, false>(src0, src0_stride, src1, src1_stride, dst, dst_stride, desc, n_blocks, w, h, 8, s);
+}
+
+hipError_t launch_convolve_counted(const void* src0, uint32_t src0_stride, const void* src1, uint32_t src1_stride, void* dst, uint32_t dst_stride,
+                                   const void* desc, uint32_t max_blocks, int w, int h, bool compound, int bd, hipStream_t s)
+{
+    if (max_blocks == 0) return hipSuccess;
+    if (bd > 8)
+        return compound ? launch_valu<true, true, true>(src0, src0_stride, src1, src1_stride, dst, dst_stride, desc, max_blocks, w, h, bd, s)
+                        : launch_valu<false, true, true>(src0, src0_stride, src0, src0_stride, dst, dst_stride, desc, max_blocks, w, h, bd, s);
+    return compound ? launch_valu<true, false, true>(src0, src0_stride, src1, src1_stride, dst, dst_stride, desc, max_blocks, w, h, 8, s)
+                    : launch_valu<false, false, true>(src0, src0_stride, src0, src0_stride, dst, dst_stride, desc, max_blocks, w, h, 8, s);
+}
+
+// the counted compound forms (dynamic LDS above 64 KB for 128-wide blocks, like convolve_compound_kernel_ptr)
+const void* convolve_compound_count_kernel_ptr(int which)
+{
+    switch (which) {
+    case 0: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<8, true, false, true>);
+    case 1: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<4, true, false, true>);
+    case 2: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<8, true, true, true>);
+    default: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<4, true, true, true>);
+    }
 }
 
 hipError_t launch_av1_highbd_convolve(const uint16_t* src0, uint32_t src0_stride, const uint16_t* src1, uint32_t src1_stride, uint16_t* dst,

@@ -171,11 +171,13 @@ __device__ __forceinline__ void conv_list_tiles(const uint8_t* __restrict__ src,
 
 // TY = output tiles stacked vertically per wave: they share the IM tile between them (TY + 1 IM tiles instead of 2 TY) and the tap fragments.
 // COMPOUND: descriptors are svthip_convolve_compound_desc, both lists are run and averaged like av1_inter_prediction's BI_PRED path.
-template <int TY, bool COMPOUND>
+// COUNTED: the job count sits in the 16 bytes in front of desc (whole-PU inter prediction, ip_inter_pred.hip); n_blocks sized the grid.
+template <int TY, bool COMPOUND, bool COUNTED = false>
 __global__ void __launch_bounds__(256, 2) av1_convolve_mfma_kernel(const uint8_t* __restrict__ src0, uint32_t src0_stride, const uint8_t* __restrict__ src1,
                                                                 uint32_t src1_stride, uint8_t* __restrict__ dst, uint32_t dst_stride,
                                                                 const uint4* __restrict__ desc, uint32_t n_blocks, int w, int h)
 {
+    if constexpr (COUNTED) n_blocks = __builtin_amdgcn_readfirstlane(desc[-1].x);
     const int lane = threadIdx.x & 63, n = lane & 31, hh = lane >> 5;
     const int tiles_x = w >> 5, tiles = tiles_x * (h / (32 * TY));
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -242,6 +244,28 @@ hipError_t launch_av1_convolve_compound_mfma(const uint8_t* src0, uint32_t src0_
         hipLaunchKernelGGL((av1_convolve_mfma_kernel<2, true>), grid, block, 0, s, src0, src0_stride, src1, src1_stride, dst, dst_stride, dd, n_blocks, w, h);
     else
         hipLaunchKernelGGL((av1_convolve_mfma_kernel<1, true>), grid, block, 0, s, src0, src0_stride, src1, src1_stride, dst, dst_stride, dd, n_blocks, w, h);
+    return hipGetLastError();
+}
+
+hipError_t launch_convolve_mfma_counted(const uint8_t* src0, uint32_t src0_stride, const uint8_t* src1, uint32_t src1_stride, uint8_t* dst,
+                                        uint32_t dst_stride, const void* desc, uint32_t max_blocks, int w, int h, bool compound, hipStream_t s)
+{
+    if (max_blocks == 0) return hipSuccess;
+    const int ty = (h & 63) == 0 ? 2 : 1;
+    const uint64_t waves = (uint64_t)max_blocks * (uint32_t)((w >> 5) * (h / (32 * ty)));
+    const dim3 grid((uint32_t)((waves + 3) / 4)), block(256);
+    const uint4* dd = reinterpret_cast<const uint4*>(desc);
+    if (compound) {
+        if (ty == 2)
+            hipLaunchKernelGGL((av1_convolve_mfma_kernel<2, true, true>), grid, block, 0, s, src0, src0_stride, src1, src1_stride, dst, dst_stride, dd, max_blocks, w, h);
+        else
+            hipLaunchKernelGGL((av1_convolve_mfma_kernel<1, true, true>), grid, block, 0, s, src0, src0_stride, src1, src1_stride, dst, dst_stride, dd, max_blocks, w, h);
+    } else {
+        if (ty == 2)
+            hipLaunchKernelGGL((av1_convolve_mfma_kernel<2, false, true>), grid, block, 0, s, src0, src0_stride, src0, src0_stride, dst, dst_stride, dd, max_blocks, w, h);
+        else
+            hipLaunchKernelGGL((av1_convolve_mfma_kernel<1, false, true>), grid, block, 0, s, src0, src0_stride, src0, src0_stride, dst, dst_stride, dd, max_blocks, w, h);
+    }
     return hipGetLastError();
 }
 

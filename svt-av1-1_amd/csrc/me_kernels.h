@@ -148,6 +148,19 @@ hipError_t launch_sad_loop_qsad(const uint8_t* src, uint32_t src_stride, const u
                                 int16_t* best_xy, hipStream_t s);
 size_t sad_loop_slice_bytes(int w, int h, int sw, int sh, int k);
 bool convolve_size_valid(int w, int h);
+// the convolution kernels with the block count in device memory, in the 16 bytes in front of desc (whole-PU inter prediction,
+// ip_inter_pred.hip): grids sized for max_blocks; bd 8 = 8-bit planes, 10 = 16-bit planes
+hipError_t launch_convolve_counted(const void* src0, uint32_t src0_stride, const void* src1, uint32_t src1_stride, void* dst, uint32_t dst_stride,
+                                   const void* desc, uint32_t max_blocks, int w, int h, bool compound, int bd, hipStream_t s);
+hipError_t launch_convolve_mfma_counted(const uint8_t* src0, uint32_t src0_stride, const uint8_t* src1, uint32_t src1_stride, uint8_t* dst,
+                                        uint32_t dst_stride, const void* desc, uint32_t max_blocks, int w, int h, bool compound, hipStream_t s);
+const void* convolve_compound_count_kernel_ptr(int which);  // 0..3
+// ip_inter_pred.hip: the descriptor expansion and the 2-wide / 2-high chroma pieces
+hipError_t launch_inter_pred(const svthip_inter_planes& ref0, const svthip_inter_planes& ref1, const svthip_inter_planes& dst,
+                             const svthip_inter_pu_desc* desc, uint32_t n_pu, int bw, int bh, int bd, bool use_mfma, void* scratch,
+                             uint32_t* refused, hipStream_t s);
+size_t inter_pred_scratch_bytes(uint32_t n_pu);
+bool inter_pred_has_pieces(int bw, int bh);
 hipError_t launch_av1_convolve_sr(const uint8_t* src, uint32_t src_stride, uint8_t* dst, uint32_t dst_stride, const svthip_convolve_desc* desc,
                                   uint32_t n_blocks, int w, int h, hipStream_t s);
 

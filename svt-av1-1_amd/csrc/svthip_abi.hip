@@ -36,9 +36,11 @@ struct svthip_ctx {
     int device;
     hipStream_t stream;
     // grow-only device scratch: slots 0-4 host-pointer full-pel form, 5 per-list ME arrays, 6 bi-pred SADs, 7 stored predictions,
-    // 8-15 host-pointer picture / TU forms
-    void* scratch[16];
-    size_t scratch_bytes[16];
+    // 8-15 host-pointer picture / TU forms, 16 whole-PU inter prediction job lists, 17 its refused-PU counter
+    void* scratch[18];
+    size_t scratch_bytes[18];
+    // stream of the last whole-PU inter prediction call (svthip_inter_pred_refused synchronises with it)
+    hipStream_t inter_stream;
     // the stream the context-owned scratch was last used on, and an event to order a different stream behind it
     hipStream_t scratch_stream;
     hipEvent_t scratch_event;
@@ -62,7 +64,9 @@ void set_kernel_attrs(int device)
                              reinterpret_cast<const void*>(svthip::bipred_pack_kernel), reinterpret_cast<const void*>(svthip::bipred_nsq_pack_kernel),
                              reinterpret_cast<const void*>(svthip::subpel_planes_kernel), svthip::convolve_compound_kernel_ptr(0),
                              svthip::convolve_compound_kernel_ptr(1),                     svthip::convolve_compound_kernel_ptr(2),
-                             svthip::convolve_compound_kernel_ptr(3)};
+                             svthip::convolve_compound_kernel_ptr(3),                     svthip::convolve_compound_count_kernel_ptr(0),
+                             svthip::convolve_compound_count_kernel_ptr(1),               svthip::convolve_compound_count_kernel_ptr(2),
+                             svthip::convolve_compound_count_kernel_ptr(3)};
     hipError_t st = hipSuccess;
     for (const void* k : kernels) {
         hipFuncAttributes fa;
@@ -228,7 +232,7 @@ void svthip_destroy(svthip_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < 16; i++)
+    for (int i = 0; i < 18; i++)
         if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     (void)hipEventDestroy(ctx->scratch_event);
     (void)hipStreamDestroy(ctx->stream);
@@ -914,6 +918,68 @@ int32_t svthip_av1_highbd_convolve_batch_dev(svthip_ctx* ctx, const uint16_t* d_
     HIP_TRY(svthip::launch_av1_highbd_convolve(d_src0, src0_stride, compound ? d_src1 : d_src0, compound ? src1_stride : src0_stride, d_dst, dst_stride,
                                                d_desc, compound != 0, n_blocks, (int)width, (int)height, (int)bit_depth, s));
     return SVTHIP_OK;
+}
+
+namespace {
+int32_t inter_pred_entry(svthip_ctx* ctx, const svthip_inter_planes* ref0, const svthip_inter_planes* ref1, const svthip_inter_planes* dst,
+                         const svthip_inter_pu_desc* d_desc, uint32_t n_pu, uint32_t bwidth, uint32_t bheight, int bd, void* stream)
+{
+    if (!svthip::convolve_size_valid((int)bwidth, (int)bheight))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "not an AV1 block size%s (width %d)", "", (int)bwidth);
+    if (n_pu == 0) return SVTHIP_OK;
+    if (!ref0 || !ref1 || !dst || !d_desc) return fail(SVTHIP_ERR_BAD_PARAMETER, "null pointer argument%s", "");
+    for (const svthip_inter_planes* p : {ref0, ref1, dst})
+        if (!p->y || !p->cb || !p->cr) return fail(SVTHIP_ERR_BAD_PARAMETER, "null plane pointer%s", "");
+    if (reinterpret_cast<uintptr_t>(d_desc) & 15u) return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor array must be 16-byte aligned%s", "");
+    if (bd > 8)
+        for (const svthip_inter_planes* p : {ref0, ref1, dst})
+            if ((reinterpret_cast<uintptr_t>(p->y) | reinterpret_cast<uintptr_t>(p->cb) | reinterpret_cast<uintptr_t>(p->cr)) & 1u)
+                return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned%s", "");
+    if (n_pu > 0x0fffffffu) return fail(SVTHIP_ERR_BAD_PARAMETER, "too many PUs in one call%s (%d)", "", (int)n_pu);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    int32_t rc;
+    if ((rc = scratch_on_stream(ctx, s))) return rc;
+    const bool first = ctx->scratch[17] == nullptr;
+    if ((rc = ensure_scratch(ctx, 16, svthip::inter_pred_scratch_bytes(n_pu)))) return rc;
+    if ((rc = ensure_scratch(ctx, 17, 256))) return rc;
+    if (first) HIP_TRY(hipMemsetAsync(ctx->scratch[17], 0, 256, s));
+    HIP_TRY(svthip::launch_inter_pred(*ref0, *ref1, *dst, d_desc, n_pu, (int)bwidth, (int)bheight, bd, !ctx->opt[SVTHIP_OPT_CONVOLVE_VALU],
+                                      ctx->scratch[16], static_cast<uint32_t*>(ctx->scratch[17]), s));
+    ctx->inter_stream = s;
+    return SVTHIP_OK;
+}
+}  // namespace
+
+int32_t svthip_av1_inter_pred_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* ref0, const svthip_inter_planes* ref1, const svthip_inter_planes* dst,
+                                        const svthip_inter_pu_desc* d_desc, uint32_t n_pu, uint32_t bwidth, uint32_t bheight, void* stream)
+{
+    ENTER(ctx);
+    return inter_pred_entry(ctx, ref0, ref1, dst, d_desc, n_pu, bwidth, bheight, 8, stream);
+}
+
+int32_t svthip_av1_highbd_inter_pred_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* ref0, const svthip_inter_planes* ref1,
+                                               const svthip_inter_planes* dst, const svthip_inter_pu_desc* d_desc, uint32_t n_pu, uint32_t bwidth,
+                                               uint32_t bheight, uint32_t bit_depth, void* stream)
+{
+    ENTER(ctx);
+    if (bit_depth != 10) return fail(SVTHIP_ERR_BAD_PARAMETER, "bit_depth must be 10%s (got %d)", "", (int)bit_depth);
+    return inter_pred_entry(ctx, ref0, ref1, dst, d_desc, n_pu, bwidth, bheight, (int)bit_depth, stream);
+}
+
+int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
+{
+    ENTER(ctx);
+    if (!out_count) return fail(SVTHIP_ERR_BAD_PARAMETER, "null pointer argument%s", "");
+    *out_count = 0;
+    if (!ctx->scratch[17]) return SVTHIP_OK;
+    hipStream_t s = ctx->inter_stream ? ctx->inter_stream : ctx->stream;
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, ctx->scratch[17], sizeof(n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!n) return SVTHIP_OK;
+    HIP_TRY(hipMemsetAsync(ctx->scratch[17], 0, sizeof(n), s));
+    *out_count = n;
+    return fail(SVTHIP_ERR_BAD_PARAMETER, "%s%d PU(s) refused: BI_PRED with sub-8x8 chroma, or a block outside the border its edges describe", "", (int)n);
 }
 
 int32_t svthip_open_loop_intra_search_batch_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* cur, uint32_t n_jobs,

@@ -136,6 +136,13 @@ def lib() -> C.CDLL:
     L.svthip_av1_highbd_convolve_batch_dev.restype = C.c_int32
     L.svthip_av1_highbd_convolve_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                                        C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.svthip_av1_inter_pred_batch_dev.restype = C.c_int32
+    L.svthip_av1_inter_pred_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p]
+    L.svthip_av1_highbd_inter_pred_batch_dev.restype = C.c_int32
+    L.svthip_av1_highbd_inter_pred_batch_dev.argtypes = L.svthip_av1_inter_pred_batch_dev.argtypes[:-1] + [C.c_uint32, C.c_void_p]
+    L.svthip_inter_pred_refused.restype = C.c_int32
+    L.svthip_inter_pred_refused.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.svthip_sad_loop_batch_dev.restype = C.c_int32
     L.svthip_sad_loop_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -750,3 +757,47 @@ def shard_sb_rows(width: int, height: int, world: int, rank: int) -> np.ndarray:
     from .sharded import shard_sb_indices
 
     return shard_sb_indices(width, height, world, rank, "row")
+
+
+# ---- whole-PU inter prediction (svthip_av1_inter_pred_batch_dev / svthip_av1_highbd_inter_pred_batch_dev) ----
+INTER_PU_DESC_DTYPE = np.dtype([("pu_origin_x", "<u2"), ("pu_origin_y", "<u2"), ("dst_origin_x", "<u2"), ("dst_origin_y", "<u2"),
+                                ("mb_to_left_edge", "<i4"), ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"),
+                                ("interp_filters", "<u4"), ("pred_direction", "u1"), ("has_uv", "u1"), ("own_list", "u1"), ("reserved0", "u1"),
+                                ("mv", "<i2", (2, 2)), ("nb_is_inter", "u1", (3,)), ("nb_list", "u1", (3,)), ("nb_mv", "<i2", (3, 2)),
+                                ("reserved1", "u1", (6,))])
+assert INTER_PU_DESC_DTYPE.itemsize == 64
+UNI_PRED_LIST_0, UNI_PRED_LIST_1, BI_PRED = 0, 1, 2
+
+
+class InterPlanes(C.Structure):
+    """svthip_inter_planes: device pointers at picture sample (0, 0) of Y / Cb / Cr, strides in samples (Cb and Cr share c_stride)."""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_uint32), ("c_stride", C.c_uint32)]
+
+
+def _planes_arg(p):
+    return None if p is None else C.byref(p)
+
+
+def _av1_inter_pred_batch_dev(self, ref0, ref1, dst, d_desc, n_pu, bwidth, bheight, stream=None):
+    """8-bit whole-PU inter prediction (Y, Cb, Cr) of n_pu PUs of one luma size; ref0 / ref1 / dst are InterPlanes, d_desc a device
+    array of INTER_PU_DESC_DTYPE."""
+    _check(lib().svthip_av1_inter_pred_batch_dev(self._h, _planes_arg(ref0), _planes_arg(ref1), _planes_arg(dst), d_desc, n_pu, bwidth, bheight,
+                                                 stream))
+
+
+def _av1_highbd_inter_pred_batch_dev(self, ref0, ref1, dst, d_desc, n_pu, bwidth, bheight, bit_depth=10, stream=None):
+    """The same for 16-bit planes holding 10-bit samples."""
+    _check(lib().svthip_av1_highbd_inter_pred_batch_dev(self._h, _planes_arg(ref0), _planes_arg(ref1), _planes_arg(dst), d_desc, n_pu, bwidth,
+                                                        bheight, bit_depth, stream))
+
+
+def _inter_pred_refused(self):
+    """Synchronises with the last inter-prediction call; raises SvtHipError naming the count if the device refused PUs since the last query."""
+    n = C.c_uint32(0)
+    _check(lib().svthip_inter_pred_refused(self._h, C.byref(n)))
+    return n.value
+
+
+Context.av1_inter_pred_batch_dev = _av1_inter_pred_batch_dev
+Context.av1_highbd_inter_pred_batch_dev = _av1_highbd_inter_pred_batch_dev
+Context.inter_pred_refused = _inter_pred_refused
