@@ -46,7 +46,7 @@ struct svthip_ctx {
     hipEvent_t scratch_event;
     // kernel-selection overrides (svthip_set_option): per context, never read from the environment
     int32_t opt[SVTHIP_OPT_COUNT];
-    // geometry the SB-origin table in slot 9 was last built for (host-pointer picture forms)
+    // geometry the SB-origin table in slot 9 was last built for (host-pointer picture forms); 0 x 0 after every (re)allocation
     uint32_t sb_table_w, sb_table_h;
 };
 
@@ -124,6 +124,13 @@ int32_t ensure_scratch(svthip_ctx* c, int slot, size_t bytes)
     }
     c->scratch_bytes[slot] = want;
     c->scratch_stream = os;
+    if (slot == 9) {
+        // a new SB-origin table holds no geometry, whoever grew it (svthip_reserve or ensure_sb_table), and starts as all (0,0)
+        // origins: were it ever read before ensure_sb_table filled it, every SB would see the first one's samples -- wrong results,
+        // but no read outside the picture pool
+        c->sb_table_w = c->sb_table_h = 0;
+        HIP_TRY(hipMemsetAsync(c->scratch[9], 0, want, os));
+    }
     return SVTHIP_OK;
 }
 
@@ -151,15 +158,15 @@ HostPoolLayout host_pool_layout(uint32_t w, uint32_t h)
     return L;
 }
 
-// raster SB origins of a w x h picture in slot 9, rebuilt only when the geometry changes (the upload is from pageable memory, so it is
-// followed by a stream synchronisation; steady-state calls skip both)
+// raster SB origins of a w x h picture in slot 9, rebuilt only when the geometry changes or the slot was reallocated (ensure_scratch
+// clears the cached geometry then); the upload is from pageable memory, so it is followed by a stream synchronisation; steady-state
+// calls skip both
 int32_t ensure_sb_table(svthip_ctx* c, uint32_t w, uint32_t h, hipStream_t s)
 {
     const uint32_t nx = (w + 63) / 64, ny = (h + 63) / 64, n_sb = nx * ny;
-    const bool grew = c->scratch_bytes[9] < sizeof(svthip_sb_origin) * n_sb;
     int32_t rc;
     if ((rc = ensure_scratch(c, 9, sizeof(svthip_sb_origin) * n_sb))) return rc;
-    if (!grew && c->sb_table_w == w && c->sb_table_h == h) return SVTHIP_OK;
+    if (c->sb_table_w == w && c->sb_table_h == h) return SVTHIP_OK;
     svthip_sb_origin* sbs = new (std::nothrow) svthip_sb_origin[n_sb];
     if (!sbs) return fail(SVTHIP_ERR_INSUFFICIENT_RESOURCES, "out of host memory%s", "");
     for (uint32_t y = 0; y < ny; y++)
@@ -823,7 +830,7 @@ int32_t svthip_sad_loop_batch_dev(svthip_ctx* ctx, const uint8_t* d_src, uint32_
     ENTER(ctx);
     if (width < 4 || width > 64 || (width & 3u) || height < 1 || height > 64)
         return fail(SVTHIP_ERR_BAD_PARAMETER, "block must be 4..64 wide (multiple of 4) and 1..64 high%s (width %d)", "", (int)width);
-    if (!search_area_width || !search_area_height || search_area_width * search_area_height > 4096u)
+    if (!search_area_width || !search_area_height || (uint64_t)search_area_width * search_area_height > 4096u)
         return fail(SVTHIP_ERR_BAD_PARAMETER, "search area must hold 1..4096 positions%s (width %d)", "", (int)search_area_width);
     if (!ref_stride_raw || (ref_stride != ref_stride_raw && ref_stride != 2 * ref_stride_raw))
         return fail(SVTHIP_ERR_BAD_PARAMETER, "ref_stride must be ref_stride_raw or twice it%s (got %d)", "", (int)ref_stride);

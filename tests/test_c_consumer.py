@@ -33,6 +33,11 @@ def test_ctypes_mirrors_match_the_header_sizes():
     import ctypes as C
     assert C.sizeof(svtav1_hip.MeParams) == 52 and C.sizeof(svtav1_hip.PaPictureDesc) == 40 and C.sizeof(svtav1_hip.FullpelDesc) == 24
     assert svtav1_hip.ME_CU_RESULT_DTYPE.itemsize == 24 and svtav1_hip.TU_DESC_DTYPE.itemsize == 32
+    # svthip_host_picture / svthip_me_cu_result_ref (consumer.c asserts the header's side of both)
+    assert C.sizeof(svtav1_hip.HostPicture) == 24 and svtav1_hip.HostPicture.width.offset == 16
+    R = svtav1_hip.ME_CU_RESULT_REF_DTYPE
+    assert R.itemsize == 40 and R.fields["distortionDirection"][1] == 8 and R.fields["totalMeCandidateIndex"][1] == 32
+    assert R["distortionDirection"].base.itemsize == 8
 
 
 def _write(path, sections):

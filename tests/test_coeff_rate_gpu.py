@@ -24,6 +24,7 @@ def _run(ctx, d_tables, tables_index, q_pool, eobs, desc, ts, d_iscan):
     import torch
     d_q, d_eob, d_desc = _dev(q_pool.astype(np.int32)), _dev(eobs.astype(np.uint16)), _dev(desc)
     d_bits = torch.zeros(len(desc), dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
     ctx.coeff_rate_batch_dev(d_tables.data_ptr() + tables_index * svtav1_hip.COEFF_RATE_TABLES_DTYPE.itemsize, d_q.data_ptr(), d_eob.data_ptr(),
                              d_iscan.data_ptr(), d_desc.data_ptr(), len(desc), ts, d_bits.data_ptr())
     ctx.synchronize()

@@ -90,6 +90,7 @@ def test_convolve_64x64_all_phases_1080p(hip_ctx, oracle):
     d_src = torch.from_numpy(np.concatenate([src.reshape(-1), np.zeros(64, np.uint8)])).to("cuda:0")
     d_dst = torch.zeros(nbx * nby * 64 * D, dtype=torch.uint8, device="cuda:0")
     d_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.av1_convolve_sr_batch_dev(d_src.data_ptr(), S, d_dst.data_ptr(), D, d_desc.data_ptr(), desc.size, 64, 64)
     hip_ctx.synchronize()
     got = d_dst.cpu().numpy().reshape(nbx * nby * 64, D)
@@ -143,6 +144,7 @@ def _run_compound(hip_ctx, s0, S0, s1, S1, dst, D, desc, w, h):
     d1 = torch.from_numpy(np.concatenate([s1.reshape(-1), np.zeros(64, np.uint8)])).to("cuda:0")
     d_dst = torch.from_numpy(dst.reshape(-1).copy()).to("cuda:0")
     d_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.av1_convolve_compound_batch_dev(d0.data_ptr(), S0, d1.data_ptr(), S1, d_dst.data_ptr(), D, d_desc.data_ptr(), len(desc), w, h)
     hip_ctx.synchronize()
     return d_dst.cpu().numpy().reshape(dst.shape)
@@ -226,6 +228,7 @@ def test_convolve_1080p_all_blocks_two_kernels_and_oracle_sample(hip_ctx, oracle
 
     def run(compound):
         out = torch.zeros(n * 4096, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
         if compound:
             hip_ctx.av1_convolve_compound_batch_dev(d_s0.data_ptr(), S, d_s1.data_ptr(), S, out.data_ptr(), 64, d_c.data_ptr(), n, w, h)
         else:
@@ -310,6 +313,7 @@ def test_highbd_convolve_every_block_size(hip_ctx, oracle, size):
                 (ud["filter_y"].astype(np.uint32) << 24)
             fu(s0.ctypes.data, S0, want.ctypes.data, D, dd.ctypes.data, n, w, h, 10)
             d_desc = dev(ud)
+        torch.cuda.synchronize()
         hip_ctx.av1_highbd_convolve_batch_dev(d0.data_ptr(), S0, d1.data_ptr(), S1, d_dst.data_ptr(), D, d_desc.data_ptr(), compound, n, w, h, 10)
         hip_ctx.synchronize()
         got = d_dst.cpu().numpy().view(np.uint16).reshape(256, D)

@@ -145,6 +145,7 @@ def test_fullpel_209pu_matches_oracle(hip_ctx, oracle, case):
     d_src, d_ref, d_desc = torch.from_numpy(cur.full).to(dev), torch.from_numpy(ref.full).to(dev), torch.from_numpy(desc).to(dev)
     n = desc.shape[0]
     d_sad = torch.full((n, 209), -1, dtype=torch.int32, device=dev); d_mv = torch.full((n, 209), -1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
     hip_ctx.fullpel_search209_dev(d_src.data_ptr(), cur.stride, d_ref.data_ptr(), ref.stride, d_desc.data_ptr(), n, int(desc[:, 4].max()),
                                   int(desc[:, 5].max()), d_sad.data_ptr(), d_mv.data_ptr())
     hip_ctx.synchronize()

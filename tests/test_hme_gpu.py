@@ -151,11 +151,13 @@ def test_batched_launch_equals_per_picture_launches(hip_ctx):
     params = svtav1_hip.default_me_params(w, h, 3, 0)
     d_one = torch.zeros((n_pic * n_sb, 6), dtype=torch.int32, device="cuda:0")
     d_cen1 = torch.zeros((n_pic * n_sb, 2), dtype=torch.int16, device="cuda:0")
+    torch.cuda.synchronize()
     for i in range(n_pic):
         hip_ctx.hme_search_center_dev(d_pool.data_ptr(), pd[i + 1], pd[i], params, 0, d_sb.data_ptr(), n_sb, None,
                                       d_one.data_ptr() + i * n_sb * 24, d_cen1.data_ptr() + i * n_sb * 4)
     d_bat = torch.zeros((n_pic * n_sb, 6), dtype=torch.int32, device="cuda:0")
     d_cen2 = torch.zeros((n_pic * n_sb, 2), dtype=torch.int16, device="cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.hme_search_center_batch_dev(d_pool.data_ptr(), [pd[i + 1] for i in range(n_pic)], [pd[i] for i in range(n_pic)], params, 0,
                                         d_sb.data_ptr(), n_sb, None, d_bat.data_ptr(), d_cen2.data_ptr())
     hip_ctx.synchronize()

@@ -50,6 +50,7 @@ def test_search_centres_and_fullpel_all_2040_sbs(hip_ctx, oracle, pics4k):
     d_desc = torch.from_numpy(desc).to("cuda:0")
     d_sad = torch.ones((desc.shape[0], 85), dtype=torch.int32, device="cuda:0")
     d_mv = torch.zeros((desc.shape[0], 85), dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.fullpel_search_dev(d_pic.data_ptr(), pics4k[0].stride, d_pic.data_ptr(), pics4k[0].stride, d_desc.data_ptr(), desc.shape[0], 64, 64,
                                d_sad.data_ptr(), d_mv.data_ptr())
     hip_ctx.synchronize()

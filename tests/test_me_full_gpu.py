@@ -137,10 +137,12 @@ def test_batched_pictures_equal_single_picture_calls(hip_ctx):
     P = svtav1_hip.default_me_params(w, h, 3, 1)
     curs = [pd[i + 1] for i in range(n_pic)]; r0 = [pd[i] for i in range(n_pic)]; r1 = [pd[i + 2] for i in range(n_pic)]
     d_one = torch.zeros((n_pic * n, 85, 24), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
     for i in range(n_pic):
         hip_ctx.motion_estimate_picture_dev(d_pool.data_ptr(), curs[i], r0[i], r1[i], P, d_sb.data_ptr(), n,
                                             d_one.data_ptr() + i * n * 85 * 24, True, 0)
     d_bat = torch.full((n_pic * n, 85, 24), 0x77, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
     hip_ctx.motion_estimate_batch_dev(d_pool.data_ptr(), curs, r0, r1, P, d_sb.data_ptr(), n, d_bat.data_ptr(), True, 0)
     hip_ctx.synchronize()
     a = d_one.cpu().numpy().view(svtav1_hip.ME_CU_RESULT_DTYPE); b = d_bat.cpu().numpy().view(svtav1_hip.ME_CU_RESULT_DTYPE)

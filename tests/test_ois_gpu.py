@@ -54,6 +54,7 @@ def run_gpu(hip_ctx, torch, pics, params, me, me_stride=85):
         d_me = torch.from_numpy(rows.view(np.uint8).reshape(-1)).to("cuda:0")
     d_cand = torch.full((n * n_sb * 85 * 18,), -1, dtype=torch.int32, device="cuda:0")
     d_total = torch.full((n * n_sb * 85,), 0xEE, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.open_loop_intra_search_batch_dev(d_pool.data_ptr(), descs, params, d_sb.data_ptr(), n_sb,
                                              None if d_me is None else d_me.data_ptr(), me_stride, d_cand.data_ptr(), d_total.data_ptr())
     hip_ctx.synchronize()

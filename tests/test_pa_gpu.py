@@ -32,6 +32,7 @@ def test_pa_derive_planes_matches_oracle(hip_ctx, oracle, size):
         f, q, s = oracle.pa_derive_planes(x)
         assert np.array_equal(f, p.full) and np.array_equal(q, p.quarter) and np.array_equal(s, p.sixteenth)
     d_pool = torch.from_numpy(raw).to("cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.pa_derive_planes_dev(d_pool.data_ptr(), descs)
     hip_ctx.synchronize()
     got = d_pool.cpu().numpy()
@@ -54,6 +55,7 @@ def test_pa_derive_planes_respects_level_flags(hip_ctx):
     pics = [synth.PaPicture(synth.synth_luma(128, 64, 1))]
     raw, want, descs = _pool_with_interiors_only(pics)
     d_pool = torch.from_numpy(raw).to("cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.pa_derive_planes_dev(d_pool.data_ptr(), descs, want_quarter=False, want_sixteenth=True)
     hip_ctx.synchronize()
     got = d_pool.cpu().numpy()
@@ -78,6 +80,7 @@ def test_pad_plane_matches_oracle(hip_ctx, oracle, case):
     want = a.copy()
     oracle.generate_padding(want, w, h, pw, ph)
     t = torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.pad_plane_dev(t.data_ptr(), stride, w, h, pw, ph, sb)
     hip_ctx.synchronize()
     got = t.cpu().numpy().view(dt).reshape(a.shape)

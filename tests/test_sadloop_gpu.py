@@ -96,5 +96,9 @@ def test_sad_loop_rejects_bad_arguments(hip_ctx):
     for bad in ((6, 8, 8, 8), (16, 16, 65, 64), (16, 0, 8, 8), (64, 64, 4096, 1)):   # width not x4; > 4096 positions; zero height; LDS window
         with pytest.raises(svtav1_hip.SvtHipError):
             hip_ctx.sad_loop_batch_dev(*a, *bad, buf.data_ptr(), buf.data_ptr())
+    # 16 x 2^28 = 2^32 positions: 0 when multiplied in 32 bits, and the packed-SAD plan's int window size wraps to under 1 KB, so only
+    # the area check stands between this call and a kernel that walks 2^28 search rows
+    with pytest.raises(svtav1_hip.SvtHipError, match="1..4096 positions"):
+        hip_ctx.sad_loop_batch_dev(*a, 16, 16, 16, 1 << 28, buf.data_ptr(), buf.data_ptr())
     with pytest.raises(svtav1_hip.SvtHipError):
         hip_ctx.sad_loop_batch_dev(buf.data_ptr(), 256, buf.data_ptr(), 768, 256, buf.data_ptr(), 1, 16, 16, 8, 8, buf.data_ptr(), buf.data_ptr())

@@ -115,6 +115,7 @@ def test_recon_exchange_entry_world1_all_slabs_then_padding(hip_ctx, case):
     try:
         ex = sharded.ReconExchange(w, h, pad, comm=comm, sample_bytes=es)
         assert ex.world == 1 and ex.my_rows == (0, h)
+        torch.cuda.synchronize()   # the planes were written on torch's stream; the exchange runs on the context's
         ex.exchange(planes)
         hip_ctx.synchronize()
     finally:
@@ -130,6 +131,7 @@ def test_me_gather_entry_world1(hip_ctx):
     try:
         local = torch.randint(0, 255, (3, 28, 85, 24), dtype=torch.uint8, device="cuda:0")
         full = torch.zeros_like(local)
+        torch.cuda.synchronize()   # local / full were written on torch's stream; the gather runs on the context's
         comm.me_gather_results_dev(local.data_ptr(), full.data_ptr(), 3, 28, 85 * 24)
         hip_ctx.synchronize()
         assert torch.equal(local, full)

@@ -224,6 +224,7 @@ def test_subpel_search_sad_methods_1080p(hip_ctx, oracle, method):
     dev = torch.device("cuda:0")
     d_src, d_ref, d_desc = torch.from_numpy(cur.full).to(dev), torch.from_numpy(ref.full).to(dev), torch.from_numpy(desc).to(dev)
     d_sad = torch.zeros((desc.shape[0], 209), dtype=torch.int32, device=dev); d_mv = torch.zeros_like(d_sad)
+    torch.cuda.synchronize()
     hip_ctx.fullpel_search209_dev(d_src.data_ptr(), cur.stride, d_ref.data_ptr(), ref.stride, d_desc.data_ptr(), desc.shape[0], 64, 64,
                                   d_sad.data_ptr(), d_mv.data_ptr())
     hip_ctx.synchronize()

@@ -106,6 +106,7 @@ def test_fwd_inv_round_trip_is_near_identity(hip_ctx):
         d_fd, d_id = _dev(fd), _dev(idd)
         d_coeff = torch.empty(n_tu * n * n, dtype=torch.int32, device="cuda:0")
         d_rec = torch.zeros(pic_w * pic_h, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
         hip_ctx.fwd_txfm2d_batch_dev(d_res.data_ptr(), d_fd.data_ptr(), n_tu, n, n, 8, d_coeff.data_ptr())
         hip_ctx.inv_txfm2d_add_batch_dev(d_coeff.data_ptr(), d_id.data_ptr(), n_tu, n, n, 8, False, d_rec.data_ptr())
         hip_ctx.synchronize()
@@ -163,6 +164,7 @@ def test_encode_tu_optional_outputs_may_be_null(hip_ctx, oracle):
     d_src, d_pred, d_desc, d_qp, d_iscan = _dev(b["src"]), _dev(b["pred"]), _dev(b["desc"]), _dev(b["qparams"]), _dev(b["iscan"])
     d_q = torch.zeros(40 * 256, dtype=torch.int32, device="cuda:0")
     d_eob = torch.zeros(40, dtype=torch.int16, device="cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.encode_tu_batch_dev(d_src.data_ptr(), d_pred.data_ptr(), d_pred.data_ptr(), d_desc.data_ptr(), 40, 16, 16, d_qp.data_ptr(),
                                 d_iscan.data_ptr(), None, d_q.data_ptr(), None, d_eob.data_ptr(), None, None)
     hip_ctx.synchronize()
@@ -219,6 +221,7 @@ def test_encode_tu_many_groups_per_wave(hip_ctx, oracle, case, max_wg):
     d_src, d_pred, d_desc, d_qp, d_iscan = _dev(b["src"]), _dev(b["pred"]), _dev(b["desc"]), _dev(b["qparams"]), _dev(b["iscan"])
     d_q = torch.full((n_tu * n,), 5, dtype=torch.int32, device="cuda:0")
     d_eob = torch.full((n_tu,), -1, dtype=torch.int16, device="cuda:0")
+    torch.cuda.synchronize()
     hip_ctx.set_option(svtav1_hip.OPT_TQ_MAX_WORKGROUPS, max_wg)
     try:
         hip_ctx.encode_tu_batch_dev(d_src.data_ptr(), d_pred.data_ptr(), d_pred.data_ptr(), d_desc.data_ptr(), n_tu, w, h, d_qp.data_ptr(),
