@@ -66,6 +66,11 @@ __device__ unsigned long long g_hme_loop_phase[2 * 4];
 #define HME_LOOP_ADD(slot, t1, t0) do { } while (0)
 #endif
 
+// Per-wave LDS slice: a band of the search window (the source blocks of full SBs sit in HmeShared).  7 KB holds the whole level-0 window
+// of the 1080p 200 % area (96 x 48 positions: 62 rows x 28 dwords = 6 944 B) in one band; 4 slices + HmeShared stay under
+// 32 KB per workgroup, five workgroups per CU.
+constexpr int kHmeLdsPerWave = 7 * 1024;
+
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
 {
 #pragma unroll
@@ -76,6 +81,25 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
     return v;
 }
 
+// The 64 x 32-row reference block of a centre check (stride already doubled) in two halves, so that a caller can issue the loads
+// before the barrier that publishes the staged source block: lane = (row mod 4, dword column), eight rows per lane.
+__device__ __forceinline__ void load_ref_block64(const uint8_t* ref, uint32_t ref_stride, int lane, uint32_t (&tv)[8])
+{
+    const uint32_t c = (uint32_t)lane & 15u, r0 = (uint32_t)lane >> 4;
+    const uint8_t* rp = ref + (size_t)r0 * ref_stride + 4u * c;
+#pragma unroll
+    for (int k = 0; k < 8; k++) tv[k] = ldu32_nb(rp + (size_t)(4 * k) * ref_stride);
+}
+
+__device__ __forceinline__ uint32_t sad_ref_block64(const uint32_t (&tv)[8], const uint32_t* src_lds, int lane)
+{
+    const uint32_t c = (uint32_t)lane & 15u, r0 = (uint32_t)lane >> 4;
+    uint32_t acc4 = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) acc4 = __builtin_amdgcn_sad_u8(src_lds[(r0 + 4 * k) * 16 + c], tv[k], acc4);
+    return wave_sum_u32(acc4);
+}
+
 // SAD of a W x H block (strides already doubled by the caller), computed by one wave.  W need not be a
 // multiple of 4: the tail dword is masked on both operands.
 __device__ uint32_t wave_block_sad(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride,
@@ -83,14 +107,9 @@ __device__ uint32_t wave_block_sad(const uint8_t* src, uint32_t src_stride, cons
 {
     if (src_lds && W == 64 && H == 32) {
         // the 64 x 32-row source block is already in LDS ([32][16] dwords): only the reference rows come from memory
-        const uint32_t c = (uint32_t)lane & 15u, r0 = (uint32_t)lane >> 4;
-        const uint8_t* rp = ref + (size_t)r0 * ref_stride + 4u * c;
-        uint32_t tv[8], acc4 = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) tv[k] = ldu32_nb(rp + (size_t)(4 * k) * ref_stride);
-#pragma unroll
-        for (int k = 0; k < 8; k++) acc4 = __builtin_amdgcn_sad_u8(src_lds[(r0 + 4 * k) * 16 + c], tv[k], acc4);
-        return wave_sum_u32(acc4);
+        uint32_t tv[8];
+        load_ref_block64(ref, ref_stride, lane, tv);
+        return sad_ref_block64(tv, src_lds, lane);
     }
     if (W == 64 && (H & 3u) == 0) {
         // full-width block: lane = (row mod 4, dword column), four rows per pass, all loads of a lane in flight together;
@@ -185,7 +204,7 @@ __device__ __forceinline__ uint64_t pack64(uint32_t lo, uint32_t hi) { return ((
 
 // Copies `wrows` plane rows of `pitch` dwords each, starting at the (unaligned) address `base`, into LDS (row r at win + r * pitch).
 // Reads up to pitch * 4 + 19 bytes per row (the pool's tail slack covers the last row of the last plane).  pitch <= 256 (a band of at
-// least 15 rows has to fit the 8 KB slice, so pitch <= 136 here).
+// least 15 rows has to fit the 7 KB slice, so pitch <= 119 here).
 __device__ __forceinline__ void stage_window_rows(const uint8_t* base, uint32_t ref_stride_raw, int wrows, int pitch, uint32_t* win,
                                                   int lane)
 {
@@ -368,6 +387,115 @@ __device__ void wave_sad_loop_lds(const uint8_t* src, uint32_t src_stride, const
     HME_LOOP_ADD(3, 1ull, 0ull);
 }
 
+// Fixed-shape SadLoopKernel of HME levels 1 and 2 for full SBs whose clipped search area is the reference's whole area: level 1 a 32 x
+// 16-row block over 16 x 16 positions, level 2 a 64 x 32-row block over 8 x 8 positions (every resolution class uses these).  The
+// general loop above spends about 330 vector instructions per level and wave beside its 128 v_qsad per lane on run-time bands, row-part
+// counts, per-row loops, u16 flushes and odd register pairs; here everything is a compile-time constant:
+//   * a lane owns one whole search row (SW positions = SW / 4 accumulators of four u16 SADs) and ROWS = H / RP of the block rows; the RP
+//     lanes of a search row are consecutive, their sums are combined with DPP adds;
+//   * ROWS * W * 255 < 2^16: no flush, one unpack at the end;
+//   * the window pitch is a multiple of four dwords, so the even window pairs (k, k + 1) arrive as aligned ds_read_b128; the odd pairs
+//     are read a second time as aligned pairs (ds_read2_b32) instead of being assembled with register moves;
+//   * the best position is a 32-bit (sad << 12 | raster index) minimum, the reference's strict-'<' raster rule (the KEY32 rule above).
+// `srcbuf` is the block staged by the workgroup ([H][W / 4] dwords); `lds` (16-byte aligned) holds the window.
+template <int W, int H, int SW, int SH>
+__device__ void wave_sad_loop_fixed(const uint8_t* ref, uint32_t ref_stride_raw, int lane, uint8_t* lds, const uint32_t* srcbuf,
+                                    uint32_t* best_sad, int* bx, int* by)
+{
+    constexpr int WD = W / 4;               // source dwords per block row
+    constexpr int NQ = SW / 4;              // accumulators (position quads) per lane
+    constexpr int RP = 64 / SH;             // lanes per search row
+    constexpr int ROWS = H / RP;            // block rows per lane
+    constexpr int ND = WD + NQ;             // window dwords a block row touches: SW + W - 1 bytes
+    constexpr int PITCH = (ND + 3) & ~3;    // window dwords per row: rows stay 16-byte aligned
+    constexpr int WROWS = SH + 2 * H - 2;
+    static_assert(RP * SH == 64 && ROWS * RP == H && (RP & (RP - 1)) == 0 && RP >= 2 && RP <= 8, "one wave pass, RP a power of two");
+    static_assert(ROWS * W * 255 < 65536 && H * W * 255 < (1 << 20) && SW * SH <= 4096 && (SW & (SW - 1)) == 0, "u16 sums, 32-bit keys");
+    static_assert(WROWS * PITCH * 4 <= kHmeLdsPerWave, "the window fits the slice");
+    typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+
+    uint32_t* win = reinterpret_cast<uint32_t*>(lds);
+    HME_PRIO(3);
+    stage_window_rows(ref, ref_stride_raw, WROWS, PITCH, win, lane);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    HME_PRIO(0);
+
+    const int iy = lane / RP, part = lane & (RP - 1);
+    const uint32_t* w0 = win + (iy + 2 * part) * PITCH;  // window row of block row `part`; block row part + RP * i is 2 * RP * i rows below
+    uint64_t acc[NQ];
+#pragma unroll
+    for (int g = 0; g < NQ; g++) acc[g] = 0;
+#pragma unroll
+    for (int i = 0; i < ROWS; i++) {
+        const int r = part + RP * i;
+        const uint32_t* wr = w0 + 2 * RP * i * PITCH;
+        // the same address as an opaque LDS pointer: the odd pairs are separate loads, not values the compiler rebuilds from the even ones
+        lds_u32* wo = (lds_u32*)wr;
+        asm("" : "+v"(wo));
+        // the even pairs: whole 16-byte loads (kept whole by the empty asm; the compiler would otherwise split them into the 8-byte
+        // pairs they feed and issue them as half-rate ds_read2_b64)
+        uint32_t d[PITCH];
+#pragma unroll
+        for (int k = 0; k < PITCH / 4; k++) {
+            if (4 * k + 2 >= ND) {  // only the first two dwords of the last quad are used (level 2)
+                u32x2_t v = *reinterpret_cast<const u32x2_t*>(wr + 4 * k);
+                asm("" : "+v"(v));
+                d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = d[4 * k + 3] = 0;
+            } else {
+                u32x4_t v = *reinterpret_cast<const u32x4_t*>(wr + 4 * k);
+                asm("" : "+v"(v));
+                d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
+            }
+        }
+        uint64_t odd[ND / 2];
+#pragma unroll
+        for (int k = 1; k + 1 < ND; k += 2) odd[k / 2] = pack64(wo[k], wo[k + 1]);
+        uint32_t sv[WD];
+#pragma unroll
+        for (int k = 0; k < WD / 4; k++) {
+            const uint4 v = *reinterpret_cast<const uint4*>(srcbuf + r * WD + 4 * k);
+            sv[4 * k] = v.x; sv[4 * k + 1] = v.y; sv[4 * k + 2] = v.z; sv[4 * k + 3] = v.w;
+        }
+#pragma unroll
+        for (int c = 0; c < WD; c++)
+#pragma unroll
+            for (int g = 0; g < NQ; g++) {
+                const int k = c + g;
+                acc[g] = __builtin_amdgcn_qsad_pk_u16_u8((k & 1) ? odd[k / 2] : pack64(d[k], d[k + 1]), sv[c], acc[g]);
+            }
+    }
+    __builtin_amdgcn_wave_barrier();  // the next level's staging overwrites the window
+
+    // per lane: min over its positions of (sad << 12 | x), after the RP lanes of the search row have added their block rows
+    uint32_t key = 0xffffffffu;
+#pragma unroll
+    for (int g = 0; g < NQ; g++) {
+        uint32_t v[4] = {(uint32_t)acc[g] & 0xffffu, (uint32_t)acc[g] >> 16, (uint32_t)(acc[g] >> 32) & 0xffffu, (uint32_t)(acc[g] >> 48)};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            v[j] += dpp_fetch<0xB1>(v[j]);                   // quad_perm [1,0,3,2]
+            v[j] += dpp_fetch<0x4E>(v[j]);                   // quad_perm [2,3,0,1]
+            if (RP == 8) v[j] += dpp_fetch<0x141>(v[j]);     // row_half_mirror: the other quad of the eight
+        }
+        key = min3u((v[0] << 12) | (uint32_t)(4 * g), (v[1] << 12) | (uint32_t)(4 * g + 1), key);
+        key = min3u((v[2] << 12) | (uint32_t)(4 * g + 2), (v[3] << 12) | (uint32_t)(4 * g + 3), key);
+    }
+    key |= (uint32_t)(iy * SW);  // the row's raster base has no bits in common with x < SW: the lane's order is kept
+    key = min(key, dpp_fetch<0xB1>(key));
+    key = min(key, dpp_fetch<0x4E>(key));
+    key = min(key, dpp_fetch<0x124>(key));  // row_ror:4
+    key = min(key, dpp_fetch<0x128>(key));  // row_ror:8: every lane of a row of 16 holds the row's minimum
+    const uint32_t best = min(min((uint32_t)__builtin_amdgcn_readlane((int)key, 0), (uint32_t)__builtin_amdgcn_readlane((int)key, 16)),
+                              min((uint32_t)__builtin_amdgcn_readlane((int)key, 32), (uint32_t)__builtin_amdgcn_readlane((int)key, 48)));
+    const uint32_t pos = best & 0xfffu;
+    *best_sad = best >> 12;
+    *by = (int)(pos / (uint32_t)SW);
+    *bx = (int)(pos % (uint32_t)SW);
+}
+
 // SadLoopKernel of HME level 0 (16 x 8-row block on the 1/16 plane; ~70 % of the search-centre work), one wave.
 // An item is 16 consecutive search positions of one search row = 16 bytes = one ds_read_b128 step along the window, so lane
 // i of a row reads window dwords 4i .. 4i+7 with two conflict-free b128 loads per block row and issues 16 v_qsad_pk_u16_u8
@@ -457,7 +585,8 @@ __device__ void wave_sad_loop_l0(const uint8_t* src, uint32_t src_stride, const 
             track(acc, iy, io, valid);
         }
         // the remainder: 2 / 4 / 8 lanes share an item and split its block rows, so that a handful of left-over items does not cost a
-        // whole 128-v_qsad pass with most lanes idle (the reference's 100 % level-0 area is 72 items: 64 + 8; the 200 % area 288 = 4 x 64 + 32).
+        // whole 128-v_qsad pass with most lanes idle (the reference's 100 % level-0 area is 72 items: 64 + 8; the 1080p 200 % area, one band
+        // since the slice is 7 KB, 288 = 4 x 64 + 32; larger areas -- 4K, the 350 / 525 % multipliers -- run in bands, each with its remainder).
         // The 16-bit partial sums of an item's lanes are added as packed pairs (a 16 x 8 SAD is < 2^16).
         while (it0 < nitems) {
             const int rem = nitems - it0;
@@ -521,13 +650,12 @@ __device__ __forceinline__ int round_hme_width(int w)
     return (w < 8) ? 8 : ((w & 7) ? (w + (w - ((w >> 3) << 3))) : w);  // :4528 (adds the remainder, sic)
 }
 
-constexpr int kHmeLdsPerWave = 6 * 1024;  // per-wave LDS slice: source block + a band of the search window
-
 struct HmeShared {
     unsigned long long cost[8];   // centre-check candidate costs
     int rx[3][4], ry[3][4];       // per level, per region ([w][h] flattened as w*2+h) centres
     unsigned long long rs[3][4];  // per level SADs (doubled)
     int cx, cy;
+    unsigned long long hcost;     // CheckZeroZeroCenter cost of (cx, cy) when level 2 already computed it, else ~0
     svthip_fullpel_desc desc;     // the final descriptor, for a consumer in the same workgroup
     // source blocks of a full 64x64 SB, staged once for the four region waves: full-res rows 0,2,..,62 (64 x 32), quarter-res
     // rows 0,2,..,30 (32 x 16), sixteenth-res rows 0,2,..,14 (16 x 8)
@@ -559,9 +687,19 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
     HME_STAMP(0);
     HME_PRIO(3);  // until the first search loop: staging and the centre checks are a few loads and SADs on the serial path of every level
 
+    const bool center_path = (P.temporal_layer_index > 0) || (list_index == 0);  // :6300
+    const int tw = P.hme_level0_total_search_area_width, th = P.hme_level0_total_search_area_height;
     // full 64x64 SBs: stage the three source blocks once for the whole workgroup (the four region waves search with the same
     // block at every level, and the centre checks compare the same 64 x 32-row block)
     const bool full_sb = sb_w == 64 && sb_h == 64;
+    // centre-check candidates 0 / B / C / D (hme_mv_center_check below, one per wave): their reference rows depend only on the SB
+    // origin, so they are loaded here and stay in flight across the source-staging barrier instead of starting after it
+    uint32_t cand_tv[8];
+    if (full_sb && center_path) {
+        int x = wave == 1 ? tw : 0, y = wave == 2 ? -th : (wave == 3 ? th : 0);
+        clamp_center(x, y, ox, oy, ref.width, ref.height);
+        load_ref_block64(ref_full + (size_t)(oy + y) * ref.full_stride + ox + x, ref.full_stride * 2, lane, cand_tv);
+    }
     if (full_sb) {
 #pragma unroll
         for (int k = 0; k < 2; k++) {
@@ -581,24 +719,28 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
     const uint32_t* src2_lds = full_sb ? sh.src2 : nullptr;
     HME_STAMP(1);
 
-    const bool center_path = (P.temporal_layer_index > 0) || (list_index == 0);  // :6300
     const uint32_t mv64 = (list_index == 1 && l0_best_mv64) ? l0_best_mv64[(size_t)sbi * l0_mv_stride] : 0u;
     const int dx = s16(0 - (s16((int)(mv64 & 0xffffu)) >> 2));
     const int dy = s16(0 - (s16((int)(mv64 >> 16)) >> 2));
-    const int tw = P.hme_level0_total_search_area_width, th = P.hme_level0_total_search_area_height;
 
     if (tid == 0 && hme_state && list_index == 0) hme_state[25 * (size_t)sbi + 24] = 0;
     int xc = 0, yc = 0;
+    unsigned long long hme_cost = ~0ull;  // see HmeShared::hcost
     if (center_path) {
         // ---- hme_mv_center_check (:5882-6145): candidates 0 / B / C / D (+ direct for list 1); A uses the stale
         //      zero-MV index, so its cost equals the zero cost and it can never be selected before it.
-        int cxs[5] = {0, tw, 0, 0, dx}, cys[5] = {0, 0, -th, th, dy};
         const int ncand = (list_index == 1) ? 5 : 4;
+        const int cxs[5] = {0, tw, 0, 0, dx}, cys[5] = {0, 0, -th, th, dy};
         for (int c = wave; c < ncand; c += 4) {
-            int x = cxs[c], y = cys[c];
-            clamp_center(x, y, ox, oy, ref.width, ref.height);
-            const uint32_t sad = wave_block_sad(src, cur.full_stride * 2, ref_full + (size_t)(oy + y) * ref.full_stride + ox + x,
-                                                ref.full_stride * 2, sb_h >> 1, sb_w, lane, src2_lds);
+            uint32_t sad;
+            if (full_sb && c == wave) {
+                sad = sad_ref_block64(cand_tv, src2_lds, lane);  // loaded before the staging barrier
+            } else {
+                int x = cxs[c], y = cys[c];
+                clamp_center(x, y, ox, oy, ref.width, ref.height);
+                sad = wave_block_sad(src, cur.full_stride * 2, ref_full + (size_t)(oy + y) * ref.full_stride + ox + x, ref.full_stride * 2,
+                                     sb_h >> 1, sb_w, lane, src2_lds);
+            }
             if (lane == 0) sh.cost[c] = (unsigned long long)(sad << 1) << 8;
         }
         __syncthreads();
@@ -661,7 +803,9 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
                     const uint8_t* s = pool + cur.quarter_offset + (size_t)(32 + o_y) * cur.quarter_stride + 32 + o_x;
                     const uint8_t* r = pool + ref.quarter_offset + (size_t)(32 + o_y + yo) * ref.quarter_stride + 32 + o_x + xo;
                     int bx, by;
-                    if (sb_w == 64 && sw * shh <= 4096)
+                    if (sb_w == 64 && sw == 16 && shh == 16)
+                        wave_sad_loop_fixed<32, 16, 16, 16>(r, ref.quarter_stride, lane, wlds, sh.src1, &sad1, &bx, &by);
+                    else if (sb_w == 64 && sw * shh <= 4096)
                         wave_sad_loop_lds<32, true>(s, cur.quarter_stride * 2, r, ref.quarter_stride, 16, sw, shh, lane, wlds,
                                                     kHmeLdsPerWave, &sad1, &bx, &by, sh.src1);
                     else if (sb_w == 64)
@@ -681,7 +825,9 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
                     clip_window(xo, yo, sw, shh, ox, oy, 63, 63, ref.width, ref.height);
                     const uint8_t* r = ref_full + (size_t)(oy + yo) * ref.full_stride + ox + xo;
                     int bx, by;
-                    if (sb_w == 64 && sw * shh <= 4096)
+                    if (sb_w == 64 && sw == 8 && shh == 8)
+                        wave_sad_loop_fixed<64, 32, 8, 8>(r, ref.full_stride, lane, wlds, sh.src2, &sad2, &bx, &by);
+                    else if (sb_w == 64 && sw * shh <= 4096)
                         wave_sad_loop_lds<64, true>(src, cur.full_stride * 2, r, ref.full_stride, 32, sw, shh, lane, wlds,
                                                     kHmeLdsPerWave, &sad2, &bx, &by, sh.src2);
                     else if (sb_w == 64)
@@ -708,9 +854,10 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
                 if (P.enable_hme_level1_flag && !P.enable_hme_level2_flag) lvl = 1;
                 if (P.enable_hme_level2_flag) lvl = 2;
                 int xh = 0, yh = 0;
+                unsigned long long bs = ~0ull;
                 if (lvl >= 0) {
                     xh = sh.rx[lvl][0]; yh = sh.ry[lvl][0];
-                    unsigned long long bs = sh.rs[lvl][0];
+                    bs = sh.rs[lvl][0];
                     int w = 1, h = 0;
                     while (h < nh) {
                         while (w < nw) {
@@ -722,26 +869,39 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
                         h++;
                     }
                 }
+                // The level-2 SAD of the chosen centre is the SAD CheckZeroZeroCenter compares: the same 64 x 32-row block at the same
+                // position, and clip_window(.., 63, 63, ref size) keeps every level-2 position inside clamp_center's range, so its clamp
+                // leaves the centre where it is.  rs[2] = 2 * SAD; the check's cost is (SAD << 1) << 8.
+                unsigned long long hcost = lvl == 2 ? bs << 8 : ~0ull;
                 if (P.enable_hme_level2_flag) {
                     const int total = nh * nw;
                     if (P.ref_poc_equal && list_index == 1 && total > 1) {
-                        // bubble sort by SAD with the reference's [q / nw][q % nw] indexing, then take [0][1] (:6606-6631)
+                        // bubble sort by SAD with the reference's [q / nw][q % nw] indexing, then take [0][1] (:6606-6631).  That indexing
+                        // can reach slots of regions that do not exist; `from` follows where each entry came from, so that only a
+                        // searched region's SAD is handed on as the centre's cost
+                        uint32_t from = 0xE4u;  // 2-bit origin slot of each entry: [3, 2, 1, 0]
                         for (int q = 0; q < total - 1; q++)
                             for (int n = q + 1; n < total; n++) {
                                 const int a = (q / nw) * 2 + (q % nw), b = (n / nw) * 2 + (n % nw);
                                 if (sh.rs[2][a] > sh.rs[2][b]) {
                                     const int tx = sh.rx[2][a], ty = sh.ry[2][a];
+                                    const uint32_t fa = (from >> (2 * a)) & 3u, fb = (from >> (2 * b)) & 3u;
                                     const unsigned long long ts = sh.rs[2][a];
                                     sh.rx[2][a] = sh.rx[2][b]; sh.ry[2][a] = sh.ry[2][b]; sh.rs[2][a] = sh.rs[2][b];
                                     sh.rx[2][b] = tx; sh.ry[2][b] = ty; sh.rs[2][b] = ts;
+                                    from ^= ((fa ^ fb) << (2 * a)) | ((fa ^ fb) << (2 * b));
                                 }
                             }
                         xh = sh.rx[2][1];
                         yh = sh.ry[2][1];
+                        const uint32_t f1 = (from >> 2) & 3u;
+                        const bool live = (int)(f1 >> 1) < nw && (int)(f1 & 1u) < nh;
+                        hcost = live ? sh.rs[2][1] << 8 : ~0ull;
                     }
                 }
                 sh.cx = xh;
                 sh.cy = yh;
+                sh.hcost = hcost;
                 if (hme_state) {
                     int16_t* so = hme_state + 25 * (size_t)sbi;
                     for (int k = 0; k < 4; k++) {
@@ -758,6 +918,7 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
             __syncthreads();
             xc = sh.cx;
             yc = sh.cy;
+            hme_cost = sh.hcost;
         }
     }
 
@@ -765,15 +926,24 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
     HME_PRIO(3);
     if ((xc != 0 || yc != 0) && P.is_used_as_reference_flag) {
         clamp_center(xc, yc, ox, oy, ref.width, ref.height);
-        __syncthreads();
-        if (wave < 2) {
-            const int x = wave ? xc : 0, y = wave ? yc : 0;
-            const uint32_t sad = wave_block_sad(src, cur.full_stride * 2, ref_full + (size_t)(oy + y) * ref.full_stride + ox + x,
-                                                ref.full_stride * 2, sb_h >> 1, sb_w, lane, src2_lds);
-            if (lane == 0) sh.cost[6 + wave] = (unsigned long long)(sad << 1) << 8;
+        unsigned long long z, hcost;
+        if (hme_cost != ~0ull && ox < ref.width && oy < ref.height) {
+            // both SADs are known: the zero vector is centre-check candidate 0 (the same block; clamp_center leaves (0, 0) in place
+            // inside the reference picture), the centre's is its level-2 SAD
+            z = sh.cost[0];
+            hcost = hme_cost;
+        } else {
+            __syncthreads();
+            if (wave < 2) {
+                const int x = wave ? xc : 0, y = wave ? yc : 0;
+                const uint32_t sad = wave_block_sad(src, cur.full_stride * 2, ref_full + (size_t)(oy + y) * ref.full_stride + ox + x,
+                                                    ref.full_stride * 2, sb_h >> 1, sb_w, lane, src2_lds);
+                if (lane == 0) sh.cost[6 + wave] = (unsigned long long)(sad << 1) << 8;
+            }
+            __syncthreads();
+            z = sh.cost[6];
+            hcost = sh.cost[7];
         }
-        __syncthreads();
-        const unsigned long long z = sh.cost[6], hcost = sh.cost[7];
         const unsigned long long m = z < hcost ? z : hcost;
         if (m == z) { xc = 0; yc = 0; }
     }
