@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "me_fullpel_img2.h"
 #include "me_kernels.h"
 #include "me_wave_reduce.h"
 
@@ -41,6 +42,23 @@ __global__ void __launch_bounds__(256, SVTHIP_FULLPEL_MIN_WAVES) fullpel85_kerne
     if (sb >= n_sb) return;
     // wave-uniform choice of the search-loop form (me_fullpel_impl.h): windows clipped at the picture's left / right edge take the general one
     if ((desc[6 * sb + 4] & 15) == 0) fullpel85_sb<true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
+    else fullpel85_sb<false>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
+}
+
+// Launches whose areas are at most 64x64 (me_fullpel_img2.h; the host chooses per launch).  A superblock whose search width is exactly 64
+// -- every one but those clipped at a picture edge -- takes the two-image form; the others run the forms of fullpel85_kernel unchanged
+// (one image, pitch SVTHIP_FULLPEL_LDS_PITCH), for which this launch's LDS is more than enough.
+__global__ void __launch_bounds__(256, SVTHIP_FULLPEL_MIN_WAVES) fullpel85_img2_kernel(
+    const uint8_t* __restrict__ src_plane, uint32_t src_stride, const uint8_t* __restrict__ ref_plane,
+    uint32_t ref_stride, const int32_t* __restrict__ desc, uint32_t n_sb, uint32_t* __restrict__ out_sad,
+    uint32_t* __restrict__ out_mv)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t sb = xcd_item(blockIdx.x, n_sb);
+    if (sb >= n_sb) return;
+    const int sw = desc[6 * sb + 4];
+    if (sw == 64) fullpel85_sb<true, true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
+    else if ((sw & 15) == 0) fullpel85_sb<true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
     else fullpel85_sb<false>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
 }
 

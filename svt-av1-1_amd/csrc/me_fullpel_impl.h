@@ -4,8 +4,24 @@
 
 
 constexpr int kPitch = SVTHIP_FULLPEL_LDS_PITCH;  // bytes per window row in LDS
+// two-image form (me_fullpel_img2.h): pitch, byte offset of image 1 behind image 0, and the search row of an iteration's 16 by
+// k = lane >> 2 (one nibble per k): one 16-lane ds_read_b128 group holds k = {0,3,5,6}, {1,2,4,7}, {8,11,13,14} or {9,10,12,15}, and
+// each of those gets rows r, r+4, r+8, r+12 -- four different bank quarters at 36 dwords per row
+constexpr int kPitch2 = SVTHIP_FULLPEL_IMG2_PITCH;
+constexpr int kImage1 = SVTHIP_FULLPEL_IMG2_ROWS * SVTHIP_FULLPEL_IMG2_PITCH;
+constexpr unsigned long long kRowLut = 0xFEAB6732DC894510ull;
 
 __device__ __forceinline__ uint64_t pack64(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
+
+// one ds_read_b128 that stays one: where only dword PAIRS of the result are used the compiler otherwise splits the 16-byte load into
+// 8-byte pieces and re-merges them as ds_read2_b64 (twice the LDS cycles, 32-bank rule)
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 lds_read_b128(const uint8_t* p)
+{
+    // the volatile access loses the address space that the compiler infers for smem, so it is named
+    const u32x4_t v = *(const volatile __attribute__((address_space(3))) u32x4_t*)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
 
 // global loads at byte alignment (one global_load_dword / _dwordx4 each)
 struct __attribute__((packed, aligned(1))) unaligned_u32 { uint32_t v; };
@@ -66,7 +82,7 @@ __device__ __forceinline__ uint32_t mv_word(int x, int y)
 
 
 // d: the superblock's descriptor (6 int32: src_offset, ref_offset, x/y search origin, search width/height), any address space;
-// smem: SVTHIP_FULLPEL_LDS_FIXED + (sh + 63) * SVTHIP_FULLPEL_LDS_PITCH bytes of workgroup LDS, 16-byte aligned.
+// smem: SVTHIP_FULLPEL_LDS_FIXED + (sh + 63) * SVTHIP_FULLPEL_LDS_PITCH bytes of workgroup LDS, 16-byte aligned (IMG2: fullpel_img2_lds_bytes()).
 // Results go to out_sad / out_mv [85 * sbi ...].  Must be called by all 256 threads.
 // CLS (search width a multiple of 16, the usual case; wave-uniform): the 8x8 PUs -- 256 of the 336 (PU, position) candidates of an item --
 // are tracked per position CLASS.  The four quads of a lane's 16 positions are first reduced with packed 16-bit minima (slot c of the
@@ -75,7 +91,12 @@ __device__ __forceinline__ uint32_t mv_word(int x, int y)
 // item: items are disjoint runs of 16 raster positions, so the first minimum in raster order lies in the first item that attains the
 // minimum -- which is what the key order picks -- and after the search four lanes per PU recompute that item's 16 SADs (8 v_qsad per lane,
 // once per superblock) and take the first position whose SAD equals the minimum: the reference's strict-'<' rule again.
-template <bool CLS>
+// IMG2 (with CLS, search width exactly 64, height <= 64): the window is staged twice at pitch kPitch2, image 1 four bytes later than
+// image 0, and a row step reads W0..7 from image 0 and W1..8 from image 1, so that every dword pair a v_qsad takes starts at an even
+// register of an aligned ds_read_b128 and the six v_mov_b32 per row step that formed the odd pairs are gone.  The lane -> item map is
+// (row = 16 it + kRowLut[lane >> 2], column group = lane & 3): results depend on the item, not on the lane that holds it, and a lane's
+// rows still ascend with `it`, which the strict-'<' update of the 64x64 PU needs.
+template <bool CLS, bool IMG2 = false>
 __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_plane, uint32_t src_stride,
                                              const uint8_t* __restrict__ ref_plane, uint32_t ref_stride, const int32_t* d, uint32_t sbi,
                                              uint32_t* __restrict__ out_sad, uint32_t* __restrict__ out_mv, uint8_t* smem)
@@ -84,6 +105,8 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
     uint32_t* xch = reinterpret_cast<uint32_t*>(smem);
     unsigned long long* best64_lds = reinterpret_cast<unsigned long long*>(smem + 16384);
     uint8_t* win = smem + 16384 + 64;
+    static_assert(!IMG2 || CLS, "the two-image form is a form of the class loop");
+    constexpr int P = IMG2 ? kPitch2 : kPitch;  // bytes per window row of this form
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -108,13 +131,10 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
         const uint8_t* base = ref_plane + ref_off;
         const int rows = sh + 63;
         const int ndw_valid = (sw + 63 + 3) >> 2;
-        constexpr int q_row = kPitch >> 4;
+        constexpr int q_row = P >> 4;
         const int total = rows * q_row;
-        for (int i = tid; i < total; i += 256) {
-            const int r = i / q_row;
-            const int c4 = i - r * q_row;
-            const uint8_t* p = base + (size_t)r * ref_stride + 16 * c4;
-            const int left = ndw_valid - 4 * c4;  // dwords of this slot that belong to the window
+        // one 16-byte slot of a window row; left = dwords of it that belong to the window
+        auto slot = [](const uint8_t* p, int left) {
             uint32_t t[4] = {0u, 0u, 0u, 0u};
             if (left >= 4) {
                 const unaligned_u32x4 u = *reinterpret_cast<const unaligned_u32x4*>(p);
@@ -124,7 +144,16 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
                 for (int k = 0; k < 3; k++)
                     if (k < left) t[k] = reinterpret_cast<const unaligned_u32*>(p + 4 * k)->v;
             }
-            reinterpret_cast<uint4*>(win)[i] = make_uint4(t[0], t[1], t[2], t[3]);
+            return make_uint4(t[0], t[1], t[2], t[3]);
+        };
+        for (int i = tid; i < total; i += 256) {
+            const int r = i / q_row;
+            const int c4 = i - r * q_row;
+            const uint8_t* p = base + (size_t)r * ref_stride + 16 * c4;
+            const int left = ndw_valid - 4 * c4;
+            reinterpret_cast<uint4*>(win)[i] = slot(p, left);
+            // image 1 = the same window one dword later (the same bytes of the plane, so nothing new is read)
+            if constexpr (IMG2) reinterpret_cast<uint4*>(win + kImage1)[i] = slot(p + 4, left - 1);
         }
         if (tid == 0) *best64_lds = ~0ull;
     }
@@ -158,22 +187,33 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
 
     const uint32_t himask = 0xffff0000u;
     const int n_items = n_xg * sh;
-    const int n_iter = (n_items + 63) >> 6;
+    const int n_iter = IMG2 ? (sh + 15) >> 4 : (n_items + 63) >> 6;
+    const int lane_row = (int)((kRowLut >> (4 * (lane >> 2))) & 15u);  // IMG2
 
     for (int it = 0; it < n_iter; it++) {
-        int pg = it * 64 + lane;
-        const bool lane_valid = pg < n_items;
-        if (!lane_valid) pg = 0;
-        const int y = (int)(((uint32_t)pg * inv_xg) >> 16);  // pg / n_xg, exact for n_xg <= 8 and pg < 1024 (the emulated division is ~20 instructions)
-        const int xg = pg - y * n_xg;
+        int y, xg;
+        bool lane_valid;
+        if constexpr (IMG2) {
+            // 16 rows x 4 column groups per pass; a lane past the last row repeats row 0 of its column group (see below)
+            y = 16 * it + lane_row;
+            xg = lane & 3;
+            lane_valid = y < sh;
+            if (!lane_valid) y = 0;
+        } else {
+            int pg = it * 64 + lane;
+            lane_valid = pg < n_items;
+            if (!lane_valid) pg = 0;
+            y = (int)(((uint32_t)pg * inv_xg) >> 16);  // pg / n_xg, exact for n_xg <= 8 and pg < 1024 (the emulated division is ~20 instructions)
+            xg = pg - y * n_xg;
+        }
 
         // per-position raster index; positions outside the search area get idx = ~0 so that every key
         // OR-ed with it is 0xffffffff and can never win (at least one position is always valid).  A lane past the last item
-        // repeats item 0: its keys duplicate lane 0's of the first pass and change no minimum.  Areas whose width is a multiple
+        // repeats item 0 (IMG2: row 0 of its column group): its keys duplicate a first-pass lane's and change no minimum.  Areas whose width is a multiple
         // of 16 (the usual case) have no outside positions at all: one add per position instead of compare + select.
         uint32_t idx[16];
         const uint32_t idx0 = (uint32_t)(y * 128 + 16 * xg);
-        if ((sw & 15) == 0) {
+        if (IMG2 || (sw & 15) == 0) {
 #pragma unroll
             for (int i = 0; i < 16; i++) idx[i] = idx0 + (uint32_t)i;
         } else {
@@ -183,16 +223,24 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
 
         uint32_t s16lo[4][4], s16hi[4][4];  // [zz][q] packed u16 16x16 sums
 
-        const uint8_t* wbase = win + (y + 32 * Qy) * kPitch + 16 * xg + 32 * Qx;
+        const uint8_t* wbase = win + (y + 32 * Qy) * P + 16 * xg + 32 * Qx;
 
         // The 32 (16x16 sub-block, row) steps are software-pipelined: the window row (two ds_read_b128) and the source row (one
         // s_load_dwordx4) of step n + 1 are issued before the 16 v_qsad of step n, so their latency hides behind ~260 issue cycles
         // instead of being waited for at the top of every row (12 more live VGPRs; the kernel stays at three workgroups per CU).
-        uint4 An, Bn;
+        // IMG2: C = W1..4 and D = W5..8 come from image 1 with the same requests (four aligned ds_read_b128 per step).
+        uint4 An, Bn, Cn = make_uint4(0, 0, 0, 0), Dn = make_uint4(0, 0, 0, 0);
         uint32_t Sn[4];
         {
-            An = *reinterpret_cast<const uint4*>(wbase);
-            Bn = *reinterpret_cast<const uint4*>(wbase + 16);
+            if constexpr (IMG2) {
+                An = lds_read_b128(wbase);
+                Bn = lds_read_b128(wbase + 16);
+                Cn = lds_read_b128(wbase + kImage1);
+                Dn = lds_read_b128(wbase + kImage1 + 16);
+            } else {
+                An = *reinterpret_cast<const uint4*>(wbase);
+                Bn = *reinterpret_cast<const uint4*>(wbase + 16);
+            }
 #pragma unroll
             for (int h = 0; h < 4; h++) Sn[h] = src4[h];  // uniform address, read-only -> s_load_dwordx4
         }
@@ -202,20 +250,32 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
 
 #pragma unroll
             for (int r8 = 0; r8 < 8; r8++) {
-                const uint4 A = An, B = Bn;
+                const uint4 A = An, B = Bn, Cw = Cn, Dw = Dn;
                 const uint32_t W[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
                 const uint32_t S[4] = {Sn[0], Sn[1], Sn[2], Sn[3]};
+                // WP[j] = (W[j], W[j+1]); IMG2 takes the odd ones from image 1, where they sit in an aligned register pair
+                const uint64_t WP[7] = {pack64(W[0], W[1]), IMG2 ? pack64(Cw.x, Cw.y) : pack64(W[1], W[2]), pack64(W[2], W[3]),
+                                        IMG2 ? pack64(Cw.z, Cw.w) : pack64(W[3], W[4]), pack64(W[4], W[5]),
+                                        IMG2 ? pack64(Dw.x, Dw.y) : pack64(W[5], W[6]), pack64(W[6], W[7])};
                 // this step's operands were requested one step ago: make the s_waitcnt for them land HERE, before the next requests go
                 // out (scalar loads return out of order, so any later wait would be lgkmcnt(0) and cover the fresh requests too)
                 asm volatile("" ::"v"(A.x), "v"(A.y), "v"(A.z), "v"(A.w), "v"(B.x), "v"(B.y), "v"(B.z), "v"(B.w), "s"(S[0]), "s"(S[1]), "s"(S[2]), "s"(S[3]));
+                if constexpr (IMG2) asm volatile("" ::"v"(Cw.x), "v"(Cw.y), "v"(Cw.z), "v"(Cw.w), "v"(Dw.x), "v"(Dw.y), "v"(Dw.z), "v"(Dw.w));
                 __builtin_amdgcn_sched_barrier(0);
                 {
                     const int nstep = zz * 8 + r8 + 1;
                     if (nstep < 32) {
                         const int nzz = nstep >> 3, nr8 = nstep & 7, nC = nzz & 1, nR = nzz >> 1;
-                        const uint8_t* p = wbase + (16 * nR + 2 * nr8) * kPitch + 16 * nC;
-                        An = *reinterpret_cast<const uint4*>(p);
-                        Bn = *reinterpret_cast<const uint4*>(p + 16);
+                        const uint8_t* p = wbase + (16 * nR + 2 * nr8) * P + 16 * nC;
+                        if constexpr (IMG2) {
+                            An = lds_read_b128(p);
+                            Bn = lds_read_b128(p + 16);
+                            Cn = lds_read_b128(p + kImage1);
+                            Dn = lds_read_b128(p + kImage1 + 16);
+                        } else {
+                            An = *reinterpret_cast<const uint4*>(p);
+                            Bn = *reinterpret_cast<const uint4*>(p + 16);
+                        }
                         const uint32_t* srow = src4 + (16 * nR + 2 * nr8) * sstride4 + 4 * nC;
 #pragma unroll
                         for (int h = 0; h < 4; h++) Sn[h] = srow[h];
@@ -229,8 +289,7 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
                     for (int h = 0; h < 4; h++) {
                         const int k = krow + (h >> 1);
                         const bool first = ((r8 & 3) == 0) && ((h & 1) == 0);  // first touch of acc[k][q]
-                        acc[k][q] = __builtin_amdgcn_qsad_pk_u16_u8(pack64(W[q + h], W[q + h + 1]), S[h],
-                                                                    first ? 0ull : acc[k][q]);
+                        acc[k][q] = __builtin_amdgcn_qsad_pk_u16_u8(WP[q + h], S[h], first ? 0ull : acc[k][q]);
                     }
             }
 
@@ -329,11 +388,11 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
         const uint32_t s = key >> 16, id = key & 0xffffu;  // id = y * 128 + 16 * xg + class
         const int y = (int)(id >> 7), xb = (int)(id & 0x70u);
         const int zz = p >> 2, k = p & 3, px = 16 * (zz & 1) + 8 * (k & 1), py = 16 * (zz >> 1) + 8 * (k >> 1);
-        const uint8_t* wp = win + (y + 32 * Qy + py) * kPitch + xb + 4 * q + 32 * Qx + px;
+        const uint8_t* wp = win + (y + 32 * Qy + py) * P + xb + 4 * q + 32 * Qx + px;
         uint64_t a = 0;
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(wp + 2 * r * kPitch);
+            const uint32_t* w = reinterpret_cast<const uint32_t*>(wp + 2 * r * P);
             const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
             a = __builtin_amdgcn_qsad_pk_u16_u8(pack64(w0, w1), rsv[r][0], a);
             a = __builtin_amdgcn_qsad_pk_u16_u8(pack64(w1, w2), rsv[r][1], a);

@@ -12,6 +12,7 @@
 #include <new>
 
 #include "../../include/svtav1_hip.h"
+#include "me_fullpel_img2.h"
 #include "me_kernels.h"
 
 namespace {
@@ -191,9 +192,14 @@ int32_t launch_fullpel(svthip_ctx* ctx, const uint8_t* d_src, uint32_t src_strid
         return fail(SVTHIP_ERR_BAD_PARAMETER, "search area must be 1..127 (%s%d)", "got ", (int)(max_sw > max_sh ? max_sw : max_sh));
     if ((src_stride & 3u) || (ref_stride & 3u) || (reinterpret_cast<uintptr_t>(d_src) & 3u))
         return fail(SVTHIP_ERR_BAD_PARAMETER, "plane strides and the source plane base must be multiples of 4%s", "");
-    const size_t lds = svthip::fullpel_lds_bytes(max_sh);
-    hipLaunchKernelGGL(svthip::fullpel85_kernel, dim3(svthip::xcd_grid(n_sb)), dim3(256), lds, s, d_src, src_stride, d_ref, ref_stride,
-                       reinterpret_cast<const int32_t*>(d_desc), n_sb, d_sad, d_mv);
+    if (svthip::fullpel_img2_fits(max_sw, max_sh)) {  // areas up to 64x64: the two-image kernel (me_fullpel_img2.h), chosen once per launch
+        hipLaunchKernelGGL(svthip::fullpel85_img2_kernel, dim3(svthip::xcd_grid(n_sb)), dim3(256), svthip::fullpel_img2_lds_bytes(), s, d_src,
+                           src_stride, d_ref, ref_stride, reinterpret_cast<const int32_t*>(d_desc), n_sb, d_sad, d_mv);
+    } else {
+        const size_t lds = svthip::fullpel_lds_bytes(max_sh);
+        hipLaunchKernelGGL(svthip::fullpel85_kernel, dim3(svthip::xcd_grid(n_sb)), dim3(256), lds, s, d_src, src_stride, d_ref, ref_stride,
+                           reinterpret_cast<const int32_t*>(d_desc), n_sb, d_sad, d_mv);
+    }
     HIP_TRY(hipGetLastError());
     return SVTHIP_OK;
 }
