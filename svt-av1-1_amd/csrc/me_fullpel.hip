@@ -9,7 +9,8 @@
 //
 // Mapping (see DESIGN.md "full-pel kernel"):
 //   * the (sw+63) x (sh+63) reference window is staged once into LDS (pitch 192 B, conflict-free for
-//     the 16-lane ds_read_b128 groups), re-aligned to the search origin with v_alignbyte;
+//     the 16-lane ds_read_b128 groups): staging reads the plane at the search origin's own byte
+//     alignment and writes ds_write_b128, so window byte 0 is search column 0;
 //   * wave w of the 256-thread workgroup owns 32x32 quadrant w of the SB, so its source pixels are
 //     wave-uniform and live in SGPRs (scalar loads straight from the source plane);
 //   * lane l owns 16 horizontally consecutive search positions of one row; a 16-pixel block row
@@ -23,16 +24,14 @@
 #include <stdint.h>
 
 #include "me_fullpel_img2.h"
+#include "me_fullpel_impl.h"
 #include "me_kernels.h"
-#include "me_wave_reduce.h"
 
 namespace svthip {
 
-namespace {
-#include "me_fullpel_impl.h"
-}  // namespace
+constexpr int kFullpelMinWaves = 3;  // workgroups per CU that the register budget is held to (three fit the LDS plans)
 
-__global__ void __launch_bounds__(256, SVTHIP_FULLPEL_MIN_WAVES) fullpel85_kernel(
+__global__ void __launch_bounds__(256, kFullpelMinWaves) fullpel85_kernel(
     const uint8_t* __restrict__ src_plane, uint32_t src_stride, const uint8_t* __restrict__ ref_plane,
     uint32_t ref_stride, const int32_t* __restrict__ desc, uint32_t n_sb, uint32_t* __restrict__ out_sad,
     uint32_t* __restrict__ out_mv)
@@ -48,7 +47,7 @@ __global__ void __launch_bounds__(256, SVTHIP_FULLPEL_MIN_WAVES) fullpel85_kerne
 // Launches whose areas are at most 64x64 (me_fullpel_img2.h; the host chooses per launch).  A superblock whose search width is exactly 64
 // -- every one but those clipped at a picture edge -- takes the two-image form; the others run the forms of fullpel85_kernel unchanged
 // (one image, pitch SVTHIP_FULLPEL_LDS_PITCH), for which this launch's LDS is more than enough.
-__global__ void __launch_bounds__(256, SVTHIP_FULLPEL_MIN_WAVES) fullpel85_img2_kernel(
+__global__ void __launch_bounds__(256, kFullpelMinWaves) fullpel85_img2_kernel(
     const uint8_t* __restrict__ src_plane, uint32_t src_stride, const uint8_t* __restrict__ ref_plane,
     uint32_t ref_stride, const int32_t* __restrict__ desc, uint32_t n_sb, uint32_t* __restrict__ out_sad,
     uint32_t* __restrict__ out_mv)

@@ -2,21 +2,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "me_fullpel209_impl.h"
 #include "me_kernels.h"
-#include "me_wave_reduce.h"
 
 namespace svthip {
 
-namespace {
-namespace fp209 {
-#include "me_fullpel209_impl.h"
-}
-}  // namespace
+constexpr int kFp209MinWaves = 3;  // workgroups per CU: 168 VGPRs, the top of that bracket (see the spill history in me_fullpel209_impl.h)
 
-#ifndef SVTHIP_FP209_MIN_WAVES
-#define SVTHIP_FP209_MIN_WAVES 3
-#endif
-__global__ void __launch_bounds__(256, SVTHIP_FP209_MIN_WAVES) fullpel209_kernel(const uint8_t* __restrict__ src_plane, uint32_t src_stride,
+__global__ void __launch_bounds__(256, kFp209MinWaves) fullpel209_kernel(const uint8_t* __restrict__ src_plane, uint32_t src_stride,
                                                             const uint8_t* __restrict__ ref_plane, uint32_t ref_stride,
                                                             const int32_t* __restrict__ desc, uint32_t n_sb, uint32_t* __restrict__ out_sad,
                                                             uint32_t* __restrict__ out_mv)
@@ -25,14 +18,10 @@ __global__ void __launch_bounds__(256, SVTHIP_FP209_MIN_WAVES) fullpel209_kernel
     const uint32_t sb = xcd_item(blockIdx.x, n_sb);  // raster neighbours share an XCD's L2 (me_kernels.h)
     if (sb >= n_sb) return;
     // wave-uniform choice of the search-loop form (me_fullpel209_impl.h): clipped windows at the picture's left / right edge take the general one
-#ifdef SVTHIP_FP209_EXPERIMENT_FAST_ONLY  // resource experiments: tools/kernel_resources.sh ... -DSVTHIP_FP209_EXPERIMENT_FAST_ONLY
-    fp209::fullpel209_sb<true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
-    return;
-#endif
-    if ((desc[6 * sb + 4] & 15) == 0) fp209::fullpel209_sb<true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
-    else fp209::fullpel209_sb<false>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
+    if ((desc[6 * sb + 4] & 15) == 0) fullpel209_sb<true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
+    else fullpel209_sb<false>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
 }
 
-size_t fullpel209_lds_bytes(uint32_t max_sh) { return (size_t)fp209::kFp209Fixed + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
+size_t fullpel209_lds_bytes(uint32_t max_sh) { return (size_t)kFp209Fixed + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 
 }  // namespace svthip

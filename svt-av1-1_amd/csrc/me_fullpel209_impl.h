@@ -12,71 +12,17 @@
 // with the current SAD whenever the SAD of 64x32[1] at that position is below the stored best.  That is a sequential
 // recurrence over raster order, resolved per iteration by wave 0 from the per-position (64x32[1], 32x16[5]) pairs in LDS:
 // "first later position whose 64x32[1] SAD is below the current best" repeated until none (the best strictly decreases).
-// Included inside namespace svthip { namespace { namespace fp209 { ... } } }.
+// The pieces shared with the 85-PU search are in me_fullpel_common.h.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
+#include "me_fullpel_common.h"
+#include "me_kernels.h"
+#include "me_wave_reduce.h"
 
-constexpr int kPitch = SVTHIP_FULLPEL_LDS_PITCH;  // bytes per window row in LDS
-
-__device__ __forceinline__ uint64_t pack64(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
-
-// global loads at byte alignment (one global_load_dword / _dwordx4 each)
-struct __attribute__((packed, aligned(1))) unaligned_u32 { uint32_t v; };
-struct __attribute__((packed, aligned(1))) unaligned_u32x4 { uint32_t v[4]; };
-
-__device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c)
-{
-    uint32_t r;
-    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-// keys for the four positions of a quad from packed u16 SADs (lo: slots 0,1  hi: slots 2,3)
-__device__ __forceinline__ uint32_t track4(uint32_t best, uint64_t acc, const uint32_t* idx, uint32_t himask)
-{
-    const uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
-    uint32_t k0 = (lo << 16) | idx[0];
-    uint32_t k1 = (lo & himask) | idx[1];
-    uint32_t k2 = (hi << 16) | idx[2];
-    uint32_t k3 = (hi & himask) | idx[3];
-    best = min3u(best, k0, k1);
-    best = min3u(best, k2, k3);
-    return best;
-}
-
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        uint32_t o = __shfl_xor(v, m);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        unsigned long long o = __shfl_xor(v, m);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t mv_word(int x, int y)
-{
-    // (uint16)(4*y) << 16 | (uint16)(4*x), Codec/EbMotionEstimation.c:1389-1391
-    return ((uint32_t)(uint16_t)(y * 4) << 16) | (uint32_t)(uint16_t)(x * 4);
-}
-
+namespace svthip {
+namespace {
 
 constexpr int kFp209Fixed = 16384 + 8192 + 1280;  // exchange buffer, (64x32[1], 32x16[5]) pairs, 64x64 result + best keys
 
@@ -143,52 +89,17 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
     const int Q = __builtin_amdgcn_readfirstlane(tid >> 6);  // quadrant = wave index
     const int Qx = Q & 1, Qy = Q >> 1;
 
-    // wave-uniform by construction; readfirstlane keeps them in SGPRs also when the descriptor is read from LDS
-    const int src_off = __builtin_amdgcn_readfirstlane(d[0]);
-    const int ref_off = __builtin_amdgcn_readfirstlane(d[1]);
-    const int xo = __builtin_amdgcn_readfirstlane(d[2]), yo = __builtin_amdgcn_readfirstlane(d[3]);
-    const int sw = __builtin_amdgcn_readfirstlane(d[4]), sh = __builtin_amdgcn_readfirstlane(d[5]);
-    const int n_xg = (sw + 15) >> 4;
-    const uint32_t inv_xg = (65536u + (uint32_t)n_xg - 1u) / (uint32_t)n_xg;  // wave-uniform, scalar unit
+    const FullpelDesc D = fullpel_decode_desc(d);
+    const int xo = D.xo, yo = D.yo, sw = D.sw, sh = D.sh, n_xg = D.n_xg;
 
-#ifdef SVTHIP_FP_STAGE_PRIO
-    __builtin_amdgcn_s_setprio(3);
-#endif
     // ---- stage the reference window: rows 0..sh+62, bytes 0..sw+62 valid, zero beyond ----
-    {
-        // 16 bytes per thread and pass, read at the window's own byte alignment (global loads need no alignment on this target) and
-        // written as one ds_write_b128: 6 passes for a 64x64 area instead of 24 dword passes with a second load + v_alignbyte each
-        const uint8_t* base = ref_plane + ref_off;
-        const int rows = sh + 63;
-        const int ndw_valid = (sw + 63 + 3) >> 2;
-        constexpr int q_row = kPitch >> 4;
-        const int total = rows * q_row;
-        for (int i = tid; i < total; i += 256) {
-            const int r = i / q_row;
-            const int c4 = i - r * q_row;
-            const uint8_t* p = base + (size_t)r * ref_stride + 16 * c4;
-            const int left = ndw_valid - 4 * c4;  // dwords of this slot that belong to the window
-            uint32_t t[4] = {0u, 0u, 0u, 0u};
-            if (left >= 4) {
-                const unaligned_u32x4 u = *reinterpret_cast<const unaligned_u32x4*>(p);
-                t[0] = u.v[0]; t[1] = u.v[1]; t[2] = u.v[2]; t[3] = u.v[3];
-            } else if (left > 0) {  // the row's last dwords: nothing is read past them
-#pragma unroll
-                for (int k = 0; k < 3; k++)
-                    if (k < left) t[k] = reinterpret_cast<const unaligned_u32*>(p + 4 * k)->v;
-            }
-            reinterpret_cast<uint4*>(win)[i] = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-        if (tid == 0) *best64_lds = ~0ull;
-        for (int i = tid; i < kFp209Slots; i += 256) pu_key[i] = 0xffffffffu;
-    }
+    stage_window<kPitch>(win, ref_plane + D.ref_off, ref_stride, sw, sh, tid);
+    if (tid == 0) *best64_lds = ~0ull;
+    for (int i = tid; i < kFp209Slots; i += 256) pu_key[i] = 0xffffffffu;
     __syncthreads();
-#ifdef SVTHIP_FP_STAGE_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
 
     // source pixels of this wave's quadrant (wave-uniform -> scalar loads)
-    const uint32_t* src4 = reinterpret_cast<const uint32_t*>(src_plane + src_off + (size_t)(32 * Qy) * src_stride + 32 * Qx);
+    const uint32_t* src4 = reinterpret_cast<const uint32_t*>(src_plane + D.src_off + (size_t)(32 * Qy) * src_stride + 32 * Qx);
     const int sstride4 = src_stride >> 2;
 
     uint32_t best64_raw = 0xffffffffu, best64_idx = 0;
@@ -208,11 +119,8 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
         // workgroups per CU the hoisted copies are what the register allocator spills and reloads around the search loop.
         uint32_t lane_v = (uint32_t)lane;
         asm volatile("" : "+v"(lane_v));
-        int pg = it * 64 + lane;
-        const bool lane_valid = pg < n_items;
-        if (!lane_valid) pg = 0;
-        const int y = (int)(((uint32_t)pg * inv_xg) >> 16);  // pg / n_xg, exact for n_xg <= 8 and pg < 1024 (the emulated division is ~20 instructions)
-        const int xg = pg - y * n_xg;
+        int y, xg;
+        const bool lane_valid = fullpel_raster_item(it, lane, n_items, n_xg, D.inv_xg, y, xg);
 
         // per-position raster index; positions outside the search area get idx = ~0 so that every key
         // OR-ed with it is 0xffffffff and can never win (at least one position is always valid)
@@ -225,7 +133,7 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
         // A lane past the last item repeats item 0: its keys duplicate lane 0's of the first pass and change no minimum (the 64x64 PU
         // and the 32x16[5] recurrence, which are not plain minima, check lane_valid).
         uint32_t idx[16];
-        const uint32_t idx0 = (uint32_t)(y * 128 + 16 * xg);
+        const uint32_t idx0 = fullpel_idx0(y, xg);
         const uint32_t orv = FAST ? idx0 : 0u;  // what a finished tracker still has to be OR-ed with
 #pragma unroll
         for (int i = 0; i < 16; i++) idx[i] = FAST ? (uint32_t)i : ((lane_valid && 16 * xg + i < sw) ? idx0 + (uint32_t)i : 0xffffffffu);
@@ -239,18 +147,6 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
 
         const uint8_t* wbase = win + (y + 32 * Qy) * kPitch + 16 * xg + 32 * Qx;
 
-        // software-pipelined row steps, as in me_fullpel_impl.h: the window row and source row of step n + 1 are requested before the
-        // 16 v_qsad of step n
-#ifdef SVTHIP_FP209_PIPELINE
-        uint4 An, Bn;
-        uint32_t Sn[4];
-        {
-            An = *reinterpret_cast<const uint4*>(wbase);
-            Bn = *reinterpret_cast<const uint4*>(wbase + 16);
-#pragma unroll
-            for (int h = 0; h < 4; h++) Sn[h] = src4[h];
-        }
-#endif
 #pragma unroll
         for (int zz = 0; zz < 4; zz++) {
             const int C = zz & 1, R = zz >> 1;
@@ -258,33 +154,14 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
 
 #pragma unroll
             for (int r8 = 0; r8 < 8; r8++) {
-#ifndef SVTHIP_FP209_PIPELINE  // operands loaded where they are used: the 85-PU kernel's software pipelining (next step's window row and
-                                // source row requested one step ahead) costs 16 more live VGPRs, which here means spills: 764 vs 723 us per 6120 SBs
+                // operands loaded where they are used: the 85-PU kernel's software pipelining (next step's window row and source row
+                // requested one step ahead, me_fullpel_impl.h) costs 16 more live VGPRs, which here means spills: 764 vs 723 us per 6120 SBs
                 const uint8_t* pp_ = wbase + (16 * R + 2 * r8) * kPitch + 16 * C;
                 const uint4 A = *reinterpret_cast<const uint4*>(pp_), B = *reinterpret_cast<const uint4*>(pp_ + 16);
                 const uint32_t* sr_ = src4 + (16 * R + 2 * r8) * sstride4 + 4 * C;
                 const uint32_t S[4] = {sr_[0], sr_[1], sr_[2], sr_[3]};
-#else
-                const uint4 A = An, B = Bn;
-                const uint32_t S[4] = {Sn[0], Sn[1], Sn[2], Sn[3]};
-#endif
                 asm volatile("" ::"v"(A.x), "v"(A.y), "v"(A.z), "v"(A.w), "v"(B.x), "v"(B.y), "v"(B.z), "v"(B.w), "s"(S[0]), "s"(S[1]), "s"(S[2]), "s"(S[3]));
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef SVTHIP_FP209_PIPELINE
-                {
-                    const int nstep = zz * 8 + r8 + 1;
-                    if (nstep < 32) {
-                        const int nzz = nstep >> 3, nr8 = nstep & 7, nC = nzz & 1, nR = nzz >> 1;
-                        const uint8_t* p = wbase + (16 * nR + 2 * nr8) * kPitch + 16 * nC;
-                        An = *reinterpret_cast<const uint4*>(p);
-                        Bn = *reinterpret_cast<const uint4*>(p + 16);
-                        const uint32_t* nsrow = src4 + (16 * nR + 2 * nr8) * sstride4 + 4 * nC;
-#pragma unroll
-                        for (int h = 0; h < 4; h++) Sn[h] = nsrow[h];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#endif
                 // window dword pairs (W[k], W[k+1]), k = 0..6: the even ones are the loaded register pairs, the odd ones are formed
                 // with one v_pk_mov_b32 each (hi of one pair, lo of the next).  Left to the compiler they cost two v_mov each
                 // and, under register pressure (209-PU kernel), a round trip through scratch memory.
@@ -312,15 +189,10 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
             // One position quad at a time, with a scheduling fence after each: left to itself the scheduler forms the ~200 keys of a 16x16
             // block's 13 trackers all at once for the sake of instruction-level parallelism and spills the live 16x16 sums to make room.
             if constexpr (FAST) {
-                // 8x8 PUs per position CLASS, as in the 85-PU kernel (me_fullpel_impl.h): packed 16-bit minima over the lane's four quads,
-                // one quad of keys (sad << 16 | class) per PU; the winner's position inside its item is resolved after the search
+                // 8x8 PUs per position CLASS, as in the 85-PU kernel: one quad of keys (sad << 16 | class) per PU; the winner's position
+                // inside its item is resolved after the search
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t mlo = pk_min_u16(pk_min_u16((uint32_t)acc[k][0], (uint32_t)acc[k][1]), pk_min_u16((uint32_t)acc[k][2], (uint32_t)acc[k][3]));
-                    const uint32_t mhi = pk_min_u16(pk_min_u16((uint32_t)(acc[k][0] >> 32), (uint32_t)(acc[k][1] >> 32)),
-                                                    pk_min_u16((uint32_t)(acc[k][2] >> 32), (uint32_t)(acc[k][3] >> 32)));
-                    k8[k] = track4(k8[k], pack64(mlo, mhi), &idx[0], himask);
-                }
+                for (int k = 0; k < 4; k++) k8[k] = track_class8(k8[k], acc[k], &idx[0], himask);
             }
 #pragma unroll
             for (int q = 0; q < 4; q++) {
@@ -405,25 +277,9 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
             __builtin_amdgcn_sched_barrier(0);
         }
 
-        // 32x32 = sum of the four 16x16: pairs are added packed (<= 2*32640 fits u16), then widened
         uint32_t s32acc[16];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t a_lo = s16lo[0][q] + s16lo[1][q], b_lo = s16lo[2][q] + s16lo[3][q];
-            const uint32_t a_hi = s16hi[0][q] + s16hi[1][q], b_hi = s16hi[2][q] + s16hi[3][q];
-            s32acc[4 * q + 0] = (a_lo & 0xffffu) + (b_lo & 0xffffu);
-            s32acc[4 * q + 1] = (a_lo >> 16) + (b_lo >> 16);
-            s32acc[4 * q + 2] = (a_hi & 0xffffu) + (b_hi & 0xffffu);
-            s32acc[4 * q + 3] = (a_hi >> 16) + (b_hi >> 16);
-        }
-
-        // 32x32 PU of this quadrant: key = raw << 14 | idx  (raw <= 130560 < 2^17)
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            uint32_t k0 = (s32acc[i] << 14) | idx[i];
-            uint32_t k1 = (s32acc[i + 1] << 14) | idx[i + 1];
-            k32 = min3u(k32, k0, k1);
-        }
+        widen_sums32(s16lo, s16hi, s32acc);
+        k32 = track32(k32, s32acc, idx);
 
         {
             // PU 92 (32x16[5], Q == 2) follows the recurrence instead: its tracker was never updated and stays 0xffffffff
@@ -558,46 +414,29 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
     // ---- publish: every PU's key is in LDS (64x64 as a 64-bit (raw, idx) pair, PU 92 from the recurrence state) ----
     uint32_t* osad = out_sad + (size_t)209 * sbi;
     uint32_t* omv = out_mv + (size_t)209 * sbi;
-    const unsigned long long k64 = wave_min_u64(((unsigned long long)best64_raw << 32) | best64_idx);
-    if (lane == 0) atomicMin(best64_lds, k64);
+    merge_best64(best64_lds, best64_raw, best64_idx, lane);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the ds_min_u32 above are invisible to the compiler's counter tracking
     __syncthreads();
     if constexpr (FAST) {
-        // resolve the 8x8 winners (key = sad << 16 | y * 128 + 16 * xg + class): lane = 4 * PU + quad recomputes the SADs of positions
-        // 4 quad .. 4 quad + 3 of the winning item; the first position whose SAD equals the minimum is the reference's strict-'<' winner
-        const int p = lane >> 2, q = lane & 3;
-        const int zz = p >> 2, k = p & 3, px = 16 * (zz & 1) + 8 * (k & 1), py = 16 * (zz >> 1) + 8 * (k >> 1);
-        const uint32_t key = pu_key[16 * (4 * Q + zz) + k];
-        const uint32_t s = key >> 16, id = key & 0xffffu;
-        const int y = (int)(id >> 7), xb = (int)(id & 0x70u);
-        const uint8_t* wp = win + (y + 32 * Qy + py) * kPitch + xb + 4 * q + 32 * Qx + px;
+        // resolve the 8x8 winners: lane = 4 * PU + quad reads PU's key from its slot.  The PU's source dwords are loaded here, not
+        // before the search as in the 85-PU kernel: this kernel has no registers to spare across the loop
+        const int p = lane >> 2;
+        int px, py;
+        pu8_origin(p, px, py);
         const uint32_t* sp = src4 + (size_t)py * sstride4 + (px >> 2);
-        uint64_t a = 0;
+        uint32_t rs[4][2];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(wp + 2 * r * kPitch);
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-            a = __builtin_amdgcn_qsad_pk_u16_u8(pack64(w0, w1), sp[(size_t)(2 * r) * sstride4], a);
-            a = __builtin_amdgcn_qsad_pk_u16_u8(pack64(w1, w2), sp[(size_t)(2 * r) * sstride4 + 1], a);
+            rs[r][0] = sp[(size_t)(2 * r) * sstride4];
+            rs[r][1] = sp[(size_t)(2 * r) * sstride4 + 1];
         }
-        const uint32_t lo = (uint32_t)a, hi = (uint32_t)(a >> 32);
-        uint32_t first = (lo & 0xffffu) == s ? 0u : (lo >> 16) == s ? 1u : (hi & 0xffffu) == s ? 2u : (hi >> 16) == s ? 3u : 64u;
-        first += 4u * (uint32_t)q;
-        first = min(first, (uint32_t)__shfl_xor((int)first, 1));
-        first = min(first, (uint32_t)__shfl_xor((int)first, 2));
-        if (q == 0) {
-            const int pu = 21 + 16 * Q + p;
-            osad[pu] = 2u * s;
-            omv[pu] = mv_word(xo + xb + (int)first, yo + y);
-        }
+        resolve_class8<kPitch>(win, pu_key[16 * (4 * Q + (p >> 2)) + (p & 3)], rs, lane, Q, xo, yo, osad, omv);
     }
     if (tid < 209 && !(FAST && tid >= 21 && tid < 85)) {
         const int pu = tid;
         uint32_t raw, id;
         if (pu == 0) {
-            const unsigned long long k = *best64_lds;
-            raw = (uint32_t)(k >> 32);
-            id = (uint32_t)k;
+            read_best64(best64_lds, raw, id);
         } else {
             // 32x32 and the cross-quadrant rectangles carry raw << 14, everything else raw << 16 (idx = y * 128 + x, 14 bits)
             const bool wide = (pu >= 1 && pu <= 4) || pu == 85 || pu == 86 || pu == 127 || pu == 128 || pu >= 201;
@@ -605,13 +444,10 @@ __device__ __forceinline__ void fullpel209_sb(const uint8_t* __restrict__ src_pl
             raw = wide ? key >> 14 : key >> 16;
             id = key & 0x3fffu;
         }
-        if (pu != 92) {
-            osad[pu] = 2u * raw;
-            omv[pu] = mv_word(xo + (int)(id & 127u), yo + (int)(id >> 7));
-        }
+        if (pu != 92) store_pu(osad, omv, pu, raw, id, xo, yo);
     }
-    if (tid == 0) {  // wave 0 holds the (wave-uniform) state of the 32x16[5] recurrence
-        osad[92] = 2u * q5_raw;
-        omv[92] = mv_word(xo + (int)(q5_idx & 127u), yo + (int)(q5_idx >> 7));
-    }
+    if (tid == 0) store_pu(osad, omv, 92, q5_raw, q5_idx, xo, yo);  // wave 0 holds the (wave-uniform) state of the 32x16[5] recurrence
 }
+
+}  // namespace
+}  // namespace svthip

@@ -1,0 +1,191 @@
+// svt-av1-1_amd/csrc/me_fullpel_common.h -- what the 85-PU (me_fullpel_impl.h) and the 209-PU (me_fullpel209_impl.h) full-pel search of
+// one superblock by one 256-thread workgroup have in common: descriptor decode, window staging, the raster lane -> item map, the
+// square-PU key steps, the 8x8 class resolver and the 64x64 publish.  The row-step loops are NOT here: the three forms (one image
+// pipelined, two images pipelined, 209-PU unpipelined with v_pk_mov_b32) differ for measured reasons.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "me_kernels.h"
+#include "me_sad_common.h"
+
+namespace svthip {
+
+constexpr int kPitch = SVTHIP_FULLPEL_LDS_PITCH;  // bytes per window row in LDS (one-image plans)
+
+// a superblock's descriptor (6 int32: src_offset, ref_offset, x/y search origin, search width/height) and what follows from it:
+// column groups of 16 positions per search row, and 2^16 / n_xg rounded up for the division by n_xg
+struct FullpelDesc {
+    int src_off, ref_off, xo, yo, sw, sh, n_xg;
+    uint32_t inv_xg;
+};
+
+// d: any address space.  The values are wave-uniform by construction; readfirstlane keeps them in SGPRs also when the descriptor is
+// read from LDS
+__device__ __forceinline__ FullpelDesc fullpel_decode_desc(const int32_t* d)
+{
+    FullpelDesc D;
+    D.src_off = __builtin_amdgcn_readfirstlane(d[0]);
+    D.ref_off = __builtin_amdgcn_readfirstlane(d[1]);
+    D.xo = __builtin_amdgcn_readfirstlane(d[2]);
+    D.yo = __builtin_amdgcn_readfirstlane(d[3]);
+    D.sw = __builtin_amdgcn_readfirstlane(d[4]);
+    D.sh = __builtin_amdgcn_readfirstlane(d[5]);
+    D.n_xg = (D.sw + 15) >> 4;
+    D.inv_xg = (65536u + (uint32_t)D.n_xg - 1u) / (uint32_t)D.n_xg;  // wave-uniform, scalar unit
+    return D;
+}
+
+// Stages the reference window at `base` into LDS at `win`, PITCH bytes per row: rows 0..sh+62, bytes 0..sw+62 valid, zero beyond.
+// 16 bytes per thread and pass, read at the window's own byte alignment (global loads need no alignment on this target) and written as
+// one ds_write_b128: 6 passes for a 64x64 area instead of 24 dword passes with a second load + v_alignbyte each.
+// IMAGE1 != 0 (the two-image LDS plan, me_fullpel_img2.h): a second image IMAGE1 bytes behind the first holds the same window one
+// dword later (the same bytes of the plane, so nothing new is read).
+template <int PITCH, int IMAGE1 = 0>
+__device__ __forceinline__ void stage_window(uint8_t* win, const uint8_t* base, uint32_t ref_stride, int sw, int sh, int tid)
+{
+    const int rows = sh + 63;
+    const int ndw_valid = (sw + 63 + 3) >> 2;
+    constexpr int q_row = PITCH >> 4;
+    const int total = rows * q_row;
+    // one 16-byte slot of a window row; left = dwords of it that belong to the window
+    auto slot = [](const uint8_t* p, int left) {
+        uint32_t t[4] = {0u, 0u, 0u, 0u};
+        if (left >= 4) {
+            const unaligned_u32x4 u = *reinterpret_cast<const unaligned_u32x4*>(p);
+            t[0] = u.v[0]; t[1] = u.v[1]; t[2] = u.v[2]; t[3] = u.v[3];
+        } else if (left > 0) {  // the row's last dwords: nothing is read past them
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                if (k < left) t[k] = reinterpret_cast<const unaligned_u32*>(p + 4 * k)->v;
+        }
+        return make_uint4(t[0], t[1], t[2], t[3]);
+    };
+    for (int i = tid; i < total; i += 256) {
+        const int r = i / q_row;
+        const int c4 = i - r * q_row;
+        const uint8_t* p = base + (size_t)r * ref_stride + 16 * c4;
+        const int left = ndw_valid - 4 * c4;
+        reinterpret_cast<uint4*>(win)[i] = slot(p, left);
+        if constexpr (IMAGE1 != 0) reinterpret_cast<uint4*>(win + IMAGE1)[i] = slot(p + 4, left - 1);
+    }
+}
+
+// Raster map of search iteration `it`: lane l holds item 64 it + l, an item being 16 horizontally consecutive positions (column group
+// xg of search row y).  A lane past the last item repeats item 0: its keys duplicate a first-pass lane's and change no minimum
+// (whatever is not a plain minimum checks the returned lane_valid).
+__device__ __forceinline__ bool fullpel_raster_item(int it, int lane, int n_items, int n_xg, uint32_t inv_xg, int& y, int& xg)
+{
+    int pg = it * 64 + lane;
+    const bool lane_valid = pg < n_items;
+    if (!lane_valid) pg = 0;
+    y = (int)(((uint32_t)pg * inv_xg) >> 16);  // pg / n_xg, exact for n_xg <= 8 and pg < 1024 (the emulated division is ~20 instructions)
+    xg = pg - y * n_xg;
+    return lane_valid;
+}
+// raster index (y * 128 + x) of an item's first position
+__device__ __forceinline__ uint32_t fullpel_idx0(int y, int xg) { return (uint32_t)(y * 128 + 16 * xg); }
+
+// 8x8 PUs per position CLASS: the four quads of a lane's 16 positions (acc[q]: packed u16 SADs of positions 4 q .. 4 q + 3) are first
+// reduced with packed 16-bit minima (slot c of the result = min over q of the SAD at position 4 q + c), then ONE quad of keys
+// (sad << 16 | idx[c]) goes into the running minimum: 12 instructions per PU and item instead of 24.  resolve_class8 finds the position.
+__device__ __forceinline__ uint32_t track_class8(uint32_t best, const uint64_t (&acc)[4], const uint32_t* idx, uint32_t himask)
+{
+    const uint32_t mlo = pk_min_u16(pk_min_u16((uint32_t)acc[0], (uint32_t)acc[1]), pk_min_u16((uint32_t)acc[2], (uint32_t)acc[3]));
+    const uint32_t mhi = pk_min_u16(pk_min_u16((uint32_t)(acc[0] >> 32), (uint32_t)(acc[1] >> 32)),
+                                    pk_min_u16((uint32_t)(acc[2] >> 32), (uint32_t)(acc[3] >> 32)));
+    return track4(best, pack64(mlo, mhi), idx, himask);
+}
+
+// 32x32 = sum of the four 16x16 ([zz][q] packed u16 sums): pairs are added packed (<= 2*32640 fits u16), then widened
+__device__ __forceinline__ void widen_sums32(const uint32_t (&s16lo)[4][4], const uint32_t (&s16hi)[4][4], uint32_t (&s32acc)[16])
+{
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint32_t a_lo = s16lo[0][q] + s16lo[1][q], b_lo = s16lo[2][q] + s16lo[3][q];
+        const uint32_t a_hi = s16hi[0][q] + s16hi[1][q], b_hi = s16hi[2][q] + s16hi[3][q];
+        s32acc[4 * q + 0] = (a_lo & 0xffffu) + (b_lo & 0xffffu);
+        s32acc[4 * q + 1] = (a_lo >> 16) + (b_lo >> 16);
+        s32acc[4 * q + 2] = (a_hi & 0xffffu) + (b_hi & 0xffffu);
+        s32acc[4 * q + 3] = (a_hi >> 16) + (b_hi >> 16);
+    }
+}
+
+// 32x32 PU of a quadrant: key = raw << 14 | idx  (raw <= 130560 < 2^17)
+__device__ __forceinline__ uint32_t track32(uint32_t best, const uint32_t (&s32acc)[16], const uint32_t (&idx)[16])
+{
+#pragma unroll
+    for (int i = 0; i < 16; i += 2) {
+        uint32_t k0 = (s32acc[i] << 14) | idx[i];
+        uint32_t k1 = (s32acc[i + 1] << 14) | idx[i + 1];
+        best = min3u(best, k0, k1);
+    }
+    return best;
+}
+
+// origin, inside its 32x32 quadrant, of 8x8 PU p = 4 zz + k (16x16 block zz, 8x8 k of it: the order of the 8x8 trackers)
+__device__ __forceinline__ void pu8_origin(int p, int& px, int& py)
+{
+    const int zz = p >> 2, k = p & 3;
+    px = 16 * (zz & 1) + 8 * (k & 1);
+    py = 16 * (zz >> 1) + 8 * (k >> 1);
+}
+
+// Resolves the 8x8 winners of quadrant Q after the class search.  The winner of a PU names its item and its SAD
+// (key = sad << 16 | y * 128 + 16 * xg + class) but not the position inside the item: items are disjoint runs of 16 raster positions, so
+// the first minimum in raster order lies in the first item that attains the minimum -- which is what the key order picks.  Lane =
+// 4 * PU + quad recomputes the SADs of positions 4 quad .. 4 quad + 3 of that item (8 v_qsad per lane, once per superblock) from the
+// PU's eight source dwords rs (rows 0, 2, 4, 6 at pu8_origin), and the first position whose SAD equals the minimum is the reference's strict-'<' winner.
+// key: the winning key of PU lane >> 2.
+template <int PITCH>
+__device__ __forceinline__ void resolve_class8(const uint8_t* win, uint32_t key, const uint32_t (&rs)[4][2], int lane, int Q, int xo, int yo,
+                                               uint32_t* osad, uint32_t* omv)
+{
+    const int p = lane >> 2, q = lane & 3;
+    const uint32_t s = key >> 16, id = key & 0xffffu;
+    const int y = (int)(id >> 7), xb = (int)(id & 0x70u);
+    int px, py;
+    pu8_origin(p, px, py);
+    const uint8_t* wp = win + (y + 32 * (Q >> 1) + py) * PITCH + xb + 4 * q + 32 * (Q & 1) + px;
+    uint64_t a = 0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(wp + 2 * r * PITCH);
+        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+        a = __builtin_amdgcn_qsad_pk_u16_u8(pack64(w0, w1), rs[r][0], a);
+        a = __builtin_amdgcn_qsad_pk_u16_u8(pack64(w1, w2), rs[r][1], a);
+    }
+    const uint32_t lo = (uint32_t)a, hi = (uint32_t)(a >> 32);
+    uint32_t first = (lo & 0xffffu) == s ? 0u : (lo >> 16) == s ? 1u : (hi & 0xffffu) == s ? 2u : (hi >> 16) == s ? 3u : 64u;
+    first += 4u * (uint32_t)q;
+    first = min(first, (uint32_t)__shfl_xor((int)first, 1));
+    first = min(first, (uint32_t)__shfl_xor((int)first, 2));
+    if (q == 0) {
+        const int pu = 21 + 16 * Q + p;
+        osad[pu] = 2u * s;
+        omv[pu] = mv_word(xo + xb + (int)first, yo + y);
+    }
+}
+
+// a PU's result from its raw SAD and the raster index of its best position (idx = y * 128 + x, 14 bits)
+__device__ __forceinline__ void store_pu(uint32_t* osad, uint32_t* omv, int pu, uint32_t raw, uint32_t id, int xo, int yo)
+{
+    osad[pu] = 2u * raw;
+    omv[pu] = mv_word(xo + (int)(id & 127u), yo + (int)(id >> 7));
+}
+
+// 64x64 PU: a wave's lanes hold (raw SAD, raster index) of their best position; the four waves meet in the 64-bit LDS cell (set to ~0
+// while the window is staged), which holds the superblock's (raw << 32 | idx) after the next barrier (read_best64)
+__device__ __forceinline__ void merge_best64(unsigned long long* best64_lds, uint32_t raw, uint32_t idx, int lane)
+{
+    const unsigned long long k64 = wave_min_u64(((unsigned long long)raw << 32) | idx);
+    if (lane == 0) atomicMin(best64_lds, k64);
+}
+__device__ __forceinline__ void read_best64(const unsigned long long* best64_lds, uint32_t& raw, uint32_t& id)
+{
+    const unsigned long long k = *best64_lds;
+    raw = (uint32_t)(k >> 32);
+    id = (uint32_t)k;
+}
+
+}  // namespace svthip

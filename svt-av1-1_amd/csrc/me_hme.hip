@@ -16,6 +16,7 @@
 
 #include "../../include/svtav1_hip.h"
 #include "me_kernels.h"
+#include "me_sad_common.h"
 #include "me_wave_reduce.h"
 
 namespace svthip {

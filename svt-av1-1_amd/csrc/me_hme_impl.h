@@ -1,5 +1,5 @@
 // svt-av1-1_amd/csrc/me_hme_impl.h -- search-centre derivation of one superblock by one 256-thread workgroup (device code).
-// Included inside namespace svthip { namespace { ... } } by me_hme.hip.  (A kernel fusing this chain with the full-pel
+// Included inside namespace svthip { namespace { ... } } by me_hme.hip, which includes me_sad_common.h (pack64, min3u, wave_min_u64) first.  (A kernel fusing this chain with the full-pel
 // search of the same superblock was bit-identical but slower -- both halves are VALU-bound -- and was removed.)  See me_hme.hip for the mapping and the reference citations.
 #pragma once
 
@@ -70,16 +70,6 @@ __device__ unsigned long long g_hme_loop_phase[2 * 4];
 // of the 1080p 200 % area (96 x 48 positions: 62 rows x 28 dwords = 6 944 B) in one band; 4 slices + HmeShared stay under
 // 32 KB per workgroup, five workgroups per CU.
 constexpr int kHmeLdsPerWave = 7 * 1024;
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        unsigned long long o = __shfl_xor(v, m);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 // The 64 x 32-row reference block of a centre check (stride already doubled) in two halves, so that a caller can issue the loads
 // before the barrier that publishes the staged source block: lane = (row mod 4, dword column), eight rows per lane.
@@ -192,15 +182,6 @@ __device__ void wave_sad_loop_generic(const uint8_t* src, uint32_t src_stride, c
     *by = (int)(pos / (uint32_t)sw);
     *bx = (int)(pos - (uint32_t)(*by) * (uint32_t)sw);
 }
-
-__device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c)
-{
-    uint32_t r;
-    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-__device__ __forceinline__ uint64_t pack64(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
 
 // Copies `wrows` plane rows of `pitch` dwords each, starting at the (unaligned) address `base`, into LDS (row r at win + r * pitch).
 // Reads up to pitch * 4 + 19 bytes per row (the pool's tail slack covers the last row of the last plane).  pitch <= 256 (a band of at

@@ -9,9 +9,6 @@
 // search_area_width 127) and == 48 dwords, which puts rows y, y+3, y+5, y+6 (one ds_read_b128 lane
 // group) on four distinct bank quarters.
 #define SVTHIP_FULLPEL_LDS_PITCH 192
-#ifndef SVTHIP_FULLPEL_MIN_WAVES
-#define SVTHIP_FULLPEL_MIN_WAVES 3
-#endif
 // fixed LDS in front of the window: 16 KB exchange buffer + 64 B
 #define SVTHIP_FULLPEL_LDS_FIXED (16384 + 64)
 

@@ -16,6 +16,7 @@
 
 #include "../../include/svtav1_hip.h"
 #include "me_kernels.h"
+#include "me_sad_common.h"
 
 namespace svthip {
 
@@ -30,10 +31,6 @@ __device__ __forceinline__ uint32_t lds_u32_at(const lds_u8* p)
     const lds_u32* q = reinterpret_cast<const lds_u32*>((uintptr_t)(a & ~3u));
     return __builtin_amdgcn_alignbyte(q[1], q[0], a & 3u);
 }
-
-// global loads at byte alignment (one global_load_dword / _dwordx4 each; this target needs no alignment for them)
-struct __attribute__((packed, aligned(1))) unaligned_u32 { uint32_t v; };
-struct __attribute__((packed, aligned(1))) unaligned_u32x4 { uint32_t v[4]; };
 
 }  // namespace
 

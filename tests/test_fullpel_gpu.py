@@ -50,7 +50,7 @@ def test_fullpel_854x480_all_sbs(hip_ctx, oracle):
 
 
 def test_fullpel_unaligned_reference_offsets(hip_ctx, oracle):
-    """Every byte alignment of the search-window origin (the LDS staging re-aligns with v_alignbyte)."""
+    """Every byte alignment of the search-window origin (the LDS staging reads the plane at byte alignment and writes ds_write_b128)."""
     cur, ref = _pictures(256, 128, "random", seed=5)
     desc = svtav1_hip.make_fullpel_desc(cur, ref, [(dx, 0) for dx in range(-3, 5)], 33, 17)
     _compare(hip_ctx, oracle, cur, ref, desc)
