@@ -617,6 +617,71 @@ int32_t svthip_av1_highbd_inter_pred_batch_dev(svthip_ctx *ctx, const svthip_int
 int32_t svthip_inter_pred_refused(svthip_ctx *ctx, uint32_t *out_count);
 
 /* ---------------------------------------------------------------------------------------------
+ * Warped-motion (WARPED_CAUSAL) inter prediction of whole PUs: Y, Cb and Cr of a batch of prediction units of ONE luma size, each exactly
+ * what one call of warped_motion_prediction (Codec/EbInterPrediction.c:2528-2861) writes.  Callers: mode decision's
+ * inter_pu_prediction_av1 (:4229, candidate_ptr->motion_mode == WARPED_CAUSAL) and EncDec (Codec/EbCodingLoop.c:3603-3663).  Per PU:
+ *   luma     av1_warp_plane(wm, .., ref Y at picture sample (0, 0), width, height, stride, dst, p_col = pu_origin_x, p_row = pu_origin_y,
+ *            bwidth, bheight, dst_stride, 0, 0, conv_params) with get_conv_params_no_round(0, 0, 0, NULL, 128, 0, bd) (round_0 = 3, not
+ *            compound): av1_warp_affine_c / av1_highbd_warp_affine_c (Codec/EbWarpedMotion.c:672-798 / :389-511), per 8x8 output block a
+ *            15x8 horizontal and an 8x8 vertical pass of 8 taps, the filter row chosen per sample from Warped_Filters[193][8];
+ *   chroma   if has_uv and bwidth >= 16 && bheight >= 16 (:2592-2644): the same warp on Cb and Cr with subsampling 1, 1,
+ *            p_col = pu_origin_x >> 1, p_row = pu_origin_y >> 1, (bwidth / 2) x (bheight / 2), plane size (width >> 1) x (height >> 1),
+ *            destination at ((dst_origin >> 3) << 3) / 2;
+ *            if has_uv otherwise (:2645-2707): translational prediction of bwidth_uv x bheight_uv with interp_filters = 0, the vector
+ *            mv_unit->mv[REF_LIST_0], clamp_mv_to_umv_border_sb(xd, mv, bwidth_uv, bheight_uv, 1, 1), source at
+ *            ((pu_origin >> 3) << 3) / 2 -- the chroma job of svthip_av1_inter_pred_batch_dev with pred_direction = 0, run by the same
+ *            convolution kernels.
+ * The entry is single-reference (the reference asserts !is_compound): `ref` is the one picture the caller passes as ref_pic_list0.
+ *
+ * Planes: as for svthip_av1_inter_pred_batch_dev (pointers at picture sample (0, 0), strides in samples).  The warp reads the reference
+ * with coordinates clamped to [0, pic_width - 1] x [0, pic_height - 1] (chroma: the halved sizes), as the reference does (:721, :736), so
+ * warped planes need no border.  pic_width / pic_height = ref_pic_list0->width / ->height.  PUs whose chroma is translational (a side
+ * of 8) inherit that entry's border rule for the chroma planes.
+ *
+ * svthip_warp_pu_desc (64 bytes), field by field:
+ *   pu_origin_x/y     warped_motion_prediction's pu_origin_x / _y (luma sample position in the reference picture)
+ *   dst_origin_x/y    its dst_origin_x / _y (luma sample position in the prediction planes)
+ *   mb_to_*_edge      cu_ptr->av1xd->mb_to_left_edge / _right_edge / _top_edge / _bottom_edge; read only by the translational chroma
+ *   wmmat[6]          wm_params->wmmat[0..5] (EbWarpedMotionParams).  For ROTZOOM wmmat[4], wmmat[5] are replaced by -wmmat[3], wmmat[2]
+ *                     as warp_plane does (Codec/EbWarpedMotion.c:806-809, :921-924)
+ *   alpha..delta      wm_params->alpha / beta / gamma / delta as get_shear_params (:344-373) left them
+ *   mv[2]             mv_unit->mv[REF_LIST_0] as (row, col) = (y, x); read only by the translational chroma
+ *   wmtype            wm_params->wmtype (TransformationType): 2 ROTZOOM, 3 AFFINE
+ *   has_uv            blk_geom->has_uv
+ *
+ * bwidth x bheight: one of the 17 AV1 block sizes with min(bwidth, bheight) >= 8 (is_motion_variation_allowed_bsize,
+ * Codec/EbEntropyCoding.c:1285).  Refused with svthip_last_error text: any other size, a null pointer when n_pu > 0 (n_pu == 0 returns
+ * OK), a descriptor array that is not 16-byte aligned, pic_width / pic_height of 0 or above 65535, a bit_depth other than 10 (16-bit
+ * entry).  Refused on the device (nothing written for that PU, counted; svthip_inter_pred_refused reports and clears the count): a model
+ * that fails the reference's validity tests (wmmat[2] <= 0, 4|alpha| + 7|beta| >= 65536, 4|gamma| + 4|delta| >= 65536,
+ * Codec/EbWarpedMotion.c:329-341 -- the filter-row index would leave [0, 192], an assert in the reference), a wmtype other than 2 or 3,
+ * and a translational chroma block beyond the border (as in svthip_av1_inter_pred_batch_dev).
+ * Nothing in the call synchronises with the host; context scratch is used as by svthip_av1_inter_pred_batch_dev.
+ *
+ * Out of scope: warped_motion_prediction_md (:2864-, the 16-bit mode-decision variant that unpacks to 8 bits and reads Cr with list 1's
+ * stride: run the 8-bit entry on the 8-bit planes instead); deriving the model (wm_find_samples, select_samples, find_projection: a serial
+ * walk of the mode-info grid and a few dozen integer operations per candidate, host work like av1_build_quantizer); the compound /
+ * do_average / use_jnt_comp_avg arms of the warp functions (never reached through this caller); global motion. */
+typedef struct svthip_warp_pu_desc {
+    uint16_t pu_origin_x, pu_origin_y;
+    uint16_t dst_origin_x, dst_origin_y;
+    int32_t mb_to_left_edge, mb_to_right_edge, mb_to_top_edge, mb_to_bottom_edge;
+    int32_t wmmat[6];
+    int16_t alpha, beta, gamma, delta;
+    int16_t mv[2];             /* [row, col] */
+    uint8_t wmtype;
+    uint8_t has_uv;
+    uint8_t reserved[2];
+} svthip_warp_pu_desc;
+
+int32_t svthip_av1_warped_pred_batch_dev(svthip_ctx *ctx, const svthip_inter_planes *ref, const svthip_inter_planes *dst,
+                                         uint32_t pic_width, uint32_t pic_height, const svthip_warp_pu_desc *d_desc, uint32_t n_pu,
+                                         uint32_t bwidth, uint32_t bheight, void *stream);
+int32_t svthip_av1_highbd_warped_pred_batch_dev(svthip_ctx *ctx, const svthip_inter_planes *ref, const svthip_inter_planes *dst,
+                                                uint32_t pic_width, uint32_t pic_height, const svthip_warp_pu_desc *d_desc, uint32_t n_pu,
+                                                uint32_t bwidth, uint32_t bheight, uint32_t bit_depth, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one
  * transform type at a time from ProductFullLoopTxSearch (Codec/EbFullLoop.c:1138-1352: for every tx_type candidate of a TU:
  * Av1EstimateTransform -> Av1QuantizeInvQuantize -> distortion -> cost), encode_pass_tx_search (:1354-1550) and Av1EncodeLoop

@@ -158,6 +158,11 @@ hipError_t launch_inter_pred(const svthip_inter_planes& ref0, const svthip_inter
                              uint32_t* refused, hipStream_t s);
 size_t inter_pred_scratch_bytes(uint32_t n_pu);
 bool inter_pred_has_pieces(int bw, int bh);
+// ip_warp.hip: warped-motion prediction of whole PUs (the warp kernel; translational chroma through the counted convolution kernels)
+hipError_t launch_warped_pred(const svthip_inter_planes& ref, const svthip_inter_planes& dst, int pic_w, int pic_h, const svthip_warp_pu_desc* desc,
+                              uint32_t n_pu, int bw, int bh, int bd, void* scratch, uint32_t* refused, hipStream_t s);
+size_t warp_scratch_bytes(uint32_t n_pu);
+bool warp_size_valid(int bw, int bh);
 hipError_t launch_av1_convolve_sr(const uint8_t* src, uint32_t src_stride, uint8_t* dst, uint32_t dst_stride, const svthip_convolve_desc* desc,
                                   uint32_t n_blocks, int w, int h, hipStream_t s);
 

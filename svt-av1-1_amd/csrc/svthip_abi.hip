@@ -37,7 +37,7 @@ struct svthip_ctx {
     int device;
     hipStream_t stream;
     // grow-only device scratch: slots 0-4 host-pointer full-pel form, 5 per-list ME arrays, 6 bi-pred SADs, 7 stored predictions,
-    // 8-15 host-pointer picture / TU forms, 16 whole-PU inter prediction job lists, 17 its refused-PU counter
+    // 8-15 host-pointer picture / TU forms, 16 whole-PU inter prediction / warped prediction job lists, 17 their refused-PU counter
     void* scratch[18];
     size_t scratch_bytes[18];
     // stream of the last whole-PU inter prediction call (svthip_inter_pred_refused synchronises with it)
@@ -979,6 +979,56 @@ int32_t svthip_av1_highbd_inter_pred_batch_dev(svthip_ctx* ctx, const svthip_int
     return inter_pred_entry(ctx, ref0, ref1, dst, d_desc, n_pu, bwidth, bheight, (int)bit_depth, stream);
 }
 
+namespace {
+// the warped entries share slot 16 (job list of the translational chroma) and the refusal counter of slot 17 with inter_pred_entry
+int32_t warped_pred_entry(svthip_ctx* ctx, const svthip_inter_planes* ref, const svthip_inter_planes* dst, uint32_t pic_width, uint32_t pic_height,
+                          const svthip_warp_pu_desc* d_desc, uint32_t n_pu, uint32_t bwidth, uint32_t bheight, int bd, void* stream)
+{
+    if (!svthip::warp_size_valid((int)bwidth, (int)bheight))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "not an AV1 block size of at least 8x8%s (width %d)", "", (int)bwidth);
+    if (n_pu == 0) return SVTHIP_OK;
+    if (!ref || !dst || !d_desc) return fail(SVTHIP_ERR_BAD_PARAMETER, "null pointer argument%s", "");
+    for (const svthip_inter_planes* p : {ref, dst})
+        if (!p->y || !p->cb || !p->cr) return fail(SVTHIP_ERR_BAD_PARAMETER, "null plane pointer%s", "");
+    if (reinterpret_cast<uintptr_t>(d_desc) & 15u) return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor array must be 16-byte aligned%s", "");
+    if (!pic_width || !pic_height || pic_width > 65535u || pic_height > 65535u)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "pic_width and pic_height must be 1..65535%s (width %d)", "", (int)pic_width);
+    if (bd > 8)
+        for (const svthip_inter_planes* p : {ref, dst})
+            if ((reinterpret_cast<uintptr_t>(p->y) | reinterpret_cast<uintptr_t>(p->cb) | reinterpret_cast<uintptr_t>(p->cr)) & 1u)
+                return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned%s", "");
+    if (n_pu > 0x00ffffffu) return fail(SVTHIP_ERR_BAD_PARAMETER, "too many PUs in one call%s (%d)", "", (int)n_pu);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    int32_t rc;
+    if ((rc = scratch_on_stream(ctx, s))) return rc;
+    const bool first = ctx->scratch[17] == nullptr;
+    if ((rc = ensure_scratch(ctx, 16, svthip::warp_scratch_bytes(n_pu)))) return rc;
+    if ((rc = ensure_scratch(ctx, 17, 256))) return rc;
+    if (first) HIP_TRY(hipMemsetAsync(ctx->scratch[17], 0, 256, s));
+    HIP_TRY(svthip::launch_warped_pred(*ref, *dst, (int)pic_width, (int)pic_height, d_desc, n_pu, (int)bwidth, (int)bheight, bd, ctx->scratch[16],
+                                       static_cast<uint32_t*>(ctx->scratch[17]), s));
+    ctx->inter_stream = s;
+    return SVTHIP_OK;
+}
+}  // namespace
+
+int32_t svthip_av1_warped_pred_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* ref, const svthip_inter_planes* dst, uint32_t pic_width,
+                                         uint32_t pic_height, const svthip_warp_pu_desc* d_desc, uint32_t n_pu, uint32_t bwidth, uint32_t bheight,
+                                         void* stream)
+{
+    ENTER(ctx);
+    return warped_pred_entry(ctx, ref, dst, pic_width, pic_height, d_desc, n_pu, bwidth, bheight, 8, stream);
+}
+
+int32_t svthip_av1_highbd_warped_pred_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* ref, const svthip_inter_planes* dst, uint32_t pic_width,
+                                                uint32_t pic_height, const svthip_warp_pu_desc* d_desc, uint32_t n_pu, uint32_t bwidth,
+                                                uint32_t bheight, uint32_t bit_depth, void* stream)
+{
+    ENTER(ctx);
+    if (bit_depth != 10) return fail(SVTHIP_ERR_BAD_PARAMETER, "bit_depth must be 10%s (got %d)", "", (int)bit_depth);
+    return warped_pred_entry(ctx, ref, dst, pic_width, pic_height, d_desc, n_pu, bwidth, bheight, (int)bit_depth, stream);
+}
+
 int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
 {
     ENTER(ctx);
@@ -992,7 +1042,7 @@ int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
     if (!n) return SVTHIP_OK;
     HIP_TRY(hipMemsetAsync(ctx->scratch[17], 0, sizeof(n), s));
     *out_count = n;
-    return fail(SVTHIP_ERR_BAD_PARAMETER, "%s%d PU(s) refused: BI_PRED with sub-8x8 chroma, or a block outside the border its edges describe", "", (int)n);
+    return fail(SVTHIP_ERR_BAD_PARAMETER, "%s%d PU(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, or an invalid warp model", "", (int)n);
 }
 
 int32_t svthip_open_loop_intra_search_batch_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* cur, uint32_t n_jobs,

@@ -141,6 +141,11 @@ def lib() -> C.CDLL:
                                                   C.c_void_p]
     L.svthip_av1_highbd_inter_pred_batch_dev.restype = C.c_int32
     L.svthip_av1_highbd_inter_pred_batch_dev.argtypes = L.svthip_av1_inter_pred_batch_dev.argtypes[:-1] + [C.c_uint32, C.c_void_p]
+    L.svthip_av1_warped_pred_batch_dev.restype = C.c_int32
+    L.svthip_av1_warped_pred_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32, C.c_void_p]
+    L.svthip_av1_highbd_warped_pred_batch_dev.restype = C.c_int32
+    L.svthip_av1_highbd_warped_pred_batch_dev.argtypes = L.svthip_av1_warped_pred_batch_dev.argtypes[:-1] + [C.c_uint32, C.c_void_p]
     L.svthip_inter_pred_refused.restype = C.c_int32
     L.svthip_inter_pred_refused.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.svthip_motion_estimate_picture.restype = C.c_int32
@@ -809,6 +814,33 @@ def _inter_pred_refused(self):
 Context.av1_inter_pred_batch_dev = _av1_inter_pred_batch_dev
 Context.av1_highbd_inter_pred_batch_dev = _av1_highbd_inter_pred_batch_dev
 Context.inter_pred_refused = _inter_pred_refused
+
+
+# ---- warped-motion prediction of whole PUs (svthip_av1_warped_pred_batch_dev / svthip_av1_highbd_warped_pred_batch_dev) ----
+WARP_PU_DESC_DTYPE = np.dtype([("pu_origin_x", "<u2"), ("pu_origin_y", "<u2"), ("dst_origin_x", "<u2"), ("dst_origin_y", "<u2"),
+                               ("mb_to_left_edge", "<i4"), ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"),
+                               ("wmmat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"),
+                               ("mv", "<i2", (2,)), ("wmtype", "u1"), ("has_uv", "u1"), ("reserved", "u1", (2,))])
+assert WARP_PU_DESC_DTYPE.itemsize == 64
+WARP_ROTZOOM, WARP_AFFINE = 2, 3
+WARP_BLOCK_SIZES_WH = [s for s in AV1_BLOCK_SIZES_WH if min(s) >= 8]
+
+
+def _av1_warped_pred_batch_dev(self, ref, dst, pic_width, pic_height, d_desc, n_pu, bwidth, bheight, stream=None):
+    """8-bit warped-motion prediction (Y, Cb, Cr) of n_pu PUs of one luma size; ref / dst are InterPlanes, d_desc a device array of
+    WARP_PU_DESC_DTYPE, pic_width x pic_height the reference picture's size (the warp clamps its reads to it)."""
+    _check(lib().svthip_av1_warped_pred_batch_dev(self._h, _planes_arg(ref), _planes_arg(dst), pic_width, pic_height, d_desc, n_pu, bwidth,
+                                                  bheight, stream))
+
+
+def _av1_highbd_warped_pred_batch_dev(self, ref, dst, pic_width, pic_height, d_desc, n_pu, bwidth, bheight, bit_depth=10, stream=None):
+    """The same for 16-bit planes holding 10-bit samples."""
+    _check(lib().svthip_av1_highbd_warped_pred_batch_dev(self._h, _planes_arg(ref), _planes_arg(dst), pic_width, pic_height, d_desc, n_pu,
+                                                         bwidth, bheight, bit_depth, stream))
+
+
+Context.av1_warped_pred_batch_dev = _av1_warped_pred_batch_dev
+Context.av1_highbd_warped_pred_batch_dev = _av1_highbd_warped_pred_batch_dev
 
 
 # ---- host-pointer picture and TU forms (svthip_motion_estimate_picture / svthip_open_loop_intra_search_picture / svthip_encode_tu_batch) ----

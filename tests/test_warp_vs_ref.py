@@ -1,0 +1,158 @@
+"""Pins the numpy restatement of warped_motion_prediction (tests/warp_util.py) and the warp filter table (tools/gen_warp_filter.py)
+against the reference's own warped_motion_prediction / get_shear_params: through the committed fixture tests/golden/warp.npz everywhere, and
+re-derived live where the reference and oracle/_ref exist.  Also checks what the fixture covers, the table's properties, that the
+generated .inc is the committed one, and that the warped entries are declared, exported and laid out as the header says.  CPU only."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools")]
+
+import inter_pred_util as ipu  # noqa: E402
+import svtav1_hip  # noqa: E402
+import warp_util as wu  # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "warp.npz")
+NEW_SYMBOLS = ("svthip_av1_warped_pred_batch_dev", "svthip_av1_highbd_warped_pred_batch_dev")
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return dict(np.load(GOLDEN))
+
+
+@pytest.fixture(scope="module")
+def pictures():
+    from make_golden_warp import reference_picture
+    return {bd: reference_picture(bd) for bd in (8, 10)}
+
+
+def fixture_cases(g):
+    for i in range(len(g["case_bw"])):
+        s, n = int(g["case_start"][i]), int(g["case_count"][i])
+        yield i, int(g["case_bw"][i]), int(g["case_bh"][i]), int(g["case_bd"][i]), g["desc"][s:s + n].view(svtav1_hip.WARP_PU_DESC_DTYPE)
+
+
+def empty_pred(bd, pic):
+    from make_golden_warp import FILL
+    dt = np.uint8 if bd == 8 else np.uint16
+    return ipu.Picture(np.full((pic, pic), FILL[bd], dt), np.full((pic // 2, pic // 2), FILL[bd], dt), np.full((pic // 2, pic // 2), FILL[bd], dt), 0)
+
+
+def test_restatement_reproduces_fixture(golden, pictures):
+    from make_golden_warp import PIC
+    for i, bw, bh, bd, desc in fixture_cases(golden):
+        pred = empty_pred(bd, PIC)
+        assert wu.predict(pictures[bd], pred, desc, bw, bh, bd, PIC, PIC) == 0
+        for p in ("y", "cb", "cr"):
+            want = golden[f"pred_{p}_{bd}"][int(golden["case_pred"][i])]
+            bad = np.argwhere(getattr(pred, p) != want)
+            assert bad.size == 0, (i, (bw, bh, bd), p, bad[:4])
+
+
+def test_fixture_covers_the_ground(golden, pictures):
+    from make_golden_warp import PIC
+    per = [(bw, bh, bd, d) for _, bw, bh, bd, d in fixture_cases(golden)]
+    for bd in (8, 10):
+        mine = [(bw, bh, d) for bw, bh, b, d in per if b == bd]
+        assert {(bw, bh) for bw, bh, _ in mine} == set(wu.SIZES) and len(wu.SIZES) == 17
+        stats = wu.new_stats()
+        modes, uv, types, signs, clamped = set(), set(), set(), set(), set()
+        for bw, bh, desc in mine:
+            wu.predict(pictures[bd], empty_pred(bd, PIC), desc, bw, bh, bd, PIC, PIC, stats)
+            for d in desc:
+                uv.add(int(d["has_uv"]))
+                types.add(int(d["wmtype"]))
+                for k in ("alpha", "beta", "gamma", "delta"):
+                    if d[k]:
+                        signs.add((k, int(d[k]) > 0))
+                if d["has_uv"]:
+                    modes.add("warp" if bw >= 16 and bh >= 16 else "translation")
+                if d["has_uv"] and not (bw >= 16 and bh >= 16):
+                    r, c = ipu.clamp_mv(d, d["mv"][0], d["mv"][1], max(4, bw >> 1), max(4, bh >> 1), 1)
+                    if c != int(d["mv"][1]):
+                        clamped.add("left" if c < 0 else "right")
+                    if r != int(d["mv"][0]):
+                        clamped.add("top" if r < 0 else "bottom")
+        assert modes == {"warp", "translation"} and uv == {0, 1} and types == {wu.ROTZOOM, wu.AFFINE}
+        assert signs == {(k, s) for k in ("alpha", "beta", "gamma", "delta") for s in (False, True)}
+        # every row of the table selected in both passes: this is what pins the table
+        assert np.flatnonzero(stats["h"] == 0).size == 0, np.flatnonzero(stats["h"] == 0)
+        assert np.flatnonzero(stats["v"] == 0).size == 0, np.flatnonzero(stats["v"] == 0)
+        assert stats["edges"] == {(k, e) for k in ("y", "c") for e in ("left", "right", "top", "bottom")}
+        assert stats["outside"] > 0
+        assert len(clamped) >= 2, clamped
+
+
+def test_restatement_rederived_live_against_reference():
+    import make_golden_warp as mg
+    if not mg.reference_available():
+        pytest.skip("the reference sources / oracle/_ref are not on this machine")
+    rng = np.random.default_rng(78)
+    with tempfile.TemporaryDirectory() as tmp:
+        L = mg.build_driver(tmp)
+        for bd in (8, 10):
+            ref = mg.reference_picture(bd)
+            for (bw, bh) in wu.SIZES:
+                desc = wu.random_descs(rng, min(6, (mg.PIC // bw) * (mg.PIC // bh)), bw, bh, mg.PIC, mg.PIC, edge_frac=0.4, clamp_frac=0.3)
+                want, got = empty_pred(bd, mg.PIC), empty_pred(bd, mg.PIC)
+                mg.reference_predict(L, ref, want, desc, bw, bh, bd)
+                assert wu.predict(ref, got, desc, bw, bh, bd, mg.PIC, mg.PIC) == 0
+                for p in ("y", "cb", "cr"):
+                    assert np.array_equal(getattr(got, p), getattr(want, p)), ((bw, bh, bd), p)
+        # get_shear_params: return value and the four parameters, valid and invalid matrices
+        n_bad = 0
+        for i in range(4000):
+            scale = (300, 6000, 40000, 1 << 20)[i % 4]
+            m = [0, 0] + [int(v) for v in rng.integers(-scale, scale + 1, 4)]
+            if i % 5:
+                m[2] += 1 << 16
+                m[5] += 1 << 16
+            if i % 97 == 0:
+                m[2] = int(rng.integers(-3, 2))
+            got, want = wu.shear_params(m), mg.reference_shear(L, m)
+            assert got == want, (m, got, want)
+            n_bad += not want[0]
+        assert 100 < n_bad < 3900
+
+
+def test_table_properties_and_generated_file():
+    import gen_warp_filter as gw
+    rows = gw.ROWS
+    assert len(rows) == 193 and all(len(r) == 8 for r in rows)
+    assert all(sum(r) == 128 for r in rows)
+    assert min(min(r) for r in rows) >= -22 and max(max(r) for r in rows) <= 127
+    assert all(rows[i][::-1] == rows[192 - i] for i in range(1, 192))
+    assert rows[0][::-1] != rows[192]
+    with open(os.path.join(ROOT, "svt-av1-1_amd", "csrc", "av1_warp_filter.inc")) as f:
+        assert f.read() == gw.render()
+    assert wu.DIV_LUT[0] == 16384 and wu.DIV_LUT[256] == 8192 and len(wu.DIV_LUT) == 257
+
+
+def test_warp_symbols_declared_and_exported():
+    with open(os.path.join(ROOT, "include", "svtav1_hip.h")) as f:
+        declared = set(re.findall(r"\b(svthip_\w+)\s*\(", f.read()))
+    lib = svtav1_hip.lib()
+    for name in NEW_SYMBOLS:
+        assert name in declared, name
+        assert hasattr(lib, name), name
+    assert svtav1_hip.WARP_PU_DESC_DTYPE.itemsize == 64
+    assert hasattr(svtav1_hip.Context, "av1_warped_pred_batch_dev") and hasattr(svtav1_hip.Context, "av1_highbd_warped_pred_batch_dev")
+
+
+def test_descriptor_layout_in_c99():
+    dt = svtav1_hip.WARP_PU_DESC_DTYPE
+    checks = "".join(f'_Static_assert(offsetof(svthip_warp_pu_desc, {n}) == {dt.fields[n][1]}, "{n}");\n' for n in dt.names)
+    src = ('#include <stddef.h>\n#include "svtav1_hip.h"\n_Static_assert(sizeof(svthip_warp_pu_desc) == 64, "size");\n' + checks +
+           "int main(void) { return 0; }\n")
+    with tempfile.TemporaryDirectory() as tmp:
+        c = os.path.join(tmp, "layout.c")
+        with open(c, "w") as f:
+            f.write(src)
+        subprocess.check_call(["cc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), c])
