@@ -188,6 +188,14 @@ def test_me_entries_reject_bad_arguments(hip_ctx):
         hip_ctx.subpel_refine209_dev(p, 256, p, 256, p, 1, 128, 64, out.data_ptr(), out.data_ptr())
     with pytest.raises(svtav1_hip.SvtHipError, match="null"):
         hip_ctx.subpel_refine209_dev(p, 256, p, 256, p, 1, 64, 64, None, out.data_ptr())
+    with pytest.raises(svtav1_hip.SvtHipError, match="multiples of 4"):
+        hip_ctx.subpel_refine209_dev(p, 256, p, 250, p, 1, 64, 64, out.data_ptr(), out.data_ptr())         # stride not 4-aligned
+    with pytest.raises(svtav1_hip.SvtHipError, match="multiples of 4"):
+        hip_ctx.bipred_pack209_dev(p, 256, p, 256, p, p, 250, p, 1, 64, 64, out.data_ptr(), out.data_ptr(), out.data_ptr(), out.data_ptr(), 2,
+                                   out.data_ptr())
+    with pytest.raises(svtav1_hip.SvtHipError, match="search area"):
+        hip_ctx.bipred_pack209_dev(p, 256, p, 256, p, p, 256, p, 1, 64, 128, out.data_ptr(), out.data_ptr(), out.data_ptr(), out.data_ptr(), 2,
+                                   out.data_ptr())
     with pytest.raises(svtav1_hip.SvtHipError, match="n_lists"):
         hip_ctx.bipred_pack209_dev(p, 256, p, 256, p, p, 256, p, 1, 64, 64, out.data_ptr(), out.data_ptr(), out.data_ptr(), out.data_ptr(), 3,
                                    out.data_ptr())

@@ -181,6 +181,9 @@ def test_refusals(hip_ctx):
             hip_ctx.av1_highbd_warped_pred_batch_dev(p0, pp, 512, 256, d_desc.data_ptr(), n, bw, bh, bit_depth=12)
         with pytest.raises(E, match="bit_depth"):
             hip_ctx.av1_highbd_warped_pred_batch_dev(p0, pp, 512, 256, d_desc.data_ptr(), n, bw, bh, bit_depth=8)
+        odd = svtav1_hip.InterPlanes(p0.y, p0.cb + 1, p0.cr, p0.y_stride, p0.c_stride)          # 16-bit planes are 2-byte aligned
+        with pytest.raises(E, match="2-byte"):
+            hip_ctx.av1_highbd_warped_pred_batch_dev(odd, pp, 512, 256, d_desc.data_ptr(), n, bw, bh, bit_depth=10)
         hip_ctx.av1_warped_pred_batch_dev(None, None, 512, 256, None, 0, bw, bh)               # n_pu == 0: OK
         assert hip_ctx.inter_pred_refused() == 0                                               # nothing refused so far
 
