@@ -16,10 +16,20 @@
 //   * lane l owns 16 horizontally consecutive search positions of one row; a 16-pixel block row
 //     against 16 positions is 16 x v_qsad_pk_u16_u8 on 8 window dwords (the sliding 4-position
 //     SAD does the byte alignment for free; measured 4 x the cost of v_sad_u8 for 4 x the work);
-//   * best (SAD, position) pairs are tracked as packed 32-bit keys  sad << 16 | raster_index  with
-//     v_min3_u32, which reproduces the reference's strict-'<' raster-order rule exactly;
+//   * best (SAD, position) pairs are tracked as packed 32-bit keys with unsigned minima, which
+//     reproduces the reference's strict-'<' raster-order rule exactly.  Areas whose width is a
+//     multiple of 16 (every one not clipped at a picture edge; the class forms of me_fullpel_impl.h)
+//     pay the key once per (PU, ITEM), an item being a lane's 16 positions: the item's SADs are first
+//     reduced to their minimum (v_pk_min_u16 for the 8x8 and 16x16 PUs, v_min3_u32 for the 32x32), and
+//     key = min << 16 | y * 128 + 16 * xg  (32x32: << 14) names the first item that attains the
+//     minimum.  After the search, once per superblock, resolve_items (me_fullpel_common.h) recomputes
+//     the winning items' SADs -- lane = 4 * (8x8 part) + position quad, three passes of 8 v_qsad for
+//     the 8x8, 16x16 and 32x32 winners -- and takes the first position that equals the minimum.
+//     Clipped areas keep one key  sad << 16 | raster_index  per (PU, position);
 //   * 64x64 sums cross the four waves through a 16 KB LDS exchange buffer, each wave finishing a
-//     quarter of the positions.
+//     quarter of the positions.  Up to 64x64 positions the 64x64 PU's key is  sum << 12 | y * 64 + x
+//     (sum < 2^19), one per position and exact without a resolver; larger areas track (sum, index)
+//     pairs with compare and select.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -22,13 +22,13 @@ constexpr unsigned long long kRowLut = 0xFEAB6732DC894510ull;
 // d: the superblock's descriptor (6 int32: src_offset, ref_offset, x/y search origin, search width/height), any address space;
 // smem: SVTHIP_FULLPEL_LDS_FIXED + (sh + 63) * SVTHIP_FULLPEL_LDS_PITCH bytes of workgroup LDS, 16-byte aligned (IMG2: fullpel_img2_lds_bytes()).
 // Results go to out_sad / out_mv [85 * sbi ...].  Must be called by all 256 threads.
-// CLS (search width a multiple of 16, the usual case; wave-uniform): the 8x8 PUs -- 256 of the 336 (PU, position) candidates of an item --
-// are tracked per position CLASS (track_class8) and the winner's position inside its item is found after the search (resolve_class8).
+// CLS (search width a multiple of 16, the usual case; wave-uniform): the 8x8, 16x16 and 32x32 PUs are tracked per ITEM (track_item16 /
+// track_item32: the minimum of the item's 16 SADs with the item's first raster index) and the winners' positions inside their items are
+// found after the search (resolve_items); up to 64x64 positions the 64x64 PU is tracked as one 32-bit key per position (track_quad64).
 // IMG2 (with CLS, search width exactly 64, height <= 64): the window is staged twice at pitch kPitch2, image 1 four bytes later than
 // image 0, and a row step reads W0..7 from image 0 and W1..8 from image 1, so that every dword pair a v_qsad takes starts at an even
 // register of an aligned ds_read_b128 and the six v_mov_b32 per row step that formed the odd pairs are gone.  The lane -> item map is
-// (row = 16 it + kRowLut[lane >> 2], column group = lane & 3): results depend on the item, not on the lane that holds it, and a lane's
-// rows still ascend with `it`, which the strict-'<' update of the 64x64 PU needs.
+// (row = 16 it + kRowLut[lane >> 2], column group = lane & 3): results depend on the item, not on the lane that holds it.
 template <bool CLS, bool IMG2 = false>
 __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_plane, uint32_t src_stride,
                                              const uint8_t* __restrict__ ref_plane, uint32_t ref_stride, const int32_t* d, uint32_t sbi,
@@ -77,7 +77,8 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
     for (int i = 0; i < 16; i++) best8[i] = 0xffffffffu;
 #pragma unroll
     for (int i = 0; i < 4; i++) best16[i] = 0xffffffffu;
-    uint32_t best64_raw = 0xffffffffu, best64_idx = 0;
+    uint32_t best64_raw = 0xffffffffu, best64_idx = 0;  // key64: best64_raw holds the key of track_quad64
+    const bool key64 = CLS && (IMG2 || (sw <= 64 && sh <= 64));
 
     const uint32_t himask = 0xffff0000u;
     const int n_items = n_xg * sh;
@@ -97,18 +98,20 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
             lane_valid = fullpel_raster_item(it, lane, n_items, n_xg, D.inv_xg, y, xg);
         }
 
-        // per-position raster index; positions outside the search area get idx = ~0 so that every key
-        // OR-ed with it is 0xffffffff and can never win (at least one position is always valid).  A lane past the last item
-        // repeats item 0 (IMG2: row 0 of its column group): its keys duplicate a first-pass lane's and change no minimum.  Areas whose width is a multiple
-        // of 16 (the usual case) have no outside positions at all: one add per position instead of compare + select.
+        // A lane past the last item repeats item 0 (IMG2: row 0 of its column group): its keys duplicate a first-pass lane's and change
+        // no minimum.  CLS: every position of an item is inside the area, and the keys carry the item's first raster index alone.
+        // General form: per-position raster index; positions outside the search area get idx = ~0 so that every key OR-ed with it is
+        // 0xffffffff and can never win (at least one position is always valid).
         uint32_t idx[16];
         const uint32_t idx0 = fullpel_idx0(y, xg);
-        if (IMG2 || (sw & 15) == 0) {
+        if constexpr (!CLS) {
+            if ((sw & 15) == 0) {
 #pragma unroll
-            for (int i = 0; i < 16; i++) idx[i] = idx0 + (uint32_t)i;
-        } else {
+                for (int i = 0; i < 16; i++) idx[i] = idx0 + (uint32_t)i;
+            } else {
 #pragma unroll
-            for (int i = 0; i < 16; i++) idx[i] = (16 * xg + i < sw) ? idx0 + (uint32_t)i : 0xffffffffu;
+                for (int i = 0; i < 16; i++) idx[i] = (16 * xg + i < sw) ? idx0 + (uint32_t)i : 0xffffffffu;
+            }
         }
 
         uint32_t s16lo[4][4], s16hi[4][4];  // [zz][q] packed u16 16x16 sums
@@ -187,7 +190,9 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 if constexpr (CLS) {
-                    best8[4 * zz + k] = track_class8(best8[4 * zz + k], acc[k], &idx[0], himask);
+                    const uint32_t d[8] = {(uint32_t)acc[k][0], (uint32_t)(acc[k][0] >> 32), (uint32_t)acc[k][1], (uint32_t)(acc[k][1] >> 32),
+                                           (uint32_t)acc[k][2], (uint32_t)(acc[k][2] >> 32), (uint32_t)acc[k][3], (uint32_t)(acc[k][3] >> 32)};
+                    best8[4 * zz + k] = track_item16(best8[4 * zz + k], d, idx0, himask);
                 } else {
 #pragma unroll
                     for (int q = 0; q < 4; q++) best8[4 * zz + k] = track4(best8[4 * zz + k], acc[k][q], &idx[4 * q], himask);
@@ -200,15 +205,20 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
                 const uint32_t lo = (uint32_t)acc[0][q] + (uint32_t)acc[1][q] + (uint32_t)acc[2][q] + (uint32_t)acc[3][q];
                 const uint32_t hi = (uint32_t)(acc[0][q] >> 32) + (uint32_t)(acc[1][q] >> 32) +
                                     (uint32_t)(acc[2][q] >> 32) + (uint32_t)(acc[3][q] >> 32);
-                best16[zz] = track4(best16[zz], pack64(lo, hi), &idx[4 * q], himask);
+                if constexpr (!CLS) best16[zz] = track4(best16[zz], pack64(lo, hi), &idx[4 * q], himask);
                 s16lo[zz][q] = lo;
                 s16hi[zz][q] = hi;
+            }
+            if constexpr (CLS) {
+                const uint32_t d[8] = {s16lo[zz][0], s16hi[zz][0], s16lo[zz][1], s16hi[zz][1], s16lo[zz][2], s16hi[zz][2], s16lo[zz][3], s16hi[zz][3]};
+                best16[zz] = track_item16(best16[zz], d, idx0, himask);
             }
         }
 
         uint32_t s32acc[16];
         widen_sums32(s16lo, s16hi, s32acc);
-        best32 = track32(best32, s32acc, idx);
+        if constexpr (CLS) best32 = track_item32(best32, s32acc, idx0);
+        else best32 = track32(best32, s32acc, idx);
 
         // 64x64: exchange 32x32 sums between the four waves; wave Q finishes positions 4Q..4Q+3
         __syncthreads();  // previous iteration's readers are done
@@ -228,15 +238,18 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
                 s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
             }
             const uint32_t sv[4] = {s.x, s.y, s.z, s.w};
-            // idx of position 4Q+j of this lane: idx[] is indexed statically, so select by Q
-            const int xbase = 16 * xg + 4 * Q;
-            const uint32_t ibase = (uint32_t)(y * 128 + xbase);
+            const int xbase = 16 * xg + 4 * Q;  // this wave finishes positions 4Q .. 4Q+3 of the item
+            if (key64) {
+                best64_raw = track_quad64(best64_raw, sv, y, xbase);
+            } else {
+                const uint32_t ibase = (uint32_t)(y * 128 + xbase);
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                // strict '<', positions visited in raster order per lane; positions outside the area never win
-                const bool better = (sv[j] < best64_raw) && lane_valid && (xbase + j < sw);
-                best64_raw = better ? sv[j] : best64_raw;
-                best64_idx = better ? (ibase + j) : best64_idx;
+                for (int j = 0; j < 4; j++) {
+                    // strict '<', positions visited in raster order per lane; positions outside the area never win
+                    const bool better = (sv[j] < best64_raw) && lane_valid && (xbase + j < sw);
+                    best64_raw = better ? sv[j] : best64_raw;
+                    best64_idx = better ? (ibase + j) : best64_idx;
+                }
             }
         }
     }
@@ -252,20 +265,23 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
     const uint32_t g16 = wave_min_scatter<8, 5>(top, lane);
 
     if constexpr (CLS) {
-        // resolve the 8x8 winners: lane = 4 * PU + quad takes PU's key from the lane that holds it
-        resolve_class8<P>(win, (uint32_t)__shfl((int)g8, lane >> 2), rsv, lane, Q, xo, yo, osad, omv);
-    }
-    if (lane < 21 && !(CLS && lane < 16)) {
+        // resolve the winners' positions: lane = 4 * part + quad takes the keys of the part's 8x8 PU, of its 16x16 PU and of the 32x32 PU
+        // from the lanes that hold them
+        resolve_items<P>(win, (uint32_t)__shfl((int)g8, lane >> 2), (uint32_t)__shfl((int)g16, lane >> 4), (uint32_t)__shfl((int)g16, 4), rsv,
+                         lane, Q, xo, yo, osad, omv);
+    } else if (lane < 21) {
         const uint32_t key = lane < 16 ? g8 : g16;
         const int pu = lane < 16 ? 21 + 16 * Q + lane : lane < 20 ? 5 + 4 * Q + (lane - 16) : 1 + Q;
         const uint32_t raw = lane == 20 ? key >> 14 : key >> 16, id = key & 0x3fffu;
         store_pu(osad, omv, pu, raw, id, xo, yo);
     }
-    merge_best64(best64_lds, best64_raw, best64_idx, lane);
+    if (key64) merge_best64_key(best64_lds, best64_raw, lane);
+    else merge_best64(best64_lds, best64_raw, best64_idx, lane);
     __syncthreads();
     if (tid == 0) {
         uint32_t raw, id;
-        read_best64(best64_lds, raw, id);
+        if (key64) read_best64_key(best64_lds, raw, id);
+        else read_best64(best64_lds, raw, id);
         store_pu(osad, omv, 0, raw, id, xo, yo);
     }
 }

@@ -50,6 +50,14 @@ __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
     return r;
 }
 
+// the same through the compiler's own packed minimum: it knows the instruction, so it schedules a tree of them without the s_nop that
+// follows every inline-asm result used by the next instruction
+typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_min_u16_tree(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2_t, a), __builtin_bit_cast(u16x2_t, b)));
+}
+
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
 {
 #pragma unroll
