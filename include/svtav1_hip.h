@@ -682,6 +682,62 @@ int32_t svthip_av1_highbd_warped_pred_batch_dev(svthip_ctx *ctx, const svthip_in
                                                 uint32_t bwidth, uint32_t bheight, uint32_t bit_depth, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * AV1 intra prediction of transform blocks: a batch of blocks of ONE TxSize, each exactly what one call of build_intra_predictors /
+ * build_intra_predictors_high (Codec/EbIntraPrediction.c:8823-9080 / :9082-9317) writes.  Callers: av1_predict_intra_block (:9512; EncDec,
+ * Codec/EbCodingLoop.c:3288 / :3362; mode decision through AV1IntraPredictionCL, :10032) and av1_predict_intra_block_16bit (:9837,
+ * EbCodingLoop.c:3215).  The contract is the reference as configured: DIS_EDGE_FIL = 1 (no edge filter, no corner filter, no upsampling),
+ * filter_intra_mode = FILTER_INTRA_MODES, no palette.
+ *
+ * Per block the device builds above_row[-1 .. txw + txh) and left_col[-1 .. txw + txh) the reference's way -- the available samples, the
+ * last one repeated beyond them; for a missing side the other side's first sample, or 127 / 129 (base - 1 / base + 1 with
+ * base = 128 << (bd - 8) at 10 bits); the corner above_ref[-1] when both sides exist, else the first sample of the side that does, else
+ * 128 (base) -- and runs dc_pred[n_left_px > 0][n_top_px > 0], V, H, SMOOTH, SMOOTH_V, SMOOTH_H, PAETH or, for the eight directional
+ * modes, dr_predictor (:7984): zone 1 for p_angle < 90, zone 2 for 90 < p_angle < 180, zone 3 above 180, plain V / H at exactly 90 / 180.
+ * Mode decision's edges (generate_intra_reference_samples, :8531-8821: both edges whole, no constant fill) and EncDec's (only what the mode
+ * reads, one value when the mode's only edge is missing) give the same block for the same four counts; the device has one semantic.
+ *
+ * svthip_intra_desc (32 bytes), offsets and strides in SAMPLES of d_edge / d_dst / d_src:
+ *   above_offset       position of above_ref[0] in d_edge.  above_ref[0 .. n_top_px + n_topright_px) is read, and above_ref[-1] when
+ *                      n_top_px > 0 && n_left_px > 0
+ *   left_offset/stride position of left_ref[0] and the distance between consecutive left samples: 1 for a neighbour array as the
+ *                      reference passes it, the plane stride to read column x - 1 of a reconstruction plane.
+ *                      left_ref[i * left_stride] is read for i < n_left_px + n_bottomleft_px
+ *   dst_offset/stride  where the txw x txh block is written in d_dst.  d_dst may be d_edge (in-place EncDec prediction); the blocks of
+ *                      one call must not overlap each other or any edge sample the call reads
+ *   n_top_px .. n_bottomleft_px   the four counts av1_predict_intra_block passes down (:9830-9833); deriving them (has_top_right /
+ *                      has_bottom_left: table look-ups on the partition tree) is host work
+ *   mode               PredictionMode 0 .. 12 (DC_PRED .. PAETH_PRED)
+ *   angle_delta        -3 .. 3: p_angle = mode_to_angle_map[mode] + 3 * angle_delta (directional modes)
+ *   src_offset/stride  8-bit entry with d_sad only: the source block
+ *
+ * d_sad (8-bit entry, may be NULL): d_sad[i] = the SAD of the predicted block against d_src + src_offset (NxMSadKernelSubSampled with
+ * sub_sampled_pred = 0, the fast loop's distortion, Codec/EbProductCodingLoop.c:1337-1370).  With d_sad == NULL d_src may be NULL.
+ *
+ * tx_size: TxSize 0 .. 18 (TX_4X4 .. TX_64X16), the numbering of svthip_tu_batcher_add.  Refused with svthip_last_error text:
+ * tx_size >= 19, a null d_edge / d_dst / d_desc when n_blocks > 0 (n_blocks == 0 returns OK), a descriptor array that is not 16-byte
+ * aligned, a bit_depth other than 10 (16-bit entry), d_sad without d_src.  Refused on the device (nothing written for that block,
+ * counted; svthip_inter_pred_refused reports and clears the count) -- the reference's asserts: mode > 12, |angle_delta| > 3, a count above
+ * the block side, n_topright_px > 0 with n_top_px != txw, n_bottomleft_px > 0 with n_left_px != txh.
+ * Nothing in the call synchronises with the host.
+ *
+ * Out of scope: CfL, the edge / corner filter and upsampling (compiled out of the reference), filter-intra, palette, 12-bit video. */
+typedef struct svthip_intra_desc {
+    uint32_t above_offset;
+    uint32_t left_offset, left_stride;
+    uint32_t dst_offset, dst_stride;
+    uint8_t n_top_px, n_topright_px, n_left_px, n_bottomleft_px;
+    uint8_t mode;
+    int8_t angle_delta;
+    uint16_t src_stride;
+    uint32_t src_offset;
+} svthip_intra_desc;
+
+int32_t svthip_av1_intra_pred_batch_dev(svthip_ctx *ctx, const uint8_t *d_edge, uint8_t *d_dst, const svthip_intra_desc *d_desc,
+                                        uint32_t n_blocks, uint32_t tx_size, const uint8_t *d_src, uint32_t *d_sad, void *stream);
+int32_t svthip_av1_highbd_intra_pred_batch_dev(svthip_ctx *ctx, const uint16_t *d_edge, uint16_t *d_dst, const svthip_intra_desc *d_desc,
+                                               uint32_t n_blocks, uint32_t tx_size, uint32_t bit_depth, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one
  * transform type at a time from ProductFullLoopTxSearch (Codec/EbFullLoop.c:1138-1352: for every tx_type candidate of a TU:
  * Av1EstimateTransform -> Av1QuantizeInvQuantize -> distortion -> cost), encode_pass_tx_search (:1354-1550) and Av1EncodeLoop

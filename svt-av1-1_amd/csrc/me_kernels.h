@@ -163,6 +163,10 @@ hipError_t launch_warped_pred(const svthip_inter_planes& ref, const svthip_inter
                               uint32_t n_pu, int bw, int bh, int bd, void* scratch, uint32_t* refused, hipStream_t s);
 size_t warp_scratch_bytes(uint32_t n_pu);
 bool warp_size_valid(int bw, int bh);
+// ip_intra.hip: AV1 intra prediction of transform blocks of one TxSize (edges built on the device, optional SAD at 8 bits)
+hipError_t launch_intra_pred(const void* edge, void* dst, const svthip_intra_desc* desc, uint32_t n_blocks, int tx_size, int bd, const uint8_t* src,
+                             uint32_t* sad, uint32_t* refused, hipStream_t s);
+bool intra_tx_size_valid(uint32_t tx_size);
 hipError_t launch_av1_convolve_sr(const uint8_t* src, uint32_t src_stride, uint8_t* dst, uint32_t dst_stride, const svthip_convolve_desc* desc,
                                   uint32_t n_blocks, int w, int h, hipStream_t s);
 

@@ -554,6 +554,27 @@ int32_t warped_pred_entry(svthip_ctx* ctx, const svthip_inter_planes* ref, const
     return SVTHIP_OK;
 }
 
+// Intra prediction of transform blocks shares only the refusal counter with the two families above: it has no job list.
+int32_t intra_pred_entry(svthip_ctx* ctx, const void* d_edge, void* d_dst, const svthip_intra_desc* d_desc, uint32_t n_blocks, uint32_t tx_size,
+                         int bd, const uint8_t* d_src, uint32_t* d_sad, void* stream)
+{
+    if (!svthip::intra_tx_size_valid(tx_size)) return fail(SVTHIP_ERR_BAD_PARAMETER, "tx_size must be 0..18 (got %d)", (int)tx_size);
+    if (n_blocks == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_edge, d_dst, d_desc}));
+    if (!aligned(d_desc, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor array must be 16-byte aligned");
+    if (bd > 8 && !aligned({d_edge, d_dst}, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
+    if (d_sad && !d_src) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sad needs d_src");
+    if (d_sad && !aligned(d_sad, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sad must be 4-byte aligned");
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(scratch_on_stream(ctx, s));
+    const bool first = ctx->scratch[SLOT_INTER_REFUSED] == nullptr;
+    TRY(ensure_scratch(ctx, SLOT_INTER_REFUSED, 256));
+    if (first) HIP_TRY(hipMemsetAsync(ctx->scratch[SLOT_INTER_REFUSED], 0, 256, s));
+    HIP_TRY(svthip::launch_intra_pred(d_edge, d_dst, d_desc, n_blocks, (int)tx_size, bd, d_src, d_sad, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
+    ctx->inter_stream = s;
+    return SVTHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1095,6 +1116,21 @@ int32_t svthip_av1_highbd_warped_pred_batch_dev(svthip_ctx* ctx, const svthip_in
     return warped_pred_entry(ctx, ref, dst, pic_width, pic_height, d_desc, n_pu, bwidth, bheight, (int)bit_depth, stream);
 }
 
+int32_t svthip_av1_intra_pred_batch_dev(svthip_ctx* ctx, const uint8_t* d_edge, uint8_t* d_dst, const svthip_intra_desc* d_desc, uint32_t n_blocks,
+                                        uint32_t tx_size, const uint8_t* d_src, uint32_t* d_sad, void* stream)
+{
+    TRY(enter(ctx));
+    return intra_pred_entry(ctx, d_edge, d_dst, d_desc, n_blocks, tx_size, 8, d_src, d_sad, stream);
+}
+
+int32_t svthip_av1_highbd_intra_pred_batch_dev(svthip_ctx* ctx, const uint16_t* d_edge, uint16_t* d_dst, const svthip_intra_desc* d_desc,
+                                               uint32_t n_blocks, uint32_t tx_size, uint32_t bit_depth, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return intra_pred_entry(ctx, d_edge, d_dst, d_desc, n_blocks, tx_size, (int)bit_depth, nullptr, nullptr, stream);
+}
+
 int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
 {
     TRY(enter(ctx));
@@ -1109,7 +1145,7 @@ int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
     if (!n) return SVTHIP_OK;
     HIP_TRY(hipMemsetAsync(d_refused, 0, sizeof(n), s));
     *out_count = n;
-    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, or an invalid warp model", (int)n);
+    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, or an intra descriptor the reference would assert on", (int)n);
 }
 
 // ---------------------------------------------------------------- host-pointer forms (run_queued: no transfer outlives a failed call)

@@ -146,6 +146,12 @@ def lib() -> C.CDLL:
                                                    C.c_uint32, C.c_void_p]
     L.svthip_av1_highbd_warped_pred_batch_dev.restype = C.c_int32
     L.svthip_av1_highbd_warped_pred_batch_dev.argtypes = L.svthip_av1_warped_pred_batch_dev.argtypes[:-1] + [C.c_uint32, C.c_void_p]
+    L.svthip_av1_intra_pred_batch_dev.restype = C.c_int32
+    L.svthip_av1_intra_pred_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+    L.svthip_av1_highbd_intra_pred_batch_dev.restype = C.c_int32
+    L.svthip_av1_highbd_intra_pred_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                         C.c_void_p]
     L.svthip_inter_pred_refused.restype = C.c_int32
     L.svthip_inter_pred_refused.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.svthip_motion_estimate_picture.restype = C.c_int32
@@ -841,6 +847,31 @@ def _av1_highbd_warped_pred_batch_dev(self, ref, dst, pic_width, pic_height, d_d
 
 Context.av1_warped_pred_batch_dev = _av1_warped_pred_batch_dev
 Context.av1_highbd_warped_pred_batch_dev = _av1_highbd_warped_pred_batch_dev
+
+
+# ---- intra prediction of transform blocks (svthip_av1_intra_pred_batch_dev / svthip_av1_highbd_intra_pred_batch_dev) ----
+INTRA_DESC_DTYPE = np.dtype([("above_offset", "<u4"), ("left_offset", "<u4"), ("left_stride", "<u4"), ("dst_offset", "<u4"), ("dst_stride", "<u4"),
+                             ("n_top_px", "u1"), ("n_topright_px", "u1"), ("n_left_px", "u1"), ("n_bottomleft_px", "u1"), ("mode", "u1"),
+                             ("angle_delta", "i1"), ("src_stride", "<u2"), ("src_offset", "<u4")])
+assert INTRA_DESC_DTYPE.itemsize == 32
+# (width, height) of TxSize 0 .. 18 (TX_4X4 .. TX_64X16)
+TX_SIZES_WH = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 8), (8, 4), (8, 16), (16, 8), (16, 32), (32, 16), (32, 64), (64, 32), (4, 16),
+               (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
+
+
+def _av1_intra_pred_batch_dev(self, d_edge, d_dst, d_desc, n_blocks, tx_size, d_src=None, d_sad=None, stream=None):
+    """8-bit intra prediction of n_blocks transform blocks of one TxSize; d_desc a device array of INTRA_DESC_DTYPE, d_edge the samples
+    the edges are read from, d_dst where the blocks go (may be d_edge); d_sad (uint32 per block) asks for the SAD against d_src."""
+    _check(lib().svthip_av1_intra_pred_batch_dev(self._h, d_edge, d_dst, d_desc, n_blocks, tx_size, d_src, d_sad, stream))
+
+
+def _av1_highbd_intra_pred_batch_dev(self, d_edge, d_dst, d_desc, n_blocks, tx_size, bit_depth=10, stream=None):
+    """The same for 16-bit samples holding 10-bit values (no SAD)."""
+    _check(lib().svthip_av1_highbd_intra_pred_batch_dev(self._h, d_edge, d_dst, d_desc, n_blocks, tx_size, bit_depth, stream))
+
+
+Context.av1_intra_pred_batch_dev = _av1_intra_pred_batch_dev
+Context.av1_highbd_intra_pred_batch_dev = _av1_highbd_intra_pred_batch_dev
 
 
 # ---- host-pointer picture and TU forms (svthip_motion_estimate_picture / svthip_open_loop_intra_search_picture / svthip_encode_tu_batch) ----

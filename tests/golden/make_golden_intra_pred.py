@@ -1,0 +1,247 @@
+"""Writes tests/golden/intra_pred.npz from the reference's own build_intra_predictors / build_intra_predictors_high and
+av1_predict_intra_block (tests/golden/ref_intra_pred_driver.c linked against the reference objects of the oracle build,
+oracle/_ref/obj_all, with EbIntraPrediction.o left out: the driver includes that source to reach its statics).  Run in the build container
+only, where the reference exists: the fixture is data and is what the GPU box checks.
+
+    python tests/golden/make_golden_intra_pred.py
+
+Contents
+  case                 one row per batch: tx_size, bit depth, desc[start : start + count], edge samples [start : start + len] and output
+                       samples [start : start + len] of that depth's arrays
+  desc                 INTRA_DESC_DTYPE rows of every batch (what the device entry takes; offsets relative to the batch's arrays)
+  edge_8 / edge_10     the neighbour arrays the reference read (per block: pad, sample -1, above 0 .. 2 txw, left 0 .. 2 txh)
+  out_8 / out_10       the reference's blocks, txw x txh each, in descriptor order
+  pos                  the batches' blocks that came from picture positions: batch row, block, width, height, shape, x, y.  Their four
+                       counts are what the reference derives at that position of a PIC_W x PIC_H picture, and their blocks are
+                       av1_predict_intra_block's (ED_STAGE, 8 bits) / av1_predict_intra_block_16bit's (10 bits), which the generator
+                       checks to equal build_intra_predictors[_high] given those counts.  Every position is run with V, H, D45 and D203,
+                       which between them read every sample the four counts admit, so a wrong count cannot pass that check.
+  md, md_out           8-bit position blocks run again through mode decision's sequence (generate_intra_reference_samples, then
+                       av1_predict_intra_block with MD_STAGE): batch row and block per entry, and the blocks it wrote, concatenated.
+                       The generator checks them to equal the ED blocks of out_8.
+Coverage (coverage() below, asserted again by tests/test_intra_pred_vs_ref.py::test_fixture_covers_the_ground): 19 sizes x the 12 modes the reference
+has (it has no PAETH predictor: pred[PAETH_PRED] is never assigned) at 8 and 10 bits, the 56 directional (mode, delta) pairs at 4x4, 8x8, 16x4, 4x16, 32x32, 64x64 at each depth, the four dc_pred arms, every substitute for a
+missing side, partial n_top_px / n_left_px from blocks at the right / bottom picture edge at each depth, at least 40 mode-decision blocks, top-right and bottom-left zero / partial / full,
+zone 1 past max_base (zone 3 cannot get there: its steepest legal angle, 212 degrees, steps 40 / 64 of a sample per column, so
+its base stays below txw + txh - 1), zone 2 reading both edges in one row, outputs 0 and the maximum."""
+import ctypes as C
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+
+import intra_pred_util as iu  # noqa: E402
+
+REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
+OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
+OUT = os.path.join(HERE, "intra_pred.npz")
+PIC_W, PIC_H = 200, 136
+DIR_SIZES = (0, 1, 14, 13, 3, 4)   # 4x4, 8x8, 16x4, 4x16, 32x32, 64x64
+PART_N, PART_H, PART_V, PART_H4, PART_V4 = 0, 1, 2, 7, 8
+
+
+def reference_available():
+    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL)
+
+
+def build_driver(out_dir):
+    """The recipe of make_golden_inter_pred.build_driver (--gc-sections from the drv_* roots, EbEncHandle.o left out, NASM-only symbols that
+    stay unresolved made weak), with EbIntraPrediction.o left out as well: the driver includes that source."""
+    S = os.path.join(REF_ROOT, "Source")
+    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
+    src = os.path.join(HERE, "ref_intra_pred_driver.c")
+    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
+    so, vmap, weak = os.path.join(out_dir, "libref_intra.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
+    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
+    with open(vmap, "w") as f:
+        f.write("{ global: drv_*; local: *; };\n")
+    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL) if o.endswith(".o") and o not in ("EbEncHandle.o", "EbIntraPrediction.o"))
+
+    def link(o):
+        subprocess.check_call(["gcc", "-shared", "-o", so, *objs, o, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
+
+    link(obj)
+    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
+    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
+    with open(weak, "w") as f:
+        f.write("\n".join(names) + "\n")
+    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
+    link(wobj)
+    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    L.drv_init.restype = C.c_int
+    L.drv_build.restype = C.c_int
+    L.drv_build.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.drv_position.restype = C.c_int
+    L.drv_position.argtypes = [C.c_int] * 10 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.drv_md.restype = C.c_int
+    L.drv_md.argtypes = [C.c_int] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.drv_init()
+    return L
+
+
+def reference_blocks(L, edge, desc, tx_size, bd):
+    """The reference's block for every descriptor of a batch in iu.random_case's layout (left_stride 1, sample -1 in front of above 0;
+    the left array gets the same sample -1 in front, as the reference's callers arrange it)."""
+    txw, txh = iu.TX_SIZES_WH[tx_size]
+    dt = edge.dtype
+    out = np.zeros((len(desc), txh, txw), dt)
+    for i, d in enumerate(desc):
+        ao, lo = int(d["above_offset"]), int(d["left_offset"])
+        above = np.ascontiguousarray(edge[ao - 1:ao + 2 * txw])
+        left = np.ascontiguousarray(np.concatenate([edge[ao - 1:ao], edge[lo:lo + 2 * txh]]))
+        counts = np.array([d["n_top_px"], d["n_topright_px"], d["n_left_px"], d["n_bottomleft_px"]], np.int32)
+        blk = np.full((txh, txw), iu.FILL[bd], dt)
+        L.drv_build(bd, above.ctypes.data, left.ctypes.data, blk.ctypes.data, txw, int(d["mode"]), int(d["angle_delta"]), tx_size, counts.ctypes.data)
+        out[i] = blk
+    return out
+
+
+POSITION_MODES = ((iu.V, 0), (iu.H, 0), (iu.D45, 0), (iu.D203, 0))
+
+
+def position_list():
+    """(tx_size, w, h, shape, x, y): blocks whose transform block is the block, aligned as their partition puts them, at the origin, at a
+    superblock boundary, inside, and crossing the right / bottom edge of the PIC_W x PIC_H picture"""
+    out = []
+    for ts, (w, h) in enumerate(iu.TX_SIZES_WH):
+        shape = PART_N if w == h else (PART_H if w == 2 * h else PART_V if h == 2 * w else PART_H4 if w == 4 * h else PART_V4)
+        last_x = (PIC_W // w) * w if PIC_W % w else PIC_W - w
+        last_y = (PIC_H // h) * h if PIC_H % h else PIC_H - h
+        if w * h > 256:
+            pts = [(0, 0), (64, 64), (last_x, 64), (64, last_y)]
+        else:
+            pts = [(x, y) for x in sorted({0, w, 64, last_x}) for y in sorted({0, h, last_y})]
+        out += [(ts, w, h, shape, x, y) for (x, y) in pts if x < PIC_W and y < PIC_H]
+    return out
+
+
+def neighbour_arrays(edge, d, w, h):
+    """above / left with sample -1 at index 0, as the reference's callers hand them over"""
+    ao, lo = int(d["above_offset"]), int(d["left_offset"])
+    return (np.ascontiguousarray(edge[ao - 1:ao + 2 * w]), np.ascontiguousarray(np.concatenate([edge[ao - 1:ao], edge[lo:lo + 2 * h]])))
+
+
+def make_cases(rng, L):
+    """[(tx_size, bd, edge, desc)], pos rows, md rows, md blocks"""
+    cases = []
+    for bd in (8, 10):
+        for ts, (w, h) in enumerate(iu.TX_SIZES_WH):
+            extra = 10 if w * h <= 256 else 3 if w * h <= 1024 else 0
+            edge, desc, _ = iu.random_case(rng, 12 + extra, ts, bd, n_modes=12)
+            desc["mode"][:12] = np.arange(12)
+            cases.append((ts, bd, edge, desc))
+        for ts in DIR_SIZES:
+            w, h = iu.TX_SIZES_WH[ts]
+            # the large blocks mostly from noisy ramps and extremes: their blocks deflate, which keeps the fixture small
+            edge, desc, _ = iu.random_case(rng, 56, ts, bd, n_modes=12, kinds=(0, 1, 2, 3) if w * h <= 256 else (0, 1, 1, 1, 1, 2, 2, 2))
+            desc["mode"] = [m for m, _ in iu.DIRECTIONAL]
+            desc["angle_delta"] = [d for _, d in iu.DIRECTIONAL]
+            desc["n_top_px"], desc["n_left_px"] = w, h
+            desc["n_topright_px"] = rng.choice([0, w, max(1, w // 2)], 56)
+            desc["n_bottomleft_px"] = rng.choice([0, h, max(1, h // 2)], 56)
+            cases.append((ts, bd, edge, desc))
+    # picture positions: the reference's own counts, through its 8-bit and its 16-bit caller, and the mode-decision sequence at 8 bits
+    pos_rows, md_rows, md_blocks = [], [], []
+    by_ts = {}
+    for (ts, w, h, shape, x, y) in position_list():
+        by_ts.setdefault(ts, []).append((w, h, shape, x, y))
+    for bd in (8, 10):
+        for ts, plist in by_ts.items():
+            w, h = iu.TX_SIZES_WH[ts]
+            jobs = [(p, m) for p in plist for m in POSITION_MODES]
+            edge, desc, _ = iu.random_case(rng, len(jobs), ts, bd, n_modes=12)
+            want = []
+            for i, ((w, h, shape, x, y), (mode, delta)) in enumerate(jobs):
+                d = desc[i]
+                d["mode"], d["angle_delta"] = mode, delta
+                above, left = neighbour_arrays(edge, d, w, h)
+                recon = np.full((PIC_H + 64, PIC_W + 64), iu.FILL[bd], edge.dtype)
+                counts = np.zeros(4, np.int32)
+                assert L.drv_position(bd, w, h, shape, x, y, PIC_W, PIC_H, mode, delta, above.ctypes.data, left.ctypes.data, recon.ctypes.data,
+                                      recon.shape[1], counts.ctypes.data) == 0
+                d["n_top_px"], d["n_topright_px"], d["n_left_px"], d["n_bottomleft_px"] = counts
+                want.append(recon[y:y + h, x:x + w].copy())
+                pos_rows.append((len(cases), i, w, h, shape, x, y))
+                if bd == 8 and w * h <= 1024:
+                    blk = np.full((h, w), iu.FILL[8], np.uint8)
+                    assert L.drv_md(w, h, shape, x, y, PIC_W, PIC_H, mode, delta, above.ctypes.data, left.ctypes.data, blk.ctypes.data) == 0
+                    assert np.array_equal(blk, want[-1]), ("the MD_STAGE block differs from the ED_STAGE block", ts, x, y, mode)
+                    md_rows.append((len(cases), i))
+                    md_blocks.append(blk.reshape(-1))
+            got = reference_blocks(L, edge, desc, ts, bd)
+            assert np.array_equal(got, np.stack(want)), ("build_intra_predictors with the derived counts differs from the position call", ts, bd)
+            cases.append((ts, bd, edge, desc))
+    return cases, np.array(pos_rows, np.int32), np.array(md_rows, np.int32), np.concatenate(md_blocks)
+
+
+def coverage(cases):
+    """None when the fixture covers what the module docstring lists, else what is missing (from the restatement's statistics)."""
+    stats = {bd: iu.new_stats() for bd in (8, 10)}
+    seen = {bd: set() for bd in (8, 10)}
+    dirs = {bd: {} for bd in (8, 10)}
+    for (ts, bd, edge, desc) in cases:
+        txw, txh = iu.TX_SIZES_WH[ts]
+        for d in desc:
+            st = iu.new_stats()
+            iu.predict_block(edge, d, txw, txh, bd, st)
+            seen[bd].add((ts, int(d["mode"])))
+            dirs[bd].setdefault(ts, set()).update(st["dir"])
+            for k, v in st.items():
+                if isinstance(v, set):
+                    stats[bd][k] |= v
+                else:
+                    stats[bd][k] += v
+    for bd in (8, 10):
+        s = stats[bd]
+        if len(seen[bd]) != 19 * 12:
+            return (bd, "size x mode", len(seen[bd]))
+        if len(s["dc_arms"]) != 4 or len(s["subst"]) != 10:
+            return (bd, "arms", s["dc_arms"], s["subst"])
+        if len(s["topright"]) != 3 or len(s["bottomleft"]) != 3 or not (s["z1_tail"] and s["z2_both"] and s["zero"] and s["max"]):
+            return (bd, "edges", s)
+        if not (s["partial_top"] and s["partial_left"]):
+            return (bd, "partial counts")
+        for ts in DIR_SIZES:
+            if len(dirs[bd][ts]) != 56:
+                return (bd, "directional pairs", ts, len(dirs[bd][ts]))
+    return None
+
+
+def main():
+    assert reference_available(), "needs the reference sources and oracle/_ref/obj_all (python -c 'import __graft_entry__ as g; g.build()')"
+    with tempfile.TemporaryDirectory() as tmp:
+        L = build_driver(tmp)
+        for seed in range(20261017, 20261017 + 8):
+            cases, pos, md, md_out = make_cases(np.random.default_rng(seed), L)
+            missing = coverage(cases)
+            if missing is None:
+                break
+            print("seed", seed, "misses", missing)
+        else:
+            raise SystemExit("no seed met the coverage conditions")
+        rows, descs = [], []
+        edges, outs = {8: [], 10: []}, {8: [], 10: []}
+        e0, o0, d0 = {8: 0, 10: 0}, {8: 0, 10: 0}, 0
+        for (ts, bd, edge, desc) in cases:
+            blocks = reference_blocks(L, edge, desc, ts, bd).reshape(-1)
+            rows.append((ts, bd, d0, len(desc), e0[bd], len(edge), o0[bd], len(blocks)))
+            d0 += len(desc)
+            e0[bd] += len(edge)
+            o0[bd] += len(blocks)
+            descs.append(desc)
+            edges[bd].append(edge)
+            outs[bd].append(blocks)
+    np.savez_compressed(OUT, case=np.array(rows, np.int64), desc=np.concatenate(descs), pos=pos, md=md, md_out=md_out, seed=np.array([seed]),
+                        edge_8=np.concatenate(edges[8]), edge_10=np.concatenate(edges[10]), out_8=np.concatenate(outs[8]),
+                        out_10=np.concatenate(outs[10]))
+    print(f"wrote {OUT}: seed {seed}, {len(rows)} batches, {d0} blocks, {len(pos)} from positions, {len(md)} through mode decision, {os.path.getsize(OUT) / 1e6:.2f} MB")
+
+
+if __name__ == "__main__":
+    main()
