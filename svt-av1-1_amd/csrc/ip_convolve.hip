@@ -4,13 +4,13 @@
 // Replaces, per block, the function av1_inter_prediction picks from convolve[subpel_x != 0][subpel_y != 0][0]
 // (Source/Lib/Codec/EbInterPrediction.c:898-911, call site :1255-1287):
 //   av1_convolve_2d_sr_c :145-198, av1_convolve_y_sr_c :200-232, av1_convolve_x_sr_c :234-267, av1_convolve_2d_copy_sr_c :269-286,
-// with the filter kernels of av1_get_interp_filter_params_with_block_size (:985-995; tables :106-127, :914-970) and the rounding
-// of get_conv_params_no_round(.., is_compound = 0, bd = 8): round_0 = 3, round_1 = 11 (convolve.h:115-143).
+// with the filter kernels of av1_get_interp_filter_params_with_block_size and the rounding of get_conv_params_no_round(.., is_compound = 0,
+// bd = 8): round_0 = 3, round_1 = 11 (convolve.h:115-143).  The filter table and its block-size rule, the job word, the horizontal rows and
+// the rounding constants of each case are ip_common.h's, shared with the matrix-core, piece and warp kernels.
 //
 // One 256-thread workgroup takes ~4096 output pixels: one block of 64x64 or larger, or 4096 / (w h) smaller blocks.
-//   pass 1  a thread produces 4 horizontally consecutive intermediate samples of one row: 4 aligned dword loads, v_alignbyte to the
-//           8-byte tap window, two v_dot4_i32_i8 per sample on (pixel - 128) bytes (the kernels sum to 128, so the bias is a
-//           constant), rounded to int16 exactly like the reference's im_block, one ds_write_b64 into LDS;
+//   pass 1  a thread produces 4 horizontally consecutive intermediate samples of one row (8 bits: hrow8), rounded to int16 exactly like
+//           the reference's im_block, one ds_write_b64 into LDS;
 //   pass 2  a thread owns 2 adjacent columns of a band of 8 rows and slides down the LDS column with the 8-row window in registers:
 //           one ds_read_b32 and 16 v_mad_i32_i24 per 2 output pixels; 64 lanes store 128 contiguous bytes per row.
 // The x-only, y-only and copy cases run the same two passes with a pass-through in the unused direction and the reference's own
@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
+#include "ip_common.h"
 #include "me_kernels.h"
 
 namespace svthip {
@@ -27,17 +28,6 @@ namespace {
 
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
-
-// [filter 0..5][phase][taps 0-3, taps 4-7] as packed signed bytes
-__device__ const uint32_t kInterp[6][16][2] =
-#include "av1_interp_filters.inc"
-    ;
-
-__device__ __forceinline__ int filter_index(int f, int size)
-{
-    if (size <= 4) return f == 1 ? 5 : (f == 3 ? 3 : 4);  // 4-tap regular for REGULAR / SHARP, 4-tap smooth for SMOOTH (:985-995)
-    return f;
-}
 
 // COMPOUND: descriptors are svthip_convolve_compound_desc; both lists are run (list 0's 16-bit results parked in LDS) and averaged like
 // av1_inter_prediction's BI_PRED path: av1_jnt_convolve_* with round_1 = 7, round_offset = 6144, round_bits = 4 (EbInterPrediction.c:290-528).
@@ -71,17 +61,15 @@ __global__ void __launch_bounds__(256) av1_convolve_sr_kernel(const uint8_t* __r
         const int items1 = nb * rows_im * w4;
         for (int i = tid; i < items1; i += 256) {
             const int g = i / (rows_im * w4), rem = i - g * (rows_im * w4), r = rem / w4, c = 4 * (rem - r * w4);
-            const uint4 d = desc[b0 + g];
-            const uint32_t soff = COMPOUND ? (list ? d.y : d.x) : d.x;
-            const int sx = COMPOUND ? (int)((d.w >> (8 * list)) & 15) : (int)(d.z & 15);
-            const int sy = COMPOUND ? (int)((d.w >> (8 * list + 4)) & 15) : (int)((d.z >> 8) & 15);
-            const int fxt = COMPOUND ? (int)((d.w >> 16) & 255) : (int)((d.z >> 16) & 255);
+            const ConvJob J = decode_job<COMPOUND>(desc[b0 + g], list);
+            const int sx = J.sx, sy = J.sy;
             const int rows = sy ? rows_im : h;  // a vertical filter needs 3 rows above and 4 below
             if (r >= rows) continue;
-            const uint8_t* p = src + ((int64_t)soff + (int64_t)(r - (sy ? 3 : 0)) * src_stride + c - (sx ? 3 : 0)) * SB;
+            const uint8_t* p = src + ((int64_t)J.src + (int64_t)(r - (sy ? 3 : 0)) * src_stride + c - (sx ? 3 : 0)) * SB;
             const uintptr_t a = reinterpret_cast<uintptr_t>(p);
             const uint32_t* q = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
             const uint32_t sh = (uint32_t)(a & 3u);
+            int v[4];
             uint32_t o01, o23;  // four int16
             if (HBD) {
                 // samples p[0..10] as halfwords of six dwords (a plane of 16-bit samples is 2-byte aligned: sh is 0 or 2)
@@ -96,18 +84,12 @@ __global__ void __launch_bounds__(256) av1_convolve_sr_kernel(const uint8_t* __r
                     e[5] = __builtin_amdgcn_alignbyte(qn, e[5], 2);
                 }
                 if (sx) {
-                    const int fi = filter_index(fxt, w);
-                    const uint32_t flo = kInterp[fi][sx][0], fhi = kInterp[fi][sx][1];
+                    const int fi = interp_filter_class(J.fx, w);
                     int f[8], sm[11];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        f[k] = (int)(int8_t)(flo >> (8 * k));
-                        f[4 + k] = (int)(int8_t)(fhi >> (8 * k));
-                    }
+                    unpack_taps(kInterpFilter[fi][sx][0], kInterpFilter[fi][sx][1], f);
 #pragma unroll
                     for (int k = 0; k < 11; k++) sm[k] = (int)((e[k >> 1] >> (16 * (k & 1))) & 0xffffu);
                     const int bias = (sy ? (1 << (bd + 6)) : 0) + 4;  // 2-D: sum = (1 << (bd + FILTER_BITS - 1)) + sum f p; then (sum + 4) >> 3
-                    int v[4];
 #pragma unroll
                     for (int i4 = 0; i4 < 4; i4++) {
                         int acc = bias;
@@ -122,19 +104,8 @@ __global__ void __launch_bounds__(256) av1_convolve_sr_kernel(const uint8_t* __r
                     o23 = e[1];
                 }
             } else if (sx) {
-                const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-                const uint32_t e0 = __builtin_amdgcn_alignbyte(q1, q0, sh) ^ 0x80808080u, e1 = __builtin_amdgcn_alignbyte(q2, q1, sh) ^ 0x80808080u,
-                               e2 = __builtin_amdgcn_alignbyte(q3, q2, sh) ^ 0x80808080u;  // bytes p[0..11] - 128
-                const int fi = filter_index(fxt, w);
-                const uint32_t flo = kInterp[fi][sx][0], fhi = kInterp[fi][sx][1];
-                // reference: sum = (1 << 14) + sum f p (2-D) or sum f p (x only); sum f p = sum f (p - 128) + 128 * 128; then (sum + 4) >> 3
-                const int bias = (sy ? (1 << 15) : (1 << 14)) + 4;
-                int v[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t lo = k ? __builtin_amdgcn_alignbyte(e1, e0, k) : e0, hi = k ? __builtin_amdgcn_alignbyte(e2, e1, k) : e1;
-                    v[k] = __builtin_amdgcn_sdot4((int)hi, (int)fhi, __builtin_amdgcn_sdot4((int)lo, (int)flo, bias, false), false) >> 3;
-                }
+                const int fi = interp_filter_class(J.fx, w);
+                hrow8<4>(p, kInterpFilter[fi][sx][0], kInterpFilter[fi][sx][1], sy != 0, v);
                 o01 = ((uint32_t)v[0] & 0xffffu) | ((uint32_t)v[1] << 16);
                 o23 = ((uint32_t)v[2] & 0xffffu) | ((uint32_t)v[3] << 16);
             } else {  // no horizontal filter: the pixels themselves
@@ -153,40 +124,11 @@ __global__ void __launch_bounds__(256) av1_convolve_sr_kernel(const uint8_t* __r
         const int items2 = nb * bands * w2;
         for (int i = tid; i < items2; i += 256) {
             const int g = i / (bands * w2), rem = i - g * (bands * w2), band = rem / w2, cp = rem - band * w2;
-            const uint4 d = desc[b0 + g];
-            const int sx = COMPOUND ? (int)((d.w >> (8 * list)) & 15) : (int)(d.z & 15);
-            const int sy = COMPOUND ? (int)((d.w >> (8 * list + 4)) & 15) : (int)((d.z >> 8) & 15);
-            const int fyt = COMPOUND ? (int)((d.w >> 24) & 255) : (int)((d.z >> 24) & 255);
-            const uint32_t doff = COMPOUND ? d.z : d.y;
-            int f[8], c0, shift, sub;
+            const ConvJob J = decode_job<COMPOUND>(desc[b0 + g], list);
             const int round_offset = (1 << (bd + 4)) + (1 << (bd + 3)), pix_max = (1 << bd) - 1;
-            if (sy) {
-                const int fi = filter_index(fyt, h);
-                const uint32_t flo = kInterp[fi][sy][0], fhi = kInterp[fi][sy][1];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    f[k] = (int)(int8_t)(flo >> (8 * k));
-                    f[4 + k] = (int)(int8_t)(fhi >> (8 * k));
-                }
-                if (!COMPOUND) {
-                    if (sx) { c0 = (1 << (bd + 11)) + (1 << 10); shift = 11; sub = (1 << bd) + (1 << (bd - 1)); }  // 2-D: offset_bits = bd + 11, round_1 = 11
-                    else { c0 = 64; shift = 7; sub = 0; }                                          // y only: ROUND_POWER_OF_TWO(res, FILTER_BITS)
-                } else {
-                    if (sx) { c0 = (1 << (bd + 11)) + 64; shift = 7; sub = 0; }  // ROUND(sum, round_1 = 7)
-                    else { c0 = 4; shift = 3; sub = -round_offset; }             // ROUND(res << 4, 7) + round_offset
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; k++) f[k] = k == 0;
-                if (!COMPOUND) {
-                    if (sx) { c0 = 8; shift = 4; }  // x only: second rounding, bits = FILTER_BITS - round_0
-                    else { c0 = 0; shift = 0; }     // copy
-                } else {
-                    if (!sx) f[0] = 16;             // copy: (p << 4) + round_offset;  x only: ROUND(sum, 3) + round_offset
-                    c0 = round_offset; shift = 0;
-                }
-                sub = 0;
-            }
+            int f[8];
+            const SecondPass K = second_pass_constants(J.sx, J.sy, interp_filter_class(J.fy, h), COMPOUND, bd, f);
+            const int c0 = K.c0, shift = K.shift, sub = K.sub;
             const lds_u32* col = reinterpret_cast<const lds_u32*>(im + g * blk_bytes) + cp;  // dword = 2 int16 columns; row pitch w2 dwords
             const int y0 = band * RB;
             int lo[RB + 7], hi[RB + 7];
@@ -196,7 +138,7 @@ __global__ void __launch_bounds__(256) av1_convolve_sr_kernel(const uint8_t* __r
                 lo[j] = (int)(int16_t)(v & 0xffffu);
                 hi[j] = (int)v >> 16;
             }
-            uint8_t* out = dst + ((size_t)doff + (size_t)y0 * dst_stride + 2 * cp) * SB;
+            uint8_t* out = dst + ((size_t)J.dst + (size_t)y0 * dst_stride + 2 * cp) * SB;
             lds_u32* park = reinterpret_cast<lds_u32*>(res0 + g * h * w * 2) + cp;  // dword = 2 uint16 columns; row pitch w2 dwords
 #pragma unroll
             for (int j = 0; j < RB; j++) {
@@ -243,80 +185,33 @@ bool convolve_size_valid(int w, int h)
 }
 
 namespace {
-template <bool COMPOUND, bool HBD, bool COUNTED = false>
-hipError_t launch_valu(const void* src0, uint32_t src0_stride, const void* src1, uint32_t src1_stride, void* dst, uint32_t dst_stride, const void* desc,
-                       uint32_t n_blocks, int w, int h, int bd, hipStream_t s)
-{
-    const int per = w * h >= 4096 ? 1 : 4096 / (w * h);
-    const size_t lds = COMPOUND ? convolve_compound_lds_bytes(w, h) : (size_t)per * (h + 7) * w * 2;
-    const uint32_t grid = (n_blocks + per - 1) / per;
-    const uint8_t *a = static_cast<const uint8_t*>(src0), *b = static_cast<const uint8_t*>(src1);
-    if (h >= 8)
-        hipLaunchKernelGGL((av1_convolve_sr_kernel<8, COMPOUND, HBD, COUNTED>), dim3(grid), dim3(256), lds, s, a, src0_stride, b, src1_stride,
-                           static_cast<uint8_t*>(dst), dst_stride, reinterpret_cast<const uint4*>(desc), n_blocks, w, h, per, bd);
-    else
-        hipLaunchKernelGGL((av1_convolve_sr_kernel<4, COMPOUND, HBD, COUNTED>), dim3(grid), dim3(256), lds, s, a, src0_stride, b, src1_stride,
-                           static_cast<uint8_t*>(dst), dst_stride, reinterpret_cast<const uint4*>(desc), n_blocks, w, h, per, bd);
-    return hipGetLastError();
-}
+using ConvolveKernel = void (*)(const uint8_t*, uint32_t, const uint8_t*, uint32_t, uint8_t*, uint32_t, const uint4*, uint32_t, int, int, int, int);
+// every instantiation, [compound][h >= 8][16-bit planes][counted]: launch_convolve_valu picks from it, and the compound half is the list
+// of kernels whose dynamic LDS can pass 64 KB (128-wide compound blocks)
+#define SVTHIP_CONV_ROW(RB, COMPOUND) \
+    {{av1_convolve_sr_kernel<RB, COMPOUND, false, false>, av1_convolve_sr_kernel<RB, COMPOUND, false, true>}, \
+     {av1_convolve_sr_kernel<RB, COMPOUND, true, false>, av1_convolve_sr_kernel<RB, COMPOUND, true, true>}}
+const ConvolveKernel kConvolveKernels[2][2][2][2] = {{SVTHIP_CONV_ROW(4, false), SVTHIP_CONV_ROW(8, false)}, {SVTHIP_CONV_ROW(4, true), SVTHIP_CONV_ROW(8, true)}};
+#undef SVTHIP_CONV_ROW
 }  // namespace
 
-hipError_t launch_av1_convolve_sr(const uint8_t* src, uint32_t src_stride, uint8_t* dst, uint32_t dst_stride, const svthip_convolve_desc* desc,
-                                  uint32_t n_blocks, int w, int h, hipStream_t s)
+void convolve_dynamic_lds_kernels(const void** list)
 {
-    return launch_valu<false, false>(src, src_stride, src, src_stride, dst, dst_stride, desc, n_blocks, w, h, 8, s);
+    static_assert(sizeof(kConvolveKernels[1]) / sizeof(ConvolveKernel) == kConvolveDynamicLdsKernels, "the compound half of the table");
+    for (int i = 0; i < kConvolveDynamicLdsKernels; i++) list[i] = reinterpret_cast<const void*>(kConvolveKernels[1][i >> 2][(i >> 1) & 1][i & 1]);
 }
 
-size_t convolve_compound_lds_bytes(int w, int h)
+hipError_t launch_convolve_valu(const ConvolveLaunch& L, hipStream_t s)
 {
-    const int per = w * h >= 4096 ? 1 : 4096 / (w * h);
-    return (size_t)per * ((h + 7) * w * 2 + h * w * 2);
-}
-
-// the instantiations whose dynamic LDS can pass 64 KB (128-wide compound blocks): svthip_abi.hip raises their limit once per device
-const void* convolve_compound_kernel_ptr(int which)
-{
-    switch (which) {
-    case 0: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<8, true, false>);
-    case 1: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<4, true, false>);
-    case 2: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<8, true, true>);
-    default: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<4, true, true>);
-    }
-}
-
-hipError_t launch_av1_convolve_compound(const uint8_t* src0, uint32_t src0_stride, const uint8_t* src1, uint32_t src1_stride, uint8_t* dst,
-                                        uint32_t dst_stride, const svthip_convolve_compound_desc* desc, uint32_t n_blocks, int w, int h, hipStream_t s)
-{
-    return launch_valu<true, false>(src0, src0_stride, src1, src1_stride, dst, dst_stride, desc, n_blocks, w, h, 8, s);
-}
-
-hipError_t launch_convolve_counted(const void* src0, uint32_t src0_stride, const void* src1, uint32_t src1_stride, void* dst, uint32_t dst_stride,
-                                   const void* desc, uint32_t max_blocks, int w, int h, bool compound, int bd, hipStream_t s)
-{
-    if (max_blocks == 0) return hipSuccess;
-    if (bd > 8)
-        return compound ? launch_valu<true, true, true>(src0, src0_stride, src1, src1_stride, dst, dst_stride, desc, max_blocks, w, h, bd, s)
-                        : launch_valu<false, true, true>(src0, src0_stride, src0, src0_stride, dst, dst_stride, desc, max_blocks, w, h, bd, s);
-    return compound ? launch_valu<true, false, true>(src0, src0_stride, src1, src1_stride, dst, dst_stride, desc, max_blocks, w, h, 8, s)
-                    : launch_valu<false, false, true>(src0, src0_stride, src0, src0_stride, dst, dst_stride, desc, max_blocks, w, h, 8, s);
-}
-
-// the counted compound forms (dynamic LDS above 64 KB for 128-wide blocks, like convolve_compound_kernel_ptr)
-const void* convolve_compound_count_kernel_ptr(int which)
-{
-    switch (which) {
-    case 0: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<8, true, false, true>);
-    case 1: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<4, true, false, true>);
-    case 2: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<8, true, true, true>);
-    default: return reinterpret_cast<const void*>(&av1_convolve_sr_kernel<4, true, true, true>);
-    }
-}
-
-hipError_t launch_av1_highbd_convolve(const uint16_t* src0, uint32_t src0_stride, const uint16_t* src1, uint32_t src1_stride, uint16_t* dst,
-                                      uint32_t dst_stride, const void* desc, bool compound, uint32_t n_blocks, int w, int h, int bd, hipStream_t s)
-{
-    return compound ? launch_valu<true, true>(src0, src0_stride, src1, src1_stride, dst, dst_stride, desc, n_blocks, w, h, bd, s)
-                    : launch_valu<false, true>(src0, src0_stride, src0, src0_stride, dst, dst_stride, desc, n_blocks, w, h, bd, s);
+    if (L.counted && L.n_blocks == 0) return hipSuccess;
+    const int w = L.w, h = L.h, per = w * h >= 4096 ? 1 : 4096 / (w * h);
+    const size_t lds = (size_t)per * ((h + 7) * w * 2 + (L.compound ? h * w * 2 : 0));  // intermediate rows; compound: and list 0's results
+    const uint32_t grid = (L.n_blocks + per - 1) / per;
+    const uint8_t *a = static_cast<const uint8_t*>(L.src0), *b = L.compound ? static_cast<const uint8_t*>(L.src1) : a;
+    hipLaunchKernelGGL(kConvolveKernels[L.compound][h >= 8][L.bd > 8][L.counted], dim3(grid), dim3(256), lds, s, a, L.stride0, b,
+                       L.compound ? L.stride1 : L.stride0, static_cast<uint8_t*>(L.dst), L.dst_stride, reinterpret_cast<const uint4*>(L.desc), L.n_blocks, w,
+                       h, per, L.bd);
+    return hipGetLastError();
 }
 
 }  // namespace svthip

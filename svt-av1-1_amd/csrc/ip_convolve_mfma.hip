@@ -2,8 +2,8 @@
 //
 // AV1 single-reference inter prediction of blocks whose sides are multiples of 32, on the matrix cores (gfx950) -- bit-exact.
 // Same contract as av1_convolve_sr_kernel (ip_convolve.hip): av1_convolve_2d_sr / _x_sr / _y_sr / _2d_copy_sr
-// (reference: Source/Lib/Codec/EbInterPrediction.c:145-286), kernels by av1_get_interp_filter_params_with_block_size (:985-995),
-// rounding of get_conv_params_no_round (round_0 = 3, round_1 = 11).
+// (reference: Source/Lib/Codec/EbInterPrediction.c:145-286), rounding of get_conv_params_no_round (round_0 = 3, round_1 = 11).  The filter
+// table and the job word are ip_common.h's; these sizes never meet the 4-tap rule (interp_filter_class), so filter_x / filter_y index the table.
 //
 // Unlike the transforms, the interpolation IS a dense integer contraction: each pass is a sum of tap x sample
 // products with ONE rounding at its end, so a pass is a product with a banded (Toeplitz) tap matrix and v_mfma_i32_32x32x32_i8
@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
+#include "ip_common.h"
 #include "me_kernels.h"
 
 namespace svthip {
@@ -31,10 +32,6 @@ namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-
-__device__ const uint32_t kInterpM[6][16][2] =
-#include "av1_interp_filters.inc"
-    ;
 
 // bytes [s, s + 8) of the sequence (.. 0, t0 .. t7, 0 ..) whose bytes 0..7 are T
 __device__ __forceinline__ uint64_t seq8(uint64_t T, int s)
@@ -61,10 +58,11 @@ __device__ __forceinline__ void conv_list_tiles(const uint8_t* __restrict__ src,
 {
     // taps as 8 packed signed bytes; a missing pass is the unit tap at k = 0 on an unshifted window (16 for the compound copy: p << 4)
     uint64_t F = 1, G = (compound && !sx && !sy) ? 16 : 1;
-    if (sx) F = ((uint64_t)kInterpM[fx][sx][1] << 32) | kInterpM[fx][sx][0];
-    if (sy) G = ((uint64_t)kInterpM[fy][sy][1] << 32) | kInterpM[fy][sy][0];
+    if (sx) F = ((uint64_t)kInterpFilter[fx][sx][1] << 32) | kInterpFilter[fx][sx][0];
+    if (sy) G = ((uint64_t)kInterpFilter[fy][sy][1] << 32) | kInterpFilter[fy][sy][0];
     const int c0 = sx ? -3 : 0, r0 = sy ? -3 : 0;
     const int rows_needed = 32 * TY + (sy ? 7 : 0), n_kx = sx ? 2 : 1, n_im = TY + (sy ? 1 : 0), n_e = sy ? 2 : 1;
+    // hrow8's bias and second_pass_constants (ip_common.h) seen through the -128 offset of a missing pass 1 and the two-digit split of IM
     const int C1 = sx ? 32768 + 4 : 128, S1 = sx ? 3 : 0;
     int C2, S2;
     if (!compound) {
@@ -185,16 +183,14 @@ __global__ void __launch_bounds__(256, 2) av1_convolve_mfma_kernel(const uint8_t
     if (b >= n_blocks) return;
     const int t = (int)(wave - b * (uint32_t)tiles), ty = t / tiles_x, tx = t - ty * tiles_x;
     const uint4 d = desc[b];
+    const ConvJob J = decode_job<COMPOUND>(d, 0);
     v16i res[TY];
-    uint32_t dst_off;
-    if (!COMPOUND) {
-        conv_list_tiles<TY>(src0, src0_stride, d.x, d.z & 15, (d.z >> 8) & 15, (d.z >> 16) & 255, (d.z >> 24) & 255, false, tx, ty, n, hh, res);
-        dst_off = d.y;
-    } else {
+    conv_list_tiles<TY>(src0, src0_stride, J.src, J.sx, J.sy, J.fx, J.fy, COMPOUND, tx, ty, n, hh, res);
+    if (COMPOUND) {
         v16i r1[TY];
-        conv_list_tiles<TY>(src0, src0_stride, d.x, d.w & 15, (d.w >> 4) & 15, (d.w >> 16) & 255, (d.w >> 24) & 255, true, tx, ty, n, hh, res);
         __builtin_amdgcn_sched_barrier(0);
-        conv_list_tiles<TY>(src1, src1_stride, d.y, (d.w >> 8) & 15, (d.w >> 12) & 15, (d.w >> 16) & 255, (d.w >> 24) & 255, true, tx, ty, n, hh, r1);
+        const ConvJob J1 = decode_job<COMPOUND>(d, 1);
+        conv_list_tiles<TY>(src1, src1_stride, J1.src, J1.sx, J1.sy, J1.fx, J1.fy, true, tx, ty, n, hh, r1);
 #pragma unroll
         for (int ot = 0; ot < TY; ot++)
 #pragma unroll
@@ -203,11 +199,10 @@ __global__ void __launch_bounds__(256, 2) av1_convolve_mfma_kernel(const uint8_t
                 asm volatile("" : "+v"(v));
                 res[ot][reg] = v;
             }
-        dst_off = d.z;
     }
 #pragma unroll
     for (int ot = 0; ot < TY; ot++) {
-        const uint32_t o = dst_off + (uint32_t)(32 * (TY * ty + ot) + 4 * hh) * dst_stride + (uint32_t)(32 * tx + n);
+        const uint32_t o = J.dst + (uint32_t)(32 * (TY * ty + ot) + 4 * hh) * dst_stride + (uint32_t)(32 * tx + n);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
             int v = res[ot][reg];
@@ -219,53 +214,19 @@ __global__ void __launch_bounds__(256, 2) av1_convolve_mfma_kernel(const uint8_t
 
 bool convolve_mfma_size_valid(int w, int h) { return (w & 31) == 0 && (h & 31) == 0 && w >= 32 && h >= 32 && w <= 128 && h <= 128; }
 
-hipError_t launch_av1_convolve_sr_mfma(const uint8_t* src, uint32_t src_stride, uint8_t* dst, uint32_t dst_stride, const svthip_convolve_desc* desc,
-                                       uint32_t n_blocks, int w, int h, hipStream_t s)
+hipError_t launch_convolve_mfma(const ConvolveLaunch& L, hipStream_t s)
 {
-    const int ty = (h & 63) == 0 ? 2 : 1;
-    const uint64_t waves = (uint64_t)n_blocks * (uint32_t)((w >> 5) * (h / (32 * ty)));
-    const dim3 grid((uint32_t)((waves + 3) / 4)), block(256);
-    const uint4* dd = reinterpret_cast<const uint4*>(desc);
-    if (ty == 2)
-        hipLaunchKernelGGL((av1_convolve_mfma_kernel<2, false>), grid, block, 0, s, src, src_stride, src, src_stride, dst, dst_stride, dd, n_blocks, w, h);
-    else
-        hipLaunchKernelGGL((av1_convolve_mfma_kernel<1, false>), grid, block, 0, s, src, src_stride, src, src_stride, dst, dst_stride, dd, n_blocks, w, h);
-    return hipGetLastError();
-}
-
-hipError_t launch_av1_convolve_compound_mfma(const uint8_t* src0, uint32_t src0_stride, const uint8_t* src1, uint32_t src1_stride, uint8_t* dst,
-                                             uint32_t dst_stride, const svthip_convolve_compound_desc* desc, uint32_t n_blocks, int w, int h, hipStream_t s)
-{
-    const int ty = (h & 63) == 0 ? 2 : 1;
-    const uint64_t waves = (uint64_t)n_blocks * (uint32_t)((w >> 5) * (h / (32 * ty)));
-    const dim3 grid((uint32_t)((waves + 3) / 4)), block(256);
-    const uint4* dd = reinterpret_cast<const uint4*>(desc);
-    if (ty == 2)
-        hipLaunchKernelGGL((av1_convolve_mfma_kernel<2, true>), grid, block, 0, s, src0, src0_stride, src1, src1_stride, dst, dst_stride, dd, n_blocks, w, h);
-    else
-        hipLaunchKernelGGL((av1_convolve_mfma_kernel<1, true>), grid, block, 0, s, src0, src0_stride, src1, src1_stride, dst, dst_stride, dd, n_blocks, w, h);
-    return hipGetLastError();
-}
-
-hipError_t launch_convolve_mfma_counted(const uint8_t* src0, uint32_t src0_stride, const uint8_t* src1, uint32_t src1_stride, uint8_t* dst,
-                                        uint32_t dst_stride, const void* desc, uint32_t max_blocks, int w, int h, bool compound, hipStream_t s)
-{
-    if (max_blocks == 0) return hipSuccess;
-    const int ty = (h & 63) == 0 ? 2 : 1;
-    const uint64_t waves = (uint64_t)max_blocks * (uint32_t)((w >> 5) * (h / (32 * ty)));
-    const dim3 grid((uint32_t)((waves + 3) / 4)), block(256);
-    const uint4* dd = reinterpret_cast<const uint4*>(desc);
-    if (compound) {
-        if (ty == 2)
-            hipLaunchKernelGGL((av1_convolve_mfma_kernel<2, true, true>), grid, block, 0, s, src0, src0_stride, src1, src1_stride, dst, dst_stride, dd, max_blocks, w, h);
-        else
-            hipLaunchKernelGGL((av1_convolve_mfma_kernel<1, true, true>), grid, block, 0, s, src0, src0_stride, src1, src1_stride, dst, dst_stride, dd, max_blocks, w, h);
-    } else {
-        if (ty == 2)
-            hipLaunchKernelGGL((av1_convolve_mfma_kernel<2, false, true>), grid, block, 0, s, src0, src0_stride, src0, src0_stride, dst, dst_stride, dd, max_blocks, w, h);
-        else
-            hipLaunchKernelGGL((av1_convolve_mfma_kernel<1, false, true>), grid, block, 0, s, src0, src0_stride, src0, src0_stride, dst, dst_stride, dd, max_blocks, w, h);
-    }
+    using Kernel = void (*)(const uint8_t*, uint32_t, const uint8_t*, uint32_t, uint8_t*, uint32_t, const uint4*, uint32_t, int, int);
+    // [h % 64 == 0][compound][counted]
+    static const Kernel kernels[2][2][2] = {
+        {{av1_convolve_mfma_kernel<1, false, false>, av1_convolve_mfma_kernel<1, false, true>}, {av1_convolve_mfma_kernel<1, true, false>, av1_convolve_mfma_kernel<1, true, true>}},
+        {{av1_convolve_mfma_kernel<2, false, false>, av1_convolve_mfma_kernel<2, false, true>}, {av1_convolve_mfma_kernel<2, true, false>, av1_convolve_mfma_kernel<2, true, true>}}};
+    if (L.counted && L.n_blocks == 0) return hipSuccess;
+    const int ty = (L.h & 63) == 0 ? 2 : 1;
+    const uint64_t waves = (uint64_t)L.n_blocks * (uint32_t)((L.w >> 5) * (L.h / (32 * ty)));
+    const uint8_t *a = static_cast<const uint8_t*>(L.src0), *b = L.compound ? static_cast<const uint8_t*>(L.src1) : a;
+    hipLaunchKernelGGL(kernels[ty - 1][L.compound][L.counted], dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, s, a, L.stride0, b,
+                       L.compound ? L.stride1 : L.stride0, static_cast<uint8_t*>(L.dst), L.dst_stride, reinterpret_cast<const uint4*>(L.desc), L.n_blocks, L.w, L.h);
     return hipGetLastError();
 }
 

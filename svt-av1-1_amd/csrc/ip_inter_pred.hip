@@ -3,7 +3,7 @@
 // Whole-PU AV1 inter prediction: Y, Cb and Cr of a batch of prediction units of one luma size, each what one call of
 // av1_inter_prediction / av1_inter_prediction_hbd writes (Source/Lib/Codec/EbInterPrediction.c:1005-2050 / :2053-).
 //
-//   expansion  one thread per PU: clamp_mv_to_umv_border_sb (:80-102) for luma (bw, bh, 0, 0) and chroma (bwidth_uv, bheight_uv, 1, 1),
+//   expansion  one thread per PU: clamp_mv_to_umv_border_sb for luma (bw, bh, 0, 0) and chroma (bwidth_uv, bheight_uv, 1, 1),
 //              integer / fraction split, source and destination offsets, the sub8x8_inter decision (:1044-1127) and its pieces
 //              (:1129-1245).  Each PU becomes one job in a uni-list-0 / uni-list-1 / bi list per plane kind (the Cb and Cr jobs of a PU
 //              have the same offsets: the two chroma planes share one stride), or up to four chroma pieces.  Slots come from per-list
@@ -12,15 +12,16 @@
 //              form (template flag COUNTED): the job count is read from device memory and the grid is sized for n_pu.
 //   pieces     2x2 / 2x4 / 4x2 / 2x8 / 8x2 chroma pieces of sub-8x8 blocks: inter_pred_piece_kernel below, one thread per piece and plane,
 //              the whole piece in registers (no LDS); filter classes are inputs chosen by the expansion from bwidth_uv / bheight_uv.
+// The clamp, the chroma geometry, the job word, the filter rows and the rounding constants are ip_common.h's.
 //
-// Offsets are 32-bit and the source planes are passed rebased by the largest distance a clamped block can lie left of / above the picture
-// (bw + 4 samples, plus 3 filter taps), so every offset is non-negative.  A PU whose offsets would still leave that range (mb_to_*_edge
-// values that do not describe the block's position) is refused like a BI_PRED PU with sub-8x8 chroma: nothing is written, the context
-// counts it.
+// Offsets are 32-bit and the source planes are passed rebased (rebase_samples), so every offset is non-negative.  A PU whose offsets would
+// still leave that range (mb_to_*_edge values that do not describe the block's position) is refused like a BI_PRED PU with sub-8x8 chroma:
+// nothing is written, the context counts it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
+#include "ip_common.h"
 #include "me_kernels.h"
 
 static_assert(sizeof(svthip_inter_pu_desc) == 64, "svthip_inter_pu_desc is 64 bytes (include/svtav1_hip.h)");
@@ -28,18 +29,6 @@ static_assert(sizeof(svthip_inter_pu_desc) == 64, "svthip_inter_pu_desc is 64 by
 namespace svthip {
 
 namespace {
-
-// [filter 0..5][phase][taps 0-3, taps 4-7] as packed signed bytes (filters 4 / 5: the 4-tap regular / smooth kernels)
-__device__ const uint32_t kInterpP[6][16][2] =
-#include "av1_interp_filters.inc"
-    ;
-
-// av1_get_interp_filter_params_with_block_size (:985-995): 4-tap kernels for sides <= 4 (BILINEAR has none)
-__host__ __device__ inline int filter_class(int f, int size)
-{
-    if (size <= 4) return f == 1 ? 5 : (f == 3 ? 3 : 4);
-    return f;
-}
 
 // scratch slot layout: the job lists, each behind a 16-byte slot whose first dword is its length (where the counted convolution kernels
 // read it); lists 0-5 hold up to n jobs, the piece list up to 4 n
@@ -55,15 +44,24 @@ struct ExpandArgs {
     int64_t ky0, ky1, kc0, kc1;           // rebasing of the source planes, in samples
 };
 
-// clamp_mv_to_umv_border_sb: (row, col) in 1/16 sample of the plane
 __device__ __forceinline__ void clamp_mv(int mv_row, int mv_col, const svthip_inter_pu_desc& d, int bw, int bh, int ss, int& r, int& c)
 {
-    const int spel_left = (4 + bw) << 4, spel_right = spel_left - 16, spel_top = (4 + bh) << 4, spel_bottom = spel_top - 16;
-    const int m = 1 << (1 - ss);
-    r = (int16_t)(mv_row * m);
-    c = (int16_t)(mv_col * m);
-    c = min(max(c, d.mb_to_left_edge * m - spel_left), d.mb_to_right_edge * m + spel_right);
-    r = min(max(r, d.mb_to_top_edge * m - spel_top), d.mb_to_bottom_edge * m + spel_bottom);
+    clamp_mv_to_umv_border(mv_row, mv_col, d.mb_to_left_edge, d.mb_to_right_edge, d.mb_to_top_edge, d.mb_to_bottom_edge, bw, bh, ss, r, c);
+}
+
+// The piece list's own job: like a uni job, but subpel_y sits beside subpel_x, the reference list is named (the pieces of a PU can differ
+// in it) and the filters are CLASSES, chosen from bwidth_uv / bheight_uv and not from the piece's own size.
+struct PieceJob {
+    uint32_t src, dst;
+    int sx, sy, list, fxc, fyc;
+};
+__device__ __forceinline__ uint4 piece_job(uint32_t src, uint32_t dst, int sx, int sy, int list, int fxc, int fyc)
+{
+    return uint4{src, dst, (uint32_t)(sx | (sy << 4) | (list << 8) | (fxc << 16) | (fyc << 24)), 0u};
+}
+__device__ __forceinline__ PieceJob decode_piece(uint4 j)
+{
+    return PieceJob{j.x, j.y, (int)(j.z & 15), (int)((j.z >> 4) & 15), (int)((j.z >> 8) & 1), (int)((j.z >> 16) & 255), (int)((j.z >> 24) & 255)};
 }
 
 // Slot allocation for the seven job lists, aggregated per workgroup: each wave's ballots give its lanes' ranks and counts, one thread per
@@ -119,7 +117,7 @@ __global__ void __launch_bounds__(256) inter_pred_expand_kernel(const svthip_int
         sub[l] = (c & 15) | ((r & 15) << 4);
         const uint32_t st = l ? A.ys1 : A.ys0;
         ysrc[l] = ((int64_t)d.pu_origin_y + (r >> 4)) * st + (int64_t)d.pu_origin_x + (c >> 4) + (l ? A.ky1 : A.ky0);
-        if ((dir == l || dir == 2) && (ysrc[l] < 0 || ysrc[l] > 0xffffffffll)) ok = false;
+        if ((dir == l || dir == 2) && !offset_in_range(ysrc[l])) ok = false;
     }
     const uint32_t ydst = (uint32_t)d.dst_origin_y * A.yd + d.dst_origin_x;
 
@@ -133,8 +131,8 @@ __global__ void __launch_bounds__(256) inter_pred_expand_kernel(const svthip_int
         if (narrow && !d.nb_is_inter[2]) sub8 = false;
     }
     if (sub8 && dir == 2) ok = false;  // assert(!is_compound) in the reference (:1148, :2195)
-    const int cx0 = (d.pu_origin_x >> 3) << 2, cy0 = (d.pu_origin_y >> 3) << 2;
-    const uint32_t cdst = (uint32_t)((d.dst_origin_y >> 3) << 2) * A.cd + (uint32_t)((d.dst_origin_x >> 3) << 2);
+    const int cx0 = chroma_origin(d.pu_origin_x), cy0 = chroma_origin(d.pu_origin_y);
+    const uint32_t cdst = (uint32_t)chroma_origin(d.dst_origin_y) * A.cd + (uint32_t)chroma_origin(d.dst_origin_x);
     int csub[2];
     int64_t csrc[2];
     const bool whole_c = d.has_uv && !sub8;
@@ -144,13 +142,13 @@ __global__ void __launch_bounds__(256) inter_pred_expand_kernel(const svthip_int
         csub[l] = (c & 15) | ((r & 15) << 4);
         const uint32_t st = l ? A.cs1 : A.cs0;
         csrc[l] = ((int64_t)cy0 + (r >> 4)) * st + cx0 + (c >> 4) + (l ? A.kc1 : A.kc0);
-        if (whole_c && (dir == l || dir == 2) && (csrc[l] < 0 || csrc[l] > 0xffffffffll)) ok = false;
+        if (whole_c && (dir == l || dir == 2) && !offset_in_range(csrc[l])) ok = false;
     }
     // pieces: b4 = (bw / 2) x (bh / 2) over the bwidth_uv x bheight_uv block, (row, col) from (row_start, col_start)
     const int b4w = A.bw >> 1, b4h = A.bh >> 1, npx = A.bwu / b4w, npy = A.bhu / b4h;
     uint4 piece[4];
     if (sub8 && ok) {
-        const int fxi = filter_class(fx, A.bwu), fyi = filter_class(fy, A.bhu);
+        const int fxi = interp_filter_class(fx, A.bwu), fyi = interp_filter_class(fy, A.bhu);
 #pragma unroll
         for (int py = 0; py < 2; py++)
 #pragma unroll
@@ -175,9 +173,8 @@ __global__ void __launch_bounds__(256) inter_pred_expand_kernel(const svthip_int
                 const int x = px * b4w, y = py * b4h;
                 const uint32_t st = list ? A.cs1 : A.cs0;
                 const int64_t so = ((int64_t)cy0 + y + (r >> 4)) * st + cx0 + x + (c >> 4) + (list ? A.kc1 : A.kc0);
-                if (so < 0 || so > 0xffffffffll) ok = false;
-                piece[py * 2 + px] = uint4{(uint32_t)so, cdst + (uint32_t)y * A.cd + (uint32_t)x,
-                                             (uint32_t)((c & 15) | ((r & 15) << 4) | (list << 8) | (fxi << 16) | (fyi << 24)), 0u};
+                if (!offset_in_range(so)) ok = false;
+                piece[py * 2 + px] = piece_job((uint32_t)so, cdst + (uint32_t)y * A.cd + (uint32_t)x, c & 15, r & 15, list, fxi, fyi);
             }
     }
     if (live && !ok) atomicAdd(refused, 1u);
@@ -193,20 +190,17 @@ __global__ void __launch_bounds__(256) inter_pred_expand_kernel(const svthip_int
     want[L_PIECE] = ok && sub8;
     uint32_t slot[N_LISTS];
     alloc_slots(lists, n_pu, want, np, slot);
-    const uint32_t fxy = ((uint32_t)fx << 16) | ((uint32_t)fy << 24);
 #pragma unroll
     for (int l = 0; l < 2; l++) {
         if (want[L_Y0 + l])
-            lists[list_offset(L_Y0 + l, n_pu) / 16 + slot[L_Y0 + l]] =
-                uint4{(uint32_t)ysrc[l], ydst, (uint32_t)(sub[l] & 15) | ((uint32_t)(sub[l] >> 4) << 8) | fxy, 0u};
+            lists[list_offset(L_Y0 + l, n_pu) / 16 + slot[L_Y0 + l]] = uni_job((uint32_t)ysrc[l], ydst, sub[l] & 15, sub[l] >> 4, fx, fy);
         if (want[L_C0 + l])
-            lists[list_offset(L_C0 + l, n_pu) / 16 + slot[L_C0 + l]] =
-                uint4{(uint32_t)csrc[l], cdst, (uint32_t)(csub[l] & 15) | ((uint32_t)(csub[l] >> 4) << 8) | fxy, 0u};
+            lists[list_offset(L_C0 + l, n_pu) / 16 + slot[L_C0 + l]] = uni_job((uint32_t)csrc[l], cdst, csub[l] & 15, csub[l] >> 4, fx, fy);
     }
     if (want[L_YBI])
-        lists[list_offset(L_YBI, n_pu) / 16 + slot[L_YBI]] = uint4{(uint32_t)ysrc[0], (uint32_t)ysrc[1], ydst, (uint32_t)sub[0] | ((uint32_t)sub[1] << 8) | fxy};
+        lists[list_offset(L_YBI, n_pu) / 16 + slot[L_YBI]] = bi_job((uint32_t)ysrc[0], (uint32_t)ysrc[1], ydst, sub[0], sub[1], fx, fy);
     if (want[L_CBI])
-        lists[list_offset(L_CBI, n_pu) / 16 + slot[L_CBI]] = uint4{(uint32_t)csrc[0], (uint32_t)csrc[1], cdst, (uint32_t)csub[0] | ((uint32_t)csub[1] << 8) | fxy};
+        lists[list_offset(L_CBI, n_pu) / 16 + slot[L_CBI]] = bi_job((uint32_t)csrc[0], (uint32_t)csrc[1], cdst, csub[0], csub[1], fx, fy);
     if (want[L_PIECE])
 #pragma unroll
         for (int py = 0; py < 2; py++)
@@ -217,7 +211,7 @@ __global__ void __launch_bounds__(256) inter_pred_expand_kernel(const svthip_int
 
 // One chroma piece of PW x PH samples per thread (threads [0, n) Cb, [n, 2n) Cr), single-reference rounding of
 // av1_convolve_{2d,x,y,2d_copy}_sr_c / av1_highbd_convolve_*_sr_c (:145-286, :530-700) with get_conv_params_no_round(.., 0, bd):
-// the constants of av1_convolve_sr_kernel's non-compound path.  8-bit rows go through v_dot4 on (pixel - 128) bytes.
+// hrow8 and the single-reference second_pass_constants of ip_common.h.
 template <int PW, int PH, bool HBD>
 __global__ void __launch_bounds__(256) inter_pred_piece_kernel(const uint8_t* __restrict__ r0cb, const uint8_t* __restrict__ r0cr, uint32_t s0,
                                                                const uint8_t* __restrict__ r1cb, const uint8_t* __restrict__ r1cr, uint32_t s1,
@@ -229,20 +223,19 @@ __global__ void __launch_bounds__(256) inter_pred_piece_kernel(const uint8_t* __
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= 2 * n) return;
     const bool cr = t >= n;
-    const uint4 j = jobs[cr ? t - n : t];
-    const int sx = (int)(j.z & 15), sy = (int)((j.z >> 4) & 15), list = (int)((j.z >> 8) & 1);
-    const int fxi = (int)((j.z >> 16) & 255), fyi = (int)((j.z >> 24) & 255);
+    const PieceJob j = decode_piece(jobs[cr ? t - n : t]);
+    const int sx = j.sx, sy = j.sy, list = j.list;
     const uint8_t* src = list ? (cr ? r1cr : r1cb) : (cr ? r0cr : r0cb);
     const uint32_t stride = list ? s1 : s0;
-    uint8_t* dst = (cr ? dcr : dcb) + (size_t)j.y * SB;
+    uint8_t* dst = (cr ? dcr : dcb) + (size_t)j.dst * SB;
 
     int im[PH + 7][PW];
     const int rows = sy ? PH + 7 : PH;
-    const int64_t base = (int64_t)j.x - (sy ? 3 * (int64_t)stride : 0) - (sx ? 3 : 0);
+    const int64_t base = (int64_t)j.src - (sy ? 3 * (int64_t)stride : 0) - (sx ? 3 : 0);
     uint32_t flo = 0, fhi = 0;
     if (sx) {
-        flo = kInterpP[fxi][sx][0];
-        fhi = kInterpP[fxi][sx][1];
+        flo = kInterpFilter[j.fxc][sx][0];
+        fhi = kInterpFilter[j.fxc][sx][1];
     }
 #pragma unroll
     for (int r = 0; r < PH + 7; r++) {
@@ -251,13 +244,8 @@ __global__ void __launch_bounds__(256) inter_pred_piece_kernel(const uint8_t* __
         if (HBD) {
             const uint16_t* p16 = reinterpret_cast<const uint16_t*>(p);
             if (sx) {
-                int f[8];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    f[k] = (int)(int8_t)(flo >> (8 * k));
-                    f[4 + k] = (int)(int8_t)(fhi >> (8 * k));
-                }
-                int s[PW + 7];
+                int f[8], s[PW + 7];
+                unpack_taps(flo, fhi, f);
 #pragma unroll
                 for (int k = 0; k < PW + 7; k++) s[k] = p16[k];
                 const int bias = (sy ? (1 << (bd + 6)) : 0) + 4;
@@ -273,24 +261,7 @@ __global__ void __launch_bounds__(256) inter_pred_piece_kernel(const uint8_t* __
                 for (int c = 0; c < PW; c++) im[r][c] = p16[c];
             }
         } else if (sx) {
-            // bytes p[0 .. PW + 7) - 128, packed, from aligned dwords (the window of the convolution entries: at most 3 bytes before
-            // and a few after the samples the filter needs)
-            constexpr int NE = (PW + 7 + 3) / 4;
-            const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-            const uint32_t* q = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-            const uint32_t sh = (uint32_t)(a & 3u);
-            uint32_t raw[NE + 1], e[NE];
-#pragma unroll
-            for (int k = 0; k < NE + 1; k++) raw[k] = q[k];
-#pragma unroll
-            for (int k = 0; k < NE; k++) e[k] = __builtin_amdgcn_alignbyte(raw[k + 1], raw[k], sh) ^ 0x80808080u;
-            const int bias = (sy ? (1 << 15) : (1 << 14)) + 4;  // sum f p = sum f (p - 128) + 128 * 128, plus the 2-D offset 1 << 14
-#pragma unroll
-            for (int c = 0; c < PW; c++) {
-                const uint32_t lo = (c & 3) ? __builtin_amdgcn_alignbyte(e[c / 4 + 1], e[c / 4], c & 3) : e[c / 4];
-                const uint32_t hi = (c & 3) ? __builtin_amdgcn_alignbyte(e[c / 4 + 2], e[c / 4 + 1], c & 3) : e[c / 4 + 1];
-                im[r][c] = __builtin_amdgcn_sdot4((int)hi, (int)fhi, __builtin_amdgcn_sdot4((int)lo, (int)flo, bias, false), false) >> 3;
-            }
+            hrow8<PW>(p, flo, fhi, sy != 0, im[r]);
         } else {
 #pragma unroll
             for (int c = 0; c < PW; c++) im[r][c] = p[c];
@@ -299,23 +270,8 @@ __global__ void __launch_bounds__(256) inter_pred_piece_kernel(const uint8_t* __
 
     const int pix_max = (1 << bd) - 1;
     int g[8];
-    int c0, shift, subtract;
-    if (sy) {
-        const uint32_t glo = kInterpP[fyi][sy][0], ghi = kInterpP[fyi][sy][1];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            g[k] = (int)(int8_t)(glo >> (8 * k));
-            g[4 + k] = (int)(int8_t)(ghi >> (8 * k));
-        }
-        if (sx) { c0 = (1 << (bd + 11)) + (1 << 10); shift = 11; subtract = (1 << bd) + (1 << (bd - 1)); }  // 2-D: round_1 = 11
-        else { c0 = 64; shift = 7; subtract = 0; }                                                      // y only: FILTER_BITS
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; k++) g[k] = k == 0;
-        if (sx) { c0 = 8; shift = 4; }  // x only: second rounding, FILTER_BITS - round_0
-        else { c0 = 0; shift = 0; }     // copy
-        subtract = 0;
-    }
+    const SecondPass K = second_pass_constants(sx, sy, j.fyc, false, bd, g);
+    const int c0 = K.c0, shift = K.shift, subtract = K.sub;
 #pragma unroll
     for (int y = 0; y < PH; y++)
 #pragma unroll
@@ -358,16 +314,13 @@ hipError_t launch_inter_pred(const svthip_inter_planes& ref0, const svthip_inter
                              uint32_t* refused, hipStream_t s)
 {
     const int SB = bd > 8 ? 2 : 1;
-    const int bwu = bw >> 1 < 4 ? 4 : bw >> 1, bhu = bh >> 1 < 4 ? 4 : bh >> 1;
+    const int bwu = chroma_side(bw), bhu = chroma_side(bh);
     ExpandArgs A;
     A.ys0 = ref0.y_stride; A.ys1 = ref1.y_stride; A.yd = dst.y_stride;
     A.cs0 = ref0.c_stride; A.cs1 = ref1.c_stride; A.cd = dst.c_stride;
     A.bw = bw; A.bh = bh; A.bwu = bwu; A.bhu = bhu;
-    // rebasing: a clamped block starts at most (size + 4) samples left of / above the picture and the filter reaches 3 further
-    A.ky0 = (int64_t)(bh + 7) * ref0.y_stride + (bw + 7);
-    A.ky1 = (int64_t)(bh + 7) * ref1.y_stride + (bw + 7);
-    A.kc0 = (int64_t)(bhu + 7) * ref0.c_stride + (bwu + 7);
-    A.kc1 = (int64_t)(bhu + 7) * ref1.c_stride + (bwu + 7);
+    A.ky0 = rebase_samples(bw, bh, ref0.y_stride); A.ky1 = rebase_samples(bw, bh, ref1.y_stride);
+    A.kc0 = rebase_samples(bwu, bhu, ref0.c_stride); A.kc1 = rebase_samples(bwu, bhu, ref1.c_stride);
     uint8_t* sc = static_cast<uint8_t*>(scratch);
     // the seven list lengths: one strided memset
     hipError_t e = hipMemset2DAsync(sc + count_offset(0, n_pu), list_pitch(n_pu), 0, sizeof(uint32_t), N_LISTS, s);
@@ -382,14 +335,8 @@ hipError_t launch_inter_pred(const svthip_inter_planes& ref0, const svthip_inter
     auto run = [&](int w, int h, int l0, const uint8_t* p0, uint32_t s0, const uint8_t* p1, uint32_t s1, void* d, uint32_t dsz) -> hipError_t {
         const bool mfma = use_mfma && bd == 8 && convolve_mfma_size_valid(w, h);
         for (int l = 0; l < 3; l++) {
-            const void* jobs = sc + list_offset(l0 + l, n_pu);
-            const uint8_t* a = l == 1 ? p1 : p0;
-            const uint32_t as = l == 1 ? s1 : s0;
-            hipError_t r;
-            if (mfma)
-                r = launch_convolve_mfma_counted(a, as, p1, s1, static_cast<uint8_t*>(d), dsz, jobs, n_pu, w, h, l == 2, s);
-            else
-                r = launch_convolve_counted(a, as, p1, s1, d, dsz, jobs, n_pu, w, h, l == 2, bd, s);
+            const ConvolveLaunch L = {l == 1 ? p1 : p0, l == 1 ? s1 : s0, p1, s1, d, dsz, sc + list_offset(l0 + l, n_pu), n_pu, w, h, bd, l == 2, true};
+            const hipError_t r = mfma ? launch_convolve_mfma(L, s) : launch_convolve_valu(L, s);
             if (r != hipSuccess) return r;
         }
         return hipSuccess;

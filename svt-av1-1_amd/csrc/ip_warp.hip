@@ -10,13 +10,13 @@
 //              the host and a block finds its PU by a division.  The block centre, ix4 / sx4 / iy4 / sy4 are wave-uniform.  The 15 x 8
 //              horizontal results (two passes of the wave) go to LDS as 16-bit values (< 2^13 at 8 bits, < 2^15 at 10), the vertical
 //              pass is one lane per output sample.  The filter row is chosen per sample from the 193-row table, staged in LDS as packed
-//              bytes (1 544 bytes); 8-bit horizontal sums are two v_dot4_i32_i8 on (pixel - 128) bytes, the bias folded into the offset
+//              bytes (1 544 bytes); 8-bit horizontal sums are ip_common.h's dot8 on (pixel - 128) bytes, the bias folded into the offset
 //              (rows sum to 128).  Source rows: when the block's 15 x 15 window (and the dwords around it) lies inside the picture,
 //              aligned dwords + v_alignbyte; otherwise per-sample coordinates clamped to the picture as the reference clamps them.
 //              The choice is wave-uniform.
 //   chroma < 8x8   warp_chroma_expand_kernel writes one job per PU in the format of the counted convolution kernels (ip_convolve.hip,
 //              COUNTED), which then run unchanged on Cb and Cr: clamp_mv_to_umv_border_sb(xd, mv, bwidth_uv, bheight_uv, 1, 1), source at
-//              ((pu_origin >> 3) << 3) / 2, filters 0 / 0.
+//              ((pu_origin >> 3) << 3) / 2, filters 0 / 0 -- the clamp, geometry and job word of ip_common.h, as in ip_inter_pred.hip.
 //
 // A PU whose model fails the reference's validity tests (is_affine_valid, is_affine_shear_allowed, Codec/EbWarpedMotion.c:329-341: the
 // filter-row index would leave [0, 192]), whose wmtype is not ROTZOOM / AFFINE, or whose translational chroma block would start outside the
@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
+#include "ip_common.h"
 #include "me_kernels.h"
 
 static_assert(sizeof(svthip_warp_pu_desc) == 64, "svthip_warp_pu_desc is 64 bytes (include/svtav1_hip.h)");
@@ -63,20 +64,17 @@ __device__ __forceinline__ bool model_valid(const svthip_warp_pu_desc& d)
     return true;
 }
 
-// The translational chroma job of a PU smaller than 16x16: clamp_mv_to_umv_border_sb (:80-102) with (bwidth_uv, bheight_uv, 1, 1), integer /
+// The translational chroma job of a PU smaller than 16x16: clamp_mv_to_umv_border_sb with (bwidth_uv, bheight_uv, 1, 1), integer /
 // fraction split, offsets.  false: the block would start outside the rebased range (edges that do not describe the PU's position).
 __device__ __forceinline__ bool chroma_job(const svthip_warp_pu_desc& d, const WarpArgs& A, uint4& job)
 {
-    const int bwu = max(4, A.bw >> 1), bhu = max(4, A.bh >> 1);
-    const int spel_left = (4 + bwu) << 4, spel_right = spel_left - 16, spel_top = (4 + bhu) << 4, spel_bottom = spel_top - 16;
-    int r = (int16_t)d.mv[0], c = (int16_t)d.mv[1];  // subsampled plane: 1/8 luma sample = 1/16 chroma sample
-    c = min(max(c, d.mb_to_left_edge - spel_left), d.mb_to_right_edge + spel_right);
-    r = min(max(r, d.mb_to_top_edge - spel_top), d.mb_to_bottom_edge + spel_bottom);
-    const int cx0 = (d.pu_origin_x >> 3) << 2, cy0 = (d.pu_origin_y >> 3) << 2;
-    const int64_t so = ((int64_t)cy0 + (r >> 4)) * A.rcs + cx0 + (c >> 4) + A.kc;
-    const uint32_t cdst = (uint32_t)((d.dst_origin_y >> 3) << 2) * A.dcs + (uint32_t)((d.dst_origin_x >> 3) << 2);
-    job = uint4{(uint32_t)so, cdst, (uint32_t)(c & 15) | ((uint32_t)(r & 15) << 8), 0u};  // interp_filters = 0
-    return so >= 0 && so <= 0xffffffffll;
+    int r, c;
+    clamp_mv_to_umv_border(d.mv[0], d.mv[1], d.mb_to_left_edge, d.mb_to_right_edge, d.mb_to_top_edge, d.mb_to_bottom_edge, chroma_side(A.bw),
+                           chroma_side(A.bh), 1, r, c);
+    const int64_t so = ((int64_t)chroma_origin(d.pu_origin_y) + (r >> 4)) * A.rcs + chroma_origin(d.pu_origin_x) + (c >> 4) + A.kc;
+    const uint32_t cdst = (uint32_t)chroma_origin(d.dst_origin_y) * A.dcs + (uint32_t)chroma_origin(d.dst_origin_x);
+    job = uni_job((uint32_t)so, cdst, c & 15, r & 15, 0, 0);  // interp_filters = 0
+    return offset_in_range(so);
 }
 
 // one thread per PU; the list length sits in the 16 bytes in front of the jobs, one atomic per wave
@@ -207,8 +205,7 @@ __global__ void __launch_bounds__(256) warp_kernel(const svthip_warp_pu_desc* __
                         }
                     }
                     // sum f p = sum f (p - 128) + 128 * 128; offset 1 << 14; rounding 4
-                    sum = __builtin_amdgcn_sdot4((int)(hi ^ 0x80808080u), (int)fhi,
-                                                 __builtin_amdgcn_sdot4((int)(lo ^ 0x80808080u), (int)flo, (1 << 15) + 4, false), false);
+                    sum = dot8(lo ^ 0x80808080u, hi ^ 0x80808080u, flo, fhi, (1 << 15) + 4);
                 }
                 tmp[wave][k * 8 + l] = (uint16_t)(sum >> 3);  // reduce_bits_horiz = 3 at 8 and 10 bits
             }
@@ -249,7 +246,7 @@ hipError_t launch_warped_pred(const svthip_inter_planes& ref, const svthip_inter
                               uint32_t n_pu, int bw, int bh, int bd, void* scratch, uint32_t* refused, hipStream_t s)
 {
     const int SB = bd > 8 ? 2 : 1;
-    const int bwu = bw >> 1 < 4 ? 4 : bw >> 1, bhu = bh >> 1 < 4 ? 4 : bh >> 1;
+    const int bwu = chroma_side(bw), bhu = chroma_side(bh);
     WarpArgs A;
     A.ry = static_cast<const uint8_t*>(ref.y); A.rcb = static_cast<const uint8_t*>(ref.cb); A.rcr = static_cast<const uint8_t*>(ref.cr);
     A.dy = static_cast<uint8_t*>(dst.y); A.dcb = static_cast<uint8_t*>(dst.cb); A.dcr = static_cast<uint8_t*>(dst.cr);
@@ -257,8 +254,7 @@ hipError_t launch_warped_pred(const svthip_inter_planes& ref, const svthip_inter
     A.pic_w = pic_w; A.pic_h = pic_h; A.bw = bw; A.bh = bh;
     A.warp_chroma = bw >= 16 && bh >= 16;
     A.bd = bd;
-    // a clamped block starts at most (size + 4) samples left of / above the picture and the filter reaches 3 further (ip_inter_pred.hip)
-    A.kc = (int64_t)(bhu + 7) * ref.c_stride + (bwu + 7);
+    A.kc = rebase_samples(bwu, bhu, ref.c_stride);
     hipError_t e;
     if (!A.warp_chroma) {
         uint4* list = static_cast<uint4*>(scratch);
@@ -266,8 +262,9 @@ hipError_t launch_warped_pred(const svthip_inter_planes& ref, const svthip_inter
         hipLaunchKernelGGL(warp_chroma_expand_kernel, dim3((n_pu + 255) / 256), dim3(256), 0, s, desc, n_pu, A, list);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         const uint8_t *cb = A.rcb - A.kc * SB, *cr = A.rcr - A.kc * SB;
-        if ((e = launch_convolve_counted(cb, ref.c_stride, cb, ref.c_stride, dst.cb, dst.c_stride, list + 1, n_pu, bwu, bhu, false, bd, s)) != hipSuccess) return e;
-        if ((e = launch_convolve_counted(cr, ref.c_stride, cr, ref.c_stride, dst.cr, dst.c_stride, list + 1, n_pu, bwu, bhu, false, bd, s)) != hipSuccess) return e;
+        const ConvolveLaunch Lcb = {cb, ref.c_stride, nullptr, 0, dst.cb, dst.c_stride, list + 1, n_pu, bwu, bhu, bd, false, true};
+        const ConvolveLaunch Lcr = {cr, ref.c_stride, nullptr, 0, dst.cr, dst.c_stride, list + 1, n_pu, bwu, bhu, bd, false, true};
+        if ((e = launch_convolve_valu(Lcb, s)) != hipSuccess || (e = launch_convolve_valu(Lcr, s)) != hipSuccess) return e;
     }
     const uint64_t per_pu = (uint64_t)(bw >> 3) * (bh >> 3) + (A.warp_chroma ? 2 * (uint64_t)(bw >> 4) * (bh >> 4) : 0);
     const uint64_t groups = (n_pu * per_pu + kBlocksPerGroup - 1) / kBlocksPerGroup;

@@ -129,29 +129,28 @@ __global__ void sad_loop_kernel(const uint8_t* __restrict__ src, uint32_t src_st
                                 uint32_t ref_stride_raw, const svthip_sad_loop_desc* __restrict__ desc, uint32_t n_blocks, int w, int h, int sw, int sh,
                                 int slice_bytes, uint32_t* __restrict__ best_sad, int16_t* __restrict__ best_xy);
 bool convolve_mfma_size_valid(int w, int h);
-hipError_t launch_av1_convolve_sr_mfma(const uint8_t* src, uint32_t src_stride, uint8_t* dst, uint32_t dst_stride, const svthip_convolve_desc* desc,
-                                       uint32_t n_blocks, int w, int h, hipStream_t s);
-hipError_t launch_av1_convolve_compound_mfma(const uint8_t* src0, uint32_t src0_stride, const uint8_t* src1, uint32_t src1_stride, uint8_t* dst,
-                                             uint32_t dst_stride, const svthip_convolve_compound_desc* desc, uint32_t n_blocks, int w, int h, hipStream_t s);
-hipError_t launch_av1_convolve_compound(const uint8_t* src0, uint32_t src0_stride, const uint8_t* src1, uint32_t src1_stride, uint8_t* dst,
-                                        uint32_t dst_stride, const svthip_convolve_compound_desc* desc, uint32_t n_blocks, int w, int h, hipStream_t s);
-size_t convolve_compound_lds_bytes(int w, int h);
-const void* convolve_compound_kernel_ptr(int which);  // 0..3
-hipError_t launch_av1_highbd_convolve(const uint16_t* src0, uint32_t src0_stride, const uint16_t* src1, uint32_t src1_stride, uint16_t* dst,
-                                      uint32_t dst_stride, const void* desc, bool compound, uint32_t n_blocks, int w, int h, int bd, hipStream_t s);
+bool convolve_size_valid(int w, int h);
+// One launch of the convolution kernels on blocks of one size (ip_convolve.hip: the 22 AV1 sizes, any bd; ip_convolve_mfma.hip: sides that
+// are multiples of 32, bd 8).  desc: svthip_convolve_desc (src1 unused) or, with compound, svthip_convolve_compound_desc.  counted: the block
+// count is in device memory, in the 16 bytes in front of desc, and n_blocks only sizes the grid.  bd above 8: 16-bit planes, units are samples.
+struct ConvolveLaunch {
+    const void* src0; uint32_t stride0;
+    const void* src1; uint32_t stride1;
+    void* dst; uint32_t dst_stride;
+    const void* desc; uint32_t n_blocks;
+    int w, h, bd;
+    bool compound, counted;
+};
+hipError_t launch_convolve_valu(const ConvolveLaunch& L, hipStream_t s);
+hipError_t launch_convolve_mfma(const ConvolveLaunch& L, hipStream_t s);
+// the instantiations whose dynamic LDS can pass 64 KB (svthip_abi.hip raises their limit once per device)
+constexpr int kConvolveDynamicLdsKernels = 8;
+void convolve_dynamic_lds_kernels(const void** list);
 size_t sad_loop_qsad_lds_bytes(int w, int h, int sw, int sh, int k);  // workgroup LDS of the packed-SAD kernel (its own plan: blocks per workgroup, pitch)
 hipError_t launch_sad_loop_qsad(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, uint32_t ref_stride_raw,
                                 const svthip_sad_loop_desc* desc, uint32_t n_blocks, int w, int h, int sw, int sh, uint32_t* best_sad,
                                 int16_t* best_xy, hipStream_t s);
 size_t sad_loop_slice_bytes(int w, int h, int sw, int sh, int k);
-bool convolve_size_valid(int w, int h);
-// the convolution kernels with the block count in device memory, in the 16 bytes in front of desc (whole-PU inter prediction,
-// ip_inter_pred.hip): grids sized for max_blocks; bd 8 = 8-bit planes, 10 = 16-bit planes
-hipError_t launch_convolve_counted(const void* src0, uint32_t src0_stride, const void* src1, uint32_t src1_stride, void* dst, uint32_t dst_stride,
-                                   const void* desc, uint32_t max_blocks, int w, int h, bool compound, int bd, hipStream_t s);
-hipError_t launch_convolve_mfma_counted(const uint8_t* src0, uint32_t src0_stride, const uint8_t* src1, uint32_t src1_stride, uint8_t* dst,
-                                        uint32_t dst_stride, const void* desc, uint32_t max_blocks, int w, int h, bool compound, hipStream_t s);
-const void* convolve_compound_count_kernel_ptr(int which);  // 0..3
 // ip_inter_pred.hip: the descriptor expansion and the 2-wide / 2-high chroma pieces
 hipError_t launch_inter_pred(const svthip_inter_planes& ref0, const svthip_inter_planes& ref1, const svthip_inter_planes& dst,
                              const svthip_inter_pu_desc* desc, uint32_t n_pu, int bw, int bh, int bd, bool use_mfma, void* scratch,
@@ -167,8 +166,6 @@ bool warp_size_valid(int bw, int bh);
 hipError_t launch_intra_pred(const void* edge, void* dst, const svthip_intra_desc* desc, uint32_t n_blocks, int tx_size, int bd, const uint8_t* src,
                              uint32_t* sad, uint32_t* refused, hipStream_t s);
 bool intra_tx_size_valid(uint32_t tx_size);
-hipError_t launch_av1_convolve_sr(const uint8_t* src, uint32_t src_stride, uint8_t* dst, uint32_t dst_stride, const svthip_convolve_desc* desc,
-                                  uint32_t n_blocks, int w, int h, hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

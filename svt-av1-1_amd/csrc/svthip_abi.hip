@@ -82,13 +82,11 @@ hipError_t g_attr_status[16];
 
 void set_kernel_attrs(int device)
 {
-    const void* kernels[] = {reinterpret_cast<const void*>(svthip::fullpel85_kernel),  reinterpret_cast<const void*>(svthip::fullpel209_kernel),
-                             reinterpret_cast<const void*>(svthip::bipred_pack_kernel), reinterpret_cast<const void*>(svthip::bipred_nsq_pack_kernel),
-                             reinterpret_cast<const void*>(svthip::subpel_planes_kernel), svthip::convolve_compound_kernel_ptr(0),
-                             svthip::convolve_compound_kernel_ptr(1),                     svthip::convolve_compound_kernel_ptr(2),
-                             svthip::convolve_compound_kernel_ptr(3),                     svthip::convolve_compound_count_kernel_ptr(0),
-                             svthip::convolve_compound_count_kernel_ptr(1),               svthip::convolve_compound_count_kernel_ptr(2),
-                             svthip::convolve_compound_count_kernel_ptr(3)};
+    const void* kernels[5 + svthip::kConvolveDynamicLdsKernels] = {
+        reinterpret_cast<const void*>(svthip::fullpel85_kernel), reinterpret_cast<const void*>(svthip::fullpel209_kernel),
+        reinterpret_cast<const void*>(svthip::bipred_pack_kernel), reinterpret_cast<const void*>(svthip::bipred_nsq_pack_kernel),
+        reinterpret_cast<const void*>(svthip::subpel_planes_kernel)};
+    svthip::convolve_dynamic_lds_kernels(kernels + 5);
     hipError_t st = hipSuccess;
     for (const void* k : kernels) {
         hipFuncAttributes fa;
@@ -1039,12 +1037,10 @@ int32_t svthip_av1_convolve_sr_batch_dev(svthip_ctx* ctx, const uint8_t* d_src, 
     TRY(check_non_null({d_src, d_dst, d_desc}));
     if (!aligned(d_desc, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor array must be 16-byte aligned");
     hipStream_t s = call_stream(ctx, stream);
-    if (svthip::convolve_mfma_size_valid((int)width, (int)height) && !ctx->opt[SVTHIP_OPT_CONVOLVE_VALU]) {
-        // sides that are multiples of 32: both passes as exact i8 matrix products on the matrix cores (ip_convolve_mfma.hip)
-        HIP_TRY(svthip::launch_av1_convolve_sr_mfma(d_src, src_stride, d_dst, dst_stride, d_desc, n_blocks, (int)width, (int)height, s));
-        return SVTHIP_OK;
-    }
-    HIP_TRY(svthip::launch_av1_convolve_sr(d_src, src_stride, d_dst, dst_stride, d_desc, n_blocks, (int)width, (int)height, s));
+    const svthip::ConvolveLaunch L = {d_src, src_stride, nullptr, 0, d_dst, dst_stride, d_desc, n_blocks, (int)width, (int)height, 8, false, false};
+    // sides that are multiples of 32: both passes as exact i8 matrix products on the matrix cores (ip_convolve_mfma.hip)
+    const bool mfma = svthip::convolve_mfma_size_valid((int)width, (int)height) && !ctx->opt[SVTHIP_OPT_CONVOLVE_VALU];
+    HIP_TRY(mfma ? svthip::launch_convolve_mfma(L, s) : svthip::launch_convolve_valu(L, s));
     return SVTHIP_OK;
 }
 
@@ -1058,12 +1054,9 @@ int32_t svthip_av1_convolve_compound_batch_dev(svthip_ctx* ctx, const uint8_t* d
     TRY(check_non_null({d_src0, d_src1, d_dst, d_desc}));
     if (!aligned(d_desc, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor array must be 16-byte aligned");
     hipStream_t s = call_stream(ctx, stream);
-    if (svthip::convolve_mfma_size_valid((int)width, (int)height) && !ctx->opt[SVTHIP_OPT_CONVOLVE_VALU]) {
-        HIP_TRY(svthip::launch_av1_convolve_compound_mfma(d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_desc, n_blocks, (int)width,
-                                                          (int)height, s));
-        return SVTHIP_OK;
-    }
-    HIP_TRY(svthip::launch_av1_convolve_compound(d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_desc, n_blocks, (int)width, (int)height, s));
+    const svthip::ConvolveLaunch L = {d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_desc, n_blocks, (int)width, (int)height, 8, true, false};
+    const bool mfma = svthip::convolve_mfma_size_valid((int)width, (int)height) && !ctx->opt[SVTHIP_OPT_CONVOLVE_VALU];
+    HIP_TRY(mfma ? svthip::launch_convolve_mfma(L, s) : svthip::launch_convolve_valu(L, s));
     return SVTHIP_OK;
 }
 
@@ -1078,8 +1071,9 @@ int32_t svthip_av1_highbd_convolve_batch_dev(svthip_ctx* ctx, const uint16_t* d_
     if (!d_src0 || (compound && !d_src1) || !d_dst || !d_desc) return fail(SVTHIP_ERR_BAD_PARAMETER, "null pointer argument");
     if (!aligned(d_desc, 16) || !aligned({d_src0, d_src1, d_dst}, 2))
         return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor array must be 16-byte aligned, planes 2-byte aligned");
-    HIP_TRY(svthip::launch_av1_highbd_convolve(d_src0, src0_stride, compound ? d_src1 : d_src0, compound ? src1_stride : src0_stride, d_dst, dst_stride,
-                                               d_desc, compound != 0, n_blocks, (int)width, (int)height, (int)bit_depth, call_stream(ctx, stream)));
+    const svthip::ConvolveLaunch L = {d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_desc, n_blocks, (int)width, (int)height,
+                                      (int)bit_depth, compound != 0, false};
+    HIP_TRY(svthip::launch_convolve_valu(L, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 
