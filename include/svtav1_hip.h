@@ -720,7 +720,8 @@ int32_t svthip_av1_highbd_warped_pred_batch_dev(svthip_ctx *ctx, const svthip_in
  * the block side, n_topright_px > 0 with n_top_px != txw, n_bottomleft_px > 0 with n_left_px != txh.
  * Nothing in the call synchronises with the host.
  *
- * Out of scope: CfL, the edge / corner filter and upsampling (compiled out of the reference), filter-intra, palette, 12-bit video. */
+ * Out of scope: the edge / corner filter and upsampling (compiled out of the reference), filter-intra, palette, 12-bit video.  CfL has its
+ * own entries below (svthip_av1_cfl_pred_batch_dev and the three that follow it). */
 typedef struct svthip_intra_desc {
     uint32_t above_offset;
     uint32_t left_offset, left_stride;
@@ -736,6 +737,89 @@ int32_t svthip_av1_intra_pred_batch_dev(svthip_ctx *ctx, const uint8_t *d_edge, 
                                         uint32_t n_blocks, uint32_t tx_size, const uint8_t *d_src, uint32_t *d_sad, void *stream);
 int32_t svthip_av1_highbd_intra_pred_batch_dev(svthip_ctx *ctx, const uint16_t *d_edge, uint16_t *d_dst, const svthip_intra_desc *d_desc,
                                                uint32_t n_blocks, uint32_t tx_size, uint32_t bit_depth, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * AV1 chroma-from-luma (CfL) prediction, 4:2:0: a batch of blocks of ONE luma size.  Per block the device computes what the reference
+ * computes in three steps (Codec/EbIntraPrediction.c):
+ *   cfl_luma_subsampling_420_{lbd,hbd}_c (:5442-5471)   q3[y][x] = (l[2y][2x] + l[2y][2x+1] + l[2y+1][2x] + l[2y+1][2x+1]) << 1
+ *   subtract_average_c (:5472-5498)                     ac = q3 - ((sum q3 + cw * ch / 2) >> (log2 cw + log2 ch))
+ *   cfl_predict_{lbd,hbd}_c (:5500-5539)                dst = clip(ROUND_POWER_OF_TWO_SIGNED(alpha_q3 * ac, 6) + dc_pred, bit_depth),
+ *                                                       the rounding on the magnitude: -(((-v) + 32) >> 6) for v < 0
+ * with alpha_q3 = cfl_idx_to_alpha(alpha_idx, alpha_signs, CFL_PRED_U / CFL_PRED_V) (Codec/EbIntraPrediction.h:1093-1101, CFL_SIGN_U/V and
+ * CFL_IDX_U/V of Codec/EbDefinitions.h:755-793), -16 .. 16.  dc_pred is the chroma block already predicted with UV_DC_PRED (the intra entry
+ * above produces it).  The AC block stays on chip.  Callers: Av1EncodeLoop (Codec/EbCodingLoop.c:714-790), Av1EncodeLoop16bit
+ * (:1121-1210) and step 4 of CflPrediction (Codec/EbProductCodingLoop.c:1884-2000).
+ *
+ * (luma_w, luma_h): the nine luma sizes the reference uses CfL with (Codec/EbModeDecision.c:1769-1842): each side 8, 16 or 32 with a ratio
+ * of at most 4.  The chroma block is luma_w / 2 x luma_h / 2.
+ *
+ * svthip_cfl_desc (32 bytes), offsets and strides in SAMPLES:
+ *   luma_offset/stride    the reconstructed luma block in d_luma: luma_w x luma_h samples are read
+ *   cb_offset, cr_offset  the chroma block's position in d_cb / d_cr, where the DC prediction is read, and in d_cb_dst / d_cr_dst, where the
+ *                         result is written (candidates entry: read only)
+ *   chroma_stride         row distance of all four chroma planes
+ *   alpha_idx/signs       cfl_alpha_idx and cfl_alpha_signs as the reference stores them (predict entries only)
+ * d_cb_dst == d_cb and d_cr_dst == d_cr is the in-place form (what EncDec does).  The blocks of one call must not overlap in the destinations.
+ *
+ * Refused with svthip_last_error text: a (luma_w, luma_h) outside the nine, a null plane or d_desc when n_blocks > 0 (n_blocks == 0
+ * returns OK), a descriptor array that is not 16-byte aligned, 16-bit planes that are not 2-byte aligned, a bit_depth other than 10
+ * (16-bit entry).  Refused on the device (nothing written for that block, counted; svthip_inter_pred_refused reports and clears the
+ * count): alpha_signs > 7.  Nothing in the call synchronises with the host. */
+typedef struct svthip_cfl_desc {
+    uint32_t luma_offset, luma_stride;
+    uint32_t cb_offset, cr_offset;
+    uint32_t chroma_stride;
+    uint8_t alpha_idx, alpha_signs;
+    uint8_t reserved[10];
+} svthip_cfl_desc;
+
+int32_t svthip_av1_cfl_pred_batch_dev(svthip_ctx *ctx, const uint8_t *d_luma, const uint8_t *d_cb, const uint8_t *d_cr, uint8_t *d_cb_dst,
+                                      uint8_t *d_cr_dst, const svthip_cfl_desc *d_desc, uint32_t n_blocks, uint32_t luma_w, uint32_t luma_h,
+                                      void *stream);
+int32_t svthip_av1_highbd_cfl_pred_batch_dev(svthip_ctx *ctx, const uint16_t *d_luma, const uint16_t *d_cb, const uint16_t *d_cr,
+                                             uint16_t *d_cb_dst, uint16_t *d_cr_dst, const svthip_cfl_desc *d_desc, uint32_t n_blocks,
+                                             uint32_t luma_w, uint32_t luma_h, uint32_t bit_depth, void *stream);
+
+/* The candidate predictions of mode decision's alpha search (8 bits, as cfl_rd_pick_alpha's is: Codec/EbProductCodingLoop.c:1720-1875
+ * through AV1CostCalcCfl, :1539-1715).  Per block `job`, plane p (0 = Cb, 1 = Cr) and k = 0 .. 32 the cw x ch prediction with
+ * alpha_q3 = k - 16 is written as a tile with row stride cw at sample ((job * 2 + p) * 33 + k) * cw * ch of d_candidates, which therefore
+ * holds n_blocks * 66 * cw * ch samples.  svthip_encode_tu_batch_dev takes that pool as its d_pred with one static descriptor per tile.
+ * alpha_idx / alpha_signs of the descriptors are not read.  Refusals as above; nothing is refused on the device. */
+int32_t svthip_av1_cfl_alpha_candidates_batch_dev(svthip_ctx *ctx, const uint8_t *d_luma, const uint8_t *d_cb_dc, const uint8_t *d_cr_dc,
+                                                  const svthip_cfl_desc *d_desc, uint32_t n_blocks, uint32_t luma_w, uint32_t luma_h,
+                                                  uint8_t *d_candidates, void *stream);
+
+/* cfl_rd_pick_alpha's walk (Codec/EbProductCodingLoop.c:1720-1875) over the costs of the candidates, one decision per block.  For a chroma
+ * TU Av1TuCalcCost leaves bits and distortion untouched (Codec/EbRateDistortionCost.c:2135-2142), so candidate t = (job * 2 + p) * 33 + k
+ * enters with
+ *   d_bits[t]                              Av1TuEstimateCoeffBits of the chroma TU (svthip_coeff_rate_batch_dev with plane_type = 1)
+ *   d_distortion[t][0] >> dist_shift       sum (coeff - dqcoeff)^2 >> ((MAX_TX_SCALE - av1_get_tx_scale(txsize_uv)) * 2), the [n_tu][2]
+ *                                          layout of svthip_encode_tu_batch_dev (CuFullDistortionFastTuMode_R, Codec/EbFullLoop.c:1925)
+ * and costs are RDCOST(lambda, R, D) = ROUND_POWER_OF_TWO((uint64_t)R * lambda, 9) + D * 128 (Codec/EbRateDistortionCost.h:213-217).
+ *   svthip_cfl_decision_job   lambda = full_lambda; cfl_mode_bits / dc_mode_bits = intraUVmodeFacBits[CFL_ALLOWED][intra_luma_mode]
+ *                             [UV_CFL_PRED] / [UV_DC_PRED] (Codec/EbMdRateEstimation.h:97-99)
+ *   d_alpha_bits              cflAlphaFacBits[8][2][16], int32, copied from the host's rate-estimation context
+ *   svthip_cfl_decision       intra_chroma_mode (UV_DC_PRED = 0 or UV_CFL_PRED = 13), cfl_alpha_idx, cfl_alpha_signs as the reference
+ *                             leaves them, and per plane the mask of the k the reference would have evaluated (bit k; the early exit
+ *                             `if (c > 2 && progress < c) break` ends a sign's run).  A candidate outside its mask is not read.
+ * The walk is the reference's to the letter, including that AV1CostCalcCfl evaluates alpha 0 where cfl_alpha_idx == 0 and
+ * cfl_alpha_signs == 0 (:1579, :1654): that is Cr's candidate for alpha -1, so bit 15 of Cr's mask is never set.
+ * Refused with svthip_last_error text: a null pointer when n_blocks > 0, d_job / d_out not 16-byte aligned, d_distortion not 8-byte or
+ * d_bits / d_alpha_bits not 4-byte aligned, dist_shift > 63.  Nothing in the call synchronises with the host. */
+typedef struct svthip_cfl_decision_job {
+    uint64_t lambda;
+    int32_t cfl_mode_bits, dc_mode_bits;
+} svthip_cfl_decision_job;
+
+typedef struct svthip_cfl_decision {
+    uint8_t intra_chroma_mode, cfl_alpha_idx, cfl_alpha_signs;
+    uint8_t reserved[13];
+    uint64_t evaluated_mask[2];
+} svthip_cfl_decision;
+
+int32_t svthip_cfl_alpha_decision_batch_dev(svthip_ctx *ctx, const uint64_t *d_distortion, const uint32_t *d_bits, uint32_t dist_shift,
+                                            const int32_t *d_alpha_bits, const svthip_cfl_decision_job *d_job, uint32_t n_blocks,
+                                            svthip_cfl_decision *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one

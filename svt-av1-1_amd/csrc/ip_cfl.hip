@@ -1,0 +1,340 @@
+// svt-av1-1_amd/csrc/ip_cfl.hip
+//
+// AV1 chroma-from-luma (CfL) prediction and the search for its alphas: a batch of blocks of ONE luma size (4:2:0, so the chroma block is
+// half of it each way), each what cfl_luma_subsampling_420_{lbd,hbd}_c, subtract_average_c and cfl_predict_{lbd,hbd}_c
+// (Source/Lib/Codec/EbIntraPrediction.c:5442-5539) compute, and the walk of cfl_rd_pick_alpha (Codec/EbProductCodingLoop.c:1720-1875)
+// over the costs of the candidates.
+//
+//   mapping    cfl_kernel<HBD, CW, CH, CANDIDATES>: a lane owns four consecutive chroma samples of a row (a quad), i.e. a 8 x 2 window of
+//              luma.  A chroma block of CW x CH is CW / 4 * CH <= 64 quads and is worked by that many lanes, so a wave holds 64 / G blocks
+//              (sixteen 4x4 .. one 16x16) and a block never spans waves.
+//   AC         the lane's four q3 sums stay in registers; the block sum is a butterfly over the block's lanes; the average is subtracted
+//              in registers.  The AC block never goes through memory.
+//   predict    alpha from (cfl_alpha_idx, cfl_alpha_signs) as cfl_idx_to_alpha does; Cb and Cr over the DC prediction read from the same
+//              position, rounding on the magnitude (ROUND_POWER_OF_TWO_SIGNED), clip to the depth.
+//   candidates 8 bits: for plane p and k = 0 .. 32 (alpha_q3 = k - 16) the CW x CH tile with row stride CW at sample
+//              ((job * 2 + p) * 33 + k) * CW * CH of the pool: the lanes of a block write one contiguous tile per candidate.
+//   stores     one dword (8 bits) or one qword (16 bits) per quad when the address allows, else per sample.
+//   decision   cfl_decision_kernel: one lane per job restates the reference's walk over the 66 (distortion, bits) pairs of the job and
+//              records which of them the reference would have evaluated; a pair outside that record is never read.
+//
+// A predict descriptor with alpha_signs > 7 (CFL_JOINT_SIGNS = 8) is refused: nothing is written for it and the context's counter is
+// incremented once.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "../../include/svtav1_hip.h"
+#include "me_kernels.h"
+
+static_assert(sizeof(svthip_cfl_desc) == 32, "svthip_cfl_desc is 32 bytes (include/svtav1_hip.h)");
+static_assert(sizeof(svthip_cfl_decision_job) == 16, "svthip_cfl_decision_job is 16 bytes (include/svtav1_hip.h)");
+static_assert(sizeof(svthip_cfl_decision) == 32, "svthip_cfl_decision is 32 bytes (include/svtav1_hip.h)");
+
+namespace svthip {
+
+namespace {
+
+struct CflArgs {
+    const void* luma;
+    const void* cb;
+    const void* cr;
+    void* cb_dst;   // candidates mode: the pool
+    void* cr_dst;
+    const svthip_cfl_desc* desc;
+    uint32_t n;
+    uint32_t* refused;
+    int bd;
+};
+
+// sum over the G lanes of a block (G a power of two, the lanes aligned to it)
+template <int G>
+__device__ __forceinline__ int group_sum(int v)
+{
+#pragma unroll
+    for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// CFL_SIGN_U / CFL_SIGN_V / CFL_IDX_U / CFL_IDX_V and cfl_idx_to_alpha (Codec/EbDefinitions.h:755-793, Codec/EbIntraPrediction.h:1093-1101)
+__device__ __forceinline__ int cfl_alpha(int idx, int joint_sign, int plane)
+{
+    const int su = ((joint_sign + 1) * 11) >> 5, sv = (joint_sign + 1) - 3 * su;
+    const int sign = plane == 0 ? su : sv, mag = plane == 0 ? idx >> 4 : idx & 15;
+    return sign == 0 ? 0 : sign == 2 ? mag + 1 : -mag - 1;
+}
+
+// eight consecutive samples
+template <typename T>
+__device__ __forceinline__ void load8(const T* p, int (&v)[8])
+{
+    if (sizeof(T) == 1) {
+        if ((reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+            const uint32_t a = reinterpret_cast<const uint32_t*>(p)[0], b = reinterpret_cast<const uint32_t*>(p)[1];
+#pragma unroll
+            for (int k = 0; k < 4; k++) { v[k] = (a >> (8 * k)) & 255; v[4 + k] = (b >> (8 * k)) & 255; }
+            return;
+        }
+    } else if ((reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
+        const uint2 a = reinterpret_cast<const uint2*>(p)[0], b = reinterpret_cast<const uint2*>(p)[1];
+        v[0] = a.x & 0xffff; v[1] = a.x >> 16; v[2] = a.y & 0xffff; v[3] = a.y >> 16;
+        v[4] = b.x & 0xffff; v[5] = b.x >> 16; v[6] = b.y & 0xffff; v[7] = b.y >> 16;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = p[k];
+}
+
+template <typename T>
+__device__ __forceinline__ void load4(const T* p, int (&v)[4])
+{
+    if (sizeof(T) == 1) {
+        if ((reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+            const uint32_t a = *reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = (a >> (8 * k)) & 255;
+            return;
+        }
+    } else if ((reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
+        const uint2 a = *reinterpret_cast<const uint2*>(p);
+        v[0] = a.x & 0xffff; v[1] = a.x >> 16; v[2] = a.y & 0xffff; v[3] = a.y >> 16;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = p[k];
+}
+
+// cfl_predict of a quad: clip(ROUND_POWER_OF_TWO_SIGNED(alpha_q3 * ac, 6) + dc), stored at p
+template <typename T>
+__device__ __forceinline__ void predict_store4(T* p, const int (&ac)[4], const int (&dc)[4], int alpha, int maxv)
+{
+    int v[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int s = alpha * ac[k], m = ((s < 0 ? -s : s) + 32) >> 6;
+        v[k] = min(max((s < 0 ? -m : m) + dc[k], 0), maxv);
+    }
+    if (sizeof(T) == 2) {
+        if ((reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
+            *reinterpret_cast<uint2*>(p) = uint2{(uint32_t)v[0] | ((uint32_t)v[1] << 16), (uint32_t)v[2] | ((uint32_t)v[3] << 16)};
+            return;
+        }
+    } else if ((reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+        *reinterpret_cast<uint32_t*>(p) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) p[k] = (T)v[k];
+}
+
+template <bool HBD, int CW, int CH, bool CANDIDATES>
+__global__ void __launch_bounds__(256) cfl_kernel(CflArgs A)
+{
+    using T = typename std::conditional<HBD, uint16_t, uint8_t>::type;
+    constexpr int QW = CW / 4, G = QW * CH, J = 64 / G;
+    constexpr int LOG2_PELS = CW * CH == 16 ? 4 : CW * CH == 32 ? 5 : CW * CH == 64 ? 6 : CW * CH == 128 ? 7 : 8;
+    static_assert(G <= 64 && (1 << LOG2_PELS) == CW * CH, "a chroma block of at most 16x16");
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int g = lane / G, l = lane % G;
+    const uint32_t job = (blockIdx.x * 4u + (uint32_t)wave) * J + (uint32_t)g;
+    if (job >= A.n) return;
+    const uint4* dp = reinterpret_cast<const uint4*>(A.desc + job);
+    const uint4 d0 = dp[0], d1 = dp[1];
+    const uint32_t luma_offset = d0.x, luma_stride = d0.y, cb_offset = d0.z, cr_offset = d0.w, chroma_stride = d1.x;
+    const int alpha_idx = d1.y & 255, alpha_signs = (d1.y >> 8) & 255;
+
+    if (!CANDIDATES && alpha_signs > 7) {
+        if (l == 0) atomicAdd(A.refused, 1u);
+        return;
+    }
+
+    // ---- the lane's quad of AC values: 2x2 luma sums << 1, minus the block's rounded average ----
+    const int r = l / QW, c0 = (l % QW) * 4;
+    int ac[4];
+    {
+        const T* lp = static_cast<const T*>(A.luma) + luma_offset + (size_t)(2 * r) * luma_stride + 2 * c0;
+        int top[8], bot[8];
+        load8(lp, top);
+        load8(lp + luma_stride, bot);
+        int s = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            ac[k] = (top[2 * k] + top[2 * k + 1] + bot[2 * k] + bot[2 * k + 1]) << 1;
+            s += ac[k];
+        }
+        const int avg = (group_sum<G>(s) + CW * CH / 2) >> LOG2_PELS;
+#pragma unroll
+        for (int k = 0; k < 4; k++) ac[k] -= avg;
+    }
+
+    const size_t at = (size_t)r * chroma_stride + c0;
+    int dcb[4], dcr[4];
+    load4(static_cast<const T*>(A.cb) + cb_offset + at, dcb);
+    load4(static_cast<const T*>(A.cr) + cr_offset + at, dcr);
+    const int maxv = HBD ? (1 << A.bd) - 1 : 255;
+
+    if (!CANDIDATES) {
+        predict_store4(static_cast<T*>(A.cb_dst) + cb_offset + at, ac, dcb, cfl_alpha(alpha_idx, alpha_signs, 0), maxv);
+        predict_store4(static_cast<T*>(A.cr_dst) + cr_offset + at, ac, dcr, cfl_alpha(alpha_idx, alpha_signs, 1), maxv);
+    } else {
+        T* tile = static_cast<T*>(A.cb_dst) + (size_t)job * (66 * CW * CH) + l * 4;
+#pragma unroll 3
+        for (int k = 0; k < 33; k++) predict_store4(tile + k * (CW * CH), ac, dcb, k - 16, maxv);
+        tile += 33 * CW * CH;
+#pragma unroll 3
+        for (int k = 0; k < 33; k++) predict_store4(tile + k * (CW * CH), ac, dcr, k - 16, maxv);
+    }
+}
+
+// ---- the walk of cfl_rd_pick_alpha ----
+
+struct CflDecisionArgs {
+    const uint64_t* distortion;   // [n * 66][2]
+    const uint32_t* bits;         // [n * 66]
+    const int32_t* alpha_bits;    // cflAlphaFacBits[8][2][16]
+    const svthip_cfl_decision_job* job;
+    svthip_cfl_decision* out;
+    uint32_t n;
+    uint32_t dist_shift;
+};
+
+// RDCOST (Codec/EbRateDistortionCost.h:213-217) as the reference's int64_t variables receive it
+__device__ __forceinline__ int64_t rdcost(uint64_t lambda, uint64_t rate, uint64_t dist) { return (int64_t)(((rate * lambda + 256) >> 9) + dist * 128); }
+
+// PLANE_SIGN_TO_JOINT_SIGN (Codec/EbProductCodingLoop.c:1717)
+__device__ __forceinline__ int joint_sign_of(int plane, int a, int b) { return plane == 0 ? a * 3 + b - 1 : b * 3 + a - 1; }
+
+__global__ void __launch_bounds__(64) cfl_decision_kernel(CflDecisionArgs A)
+{
+    const uint32_t job = blockIdx.x * 64u + threadIdx.x;
+    if (job >= A.n) return;
+    const int64_t kMax = INT64_MAX;
+    const uint64_t lambda = A.job[job].lambda;
+    const uint64_t* dist = A.distortion + (size_t)job * 132;
+    const uint32_t* bits = A.bits + (size_t)job * 66;
+    uint64_t mask[2] = {0, 0};
+    int64_t best_rd_uv[8][2];
+    int best_c[8][2];
+    const int64_t mode_rd = rdcost(lambda, (uint64_t)A.job[job].cfl_mode_bits, 0);
+
+    // the candidate AV1CostCalcCfl runs for (cfl_alpha_idx, cfl_alpha_signs) on `plane`: its alpha, forced to 0 when both fields are 0
+    auto candidate = [&](int plane, int idx, int js, uint64_t* rate, uint64_t* d) {
+        const int k = ((idx | js) == 0 ? 0 : cfl_alpha(idx, js, plane)) + 16;
+        mask[plane] |= 1ull << k;
+        *rate = bits[plane * 33 + k];
+        *d = dist[(plane * 33 + k) * 2] >> A.dist_shift;
+    };
+
+    for (int plane = 0; plane < 2; plane++) {
+        uint64_t rate = 0, d = 0;
+        for (int js = 0; js < 8; js++) { best_rd_uv[js][plane] = kMax; best_c[js][plane] = 0; }
+        for (int i = 1; i < 3; i++) {
+            const int js = joint_sign_of(plane, 0, i);
+            if (i == 1) candidate(plane, 0, js, &rate, &d);
+            best_rd_uv[js][plane] = rdcost(lambda, rate + (uint64_t)(int64_t)A.alpha_bits[(js * 2 + plane) * 16], d);
+        }
+    }
+
+    int64_t best_rd = kMax;
+    int best_joint_sign = -1;
+    for (int plane = 0; plane < 2; plane++) {
+        for (int pn_sign = 1; pn_sign < 3; pn_sign++) {
+            int progress = 0;
+            for (int c = 0; c < 16; c++) {
+                int flag = 0;
+                if (c > 2 && progress < c) break;
+                uint64_t rate = 0, d = 0;
+                for (int i = 0; i < 3; i++) {
+                    const int js = joint_sign_of(plane, pn_sign, i);
+                    if (i == 0) candidate(plane, (c << 4) + c, js, &rate, &d);
+                    int64_t this_rd = rdcost(lambda, rate + (uint64_t)(int64_t)A.alpha_bits[(js * 2 + plane) * 16 + c], d);
+                    if (this_rd >= best_rd_uv[js][plane]) continue;
+                    best_rd_uv[js][plane] = this_rd;
+                    best_c[js][plane] = c;
+                    flag = 2;
+                    if (best_rd_uv[js][plane ^ 1] == kMax) continue;
+                    this_rd += mode_rd + best_rd_uv[js][plane ^ 1];
+                    if (this_rd >= best_rd) continue;
+                    best_rd = this_rd;
+                    best_joint_sign = js;
+                }
+                progress += flag;
+            }
+        }
+    }
+
+    // "compare with DC": alpha 0 on both planes, which both planes have evaluated already
+    const uint64_t dc_rate = (uint64_t)bits[16] + bits[33 + 16];
+    const uint64_t dc_dist = (dist[16 * 2] >> A.dist_shift) + (dist[(33 + 16) * 2] >> A.dist_shift);
+    const int64_t dc_rd = rdcost(lambda, dc_rate, dc_dist) + rdcost(lambda, (uint64_t)A.job[job].dc_mode_bits, 0);
+
+    svthip_cfl_decision o = {};
+    if (dc_rd <= best_rd) {
+        o.intra_chroma_mode = 0;   // UV_DC_PRED
+    } else {
+        o.intra_chroma_mode = 13;  // UV_CFL_PRED
+        if (best_joint_sign >= 0) {
+            o.cfl_alpha_idx = (uint8_t)((best_c[best_joint_sign][0] << 4) + best_c[best_joint_sign][1]);
+            o.cfl_alpha_signs = (uint8_t)best_joint_sign;
+        }
+    }
+    o.evaluated_mask[0] = mask[0];
+    o.evaluated_mask[1] = mask[1];
+    A.out[job] = o;
+}
+
+template <bool HBD, int CW, int CH, bool CANDIDATES>
+hipError_t launch_size(const CflArgs& A, hipStream_t s)
+{
+    constexpr int per_group = 4 * (64 / (CW / 4 * CH));
+    const uint64_t groups = ((uint64_t)A.n + per_group - 1) / per_group;
+    if (groups > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((cfl_kernel<HBD, CW, CH, CANDIDATES>), dim3((uint32_t)groups), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+template <bool HBD, bool CANDIDATES>
+hipError_t launch_shape(const CflArgs& A, int luma_w, int luma_h, hipStream_t s)
+{
+    switch (luma_w * 64 + luma_h) {
+#define SVTHIP_CFL_CASE(W, H) case W * 64 + H: return launch_size<HBD, W / 2, H / 2, CANDIDATES>(A, s);
+        SVTHIP_CFL_CASE(8, 8) SVTHIP_CFL_CASE(16, 8) SVTHIP_CFL_CASE(8, 16) SVTHIP_CFL_CASE(16, 16) SVTHIP_CFL_CASE(32, 8) SVTHIP_CFL_CASE(8, 32)
+        SVTHIP_CFL_CASE(32, 16) SVTHIP_CFL_CASE(16, 32) SVTHIP_CFL_CASE(32, 32)
+#undef SVTHIP_CFL_CASE
+    default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+bool cfl_luma_size_valid(uint32_t w, uint32_t h)
+{
+    const bool side_ok = (w == 8 || w == 16 || w == 32) && (h == 8 || h == 16 || h == 32);
+    return side_ok && w <= 4 * h && h <= 4 * w;
+}
+
+hipError_t launch_cfl_pred(const void* luma, const void* cb, const void* cr, void* cb_dst, void* cr_dst, const svthip_cfl_desc* desc,
+                           uint32_t n_blocks, int luma_w, int luma_h, int bd, uint32_t* refused, hipStream_t s)
+{
+    CflArgs A{luma, cb, cr, cb_dst, cr_dst, desc, n_blocks, refused, bd};
+    return bd > 8 ? launch_shape<true, false>(A, luma_w, luma_h, s) : launch_shape<false, false>(A, luma_w, luma_h, s);
+}
+
+hipError_t launch_cfl_candidates(const uint8_t* luma, const uint8_t* cb_dc, const uint8_t* cr_dc, const svthip_cfl_desc* desc, uint32_t n_blocks,
+                                 int luma_w, int luma_h, uint8_t* candidates, hipStream_t s)
+{
+    CflArgs A{luma, cb_dc, cr_dc, candidates, nullptr, desc, n_blocks, nullptr, 8};
+    return launch_shape<false, true>(A, luma_w, luma_h, s);
+}
+
+hipError_t launch_cfl_decision(const uint64_t* distortion, const uint32_t* bits, uint32_t dist_shift, const int32_t* alpha_bits,
+                               const svthip_cfl_decision_job* job, uint32_t n_blocks, svthip_cfl_decision* out, hipStream_t s)
+{
+    CflDecisionArgs A{distortion, bits, alpha_bits, job, out, n_blocks, dist_shift};
+    hipLaunchKernelGGL(cfl_decision_kernel, dim3((n_blocks + 63u) / 64u), dim3(64), 0, s, A);
+    return hipGetLastError();
+}
+
+}  // namespace svthip

@@ -167,6 +167,15 @@ hipError_t launch_intra_pred(const void* edge, void* dst, const svthip_intra_des
                              uint32_t* sad, uint32_t* refused, hipStream_t s);
 bool intra_tx_size_valid(uint32_t tx_size);
 
+// ip_cfl.hip: chroma-from-luma prediction, its 2 x 33 candidate tiles per block, and cfl_rd_pick_alpha's walk over their costs
+hipError_t launch_cfl_pred(const void* luma, const void* cb, const void* cr, void* cb_dst, void* cr_dst, const svthip_cfl_desc* desc,
+                           uint32_t n_blocks, int luma_w, int luma_h, int bd, uint32_t* refused, hipStream_t s);
+hipError_t launch_cfl_candidates(const uint8_t* luma, const uint8_t* cb_dc, const uint8_t* cr_dc, const svthip_cfl_desc* desc, uint32_t n_blocks,
+                                 int luma_w, int luma_h, uint8_t* candidates, hipStream_t s);
+hipError_t launch_cfl_decision(const uint64_t* distortion, const uint32_t* bits, uint32_t dist_shift, const int32_t* alpha_bits,
+                               const svthip_cfl_decision_job* job, uint32_t n_blocks, svthip_cfl_decision* out, hipStream_t s);
+bool cfl_luma_size_valid(uint32_t w, uint32_t h);
+
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 
 }  // namespace svthip

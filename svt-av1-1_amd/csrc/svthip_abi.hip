@@ -504,6 +504,15 @@ int32_t pred_check_args(InterPlanesList planes, const void* d_desc)
     return SVTHIP_OK;
 }
 
+// the refusal counter of SLOT_INTER_REFUSED on the call's stream (scratch_on_stream has run), cleared on its first use
+int32_t ensure_refused_counter(svthip_ctx* ctx, hipStream_t s)
+{
+    const bool first = ctx->scratch[SLOT_INTER_REFUSED] == nullptr;
+    TRY(ensure_scratch(ctx, SLOT_INTER_REFUSED, 256));
+    if (first) HIP_TRY(hipMemsetAsync(ctx->scratch[SLOT_INTER_REFUSED], 0, 256, s));
+    return SVTHIP_OK;
+}
+
 int32_t pred_begin(svthip_ctx* ctx, InterPlanesList planes, int bd, uint32_t n_pu, uint32_t n_pu_cap, size_t (*scratch_bytes)(uint32_t),
                    void* stream, hipStream_t* out_s)
 {
@@ -513,10 +522,8 @@ int32_t pred_begin(svthip_ctx* ctx, InterPlanesList planes, int bd, uint32_t n_p
     if (n_pu > n_pu_cap) return fail(SVTHIP_ERR_BAD_PARAMETER, "too many PUs in one call (%d)", (int)n_pu);
     hipStream_t s = call_stream(ctx, stream);
     TRY(scratch_on_stream(ctx, s));
-    const bool first = ctx->scratch[SLOT_INTER_REFUSED] == nullptr;
     TRY(ensure_scratch(ctx, SLOT_INTER_JOBS, scratch_bytes(n_pu)));
-    TRY(ensure_scratch(ctx, SLOT_INTER_REFUSED, 256));
-    if (first) HIP_TRY(hipMemsetAsync(ctx->scratch[SLOT_INTER_REFUSED], 0, 256, s));
+    TRY(ensure_refused_counter(ctx, s));
     *out_s = s;
     return SVTHIP_OK;
 }
@@ -565,10 +572,40 @@ int32_t intra_pred_entry(svthip_ctx* ctx, const void* d_edge, void* d_dst, const
     if (d_sad && !aligned(d_sad, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sad must be 4-byte aligned");
     hipStream_t s = call_stream(ctx, stream);
     TRY(scratch_on_stream(ctx, s));
-    const bool first = ctx->scratch[SLOT_INTER_REFUSED] == nullptr;
-    TRY(ensure_scratch(ctx, SLOT_INTER_REFUSED, 256));
-    if (first) HIP_TRY(hipMemsetAsync(ctx->scratch[SLOT_INTER_REFUSED], 0, 256, s));
+    TRY(ensure_refused_counter(ctx, s));
     HIP_TRY(svthip::launch_intra_pred(d_edge, d_dst, d_desc, n_blocks, (int)tx_size, bd, d_src, d_sad, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
+    ctx->inter_stream = s;
+    return SVTHIP_OK;
+}
+
+// Chroma-from-luma: the two predict entries and the candidates entry share the checks; only the predict entries can refuse on the device.
+int32_t check_cfl_args(std::initializer_list<const void*> planes, const svthip_cfl_desc* d_desc, int bd)
+{
+    TRY(check_non_null(planes));
+    TRY(check_non_null({d_desc}));
+    if (!aligned(d_desc, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor array must be 16-byte aligned");
+    if (bd > 8 && !aligned(planes, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
+    return SVTHIP_OK;
+}
+
+int32_t check_cfl_luma_size(uint32_t luma_w, uint32_t luma_h)
+{
+    return svthip::cfl_luma_size_valid(luma_w, luma_h)
+               ? SVTHIP_OK
+               : fail(SVTHIP_ERR_BAD_PARAMETER, "not a CfL luma size: sides 8, 16 or 32 with a ratio of at most 4 (got %dx%d)", (int)luma_w, (int)luma_h);
+}
+
+int32_t cfl_pred_entry(svthip_ctx* ctx, const void* d_luma, const void* d_cb, const void* d_cr, void* d_cb_dst, void* d_cr_dst,
+                       const svthip_cfl_desc* d_desc, uint32_t n_blocks, uint32_t luma_w, uint32_t luma_h, int bd, void* stream)
+{
+    TRY(check_cfl_luma_size(luma_w, luma_h));
+    if (n_blocks == 0) return SVTHIP_OK;
+    TRY(check_cfl_args({d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst}, d_desc, bd));
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(scratch_on_stream(ctx, s));
+    TRY(ensure_refused_counter(ctx, s));
+    HIP_TRY(svthip::launch_cfl_pred(d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst, d_desc, n_blocks, (int)luma_w, (int)luma_h, bd,
+                                    slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
     ctx->inter_stream = s;
     return SVTHIP_OK;
 }
@@ -1125,6 +1162,50 @@ int32_t svthip_av1_highbd_intra_pred_batch_dev(svthip_ctx* ctx, const uint16_t* 
     return intra_pred_entry(ctx, d_edge, d_dst, d_desc, n_blocks, tx_size, (int)bit_depth, nullptr, nullptr, stream);
 }
 
+int32_t svthip_av1_cfl_pred_batch_dev(svthip_ctx* ctx, const uint8_t* d_luma, const uint8_t* d_cb, const uint8_t* d_cr, uint8_t* d_cb_dst,
+                                      uint8_t* d_cr_dst, const svthip_cfl_desc* d_desc, uint32_t n_blocks, uint32_t luma_w, uint32_t luma_h,
+                                      void* stream)
+{
+    TRY(enter(ctx));
+    return cfl_pred_entry(ctx, d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst, d_desc, n_blocks, luma_w, luma_h, 8, stream);
+}
+
+int32_t svthip_av1_highbd_cfl_pred_batch_dev(svthip_ctx* ctx, const uint16_t* d_luma, const uint16_t* d_cb, const uint16_t* d_cr,
+                                             uint16_t* d_cb_dst, uint16_t* d_cr_dst, const svthip_cfl_desc* d_desc, uint32_t n_blocks,
+                                             uint32_t luma_w, uint32_t luma_h, uint32_t bit_depth, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return cfl_pred_entry(ctx, d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst, d_desc, n_blocks, luma_w, luma_h, (int)bit_depth, stream);
+}
+
+int32_t svthip_av1_cfl_alpha_candidates_batch_dev(svthip_ctx* ctx, const uint8_t* d_luma, const uint8_t* d_cb_dc, const uint8_t* d_cr_dc,
+                                                  const svthip_cfl_desc* d_desc, uint32_t n_blocks, uint32_t luma_w, uint32_t luma_h,
+                                                  uint8_t* d_candidates, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_cfl_luma_size(luma_w, luma_h));
+    if (n_blocks == 0) return SVTHIP_OK;
+    TRY(check_cfl_args({d_luma, d_cb_dc, d_cr_dc, d_candidates}, d_desc, 8));
+    HIP_TRY(svthip::launch_cfl_candidates(d_luma, d_cb_dc, d_cr_dc, d_desc, n_blocks, (int)luma_w, (int)luma_h, d_candidates, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_cfl_alpha_decision_batch_dev(svthip_ctx* ctx, const uint64_t* d_distortion, const uint32_t* d_bits, uint32_t dist_shift,
+                                            const int32_t* d_alpha_bits, const svthip_cfl_decision_job* d_job, uint32_t n_blocks,
+                                            svthip_cfl_decision* d_out, void* stream)
+{
+    TRY(enter(ctx));
+    if (dist_shift > 63) return fail(SVTHIP_ERR_BAD_PARAMETER, "dist_shift must be 0..63 (got %u)", (unsigned)dist_shift);
+    if (n_blocks == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_distortion, d_bits, d_alpha_bits, d_job, d_out}));
+    if (!aligned({d_job, d_out}, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "job and decision arrays must be 16-byte aligned");
+    if (!aligned(d_distortion, 8) || !aligned({d_bits, d_alpha_bits}, 4))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_distortion must be 8-byte, d_bits and d_alpha_bits 4-byte aligned");
+    HIP_TRY(svthip::launch_cfl_decision(d_distortion, d_bits, dist_shift, d_alpha_bits, d_job, n_blocks, d_out, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
 int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
 {
     TRY(enter(ctx));
@@ -1139,7 +1220,7 @@ int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
     if (!n) return SVTHIP_OK;
     HIP_TRY(hipMemsetAsync(d_refused, 0, sizeof(n), s));
     *out_count = n;
-    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, or an intra descriptor the reference would assert on", (int)n);
+    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, or a CfL descriptor with alpha_signs > 7", (int)n);
 }
 
 // ---------------------------------------------------------------- host-pointer forms (run_queued: no transfer outlives a failed call)

@@ -1,0 +1,251 @@
+"""Writes tests/golden/cfl.npz from the reference's own chroma-from-luma functions and its own cfl_rd_pick_alpha
+(tests/golden/ref_cfl_driver.c linked against the reference objects of the oracle build, oracle/_ref/obj_all, with EbProductCodingLoop.o
+left out -- the driver includes that source to reach the static -- and with FullLoop_R / CuFullDistortionFastTuMode_R of EbFullLoop.o
+weakened so that the driver's stand-ins take their place).  Run in the build container only, where the reference exists: the fixture is
+data and is what the GPU box checks.
+
+    python tests/golden/make_golden_cfl.py
+
+Contents
+  case                 one row per batch: luma_w, luma_h, bit depth, desc[start : start + count], and start / length of the batch's luma,
+                       chroma (Cb and Cr have one length) and AC samples in that depth's arrays
+  desc                 CFL_DESC_DTYPE rows of every batch (offsets relative to the batch's arrays)
+  luma_8 / luma_10     reconstructed luma blocks
+  cb_8, cr_8 / _10     the DC predictions the reference read
+  ocb_8, ocr_8 / _10   what cfl_predict_{lbd,hbd}_c wrote over them (the generator checks the AVX2 forms to write the same)
+  ac                   int16: the AC block of every descriptor after subtract_average_c (= subtract_average_avx2, checked), cw x ch each
+  alpha                (idx, joint sign, plane, alpha) for every idx 0 .. 255 x joint sign 0 .. 7 x plane: cfl_idx_to_alpha
+  dec_alpha_bits       [groups][8][2][16] cflAlphaFacBits tables
+  dec_group, dec_job   per decision job its table and its CFL_DECISION_JOB_DTYPE row
+  dec_dist, dec_bits   [jobs][2][33] what the stand-in for CuFullDistortionFastTuMode_R answered per plane and alpha_q3 + 16
+  dec_out              [jobs][3] intra_chroma_mode, cfl_alpha_idx, cfl_alpha_signs as cfl_rd_pick_alpha left them
+  dec_mask             [jobs][2] the alphas AV1CostCalcCfl asked a prediction for, per plane (bit alpha_q3 + 16)
+Coverage (coverage() below, asserted again by tests/test_cfl_vs_ref.py::test_fixture_covers_the_ground): the nine luma shapes at 8 and 10
+bits, every alpha_q3 -16 .. 16 on each plane, an all-equal luma block, the largest |AC| of each depth (2x2 quads alternating 0 and the
+maximum; with |alpha| = 16 at 10 bits the product exceeds 16 bits), a negative product that is 32 mod 64, outputs clipped at 0 and at the
+maximum, a block sum whose rounding term decides the average; decision tables that reach the early exit at c = 3 and later, a run with no
+early exit, a tie on this_rd >= best_rd_uv, a tie on dc_rd <= best_rd (DC wins), each of the eight joint signs as winner, DC as winner."""
+import ctypes as C
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+
+import cfl_util as cu  # noqa: E402
+
+REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
+OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
+OUT = os.path.join(HERE, "cfl.npz")
+BUF_LINE = 32   # CFL_BUF_LINE
+N_DEC_RANDOM, N_DEC_TIES = 144, 16
+
+
+def reference_available():
+    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL)
+
+
+def build_driver(out_dir):
+    """The recipe of make_golden_intra_pred.build_driver (--gc-sections from the drv_* roots, EbEncHandle.o left out, NASM-only symbols that
+    stay unresolved made weak), with EbProductCodingLoop.o left out (the driver includes that source) and a copy of EbFullLoop.o in which
+    the two functions the driver replaces are weak."""
+    S = os.path.join(REF_ROOT, "Source")
+    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
+    src = os.path.join(HERE, "ref_cfl_driver.c")
+    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
+    so, vmap, weak = os.path.join(out_dir, "libref_cfl.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
+    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
+    with open(vmap, "w") as f:
+        f.write("{ global: drv_*; local: *; };\n")
+    full_loop = os.path.join(out_dir, "EbFullLoop_weak.o")
+    subprocess.check_call(["objcopy", "--weaken-symbol=FullLoop_R", "--weaken-symbol=CuFullDistortionFastTuMode_R",
+                           os.path.join(OBJ_ALL, "EbFullLoop.o"), full_loop])
+    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL)
+                  if o.endswith(".o") and o not in ("EbEncHandle.o", "EbProductCodingLoop.o", "EbFullLoop.o")) + [full_loop]
+
+    def link(o):
+        subprocess.check_call(["gcc", "-shared", "-o", so, o, *objs, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
+
+    link(obj)
+    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
+    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
+    with open(weak, "w") as f:
+        f.write("\n".join(names) + "\n")
+    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
+    link(wobj)
+    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    L.drv_subsample.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.drv_subtract_average.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.drv_predict.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.drv_idx_to_alpha.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.drv_idx_to_alpha.restype = C.c_int
+    L.drv_pick_alpha.restype = C.c_int
+    L.drv_pick_alpha.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]
+    return L
+
+
+def aligned_q3():
+    """a CFL_BUF_LINE x CFL_BUF_LINE int16 buffer on a 32-byte boundary (the AVX2 forms use aligned loads)"""
+    raw = np.zeros(BUF_LINE * BUF_LINE + 16, np.int16)
+    skip = (-raw.ctypes.data % 32) // 2
+    return raw[skip:skip + BUF_LINE * BUF_LINE].reshape(BUF_LINE, BUF_LINE)
+
+
+def reference_predict(L, luma, cb, cr, desc, lw, lh, bd):
+    """(Cb, Cr, AC) as the reference's C functions leave them, the AVX2 forms checked to agree"""
+    cw, ch = lw // 2, lh // 2
+    ocb, ocr = cb.copy(), cr.copy()
+    acs = np.zeros((len(desc), ch, cw), np.int16)
+    for i, d in enumerate(desc):
+        q3 = {}
+        for avx2 in (0, 1):
+            q = aligned_q3()
+            blk = np.ascontiguousarray(luma[int(d["luma_offset"]):])
+            L.drv_subsample(bd, blk.ctypes.data, int(d["luma_stride"]), lw, lh, q.ctypes.data)
+            L.drv_subtract_average(avx2, q.ctypes.data, cw, ch)
+            q3[avx2] = q
+        assert np.array_equal(q3[0][:ch, :cw], q3[1][:ch, :cw]), ("subtract_average_c and _avx2 differ", lw, lh, bd, i)
+        acs[i] = q3[0][:ch, :cw]
+        cs = int(d["chroma_stride"])
+        for plane, (src, dst, off) in enumerate(((cb, ocb, int(d["cb_offset"])), (cr, ocr, int(d["cr_offset"])))):
+            a = L.drv_idx_to_alpha(int(d["alpha_idx"]), int(d["alpha_signs"]), plane)
+            got = {}
+            for avx2 in (0, 1):
+                pred = np.ascontiguousarray(src[off:off + cs * ch + 32])
+                out = pred.copy()   # in place, as EncDec calls it
+                L.drv_predict(avx2, bd, q3[0].ctypes.data, out.ctypes.data, cs, out.ctypes.data, cs, a, cw, ch)
+                got[avx2] = out[(np.arange(ch)[:, None] * cs + np.arange(cw)[None, :])]
+            assert np.array_equal(got[0], got[1]), ("cfl_predict C and AVX2 differ", lw, lh, bd, i, plane, a)
+            dst[off + np.arange(ch)[:, None] * cs + np.arange(cw)[None, :]] = got[0]
+    return ocb, ocr, acs
+
+
+def make_pred_cases(rng):
+    """[(lw, lh, bd, luma, cb, cr, desc)]: per shape and depth 14 mixed blocks, of which the first four are constructed"""
+    cases = []
+    all_alphas = list(range(-16, 17))
+    turn = 0
+    for bd in (8, 10):
+        mx = (1 << bd) - 1
+        for (lw, lh) in cu.LUMA_SIZES_WH:
+            cw, ch = lw // 2, lh // 2
+            n = 14
+            luma, cb, cr, desc = cu.random_case(rng, n, lw, lh, bd)
+            l3 = luma.reshape(n, lh, lw)
+            l3[0] = rng.integers(0, mx + 1)                                   # all equal: AC = 0
+            q = (np.arange(ch)[:, None] + np.arange(cw)[None, :]) % 2 * mx    # quads alternating 0 and the maximum: |AC| = 4 max
+            l3[1] = l3[2] = np.repeat(np.repeat(q, 2, 0), 2, 1)
+            at = np.arange(ch)[:, None] * cw + np.arange(cw)[None, :]
+            desc[1]["alpha_idx"], desc[1]["alpha_signs"] = cu.alpha_to_fields(16, -16)
+            desc[2]["alpha_idx"], desc[2]["alpha_signs"] = cu.alpha_to_fields(-16, 16)
+            for i, v in ((1, mx // 2), (2, mx // 2 + 1)):
+                cb[int(desc[i]["cb_offset"]) + at] = v
+                cr[int(desc[i]["cr_offset"]) + at] = v
+            for i in range(3, n):      # the alphas in turn, so that each plane sees all 33
+                a_u, a_v = all_alphas[turn % 33], all_alphas[(turn * 7 + 5) % 33]
+                turn += 1
+                if a_u == 0 and a_v == 0:
+                    a_v = -1
+                desc[i]["alpha_idx"], desc[i]["alpha_signs"] = cu.alpha_to_fields(a_u, a_v)
+            cases.append((lw, lh, bd, luma, cb, cr, desc))
+    return cases
+
+
+def reference_decide(L, dist, bits, alpha_bits, job):
+    d, b = np.ascontiguousarray(dist, np.uint64), np.ascontiguousarray(bits.astype(np.uint64))
+    ab = np.ascontiguousarray(alpha_bits, np.int32)
+    out, masks = np.zeros(3, np.int32), np.zeros(2, np.uint64)
+    rc = L.drv_pick_alpha(b.ctypes.data, d.ctypes.data, int(job["lambda"]), ab.ctypes.data, int(job["cfl_mode_bits"]), int(job["dc_mode_bits"]),
+                          8, 8, out.ctypes.data, masks.ctypes.data, None, None)
+    assert rc == 0, rc
+    return out, masks
+
+
+def make_decision_tables(rng):
+    """(alpha_bits [2][8][2][16], group [n], dist, bits, jobs): group 0 random rates and tables of every kind; group 1 all-zero alpha
+    rates with tables on which whole runs tie, among them the dc_rd == best_rd tie"""
+    ab = np.stack([cu.random_alpha_bits(rng), np.zeros((8, 2, 16), np.int32)])
+    dist, bits, jobs = cu.random_decision_tables(rng, N_DEC_RANDOM)
+    d1, b1, j1 = cu.random_decision_tables(rng, N_DEC_TIES, kind=4)
+    j1["dc_mode_bits"][: N_DEC_TIES // 2] = j1["cfl_mode_bits"][: N_DEC_TIES // 2]
+    group = np.concatenate([np.zeros(N_DEC_RANDOM, np.int32), np.ones(N_DEC_TIES, np.int32)])
+    return ab, group, np.concatenate([dist, d1]), np.concatenate([bits, b1]), np.concatenate([jobs, j1])
+
+
+DIST_SHIFT = 4   # the fixture's tables are stored before the shift a 16x16 chroma transform would ask for ((MAX_TX_SCALE - 0) * 2 is 4)
+
+
+def coverage(cases, ab, group, dist, bits, jobs):
+    """None when the fixture covers what the module docstring lists, else what is missing (from the restatement's statistics)."""
+    for bd in (8, 10):
+        st = cu.new_stats()
+        for (lw, lh, cbd, luma, cb, cr, desc) in cases:
+            if cbd == bd:
+                cu.predict(luma, cb, cr, cb.copy(), cr.copy(), desc, lw, lh, bd, st)
+        if len(st["shapes"]) != 9:
+            return (bd, "shapes", st["shapes"])
+        if st["alphas_u"] != set(range(-16, 17)) or st["alphas_v"] != set(range(-16, 17)):
+            return (bd, "alphas", st["alphas_u"], st["alphas_v"])
+        for k in ("ac_zero", "ac_extreme", "neg_half", "clip0", "clipmax", "avg_rounds_up"):
+            if not st[k]:
+                return (bd, k)
+        if bd == 10 and not st["wide_product"]:
+            return (bd, "wide_product")
+    ds = cu.new_decision_stats()
+    for g in range(len(ab)):
+        sel = group == g
+        cu.decide_batch(dist[sel], bits[sel], DIST_SHIFT, ab[g], jobs[sel], ds)
+    if 3 not in ds["exit_c"] or not any(c > 3 for c in ds["exit_c"]) or not ds["full_runs"]:
+        return ("decision runs", ds["exit_c"], ds["full_runs"])
+    if not ds["tie_uv"] or not ds["tie_dc"] or not ds["dc_wins"] or ds["winners"] != set(range(8)):
+        return ("decision arms", ds)
+    return None
+
+
+def main():
+    assert reference_available(), "needs the reference sources and oracle/_ref/obj_all (python -c 'import __graft_entry__ as g; g.build()')"
+    with tempfile.TemporaryDirectory() as tmp:
+        L = build_driver(tmp)
+        for seed in range(20261017, 20261017 + 8):
+            rng = np.random.default_rng(seed)
+            cases = make_pred_cases(rng)
+            ab, group, dist, bits, jobs = make_decision_tables(rng)
+            missing = coverage(cases, ab, group, dist, bits, jobs)
+            if missing is None:
+                break
+            print("seed", seed, "misses", missing)
+        else:
+            raise SystemExit("no seed met the coverage conditions")
+        rows, descs, acs = [], [], []
+        arr = {k: {8: [], 10: []} for k in ("luma", "cb", "cr", "ocb", "ocr")}
+        l0, c0, d0, a0 = {8: 0, 10: 0}, {8: 0, 10: 0}, 0, 0
+        for (lw, lh, bd, luma, cb, cr, desc) in cases:
+            ocb, ocr, ac = reference_predict(L, luma, cb, cr, desc, lw, lh, bd)
+            rows.append((lw, lh, bd, d0, len(desc), l0[bd], len(luma), c0[bd], len(cb), a0, ac.size))
+            d0 += len(desc)
+            l0[bd] += len(luma)
+            c0[bd] += len(cb)
+            a0 += ac.size
+            descs.append(desc)
+            acs.append(ac.reshape(-1))
+            for k, v in (("luma", luma), ("cb", cb), ("cr", cr), ("ocb", ocb), ("ocr", ocr)):
+                arr[k][bd].append(v)
+        alpha = np.array([(i, js, p, L.drv_idx_to_alpha(i, js, p)) for i in range(256) for js in range(8) for p in range(2)], np.int16)
+        dec_out, dec_mask = np.zeros((len(jobs), 3), np.uint8), np.zeros((len(jobs), 2), np.uint64)
+        for i in range(len(jobs)):
+            dec_out[i], dec_mask[i] = reference_decide(L, dist[i] >> np.uint64(DIST_SHIFT), bits[i], ab[group[i]], jobs[i])
+    np.savez_compressed(OUT, case=np.array(rows, np.int64), desc=np.concatenate(descs), ac=np.concatenate(acs), alpha=alpha, seed=np.array([seed]),
+                        dec_alpha_bits=ab, dec_group=group, dec_job=jobs, dec_dist=dist, dec_bits=bits, dec_out=dec_out, dec_mask=dec_mask,
+                        dec_dist_shift=np.array([DIST_SHIFT]),
+                        **{f"{k}_{bd}": np.concatenate(v[bd]) for k, v in arr.items() for bd in (8, 10)})
+    print(f"wrote {OUT}: seed {seed}, {len(rows)} batches, {d0} blocks, {len(jobs)} decisions, {os.path.getsize(OUT) / 1e6:.2f} MB")
+
+
+if __name__ == "__main__":
+    main()
