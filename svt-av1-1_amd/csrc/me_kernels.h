@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
+#include "tq_tile.h"
 
 // LDS row pitch of the staged reference window.  192 B: >= 16*8 + 64 (widest lane footprint at
 // search_area_width 127) and == 48 dwords, which puts rows y, y+3, y+5, y+6 (one ds_read_b128 lane
@@ -93,6 +94,14 @@ hipError_t launch_inv_txfm2d_add(const int32_t* coeff, const svthip_itxfm_desc* 
 hipError_t launch_encode_tu(const void* src, const void* pred, void* recon, int planes_16bit, const svthip_tu_desc* desc, uint32_t n_tu,
                             int w, int h, const int16_t* qparams, const int16_t* iscan, int32_t* coeff, int32_t* qcoeff,
                             int32_t* dqcoeff, uint16_t* eob, uint64_t* energy, uint64_t* dist, uint32_t max_workgroups, hipStream_t s);
+// the instantiations of the three transform kernels whose dynamic LDS passes 64 KB (svthip_abi.hip raises their limit once per device):
+// one per size, x 2 sample types (inverse, fused), x 2 with / without distortion sums (fused)
+constexpr int kFwdTxfmDynamicLdsKernels = tx_dynamic_lds_sizes(false), kInvTxfmDynamicLdsKernels = 2 * tx_dynamic_lds_sizes(false),
+              kEncodeTuDynamicLdsKernels = 4 * tx_dynamic_lds_sizes(true);
+#define SVTHIP_LOCAL __attribute__((visibility("hidden")))  // the library's exported symbol list stays as it is
+SVTHIP_LOCAL void fwd_txfm_dynamic_lds_kernels(const void** list);
+SVTHIP_LOCAL void inv_txfm_dynamic_lds_kernels(const void** list);
+SVTHIP_LOCAL void encode_tu_dynamic_lds_kernels(const void** list);
 
 // TxSize -> width / height (TX_4X4 .. TX_64X16, Codec/EbDefinitions.h)
 __host__ __device__ inline int tx_w(int tx_size)

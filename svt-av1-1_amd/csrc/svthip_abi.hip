@@ -82,11 +82,16 @@ hipError_t g_attr_status[16];
 
 void set_kernel_attrs(int device)
 {
-    const void* kernels[5 + svthip::kConvolveDynamicLdsKernels] = {
+    constexpr int kTq = 5 + svthip::kConvolveDynamicLdsKernels, kInv = kTq + svthip::kFwdTxfmDynamicLdsKernels,
+                  kEnc = kInv + svthip::kInvTxfmDynamicLdsKernels;
+    const void* kernels[kEnc + svthip::kEncodeTuDynamicLdsKernels] = {
         reinterpret_cast<const void*>(svthip::fullpel85_kernel), reinterpret_cast<const void*>(svthip::fullpel209_kernel),
         reinterpret_cast<const void*>(svthip::bipred_pack_kernel), reinterpret_cast<const void*>(svthip::bipred_nsq_pack_kernel),
         reinterpret_cast<const void*>(svthip::subpel_planes_kernel)};
     svthip::convolve_dynamic_lds_kernels(kernels + 5);
+    svthip::fwd_txfm_dynamic_lds_kernels(kernels + kTq);
+    svthip::inv_txfm_dynamic_lds_kernels(kernels + kInv);
+    svthip::encode_tu_dynamic_lds_kernels(kernels + kEnc);
     hipError_t st = hipSuccess;
     for (const void* k : kernels) {
         hipFuncAttributes fa;

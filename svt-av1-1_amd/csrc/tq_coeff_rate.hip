@@ -200,9 +200,7 @@ __global__ __launch_bounds__(256) void coeff_rate_kernel(const svthip_coeff_rate
         if (bad) eob = 0;
         // the wave's padded level images: zero, then the clamped levels (a dword per lane and round)
         for (int i = lane; i < per_wave * img / 4; i += 64) reinterpret_cast<uint32_t*>(lv_wave)[i] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         int32_t q[MAXR][4];
         int16_t si[MAXR][4];
 #pragma unroll
@@ -227,9 +225,7 @@ __global__ __launch_bounds__(256) void coeff_rate_kernel(const svthip_coeff_rate
             const int r = p >> bwl, c = p & (Wa - 1);
             *reinterpret_cast<uint32_t*>(lv + r * stride + c) = packed;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
 
         // out-of-range contexts / modes are clamped: a bad descriptor gives a wrong rate, never a read outside the tables
         const int pt = d.plane_type ? 1 : 0, tx_type = d.tx_type & 15;
@@ -279,9 +275,7 @@ __global__ __launch_bounds__(256) void coeff_rate_kernel(const svthip_coeff_rate
             }
             bits[t] = bad ? 0xffffffffu : total;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next group clears the images this one read
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();  // the next group clears the images this one read
     }
 }
 

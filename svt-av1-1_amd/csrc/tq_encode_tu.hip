@@ -11,7 +11,7 @@
 // pixel: 1 B source + 1 B prediction + 2 B inverse-scan index in, 4 B quantised coefficient + 1 B reconstruction out
 // (+ 4 B each for the optional transform / dequantised outputs), against 28 B for the five separate passes.
 //
-// Mapping: a wave owns G = 64 / min(W, H) TUs, so the pass over the SHORTER dimension's lanes fills the wave exactly and the pass
+// Mapping (TxTile, tq_tile.h): a wave owns G = 64 / min(W, H) TUs, so the pass over the SHORTER dimension's lanes fills the wave exactly and the pass
 // over the longer one takes max / min rounds of 64 lanes (with G = 64 / max the 4:1 rectangles ran one pass at 25 % of the lanes).
 //   A  lane = (tu, column): residual column -> forward column network -> LDS tile
 //   B  lane = (tu, row):    forward row network -> coefficients (registers) -> energy of the dropped part of 64-point
@@ -42,24 +42,6 @@ namespace {
 #include "tq_inv_networks.h"
 #include "tq_quant_common.h"
 
-template <int SPAN>
-__device__ __forceinline__ uint64_t group_sum_u64(uint64_t v)
-{
-#pragma unroll
-    for (int m = 1; m < SPAN; m <<= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)v, m), hi = __shfl_xor((uint32_t)(v >> 32), m);
-        v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-template <int SPAN>
-__device__ __forceinline__ int group_max_i32(int v)
-{
-#pragma unroll
-    for (int m = 1; m < SPAN; m <<= 1) v = max(v, __shfl_xor(v, m));
-    return v;
-}
-
 // One row of a TU as N dwords at byte alignment (global_load_dword / x2 / x4; this target needs no alignment for them).
 template <int N>
 struct __attribute__((packed, aligned(1))) unaligned_row { uint32_t v[N]; };
@@ -79,14 +61,11 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
                                                         int32_t* __restrict__ dqcoeff_out, uint16_t* __restrict__ eob_out,
                                                         uint64_t* __restrict__ energy_out, uint64_t* __restrict__ dist_out)
 {
-    constexpr int W = 1 << WL, H = 1 << HL, WI = WL - 2, HI = HL - 2;
-    constexpr int MIND = W < H ? W : H, G = 64 / MIND, P = W + 1;
-    constexpr int ROUNDS_COL = G * W / 64, ROUNDS_ROW = G * H / 64;  // rounds of 64 (tu, column) / (tu, row) lanes
-    constexpr int WIN = W > 32 ? 32 : W, HIN = H > 32 ? 32 : H;
-    constexpr int SH0 = kShift[WI][HI][0], SH1 = kShift[WI][HI][1], SH2 = kShift[WI][HI][2];
-    constexpr int BITC = kCosCol[WI][HI], BITR = kCosRow[WI][HI];
-    constexpr int ISH0 = kInvShift0[WI][HI];
-    constexpr bool RECT2 = (WL - HL == 1) || (HL - WL == 1);
+    using T = TxTile<WL, HL>;
+    constexpr int W = T::W, H = T::H, G = T::G, P = T::P, WIN = T::WIN, HIN = T::HIN;
+    constexpr int SH0 = kShift[T::WI][T::HI][0], SH1 = kShift[T::WI][T::HI][1], SH2 = kShift[T::WI][T::HI][2];
+    constexpr int BITC = kCosCol[T::WI][T::HI], BITR = kCosRow[T::WI][T::HI];
+    constexpr int ISH0 = kInvShift0[T::WI][T::HI];
     constexpr int LOG_SCALE = (W * H > 256) + (W * H > 1024);  // av1_get_tx_scale (EbTransforms.h:312-316)
     extern __shared__ int32_t lds_all[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -94,16 +73,13 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
     // contiguous 1 KB pieces per instruction.  Stored straight from the row lanes, every lane's 16 bytes were their own write request at the L2
     // (64 per instruction, 256 per group of 1024 pixels), and the stamps showed the row pass -- the one that issues them -- taking half of a
     // group's time with a 4x spread (an earlier run of tools/tq_stamps_probe.py; profiles/r03_tq_stamps_16x16.txt is the current build): waves queueing at the vector-memory issue.
-    constexpr bool QSTAGE = (W == H) && W <= 32;
-    constexpr int QP_ = W + 4;                                  // staging row pitch in dwords: 16-byte rows at a stride that spreads the banks
-    constexpr int WAVE_LDS = G * H * P + (QSTAGE ? 64 * QP_ + 16 : 0);
-    int32_t* tile = lds_all + wave * WAVE_LDS;
-    int32_t* qst = tile + G * H * P;                            // [64][QP_] then coeff_offset of the group's TUs [16]
+    constexpr bool QSTAGE = T::QSTAGE;
+    constexpr int QP_ = T::QP;                                  // staging row pitch in dwords: 16-byte rows at a stride that spreads the banks
+    int32_t* tile = lds_all + wave * (T::tile_words + T::stage_words);
+    int32_t* qst = tile + T::tile_words;  // [64][QP_] then coeff_offset of the group's TUs [16]
     constexpr int BD = sizeof(PIX) == 1 ? 8 : 10, HIGHBD = sizeof(PIX) == 1 ? 0 : 1;
-    const Clamp cl_in = {-(1 << (BD + 7)), (1 << (BD + 7)) - 1};  // bd + 8 bits
-    const Clamp cl_col = {-(1 << 15), (1 << 15) - 1};             // max(bd + 6, 16) = 16 bits for bd 8 and 10
-    constexpr int32_t res_max = (1 << (7 + BD)) - 1 + (914 << (BD - 7)), pix_max = (1 << BD) - 1;
-    const uint32_t groups = (n_tu + G - 1) / G;
+    const TxLimits lim = tx_limits(BD);
+    const uint32_t groups = T::groups(n_tu);
     // Square sizes (one round per pass, the same TU on a lane in every pass): everything a group reads from memory is requested
     // AHEAD of the group, and the prediction row stays in registers (packed as loaded) for the reconstruction.  A wave walks its groups with
     // a two-step prefetch: the descriptor of the next group is requested at the top of the current one, the next group's source /
@@ -111,10 +87,9 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
     // and ~3.4 waves per SIMD the counters showed a wave issuing a quarter of its 27 k-cycle life -- descriptor, then rows, then the
     // stores, three exposed round trips -- and the vector unit busy 0.71 (profiles/r03_pmcx_tq_rows.txt).
     constexpr int PER = 4 / (int)sizeof(PIX), PBITS = 8 * (int)sizeof(PIX);  // samples per dword
-    constexpr bool HOIST = (W == H) && (sizeof(PIX) == 1 || W <= 32);
-    constexpr bool HOIST_ISCAN = HOIST && W <= 16;
+    constexpr bool HOIST = T::template HOIST<PIX>, HOIST_ISCAN = T::template HOIST_ISCAN<PIX>;
     constexpr int ROWDW = HOIST ? W / PER : 1;
-    constexpr bool PIPE = HOIST && W <= 32;  // 64x64 has no registers to spare for a second set of rows: it fetches at the top of each group
+    constexpr bool PIPE = T::PIPE;  // 64x64 has no registers to spare for a second set of rows: it fetches at the top of each group
     const uint32_t gstride = gridDim.x * 4;
     const int hg = lane / W, hi = lane % W;  // square sizes: the lane's TU of the group and its row (A0, B, D) / column (A, C)
     svthip_tu_desc d_nx{};                   // next group: descriptor ...
@@ -229,14 +204,12 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
 #pragma unroll
                 for (int c = 0; c < ROWDW; c++) ppk[c] = pv.v[c];
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
         }
         SVTHIP_STAMP(1);
         // ---- A: residual + forward column pass ----
 #pragma unroll 1
-        for (int round = 0; round < ROUNDS_COL; round++) {
+        for (int round = 0; round < T::ROUNDS_COL; round++) {
             const int t = round * 64 + lane, g = t / W, c = t % W;
             const uint32_t tu = grp * G + g;
             if (tu < n_tu) {
@@ -265,9 +238,7 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
                 for (int r = 0; r < H; r++) col[r * P] = shift_val<SH1>(y[r]);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         SVTHIP_STAMP(2);
         if constexpr (PIPE) {
             asm volatile("" : "+v"(rd_nx.a.v[0]), "+v"(rd_nx.a.v[1]), "+v"(rd_nx.a.v[2]), "+v"(rd_nx.a.v[3]), "+v"(rd_nx.b.v[0]), "+v"(rd_nx.b.v[1]),
@@ -278,7 +249,7 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
         SVTHIP_STAMP(3);
         // ---- B: forward row pass, quantiser, inverse row pass ----
 #pragma unroll 1
-        for (int round = 0; round < ROUNDS_ROW; round++) {
+        for (int round = 0; round < T::ROUNDS_ROW; round++) {
             const int t = round * 64 + lane, g = t / H, r = t % H;
             const uint32_t tu = grp * G + g;
             const bool active = tu < n_tu;
@@ -297,7 +268,7 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
 #pragma unroll
                 for (int c = 0; c < W; c++) {
                     y[c] = shift_val<SH2>(y[c]);
-                    if constexpr (RECT2) y[c] = mulrs<12>(y[c], 5793);
+                    if constexpr (T::RECT2) y[c] = mulrs<12>(y[c], 5793);
                 }
                 if constexpr (W > 32 || H > 32) {
                     int64_t e4[4] = {0, 0, 0, 0};  // four independent chains: a single one would serialise on the mad latency
@@ -354,12 +325,12 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
 #pragma unroll
                     for (int c = 0; c < WIN; c++) {
                         int32_t v = dq[c];
-                        if constexpr (RECT2) v = mulrs<12>(v, 2896);
-                        xi[c] = cl_in(v);
+                        if constexpr (T::RECT2) v = mulrs<12>(v, 2896);
+                        xi[c] = lim.in(v);
                     }
 #pragma unroll
                     for (int c = WIN; c < W; c++) xi[c] = 0;
-                    itxfm1d<W, WIN>(kr, xi, yi, cl_in);
+                    itxfm1d<W, WIN>(kr, xi, yi, lim.in);
 #pragma unroll
                     for (int c = 0; c < W; c++) {
                         if constexpr (ISH0 > 0) row[c] = rs<(ISH0 > 0 ? ISH0 : 1)>((int64_t)yi[c]);
@@ -386,9 +357,7 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         if constexpr (QSTAGE) {
             // quad q = k * 64 + lane of the group's 64 x W coefficients: row R = q / (W / 4) of the image, TU R / H, row R % H of that TU
 #pragma unroll
@@ -407,7 +376,7 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
         SVTHIP_STAMP(4);
         // ---- C: inverse column pass + reconstruction ----
 #pragma unroll 1
-        for (int round = 0; round < ROUNDS_COL; round++) {
+        for (int round = 0; round < T::ROUNDS_COL; round++) {
             const int t = round * 64 + lane, g = t / W, c = t % W;
             const uint32_t tu = grp * G + g;
             if (tu < n_tu) {
@@ -418,35 +387,29 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
                 const int32_t* col = tile + g * (H * P) + (kr == 2 ? W - 1 - c : c);
                 int32_t x[H], y[H];
 #pragma unroll
-                for (int r = 0; r < HIN; r++) x[r] = cl_col(col[r * P]);
+                for (int r = 0; r < HIN; r++) x[r] = lim.col(col[r * P]);
 #pragma unroll
                 for (int r = HIN; r < H; r++) x[r] = 0;
-                itxfm1d<H, HIN>(kc, x, y, cl_col);
+                itxfm1d<H, HIN>(kc, x, y, lim.col);
                 const PIX* p = pred + d.pred_offset + c;
                 PIX* out = recon + d.recon_offset + c;
                 const int ps = d.pred_stride, rs_ = d.recon_stride;
                 if constexpr (HOIST) {
                     int32_t* cout_ = tile + g * (H * P) + c;  // image column c, image rows (every lane has read its input column by now)
 #pragma unroll
-                    for (int r = 0; r < H; r++) {
-                        const int32_t t = rs<4>((int64_t)y[r]);
-                        cout_[flip_row<H>(r, kc) * P] = min(max(t, -res_max - 1), res_max);
-                    }
+                    for (int r = 0; r < H; r++) cout_[flip_row<H>(r, kc) * P] = lim.residual(rs<4>((int64_t)y[r]));
                 } else {
 #pragma unroll
                     for (int r = 0; r < H; r++) {
-                        int32_t t = rs<4>((int64_t)y[r]);
-                        t = min(max(t, -res_max - 1), res_max);
+                        const int32_t t = lim.residual(rs<4>((int64_t)y[r]));
                         const int rr = flip_row<H>(r, kc);
                         const int32_t v = (int32_t)p[rr * ps] + t;
-                        out[rr * rs_] = (PIX)min(max(v, 0), pix_max);
+                        out[rr * rs_] = (PIX)min(max(v, 0), lim.pix_max);
                     }
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         SVTHIP_STAMP(5);
         // ---- D (square sizes): reconstruction by rows ----
         if constexpr (HOIST) {
@@ -461,7 +424,7 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
 #pragma unroll
                     for (int k = 0; k < PER; k++) {
                         const int32_t pc = (int32_t)((ppk[c] >> (PBITS * k)) & ((1u << PBITS) - 1u));
-                        const int32_t v = min(max(pc + row[c * PER + k], 0), pix_max);
+                        const int32_t v = min(max(pc + row[c * PER + k], 0), lim.pix_max);
                         pk |= (uint32_t)v << (PBITS * k);
                     }
                     o.v[c] = pk;
@@ -474,9 +437,7 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
                     *reinterpret_cast<unaligned_row<ROWDW>*>(optr) = o;
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
         }
 #ifdef SVTHIP_TQ_STAMPS
         SVTHIP_STAMP(6);
@@ -492,19 +453,15 @@ __global__ void __launch_bounds__(256, (WL >= 6 || HL >= 6) ? 2 : 1) encode_tu_k
     }
 }
 
-template <int WL, int HL, typename PIX>
+template <typename T, typename PIX>
 hipError_t launch_one(const PIX* src, const PIX* pred, PIX* recon, const svthip_tu_desc* desc, uint32_t n_tu,
                       const int16_t* qparams, const int16_t* iscan, int32_t* coeff, int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob,
                       uint64_t* energy, uint64_t* dist, uint32_t max_wg, hipStream_t s)
 {
-    constexpr int W = 1 << WL, H = 1 << HL, MIND = W < H ? W : H, G = 64 / MIND;
-    constexpr bool QSTAGE = (W == H) && W <= 32;  // as in the kernel
-    constexpr size_t lds = (size_t)4 * (G * H * (W + 1) + (QSTAGE ? 64 * (W + 4) + 16 : 0)) * sizeof(int32_t);
-    const uint32_t groups = (n_tu + G - 1) / G;
-    uint32_t blocks = (groups + 3) / 4;
-    if (blocks > 256u * 64u) blocks = 256u * 64u;
-    constexpr bool PIPELINED = (W == H) && W <= 32;  // the kernel's PIPE: waves walk several groups, prefetching
-    if constexpr (PIPELINED) {
+    constexpr int WL = T::WL, HL = T::HL;
+    constexpr size_t lds = T::lds_bytes(true);
+    uint32_t blocks = T::blocks(n_tu);
+    if constexpr (T::PIPE) {  // waves walk several groups, prefetching
         // as many workgroups as the chip holds at once (all of one kernel variant's launches run on one GPU model)
         static const uint32_t resident = [] {
             int dev = 0, cus = 256, per_cu = 0;
@@ -517,20 +474,8 @@ hipError_t launch_one(const PIX* src, const PIX* pred, PIX* recon, const svthip_
         if (blocks > 2 * resident) blocks = resident;  // up to two rounds of workgroups there is nothing to walk
     }
     if (max_wg && blocks > max_wg) blocks = max_wg;  // SVTHIP_OPT_TQ_MAX_WORKGROUPS (every kernel form walks its groups grid-stride)
-    if (lds > 64 * 1024) {
-        static hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_tu_kernel<WL, HL, PIX, false>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        static hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_tu_kernel<WL, HL, PIX, true>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (attr0 != hipSuccess) return attr0;
-        if (attr1 != hipSuccess) return attr1;
-    }
-    if (dist)
-        hipLaunchKernelGGL((encode_tu_kernel<WL, HL, PIX, true>), dim3(blocks), dim3(256), lds, s, src, pred, recon, desc, n_tu, qparams, iscan,
-                           coeff, qcoeff, dqcoeff, eob, energy, dist);
-    else
-        hipLaunchKernelGGL((encode_tu_kernel<WL, HL, PIX, false>), dim3(blocks), dim3(256), lds, s, src, pred, recon, desc, n_tu, qparams, iscan,
-                           coeff, qcoeff, dqcoeff, eob, energy, dist);
+    const auto kernel = dist ? &encode_tu_kernel<WL, HL, PIX, true> : &encode_tu_kernel<WL, HL, PIX, false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, s, src, pred, recon, desc, n_tu, qparams, iscan, coeff, qcoeff, dqcoeff, eob, energy, dist);
     return hipGetLastError();
 }
 
@@ -539,17 +484,9 @@ hipError_t launch_sized(const PIX* src, const PIX* pred, PIX* recon, const svthi
                         const int16_t* qparams, const int16_t* iscan, int32_t* coeff, int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob,
                         uint64_t* energy, uint64_t* dist, uint32_t max_wg, hipStream_t s)
 {
-    const int key = clog2(w) * 8 + clog2(h);
-#define CASE(WL, HL) \
-    case (WL) * 8 + (HL): \
-        return launch_one<WL, HL, PIX>(src, pred, recon, desc, n_tu, qparams, iscan, coeff, qcoeff, dqcoeff, eob, energy, dist, max_wg, s)
-    switch (key) {
-        CASE(2, 2); CASE(3, 3); CASE(4, 4); CASE(5, 5); CASE(6, 6);
-        CASE(2, 3); CASE(3, 2); CASE(3, 4); CASE(4, 3); CASE(4, 5); CASE(5, 4); CASE(5, 6); CASE(6, 5);
-        CASE(2, 4); CASE(4, 2); CASE(3, 5); CASE(5, 3); CASE(4, 6); CASE(6, 4);
-        default: return hipErrorInvalidValue;
-    }
-#undef CASE
+    return tx_size_dispatch(w, h, hipErrorInvalidValue, [&](auto tile) {
+        return launch_one<decltype(tile), PIX>(src, pred, recon, desc, n_tu, qparams, iscan, coeff, qcoeff, dqcoeff, eob, energy, dist, max_wg, s);
+    });
 }
 
 }  // namespace
@@ -563,6 +500,17 @@ hipError_t launch_encode_tu(const void* src, const void* pred, void* recon, int 
                                       desc, n_tu, w, h, qparams, iscan, coeff, qcoeff, dqcoeff, eob, energy, dist, max_workgroups, s);
     return launch_sized<uint8_t>(static_cast<const uint8_t*>(src), static_cast<const uint8_t*>(pred), static_cast<uint8_t*>(recon), desc,
                                  n_tu, w, h, qparams, iscan, coeff, qcoeff, dqcoeff, eob, energy, dist, max_workgroups, s);
+}
+
+void encode_tu_dynamic_lds_kernels(const void** list)
+{
+#define ADD(WL, HL)                                                                                                                             \
+    if (TxTile<WL, HL>::lds_bytes(true) > kDefaultDynamicLdsLimit)                                                                              \
+        for (const void* k : {(const void*)&encode_tu_kernel<WL, HL, uint8_t, false>, (const void*)&encode_tu_kernel<WL, HL, uint8_t, true>,    \
+                              (const void*)&encode_tu_kernel<WL, HL, uint16_t, false>, (const void*)&encode_tu_kernel<WL, HL, uint16_t, true>}) \
+            *list++ = k;
+    SVTHIP_TX_SIZES(ADD)
+#undef ADD
 }
 
 }  // namespace svthip

@@ -5,8 +5,8 @@
 // Av1TransformConfig (:3847-3867), with the 1-D networks av1_fdct{4,8,16,32,64}_new (:1314-2762),
 // av1_fadst{4,8,16}_new (:2764-3183) and av1_fidentity{4,8,16,32}_c.
 //
-// Mapping.  One launch handles TUs of one size W x H.  A wave owns G = 64 / min(W, H) TUs at a time, so the pass whose lanes
-// run along the shorter dimension fills the wave exactly and the other pass takes max / min rounds of 64 lanes:
+// Mapping.  One launch handles TUs of one size W x H.  A wave owns G = 64 / min(W, H) TUs at a time (TxTile, tq_tile.h), so the pass whose
+// lanes run along the shorter dimension fills the wave exactly and the other pass takes max / min rounds of 64 lanes:
 //   column pass: lane = (tu, column); the lane loads its H residuals (2-byte loads, a row of a TU is contiguous across lanes),
 //                runs the whole 1-D network in registers (every index is a compile-time constant, so the arrays below are
 //                VGPRs) and writes the rounded column into the wave's LDS tile (pitch W + 1 words: conflict-free both ways);
@@ -36,22 +36,20 @@ template <int WL, int HL>
 __global__ void __launch_bounds__(256) fwd_txfm2d_kernel(const int16_t* __restrict__ residual, const svthip_txfm_desc* __restrict__ desc,
                                                          uint32_t n_tu, int32_t* __restrict__ coeff)
 {
-    constexpr int W = 1 << WL, H = 1 << HL, WI = WL - 2, HI = HL - 2;
-    constexpr int MIND = W < H ? W : H, G = 64 / MIND, P = W + 1;  // a wave owns 64 / min(W, H) TUs: see tq_encode_tu.hip
-    constexpr int ROUNDS_COL = G * W / 64, ROUNDS_ROW = G * H / 64;
-    constexpr int SH0 = kShift[WI][HI][0], SH1 = kShift[WI][HI][1], SH2 = kShift[WI][HI][2];
-    constexpr int BITC = kCosCol[WI][HI], BITR = kCosRow[WI][HI];
-    constexpr bool RECT2 = (WL - HL == 1) || (HL - WL == 1);
+    using T = TxTile<WL, HL>;
+    constexpr int W = T::W, H = T::H, G = T::G, P = T::P;
+    constexpr int SH0 = kShift[T::WI][T::HI][0], SH1 = kShift[T::WI][T::HI][1], SH2 = kShift[T::WI][T::HI][2];
+    constexpr int BITC = kCosCol[T::WI][T::HI], BITR = kCosRow[T::WI][T::HI];
     // rows of >= 16 coefficients leave through LDS with coalesced stores (measured: +10..15 % at 16x16 .. 64x64, -10 % at 4x4 / 8x8)
     constexpr bool STAGED_OUT = W >= 16;
     extern __shared__ int32_t lds_all[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int32_t* tile = lds_all + wave * (G * H * P);
-    const uint32_t groups = (n_tu + G - 1) / G;
+    int32_t* tile = lds_all + wave * T::tile_words;
+    const uint32_t groups = T::groups(n_tu);
     for (uint32_t grp = blockIdx.x * 4 + wave; grp < groups; grp += gridDim.x * 4) {
         // ---- column pass ----
 #pragma unroll 1
-        for (int round = 0; round < ROUNDS_COL; round++) {
+        for (int round = 0; round < T::ROUNDS_COL; round++) {
             const int t = round * 64 + lane, g = t / W, c = t % W;
             const uint32_t tu = grp * G + g;
             if (tu < n_tu) {
@@ -68,12 +66,10 @@ __global__ void __launch_bounds__(256) fwd_txfm2d_kernel(const int16_t* __restri
                 for (int r = 0; r < H; r++) col[r * P] = shift_val<SH1>(y[r]);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         // ---- row pass ----
 #pragma unroll 1
-        for (int round = 0; round < ROUNDS_ROW; round++) {
+        for (int round = 0; round < T::ROUNDS_ROW; round++) {
             const int t = round * 64 + lane, g = t / H, r = t % H;
             const uint32_t tu = grp * G + g;
             if (tu < n_tu) {
@@ -90,7 +86,7 @@ __global__ void __launch_bounds__(256) fwd_txfm2d_kernel(const int16_t* __restri
 #pragma unroll
                     for (int c = 0; c < W; c++) {
                         int32_t v = shift_val<SH2>(y[c]);
-                        if constexpr (RECT2) v = mulrs<12>(v, 5793);
+                        if constexpr (T::RECT2) v = mulrs<12>(v, 5793);
                         orow[c] = v;
                     }
                 } else {
@@ -101,7 +97,7 @@ __global__ void __launch_bounds__(256) fwd_txfm2d_kernel(const int16_t* __restri
 #pragma unroll
                         for (int k = 0; k < 4; k++) {
                             v[k] = shift_val<SH2>(y[c + k]);
-                            if constexpr (RECT2) v[k] = mulrs<12>(v[k], 5793);
+                            if constexpr (T::RECT2) v[k] = mulrs<12>(v[k], 5793);
                         }
                         *reinterpret_cast<int4*>(out + c) = make_int4(v[0], v[1], v[2], v[3]);
                     }
@@ -109,9 +105,7 @@ __global__ void __launch_bounds__(256) fwd_txfm2d_kernel(const int16_t* __restri
             }
         }
         if constexpr (STAGED_OUT) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             // ... and the group's coefficients leave with coalesced 16-byte stores (a TU is one contiguous run of W * H int32)
             constexpr int NQ = W * H / 4;
 #pragma unroll 4
@@ -125,47 +119,19 @@ __global__ void __launch_bounds__(256) fwd_txfm2d_kernel(const int16_t* __restri
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
     }
-}
-
-template <int WL, int HL>
-hipError_t launch_one(const int16_t* residual, const svthip_txfm_desc* desc, uint32_t n_tu, int32_t* coeff, hipStream_t s)
-{
-    constexpr int W = 1 << WL, H = 1 << HL, MIND = W < H ? W : H, G = 64 / MIND;
-    constexpr size_t lds = (size_t)4 * G * H * (W + 1) * sizeof(int32_t);
-    const uint32_t groups = (n_tu + G - 1) / G;
-    uint32_t blocks = (groups + 3) / 4;
-    if (blocks > 256u * 64u) blocks = 256u * 64u;
-    if (lds > 64 * 1024) {
-        static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_txfm2d_kernel<WL, HL>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (attr != hipSuccess) return attr;
-    }
-    hipLaunchKernelGGL((fwd_txfm2d_kernel<WL, HL>), dim3(blocks), dim3(256), lds, s, residual, desc, n_tu, coeff);
-    return hipGetLastError();
 }
 
 }  // namespace
 
-// valid (W, H): both in {4..64}, aspect ratio at most 4:1 (the 19 AV1 transform sizes)
-bool fwd_txfm2d_size_valid(int w, int h)
-{
-    const int wl = clog2(w), hl = clog2(h);
-    if ((1 << wl) != w || (1 << hl) != h || wl < 2 || wl > 6 || hl < 2 || hl > 6) return false;
-    const int dl = wl - hl;
-    return dl >= -2 && dl <= 2;
-}
+bool fwd_txfm2d_size_valid(int w, int h) { return tx_size_dispatch(w, h, false, [](auto) { return true; }); }
 
 // (size, tx_type) combinations for which the reference has a 1-D network (ADST up to 16 points, identity up to 32)
 bool fwd_txfm2d_type_valid(int w, int h, int tx_type)
 {
     if (tx_type < 0 || tx_type > 15) return false;
-    constexpr int8_t vt[16] = {0, 1, 0, 1, 2, 0, 2, 1, 2, 3, 0, 3, 1, 3, 2, 3};
-    constexpr int8_t ht[16] = {0, 0, 1, 1, 0, 2, 2, 2, 1, 3, 3, 0, 3, 1, 3, 2};
-    const int kc = vt[tx_type], kr = ht[tx_type];
+    const int kc = kVtx[tx_type], kr = kHtx[tx_type];
     if ((kc == 1 || kc == 2) && h > 16) return false;
     if ((kr == 1 || kr == 2) && w > 16) return false;
     if (kc == 3 && h > 32) return false;
@@ -176,15 +142,19 @@ bool fwd_txfm2d_type_valid(int w, int h, int tx_type)
 hipError_t launch_fwd_txfm2d(const int16_t* residual, const svthip_txfm_desc* desc, uint32_t n_tu, int w, int h, int32_t* coeff,
                              hipStream_t s)
 {
-    const int key = clog2(w) * 8 + clog2(h);
-#define CASE(WL, HL) case (WL) * 8 + (HL): return launch_one<WL, HL>(residual, desc, n_tu, coeff, s)
-    switch (key) {
-        CASE(2, 2); CASE(3, 3); CASE(4, 4); CASE(5, 5); CASE(6, 6);
-        CASE(2, 3); CASE(3, 2); CASE(3, 4); CASE(4, 3); CASE(4, 5); CASE(5, 4); CASE(5, 6); CASE(6, 5);
-        CASE(2, 4); CASE(4, 2); CASE(3, 5); CASE(5, 3); CASE(4, 6); CASE(6, 4);
-        default: return hipErrorInvalidValue;
-    }
-#undef CASE
+    return tx_size_dispatch(w, h, hipErrorInvalidValue, [&](auto tile) {
+        using T = decltype(tile);
+        hipLaunchKernelGGL((fwd_txfm2d_kernel<T::WL, T::HL>), dim3(T::blocks(n_tu)), dim3(256), T::lds_bytes(), s, residual, desc, n_tu, coeff);
+        return hipGetLastError();
+    });
+}
+
+void fwd_txfm_dynamic_lds_kernels(const void** list)
+{
+#define ADD(WL, HL) \
+    if (TxTile<WL, HL>::lds_bytes() > kDefaultDynamicLdsLimit) *list++ = reinterpret_cast<const void*>(&fwd_txfm2d_kernel<WL, HL>);
+    SVTHIP_TX_SIZES(ADD)
+#undef ADD
 }
 
 }  // namespace svthip

@@ -167,3 +167,13 @@ __device__ __forceinline__ void itxfm1d(int kind, const int32_t* x, int32_t* out
 // inv_shift_WxH[0] (EbTransforms.h:255-273) as a right-shift amount, [log2 w - 2][log2 h - 2]; shift[1] is 4 for every size
 constexpr int kInvShift0[5][5] = {{0, 0, 1, 0, 0}, {0, 1, 1, 2, 0}, {1, 1, 2, 1, 2}, {0, 2, 1, 2, 1}, {0, 0, 2, 1, 2}};
 
+// value ranges of inv_txfm2d_add_c for bit depth bd (8 or 10)
+struct TxLimits {
+    Clamp in, col;             // bd + 8 bits: row input and row stage range; max(bd + 6, 16) = 16 bits: column input and stage range
+    int32_t res_max, pix_max;  // the residual that is added to the prediction, and the sample
+    __device__ __forceinline__ int32_t residual(int32_t v) const { return min(max(v, -res_max - 1), res_max); }
+};
+__device__ __forceinline__ TxLimits tx_limits(int bd)
+{
+    return {{-(1 << (bd + 7)), (1 << (bd + 7)) - 1}, {-(1 << 15), (1 << 15) - 1}, (1 << (7 + bd)) - 1 + (914 << (bd - 7)), (1 << bd) - 1};
+}

@@ -5,8 +5,8 @@
 // (:7590-7616), reached from Av1InvTransformRecon / Av1InvTransformRecon8bit (:8344-8399) through highbd_inv_txfm_add
 // (:8252-8320); 1-D networks av1_idct{4..64}_new (:4902-7000), av1_iadst{4,8,16}_new (:5560-6100), av1_iidentity*_c.
 //
-// Mapping (mirror of tq_fwd_txfm.hip).  A wave owns G = 64 / min(W, H) TUs at a time (the pass over the longer dimension takes
-// max / min rounds of 64 lanes):
+// Mapping (mirror of tq_fwd_txfm.hip; TxTile, tq_tile.h).  A wave owns G = 64 / min(W, H) TUs at a time (the pass over the longer
+// dimension takes max / min rounds of 64 lanes):
 //   row pass:    lane = (tu, row); loads its min(W,32) dequantised coefficients (64-point dimensions are stored packed
 //                32 wide / 32 high, the rest is zero -- :7736-7760 -- so rows >= 32 are skipped and the upper inputs are
 //                compile-time zeros), 1/sqrt(2) pre-scaling for 2:1 rectangles, clamp to bd+8 bits, row network in
@@ -33,25 +33,19 @@ template <int WL, int HL, typename PIX>
 __global__ void __launch_bounds__(256) inv_txfm2d_add_kernel(const int32_t* __restrict__ coeff, const svthip_itxfm_desc* __restrict__ desc,
                                                              uint32_t n_tu, int bd, PIX* __restrict__ recon)
 {
-    constexpr int W = 1 << WL, H = 1 << HL, WI = WL - 2, HI = HL - 2;
-    constexpr int MIND = W < H ? W : H, G = 64 / MIND, P = W + 1;  // a wave owns 64 / min(W, H) TUs: see tq_encode_tu.hip
-    constexpr int ROUNDS_COL = G * W / 64, ROUNDS_ROW = G * H / 64;
-    constexpr int WIN = W > 32 ? 32 : W, HIN = H > 32 ? 32 : H;
-    constexpr int SH0 = kInvShift0[WI][HI];
-    constexpr bool RECT2 = (WL - HL == 1) || (HL - WL == 1);
+    using T = TxTile<WL, HL>;
+    constexpr int W = T::W, H = T::H, G = T::G, P = T::P, WIN = T::WIN, HIN = T::HIN;
+    constexpr int SH0 = kInvShift0[T::WI][T::HI];
     constexpr bool PACKED_RECON = sizeof(PIX) == 1 && W >= 16;  // 8-bit planes, rows of at least 16 pixels
     extern __shared__ int32_t lds_all[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int32_t* tile = lds_all + wave * (G * H * P);
-    const Clamp cl_in = {-(1 << (bd + 7)), (1 << (bd + 7)) - 1};  // bd + 8 bits: row input and row stage range
-    const Clamp cl_col = {-(1 << 15), (1 << 15) - 1};             // max(bd + 6, 16) = 16 bits for bd 8 and 10
-    const int32_t res_max = (1 << (7 + bd)) - 1 + (914 << (bd - 7));
-    const int32_t pix_max = (1 << bd) - 1;
-    const uint32_t groups = (n_tu + G - 1) / G;
+    int32_t* tile = lds_all + wave * T::tile_words;
+    const TxLimits lim = tx_limits(bd);
+    const uint32_t groups = T::groups(n_tu);
     for (uint32_t grp = blockIdx.x * 4 + wave; grp < groups; grp += gridDim.x * 4) {
         // ---- row pass ----
 #pragma unroll 1
-        for (int round = 0; round < ROUNDS_ROW; round++) {
+        for (int round = 0; round < T::ROUNDS_ROW; round++) {
             const int t = round * 64 + lane, g = t / H, r = t % H;
             const uint32_t tu = grp * G + g;
             if (tu < n_tu && r < HIN) {
@@ -66,12 +60,12 @@ __global__ void __launch_bounds__(256) inv_txfm2d_add_kernel(const int32_t* __re
                 }
 #pragma unroll
                 for (int c = 0; c < WIN; c++) {
-                    if constexpr (RECT2) x[c] = mulrs<12>(x[c], 2896);
-                    x[c] = cl_in(x[c]);
+                    if constexpr (T::RECT2) x[c] = mulrs<12>(x[c], 2896);
+                    x[c] = lim.in(x[c]);
                 }
 #pragma unroll
                 for (int c = WIN; c < W; c++) x[c] = 0;
-                itxfm1d<W, WIN>(kr, x, y, cl_in);
+                itxfm1d<W, WIN>(kr, x, y, lim.in);
                 int32_t* row = tile + g * (H * P) + r * P;
 #pragma unroll
                 for (int c = 0; c < W; c++) {
@@ -80,12 +74,10 @@ __global__ void __launch_bounds__(256) inv_txfm2d_add_kernel(const int32_t* __re
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         // ---- column pass ----
 #pragma unroll 1
-        for (int round = 0; round < ROUNDS_COL; round++) {
+        for (int round = 0; round < T::ROUNDS_COL; round++) {
             const int t = round * 64 + lane, g = t / W, c = t % W;
             const uint32_t tu = grp * G + g;
             if (tu < n_tu) {
@@ -94,36 +86,30 @@ __global__ void __launch_bounds__(256) inv_txfm2d_add_kernel(const int32_t* __re
                 const int32_t* col = tile + g * (H * P) + (kr == 2 ? W - 1 - c : c);
                 int32_t x[H], y[H];
 #pragma unroll
-                for (int r = 0; r < HIN; r++) x[r] = cl_col(col[r * P]);
+                for (int r = 0; r < HIN; r++) x[r] = lim.col(col[r * P]);
 #pragma unroll
                 for (int r = HIN; r < H; r++) x[r] = 0;
-                itxfm1d<H, HIN>(kc, x, y, cl_col);
+                itxfm1d<H, HIN>(kc, x, y, lim.col);
                 if constexpr (PACKED_RECON) {
                     // residual column back to the tile (same lane, same column); reconstruction follows four pixels per lane
                     int32_t* ocol = tile + g * (H * P) + c;
 #pragma unroll
-                    for (int r = 0; r < H; r++) {
-                        const int32_t t = rs<4>((int64_t)y[r]);
-                        ocol[flip_row<H>(r, kc) * P] = min(max(t, -res_max - 1), res_max);
-                    }
+                    for (int r = 0; r < H; r++) ocol[flip_row<H>(r, kc) * P] = lim.residual(rs<4>((int64_t)y[r]));
                 } else {
                     PIX* out = recon + d.recon_offset + c;
                     const int stride = d.recon_stride;
 #pragma unroll
                     for (int r = 0; r < H; r++) {
-                        int32_t t = rs<4>((int64_t)y[r]);
-                        t = min(max(t, -res_max - 1), res_max);
+                        const int32_t t = lim.residual(rs<4>((int64_t)y[r]));
                         PIX* p = out + flip_row<H>(r, kc) * stride;
                         const int32_t v = (int32_t)*p + t;
-                        *p = (PIX)min(max(v, 0), pix_max);
+                        *p = (PIX)min(max(v, 0), lim.pix_max);
                     }
                 }
             }
         }
         if constexpr (PACKED_RECON) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             // prediction + residual -> clip, 4 horizontally consecutive 8-bit pixels per lane (one dword load / store instead of
             // four byte loads / stores per lane); TUs whose rows are not 4-byte aligned take the byte path
             if constexpr (W * H / 4 < 64) {
@@ -182,42 +168,20 @@ __global__ void __launch_bounds__(256) inv_txfm2d_add_kernel(const int32_t* __re
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
     }
-}
-
-template <int WL, int HL, typename PIX>
-hipError_t launch_one(const int32_t* coeff, const svthip_itxfm_desc* desc, uint32_t n_tu, int bd, PIX* recon, hipStream_t s)
-{
-    constexpr int W = 1 << WL, H = 1 << HL, MIND = W < H ? W : H, G = 64 / MIND;
-    constexpr size_t lds = (size_t)4 * G * H * (W + 1) * sizeof(int32_t);
-    const uint32_t groups = (n_tu + G - 1) / G;
-    uint32_t blocks = (groups + 3) / 4;
-    if (blocks > 256u * 64u) blocks = 256u * 64u;
-    if (lds > 64 * 1024) {
-        static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_txfm2d_add_kernel<WL, HL, PIX>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (attr != hipSuccess) return attr;
-    }
-    hipLaunchKernelGGL((inv_txfm2d_add_kernel<WL, HL, PIX>), dim3(blocks), dim3(256), lds, s, coeff, desc, n_tu, bd, recon);
-    return hipGetLastError();
 }
 
 template <typename PIX>
 hipError_t launch_sized(const int32_t* coeff, const svthip_itxfm_desc* desc, uint32_t n_tu, int w, int h, int bd, PIX* recon,
                         hipStream_t s)
 {
-    const int key = clog2(w) * 8 + clog2(h);
-#define CASE(WL, HL) case (WL) * 8 + (HL): return launch_one<WL, HL, PIX>(coeff, desc, n_tu, bd, recon, s)
-    switch (key) {
-        CASE(2, 2); CASE(3, 3); CASE(4, 4); CASE(5, 5); CASE(6, 6);
-        CASE(2, 3); CASE(3, 2); CASE(3, 4); CASE(4, 3); CASE(4, 5); CASE(5, 4); CASE(5, 6); CASE(6, 5);
-        CASE(2, 4); CASE(4, 2); CASE(3, 5); CASE(5, 3); CASE(4, 6); CASE(6, 4);
-        default: return hipErrorInvalidValue;
-    }
-#undef CASE
+    return tx_size_dispatch(w, h, hipErrorInvalidValue, [&](auto tile) {
+        using T = decltype(tile);
+        hipLaunchKernelGGL((inv_txfm2d_add_kernel<T::WL, T::HL, PIX>), dim3(T::blocks(n_tu)), dim3(256), T::lds_bytes(), s, coeff, desc, n_tu, bd,
+                           recon);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -227,6 +191,16 @@ hipError_t launch_inv_txfm2d_add(const int32_t* coeff, const svthip_itxfm_desc* 
 {
     if (recon_16bit) return launch_sized<uint16_t>(coeff, desc, n_tu, w, h, bd, static_cast<uint16_t*>(recon), s);
     return launch_sized<uint8_t>(coeff, desc, n_tu, w, h, bd, static_cast<uint8_t*>(recon), s);
+}
+
+void inv_txfm_dynamic_lds_kernels(const void** list)
+{
+#define ADD(WL, HL)                                                                                                                     \
+    if (TxTile<WL, HL>::lds_bytes() > kDefaultDynamicLdsLimit)                                                                          \
+        for (const void* k : {(const void*)&inv_txfm2d_add_kernel<WL, HL, uint8_t>, (const void*)&inv_txfm2d_add_kernel<WL, HL, uint16_t>}) \
+            *list++ = k;
+    SVTHIP_TX_SIZES(ADD)
+#undef ADD
 }
 
 }  // namespace svthip

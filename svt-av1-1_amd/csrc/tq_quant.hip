@@ -56,8 +56,7 @@ __global__ void __launch_bounds__(256) quantize_b_batch_kernel(const int32_t* __
             *reinterpret_cast<int4*>(qo + base) = make_int4(qv[0], qv[1], qv[2], qv[3]);
             *reinterpret_cast<int4*>(dqo + base) = make_int4(dqv[0], dqv[1], dqv[2], dqv[3]);
         }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) last = max(last, __shfl_xor(last, m));
+        last = group_max_i32<64>(last);
         if (lane == 0) eob[tu] = (uint16_t)last;
     }
 }

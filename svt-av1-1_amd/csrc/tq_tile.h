@@ -1,0 +1,91 @@
+// svt-av1-1_amd/csrc/tq_tile.h -- what the transform / quantisation kernels and their launchers share: the list of the 19 AV1 transform
+// sizes, the tile geometry and launch plan of one size (TxTile), and the wave-level exchange and reductions.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace svthip {
+
+// (log2 W, log2 H) of the 19 AV1 transform sizes: both sides in {4..64}, aspect ratio at most 4:1
+#define SVTHIP_TX_SIZES(X)                                                                                                   \
+    X(2, 2) X(3, 3) X(4, 4) X(5, 5) X(6, 6) X(2, 3) X(3, 2) X(3, 4) X(4, 3) X(4, 5) X(5, 4) X(5, 6) X(6, 5) /* 1:1, 1:2 / 2:1 */ \
+    X(2, 4) X(4, 2) X(3, 5) X(5, 3) X(4, 6) X(6, 4)                                                         /* 1:4 / 4:1 */
+
+// One launch handles TUs of one size W x H with workgroups of four waves.  A wave owns G = 64 / min(W, H) TUs at a time in an LDS tile of
+// G * H rows at a pitch of W + 1 words (conflict-free by rows and by columns), so the pass whose lanes run along the shorter dimension fills
+// the wave exactly and the other one takes max / min rounds of 64 lanes.
+template <int WL_, int HL_>
+struct TxTile {
+    static constexpr int WL = WL_, HL = HL_, W = 1 << WL, H = 1 << HL, WI = WL - 2, HI = HL - 2;  // WI / HI index the per-size tables
+    static constexpr int MIND = W < H ? W : H, G = 64 / MIND, P = W + 1;
+    static constexpr int ROUNDS_COL = G * W / 64, ROUNDS_ROW = G * H / 64;  // rounds of 64 (tu, column) / (tu, row) lanes
+    static constexpr int WIN = W > 32 ? 32 : W, HIN = H > 32 ? 32 : H;      // 64-point dimensions keep 32 coefficients
+    static constexpr bool RECT2 = (WL - HL == 1) || (HL - WL == 1);
+    static constexpr int tile_words = G * H * P;
+    // the fused kernel (tq_encode_tu.hip; the reasons are next to the code that uses them)
+    static constexpr bool QSTAGE = (W == H) && W <= 32;  // quantised coefficients leave through a per-wave staging image ...
+    static constexpr int QP = W + 4;                     // ... [64 rows][QP] (16-byte rows at a stride that spreads the banks), then
+    static constexpr int stage_words = QSTAGE ? 64 * QP + 16 : 0;  // coeff_offset of the group's TUs [16]
+    template <typename PIX>
+    static constexpr bool HOIST = (W == H) && (sizeof(PIX) == 1 || W <= 32);  // planes touched by rows, operands fetched ahead of the passes
+    template <typename PIX>
+    static constexpr bool HOIST_ISCAN = HOIST<PIX> && W <= 16;
+    static constexpr bool PIPE = (W == H) && W <= 32;  // HOIST and a wave walks several groups, prefetching the next one
+
+    static constexpr size_t lds_bytes(bool staged = false) { return (size_t)4 * (tile_words + (staged ? stage_words : 0)) * sizeof(int32_t); }
+    static constexpr uint32_t groups(uint32_t n_tu) { return (n_tu + G - 1) / G; }
+    static constexpr uint32_t blocks(uint32_t n_tu)  // a group per wave, at most 256 CUs x 64 workgroups (the kernels walk grid-stride)
+    {
+        const uint32_t b = (groups(n_tu) + 3) / 4;
+        return b > 256u * 64u ? 256u * 64u : b;
+    }
+};
+
+// f(TxTile<WL, HL>{}) for the size w x h; `none` when it is not one of the 19
+template <typename R, typename F>
+inline R tx_size_dispatch(int w, int h, R none, F&& f)
+{
+#define SVTHIP_TX_CASE(WL, HL) if (w == (1 << WL) && h == (1 << HL)) return f(TxTile<WL, HL>{});
+    SVTHIP_TX_SIZES(SVTHIP_TX_CASE)
+#undef SVTHIP_TX_CASE
+    return none;
+}
+
+// sizes whose dynamic LDS passes what a kernel may take without a raised limit (svthip_abi.hip raises it once per device)
+constexpr size_t kDefaultDynamicLdsLimit = 64 * 1024;
+constexpr int tx_dynamic_lds_sizes(bool staged)
+{
+#define SVTHIP_TX_CASE(WL, HL) +(TxTile<WL, HL>::lds_bytes(staged) > kDefaultDynamicLdsLimit ? 1 : 0)
+    return 0 SVTHIP_TX_SIZES(SVTHIP_TX_CASE);
+#undef SVTHIP_TX_CASE
+}
+
+#ifdef __HIPCC__
+// the lanes of a wave exchange data through LDS: everything written before is visible to every lane after
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// sum / maximum over aligned groups of SPAN lanes, in every lane of the group
+template <int SPAN>
+__device__ __forceinline__ uint64_t group_sum_u64(uint64_t v)
+{
+#pragma unroll
+    for (int m = 1; m < SPAN; m <<= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, m), hi = __shfl_xor((uint32_t)(v >> 32), m);
+        v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+template <int SPAN>
+__device__ __forceinline__ int group_max_i32(int v)
+{
+#pragma unroll
+    for (int m = 1; m < SPAN; m <<= 1) v = max(v, __shfl_xor(v, m));
+    return v;
+}
+#endif
+
+}  // namespace svthip

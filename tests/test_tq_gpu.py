@@ -172,7 +172,7 @@ def test_encode_tu_optional_outputs_may_be_null(hip_ctx, oracle):
     assert np.array_equal(d_pred.cpu().numpy(), ref["recon"])
 
 
-@pytest.mark.parametrize("size", [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (16, 8), (8, 32), (64, 32)])
+@pytest.mark.parametrize("size", svtav1_hip.TX_SIZES_WH)
 def test_encode_tu16_batch_matches_oracle(hip_ctx, oracle, size):
     """Fused chain on 10-bit samples in 16-bit planes (high-bit-depth quantiser, bd = 10 inverse transform), in place."""
     torch = pytest.importorskip("torch")
@@ -201,6 +201,35 @@ def test_encode_tu16_batch_matches_oracle(hip_ctx, oracle, size):
     assert np.array_equal(d_en.cpu().numpy().view(np.uint64), ref["energy"])
     assert np.array_equal(d_dist.cpu().numpy().view(np.uint64), ref["dist"])
     assert np.array_equal(d_pred.cpu().numpy().view(np.uint16), ref["recon"])
+
+
+def test_encode_tu_on_two_devices(oracle):
+    """What a sharded host does: one process, a context on device 0 and one on device 1, the same batches on both.  64x64 and 32x32 are
+    the fused kernel's sizes whose LDS tile needs the raised dynamic-LDS limit, which is per device; 5 TUs leave a partial group."""
+    torch = pytest.importorskip("torch")
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    batches = []
+    for w in (64, 32):
+        b = random_encode_batch(np.random.default_rng(w), 5, w, w)
+        batches.append((w, b, oracle_encode_batch(oracle, b)))
+    for device in (0, 1):
+        ctx = svtav1_hip.Context(device)
+        try:
+            for w, b, ref in batches:
+                dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(f"cuda:{device}")  # noqa: E731
+                d_src, d_pred, d_desc, d_qp, d_iscan = dev(b["src"]), dev(b["pred"]), dev(b["desc"]), dev(b["qparams"]), dev(b["iscan"])
+                d_q = torch.full((5 * b["n"],), 5, dtype=torch.int32, device=f"cuda:{device}")
+                d_eob = torch.full((5,), -1, dtype=torch.int16, device=f"cuda:{device}")
+                torch.cuda.synchronize(device)
+                ctx.encode_tu_batch_dev(d_src.data_ptr(), d_pred.data_ptr(), d_pred.data_ptr(), d_desc.data_ptr(), 5, w, w, d_qp.data_ptr(),
+                                        d_iscan.data_ptr(), None, d_q.data_ptr(), None, d_eob.data_ptr(), None, None)
+                ctx.synchronize()
+                assert np.array_equal(d_q.cpu().numpy(), ref["qcoeff"]), (device, w)
+                assert np.array_equal(d_eob.cpu().numpy().view(np.uint16), ref["eob"]), (device, w)
+                assert np.array_equal(d_pred.cpu().numpy(), ref["recon"]), (device, w)
+        finally:
+            ctx.close()
 
 
 @pytest.mark.parametrize("case", [(4, 4, 8, 3001), (8, 8, 8, 1501), (16, 16, 8, 1203), (32, 32, 8, 331), (64, 64, 8, 37), (16, 8, 8, 403), (32, 64, 8, 45),
