@@ -822,6 +822,74 @@ int32_t svthip_cfl_alpha_decision_batch_dev(svthip_ctx *ctx, const uint64_t *d_d
                                             svthip_cfl_decision *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The deblocking filter of a reconstructed picture and the search for its levels (Codec/EbDeblockingFilter.c).  4:2:0, 64x64
+ * superblocks, 8 and 10 bits.  The reference never enables mode / reference deltas (EbResourceCoordinationProcess.c:615), delta_lf or
+ * segment features, so the filter level is one number per plane and direction: levels[4] = lf.filter_level[0] (luma, vertical edges),
+ * lf.filter_level[1] (luma, horizontal edges), lf.filter_level_u, lf.filter_level_v.  Every entry takes them as a DEVICE array of four
+ * int32, so that the levels a search leaves on the device feed the filter without a host round trip.
+ *
+ *   svthip_lf_mi        what set_lpf_parameters (:1004-1123) reads of a mode-info cell, one per 4x4 luma samples: sb_type and tx_size
+ *                       with the reference's enum values (BlockSize, TxSize), flags bit 0 = mbmi->skip && ref_frame[0] > INTRA_FRAME.
+ *                       The grid has at least height / 4 rows of mi_stride >= width / 4 cells (the reference's stride is
+ *                       picture_width_in_sb * 16) and describes whole blocks, also where they reach past the picture.
+ *   svthip_lf_picture   device pointers to sample (0, 0) of the three reconstructed planes (filtered in place) and, for the search
+ *                       entries, of the source planes (8 bits: enhanced_picture_ptr; 16 bits: input_frame16bit), strides in samples,
+ *                       and the luma size.  The reference works on the padded size: width and height are multiples of 8.
+ *
+ * svthip_av1_[highbd_]loop_filter_frame_dev   av1_loop_filter_frame (:1462-1501) on planes [plane_start, plane_end): luma is left
+ *     alone when both its levels are 0 and, as loop_filter_sb's loop ends there (:1409-1410), so are the planes after it in the range;
+ *     a chroma plane is left alone when its level is 0.  One pass over all vertical edges, then one over all horizontal edges, which
+ *     leaves what the reference's superblock order leaves.
+ * svthip_av1_[highbd_]loop_filter_sse_table_dev   d_sse[level], level 0 .. 63 = what try_filter_frame(level, plane, dir) (:1773-1827)
+ *     returns: the plane filtered with the candidate, PictureSseCalculations (:1608-1770) against the source over the plane.  dir 2
+ *     ties both luma directions to the candidate; dir 0 / 1 searches one and reads the other from d_levels; chroma ignores dir's
+ *     value.  The reconstruction is not written.  Exact integer sums.
+ * svthip_lf_level_walk_dev   search_filter_level's walk (:1852-1985) over a full table, one lane: the level to *d_level_out, the levels
+ *     it asked the table for as bit mask to *d_visited (may be null).  start_level is last_frame_filter_level[..] before the clamp.
+ * svthip_av1_[highbd_]pick_filter_level_dev   the LPF_PICK_FROM_FULL_IMAGE arm of av1_pick_filter_level (:2065-2091): tied luma, luma
+ *     vertical, luma horizontal, Cb, Cr, each a table and a walk, all on one stream with no host synchronisation.  d_levels receives
+ *     last_frame_filter_level first and holds the four picked levels at the end; d_sse_tables is [5][64] workspace that keeps the five
+ *     tables; d_visited ([5], may be null) the walks' masks.  As in the reference the tied search starts from
+ *     last_frame_filter_level[2] (:1847 indexes with dir == 2).  LPF_PICK_FROM_Q and LPF_PICK_MINIMAL_LPF are host arithmetic.
+ * Only the planes a call works on are read or checked: [plane_start, plane_end) for the frame filter, `plane` (recon and source) for a table,
+ * all three for the pick; the other entries of svthip_lf_picture may be null.
+ * Refused with svthip_last_error text and without a launch: a null pointer, a width or height that is 0 or no multiple of 8, a stride
+ * smaller than its plane, mi_stride < width / 4, plane > 2, dir > 2, plane_start > plane_end or plane_end > 3, sharpness > 7, a level
+ * of last_frame_filter_level outside 0 .. 63, 16-bit planes not 2-byte aligned, d_levels not 4-byte or d_sse not 8-byte aligned, a
+ * bit depth other than 10 for the highbd entries. */
+typedef struct svthip_lf_mi {
+    uint8_t sb_type, tx_size, flags, reserved;
+} svthip_lf_mi;
+
+typedef struct svthip_lf_picture {
+    void *recon[3];
+    const void *source[3];
+    uint32_t recon_stride[3], source_stride[3];
+    uint32_t width, height;
+} svthip_lf_picture;
+
+int32_t svthip_av1_loop_filter_frame_dev(svthip_ctx *ctx, const svthip_lf_picture *picture, const svthip_lf_mi *d_mi, uint32_t mi_stride,
+                                         const int32_t *d_levels, uint32_t sharpness, uint32_t plane_start, uint32_t plane_end, void *stream);
+int32_t svthip_av1_highbd_loop_filter_frame_dev(svthip_ctx *ctx, const svthip_lf_picture *picture, const svthip_lf_mi *d_mi,
+                                                uint32_t mi_stride, const int32_t *d_levels, uint32_t sharpness, uint32_t plane_start,
+                                                uint32_t plane_end, uint32_t bit_depth, void *stream);
+int32_t svthip_av1_loop_filter_sse_table_dev(svthip_ctx *ctx, const svthip_lf_picture *picture, const svthip_lf_mi *d_mi, uint32_t mi_stride,
+                                             uint32_t plane, uint32_t dir, const int32_t *d_levels, uint32_t sharpness, uint64_t *d_sse,
+                                             void *stream);
+int32_t svthip_av1_highbd_loop_filter_sse_table_dev(svthip_ctx *ctx, const svthip_lf_picture *picture, const svthip_lf_mi *d_mi,
+                                                    uint32_t mi_stride, uint32_t plane, uint32_t dir, const int32_t *d_levels,
+                                                    uint32_t sharpness, uint32_t bit_depth, uint64_t *d_sse, void *stream);
+int32_t svthip_lf_level_walk_dev(svthip_ctx *ctx, const uint64_t *d_sse, int32_t start_level, uint32_t tx_mode_is_only_4x4,
+                                 int32_t *d_level_out, uint64_t *d_visited, void *stream);
+int32_t svthip_av1_pick_filter_level_dev(svthip_ctx *ctx, const svthip_lf_picture *picture, const svthip_lf_mi *d_mi, uint32_t mi_stride,
+                                         const int32_t last_frame_filter_level[4], uint32_t sharpness, uint32_t tx_mode_is_only_4x4,
+                                         int32_t *d_levels, uint64_t *d_sse_tables, uint64_t *d_visited, void *stream);
+int32_t svthip_av1_highbd_pick_filter_level_dev(svthip_ctx *ctx, const svthip_lf_picture *picture, const svthip_lf_mi *d_mi,
+                                                uint32_t mi_stride, const int32_t last_frame_filter_level[4], uint32_t sharpness,
+                                                uint32_t tx_mode_is_only_4x4, uint32_t bit_depth, int32_t *d_levels, uint64_t *d_sse_tables,
+                                                uint64_t *d_visited, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one
  * transform type at a time from ProductFullLoopTxSearch (Codec/EbFullLoop.c:1138-1352: for every tx_type candidate of a TU:
  * Av1EstimateTransform -> Av1QuantizeInvQuantize -> distortion -> cost), encode_pass_tx_search (:1354-1550) and Av1EncodeLoop

@@ -161,6 +161,17 @@ def lib() -> C.CDLL:
     L.svthip_cfl_alpha_decision_batch_dev.restype = C.c_int32
     L.svthip_cfl_alpha_decision_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                       C.c_void_p, C.c_void_p]
+    for name, args in (("svthip_av1_loop_filter_frame_dev", [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+                       ("svthip_av1_highbd_loop_filter_frame_dev", [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p]),
+                       ("svthip_av1_loop_filter_sse_table_dev", [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+                       ("svthip_av1_highbd_loop_filter_sse_table_dev",
+                        [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+                       ("svthip_lf_level_walk_dev", [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+                       ("svthip_av1_pick_filter_level_dev", [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4),
+                       ("svthip_av1_highbd_pick_filter_level_dev",
+                        [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4)):
+        getattr(L, name).restype = C.c_int32
+        getattr(L, name).argtypes = args
     L.svthip_inter_pred_refused.restype = C.c_int32
     L.svthip_inter_pred_refused.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.svthip_motion_estimate_picture.restype = C.c_int32
@@ -921,6 +932,72 @@ Context.av1_cfl_pred_batch_dev = _av1_cfl_pred_batch_dev
 Context.av1_highbd_cfl_pred_batch_dev = _av1_highbd_cfl_pred_batch_dev
 Context.av1_cfl_alpha_candidates_batch_dev = _av1_cfl_alpha_candidates_batch_dev
 Context.cfl_alpha_decision_batch_dev = _cfl_alpha_decision_batch_dev
+
+
+# ---- the deblocking filter and its level search (svthip_av1_[highbd_]loop_filter_frame_dev, .._loop_filter_sse_table_dev,
+# svthip_lf_level_walk_dev, svthip_av1_[highbd_]pick_filter_level_dev) ----
+LF_MI_DTYPE = np.dtype([("sb_type", "u1"), ("tx_size", "u1"), ("flags", "u1"), ("reserved", "u1")])
+assert LF_MI_DTYPE.itemsize == 4
+
+
+class LfPicture(C.Structure):
+    """svthip_lf_picture: device pointers to sample (0, 0) of the planes, strides in samples, the luma size"""
+    _fields_ = [("recon", C.c_void_p * 3), ("source", C.c_void_p * 3), ("recon_stride", C.c_uint32 * 3), ("source_stride", C.c_uint32 * 3),
+                ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+def make_lf_picture(width, height, recon, recon_stride, source=(None, None, None), source_stride=(0, 0, 0)):
+    p = LfPicture()
+    for i in range(3):
+        p.recon[i], p.source[i], p.recon_stride[i], p.source_stride[i] = recon[i], source[i], recon_stride[i], source_stride[i]
+    p.width, p.height = width, height
+    return p
+
+
+def _picture_ref(picture):
+    return C.cast(C.byref(picture), C.c_void_p) if picture is not None else None
+
+
+def _av1_loop_filter_frame_dev(self, picture, d_mi, mi_stride, d_levels, sharpness, plane_start, plane_end, bit_depth=8, stream=None):
+    """av1_loop_filter_frame on planes [plane_start, plane_end) in place; d_mi a device grid of LF_MI_DTYPE, d_levels four int32 on the device."""
+    if bit_depth == 8:
+        _check(lib().svthip_av1_loop_filter_frame_dev(self._h, _picture_ref(picture), d_mi, mi_stride, d_levels, sharpness, plane_start, plane_end, stream))
+    else:
+        _check(lib().svthip_av1_highbd_loop_filter_frame_dev(self._h, _picture_ref(picture), d_mi, mi_stride, d_levels, sharpness, plane_start,
+                                                             plane_end, bit_depth, stream))
+
+
+def _av1_loop_filter_sse_table_dev(self, picture, d_mi, mi_stride, plane, direction, d_levels, sharpness, d_sse, bit_depth=8, stream=None):
+    """d_sse[64] (uint64): try_filter_frame's result for every level of (plane, direction)."""
+    if bit_depth == 8:
+        _check(lib().svthip_av1_loop_filter_sse_table_dev(self._h, _picture_ref(picture), d_mi, mi_stride, plane, direction, d_levels, sharpness, d_sse,
+                                                          stream))
+    else:
+        _check(lib().svthip_av1_highbd_loop_filter_sse_table_dev(self._h, _picture_ref(picture), d_mi, mi_stride, plane, direction, d_levels, sharpness,
+                                                                 bit_depth, d_sse, stream))
+
+
+def _lf_level_walk_dev(self, d_sse, start_level, only_4x4, d_level_out, d_visited=None, stream=None):
+    """search_filter_level's walk over a table of 64 sums: the level (int32) and the mask of the levels it asked for (uint64)."""
+    _check(lib().svthip_lf_level_walk_dev(self._h, d_sse, start_level, int(only_4x4), d_level_out, d_visited, stream))
+
+
+def _av1_pick_filter_level_dev(self, picture, d_mi, mi_stride, last_levels, sharpness, only_4x4, d_levels, d_sse_tables, d_visited=None, bit_depth=8,
+                               stream=None):
+    """av1_pick_filter_level(LPF_PICK_FROM_FULL_IMAGE): the four levels into d_levels, the five tables into d_sse_tables[5][64]."""
+    last = (C.c_int32 * 4)(*[int(v) for v in last_levels]) if last_levels is not None else None
+    if bit_depth == 8:
+        _check(lib().svthip_av1_pick_filter_level_dev(self._h, _picture_ref(picture), d_mi, mi_stride, last, sharpness, int(only_4x4), d_levels,
+                                                      d_sse_tables, d_visited, stream))
+    else:
+        _check(lib().svthip_av1_highbd_pick_filter_level_dev(self._h, _picture_ref(picture), d_mi, mi_stride, last, sharpness, int(only_4x4), bit_depth,
+                                                             d_levels, d_sse_tables, d_visited, stream))
+
+
+Context.av1_loop_filter_frame_dev = _av1_loop_filter_frame_dev
+Context.av1_loop_filter_sse_table_dev = _av1_loop_filter_sse_table_dev
+Context.lf_level_walk_dev = _lf_level_walk_dev
+Context.av1_pick_filter_level_dev = _av1_pick_filter_level_dev
 
 
 # ---- host-pointer picture and TU forms (svthip_motion_estimate_picture / svthip_open_loop_intra_search_picture / svthip_encode_tu_batch) ----
