@@ -890,6 +890,125 @@ int32_t svthip_av1_highbd_pick_filter_level_dev(svthip_ctx *ctx, const svthip_lf
                                                 uint64_t *d_visited, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Wiener loop restoration (Codec/EbRestorationPick.c, EbRestoration.c, convolve.c): the Wiener arm of restoration_seg_search
+ * (search_norestore_seg :1884-1896, search_wiener_seg :1742-1824) and av1_loop_restoration_filter_frame (EbRestoration.c:1283-1341) for
+ * units of type RESTORE_NONE and RESTORE_WIENER, 8 and 10 bits, one tile (the reference's whole_frame_rect), no superres.  Every step is
+ * integer arithmetic, the solve included, and every result is the reference's bit for bit.
+ * NOT covered, and staying on the host: self-guided restoration (search_sgrproj_seg, RESTORE_SGRPROJ units), rest_finish_search (bit
+ * counts and the double-precision RD decisions, which consume what these entries produce), CDEF, 12-bit video (get_conv_params_wiener
+ * changes round_0 there).
+ *
+ *   svthip_lr_picture   device pointers to sample (0, 0) of the CDEF'd planes (the pictures restoration filters), the deblocked planes
+ *                       (stripe boundary rows; av1_loop_restoration_save_boundary_lines is not needed on the host for this path: with one
+ *                       tile the CDEF boundary lines it saves are never read) and the source planes, strides in samples, the luma size
+ *                       (multiples of 8) and the restoration unit size per plane (EbPictureControlSet.c:32-47: luma 256 when
+ *                       width * height > 352 * 288, else 128; chroma half of it).  No plane needs a border: every read outside a plane
+ *                       is a coordinate clamp, which is what extend_frame (EbRestoration.c:241-287) and the sideways replication of
+ *                       the boundary rows (:1609-1652) amount to.
+ *   units               Unit geometry is av1_alloc_restoration_struct (:198-237) and foreach_rest_unit_in_tile (:1343-1389):
+ *                       svthip_lr_unit_geometry restates it on the host and is what the kernels' launch code uses.  Per-unit device arrays
+ *                       are indexed by unit_base[plane] + the unit's raster index in its plane, whatever planes a call works on.
+ *   taps                16 int16 per unit: WienerInfo.vfilter[8] then hfilter[8] (InterpKernel; entry 3 holds -2 * (f0 + f1 + f2), entry 7 is 0).
+ *
+ * svthip_av1_[highbd_]wiener_stats_dev   av1_compute_stats[_highbd]_c (EbRestorationPick.c:743-836) and search_norestore_seg for the units
+ *     of planes [plane_start, plane_end): d_M[unit][49], d_H[unit][49 * 49] (the first win^2 resp. win^4 entries of a row are written, H
+ *     full and symmetric; win 7 luma, 5 chroma), d_avg[unit] (find_average, EbRestorationPick.h:33-56), d_sse_none[unit].  10 bits: M and H
+ *     divided by 4 towards zero after the whole sum.  d_work: svthip_lr_workspace_bytes(units of the picture) bytes, 8-byte aligned.
+ * svthip_wiener_solve_dev   wiener_decompose_sep_sym, finalize_sym_filter, compute_score (:845-1104) for units [unit_begin, unit_end) with
+ *     one window size, one lane per unit, int64 arithmetic in the reference's order: d_taps[unit][16], d_rejected[unit] = score > 0.
+ * svthip_av1_[highbd_]wiener_trial_sse_dev   try_restoration_unit_seg (:217-246): d_sse[unit] = sse_restoration_unit of the unit filtered with
+ *     d_taps[unit] (av1_loop_restoration_filter_unit, EbRestoration.c:1172-1246; wiener_filter_stripe[_highbd] :536-554;
+ *     av1_[highbd_]wiener_convolve_add_src_c, convolve.c:64-222).  Writes no picture.  d_skip (may be null): units with a non-zero byte
+ *     are left out and their d_sse is 0.  The sum is the plain sum of squares; the reference's get_sse (EbPsnr.c:113-193) adds 32-bit
+ *     partial sums, which is the same number while each stays below 2^32.
+ * svthip_wiener_walk_init_dev / svthip_wiener_walk_step_dev   finer_tile_search_wiener_seg (:1257-1366) as a state machine, one lane per
+ *     unit: init makes the state of a walk that starts from d_taps (a rejected unit is done at once, err INT64_MAX); a step consumes
+ *     d_trial_sse[unit], the SSE of the state's taps, accepts or reverts, and leaves the next candidate in the state's taps or marks the
+ *     unit done with the best taps in place.  *d_pending (may be null) receives the number of units of the range not yet done.
+ * svthip_av1_[highbd_]search_wiener_dev   search_norestore_seg + search_wiener_seg for planes [plane_start, plane_end) on one stream with
+ *     no host synchronisation: stats, solve, walk init, then n_steps pairs of trial and step.  Resumable: the state stays in d_work; read
+ *     *d_pending and call again with resume = 1 while it is not 0.  Trial workgroups of finished units exit at once.  Outputs per unit,
+ *     final once *d_pending is 0: d_sse[unit][2] = sse[RESTORE_NONE], sse[RESTORE_WIENER] (INT64_MAX when compute_score rejects),
+ *     d_taps[unit][16] the final WienerInfo (zeros when rejected, as the reference's zeroed RestUnitSearchInfo), d_n_trials[unit].
+ *     n_steps = 0 asks for svthip_wiener_walk_max_trials(7), which no walk exceeds: the first trial; at step 4 per filter and tap one
+ *     minus attempt that fails and then at most (MAXV - MINV) / 4 plus moves (a run of minus moves is shorter); at steps 2 and 1 one
+ *     minus and one plus attempt per filter and tap: 1 + 2 * sum_p (1 + (MAXV_p - MINV_p) / 4) + 2 * 2 * 2 * 3 = 81.
+ * svthip_av1_[highbd_]loop_restoration_filter_frame_dev   av1_loop_restoration_filter_frame for planes [plane_start, plane_end), which the
+ *     caller restricts to the planes whose frame_restoration_type is not RESTORE_NONE, out of place into d_out (the reference filters
+ *     into rst_frame and copies back): RESTORE_WIENER units (d_unit_type[unit] == 1) are filtered with d_taps[unit], RESTORE_NONE units (0)
+ *     copied.  Types and taps are device arrays, so a search feeds the filter without a round trip.  A unit of another type
+ *     (RESTORE_SGRPROJ) is refused on the device: nothing of it is written and the context's refusal counter (svthip_inter_pred_refused)
+ *     counts it.
+ * Refused with svthip_last_error text and without a launch: a null pointer (planes: of the planes in range only), a width or height that
+ * is 0 or no multiple of 8, a stride smaller than its plane, a unit size other than 64, 128 or 256, plane_start >= plane_end or
+ * plane_end > 3, a bit depth other than 10 for the highbd entries, 16-bit planes not 2-byte aligned, per-unit arrays not aligned to their
+ * element, a window size other than 5 or 7, unit_begin > unit_end. */
+#define SVTHIP_RESTORE_NONE 0
+#define SVTHIP_RESTORE_WIENER 1
+#define SVTHIP_RESTORE_SGRPROJ 2
+#define SVTHIP_WIENER_STATS_M 49
+#define SVTHIP_WIENER_STATS_H (49 * 49)
+
+typedef struct svthip_lr_picture {
+    const void *cdef[3];
+    const void *deblocked[3];
+    const void *source[3];
+    uint32_t cdef_stride[3], deblocked_stride[3], source_stride[3];
+    uint32_t width, height;
+    uint32_t unit_size[3];
+} svthip_lr_picture;
+
+typedef struct svthip_wiener_walk_state {
+    int64_t err;      /* the best error so far */
+    int16_t taps[16]; /* vfilter[8], hfilter[8]: the candidate whose SSE the next step consumes; the best taps once done */
+    int8_t step;      /* 4, 2, 1 */
+    int8_t filt;      /* 0 hfilter, 1 vfilter */
+    int8_t tap;       /* p */
+    int8_t dir;       /* 0 minus, 1 plus */
+    int8_t skip;      /* a minus move of this tap was accepted */
+    int8_t first_tap; /* plane_off: 0 luma, 1 chroma */
+    int8_t started;   /* the first trial (the start taps) has been consumed */
+    uint8_t done;
+    int32_t n_trials;
+    int32_t reserved;
+} svthip_wiener_walk_state;
+
+/* unit_base[0..2]: index of each plane's first unit, unit_base[3]: units of the picture (returned as well; 0 for a bad size).
+ * limits (may be null): [units][4] h_start, h_end, v_start, v_end. */
+uint32_t svthip_lr_unit_geometry(uint32_t width, uint32_t height, const uint32_t unit_size[3], uint32_t unit_base[4], int32_t *limits);
+size_t svthip_lr_workspace_bytes(uint32_t n_units);
+uint32_t svthip_wiener_walk_max_trials(uint32_t wiener_win);
+
+int32_t svthip_av1_wiener_stats_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end, int64_t *d_M,
+                                    int64_t *d_H, int32_t *d_avg, int64_t *d_sse_none, void *d_work, void *stream);
+int32_t svthip_av1_highbd_wiener_stats_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end,
+                                           uint32_t bit_depth, int64_t *d_M, int64_t *d_H, int32_t *d_avg, int64_t *d_sse_none, void *d_work,
+                                           void *stream);
+int32_t svthip_wiener_solve_dev(svthip_ctx *ctx, const int64_t *d_M, const int64_t *d_H, uint32_t unit_begin, uint32_t unit_end,
+                                uint32_t wiener_win, int16_t *d_taps, int32_t *d_rejected, void *stream);
+int32_t svthip_av1_wiener_trial_sse_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end,
+                                        const int16_t *d_taps, const uint8_t *d_skip, int64_t *d_sse, void *stream);
+int32_t svthip_av1_highbd_wiener_trial_sse_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end,
+                                               uint32_t bit_depth, const int16_t *d_taps, const uint8_t *d_skip, int64_t *d_sse, void *stream);
+int32_t svthip_wiener_walk_init_dev(svthip_ctx *ctx, svthip_wiener_walk_state *d_state, const int16_t *d_taps, const int32_t *d_rejected,
+                                    uint32_t unit_begin, uint32_t unit_end, uint32_t wiener_win, void *stream);
+int32_t svthip_wiener_walk_step_dev(svthip_ctx *ctx, svthip_wiener_walk_state *d_state, const int64_t *d_trial_sse, uint32_t unit_begin,
+                                    uint32_t unit_end, int32_t *d_pending, void *stream);
+int32_t svthip_av1_search_wiener_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end,
+                                     uint32_t n_steps, uint32_t resume, void *d_work, int64_t *d_sse, int16_t *d_taps, int32_t *d_n_trials,
+                                     int32_t *d_pending, void *stream);
+int32_t svthip_av1_highbd_search_wiener_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end,
+                                            uint32_t bit_depth, uint32_t n_steps, uint32_t resume, void *d_work, int64_t *d_sse, int16_t *d_taps,
+                                            int32_t *d_n_trials, int32_t *d_pending, void *stream);
+int32_t svthip_av1_loop_restoration_filter_frame_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, void *const d_out[3],
+                                                     const uint32_t out_stride[3], uint32_t plane_start, uint32_t plane_end,
+                                                     const uint8_t *d_unit_type, const int16_t *d_taps, void *stream);
+int32_t svthip_av1_highbd_loop_restoration_filter_frame_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, void *const d_out[3],
+                                                            const uint32_t out_stride[3], uint32_t plane_start, uint32_t plane_end,
+                                                            uint32_t bit_depth, const uint8_t *d_unit_type, const int16_t *d_taps,
+                                                            void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one
  * transform type at a time from ProductFullLoopTxSearch (Codec/EbFullLoop.c:1138-1352: for every tx_type candidate of a TU:
  * Av1EstimateTransform -> Av1QuantizeInvQuantize -> distortion -> cost), encode_pass_tx_search (:1354-1550) and Av1EncodeLoop

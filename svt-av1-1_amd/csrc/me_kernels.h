@@ -193,6 +193,28 @@ hipError_t launch_lf_sse_table(const svthip_lf_picture& pic, const svthip_lf_mi*
 hipError_t launch_lf_walk(const uint64_t* sse, int start_level, int only_4x4, int32_t* out0, int32_t* out1, uint64_t* visited, hipStream_t s);
 hipError_t launch_lf_set_levels(int32_t* levels, const int32_t v[4], hipStream_t s);
 
+// lr_wiener.hip: Wiener loop restoration -- unit statistics, the solve, the unit filter as SSE trial and as frame filter, the refinement walk
+struct LrWorkspace {   // byte offsets into the caller's workspace, and its size
+    size_t raw, M, H, sse_none, trial_sse, state, start_taps, avg, rejected, total;
+};
+LrWorkspace lr_workspace(uint32_t n_units);
+uint32_t lr_unit_geometry(uint32_t width, uint32_t height, const uint32_t unit_size[3], uint32_t unit_base[4], int32_t* limits);
+uint32_t lr_walk_max_trials(int win);
+hipError_t launch_lr_stats(const svthip_lr_picture& pic, int plane_start, int plane_end, int bd, void* raw, int64_t* M, int64_t* H, int32_t* avg,
+                           int64_t* sse_none, hipStream_t s);
+hipError_t launch_lr_solve(const int64_t* M, const int64_t* H, uint32_t unit_begin, uint32_t unit_end, int win, int16_t* taps, int32_t* rejected,
+                           hipStream_t s);
+hipError_t launch_lr_trial(const svthip_lr_picture& pic, int plane_start, int plane_end, int bd, const void* taps, size_t taps_stride,
+                           const uint8_t* skip, size_t skip_stride, int64_t* sse, hipStream_t s);
+hipError_t launch_lr_filter_frame(const svthip_lr_picture& pic, void* const out[3], const uint32_t out_stride[3], int plane_start, int plane_end,
+                                  int bd, const uint8_t* unit_type, const int16_t* taps, uint32_t* refused, hipStream_t s);
+hipError_t launch_lr_walk_init(svthip_wiener_walk_state* state, const int16_t* taps, const int32_t* rejected, uint32_t unit_begin, uint32_t unit_end,
+                               int win, hipStream_t s);
+hipError_t launch_lr_walk_step(svthip_wiener_walk_state* state, const int64_t* trial_sse, uint32_t unit_begin, uint32_t unit_end, int32_t* pending,
+                               hipStream_t s);
+hipError_t launch_lr_search_output(const svthip_wiener_walk_state* state, const int64_t* sse_none, uint32_t unit_begin, uint32_t unit_end,
+                                   int64_t* sse, int16_t* taps, int32_t* n_trials, hipStream_t s);
+
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 
 }  // namespace svthip

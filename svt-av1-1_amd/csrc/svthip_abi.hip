@@ -684,6 +684,119 @@ int32_t lf_pick_entry(svthip_ctx* ctx, const svthip_lf_picture* pic, const svthi
     return SVTHIP_OK;
 }
 
+// The restoration entries: one check of the picture for all of them.  Only the planes [plane_start, plane_end) are looked at; the source
+// planes only where the entry compares against them.
+int32_t check_lr_args(const svthip_lr_picture* pic, int bd, bool need_source, uint32_t plane_start, uint32_t plane_end)
+{
+    TRY(check_non_null({pic}));
+    if (bd != 8 && bd != 10) return fail(SVTHIP_ERR_BAD_PARAMETER, "bit depth must be 8 or 10 (got %d)", bd);
+    if (plane_start >= plane_end || plane_end > 3)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "planes [%u, %u) are empty or not within 0..3", (unsigned)plane_start, (unsigned)plane_end);
+    if (pic->width == 0 || pic->height == 0 || (pic->width | pic->height) % 8 != 0 || pic->width > 16384 || pic->height > 16384)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "picture size must be a multiple of 8 each way, at most 16384 (got %ux%u)", (unsigned)pic->width,
+                    (unsigned)pic->height);
+    for (uint32_t p = 0; p < 3; p++)   // the unit index space spans all three planes
+        if (pic->unit_size[p] != 64 && pic->unit_size[p] != 128 && pic->unit_size[p] != 256)
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "unit size of plane %d must be 64, 128 or 256 (got %u)", (int)p, (unsigned)pic->unit_size[p]);
+    for (uint32_t p = plane_start; p < plane_end; p++) {
+        const uint32_t pw = p ? pic->width / 2 : pic->width;
+        TRY(check_non_null({pic->cdef[p], pic->deblocked[p]}));
+        if (need_source) TRY(check_non_null({pic->source[p]}));
+        if (pic->cdef_stride[p] < pw || pic->deblocked_stride[p] < pw || (need_source && pic->source_stride[p] < pw))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "stride of plane %d is smaller than its width %u", (int)p, (unsigned)pw);
+        if (bd > 8 && !aligned({pic->cdef[p], pic->deblocked[p], need_source ? pic->source[p] : nullptr}, 2))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
+    }
+    return SVTHIP_OK;
+}
+
+int32_t check_lr_units(uint32_t unit_begin, uint32_t unit_end, uint32_t win)
+{
+    if (win != 5 && win != 7) return fail(SVTHIP_ERR_BAD_PARAMETER, "wiener_win must be 5 or 7 (got %u)", (unsigned)win);
+    if (unit_begin > unit_end) return fail(SVTHIP_ERR_BAD_PARAMETER, "units [%u, %u) run backwards", (unsigned)unit_begin, (unsigned)unit_end);
+    return SVTHIP_OK;
+}
+
+int32_t lr_stats_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t ps, uint32_t pe, int bd, int64_t* d_M, int64_t* d_H, int32_t* d_avg,
+                       int64_t* d_sse_none, void* d_work, void* stream)
+{
+    TRY(check_lr_args(pic, bd, true, ps, pe));
+    TRY(check_non_null({d_M, d_H, d_avg, d_sse_none, d_work}));
+    if (!aligned({d_M, d_H, d_sse_none, d_work}, 8) || !aligned(d_avg, 4))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_M, d_H, d_sse_none and d_work must be 8-byte aligned, d_avg 4-byte");
+    HIP_TRY(svthip::launch_lr_stats(*pic, (int)ps, (int)pe, bd, d_work, d_M, d_H, d_avg, d_sse_none, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t lr_trial_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t ps, uint32_t pe, int bd, const int16_t* d_taps, const uint8_t* d_skip,
+                       int64_t* d_sse, void* stream)
+{
+    TRY(check_lr_args(pic, bd, true, ps, pe));
+    TRY(check_non_null({d_taps, d_sse}));
+    if (!aligned(d_taps, 2) || !aligned(d_sse, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_taps must be 2-byte and d_sse 8-byte aligned");
+    HIP_TRY(svthip::launch_lr_trial(*pic, (int)ps, (int)pe, bd, d_taps, 32, d_skip, 1, d_sse, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+// stats -> solve -> walk init, then n_steps x (trial of every unfinished unit -> step), all on one stream; the state lives in d_work
+int32_t lr_search_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t ps, uint32_t pe, int bd, uint32_t n_steps, uint32_t resume,
+                        void* d_work, int64_t* d_sse, int16_t* d_taps, int32_t* d_n_trials, int32_t* d_pending, void* stream)
+{
+    TRY(check_lr_args(pic, bd, true, ps, pe));
+    TRY(check_non_null({d_work, d_sse, d_taps, d_n_trials, d_pending}));
+    if (!aligned({d_work, d_sse}, 8) || !aligned({d_n_trials, d_pending}, 4) || !aligned(d_taps, 2))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_work and d_sse must be 8-byte, d_n_trials and d_pending 4-byte, d_taps 2-byte aligned");
+    uint32_t base[4];
+    svthip::lr_unit_geometry(pic->width, pic->height, pic->unit_size, base, nullptr);
+    const svthip::LrWorkspace W = svthip::lr_workspace(base[3]);
+    uint8_t* w = static_cast<uint8_t*>(d_work);
+    auto* M = reinterpret_cast<int64_t*>(w + W.M);
+    auto* H = reinterpret_cast<int64_t*>(w + W.H);
+    auto* sse_none = reinterpret_cast<int64_t*>(w + W.sse_none);
+    auto* trial = reinterpret_cast<int64_t*>(w + W.trial_sse);
+    auto* state = reinterpret_cast<svthip_wiener_walk_state*>(w + W.state);
+    auto* start = reinterpret_cast<int16_t*>(w + W.start_taps);
+    auto* avg = reinterpret_cast<int32_t*>(w + W.avg);
+    auto* rejected = reinterpret_cast<int32_t*>(w + W.rejected);
+    const uint32_t ub = base[ps], ue = base[pe];
+    hipStream_t s = call_stream(ctx, stream);
+    if (!resume) {
+        HIP_TRY(svthip::launch_lr_stats(*pic, (int)ps, (int)pe, bd, w + W.raw, M, H, avg, sse_none, s));
+        for (uint32_t p = ps; p < pe; p++) {
+            HIP_TRY(svthip::launch_lr_solve(M, H, base[p], base[p + 1], p ? 5 : 7, start, rejected, s));
+            HIP_TRY(svthip::launch_lr_walk_init(state, start, rejected, base[p], base[p + 1], p ? 5 : 7, s));
+        }
+    }
+    if (n_steps == 0) n_steps = svthip::lr_walk_max_trials(7);
+    for (uint32_t i = 0; i < n_steps; i++) {
+        HIP_TRY(svthip::launch_lr_trial(*pic, (int)ps, (int)pe, bd, state[0].taps, sizeof(svthip_wiener_walk_state), &state[0].done,
+                                        sizeof(svthip_wiener_walk_state), trial, s));
+        HIP_TRY(svthip::launch_lr_walk_step(state, trial, ub, ue, d_pending, s));
+    }
+    HIP_TRY(svthip::launch_lr_search_output(state, sse_none, ub, ue, d_sse, d_taps, d_n_trials, s));
+    return SVTHIP_OK;
+}
+
+int32_t lr_filter_frame_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, void* const d_out[3], const uint32_t out_stride[3], uint32_t ps,
+                              uint32_t pe, int bd, const uint8_t* d_unit_type, const int16_t* d_taps, void* stream)
+{
+    TRY(check_lr_args(pic, bd, false, ps, pe));
+    TRY(check_non_null({d_out, out_stride, d_unit_type, d_taps}));
+    if (!aligned(d_taps, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_taps must be 2-byte aligned");
+    for (uint32_t p = ps; p < pe; p++) {
+        TRY(check_non_null({d_out[p]}));
+        if (out_stride[p] < (p ? pic->width / 2 : pic->width))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "output stride of plane %d is smaller than its width", (int)p);
+        if (bd > 8 && !aligned(d_out[p], 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
+    }
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(scratch_on_stream(ctx, s));
+    TRY(ensure_refused_counter(ctx, s));
+    HIP_TRY(svthip::launch_lr_filter_frame(*pic, d_out, out_stride, (int)ps, (int)pe, bd, d_unit_type, d_taps, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
+    ctx->inter_stream = s;
+    return SVTHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1346,6 +1459,124 @@ int32_t svthip_av1_highbd_pick_filter_level_dev(svthip_ctx* ctx, const svthip_lf
                          d_sse_tables, d_visited, stream);
 }
 
+// Wiener loop restoration (Codec/EbRestorationPick.c:743-1104, :1257-1366, :1742-1896; EbRestoration.c:1172-1341): statistics, solve, SSE
+// trial, walk, the whole search, and the frame filter for RESTORE_NONE / RESTORE_WIENER units
+uint32_t svthip_lr_unit_geometry(uint32_t width, uint32_t height, const uint32_t unit_size[3], uint32_t unit_base[4], int32_t* limits)
+{
+    uint32_t local[4];
+    if (!unit_base) unit_base = local;
+    for (int p = 0; p < 4; p++) unit_base[p] = 0;
+    if (!unit_size || width == 0 || height == 0 || (width | height) % 8 != 0 || width > 16384 || height > 16384) return 0;
+    for (int p = 0; p < 3; p++)
+        if (unit_size[p] != 64 && unit_size[p] != 128 && unit_size[p] != 256) return 0;
+    return svthip::lr_unit_geometry(width, height, unit_size, unit_base, limits);
+}
+
+size_t svthip_lr_workspace_bytes(uint32_t n_units) { return svthip::lr_workspace(n_units).total; }
+
+uint32_t svthip_wiener_walk_max_trials(uint32_t wiener_win) { return wiener_win == 5 || wiener_win == 7 ? svthip::lr_walk_max_trials((int)wiener_win) : 0; }
+
+int32_t svthip_av1_wiener_stats_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end, int64_t* d_M,
+                                    int64_t* d_H, int32_t* d_avg, int64_t* d_sse_none, void* d_work, void* stream)
+{
+    TRY(enter(ctx));
+    return lr_stats_entry(ctx, picture, plane_start, plane_end, 8, d_M, d_H, d_avg, d_sse_none, d_work, stream);
+}
+
+int32_t svthip_av1_highbd_wiener_stats_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end,
+                                           uint32_t bit_depth, int64_t* d_M, int64_t* d_H, int32_t* d_avg, int64_t* d_sse_none, void* d_work,
+                                           void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return lr_stats_entry(ctx, picture, plane_start, plane_end, 10, d_M, d_H, d_avg, d_sse_none, d_work, stream);
+}
+
+int32_t svthip_wiener_solve_dev(svthip_ctx* ctx, const int64_t* d_M, const int64_t* d_H, uint32_t unit_begin, uint32_t unit_end, uint32_t wiener_win,
+                                int16_t* d_taps, int32_t* d_rejected, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_lr_units(unit_begin, unit_end, wiener_win));
+    TRY(check_non_null({d_M, d_H, d_taps, d_rejected}));
+    if (!aligned({d_M, d_H}, 8) || !aligned(d_rejected, 4) || !aligned(d_taps, 2))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_M and d_H must be 8-byte, d_rejected 4-byte, d_taps 2-byte aligned");
+    HIP_TRY(svthip::launch_lr_solve(d_M, d_H, unit_begin, unit_end, (int)wiener_win, d_taps, d_rejected, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_av1_wiener_trial_sse_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end,
+                                        const int16_t* d_taps, const uint8_t* d_skip, int64_t* d_sse, void* stream)
+{
+    TRY(enter(ctx));
+    return lr_trial_entry(ctx, picture, plane_start, plane_end, 8, d_taps, d_skip, d_sse, stream);
+}
+
+int32_t svthip_av1_highbd_wiener_trial_sse_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end,
+                                               uint32_t bit_depth, const int16_t* d_taps, const uint8_t* d_skip, int64_t* d_sse, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return lr_trial_entry(ctx, picture, plane_start, plane_end, 10, d_taps, d_skip, d_sse, stream);
+}
+
+int32_t svthip_wiener_walk_init_dev(svthip_ctx* ctx, svthip_wiener_walk_state* d_state, const int16_t* d_taps, const int32_t* d_rejected,
+                                    uint32_t unit_begin, uint32_t unit_end, uint32_t wiener_win, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_lr_units(unit_begin, unit_end, wiener_win));
+    TRY(check_non_null({d_state, d_taps}));
+    if (!aligned(d_state, 8) || !aligned(d_rejected, 4) || !aligned(d_taps, 2))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_state must be 8-byte, d_rejected 4-byte, d_taps 2-byte aligned");
+    HIP_TRY(svthip::launch_lr_walk_init(d_state, d_taps, d_rejected, unit_begin, unit_end, (int)wiener_win, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_wiener_walk_step_dev(svthip_ctx* ctx, svthip_wiener_walk_state* d_state, const int64_t* d_trial_sse, uint32_t unit_begin,
+                                    uint32_t unit_end, int32_t* d_pending, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_lr_units(unit_begin, unit_end, 7));
+    TRY(check_non_null({d_state, d_trial_sse}));
+    if (!aligned({d_state, d_trial_sse}, 8) || !aligned(d_pending, 4))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_state and d_trial_sse must be 8-byte, d_pending 4-byte aligned");
+    HIP_TRY(svthip::launch_lr_walk_step(d_state, d_trial_sse, unit_begin, unit_end, d_pending, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_av1_search_wiener_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end, uint32_t n_steps,
+                                     uint32_t resume, void* d_work, int64_t* d_sse, int16_t* d_taps, int32_t* d_n_trials, int32_t* d_pending,
+                                     void* stream)
+{
+    TRY(enter(ctx));
+    return lr_search_entry(ctx, picture, plane_start, plane_end, 8, n_steps, resume, d_work, d_sse, d_taps, d_n_trials, d_pending, stream);
+}
+
+int32_t svthip_av1_highbd_search_wiener_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end,
+                                            uint32_t bit_depth, uint32_t n_steps, uint32_t resume, void* d_work, int64_t* d_sse, int16_t* d_taps,
+                                            int32_t* d_n_trials, int32_t* d_pending, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return lr_search_entry(ctx, picture, plane_start, plane_end, 10, n_steps, resume, d_work, d_sse, d_taps, d_n_trials, d_pending, stream);
+}
+
+int32_t svthip_av1_loop_restoration_filter_frame_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, void* const d_out[3],
+                                                     const uint32_t out_stride[3], uint32_t plane_start, uint32_t plane_end,
+                                                     const uint8_t* d_unit_type, const int16_t* d_taps, void* stream)
+{
+    TRY(enter(ctx));
+    return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 8, d_unit_type, d_taps, stream);
+}
+
+int32_t svthip_av1_highbd_loop_restoration_filter_frame_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, void* const d_out[3],
+                                                            const uint32_t out_stride[3], uint32_t plane_start, uint32_t plane_end,
+                                                            uint32_t bit_depth, const uint8_t* d_unit_type, const int16_t* d_taps, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 10, d_unit_type, d_taps, stream);
+}
+
 int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
 {
     TRY(enter(ctx));
@@ -1360,7 +1591,7 @@ int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
     if (!n) return SVTHIP_OK;
     HIP_TRY(hipMemsetAsync(d_refused, 0, sizeof(n), s));
     *out_count = n;
-    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, or a CfL descriptor with alpha_signs > 7", (int)n);
+    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) or unit(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, a CfL descriptor with alpha_signs > 7, or a restoration unit that is neither RESTORE_NONE nor RESTORE_WIENER", (int)n);
 }
 
 // ---------------------------------------------------------------- host-pointer forms (run_queued: no transfer outlives a failed call)

@@ -1,0 +1,70 @@
+"""The Wiener loop-restoration entries are declared in include/svtav1_hip.h, exported by the library, bound by the package, and the header
+still compiles as C99 with the layouts the binding assumes (no GPU needed)."""
+import ctypes
+import os
+import re
+import subprocess
+import tempfile
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+ENTRIES = ("svthip_lr_unit_geometry", "svthip_lr_workspace_bytes", "svthip_wiener_walk_max_trials", "svthip_av1_wiener_stats_dev",
+           "svthip_av1_highbd_wiener_stats_dev", "svthip_wiener_solve_dev", "svthip_av1_wiener_trial_sse_dev", "svthip_av1_highbd_wiener_trial_sse_dev",
+           "svthip_wiener_walk_init_dev", "svthip_wiener_walk_step_dev", "svthip_av1_search_wiener_dev", "svthip_av1_highbd_search_wiener_dev",
+           "svthip_av1_loop_restoration_filter_frame_dev", "svthip_av1_highbd_loop_restoration_filter_frame_dev")
+
+
+def test_header_declares_and_library_exports_every_entry():
+    import svtav1_hip
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "svtav1_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(svthip_[a-z0-9_]+)\s*\(", text))
+    lib = ctypes.CDLL(svtav1_hip.LIB_PATH)
+    for n in ENTRIES:
+        assert n in declared, f"{n} is not declared in include/svtav1_hip.h"
+        assert hasattr(lib, n), f"{n} is not exported"
+    assert "struct svthip_lr_picture" in text and "struct svthip_wiener_walk_state" in text
+
+
+def test_header_compiles_as_c99_and_layouts_match_the_binding():
+    import svtav1_hip
+    src = """
+#include <stddef.h>
+#include "svtav1_hip.h"
+typedef char walk_state_size[sizeof(svthip_wiener_walk_state) == %d ? 1 : -1];
+typedef char walk_state_taps[offsetof(svthip_wiener_walk_state, taps) == 8 ? 1 : -1];
+typedef char walk_state_done[offsetof(svthip_wiener_walk_state, done) == %d ? 1 : -1];
+typedef char walk_state_trials[offsetof(svthip_wiener_walk_state, n_trials) == %d ? 1 : -1];
+typedef char picture_size[sizeof(svthip_lr_picture) == %d ? 1 : -1];
+typedef char picture_units[offsetof(svthip_lr_picture, unit_size) == %d ? 1 : -1];
+int main(void) { return 0; }
+""" % (svtav1_hip.WIENER_WALK_STATE_DTYPE.itemsize, svtav1_hip.WIENER_WALK_STATE_DTYPE.fields["done"][1],
+       svtav1_hip.WIENER_WALK_STATE_DTYPE.fields["n_trials"][1], ctypes.sizeof(svtav1_hip.LrPicture), svtav1_hip.LrPicture.unit_size.offset)
+    with tempfile.TemporaryDirectory() as tmp:
+        c = os.path.join(tmp, "lr_layout.c")
+        with open(c, "w") as f:
+            f.write(src)
+        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", c],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+
+
+def test_geometry_and_walk_bound_from_the_library():
+    """host functions of the library, no device: the geometry the kernels launch with and the default step count"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+
+    import lr_util as lu
+    import svtav1_hip
+    for (w, h) in ((64, 64), (200, 136), (136, 200), (392, 264), (1920, 1080), (352, 288), (360, 288), (8, 8), (96, 320), (4096, 2176)):
+        base, limits = svtav1_hip.lr_unit_geometry(w, h)
+        planes, want_base = lu.picture_units(w, h)
+        assert base == want_base and np.array_equal(limits, np.concatenate([p[0] for p in planes])), (w, h)
+    base, limits = svtav1_hip.lr_unit_geometry(200, 136, (64, 64, 64))
+    planes, want_base = lu.picture_units(200, 136, (64, 64, 64))
+    assert base == want_base and np.array_equal(limits, np.concatenate([p[0] for p in planes]))
+    assert svtav1_hip.lr_unit_geometry(200, 132)[0] == [0, 0, 0, 0] and svtav1_hip.lr_unit_geometry(200, 136, (64, 96, 64))[0] == [0, 0, 0, 0]
+    for win in (5, 7):
+        assert svtav1_hip.wiener_walk_max_trials(win) == lu.max_walk_trials(win)
+    assert svtav1_hip.wiener_walk_max_trials(7) == 81 and svtav1_hip.wiener_walk_max_trials(6) == 0
+    assert svtav1_hip.lr_workspace_bytes(40) >= 40 * (1325 + 49 + 2401 + 2) * 8
