@@ -894,9 +894,9 @@ int32_t svthip_av1_highbd_pick_filter_level_dev(svthip_ctx *ctx, const svthip_lf
  * (search_norestore_seg :1884-1896, search_wiener_seg :1742-1824) and av1_loop_restoration_filter_frame (EbRestoration.c:1283-1341) for
  * units of type RESTORE_NONE and RESTORE_WIENER, 8 and 10 bits, one tile (the reference's whole_frame_rect), no superres.  Every step is
  * integer arithmetic, the solve included, and every result is the reference's bit for bit.
- * NOT covered, and staying on the host: self-guided restoration (search_sgrproj_seg, RESTORE_SGRPROJ units), rest_finish_search (bit
- * counts and the double-precision RD decisions, which consume what these entries produce), CDEF, 12-bit video (get_conv_params_wiener
- * changes round_0 there).
+ * NOT covered, and staying on the host: rest_finish_search (bit counts and the double-precision RD decisions, which consume what these
+ * entries produce), CDEF, 12-bit video (get_conv_params_wiener changes round_0 there).  Self-guided restoration (search_sgrproj_seg,
+ * RESTORE_SGRPROJ units) is the next block.
  *
  *   svthip_lr_picture   device pointers to sample (0, 0) of the CDEF'd planes (the pictures restoration filters), the deblocked planes
  *                       (stripe boundary rows; av1_loop_restoration_save_boundary_lines is not needed on the host for this path: with one
@@ -938,7 +938,7 @@ int32_t svthip_av1_highbd_pick_filter_level_dev(svthip_ctx *ctx, const svthip_lf
  *     into rst_frame and copies back): RESTORE_WIENER units (d_unit_type[unit] == 1) are filtered with d_taps[unit], RESTORE_NONE units (0)
  *     copied.  Types and taps are device arrays, so a search feeds the filter without a round trip.  A unit of another type
  *     (RESTORE_SGRPROJ) is refused on the device: nothing of it is written and the context's refusal counter (svthip_inter_pred_refused)
- *     counts it.
+ *     counts it; svthip_av1_[highbd_]lr_filter_frame_dev below filters such units too.
  * Refused with svthip_last_error text and without a launch: a null pointer (planes: of the planes in range only), a width or height that
  * is 0 or no multiple of 8, a stride smaller than its plane, a unit size other than 64, 128 or 256, plane_start >= plane_end or
  * plane_end > 3, a bit depth other than 10 for the highbd entries, 16-bit planes not 2-byte aligned, per-unit arrays not aligned to their
@@ -1007,6 +1007,83 @@ int32_t svthip_av1_highbd_loop_restoration_filter_frame_dev(svthip_ctx *ctx, con
                                                             const uint32_t out_stride[3], uint32_t plane_start, uint32_t plane_end,
                                                             uint32_t bit_depth, const uint8_t *d_unit_type, const int16_t *d_taps,
                                                             void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Self-guided loop restoration (Codec/EbRestorationPick.c, EbRestoration.c): the self-guided arm of restoration_seg_search
+ * (search_sgrproj_seg :1670-1706, search_selfguided_restoration :627-670) and av1_loop_restoration_filter_frame for RESTORE_SGRPROJ units,
+ * on the svthip_lr_picture, unit geometry and per-unit indexing of the Wiener block above; 8 and 10 bits.  Every result is the reference's
+ * bit for bit: the filter is integer arithmetic, the five sums of the projection are exact integers (the reference adds them in double,
+ * where they are exact too), and the 2 x 2 solve is IEEE double in the reference's order of operations without fused multiply-adds.
+ * NOT covered, and staying on the host: rest_finish_search, CDEF, 12-bit video, superres, more than one tile.
+ *
+ * Two geometries.  The search filters a unit in processing units (64 x 64 luma, 32 x 32 chroma) anchored at the unit's corner and reads
+ * its 3-sample border from the CDEF'd plane itself (apply_sgr :602-625).  The unit filter and its SSE trial work stripe by stripe with
+ * the stripe rule of the Wiener unit filter, column blocks of a processing unit's width from the unit's h_start
+ * (av1_loop_restoration_filter_unit, EbRestoration.c:1172-1246; sgrproj_filter_stripe[_highbd] :1105-1156).
+ *
+ * svthip_sgrproj_workspace_bytes   bytes of d_work for a picture of this size (any unit sizes): 64 bytes per sample of the three planes
+ *     (flt - u of 16 sets x 2 filters as int16) plus the per-(unit, set) records.
+ * svthip_sgrproj_walk_max_trials   131: the first trial; at step 2 at most 63 trials per parameter (a run of accepted moves spans at
+ *     most MAX - MIN = 127, i.e. 63 moves, and a failing trial takes the place of one); at step 1 a minus and a plus trial per parameter.
+ * svthip_av1_[highbd_]selfguided_restoration_dev   av1_selfguided_restoration_c (EbRestoration.c:1026-1064) over plane `plane` in search
+ *     geometry for parameter set ep: d_flt0 / d_flt1 [rows][flt_stride] int32.  The plane of a radius that is 0 (sets 10-13: flt0, 14-15:
+ *     flt1) is not written and its pointer may be null.
+ * svthip_sgrproj_solve_dev   the tail of get_proj_subspace_c (:544-580) and encode_xq (:583-599), one lane per job: from
+ *     d_sums[n][5] = sum f0 f0, sum f1 f1, sum f0 f1, sum f0 s, sum f1 s (f = flt - u, 0 for a radius of 0; s = (src << 4) - u),
+ *     d_size[n] = samples of the unit and d_ep[n] (only the low four bits are read): d_xq[n][2] and d_xqd[n][2].
+ * svthip_sgrproj_walk_table_dev   finer_search_pixel_proj_error (:420-481, start_step 2) with a table lookup as the error of a trial:
+ *     d_err[n][128][128] indexed [xqd0 - SGRPROJ_PRJ_MIN0][xqd1 - SGRPROJ_PRJ_MIN1], start at d_start_xqd[n][2] (clamped to the ranges):
+ *     d_xqd[n][2], d_best_err[n], d_n_trials[n].  The same device function walks in the search; this entry pins ties, range stops and
+ *     the `skip` break on constructed tables.
+ * svthip_av1_[highbd_]search_sgrproj_dev   search_sgrproj_seg for the units of planes [plane_start, plane_end) on one stream with no host
+ *     synchronisation: d_sgrproj[unit][4] = ep, xqd[0], xqd[1], 0 of the best set (strict <, sets ascending), d_sse[unit] =
+ *     sse[RESTORE_SGRPROJ] (try_restoration_unit_seg of that filter).  d_detail (may be null): [unit][16] records of every set.
+ *     d_work: svthip_sgrproj_workspace_bytes(width, height) bytes, 8-byte aligned.
+ * svthip_av1_[highbd_]sgrproj_trial_sse_dev   try_restoration_unit_seg (:217-246) for RESTORE_SGRPROJ units with d_sgrproj[unit][4]:
+ *     d_sse[unit]; writes no picture; d_skip as in the Wiener trial.  A set above 15 or an xqd outside its range: d_sse[unit] = -1.
+ * svthip_av1_[highbd_]lr_filter_frame_dev   av1_loop_restoration_filter_frame for all three unit types: RESTORE_NONE copied,
+ *     RESTORE_WIENER filtered with d_taps[unit], RESTORE_SGRPROJ with d_sgrproj[unit].  d_sgrproj may be null only if no unit is
+ *     RESTORE_SGRPROJ and d_taps only if none is RESTORE_WIENER: such a unit is then refused on the device (nothing of it is written, the
+ *     context's refusal counter counts it), as is a unit of an unknown type, a set above 15 or an xqd outside SGRPROJ_PRJ_MIN / MAX.
+ *     svthip_av1_[highbd_]loop_restoration_filter_frame_dev is this entry with d_sgrproj null.
+ * Refused with svthip_last_error text and without a launch: what the Wiener entries refuse, and: plane or ep out of range for the plane
+ * entry, a flt_stride below the plane's width, arrays not aligned to their element. */
+typedef struct svthip_sgrproj_detail {
+    int64_t sums[5];      /* sum f0 f0, f1 f1, f0 f1, f0 s, f1 s */
+    int32_t exq[2];       /* get_proj_subspace */
+    int32_t start_xqd[2]; /* encode_xq */
+    int32_t xqd[2];       /* after the walk */
+    int64_t err;
+    int32_t n_trials;
+    int32_t reserved;
+} svthip_sgrproj_detail;
+
+size_t svthip_sgrproj_workspace_bytes(uint32_t width, uint32_t height);
+uint32_t svthip_sgrproj_walk_max_trials(void);
+int32_t svthip_av1_selfguided_restoration_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane, uint32_t ep, int32_t *d_flt0,
+                                              int32_t *d_flt1, uint32_t flt_stride, void *stream);
+int32_t svthip_av1_highbd_selfguided_restoration_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane, uint32_t bit_depth,
+                                                     uint32_t ep, int32_t *d_flt0, int32_t *d_flt1, uint32_t flt_stride, void *stream);
+int32_t svthip_sgrproj_solve_dev(svthip_ctx *ctx, const int64_t *d_sums, const int32_t *d_size, const int32_t *d_ep, uint32_t n, int32_t *d_xq,
+                                 int32_t *d_xqd, void *stream);
+int32_t svthip_sgrproj_walk_table_dev(svthip_ctx *ctx, const int64_t *d_err, const int32_t *d_ep, const int32_t *d_start_xqd, uint32_t n,
+                                      int32_t *d_xqd, int64_t *d_best_err, int32_t *d_n_trials, void *stream);
+int32_t svthip_av1_search_sgrproj_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end, void *d_work,
+                                      int32_t *d_sgrproj, int64_t *d_sse, svthip_sgrproj_detail *d_detail, void *stream);
+int32_t svthip_av1_highbd_search_sgrproj_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end,
+                                             uint32_t bit_depth, void *d_work, int32_t *d_sgrproj, int64_t *d_sse,
+                                             svthip_sgrproj_detail *d_detail, void *stream);
+int32_t svthip_av1_sgrproj_trial_sse_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end,
+                                         const int32_t *d_sgrproj, const uint8_t *d_skip, int64_t *d_sse, void *stream);
+int32_t svthip_av1_highbd_sgrproj_trial_sse_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t plane_start, uint32_t plane_end,
+                                                uint32_t bit_depth, const int32_t *d_sgrproj, const uint8_t *d_skip, int64_t *d_sse,
+                                                void *stream);
+int32_t svthip_av1_lr_filter_frame_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, void *const d_out[3], const uint32_t out_stride[3],
+                                       uint32_t plane_start, uint32_t plane_end, const uint8_t *d_unit_type, const int16_t *d_taps,
+                                       const int32_t *d_sgrproj, void *stream);
+int32_t svthip_av1_highbd_lr_filter_frame_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, void *const d_out[3],
+                                              const uint32_t out_stride[3], uint32_t plane_start, uint32_t plane_end, uint32_t bit_depth,
+                                              const uint8_t *d_unit_type, const int16_t *d_taps, const int32_t *d_sgrproj, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one

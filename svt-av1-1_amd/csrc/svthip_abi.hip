@@ -777,12 +777,16 @@ int32_t lr_search_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t 
     return SVTHIP_OK;
 }
 
+// all_types: the entry for the three unit types, where d_taps and d_sgrproj may each be null (a unit that needs the missing one is refused
+// on the device); otherwise the Wiener-only entry, which has no d_sgrproj and needs d_taps
 int32_t lr_filter_frame_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, void* const d_out[3], const uint32_t out_stride[3], uint32_t ps,
-                              uint32_t pe, int bd, const uint8_t* d_unit_type, const int16_t* d_taps, void* stream)
+                              uint32_t pe, int bd, const uint8_t* d_unit_type, const int16_t* d_taps, const int32_t* d_sgrproj, bool all_types,
+                              void* stream)
 {
     TRY(check_lr_args(pic, bd, false, ps, pe));
-    TRY(check_non_null({d_out, out_stride, d_unit_type, d_taps}));
-    if (!aligned(d_taps, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_taps must be 2-byte aligned");
+    TRY(check_non_null({d_out, out_stride, d_unit_type}));
+    if (!all_types) TRY(check_non_null({d_taps}));
+    if (!aligned(d_taps, 2) || !aligned(d_sgrproj, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_taps must be 2-byte and d_sgrproj 4-byte aligned");
     for (uint32_t p = ps; p < pe; p++) {
         TRY(check_non_null({d_out[p]}));
         if (out_stride[p] < (p ? pic->width / 2 : pic->width))
@@ -792,8 +796,45 @@ int32_t lr_filter_frame_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, voi
     hipStream_t s = call_stream(ctx, stream);
     TRY(scratch_on_stream(ctx, s));
     TRY(ensure_refused_counter(ctx, s));
-    HIP_TRY(svthip::launch_lr_filter_frame(*pic, d_out, out_stride, (int)ps, (int)pe, bd, d_unit_type, d_taps, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
+    HIP_TRY(svthip::launch_lr_filter_frame(*pic, d_out, out_stride, (int)ps, (int)pe, bd, d_unit_type, d_taps, d_sgrproj, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
     ctx->inter_stream = s;
+    return SVTHIP_OK;
+}
+
+// the self-guided entries: the picture through check_lr_args like the Wiener entries
+int32_t sgr_plane_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t plane, int bd, uint32_t ep, int32_t* d_flt0, int32_t* d_flt1,
+                        uint32_t flt_stride, void* stream)
+{
+    if (plane > 2) return fail(SVTHIP_ERR_BAD_PARAMETER, "plane must be 0..2 (got %u)", (unsigned)plane);
+    TRY(check_lr_args(pic, bd, false, plane, plane + 1));
+    if (ep > 15) return fail(SVTHIP_ERR_BAD_PARAMETER, "ep must be 0..15 (got %u)", (unsigned)ep);
+    const bool r0 = !(ep >= 10 && ep < 14), r1 = ep < 14;
+    if (r0) TRY(check_non_null({d_flt0}));
+    if (r1) TRY(check_non_null({d_flt1}));
+    if (!aligned({d_flt0, d_flt1}, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_flt0 and d_flt1 must be 4-byte aligned");
+    if (flt_stride < (plane ? pic->width / 2 : pic->width)) return fail(SVTHIP_ERR_BAD_PARAMETER, "flt_stride is smaller than the width of plane %u", (unsigned)plane);
+    HIP_TRY(svthip::launch_sgr_plane(*pic, (int)plane, bd, (int)ep, d_flt0, d_flt1, flt_stride, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t sgr_search_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t ps, uint32_t pe, int bd, void* d_work, int32_t* d_sgrproj, int64_t* d_sse,
+                         svthip_sgrproj_detail* d_detail, void* stream)
+{
+    TRY(check_lr_args(pic, bd, true, ps, pe));
+    TRY(check_non_null({d_work, d_sgrproj, d_sse}));
+    if (!aligned({d_work, d_sse, d_detail}, 8) || !aligned(d_sgrproj, 4))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_work, d_sse and d_detail must be 8-byte, d_sgrproj 4-byte aligned");
+    HIP_TRY(svthip::launch_sgr_search(*pic, (int)ps, (int)pe, bd, d_work, d_sgrproj, d_sse, d_detail, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t sgr_trial_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t ps, uint32_t pe, int bd, const int32_t* d_sgrproj, const uint8_t* d_skip,
+                        int64_t* d_sse, void* stream)
+{
+    TRY(check_lr_args(pic, bd, true, ps, pe));
+    TRY(check_non_null({d_sgrproj, d_sse}));
+    if (!aligned(d_sgrproj, 4) || !aligned(d_sse, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sgrproj must be 4-byte and d_sse 8-byte aligned");
+    HIP_TRY(svthip::launch_sgr_trial(*pic, (int)ps, (int)pe, bd, d_sgrproj, d_skip, d_sse, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 
@@ -1565,7 +1606,7 @@ int32_t svthip_av1_loop_restoration_filter_frame_dev(svthip_ctx* ctx, const svth
                                                      const uint8_t* d_unit_type, const int16_t* d_taps, void* stream)
 {
     TRY(enter(ctx));
-    return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 8, d_unit_type, d_taps, stream);
+    return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 8, d_unit_type, d_taps, nullptr, false, stream);
 }
 
 int32_t svthip_av1_highbd_loop_restoration_filter_frame_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, void* const d_out[3],
@@ -1574,7 +1615,98 @@ int32_t svthip_av1_highbd_loop_restoration_filter_frame_dev(svthip_ctx* ctx, con
 {
     TRY(enter(ctx));
     TRY(check_bit_depth_10(bit_depth));
-    return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 10, d_unit_type, d_taps, stream);
+    return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 10, d_unit_type, d_taps, nullptr, false, stream);
+}
+
+// Self-guided loop restoration (Codec/EbRestorationPick.c:248-670, :1670-1706; EbRestoration.c:731-1246): the box filter over a plane, the
+// projection solve, the walk on a table, the whole search, the SSE trial, and the frame filter for all three unit types
+size_t svthip_sgrproj_workspace_bytes(uint32_t width, uint32_t height) { return svthip::sgr_workspace(width, height).total; }
+
+uint32_t svthip_sgrproj_walk_max_trials(void) { return svthip::sgr_walk_max_trials(); }
+
+int32_t svthip_av1_selfguided_restoration_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane, uint32_t ep, int32_t* d_flt0,
+                                              int32_t* d_flt1, uint32_t flt_stride, void* stream)
+{
+    TRY(enter(ctx));
+    return sgr_plane_entry(ctx, picture, plane, 8, ep, d_flt0, d_flt1, flt_stride, stream);
+}
+
+int32_t svthip_av1_highbd_selfguided_restoration_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane, uint32_t bit_depth, uint32_t ep,
+                                                     int32_t* d_flt0, int32_t* d_flt1, uint32_t flt_stride, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return sgr_plane_entry(ctx, picture, plane, 10, ep, d_flt0, d_flt1, flt_stride, stream);
+}
+
+int32_t svthip_sgrproj_solve_dev(svthip_ctx* ctx, const int64_t* d_sums, const int32_t* d_size, const int32_t* d_ep, uint32_t n, int32_t* d_xq,
+                                 int32_t* d_xqd, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_non_null({d_sums, d_size, d_ep, d_xq, d_xqd}));
+    if (!aligned(d_sums, 8) || !aligned({d_size, d_ep, d_xq, d_xqd}, 4))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sums must be 8-byte, d_size, d_ep, d_xq and d_xqd 4-byte aligned");
+    HIP_TRY(svthip::launch_sgr_solve(d_sums, d_size, d_ep, n, d_xq, d_xqd, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_sgrproj_walk_table_dev(svthip_ctx* ctx, const int64_t* d_err, const int32_t* d_ep, const int32_t* d_start_xqd, uint32_t n, int32_t* d_xqd,
+                                      int64_t* d_best_err, int32_t* d_n_trials, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_non_null({d_err, d_ep, d_start_xqd, d_xqd, d_best_err, d_n_trials}));
+    if (!aligned({d_err, d_best_err}, 8) || !aligned({d_ep, d_start_xqd, d_xqd, d_n_trials}, 4))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_err and d_best_err must be 8-byte, d_ep, d_start_xqd, d_xqd and d_n_trials 4-byte aligned");
+    HIP_TRY(svthip::launch_sgr_walk_table(d_err, d_ep, d_start_xqd, n, d_xqd, d_best_err, d_n_trials, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_av1_search_sgrproj_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end, void* d_work,
+                                      int32_t* d_sgrproj, int64_t* d_sse, svthip_sgrproj_detail* d_detail, void* stream)
+{
+    TRY(enter(ctx));
+    return sgr_search_entry(ctx, picture, plane_start, plane_end, 8, d_work, d_sgrproj, d_sse, d_detail, stream);
+}
+
+int32_t svthip_av1_highbd_search_sgrproj_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end,
+                                             uint32_t bit_depth, void* d_work, int32_t* d_sgrproj, int64_t* d_sse, svthip_sgrproj_detail* d_detail,
+                                             void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return sgr_search_entry(ctx, picture, plane_start, plane_end, 10, d_work, d_sgrproj, d_sse, d_detail, stream);
+}
+
+int32_t svthip_av1_sgrproj_trial_sse_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end,
+                                         const int32_t* d_sgrproj, const uint8_t* d_skip, int64_t* d_sse, void* stream)
+{
+    TRY(enter(ctx));
+    return sgr_trial_entry(ctx, picture, plane_start, plane_end, 8, d_sgrproj, d_skip, d_sse, stream);
+}
+
+int32_t svthip_av1_highbd_sgrproj_trial_sse_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t plane_start, uint32_t plane_end,
+                                                uint32_t bit_depth, const int32_t* d_sgrproj, const uint8_t* d_skip, int64_t* d_sse, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return sgr_trial_entry(ctx, picture, plane_start, plane_end, 10, d_sgrproj, d_skip, d_sse, stream);
+}
+
+int32_t svthip_av1_lr_filter_frame_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, void* const d_out[3], const uint32_t out_stride[3],
+                                       uint32_t plane_start, uint32_t plane_end, const uint8_t* d_unit_type, const int16_t* d_taps,
+                                       const int32_t* d_sgrproj, void* stream)
+{
+    TRY(enter(ctx));
+    return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 8, d_unit_type, d_taps, d_sgrproj, true, stream);
+}
+
+int32_t svthip_av1_highbd_lr_filter_frame_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, void* const d_out[3], const uint32_t out_stride[3],
+                                              uint32_t plane_start, uint32_t plane_end, uint32_t bit_depth, const uint8_t* d_unit_type,
+                                              const int16_t* d_taps, const int32_t* d_sgrproj, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 10, d_unit_type, d_taps, d_sgrproj, true, stream);
 }
 
 int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
@@ -1591,7 +1723,7 @@ int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
     if (!n) return SVTHIP_OK;
     HIP_TRY(hipMemsetAsync(d_refused, 0, sizeof(n), s));
     *out_count = n;
-    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) or unit(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, a CfL descriptor with alpha_signs > 7, or a restoration unit that is neither RESTORE_NONE nor RESTORE_WIENER", (int)n);
+    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) or unit(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, a CfL descriptor with alpha_signs > 7, or a restoration unit that is neither RESTORE_NONE nor RESTORE_WIENER (svthip_av1_[highbd_]lr_filter_frame_dev: a unit of an unknown type, one whose taps or self-guided parameters the call was not given, or self-guided parameters out of range)", (int)n);
 }
 
 // ---------------------------------------------------------------- host-pointer forms (run_queued: no transfer outlives a failed call)

@@ -181,7 +181,15 @@ def lib() -> C.CDLL:
                        ("svthip_av1_search_wiener_dev", [V, V, U, U, U, U] + [V] * 6),
                        ("svthip_av1_highbd_search_wiener_dev", [V, V, U, U, U, U, U] + [V] * 6),
                        ("svthip_av1_loop_restoration_filter_frame_dev", [V, V, V, V, U, U, V, V, V]),
-                       ("svthip_av1_highbd_loop_restoration_filter_frame_dev", [V, V, V, V, U, U, U, V, V, V])):
+                       ("svthip_av1_highbd_loop_restoration_filter_frame_dev", [V, V, V, V, U, U, U, V, V, V]),
+                       ("svthip_av1_selfguided_restoration_dev", [V, V, U, U, V, V, U, V]),
+                       ("svthip_av1_highbd_selfguided_restoration_dev", [V, V, U, U, U, V, V, U, V]),
+                       ("svthip_sgrproj_solve_dev", [V, V, V, V, U, V, V, V]), ("svthip_sgrproj_walk_table_dev", [V, V, V, V, U, V, V, V, V]),
+                       ("svthip_av1_search_sgrproj_dev", [V, V, U, U] + [V] * 5), ("svthip_av1_highbd_search_sgrproj_dev", [V, V, U, U, U] + [V] * 5),
+                       ("svthip_av1_sgrproj_trial_sse_dev", [V, V, U, U, V, V, V, V]),
+                       ("svthip_av1_highbd_sgrproj_trial_sse_dev", [V, V, U, U, U, V, V, V, V]),
+                       ("svthip_av1_lr_filter_frame_dev", [V, V, V, V, U, U, V, V, V, V]),
+                       ("svthip_av1_highbd_lr_filter_frame_dev", [V, V, V, V, U, U, U, V, V, V, V])):
         getattr(L, name).restype = C.c_int32
         getattr(L, name).argtypes = args
     L.svthip_lr_unit_geometry.restype = C.c_uint32
@@ -190,6 +198,10 @@ def lib() -> C.CDLL:
     L.svthip_lr_workspace_bytes.argtypes = [U]
     L.svthip_wiener_walk_max_trials.restype = C.c_uint32
     L.svthip_wiener_walk_max_trials.argtypes = [U]
+    L.svthip_sgrproj_workspace_bytes.restype = C.c_size_t
+    L.svthip_sgrproj_workspace_bytes.argtypes = [U, U]
+    L.svthip_sgrproj_walk_max_trials.restype = C.c_uint32
+    L.svthip_sgrproj_walk_max_trials.argtypes = []
     L.svthip_inter_pred_refused.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.svthip_motion_estimate_picture.restype = C.c_int32
     L.svthip_motion_estimate_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32,
@@ -1113,6 +1125,60 @@ Context.wiener_walk_init_dev = _wiener_walk_init_dev
 Context.wiener_walk_step_dev = _wiener_walk_step_dev
 Context.av1_search_wiener_dev = _av1_search_wiener_dev
 Context.av1_loop_restoration_filter_frame_dev = _av1_loop_restoration_filter_frame_dev
+
+
+# ---- self-guided loop restoration (svthip_av1_[highbd_]selfguided_restoration_dev, svthip_sgrproj_solve_dev, svthip_sgrproj_walk_table_dev,
+# .._search_sgrproj_dev, .._sgrproj_trial_sse_dev, .._lr_filter_frame_dev): pointer marshalling only ----
+SGRPROJ_DETAIL_DTYPE = np.dtype([("sums", "<i8", (5,)), ("exq", "<i4", (2,)), ("start_xqd", "<i4", (2,)), ("xqd", "<i4", (2,)), ("err", "<i8"),
+                                 ("n_trials", "<i4"), ("reserved", "<i4")])
+assert SGRPROJ_DETAIL_DTYPE.itemsize == 80
+SGRPROJ_PARAMS = 16
+
+
+def sgrproj_workspace_bytes(width, height):
+    return int(lib().svthip_sgrproj_workspace_bytes(width, height))
+
+
+def sgrproj_walk_max_trials():
+    return int(lib().svthip_sgrproj_walk_max_trials())
+
+
+def _av1_selfguided_restoration_dev(self, picture, plane, ep, d_flt0, d_flt1, flt_stride, bit_depth=8, stream=None):
+    f, bd = _hbd(bit_depth, "selfguided_restoration_dev")
+    _check(f(self._h, _picture_ref(picture), plane, *bd, ep, d_flt0, d_flt1, flt_stride, stream))
+
+
+def _sgrproj_solve_dev(self, d_sums, d_size, d_ep, n, d_xq, d_xqd, stream=None):
+    _check(lib().svthip_sgrproj_solve_dev(self._h, d_sums, d_size, d_ep, n, d_xq, d_xqd, stream))
+
+
+def _sgrproj_walk_table_dev(self, d_err, d_ep, d_start_xqd, n, d_xqd, d_best_err, d_n_trials, stream=None):
+    _check(lib().svthip_sgrproj_walk_table_dev(self._h, d_err, d_ep, d_start_xqd, n, d_xqd, d_best_err, d_n_trials, stream))
+
+
+def _av1_search_sgrproj_dev(self, picture, plane_start, plane_end, d_work, d_sgrproj, d_sse, d_detail=None, bit_depth=8, stream=None):
+    f, bd = _hbd(bit_depth, "search_sgrproj_dev")
+    _check(f(self._h, _picture_ref(picture), plane_start, plane_end, *bd, d_work, d_sgrproj, d_sse, d_detail, stream))
+
+
+def _av1_sgrproj_trial_sse_dev(self, picture, plane_start, plane_end, d_sgrproj, d_sse, d_skip=None, bit_depth=8, stream=None):
+    f, bd = _hbd(bit_depth, "sgrproj_trial_sse_dev")
+    _check(f(self._h, _picture_ref(picture), plane_start, plane_end, *bd, d_sgrproj, d_skip, d_sse, stream))
+
+
+def _av1_lr_filter_frame_dev(self, picture, d_out, out_stride, plane_start, plane_end, d_unit_type, d_taps, d_sgrproj, bit_depth=8, stream=None):
+    f, bd = _hbd(bit_depth, "lr_filter_frame_dev")
+    out = (C.c_void_p * 3)(*d_out) if d_out is not None else None
+    strides = (C.c_uint32 * 3)(*out_stride) if out_stride is not None else None
+    _check(f(self._h, _picture_ref(picture), out, strides, plane_start, plane_end, *bd, d_unit_type, d_taps, d_sgrproj, stream))
+
+
+Context.av1_selfguided_restoration_dev = _av1_selfguided_restoration_dev
+Context.sgrproj_solve_dev = _sgrproj_solve_dev
+Context.sgrproj_walk_table_dev = _sgrproj_walk_table_dev
+Context.av1_search_sgrproj_dev = _av1_search_sgrproj_dev
+Context.av1_sgrproj_trial_sse_dev = _av1_sgrproj_trial_sse_dev
+Context.av1_lr_filter_frame_dev = _av1_lr_filter_frame_dev
 
 
 # ---- host-pointer picture and TU forms (svthip_motion_estimate_picture / svthip_open_loop_intra_search_picture / svthip_encode_tu_batch) ----
