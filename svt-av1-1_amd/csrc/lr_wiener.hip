@@ -1,987 +1,12 @@
-// svt-av1-1_amd/csrc/lr_wiener.hip -- loop restoration on the device, both filters.  Wiener: per-unit statistics, the separable solve, the
-// unit filter (as SSE trial and as frame filter) and the refinement walk as a state machine; restates Codec/EbRestorationPick.c:743-1104,
-// :1257-1366, EbRestoration.c:198-237, :346-554, :1172-1246, :1343-1389 and convolve.c:64-222.  Self-guided: the box filter in search
-// geometry with the projection sums, the projection solve, the xqd walk, the pick of the best parameter set and the unit filter in filter
-// geometry (SSE trial and frame filter); restates EbRestorationPick.c:248-670, :1670-1706 and EbRestoration.c:167-176, :731-1246.  The two
-// unit filters share one statement of the stripe rule.  The contract is in include/svtav1_hip.h.
-// Not here: rest_finish_search, CDEF, 12 bits, superres, more than one tile.
+// svt-av1-1_amd/csrc/lr_wiener.hip -- Wiener loop restoration on the device, host side: the unit geometry through the ABI, the workspace,
+// the launches of the kernels of lr_wiener_kernels.h, the whole search and the frame filter of the three unit types.  The contract is in
+// include/svtav1_hip.h.  Not here: rest_finish_search, CDEF, 12 bits, superres, more than one tile.
 #include "me_kernels.h"
+
+#include "lr_wiener_kernels.h"
 
 namespace svthip {
 
-namespace {
-
-constexpr int kTapMid[3] = {3, -7, 15};   // WIENER_FILT_TAPn_MIDV
-constexpr int kTapBits[3] = {4, 5, 6};    // WIENER_FILT_TAPn_BITS
-__host__ __device__ constexpr int tap_min(int p) { return kTapMid[p] - (1 << kTapBits[p]) / 2; }
-__host__ __device__ constexpr int tap_max(int p) { return kTapMid[p] - 1 + (1 << kTapBits[p]) / 2; }
-constexpr int kFiltStep = 128;                     // WIENER_FILT_STEP
-constexpr int64_t kTapScale = (int64_t)1 << 16;    // WIENER_TAP_SCALE_FACTOR
-constexpr int kNumIters = 5;                       // NUM_WIENER_ITERS
-// Lanes per workgroup of the tiled kernels.  tests/test_lr_kernels_host.py compiles the kernel bodies below for the host with one lane
-// per workgroup (which then does all of its workgroup's work in order) to check them against the fixture without a GPU.
-#ifndef SVTHIP_LR_THREADS
-#define SVTHIP_LR_THREADS 256
-#endif
-constexpr int kThreads = SVTHIP_LR_THREADS;
-
-// ---------------------------------------------------------------- geometry: the one place (host, binding through the ABI, kernels)
-struct PlaneGeom {
-    int w, h, unit, ss, nx, ny, base, win;
-};
-struct Limits {
-    int h0, h1, v0, v1;
-};
-
-__host__ __device__ inline int units_in(int size, int unit)
-{
-    const int n = (size + (unit >> 1)) / unit;
-    return n < 1 ? 1 : n;
-}
-
-__host__ __device__ inline PlaneGeom plane_geom(uint32_t width, uint32_t height, const uint32_t unit_size[3], int plane)
-{
-    PlaneGeom g{};
-    int base = 0;
-    for (int p = 0; p <= plane; p++) {
-        g.ss = p > 0;
-        g.w = (int)width >> g.ss, g.h = (int)height >> g.ss, g.unit = (int)unit_size[p];
-        g.nx = units_in(g.w, g.unit), g.ny = units_in(g.h, g.unit);
-        g.base = base;
-        base += g.nx * g.ny;
-    }
-    g.win = plane ? 5 : 7;
-    return g;
-}
-
-// Unit i of a row or column starts at i * unit; the last one takes what remains (less than 1.5 units, by the rounding of units_in).
-// Vertically every unit but the first starts 8 >> ss rows early and every unit but the last ends that much early.
-__host__ __device__ inline Limits unit_limits(const PlaneGeom& g, int i)
-{
-    const int ux = i % g.nx, uy = i / g.nx, off = 8 >> g.ss;
-    Limits L;
-    L.h0 = ux * g.unit;
-    L.h1 = ux == g.nx - 1 ? g.w : (ux + 1) * g.unit;
-    L.v0 = uy == 0 ? 0 : uy * g.unit - off;
-    L.v1 = uy == g.ny - 1 ? g.h : (uy + 1) * g.unit - off;
-    return L;
-}
-
-__host__ __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-// ---------------------------------------------------------------- statistics
-// One workgroup sums one 32x32 tile of a unit.  With Z = (the win^2 window samples, the source sample, 1) per pixel, every sum the
-// statistics need is a sum of products Z_k * Z_l, k <= l: the Gram matrix of the window (H), window x source (M), the plain sums (for
-// avg, which is then needed only in the integer epilogue: sum (d - a)(d' - a) = sum d d' - a sum d - a sum d' + N a^2), source^2 (with M
-// and H at the centre: the SSE of the unrestored unit).  A lane owns up to 6 of the (win^2 + 2)(win^2 + 3) / 2 - 1 products and keeps each
-// tile sum in 32 bits: a product of raw samples is below 2^20 at 10 bits (2^16 at 8), so 1024 pixels stay below 2^30 (2^26); a 64x64
-// tile would not at 10 bits.  The tile sums are added to the unit's in 64 bits with integer atomics, whose order does not matter.
-constexpr int kStatTile = 32;
-constexpr int kStatPitch = 40;                        // LDS row pitch in samples: window rows 0..6 start on distinct bank groups
-constexpr int kStatRowsD = kStatTile + 6;             // window tile with its halo
-constexpr int kStatItemsPerLane = (1325 + kThreads - 1) / kThreads;   // 6 with 256 lanes
-constexpr int kRawStride = 1328;                      // 64-bit sums per unit: 51 * 52 / 2 - 1 = 1325, padded
-
-__host__ __device__ inline int tri_index(int k, int l, int nz) { return k * nz - k * (k - 1) / 2 + (l - k); }  // k <= l
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void lr_stats_kernel(const T* __restrict__ dgd, uint32_t dgd_stride, const T* __restrict__ src, uint32_t src_stride,
-                                                        PlaneGeom g, unsigned long long* __restrict__ raw)
-{
-    __shared__ uint16_t buf[(kStatRowsD + 2 * kStatTile) * kStatPitch];
-    const int u = blockIdx.z, tid = threadIdx.x;
-    const Limits L = unit_limits(g, u);
-    const int tx0 = L.h0 + (int)blockIdx.x * kStatTile, ty0 = L.v0 + (int)blockIdx.y * kStatTile;
-    if (tx0 >= L.h1 || ty0 >= L.v1) return;
-    const int tw = min(kStatTile, L.h1 - tx0), th = min(kStatTile, L.v1 - ty0);
-    const int win = g.win, half = win >> 1, n = win * win, nz = n + 2, items = nz * (nz + 1) / 2 - 1;
-    const int dw = tw + 2 * half, dh = th + 2 * half;
-    for (int i = tid; i < dw * dh; i += kThreads) {
-        const int r = i / dw, c = i - r * dw;
-        const int y = clampi(ty0 - half + r, 0, g.h - 1), x = clampi(tx0 - half + c, 0, g.w - 1);
-        buf[r * kStatPitch + c] = (uint16_t)dgd[(size_t)y * dgd_stride + x];
-    }
-    for (int i = tid; i < kStatTile * kStatTile; i += kThreads) {
-        const int r = i / kStatTile, c = i % kStatTile;
-        buf[(kStatRowsD + r) * kStatPitch + c] = r < th && c < tw ? (uint16_t)src[(size_t)(ty0 + r) * src_stride + tx0 + c] : 0;
-        buf[(kStatRowsD + kStatTile + r) * kStatPitch + c] = 1;
-    }
-    __syncthreads();
-    int off_a[kStatItemsPerLane], off_b[kStatItemsPerLane];
-    uint32_t acc[kStatItemsPerLane];
-#pragma unroll
-    for (int q = 0; q < kStatItemsPerLane; q++) {
-        const int item = tid + kThreads * q;
-        int k = 0, rem = item < items ? item : 0;
-        while (rem >= nz - k) rem -= nz - k, k++;
-        const int l = k + rem;
-        // Z index -> LDS offset of its value at pixel (0, 0): window index = horizontal offset * win + vertical offset
-        off_a[q] = k < n ? (k % win) * kStatPitch + k / win : (kStatRowsD + (k - n) * kStatTile) * kStatPitch;
-        off_b[q] = l < n ? (l % win) * kStatPitch + l / win : (kStatRowsD + (l - n) * kStatTile) * kStatPitch;
-        acc[q] = 0;
-    }
-    for (int i = 0; i < th; i++)
-        for (int j = 0; j < tw; j++) {
-            const int at = i * kStatPitch + j;
-#pragma unroll
-            for (int q = 0; q < kStatItemsPerLane; q++) acc[q] += (uint32_t)buf[off_a[q] + at] * (uint32_t)buf[off_b[q] + at];
-        }
-#pragma unroll
-    for (int q = 0; q < kStatItemsPerLane; q++) {
-        const int item = tid + kThreads * q;
-        if (item < items) atomicAdd(&raw[(size_t)(g.base + u) * kRawStride + item], (unsigned long long)acc[q]);
-    }
-}
-
-// The integer epilogue of one unit: avg, then M, H and the unrestored SSE from the raw sums.  Every raw sum is below 2^20 * 384^2 < 2^38.
-__global__ __launch_bounds__(kThreads) void lr_stats_finish_kernel(const unsigned long long* __restrict__ raw_all, PlaneGeom g, int bd, int64_t* __restrict__ M,
-                                                               int64_t* __restrict__ H, int32_t* __restrict__ avg_out, int64_t* __restrict__ sse_none)
-{
-    const int u = blockIdx.x, unit = g.base + u;
-    const Limits L = unit_limits(g, u);
-    const int64_t N = (int64_t)(L.h1 - L.h0) * (L.v1 - L.v0);
-    const int n = g.win * g.win, nz = n + 2, c = n >> 1;
-    const unsigned long long* raw = raw_all + (size_t)unit * kRawStride;
-    const int64_t avg = (int64_t)(raw[tri_index(c, n + 1, nz)] / (unsigned long long)N);
-    const int64_t sx = (int64_t)raw[tri_index(n, n + 1, nz)];
-    const int64_t div = bd == 10 ? 4 : 1;
-    for (int i = threadIdx.x; i < n * n; i += blockDim.x) {
-        const int k = i / n, l = i - k * n;
-        const int64_t hr = (int64_t)raw[tri_index(min(k, l), max(k, l), nz)];
-        const int64_t sk = (int64_t)raw[tri_index(k, n + 1, nz)], sl = (int64_t)raw[tri_index(l, n + 1, nz)];
-        H[(size_t)unit * SVTHIP_WIENER_STATS_H + i] = (hr - avg * (sk + sl) + N * avg * avg) / div;   // C division: towards zero
-        if (l == 0) M[(size_t)unit * SVTHIP_WIENER_STATS_M + k] = ((int64_t)raw[tri_index(k, n, nz)] - avg * sk - avg * sx + N * avg * avg) / div;
-    }
-    if (threadIdx.x == 0) {
-        avg_out[unit] = (int32_t)avg;
-        sse_none[unit] = (int64_t)raw[tri_index(n, n, nz)] - 2 * (int64_t)raw[tri_index(c, n, nz)] + (int64_t)raw[tri_index(c, c, nz)];
-    }
-}
-
-// ---------------------------------------------------------------- solve: one lane per unit, the reference's order of operations on int64
-__device__ inline int64_t abs64(int64_t v) { return v < 0 ? -v : v; }
-__device__ inline int wrap_index(int i, int win) { return i >= (win >> 1) + 1 ? win - 1 - i : i; }
-
-__device__ bool linsolve(int n, int64_t* A, int stride, int64_t* b, int32_t* x)
-{
-    for (int k = 0; k < n - 1; k++) {
-        for (int i = n - 1; i > k; i--)
-            if (abs64(A[(i - 1) * stride + k]) < abs64(A[i * stride + k])) {
-                for (int j = 0; j < n; j++) {
-                    const int64_t c = A[i * stride + j];
-                    A[i * stride + j] = A[(i - 1) * stride + j];
-                    A[(i - 1) * stride + j] = c;
-                }
-                const int64_t c = b[i];
-                b[i] = b[i - 1];
-                b[i - 1] = c;
-            }
-        for (int i = k; i < n - 1; i++) {
-            if (A[k * stride + k] == 0) return false;
-            const int64_t c = A[(i + 1) * stride + k], cd = A[k * stride + k];
-            for (int j = 0; j < n; j++) A[(i + 1) * stride + j] -= c / 256 * A[k * stride + j] / cd * 256;
-            b[i + 1] -= c * b[k] / cd;
-        }
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        if (A[i * stride + i] == 0) return false;
-        int64_t c = 0;
-        for (int j = i + 1; j <= n - 1; j++) c += A[i * stride + j] * x[j] / kTapScale;
-        x[i] = (int32_t)(kTapScale * (b[i] - c) / A[i * stride + i]);
-    }
-    return true;
-}
-
-// which 0: b fixed, a updated (update_a_sep_sym); 1: a fixed, b updated (update_b_sep_sym)
-__device__ void update_sep_sym(int win, const int64_t* M, const int64_t* H, int32_t* a, int32_t* b, int which)
-{
-    const int win2 = win * win, h1 = (win >> 1) + 1, e = h1 - 1;
-    int64_t A[4] = {0, 0, 0, 0}, B[16];
-    int32_t S[7];
-    for (int i = 0; i < 16; i++) B[i] = 0;
-    for (int i = 0; i < win; i++)
-        for (int j = 0; j < win; j++) {
-            if (which == 0)
-                A[wrap_index(j, win)] += M[i * win + j] * b[i] / kTapScale;
-            else
-                A[wrap_index(i, win)] += M[i * win + j] * a[j] / kTapScale;
-        }
-    for (int i = 0; i < win; i++)
-        for (int j = 0; j < win; j++)
-            for (int k = 0; k < win; k++)
-                for (int l = 0; l < win; l++) {
-                    if (which == 0)
-                        B[wrap_index(l, win) * h1 + wrap_index(k, win)] += H[j * win * win2 + i * win + k * win2 + l] * b[i] / kTapScale * b[j] / kTapScale;
-                    else
-                        B[wrap_index(j, win) * h1 + wrap_index(i, win)] += H[i * win * win2 + j * win + k * win2 + l] * a[k] / kTapScale * a[l] / kTapScale;
-                }
-    for (int i = 0; i < e; i++) A[i] -= A[e] * 2 + B[i * h1 + e] - 2 * B[e * h1 + e];
-    for (int i = 0; i < e; i++)
-        for (int j = 0; j < e; j++) B[i * h1 + j] -= 2 * (B[i * h1 + e] + B[e * h1 + j] - 2 * B[e * h1 + e]);
-    if (!linsolve(e, B, h1, A, S)) return;
-    S[e] = (int32_t)kTapScale;
-    for (int i = h1; i < win; i++) {
-        S[i] = S[win - 1 - i];
-        S[e] = (int32_t)((uint32_t)S[e] - 2u * (uint32_t)S[i]);
-    }
-    int32_t* out = which == 0 ? a : b;
-    for (int i = 0; i < win; i++) out[i] = S[i];
-}
-
-__device__ void finalize_filter(int win, const int32_t* f, int16_t* fi)
-{
-    const int half = win >> 1;
-    for (int i = 0; i < 8; i++) fi[i] = 0;
-    for (int i = 0; i < half; i++) {
-        const int64_t dividend = (int32_t)((uint32_t)f[i] * (uint32_t)kFiltStep), divisor = kTapScale;
-        fi[i] = (int16_t)(dividend < 0 ? (dividend - divisor / 2) / divisor : (dividend + divisor / 2) / divisor);
-    }
-    if (win == 7) {
-        for (int p = 0; p < 3; p++) fi[p] = (int16_t)clampi(fi[p], tap_min(p), tap_max(p));
-    } else {
-        fi[2] = (int16_t)clampi(fi[1], tap_min(2), tap_max(2));
-        fi[1] = (int16_t)clampi(fi[0], tap_min(1), tap_max(1));
-        fi[0] = 0;
-    }
-    fi[6] = fi[0], fi[5] = fi[1], fi[4] = fi[2];
-    fi[3] = (int16_t)(-2 * (fi[0] + fi[1] + fi[2]));
-}
-
-__device__ int64_t filter_score(int win, const int64_t* M, const int64_t* H, const int16_t* vf, const int16_t* hf)
-{
-    const int off = (7 - win) >> 1, win2 = win * win;
-    int16_t a[7], b[7];
-    int32_t ab[49];
-    a[3] = b[3] = kFiltStep;
-    for (int i = 0; i < 3; i++) {
-        a[i] = a[6 - i] = vf[i];
-        b[i] = b[6 - i] = hf[i];
-        a[3] -= 2 * vf[i];
-        b[3] -= 2 * hf[i];
-    }
-    for (int k = 0; k < win; k++)
-        for (int l = 0; l < win; l++) ab[k * win + l] = a[l + off] * b[k + off];
-    int64_t P = 0, Q = 0;
-    for (int k = 0; k < win2; k++) {
-        P += ab[k] * M[k] / kFiltStep / kFiltStep;
-        for (int l = 0; l < win2; l++) Q += ab[k] * H[k * win2 + l] * ab[l] / kFiltStep / kFiltStep / kFiltStep / kFiltStep;
-    }
-    const int c = win2 >> 1;
-    return (Q - 2 * P) - (H[c * win2 + c] - 2 * M[c]);
-}
-
-__global__ __launch_bounds__(64) void lr_solve_kernel(const int64_t* __restrict__ M_all, const int64_t* __restrict__ H_all, uint32_t unit_begin, uint32_t unit_end, int win,
-                                int16_t* __restrict__ taps, int32_t* __restrict__ rejected)
-{
-    const uint32_t unit = unit_begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (unit >= unit_end) return;
-    const int64_t* M = M_all + (size_t)unit * SVTHIP_WIENER_STATS_M;
-    const int64_t* H = H_all + (size_t)unit * SVTHIP_WIENER_STATS_H;
-    const int init[7] = {kTapMid[0], kTapMid[1], kTapMid[2], kFiltStep - 2 * (kTapMid[0] + kTapMid[1] + kTapMid[2]), kTapMid[2], kTapMid[1], kTapMid[0]};
-    const int off = (7 - win) >> 1;
-    int32_t a[7], b[7];
-    for (int i = 0; i < win; i++) a[i] = b[i] = (int32_t)(kTapScale / kFiltStep) * init[i + off];
-    for (int iter = 1; iter < kNumIters; iter++) {
-        update_sep_sym(win, M, H, a, b, 0);
-        update_sep_sym(win, M, H, a, b, 1);
-    }
-    int16_t vf[8], hf[8];
-    finalize_filter(win, a, vf);
-    finalize_filter(win, b, hf);
-    for (int i = 0; i < 8; i++) taps[(size_t)unit * 16 + i] = vf[i], taps[(size_t)unit * 16 + 8 + i] = hf[i];
-    rejected[unit] = filter_score(win, M, H, vf, hf) > 0;
-}
-
-// ---------------------------------------------------------------- stripes: the one statement of the stripe rule, for both unit filters
-// A unit is filtered stripe by stripe (64 >> ss rows, offset 8 >> ss).  A stripe's rows with three above and three below go to LDS and
-// the stripe rule is applied while loading (EbRestoration.c:346-467): rows above the stripe come from the deblocked plane (rows y0-2,
-// y0-2, y0-1) unless the stripe is the picture's first, rows below it (y1, y1+1, y1+1, clamped to the last row) unless it is the last;
-// everything else is the CDEF'd plane with clamped coordinates.
-struct Stripe {
-    int y0, y1;          // rows [y0, y1) of the plane
-    bool above, below;   // the rows above / below come from the deblocked plane
-};
-
-// stripe i of a unit, counted from the unit's first; y0 >= L.v1 when the unit has fewer
-__host__ __device__ inline Stripe unit_stripe(const PlaneGeom& g, const Limits& L, int i)
-{
-    const int sh = 64 >> g.ss, off = 8 >> g.ss;
-    const int k = (L.v0 + off) / sh + i;          // the stripe's index in the picture
-    Stripe S;
-    S.y0 = max(k * sh - off, L.v0), S.y1 = min((k + 1) * sh - off, L.v1);
-    S.above = S.y0 != 0, S.below = (k + 1) * sh - off < g.h;
-    return S;
-}
-
-// rows [ya, ya + rows) x columns [xa, xa + cols) of what a filter of stripe S reads, into LDS
-template <typename T>
-__device__ inline void load_stripe_rows(uint16_t* lds, int pitch, const T* __restrict__ cdef, uint32_t cdef_stride, const T* __restrict__ dbk,
-                                        uint32_t dbk_stride, const PlaneGeom& g, const Stripe& S, int ya, int rows, int xa, int cols, int tid)
-{
-    for (int i = tid; i < rows * cols; i += kThreads) {
-        const int r = i / cols, c = i - r * cols;
-        const int y = ya + r, x = clampi(xa + c, 0, g.w - 1);
-        uint16_t v;
-        if (y < S.y0 && S.above)
-            v = (uint16_t)dbk[(size_t)max(y, S.y0 - 2) * dbk_stride + x];
-        else if (y >= S.y1 && S.below)
-            v = (uint16_t)dbk[(size_t)min(min(y, S.y1 + 1), g.h - 1) * dbk_stride + x];
-        else
-            v = (uint16_t)cdef[(size_t)clampi(y, 0, g.h - 1) * cdef_stride + x];
-        lds[r * pitch + c] = v;
-    }
-}
-
-// ---------------------------------------------------------------- the Wiener unit filter: one workgroup = 32 columns of one stripe of one unit
-constexpr int kFiltCols = 32;
-constexpr int kFiltRows = 64 + 6;
-constexpr int kFiltPitch = kFiltCols + 8;   // 6 halo columns, padded
-
-template <typename T, bool WRITE>
-__global__ __launch_bounds__(kThreads) void lr_filter_kernel(const T* __restrict__ cdef, uint32_t cdef_stride, const T* __restrict__ dbk, uint32_t dbk_stride,
-                                                         const T* __restrict__ src, uint32_t src_stride, T* __restrict__ out, uint32_t out_stride,
-                                                         PlaneGeom g, int bd, const uint8_t* __restrict__ taps_base, size_t taps_stride,
-                                                         const uint8_t* __restrict__ flag_base, size_t flag_stride,
-                                                         unsigned long long* __restrict__ sse, uint32_t* __restrict__ refused,
-                                                         int sgrproj_elsewhere = 0)   // the launch code always passes it; the default is for
-                                                                                      // tests/test_lr_kernels_host.py, which calls with 16 arguments
-{
-    __shared__ uint16_t in[kFiltRows * kFiltPitch];
-    __shared__ uint16_t mid[kFiltRows * kFiltCols];
-    __shared__ unsigned long long block_sse;
-    const int u = blockIdx.z, unit = g.base + u, tid = threadIdx.x;
-    // trial: flag = skip this unit; write: flag = the unit's restoration type
-    const int flag = flag_base ? flag_base[(size_t)unit * flag_stride] : (WRITE ? SVTHIP_RESTORE_WIENER : 0);
-    if (!WRITE && flag) return;
-    const Limits L = unit_limits(g, u);
-    const int x0 = L.h0 + (int)blockIdx.x * kFiltCols;
-    if (x0 >= L.h1) return;
-    const int tw = min(kFiltCols, L.h1 - x0);
-    const Stripe S = unit_stripe(g, L, (int)blockIdx.y);
-    const int y0 = S.y0;
-    if (y0 >= L.v1) return;
-    const int nrows = S.y1 - y0;
-    if (WRITE && (flag != SVTHIP_RESTORE_WIENER || !taps_base)) {
-        if (flag == SVTHIP_RESTORE_NONE) {
-            for (int i = tid; i < nrows * kFiltCols; i += kThreads) {
-                const int r = i / kFiltCols, c = i % kFiltCols;
-                if (c < tw) out[(size_t)(y0 + r) * out_stride + x0 + c] = cdef[(size_t)(y0 + r) * cdef_stride + x0 + c];
-            }
-        } else if (!(flag == SVTHIP_RESTORE_SGRPROJ && sgrproj_elsewhere) && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-            atomicAdd(refused, 1u);   // a type nobody filters, or a Wiener unit without taps
-        }
-        return;
-    }
-    const int16_t* taps = reinterpret_cast<const int16_t*>(taps_base + (size_t)unit * taps_stride);
-    int fv[7], fh[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) fv[i] = taps[i], fh[i] = taps[8 + i];
-    load_stripe_rows(in, kFiltPitch, cdef, cdef_stride, dbk, dbk_stride, g, S, y0 - 3, nrows + 6, x0 - 3, tw + 6, tid);
-    if (tid == 0) block_sse = 0;
-    __syncthreads();
-    // horizontal: 7 taps plus the centre sample, round_0 = 3, clamped to [0, WIENER_CLAMP_LIMIT(3, bd))
-    const int lim0 = (1 << (bd + 1 + 7 - 3)) - 1;
-    for (int i = tid; i < (nrows + 6) * kFiltCols; i += kThreads) {
-        const int r = i / kFiltCols, c = i % kFiltCols;
-        if (c >= tw) continue;
-        const uint16_t* p = &in[r * kFiltPitch + c];
-        int sum = ((int)p[3] << 7) + (1 << (bd + 6));
-#pragma unroll
-        for (int t = 0; t < 7; t++) sum += (int)p[t] * fh[t];
-        mid[r * kFiltCols + c] = (uint16_t)clampi((sum + 4) >> 3, 0, lim0);
-    }
-    __syncthreads();
-    // vertical: round_1 = 11 with the negative offset, clipped to the pixel range
-    const int top = (1 << bd) - 1;
-    unsigned long long acc = 0;
-    for (int i = tid; i < nrows * kFiltCols; i += kThreads) {
-        const int r = i / kFiltCols, c = i % kFiltCols;
-        if (c >= tw) continue;
-        const uint16_t* p = &mid[r * kFiltCols + c];
-        int sum = ((int)p[3 * kFiltCols] << 7) - (1 << (bd + 10));
-#pragma unroll
-        for (int t = 0; t < 7; t++) sum += (int)p[t * kFiltCols] * fv[t];
-        const int v = clampi((sum + 1024) >> 11, 0, top);
-        if (WRITE) {
-            out[(size_t)(y0 + r) * out_stride + x0 + c] = (T)v;
-        } else {
-            const int d = v - (int)src[(size_t)(y0 + r) * src_stride + x0 + c];
-            acc += (unsigned long long)(d * d);
-        }
-    }
-    if (!WRITE) {
-        if (acc) atomicAdd(&block_sse, acc);
-        __syncthreads();
-        if (tid == 0 && block_sse) atomicAdd(&sse[unit], block_sse);
-    }
-}
-
-// ---------------------------------------------------------------- the walk (EbRestorationPick.c:1257-1366) as a state machine
-__device__ inline void move_tap(int16_t* f, int p, int d)
-{
-    f[p] = (int16_t)(f[p] + d);
-    f[6 - p] = (int16_t)(f[6 - p] + d);
-    f[3] = (int16_t)(f[3] - 2 * d);
-}
-
-// after the attempts on tap p end: the next tap -- or, when a minus move was accepted, past the last one (`if (skip) break;` leaves the
-// loop over p) --, then the other filter, then the next step
-__device__ inline void next_tap(svthip_wiener_walk_state& S)
-{
-    const int p = S.skip ? 3 : S.tap + 1;
-    S.dir = 0, S.skip = 0;
-    if (p < 3) {
-        S.tap = (int8_t)p;
-        return;
-    }
-    S.tap = S.first_tap;
-    if (S.filt == 0) {
-        S.filt = 1;
-        return;
-    }
-    S.filt = 0;
-    S.step >>= 1;
-    if (S.step == 0) S.done = 1;
-}
-
-// from the position (step, filt, tap, dir): apply the move of the next trial, or mark the walk done
-__device__ inline void advance(svthip_wiener_walk_state& S)
-{
-    while (!S.done) {
-        int16_t* f = S.taps + (S.filt ? 0 : 8);
-        const int p = S.tap, s = S.step;
-        if (S.dir == 0) {
-            if (f[p] - s >= tap_min(p)) {
-                move_tap(f, p, -s);
-                return;
-            }
-            if (!S.skip) {
-                S.dir = 1;
-                continue;
-            }
-        } else if (f[p] + s <= tap_max(p)) {
-            move_tap(f, p, s);
-            return;
-        }
-        next_tap(S);
-    }
-}
-
-__global__ __launch_bounds__(64) void lr_walk_init_kernel(svthip_wiener_walk_state* __restrict__ state, const int16_t* __restrict__ taps, const int32_t* __restrict__ rejected,
-                                    uint32_t unit_begin, uint32_t unit_end, int win)
-{
-    const uint32_t unit = unit_begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (unit >= unit_end) return;
-    svthip_wiener_walk_state S{};
-    const bool rej = rejected && rejected[unit];
-    S.err = rej ? INT64_MAX : 0;
-    for (int i = 0; i < 16; i++) S.taps[i] = taps[(size_t)unit * 16 + i];
-    S.step = 4;
-    S.first_tap = S.tap = (int8_t)((7 - win) >> 1);
-    S.done = rej;
-    state[unit] = S;
-}
-
-__global__ __launch_bounds__(64) void lr_walk_step_kernel(svthip_wiener_walk_state* __restrict__ state, const int64_t* __restrict__ trial_sse, uint32_t unit_begin,
-                                    uint32_t unit_end, int32_t* __restrict__ pending)
-{
-    const uint32_t unit = unit_begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (unit >= unit_end) return;
-    svthip_wiener_walk_state S = state[unit];
-    if (S.done) return;
-    const int64_t e = trial_sse[unit];
-    S.n_trials++;
-    if (!S.started) {
-        S.started = 1;
-        S.err = e;
-    } else {
-        int16_t* f = S.taps + (S.filt ? 0 : 8);
-        const int s = S.step, d = S.dir == 0 ? -s : s;
-        if (e > S.err) {   // a tie is accepted
-            move_tap(f, S.tap, -d);
-            if (S.dir == 0 && !S.skip)
-                S.dir = 1;
-            else
-                next_tap(S);
-        } else {
-            S.err = e;
-            if (S.dir == 0) S.skip = 1;
-            if (s != 4) next_tap(S);   // at step 4 an accepted move repeats in the same direction
-        }
-    }
-    advance(S);
-    state[unit] = S;
-    if (!S.done && pending) atomicAdd(pending, 1);
-}
-
-__global__ __launch_bounds__(64) void lr_search_output_kernel(const svthip_wiener_walk_state* __restrict__ state, const int64_t* __restrict__ sse_none, uint32_t unit_begin,
-                                        uint32_t unit_end, int64_t* __restrict__ sse, int16_t* __restrict__ taps, int32_t* __restrict__ n_trials)
-{
-    const uint32_t unit = unit_begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (unit >= unit_end) return;
-    const svthip_wiener_walk_state S = state[unit];
-    const bool rej = S.err == INT64_MAX;
-    sse[2 * (size_t)unit] = sse_none[unit];
-    sse[2 * (size_t)unit + 1] = S.err;
-    for (int i = 0; i < 16; i++) taps[(size_t)unit * 16 + i] = rej ? (int16_t)0 : S.taps[i];
-    n_trials[unit] = S.n_trials;
-}
-
-// ================================================================ self-guided restoration
-// sgr_params (EbRestoration.c:167-176): sets 0-9 filter with r = {2, 1}, 10-13 with {0, 1}, 14-15 with {2, 0}; only s differs within a class
-constexpr int kSgrS[16][2] = {{140, 3236}, {112, 2158}, {93, 1618}, {80, 1438}, {70, 1295}, {58, 1177}, {47, 1079}, {37, 996},
-                              {30, 925},   {25, 863},   {-1, 2589}, {-1, 1618}, {-1, 1177}, {-1, 925},  {56, -1},   {22, -1}};
-__host__ __device__ constexpr int sgr_s(int ep, int k) { return kSgrS[ep][k]; }
-__host__ __device__ constexpr int sgr_r(int ep, int k) { return k == 0 ? (ep >= 10 && ep < 14 ? 0 : 2) : (ep < 14 ? 1 : 0); }
-__host__ __device__ constexpr int prj_min(int p) { return p ? -32 : -96; }   // SGRPROJ_PRJ_MIN0 / MIN1
-__host__ __device__ constexpr int prj_max(int p) { return p ? 95 : 31; }     // SGRPROJ_PRJ_MAX0 / MAX1
-constexpr int kSgrParams = 16;
-constexpr int kRstBits = 4, kPrjBits = 7;   // SGRPROJ_RST_BITS, SGRPROJ_PRJ_BITS
-
-// ---------------------------------------------------------------- the box filter of one tile (EbRestoration.c:774-1064, the C forms)
-// A tile is up to 64 columns x 32 rows: a processing unit is 64 x 64 luma (two tiles) or 32 x 32 chroma (one).  Halving a luma unit
-// changes nothing: a sample's result depends on the plane's samples around it and on the parity of its row counted from the processing
-// unit's first row (the r = 2 filter has A and B on rows -1, 1, 3, ... only), and 32 is even.  It brings the LDS of a workgroup from 75 KB
-// to 39 KB.  In LDS: the samples with their 3-sample border; per box position (rows -1 .. h, columns -1 .. w; r = 2: every other row)
-// p = max(a n - b b, 0) and the box sum, which no parameter set changes; per set A (9 bits) and B (< 2^18) packed in one word.
-constexpr int kSgrTileW = 64, kSgrTileH = 32;
-constexpr int kSgrDatPitch = kSgrTileW + 8;
-constexpr int kSgrAbW = kSgrTileW + 2;
-constexpr int kSgrRows1 = kSgrTileH + 2, kSgrRows2 = kSgrTileH / 2 + 1;
-
-struct SgrTile {
-    uint32_t p1[kSgrRows1 * kSgrAbW], p2[kSgrRows2 * kSgrAbW];
-    uint32_t ab1[kSgrRows1 * kSgrAbW], ab2[kSgrRows2 * kSgrAbW];
-    uint16_t s1[kSgrRows1 * kSgrAbW], s2[kSgrRows2 * kSgrAbW];
-    uint16_t dat[(kSgrTileH + 6) * kSgrDatPitch];
-    uint16_t x_by_xplus1[256];
-};
-
-// box sums of radius r around (row i, column j) of the tile -> p and the sum.  a n - b b < 2^26 and the sum < 25 * 1023 < 2^15.
-__device__ inline void sgr_box(const SgrTile& t, int i, int j, int r, int bd, uint32_t& p, uint16_t& sum)
-{
-    uint32_t s = 0, q = 0;
-    for (int dy = -r; dy <= r; dy++)
-        for (int dx = -r; dx <= r; dx++) {
-            const uint32_t v = t.dat[(i + 3 + dy) * kSgrDatPitch + j + 3 + dx];
-            s += v, q += v * v;
-        }
-    const int sh = bd - 8;
-    const uint32_t n = (uint32_t)((2 * r + 1) * (2 * r + 1));
-    const uint32_t a = (q + ((1u << (2 * sh)) >> 1)) >> (2 * sh), b = (s + ((1u << sh) >> 1)) >> sh;
-    p = a * n < b * b ? 0u : a * n - b * b;
-    sum = (uint16_t)s;
-}
-
-// after the samples are in t.dat: everything that does not depend on the parameter set
-__device__ inline void sgr_tile_prepare(SgrTile& t, int tw, int th, int bd, int tid)
-{
-    for (int z = tid; z < 256; z += kThreads) t.x_by_xplus1[z] = (uint16_t)(z == 0 ? 1 : z == 255 ? 256 : (256 * z + ((z + 1) >> 1)) / (z + 1));
-    const int cols = tw + 2, rows2 = (th + 3) >> 1;
-    for (int i = tid; i < (th + 2) * cols; i += kThreads) {
-        const int r = i / cols, c = i - r * cols;
-        sgr_box(t, r - 1, c - 1, 1, bd, t.p1[r * kSgrAbW + c], t.s1[r * kSgrAbW + c]);
-    }
-    for (int i = tid; i < rows2 * cols; i += kThreads) {
-        const int r = i / cols, c = i - r * cols;
-        sgr_box(t, 2 * r - 1, c - 1, 2, bd, t.p2[r * kSgrAbW + c], t.s2[r * kSgrAbW + c]);
-    }
-}
-
-// z, A = x_by_xplus1[min(z, 255)], B = (256 - A) * sum * one_by_x[n - 1], in the reference's 32-bit unsigned arithmetic
-__device__ inline uint32_t sgr_ab(const SgrTile& t, uint32_t p, uint32_t sum, uint32_t s, uint32_t one_by_n)
-{
-    const uint32_t z = (p * s + (1u << 19)) >> 20;
-    const uint32_t A = t.x_by_xplus1[z < 255u ? z : 255u];
-    const uint32_t B = ((256u - A) * sum * one_by_n + (1u << 11)) >> 12;
-    return A | (B << 9);
-}
-
-__device__ inline void sgr_tile_ab(SgrTile& t, int tw, int th, int ep, int tid)
-{
-    const int cols = tw + 2, rows2 = (th + 3) >> 1;
-    if (sgr_r(ep, 1))
-        for (int i = tid; i < (th + 2) * cols; i += kThreads) {
-            const int at = (i / cols) * kSgrAbW + i % cols;
-            t.ab1[at] = sgr_ab(t, t.p1[at], t.s1[at], (uint32_t)sgr_s(ep, 1), 455u);
-        }
-    if (sgr_r(ep, 0))
-        for (int i = tid; i < rows2 * cols; i += kThreads) {
-            const int at = (i / cols) * kSgrAbW + i % cols;
-            t.ab2[at] = sgr_ab(t, t.p2[at], t.s2[at], (uint32_t)sgr_s(ep, 0), 164u);
-        }
-}
-
-__device__ inline int ab_a(uint32_t v) { return (int)(v & 511u); }
-__device__ inline int ab_b(uint32_t v) { return (int)(v >> 9); }
-
-// selfguided_restoration_fast_internal's output stage: weights 6 / 5, even rows from the rows above and below, odd rows from their own
-__device__ inline int sgr_flt0(const SgrTile& t, int i, int j, int dgd)
-{
-    if (!(i & 1)) {
-        const uint32_t* up = &t.ab2[(i >> 1) * kSgrAbW + j];
-        const uint32_t* dn = up + kSgrAbW;
-        const int a = (ab_a(up[1]) + ab_a(dn[1])) * 6 + (ab_a(up[0]) + ab_a(dn[0]) + ab_a(up[2]) + ab_a(dn[2])) * 5;
-        const int b = (ab_b(up[1]) + ab_b(dn[1])) * 6 + (ab_b(up[0]) + ab_b(dn[0]) + ab_b(up[2]) + ab_b(dn[2])) * 5;
-        return (a * dgd + b + (1 << 8)) >> 9;
-    }
-    const uint32_t* m = &t.ab2[((i + 1) >> 1) * kSgrAbW + j];
-    const int a = ab_a(m[1]) * 6 + (ab_a(m[0]) + ab_a(m[2])) * 5;
-    const int b = ab_b(m[1]) * 6 + (ab_b(m[0]) + ab_b(m[2])) * 5;
-    return (a * dgd + b + (1 << 7)) >> 8;
-}
-
-// selfguided_restoration_internal's output stage: weights 4 / 3 over the 3 x 3 neighbours
-__device__ inline int sgr_flt1(const SgrTile& t, int i, int j, int dgd)
-{
-    const uint32_t* up = &t.ab1[i * kSgrAbW + j];
-    const uint32_t* md = up + kSgrAbW;
-    const uint32_t* dn = md + kSgrAbW;
-    const int a = (ab_a(md[1]) + ab_a(md[0]) + ab_a(md[2]) + ab_a(up[1]) + ab_a(dn[1])) * 4 + (ab_a(up[0]) + ab_a(dn[0]) + ab_a(up[2]) + ab_a(dn[2])) * 3;
-    const int b = (ab_b(md[1]) + ab_b(md[0]) + ab_b(md[2]) + ab_b(up[1]) + ab_b(dn[1])) * 4 + (ab_b(up[0]) + ab_b(dn[0]) + ab_b(up[2]) + ab_b(dn[2])) * 3;
-    return (a * dgd + b + (1 << 8)) >> 9;
-}
-
-__device__ inline void decode_xq(int ep, int xqd0, int xqd1, int& xq0, int& xq1)
-{
-    xq0 = sgr_r(ep, 0) ? xqd0 : 0;
-    xq1 = sgr_r(ep, 1) ? (1 << kPrjBits) - xq0 - xqd1 : 0;
-}
-
-// ---------------------------------------------------------------- search geometry (apply_sgr, EbRestorationPick.c:602-625)
-// One workgroup per tile of a processing unit of a unit; processing units are anchored at the unit's corner and the border comes from the
-// CDEF'd plane itself (no stripe: a Stripe that substitutes nothing).  SEARCH: all 16 sets; f_k = flt_k - u goes to the workspace as
-// int16 ([set][k][plane rows][plane columns]; 0 <= flt <= 2^14 and 0 <= u < 2^14 at 10 bits) and the five sums of
-// get_proj_subspace are added per (unit, set) as integers: per lane in 64 bits, per workgroup in LDS, then one 64-bit atomic per sum.
-// Otherwise: flt0 / flt1 of one set as int32, the reference's av1_selfguided_restoration over the plane.
-template <typename T, bool SEARCH>
-__global__ __launch_bounds__(kThreads) void sgr_box_kernel(const T* __restrict__ cdef, uint32_t cdef_stride, const T* __restrict__ src, uint32_t src_stride,
-                                                       PlaneGeom g, int bd, int ep_begin, int ep_end, int32_t* __restrict__ flt0, int32_t* __restrict__ flt1,
-                                                       uint32_t flt_stride, int16_t* __restrict__ f16, unsigned long long* __restrict__ sums)
-{
-    __shared__ SgrTile t;
-    __shared__ unsigned long long part[5];
-    const int u = blockIdx.z, tid = threadIdx.x, pu = 64 >> g.ss;
-    const Limits L = unit_limits(g, u);
-    const int tx0 = L.h0 + (int)blockIdx.x * pu, ty0 = L.v0 + (int)blockIdx.y * kSgrTileH;
-    if (tx0 >= L.h1 || ty0 >= L.v1) return;
-    const int tw = min(pu, L.h1 - tx0), th = min(kSgrTileH, L.v1 - ty0);
-    const Stripe none = {0, g.h, false, false};
-    load_stripe_rows(t.dat, kSgrDatPitch, cdef, cdef_stride, cdef, cdef_stride, g, none, ty0 - 3, th + 6, tx0 - 3, tw + 6, tid);
-    __syncthreads();
-    sgr_tile_prepare(t, tw, th, bd, tid);
-    for (int ep = ep_begin; ep < ep_end; ep++) {
-        __syncthreads();
-        sgr_tile_ab(t, tw, th, ep, tid);
-        if (SEARCH)
-            for (int k = tid; k < 5; k += kThreads) part[k] = 0;
-        __syncthreads();
-        const bool r0 = sgr_r(ep, 0) != 0, r1 = sgr_r(ep, 1) != 0;
-        long long acc[5] = {0, 0, 0, 0, 0};
-        for (int i = tid; i < th * tw; i += kThreads) {
-            const int r = i / tw, c = i - r * tw, y = ty0 + r, x = tx0 + c;
-            const int dgd = t.dat[(r + 3) * kSgrDatPitch + c + 3], uu = dgd << kRstBits;
-            const int a = r0 ? sgr_flt0(t, r, c, dgd) : uu, b = r1 ? sgr_flt1(t, r, c, dgd) : uu;
-            if (SEARCH) {
-                const long long f0 = a - uu, f1 = b - uu, s = ((int)src[(size_t)y * src_stride + x] << kRstBits) - uu;
-                const size_t at = ((size_t)(ep * 2) * g.h + y) * g.w + x;
-                if (r0) f16[at] = (int16_t)f0;
-                if (r1) f16[at + (size_t)g.h * g.w] = (int16_t)f1;
-                acc[0] += f0 * f0, acc[1] += f1 * f1, acc[2] += f0 * f1, acc[3] += f0 * s, acc[4] += f1 * s;
-            } else {
-                if (r0) flt0[(size_t)y * flt_stride + x] = a;
-                if (r1) flt1[(size_t)y * flt_stride + x] = b;
-            }
-        }
-        if (SEARCH) {
-#pragma unroll
-            for (int k = 0; k < 5; k++)
-                if (acc[k]) atomicAdd(&part[k], (unsigned long long)acc[k]);
-            __syncthreads();
-            for (int k = tid; k < 5; k += kThreads)
-                if (part[k]) atomicAdd(&sums[((size_t)(g.base + u) * kSgrParams + ep) * 5 + k], part[k]);
-        }
-    }
-}
-
-// one lane per (unit, set) of a plane: the sums start at 0; size and set of the job for the solve
-__global__ __launch_bounds__(64) void sgr_search_init_kernel(PlaneGeom g, int64_t* __restrict__ sums, int32_t* __restrict__ size, int32_t* __restrict__ ep)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= g.nx * g.ny * kSgrParams) return;
-    const Limits L = unit_limits(g, i / kSgrParams);
-    const size_t job = (size_t)g.base * kSgrParams + i;
-    for (int k = 0; k < 5; k++) sums[job * 5 + k] = 0;
-    size[job] = (L.h1 - L.h0) * (L.v1 - L.v0);
-    ep[job] = i % kSgrParams;
-}
-
-// ---------------------------------------------------------------- solve: the tail of get_proj_subspace_c (:544-580) and encode_xq (:583-599)
-// IEEE double in the reference's order of operations.  The compiler must not fuse a multiplication with the subtraction that follows it:
-// H00 * H11 - H01 * H10 of a nearly singular H changes in the last place, and with it rint(x * 128).
-__device__ inline void sgr_project(const int64_t* sums, int size, int ep, int32_t xq[2])
-{
-#pragma clang fp contract(off)
-    const double H00 = (double)sums[0] / size, H11 = (double)sums[1] / size, H01 = (double)sums[2] / size, H10 = H01;
-    const double C0 = (double)sums[3] / size, C1 = (double)sums[4] / size;
-    xq[0] = xq[1] = 0;
-    if (sgr_r(ep, 0) == 0) {
-        const double det = H11;
-        if (det < 1e-8) return;
-        xq[1] = (int32_t)__builtin_rint(C1 / det * (1 << kPrjBits));
-    } else if (sgr_r(ep, 1) == 0) {
-        const double det = H00;
-        if (det < 1e-8) return;
-        xq[0] = (int32_t)__builtin_rint(C0 / det * (1 << kPrjBits));
-    } else {
-        const double det = H00 * H11 - H01 * H10;
-        if (det < 1e-8) return;
-        const double x0 = (H11 * C0 - H01 * C1) / det, x1 = (H00 * C1 - H10 * C0) / det;
-        xq[0] = (int32_t)__builtin_rint(x0 * (1 << kPrjBits));
-        xq[1] = (int32_t)__builtin_rint(x1 * (1 << kPrjBits));
-    }
-}
-
-__device__ inline void encode_xq(int ep, const int32_t xq[2], int32_t xqd[2])
-{
-    if (sgr_r(ep, 0) == 0) {
-        xqd[0] = 0;
-        xqd[1] = clampi((1 << kPrjBits) - xq[1], prj_min(1), prj_max(1));
-    } else {
-        xqd[0] = clampi(xq[0], prj_min(0), prj_max(0));
-        xqd[1] = clampi((1 << kPrjBits) - xqd[0] - (sgr_r(ep, 1) ? xq[1] : 0), prj_min(1), prj_max(1));
-    }
-}
-
-__global__ __launch_bounds__(64) void sgr_solve_kernel(const int64_t* __restrict__ sums, const int32_t* __restrict__ size, const int32_t* __restrict__ ep_of,
-                                                   uint32_t n, int32_t* __restrict__ xq_out, int32_t* __restrict__ xqd_out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int ep = ep_of[i] & (kSgrParams - 1);
-    int32_t xq[2], xqd[2];
-    sgr_project(sums + (size_t)i * 5, size[i], ep, xq);
-    encode_xq(ep, xq, xqd);
-    xq_out[2 * i] = xq[0], xq_out[2 * i + 1] = xq[1];
-    xqd_out[2 * i] = xqd[0], xqd_out[2 * i + 1] = xqd[1];
-}
-
-// ---------------------------------------------------------------- the walk: finer_search_pixel_proj_error (:420-481) with start_step 2
-// err_of(xqd) is the error of a candidate.  An accepted move (a tie is accepted) repeats at step 2 only; an accepted minus move ends the
-// step for both parameters (`if (skip) break;` leaves the loop over p).  Every loop is bounded by the parameter's range.
-// Trials: the first; at step 2 at most 63 per parameter (a run of accepted moves spans at most MAX - MIN = 127, so at most 63 moves, and
-// a failing trial takes the place of one: a failed minus attempt means xqd >= MIN + 2, which leaves 62 plus moves and one failing), 126
-// for both; at step 1 a minus and a plus trial per parameter, 4: at most 131.
-constexpr int kSgrWalkMaxTrials = 1 + 2 * 63 + 4;
-
-template <typename Err>
-__device__ inline int64_t sgr_walk(Err& err_of, int ep, int xqd[2], int& n_trials)
-{
-    int64_t err = err_of(xqd);
-    n_trials = 1;
-    for (int s = 2; s >= 1; s >>= 1)
-        for (int p = 0; p < 2; p++) {
-            if (sgr_r(ep, p) == 0) continue;
-            bool skip = false;
-            while (xqd[p] - s >= prj_min(p)) {
-                xqd[p] -= s;
-                const int64_t e = err_of(xqd);
-                n_trials++;
-                if (e > err) {
-                    xqd[p] += s;
-                    break;
-                }
-                err = e, skip = true;
-                if (s != 2) break;
-            }
-            if (skip) break;
-            while (xqd[p] + s <= prj_max(p)) {
-                xqd[p] += s;
-                const int64_t e = err_of(xqd);
-                n_trials++;
-                if (e > err) {
-                    xqd[p] -= s;
-                    break;
-                }
-                err = e;
-                if (s != 2) break;
-            }
-        }
-    return err;
-}
-
-// the error of a constructed table [xqd0 - MIN0][xqd1 - MIN1]: ties, range stops and the skip break without a picture
-struct SgrTableError {
-    const int64_t* table;
-    __device__ int64_t operator()(const int xqd[2]) const { return table[(xqd[0] - prj_min(0)) * 128 + xqd[1] - prj_min(1)]; }
-};
-
-__global__ __launch_bounds__(64) void sgr_walk_table_kernel(const int64_t* __restrict__ tables, const int32_t* __restrict__ ep_of, const int32_t* __restrict__ start,
-                                                        uint32_t n, int32_t* __restrict__ xqd_out, int64_t* __restrict__ err_out, int32_t* __restrict__ n_trials)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    SgrTableError e{tables + (size_t)i * 128 * 128};
-    int xqd[2] = {clampi(start[2 * i], prj_min(0), prj_max(0)), clampi(start[2 * i + 1], prj_min(1), prj_max(1))}, nt;
-    err_out[i] = sgr_walk(e, ep_of[i] & (kSgrParams - 1), xqd, nt);
-    xqd_out[2 * i] = xqd[0], xqd_out[2 * i + 1] = xqd[1];
-    n_trials[i] = nt;
-}
-
-// av1_lowbd_ / av1_highbd_pixel_proj_error (:248-397) of one unit as a workgroup reduction over the stored f0 / f1.  The 8-bit form rounds
-// (u << 7) + xq0 f0 + xq1 f1 by 11 bits and subtracts the source, the 10-bit form rounds xq0 f0 + xq1 f1 and adds dat - src: the same
-// number, as u << 7 = dat << 11.  The three arms on r are the zero xq of decode_xq and the skipped load.
-template <typename T>
-struct SgrUnitError {
-    const T* cdef;
-    const T* src;
-    const int16_t* f0;
-    const int16_t* f1;
-    uint32_t cdef_stride, src_stride;
-    int w, ep;
-    Limits L;
-    unsigned long long* red;
-
-    __device__ int64_t operator()(const int xqd[2]) const
-    {
-        int xq0, xq1;
-        decode_xq(ep, xqd[0], xqd[1], xq0, xq1);
-        const bool r0 = sgr_r(ep, 0) != 0, r1 = sgr_r(ep, 1) != 0;
-        const int tid = threadIdx.x, uw = L.h1 - L.h0, lanes_x = kThreads < 64 ? kThreads : 64, lanes_y = kThreads / lanes_x;
-        unsigned long long acc = 0;
-        for (int y = L.v0 + tid / lanes_x; y < L.v1; y += lanes_y)
-            for (int x = L.h0 + tid % lanes_x; x < L.h0 + uw; x += lanes_x) {
-                const size_t at = (size_t)y * w + x;
-                int v = 1 << (kRstBits + kPrjBits - 1);
-                if (r0) v += xq0 * f0[at];
-                if (r1) v += xq1 * f1[at];
-                const int e = (v >> (kRstBits + kPrjBits)) + (int)cdef[(size_t)y * cdef_stride + x] - (int)src[(size_t)y * src_stride + x];
-                acc += (unsigned long long)(e * e);
-            }
-        if (tid == 0) *red = 0;
-        __syncthreads();
-        if (acc) atomicAdd(red, acc);
-        __syncthreads();
-        const unsigned long long sum = *red;
-        __syncthreads();
-        return (int64_t)sum;
-    }
-};
-
-// one workgroup per (set, unit): every lane follows the same walk, the error of each trial is the workgroup's sum
-template <typename T>
-__global__ __launch_bounds__(kThreads) void sgr_walk_kernel(const T* __restrict__ cdef, uint32_t cdef_stride, const T* __restrict__ src, uint32_t src_stride,
-                                                        PlaneGeom g, const int16_t* __restrict__ f16, const int32_t* __restrict__ start,
-                                                        int32_t* __restrict__ xqd_out, int64_t* __restrict__ err_out, int32_t* __restrict__ n_trials)
-{
-    __shared__ unsigned long long red;
-    const int ep = blockIdx.x, u = blockIdx.y;
-    const size_t job = (size_t)(g.base + u) * kSgrParams + ep, plane = (size_t)g.h * g.w;
-    SgrUnitError<T> e{cdef, src, f16 + (size_t)(ep * 2) * plane, f16 + (size_t)(ep * 2 + 1) * plane, cdef_stride, src_stride, g.w, ep, unit_limits(g, u), &red};
-    int xqd[2] = {start[2 * job], start[2 * job + 1]}, nt;
-    const int64_t err = sgr_walk(e, ep, xqd, nt);
-    if (threadIdx.x == 0) {
-        xqd_out[2 * job] = xqd[0], xqd_out[2 * job + 1] = xqd[1];
-        err_out[job] = err;
-        n_trials[job] = nt;
-    }
-}
-
-// one lane per unit: the smallest error over the sets, strict < with the sets ascending (:643-663); the records of the sets on request
-__global__ __launch_bounds__(64) void sgr_pick_kernel(const int64_t* __restrict__ sums, const int32_t* __restrict__ xq, const int32_t* __restrict__ start,
-                                                  const int32_t* __restrict__ fin, const int64_t* __restrict__ err, const int32_t* __restrict__ n_trials,
-                                                  uint32_t unit_begin, uint32_t unit_end, int32_t* __restrict__ sgrproj, svthip_sgrproj_detail* __restrict__ detail)
-{
-    const uint32_t unit = unit_begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (unit >= unit_end) return;
-    int best = 0;
-    for (int ep = 0; ep < kSgrParams; ep++) {
-        const size_t job = (size_t)unit * kSgrParams + ep;
-        if (err[job] < err[(size_t)unit * kSgrParams + best]) best = ep;
-        if (detail) {
-            svthip_sgrproj_detail d;
-            for (int k = 0; k < 5; k++) d.sums[k] = sums[job * 5 + k];
-            for (int k = 0; k < 2; k++) d.exq[k] = xq[2 * job + k], d.start_xqd[k] = start[2 * job + k], d.xqd[k] = fin[2 * job + k];
-            d.err = err[job], d.n_trials = n_trials[job], d.reserved = 0;
-            detail[job] = d;
-        }
-    }
-    const size_t job = (size_t)unit * kSgrParams + best;
-    sgrproj[4 * unit] = best, sgrproj[4 * unit + 1] = fin[2 * job], sgrproj[4 * unit + 2] = fin[2 * job + 1], sgrproj[4 * unit + 3] = 0;
-}
-
-// ---------------------------------------------------------------- the self-guided unit filter, filter geometry (EbRestoration.c:1066-1246)
-// One workgroup = one tile of one stripe of one unit: apply_selfguided_restoration_c per processing-unit-wide column block from the
-// unit's h_start, rows through the stripe loader; a stripe of 64 luma rows is two tiles (the first stripe of a picture has 56 rows, an
-// even number, so the second tile keeps the row parity).  WRITE: the frame filter for the units of type RESTORE_SGRPROJ.  Otherwise: the
-// SSE against the source, the plain sum of squares.  A set above 15 or an xqd outside its range: nothing of the unit is written and the
-// refusal is counted once (WRITE), or the unit's SSE reads -1.
-template <typename T, bool WRITE>
-__global__ __launch_bounds__(kThreads) void sgr_filter_kernel(const T* __restrict__ cdef, uint32_t cdef_stride, const T* __restrict__ dbk, uint32_t dbk_stride,
-                                                          const T* __restrict__ src, uint32_t src_stride, T* __restrict__ out, uint32_t out_stride, PlaneGeom g,
-                                                          int bd, const int32_t* __restrict__ sgrproj, const uint8_t* __restrict__ flag_base,
-                                                          unsigned long long* __restrict__ sse, uint32_t* __restrict__ refused)
-{
-    __shared__ SgrTile t;
-    __shared__ unsigned long long block_sse;
-    const int u = blockIdx.z, unit = g.base + u, tid = threadIdx.x, pu = 64 >> g.ss, halves = pu / kSgrTileH;
-    // trial: flag = skip this unit; write: flag = the unit's restoration type
-    if (WRITE ? flag_base[unit] != SVTHIP_RESTORE_SGRPROJ : (flag_base && flag_base[unit])) return;
-    const int ep = sgrproj[4 * unit], xqd0 = sgrproj[4 * unit + 1], xqd1 = sgrproj[4 * unit + 2];
-    if ((unsigned)ep >= (unsigned)kSgrParams || xqd0 < prj_min(0) || xqd0 > prj_max(0) || xqd1 < prj_min(1) || xqd1 > prj_max(1)) {
-        if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-            if (WRITE)
-                atomicAdd(refused, 1u);
-            else
-                sse[unit] = ~0ull;
-        }
-        return;
-    }
-    const Limits L = unit_limits(g, u);
-    const Stripe S = unit_stripe(g, L, (int)blockIdx.y / halves);
-    const int tx0 = L.h0 + (int)blockIdx.x * pu, ty0 = S.y0 + ((int)blockIdx.y % halves) * kSgrTileH;
-    if (tx0 >= L.h1 || S.y0 >= L.v1 || ty0 >= S.y1) return;
-    const int tw = min(pu, L.h1 - tx0), th = min(kSgrTileH, S.y1 - ty0);
-    load_stripe_rows(t.dat, kSgrDatPitch, cdef, cdef_stride, dbk, dbk_stride, g, S, ty0 - 3, th + 6, tx0 - 3, tw + 6, tid);
-    if (tid == 0) block_sse = 0;
-    __syncthreads();
-    sgr_tile_prepare(t, tw, th, bd, tid);
-    __syncthreads();
-    sgr_tile_ab(t, tw, th, ep, tid);
-    __syncthreads();
-    int xq0, xq1;
-    decode_xq(ep, xqd0, xqd1, xq0, xq1);
-    const bool r0 = sgr_r(ep, 0) != 0, r1 = sgr_r(ep, 1) != 0;
-    const int top = (1 << bd) - 1;
-    unsigned long long acc = 0;
-    for (int i = tid; i < th * tw; i += kThreads) {
-        const int r = i / tw, c = i - r * tw, y = ty0 + r, x = tx0 + c;
-        const int dgd = t.dat[(r + 3) * kSgrDatPitch + c + 3], uu = dgd << kRstBits;
-        int v = uu << kPrjBits;
-        if (r0) v += xq0 * (sgr_flt0(t, r, c, dgd) - uu);
-        if (r1) v += xq1 * (sgr_flt1(t, r, c, dgd) - uu);
-        const int w16 = (int16_t)((v + (1 << (kPrjBits + kRstBits - 1))) >> (kPrjBits + kRstBits));
-        const int px = clampi(w16, 0, top);
-        if (WRITE) {
-            out[(size_t)y * out_stride + x] = (T)px;
-        } else {
-            const int d = px - (int)src[(size_t)y * src_stride + x];
-            acc += (unsigned long long)(d * d);
-        }
-    }
-    if (!WRITE) {
-        if (acc) atomicAdd(&block_sse, acc);
-        __syncthreads();
-        if (tid == 0 && block_sse) atomicAdd(&sse[unit], block_sse);
-    }
-}
-
-template <typename T>
-const T* plane_ptr(const void* p) { return static_cast<const T*>(p); }
-
-}  // namespace
-
-// ---------------------------------------------------------------- host side
 uint32_t lr_unit_geometry(uint32_t width, uint32_t height, const uint32_t unit_size[3], uint32_t unit_base[4], int32_t* limits)
 {
     uint32_t n = 0;
@@ -1011,218 +36,81 @@ uint32_t lr_walk_max_trials(int win)
 LrWorkspace lr_workspace(uint32_t n_units)
 {
     LrWorkspace w;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
-    w.raw = take((size_t)n_units * kRawStride * 8);
-    w.M = take((size_t)n_units * SVTHIP_WIENER_STATS_M * 8);
-    w.H = take((size_t)n_units * SVTHIP_WIENER_STATS_H * 8);
-    w.sse_none = take((size_t)n_units * 8);
-    w.trial_sse = take((size_t)n_units * 8);
-    w.state = take((size_t)n_units * sizeof(svthip_wiener_walk_state));
-    w.start_taps = take((size_t)n_units * 32);
-    w.avg = take((size_t)n_units * 4);
-    w.rejected = take((size_t)n_units * 4);
-    w.total = at;
+    WorkspaceLayout L;
+    w.raw = L.take((size_t)n_units * kRawStride * 8);
+    w.M = L.take((size_t)n_units * SVTHIP_WIENER_STATS_M * 8);
+    w.H = L.take((size_t)n_units * SVTHIP_WIENER_STATS_H * 8);
+    w.sse_none = L.take((size_t)n_units * 8);
+    w.trial_sse = L.take((size_t)n_units * 8);
+    w.state = L.take((size_t)n_units * sizeof(svthip_wiener_walk_state));
+    w.start_taps = L.take((size_t)n_units * 32);
+    w.avg = L.take((size_t)n_units * 4);
+    w.rejected = L.take((size_t)n_units * 4);
+    w.total = L.at;
     return w;
-}
-
-template <typename T>
-static hipError_t stats_t(const svthip_lr_picture& pic, int ps, int pe, int bd, void* raw, int64_t* M, int64_t* H, int32_t* avg, int64_t* sse_none,
-                          hipStream_t s)
-{
-    for (int p = ps; p < pe; p++) {
-        const PlaneGeom g = plane_geom(pic.width, pic.height, pic.unit_size, p);
-        const int n = g.nx * g.ny, tiles = (g.unit * 3 / 2 + kStatTile - 1) / kStatTile;
-        auto* r = static_cast<unsigned long long*>(raw);
-        hipError_t e = hipMemsetAsync(r + (size_t)g.base * kRawStride, 0, (size_t)n * kRawStride * 8, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(lr_stats_kernel<T>, dim3(tiles, tiles, n), dim3(kThreads), 0, s, plane_ptr<T>(pic.cdef[p]), pic.cdef_stride[p],
-                           plane_ptr<T>(pic.source[p]), pic.source_stride[p], g, r);
-        hipLaunchKernelGGL(lr_stats_finish_kernel, dim3(n), dim3(kThreads), 0, s, r, g, bd, M, H, avg, sse_none);
-    }
-    return hipGetLastError();
 }
 
 hipError_t launch_lr_stats(const svthip_lr_picture& pic, int ps, int pe, int bd, void* raw, int64_t* M, int64_t* H, int32_t* avg, int64_t* sse_none,
                            hipStream_t s)
 {
-    return bd > 8 ? stats_t<uint16_t>(pic, ps, pe, bd, raw, M, H, avg, sse_none, s) : stats_t<uint8_t>(pic, ps, pe, bd, raw, M, H, avg, sse_none, s);
+    return by_bit_depth(bd, [&](auto t) {
+        using T = typename decltype(t)::type;
+        for (int p = ps; p < pe; p++) {
+            const PlaneGeom g = plane_geom(pic.width, pic.height, pic.unit_size, p);
+            auto* r = static_cast<unsigned long long*>(raw);
+            hipError_t e = hipMemsetAsync(r + (size_t)g.base * kRawStride, 0, (size_t)g.nx * g.ny * kRawStride * 8, s);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(lr_stats_kernel<T>, lr_stats_grid(g), dim3(kThreads), 0, s, plane_ptr<T>(pic.cdef[p]), pic.cdef_stride[p],
+                               plane_ptr<T>(pic.source[p]), pic.source_stride[p], g, r);
+            hipLaunchKernelGGL(lr_stats_finish_kernel, unit_grid(g), dim3(kThreads), 0, s, r, g, bd, M, H, avg, sse_none);
+        }
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_lr_solve(const int64_t* M, const int64_t* H, uint32_t unit_begin, uint32_t unit_end, int win, int16_t* taps, int32_t* rejected,
                            hipStream_t s)
 {
     if (unit_end == unit_begin) return hipSuccess;
-    hipLaunchKernelGGL(lr_solve_kernel, dim3((unit_end - unit_begin + 63) / 64), dim3(64), 0, s, M, H, unit_begin, unit_end, win, taps, rejected);
+    hipLaunchKernelGGL(lr_solve_kernel, lane_grid(unit_end - unit_begin), dim3(64), 0, s, M, H, unit_begin, unit_end, win, taps, rejected);
     return hipGetLastError();
 }
 
-template <typename T, bool WRITE>
-static hipError_t filter_t(const svthip_lr_picture& pic, void* const out[3], const uint32_t out_stride[3], int ps, int pe, int bd, const void* taps,
-                           size_t taps_stride, const uint8_t* flag, size_t flag_stride, int64_t* sse, uint32_t* refused, int sgrproj_elsewhere, hipStream_t s)
+// the Wiener unit filter over the planes: trial (sse) or frame filter (out)
+template <bool WRITE>
+static hipError_t wiener_filter(const svthip_lr_picture& pic, void* const out[3], const uint32_t out_stride[3], int ps, int pe, int bd, const void* taps,
+                                size_t taps_stride, const uint8_t* flag, size_t flag_stride, int64_t* sse, uint32_t* refused, int sgrproj_elsewhere, hipStream_t s)
 {
-    for (int p = ps; p < pe; p++) {
-        const PlaneGeom g = plane_geom(pic.width, pic.height, pic.unit_size, p);
-        const int n = g.nx * g.ny, max_side = g.unit * 3 / 2, sh = 64 >> g.ss;
-        if (!WRITE) {
-            hipError_t e = hipMemsetAsync(sse + g.base, 0, (size_t)n * 8, s);
-            if (e != hipSuccess) return e;
-        }
-        // a unit of up to 1.5 unit sizes starts on a stripe boundary (or at row 0) and so meets at most ceil(1.5 unit / stripe) + 1 stripes
-        hipLaunchKernelGGL((lr_filter_kernel<T, WRITE>), dim3((max_side + kFiltCols - 1) / kFiltCols, (max_side + sh - 1) / sh + 1, n), dim3(kThreads), 0, s,
-                           plane_ptr<T>(pic.cdef[p]), pic.cdef_stride[p], plane_ptr<T>(pic.deblocked[p]), pic.deblocked_stride[p],
-                           plane_ptr<T>(pic.source[p]), pic.source_stride[p], WRITE ? static_cast<T*>(out[p]) : nullptr, WRITE ? out_stride[p] : 0u, g, bd,
-                           static_cast<const uint8_t*>(taps), taps_stride, flag, flag_stride, reinterpret_cast<unsigned long long*>(sse), refused, sgrproj_elsewhere);
-    }
-    return hipGetLastError();
+    return by_bit_depth(bd, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_unit_filter<T, WRITE>(lr_filter_kernel<T, WRITE>, lr_filter_grid, pic, out, out_stride, ps, pe, bd, sse, s,
+                                            static_cast<const uint8_t*>(taps), taps_stride, flag, flag_stride, reinterpret_cast<unsigned long long*>(sse),
+                                            refused, sgrproj_elsewhere);
+    });
 }
 
 hipError_t launch_lr_trial(const svthip_lr_picture& pic, int ps, int pe, int bd, const void* taps, size_t taps_stride, const uint8_t* skip,
                            size_t skip_stride, int64_t* sse, hipStream_t s)
 {
-    return bd > 8 ? filter_t<uint16_t, false>(pic, nullptr, nullptr, ps, pe, bd, taps, taps_stride, skip, skip_stride, sse, nullptr, 0, s)
-                  : filter_t<uint8_t, false>(pic, nullptr, nullptr, ps, pe, bd, taps, taps_stride, skip, skip_stride, sse, nullptr, 0, s);
-}
-
-// the self-guided unit filter over the planes: trial (sse) or frame filter (out)
-template <typename T, bool WRITE>
-static hipError_t sgr_filter_t(const svthip_lr_picture& pic, void* const out[3], const uint32_t out_stride[3], int ps, int pe, int bd, const int32_t* sgrproj,
-                               const uint8_t* flag, int64_t* sse, uint32_t* refused, hipStream_t s)
-{
-    for (int p = ps; p < pe; p++) {
-        const PlaneGeom g = plane_geom(pic.width, pic.height, pic.unit_size, p);
-        const int n = g.nx * g.ny, max_side = g.unit * 3 / 2, sh = 64 >> g.ss;
-        if (!WRITE) {
-            hipError_t e = hipMemsetAsync(sse + g.base, 0, (size_t)n * 8, s);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((sgr_filter_kernel<T, WRITE>), dim3((max_side + sh - 1) / sh, ((max_side + sh - 1) / sh + 1) * (sh / kSgrTileH), n), dim3(kThreads), 0, s,
-                           plane_ptr<T>(pic.cdef[p]), pic.cdef_stride[p], plane_ptr<T>(pic.deblocked[p]), pic.deblocked_stride[p],
-                           plane_ptr<T>(pic.source[p]), pic.source_stride[p], WRITE ? static_cast<T*>(out[p]) : nullptr, WRITE ? out_stride[p] : 0u, g, bd,
-                           sgrproj, flag, reinterpret_cast<unsigned long long*>(sse), refused);
-    }
-    return hipGetLastError();
+    return wiener_filter<false>(pic, nullptr, nullptr, ps, pe, bd, taps, taps_stride, skip, skip_stride, sse, nullptr, 0, s);
 }
 
 // The frame filter for the three unit types: the Wiener kernel copies RESTORE_NONE units and filters RESTORE_WIENER ones, the self-guided
 // kernel filters RESTORE_SGRPROJ ones.  Without sgrproj such a unit is refused by the Wiener kernel, without taps a Wiener unit is.
+// It is here because the Wiener kernel is the pass that looks at every unit; the self-guided pass is one call into lr_sgrproj.hip.
 hipError_t launch_lr_filter_frame(const svthip_lr_picture& pic, void* const out[3], const uint32_t out_stride[3], int ps, int pe, int bd,
                                   const uint8_t* unit_type, const int16_t* taps, const int32_t* sgrproj, uint32_t* refused, hipStream_t s)
 {
-    hipError_t e = bd > 8 ? filter_t<uint16_t, true>(pic, out, out_stride, ps, pe, bd, taps, 32, unit_type, 1, nullptr, refused, sgrproj != nullptr, s)
-                          : filter_t<uint8_t, true>(pic, out, out_stride, ps, pe, bd, taps, 32, unit_type, 1, nullptr, refused, sgrproj != nullptr, s);
+    hipError_t e = wiener_filter<true>(pic, out, out_stride, ps, pe, bd, taps, 32, unit_type, 1, nullptr, refused, sgrproj != nullptr, s);
     if (e != hipSuccess || !sgrproj) return e;
-    return bd > 8 ? sgr_filter_t<uint16_t, true>(pic, out, out_stride, ps, pe, bd, sgrproj, unit_type, nullptr, refused, s)
-                  : sgr_filter_t<uint8_t, true>(pic, out, out_stride, ps, pe, bd, sgrproj, unit_type, nullptr, refused, s);
-}
-
-hipError_t launch_sgr_trial(const svthip_lr_picture& pic, int ps, int pe, int bd, const int32_t* sgrproj, const uint8_t* skip, int64_t* sse, hipStream_t s)
-{
-    return bd > 8 ? sgr_filter_t<uint16_t, false>(pic, nullptr, nullptr, ps, pe, bd, sgrproj, skip, sse, nullptr, s)
-                  : sgr_filter_t<uint8_t, false>(pic, nullptr, nullptr, ps, pe, bd, sgrproj, skip, sse, nullptr, s);
-}
-
-uint32_t sgr_walk_max_trials() { return kSgrWalkMaxTrials; }
-
-// The workspace of the search: per (unit, set) job the sums, size, set, xq, start xqd, final xqd, error and trial count, sized for the
-// most units a picture of this size can have (unit size 64 in every plane), then f0 / f1 of every set: per plane [16][2][rows][columns] int16.
-SgrWorkspace sgr_workspace(uint32_t width, uint32_t height)
-{
-    SgrWorkspace w;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t jobs = (size_t)3 * units_in((int)width, 64) * units_in((int)height, 64) * kSgrParams;
-    w.sums = take(jobs * 5 * 8);
-    w.err = take(jobs * 8);
-    w.size = take(jobs * 4);
-    w.ep = take(jobs * 4);
-    w.ntr = take(jobs * 4);
-    w.xq = take(jobs * 8);
-    w.start = take(jobs * 8);
-    w.fin = take(jobs * 8);
-    for (int p = 0; p < 3; p++) w.f[p] = take((size_t)(width >> (p > 0)) * (height >> (p > 0)) * kSgrParams * 2 * sizeof(int16_t));
-    w.total = at;
-    return w;
-}
-
-template <typename T>
-static hipError_t sgr_plane_t(const svthip_lr_picture& pic, int p, int bd, int ep, int32_t* flt0, int32_t* flt1, uint32_t flt_stride, hipStream_t s)
-{
-    const PlaneGeom g = plane_geom(pic.width, pic.height, pic.unit_size, p);
-    const int max_side = g.unit * 3 / 2, pu = 64 >> g.ss;
-    hipLaunchKernelGGL((sgr_box_kernel<T, false>), dim3((max_side + pu - 1) / pu, (max_side + kSgrTileH - 1) / kSgrTileH, g.nx * g.ny), dim3(kThreads), 0, s,
-                       plane_ptr<T>(pic.cdef[p]), pic.cdef_stride[p], (const T*)nullptr, 0u, g, bd, ep, ep + 1, flt0, flt1, flt_stride, (int16_t*)nullptr,
-                       (unsigned long long*)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_sgr_plane(const svthip_lr_picture& pic, int plane, int bd, int ep, int32_t* flt0, int32_t* flt1, uint32_t flt_stride, hipStream_t s)
-{
-    return bd > 8 ? sgr_plane_t<uint16_t>(pic, plane, bd, ep, flt0, flt1, flt_stride, s) : sgr_plane_t<uint8_t>(pic, plane, bd, ep, flt0, flt1, flt_stride, s);
-}
-
-hipError_t launch_sgr_solve(const int64_t* sums, const int32_t* size, const int32_t* ep, uint32_t n, int32_t* xq, int32_t* xqd, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(sgr_solve_kernel, dim3((n + 63) / 64), dim3(64), 0, s, sums, size, ep, n, xq, xqd);
-    return hipGetLastError();
-}
-
-hipError_t launch_sgr_walk_table(const int64_t* tables, const int32_t* ep, const int32_t* start, uint32_t n, int32_t* xqd, int64_t* err, int32_t* n_trials,
-                                 hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(sgr_walk_table_kernel, dim3((n + 63) / 64), dim3(64), 0, s, tables, ep, start, n, xqd, err, n_trials);
-    return hipGetLastError();
-}
-
-// search_sgrproj_seg for the units of the planes: box filter and sums, solve, walk, pick, then the SSE of the picked filter in filter geometry
-template <typename T>
-static hipError_t sgr_search_t(const svthip_lr_picture& pic, int ps, int pe, int bd, uint8_t* work, int32_t* sgrproj, int64_t* sse,
-                               svthip_sgrproj_detail* detail, hipStream_t s)
-{
-    const SgrWorkspace W = sgr_workspace(pic.width, pic.height);
-    auto* sums = reinterpret_cast<int64_t*>(work + W.sums);
-    auto* err = reinterpret_cast<int64_t*>(work + W.err);
-    auto* size = reinterpret_cast<int32_t*>(work + W.size);
-    auto* ep = reinterpret_cast<int32_t*>(work + W.ep);
-    auto* ntr = reinterpret_cast<int32_t*>(work + W.ntr);
-    auto* xq = reinterpret_cast<int32_t*>(work + W.xq);
-    auto* start = reinterpret_cast<int32_t*>(work + W.start);
-    auto* fin = reinterpret_cast<int32_t*>(work + W.fin);
-    for (int p = ps; p < pe; p++) {
-        const PlaneGeom g = plane_geom(pic.width, pic.height, pic.unit_size, p);
-        const int n = g.nx * g.ny, max_side = g.unit * 3 / 2, pu = 64 >> g.ss;
-        const size_t job0 = (size_t)g.base * kSgrParams;
-        auto* f16 = reinterpret_cast<int16_t*>(work + W.f[p]);
-        hipLaunchKernelGGL(sgr_search_init_kernel, dim3((n * kSgrParams + 63) / 64), dim3(64), 0, s, g, sums, size, ep);
-        hipLaunchKernelGGL((sgr_box_kernel<T, true>), dim3((max_side + pu - 1) / pu, (max_side + kSgrTileH - 1) / kSgrTileH, n), dim3(kThreads), 0, s,
-                           plane_ptr<T>(pic.cdef[p]), pic.cdef_stride[p], plane_ptr<T>(pic.source[p]), pic.source_stride[p], g, bd, 0, kSgrParams,
-                           (int32_t*)nullptr, (int32_t*)nullptr, 0u, f16, reinterpret_cast<unsigned long long*>(sums));
-        hipLaunchKernelGGL(sgr_solve_kernel, dim3((n * kSgrParams + 63) / 64), dim3(64), 0, s, sums + job0 * 5, size + job0, ep + job0,
-                           (uint32_t)(n * kSgrParams), xq + job0 * 2, start + job0 * 2);
-        hipLaunchKernelGGL(sgr_walk_kernel<T>, dim3(kSgrParams, n), dim3(kThreads), 0, s, plane_ptr<T>(pic.cdef[p]), pic.cdef_stride[p],
-                           plane_ptr<T>(pic.source[p]), pic.source_stride[p], g, f16, start, fin, err, ntr);
-        hipLaunchKernelGGL(sgr_pick_kernel, dim3((n + 63) / 64), dim3(64), 0, s, sums, xq, start, fin, err, ntr, (uint32_t)g.base, (uint32_t)(g.base + n),
-                           sgrproj, detail);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return sgr_filter_t<T, false>(pic, nullptr, nullptr, ps, pe, bd, sgrproj, nullptr, sse, nullptr, s);
-}
-
-hipError_t launch_sgr_search(const svthip_lr_picture& pic, int ps, int pe, int bd, void* work, int32_t* sgrproj, int64_t* sse, svthip_sgrproj_detail* detail,
-                             hipStream_t s)
-{
-    return bd > 8 ? sgr_search_t<uint16_t>(pic, ps, pe, bd, static_cast<uint8_t*>(work), sgrproj, sse, detail, s)
-                  : sgr_search_t<uint8_t>(pic, ps, pe, bd, static_cast<uint8_t*>(work), sgrproj, sse, detail, s);
+    return launch_sgr_filter_frame(pic, out, out_stride, ps, pe, bd, unit_type, sgrproj, refused, s);
 }
 
 hipError_t launch_lr_walk_init(svthip_wiener_walk_state* state, const int16_t* taps, const int32_t* rejected, uint32_t unit_begin, uint32_t unit_end,
                                int win, hipStream_t s)
 {
     if (unit_end == unit_begin) return hipSuccess;
-    hipLaunchKernelGGL(lr_walk_init_kernel, dim3((unit_end - unit_begin + 63) / 64), dim3(64), 0, s, state, taps, rejected, unit_begin, unit_end, win);
+    hipLaunchKernelGGL(lr_walk_init_kernel, lane_grid(unit_end - unit_begin), dim3(64), 0, s, state, taps, rejected, unit_begin, unit_end, win);
     return hipGetLastError();
 }
 
@@ -1234,16 +122,38 @@ hipError_t launch_lr_walk_step(svthip_wiener_walk_state* state, const int64_t* t
         if (e != hipSuccess) return e;
     }
     if (unit_end == unit_begin) return hipSuccess;
-    hipLaunchKernelGGL(lr_walk_step_kernel, dim3((unit_end - unit_begin + 63) / 64), dim3(64), 0, s, state, trial_sse, unit_begin, unit_end, pending);
+    hipLaunchKernelGGL(lr_walk_step_kernel, lane_grid(unit_end - unit_begin), dim3(64), 0, s, state, trial_sse, unit_begin, unit_end, pending);
     return hipGetLastError();
 }
 
-hipError_t launch_lr_search_output(const svthip_wiener_walk_state* state, const int64_t* sse_none, uint32_t unit_begin, uint32_t unit_end, int64_t* sse,
-                                   int16_t* taps, int32_t* n_trials, hipStream_t s)
+// search_wiener for the units of the planes: stats -> solve -> walk init, then n_steps x (trial of every unfinished unit -> step), then the
+// output; the state lives in the workspace, so that a later call can resume
+hipError_t launch_lr_search(const svthip_lr_picture& pic, int ps, int pe, int bd, uint32_t n_steps, bool resume, void* work, int64_t* sse, int16_t* taps,
+                            int32_t* n_trials, int32_t* pending, hipStream_t s)
 {
-    if (unit_end == unit_begin) return hipSuccess;
-    hipLaunchKernelGGL(lr_search_output_kernel, dim3((unit_end - unit_begin + 63) / 64), dim3(64), 0, s, state, sse_none, unit_begin, unit_end, sse, taps,
-                       n_trials);
+    uint32_t base[4];
+    const LrWorkspace W = lr_workspace(lr_unit_geometry(pic.width, pic.height, pic.unit_size, base, nullptr));
+    const WorkspaceView V{static_cast<uint8_t*>(work)};
+    int64_t *M = V.at<int64_t>(W.M), *H = V.at<int64_t>(W.H), *sse_none = V.at<int64_t>(W.sse_none), *trial = V.at<int64_t>(W.trial_sse);
+    auto* state = V.at<svthip_wiener_walk_state>(W.state);
+    int16_t* start = V.at<int16_t>(W.start_taps);
+    int32_t* rejected = V.at<int32_t>(W.rejected);
+    const uint32_t ub = base[ps], ue = base[pe];
+    hipError_t e = hipSuccess;
+    if (!resume) {
+        e = launch_lr_stats(pic, ps, pe, bd, V.at<void>(W.raw), M, H, V.at<int32_t>(W.avg), sse_none, s);
+        for (int p = ps; p < pe && e == hipSuccess; p++) {
+            e = launch_lr_solve(M, H, base[p], base[p + 1], p ? 5 : 7, start, rejected, s);
+            if (e == hipSuccess) e = launch_lr_walk_init(state, start, rejected, base[p], base[p + 1], p ? 5 : 7, s);
+        }
+    }
+    if (n_steps == 0) n_steps = lr_walk_max_trials(7);
+    for (uint32_t i = 0; i < n_steps && e == hipSuccess; i++) {
+        e = launch_lr_trial(pic, ps, pe, bd, state[0].taps, sizeof(svthip_wiener_walk_state), &state[0].done, sizeof(svthip_wiener_walk_state), trial, s);
+        if (e == hipSuccess) e = launch_lr_walk_step(state, trial, ub, ue, pending, s);
+    }
+    if (e != hipSuccess || ue == ub) return e;
+    hipLaunchKernelGGL(lr_search_output_kernel, lane_grid(ue - ub), dim3(64), 0, s, state, sse_none, ub, ue, sse, taps, n_trials);
     return hipGetLastError();
 }
 

@@ -193,7 +193,8 @@ hipError_t launch_lf_sse_table(const svthip_lf_picture& pic, const svthip_lf_mi*
 hipError_t launch_lf_walk(const uint64_t* sse, int start_level, int only_4x4, int32_t* out0, int32_t* out1, uint64_t* visited, hipStream_t s);
 hipError_t launch_lf_set_levels(int32_t* levels, const int32_t v[4], hipStream_t s);
 
-// lr_wiener.hip: Wiener loop restoration -- unit statistics, the solve, the unit filter as SSE trial and as frame filter, the refinement walk
+// lr_wiener.hip: Wiener loop restoration -- the unit geometry, the statistics, the solve, the unit filter as SSE trial, the refinement walk
+// step by step and as the whole search, and the frame filter of the three unit types (kernels: lr_wiener_kernels.h)
 struct LrWorkspace {   // byte offsets into the caller's workspace, and its size
     size_t raw, M, H, sse_none, trial_sse, state, start_taps, avg, rejected, total;
 };
@@ -212,9 +213,10 @@ hipError_t launch_lr_walk_init(svthip_wiener_walk_state* state, const int16_t* t
                                int win, hipStream_t s);
 hipError_t launch_lr_walk_step(svthip_wiener_walk_state* state, const int64_t* trial_sse, uint32_t unit_begin, uint32_t unit_end, int32_t* pending,
                                hipStream_t s);
-hipError_t launch_lr_search_output(const svthip_wiener_walk_state* state, const int64_t* sse_none, uint32_t unit_begin, uint32_t unit_end,
-                                   int64_t* sse, int16_t* taps, int32_t* n_trials, hipStream_t s);
-// lr_wiener.hip, self-guided restoration: the box filter in search geometry with the projection sums, the solve, the walk, the unit filter
+SVTHIP_LOCAL hipError_t launch_lr_search(const svthip_lr_picture& pic, int plane_start, int plane_end, int bd, uint32_t n_steps, bool resume,
+                                         void* work, int64_t* sse, int16_t* taps, int32_t* n_trials, int32_t* pending, hipStream_t s);
+// lr_sgrproj.hip: self-guided loop restoration -- the box filter over a plane, the solve, the walk on tables, the whole search, the unit
+// filter as SSE trial and as the self-guided pass of launch_lr_filter_frame (kernels: lr_sgrproj_kernels.h)
 struct SgrWorkspace {   // byte offsets into the caller's workspace, and its size
     size_t sums, err, size, ep, ntr, xq, start, fin, f[3], total;
 };
@@ -228,6 +230,9 @@ hipError_t launch_sgr_search(const svthip_lr_picture& pic, int plane_start, int 
                              svthip_sgrproj_detail* detail, hipStream_t s);
 hipError_t launch_sgr_trial(const svthip_lr_picture& pic, int plane_start, int plane_end, int bd, const int32_t* sgrproj, const uint8_t* skip, int64_t* sse,
                             hipStream_t s);
+SVTHIP_LOCAL hipError_t launch_sgr_filter_frame(const svthip_lr_picture& pic, void* const out[3], const uint32_t out_stride[3], int plane_start,
+                                                int plane_end, int bd, const uint8_t* unit_type, const int32_t* sgrproj, uint32_t* refused,
+                                                hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

@@ -738,7 +738,6 @@ int32_t lr_trial_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t p
     return SVTHIP_OK;
 }
 
-// stats -> solve -> walk init, then n_steps x (trial of every unfinished unit -> step), all on one stream; the state lives in d_work
 int32_t lr_search_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t ps, uint32_t pe, int bd, uint32_t n_steps, uint32_t resume,
                         void* d_work, int64_t* d_sse, int16_t* d_taps, int32_t* d_n_trials, int32_t* d_pending, void* stream)
 {
@@ -746,34 +745,7 @@ int32_t lr_search_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t 
     TRY(check_non_null({d_work, d_sse, d_taps, d_n_trials, d_pending}));
     if (!aligned({d_work, d_sse}, 8) || !aligned({d_n_trials, d_pending}, 4) || !aligned(d_taps, 2))
         return fail(SVTHIP_ERR_BAD_PARAMETER, "d_work and d_sse must be 8-byte, d_n_trials and d_pending 4-byte, d_taps 2-byte aligned");
-    uint32_t base[4];
-    svthip::lr_unit_geometry(pic->width, pic->height, pic->unit_size, base, nullptr);
-    const svthip::LrWorkspace W = svthip::lr_workspace(base[3]);
-    uint8_t* w = static_cast<uint8_t*>(d_work);
-    auto* M = reinterpret_cast<int64_t*>(w + W.M);
-    auto* H = reinterpret_cast<int64_t*>(w + W.H);
-    auto* sse_none = reinterpret_cast<int64_t*>(w + W.sse_none);
-    auto* trial = reinterpret_cast<int64_t*>(w + W.trial_sse);
-    auto* state = reinterpret_cast<svthip_wiener_walk_state*>(w + W.state);
-    auto* start = reinterpret_cast<int16_t*>(w + W.start_taps);
-    auto* avg = reinterpret_cast<int32_t*>(w + W.avg);
-    auto* rejected = reinterpret_cast<int32_t*>(w + W.rejected);
-    const uint32_t ub = base[ps], ue = base[pe];
-    hipStream_t s = call_stream(ctx, stream);
-    if (!resume) {
-        HIP_TRY(svthip::launch_lr_stats(*pic, (int)ps, (int)pe, bd, w + W.raw, M, H, avg, sse_none, s));
-        for (uint32_t p = ps; p < pe; p++) {
-            HIP_TRY(svthip::launch_lr_solve(M, H, base[p], base[p + 1], p ? 5 : 7, start, rejected, s));
-            HIP_TRY(svthip::launch_lr_walk_init(state, start, rejected, base[p], base[p + 1], p ? 5 : 7, s));
-        }
-    }
-    if (n_steps == 0) n_steps = svthip::lr_walk_max_trials(7);
-    for (uint32_t i = 0; i < n_steps; i++) {
-        HIP_TRY(svthip::launch_lr_trial(*pic, (int)ps, (int)pe, bd, state[0].taps, sizeof(svthip_wiener_walk_state), &state[0].done,
-                                        sizeof(svthip_wiener_walk_state), trial, s));
-        HIP_TRY(svthip::launch_lr_walk_step(state, trial, ub, ue, d_pending, s));
-    }
-    HIP_TRY(svthip::launch_lr_search_output(state, sse_none, ub, ue, d_sse, d_taps, d_n_trials, s));
+    HIP_TRY(svthip::launch_lr_search(*pic, (int)ps, (int)pe, bd, n_steps, resume != 0, d_work, d_sse, d_taps, d_n_trials, d_pending, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 

@@ -3,7 +3,8 @@ of M and H, the solve on the fixture's and on constructed M and H, the SSE of ev
 against the recorded traces and constructed error functions, the whole search (default step count, and three steps at a time resumed
 until nothing is pending), the frame filter for every recorded assignment and fed from a search's device-side taps, the plane-subset
 calls and every refusal.  Planes sit inside larger allocations with an odd guard of pattern samples that must come back untouched.
-Everything is integer: every comparison is equality."""
+Everything is integer: every comparison is equality.  A tensor that torch fills is handed to an entry only after _ready()
+(tests/lr_gpu_util.py)."""
 import os
 import sys
 
@@ -15,71 +16,29 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden
 
 import lr_util as lu  # noqa: E402
 import svtav1_hip  # noqa: E402
+from lr_gpu_util import DevCase, _dev, _ready  # noqa: E402
 from test_lr_vs_ref import N_CASES, fixture, fixture_case, synthetic_error, taps_of, unit_traces  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 9   # samples of guard around every plane, odd so that the planes start unaligned to a dword row
-FILL = {8: 0xA5, 10: 0x2A5}
 INT64_MAX = lu.INT64_MAX
 
 
-def _dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda:0")
-
-
-class Guarded:
-    """three planes embedded in larger allocations filled with a guard pattern"""
-
-    def __init__(self, torch, planes, bd):
-        self.bd, self.host, self.dev, self.ptr, self.stride = bd, [], [], [], []
-        for p, pl in enumerate(planes):
-            ph, pw = pl.shape
-            big = np.full((ph + 2 * GUARD, pw + 2 * GUARD + p), FILL[bd] + p, pl.dtype)
-            big[GUARD:GUARD + ph, GUARD:GUARD + pw] = pl
-            d = _dev(torch, big)
-            self.host.append(big), self.dev.append(d)
-            self.ptr.append(d.data_ptr() + (GUARD * big.shape[1] + GUARD) * big.itemsize)
-            self.stride.append(big.shape[1])
-
-    def planes(self):
-        """(planes, guard untouched)"""
-        out, ok = [], True
-        for p in range(3):
-            big = self.dev[p].cpu().numpy().view(self.host[p].dtype).reshape(self.host[p].shape)
-            ph, pw = big.shape[0] - 2 * GUARD, big.shape[1] - 2 * GUARD - p
-            out.append(big[GUARD:GUARD + ph, GUARD:GUARD + pw].copy())
-            mask = np.ones(big.shape, bool)
-            mask[GUARD:GUARD + ph, GUARD:GUARD + pw] = False
-            ok &= bool(np.all(big[mask] == FILL[self.bd] + p))
-        return out, ok
-
-
-class DevCase:
-    def __init__(self, torch, F):
-        self.F, self.bd = F, F["bd"]
-        self.cdef, self.dbk, self.src = (Guarded(torch, F[k], F["bd"]) for k in ("cdef", "dbk", "src"))
-        self.out = Guarded(torch, [np.full_like(p, 7) for p in F["cdef"]], F["bd"])
-        self.pic = svtav1_hip.make_lr_picture(F["w"], F["h"], self.cdef.ptr, self.cdef.stride, self.dbk.ptr, self.dbk.stride, self.src.ptr,
-                                              self.src.stride)
-        self.n = F["base"][3]
-        self.work = torch.zeros(svtav1_hip.lr_workspace_bytes(self.n) // 8, dtype=torch.int64, device="cuda:0")
-
-    def inputs_untouched(self):
-        return all(g.planes()[1] and all(np.array_equal(a, b) for a, b in zip(g.planes()[0], self.F[k]))
-                   for g, k in ((self.cdef, "cdef"), (self.dbk, "dbk"), (self.src, "src")))
+def _case(torch, F):
+    return DevCase(torch, F, svtav1_hip.lr_workspace_bytes(F["base"][3]))
 
 
 @pytest.mark.parametrize("c", range(N_CASES))
 def test_stats_match_fixture(hip_ctx, c):
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     n = D.n
     d_M = torch.full((n, 49), -1, dtype=torch.int64, device="cuda:0")
     d_H = torch.full((n, 49 * 49), -1, dtype=torch.int64, device="cuda:0")
     d_avg = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
     d_none = torch.full((n,), -1, dtype=torch.int64, device="cuda:0")
+    _ready(torch)
     hip_ctx.av1_wiener_stats_dev(D.pic, 0, 3, d_M.data_ptr(), d_H.data_ptr(), d_avg.data_ptr(), d_none.data_ptr(), D.work.data_ptr(), bit_depth=F["bd"])
     hip_ctx.synchronize()
     M, H = d_M.cpu().numpy(), d_H.cpu().numpy()
@@ -112,6 +71,7 @@ def test_solve_matches_fixture_and_constructed(hip_ctx):
     d_M, d_H = _dev(torch, np.array([Ms[i] for i in order], np.int64)), _dev(torch, np.array([Hs[i] for i in order], np.int64))
     d_taps = torch.full((len(order), 16), -1, dtype=torch.int16, device="cuda:0")
     d_rej = torch.full((len(order),), -1, dtype=torch.int32, device="cuda:0")
+    _ready(torch)
     hip_ctx.wiener_solve_dev(d_M.data_ptr(), d_H.data_ptr(), 0, n7, 7, d_taps.data_ptr(), d_rej.data_ptr())
     hip_ctx.wiener_solve_dev(d_M.data_ptr(), d_H.data_ptr(), n7, len(order), 5, d_taps.data_ptr(), d_rej.data_ptr())
     hip_ctx.synchronize()
@@ -125,7 +85,7 @@ def test_trial_sse_matches_every_recorded_trial_of_a_unit(hip_ctx, c):
     """the unit with the most trials; the other units carry default taps or are skipped"""
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     traces = unit_traces(F)
     u = int(np.argmax(F["n_trials"]))
     p = F["plane"][u]
@@ -134,6 +94,7 @@ def test_trial_sse_matches_every_recorded_trial_of_a_unit(hip_ctx, c):
     skip[u] = 0
     d_skip = _dev(torch, skip)
     d_sse = torch.full((D.n,), -1, dtype=torch.int64, device="cuda:0")
+    _ready(torch)
     got = []
     for (t, _) in traces[u]:
         taps[u] = t
@@ -166,6 +127,7 @@ def _run_walks(torch, hip_ctx, jobs):
     d_rej = _dev(torch, np.array([jobs[i][2] for i in order], np.int32))
     d_state = torch.zeros(n * 56, dtype=torch.uint8, device="cuda:0")
     d_pending = torch.full((1,), -1, dtype=torch.int32, device="cuda:0")
+    _ready(torch)
     hip_ctx.wiener_walk_init_dev(d_state.data_ptr(), d_taps.data_ptr(), d_rej.data_ptr(), 0, n7, 7)
     hip_ctx.wiener_walk_init_dev(d_state.data_ptr(), d_taps.data_ptr(), d_rej.data_ptr(), n7, n, 5)
     asked = [[] for _ in range(n)]
@@ -232,6 +194,7 @@ def _search(torch, hip_ctx, D, F, ps, pe, n_steps):
     d_taps = torch.full((n, 16), -1, dtype=torch.int16, device="cuda:0")
     d_ntr = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
     d_pending = torch.full((1,), -1, dtype=torch.int32, device="cuda:0")
+    _ready(torch)
     args = (D.pic, ps, pe, D.work.data_ptr(), d_sse.data_ptr(), d_taps.data_ptr(), d_ntr.data_ptr(), d_pending.data_ptr())
     hip_ctx.av1_search_wiener_dev(*args, n_steps=n_steps, bit_depth=F["bd"])
     hip_ctx.synchronize()
@@ -248,7 +211,7 @@ def _search(torch, hip_ctx, D, F, ps, pe, n_steps):
 def test_search_matches_reference_and_feeds_the_filter(hip_ctx, c):
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     for n_steps in (0, 3):
         d_sse, d_taps, d_ntr, calls = _search(torch, hip_ctx, D, F, 0, 3, n_steps)
         assert np.array_equal(d_sse.cpu().numpy(), F["sse"]), (c, n_steps)
@@ -271,7 +234,7 @@ def test_frame_filter_matches_fixture(hip_ctx, c):
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
     for r in range(len(F["ftype"])):
-        D = DevCase(torch, F)
+        D = _case(torch, F)
         d_type, d_taps = _dev(torch, F["utype"][r]), _dev(torch, F["utaps"][r])
         planes = [p for p in range(3) if F["ftype"][r][p]]
         hip_ctx.av1_loop_restoration_filter_frame_dev(D.pic, D.out.ptr, D.out.stride, planes[0], planes[-1] + 1, d_type.data_ptr(), d_taps.data_ptr(),
@@ -289,7 +252,7 @@ def test_plane_subset_calls(hip_ctx):
     """a chroma-only search and a luma-only filter with null entries for the other planes"""
     torch = pytest.importorskip("torch")
     F = fixture_case(1)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     b = F["base"]
     cb = svtav1_hip.make_lr_picture(F["w"], F["h"], [None, D.cdef.ptr[1], None], D.cdef.stride, [None, D.dbk.ptr[1], None], D.dbk.stride,
                                     [None, D.src.ptr[1], None], D.src.stride)
@@ -314,7 +277,7 @@ def test_plane_subset_calls(hip_ctx):
 def test_sgrproj_unit_is_refused_on_the_device(hip_ctx):
     torch = pytest.importorskip("torch")
     F = fixture_case(1)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     types = F["utype"][0].copy()
     types[1] = svtav1_hip.RESTORE_SGRPROJ
     assert hip_ctx.inter_pred_refused() == 0
@@ -335,11 +298,12 @@ def test_refusals(hip_ctx):
     """refused on the host, before any launch: nothing is written"""
     torch = pytest.importorskip("torch")
     F = fixture_case(0)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     n = D.n
     d64 = torch.full((n * 49 * 49,), -1, dtype=torch.int64, device="cuda:0")
     d32 = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
     d16 = torch.full((n, 16), -1, dtype=torch.int16, device="cuda:0")
+    _ready(torch)
     d8 = _dev(torch, F["utype"][0])
     w, h = F["w"], F["h"]
     mk = lambda **k: svtav1_hip.make_lr_picture(k.get("w", w), k.get("h", h), k.get("cdef", D.cdef.ptr), D.cdef.stride, D.dbk.ptr,  # noqa: E731

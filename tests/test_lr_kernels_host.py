@@ -1,9 +1,9 @@
-"""CPU: the kernel bodies of svt-av1-1_amd/csrc/lr_wiener.hip compiled for the host and run against the reference's fixture
-(tests/golden/lr.npz), so that the device code's arithmetic, indexing and stripe rule are checked where there is no GPU.  The anonymous
-namespace of the file (every kernel and device function) is compiled by g++ behind a small shim: one lane per workgroup
-(SVTHIP_LR_THREADS = 1, which then does its workgroup's work in order, so a barrier is a no-op), blockIdx / threadIdx as globals, atomicAdd
-as a plain add; a driver walks the grids the launch code would launch.  Built with -fsanitize=address,undefined: an index past an LDS
-array or a plane ends the run.  What this cannot show -- lanes racing, the launch code itself -- is what tests/test_lr_gpu.py is for."""
+"""CPU: the Wiener kernels of svt-av1-1_amd/csrc/lr_wiener_kernels.h compiled for the host and run against the reference's fixture
+(tests/golden/lr.npz), so that the device code's arithmetic, indexing and stripe rule are checked where there is no GPU.
+tests/host_kernels/lr_wiener_host.cpp includes the kernel header behind tests/host_kernels/hip_on_host.h (one lane per workgroup, blockIdx /
+threadIdx as globals, atomicAdd as a plain add) and runs every kernel over the grid function the launch code calls, so a wrong grid fails
+here too.  A stand-alone program with its own main, built with -fsanitize=address,undefined: an index past an LDS array or a plane ends the
+run.  What this cannot show -- lanes racing, the launch code's arguments -- is what tests/test_lr_gpu.py is for."""
 import os
 import subprocess
 import sys
@@ -14,102 +14,14 @@ import pytest
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path[:0] = [os.path.join(ROOT, "tests")]
 
+from lr_host_util import build_host_program  # noqa: E402
 from test_lr_vs_ref import fixture_case, unit_traces  # noqa: E402
-
-SHIM = r"""
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include "svtav1_hip.h"
-#define __global__
-#define __device__
-#define __host__
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(x)
-#define __forceinline__ inline
-#define __syncthreads()
-#define SVTHIP_LR_THREADS 1
-struct dim3 { unsigned x, y, z; };
-static dim3 blockIdx = {0, 0, 0}, threadIdx = {0, 0, 0}, blockDim = {1, 1, 1};
-template <typename T, typename V> static T atomicAdd(T* p, V v) { const T o = *p; *p = (T)(o + (T)v); return o; }
-using std::max;
-using std::min;
-namespace svthip {
-@@KERNELS@@
-}  // namespace svthip
-using namespace svthip;
-
-template <typename T> static std::vector<T> rd(FILE* f, size_t n) { std::vector<T> v(n); if (n && fread(v.data(), sizeof(T), n, f) != n) abort(); return v; }
-template <typename T> static void wr(FILE* f, const std::vector<T>& v) { fwrite(v.data(), sizeof(T), v.size(), f); }
-
-template <typename T> static int run(FILE* in, FILE* out, int w, int h, int bd, const uint32_t* unit, int n_units)
-{
-    std::vector<T> cdef[3], dbk[3], src[3], res[3];
-    for (int p = 0; p < 3; p++) { const size_t n = (size_t)(w >> (p > 0)) * (h >> (p > 0)); cdef[p] = rd<T>(in, n); dbk[p] = rd<T>(in, n); src[p] = rd<T>(in, n); res[p].assign(n, 7); }
-    std::vector<int16_t> trial_taps = rd<int16_t>(in, 16 * n_units), frame_taps = rd<int16_t>(in, 16 * n_units);
-    std::vector<uint8_t> types = rd<uint8_t>(in, n_units);
-    std::vector<unsigned long long> raw((size_t)n_units * kRawStride, 0), sse(n_units, 0);
-    std::vector<int64_t> M((size_t)n_units * 49, -1), H((size_t)n_units * 2401, -1), none(n_units, -1);
-    std::vector<int32_t> avg(n_units, -1), rej(n_units, -1);
-    std::vector<int16_t> start(16 * n_units, -1);
-    uint32_t refused = 0;
-    blockDim.x = 1;
-    for (int p = 0; p < 3; p++) {
-        const PlaneGeom g = plane_geom(w, h, unit, p);
-        const int n = g.nx * g.ny, tiles = (g.unit * 3 / 2 + kStatTile - 1) / kStatTile, side = g.unit * 3 / 2, sh = 64 >> g.ss;
-        for (blockIdx.z = 0; (int)blockIdx.z < n; blockIdx.z++)
-            for (blockIdx.y = 0; (int)blockIdx.y < tiles; blockIdx.y++)
-                for (blockIdx.x = 0; (int)blockIdx.x < tiles; blockIdx.x++) lr_stats_kernel<T>(cdef[p].data(), g.w, src[p].data(), g.w, g, raw.data());
-        blockIdx.y = blockIdx.z = 0;
-        for (blockIdx.x = 0; (int)blockIdx.x < n; blockIdx.x++) lr_stats_finish_kernel(raw.data(), g, bd, M.data(), H.data(), avg.data(), none.data());
-        for (blockIdx.x = 0; (int)blockIdx.x < n; blockIdx.x++) lr_solve_kernel(M.data(), H.data(), g.base, g.base + n, g.win, start.data(), rej.data());
-        for (int wr_ = 0; wr_ < 2; wr_++)
-            for (blockIdx.z = 0; (int)blockIdx.z < n; blockIdx.z++)
-                for (blockIdx.y = 0; (int)blockIdx.y < (side + sh - 1) / sh + 1; blockIdx.y++)
-                    for (blockIdx.x = 0; (int)blockIdx.x < (side + kFiltCols - 1) / kFiltCols; blockIdx.x++) {
-                        if (wr_)
-                            lr_filter_kernel<T, true>(cdef[p].data(), g.w, dbk[p].data(), g.w, src[p].data(), g.w, res[p].data(), g.w, g, bd,
-                                                      (const uint8_t*)frame_taps.data(), 32, types.data(), 1, nullptr, &refused);
-                        else
-                            lr_filter_kernel<T, false>(cdef[p].data(), g.w, dbk[p].data(), g.w, src[p].data(), g.w, nullptr, 0, g, bd,
-                                                       (const uint8_t*)trial_taps.data(), 32, nullptr, 0, sse.data(), nullptr);
-                    }
-    }
-    wr(out, M), wr(out, H), wr(out, none), wr(out, avg), wr(out, rej), wr(out, start), wr(out, sse);
-    for (int p = 0; p < 3; p++) wr(out, res[p]);
-    return (int)refused;
-}
-
-int main(int argc, char** argv)
-{
-    FILE* in = fopen(argv[1], "rb");
-    FILE* out = fopen(argv[2], "wb");
-    int32_t hd[8];
-    if (!in || !out || fread(hd, 4, 8, in) != 8) return 2;
-    const uint32_t unit[3] = {(uint32_t)hd[3], (uint32_t)hd[4], (uint32_t)hd[5]};
-    const int refused = hd[2] > 8 ? run<uint16_t>(in, out, hd[0], hd[1], hd[2], unit, hd[6]) : run<uint8_t>(in, out, hd[0], hd[1], hd[2], unit, hd[6]);
-    fclose(out);
-    return refused ? 3 : 0;
-}
-"""
 
 
 @pytest.fixture(scope="module")
 def host_kernels(tmp_path_factory):
-    src = open(os.path.join(ROOT, "svt-av1-1_amd", "csrc", "lr_wiener.hip")).read()
-    a, b = src.index("namespace {\n"), src.index("// ---------------------------------------------------------------- host side")
     tmp = tmp_path_factory.mktemp("lr_host")
-    cpp, exe = str(tmp / "lr_host.cpp"), str(tmp / "lr_host")
-    with open(cpp, "w") as f:
-        f.write(SHIM.replace("@@KERNELS@@", src[a:b]))
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-                        "-o", exe, cpp], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe, str(tmp)
+    return build_host_program(tmp, "lr_wiener_host"), str(tmp)
 
 
 @pytest.mark.parametrize("c", (1, 2, 4, 6))

@@ -2,11 +2,8 @@
 plane (the samples of the 64x64 pictures at one set per arm, the sums of all sets of a 200x136 picture), the solve on the fixture's and on
 constructed sums (rows that a fused multiply-add would change among them), the walk on constructed error tables, the whole search with
 every record of every (unit, set), the SSE trial, and the frame filter for every recorded run and fed from a search's device-side result.
-Planes sit inside larger allocations with an odd guard of pattern samples that must come back untouched (the pattern of
-tests/test_lr_gpu.py).  Every comparison is equality.
-The context's stream does not wait for torch's: a tensor that torch fills on its own stream (torch.full, fill_, zeros) is only safe to hand
-to an entry after _ready(), or the tail of the fill can land on what the kernel has already written.  (_dev copies from pageable host
-memory and has landed when it returns.)"""
+Planes sit inside larger allocations with an odd guard of pattern samples that must come back untouched.  Every comparison is equality.
+A tensor that torch fills is handed to an entry only after _ready() (tests/lr_gpu_util.py)."""
 import os
 import sys
 
@@ -18,31 +15,14 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden
 
 import lr_sgr_util as su  # noqa: E402
 import svtav1_hip  # noqa: E402
-from test_lr_gpu import Guarded, _dev  # noqa: E402
+from lr_gpu_util import DevCase, _dev, _ready  # noqa: E402
 from test_lr_sgr_vs_ref import N_CASES, fixture, fixture_case, walk_table  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 
-def _ready(torch):
-    """torch's fills have landed: the library's stream does not order itself behind them"""
-    torch.cuda.synchronize()
-
-
-class DevCase:
-    def __init__(self, torch, F):
-        self.F, self.bd = F, F["bd"]
-        self.cdef, self.dbk, self.src = (Guarded(torch, F[k], F["bd"]) for k in ("cdef", "dbk", "src"))
-        self.out = Guarded(torch, [np.full_like(p, 7) for p in F["cdef"]], F["bd"])
-        self.pic = svtav1_hip.make_lr_picture(F["w"], F["h"], self.cdef.ptr, self.cdef.stride, self.dbk.ptr, self.dbk.stride, self.src.ptr,
-                                              self.src.stride)
-        self.n = F["base"][3]
-        self.work = torch.zeros(svtav1_hip.sgrproj_workspace_bytes(F["w"], F["h"]) // 8 + 1, dtype=torch.int64, device="cuda:0")
-        _ready(torch)
-
-    def inputs_untouched(self):
-        return all(g.planes()[1] and all(np.array_equal(a, b) for a, b in zip(g.planes()[0], self.F[k]))
-                   for g, k in ((self.cdef, "cdef"), (self.dbk, "dbk"), (self.src, "src")))
+def _case(torch, F):
+    return DevCase(torch, F, svtav1_hip.sgrproj_workspace_bytes(F["w"], F["h"]))
 
 
 def _plane_flt(torch, hip_ctx, D, p, ep):
@@ -67,7 +47,7 @@ def _plane_flt(torch, hip_ctx, D, p, ep):
 def test_plane_entry_matches_the_samples_of_three_sets(hip_ctx, c):
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     for e, ep in enumerate(int(v) for v in fixture()["dump_ep"]):
         for p in range(3):
             at = sum(F["cdef"][q].size for q in range(p))
@@ -83,7 +63,7 @@ def test_plane_entry_matches_the_samples_of_three_sets(hip_ctx, c):
 def test_plane_entry_matches_the_sums_of_every_set(hip_ctx, c):
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     for p in range(3):
         for ep in range(16):
             got = _plane_flt(torch, hip_ctx, D, p, ep)
@@ -150,7 +130,7 @@ def _search(torch, hip_ctx, D, ps, pe, pic=None, detail=True):
 def test_search_matches_fixture_with_every_record(hip_ctx, c):
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     d_sgr, d_sse, d_det = _search(torch, hip_ctx, D, 0, 3)
     hip_ctx.synchronize()
     det = d_det.cpu().numpy().view(svtav1_hip.SGRPROJ_DETAIL_DTYPE).reshape(D.n, 16)
@@ -172,7 +152,7 @@ def test_search_matches_fixture_with_every_record(hip_ctx, c):
 def test_chroma_only_search_with_null_luma(hip_ctx):
     torch = pytest.importorskip("torch")
     F = fixture_case(4)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     b = F["base"]
     cb = svtav1_hip.make_lr_picture(F["w"], F["h"], [None, D.cdef.ptr[1], None], D.cdef.stride, [None, D.dbk.ptr[1], None], D.dbk.stride,
                                     [None, D.src.ptr[1], None], D.src.stride)
@@ -196,7 +176,7 @@ def test_trial_sse_matches_fixture(hip_ctx, c):
     """the SSE of the search's filter; with a skip mask; of the filters of the other runs against the restatement"""
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     d_sgr = _dev(torch, F["sgrproj"])
     d_sse = torch.full((D.n,), -1, dtype=torch.int64, device="cuda:0")
     _ready(torch)
@@ -232,7 +212,7 @@ def test_frame_filter_matches_every_run(hip_ctx, c):
     torch = pytest.importorskip("torch")
     F = fixture_case(c)
     for r in range(len(F["ftype"])):
-        D = DevCase(torch, F)
+        D = _case(torch, F)
         ps = 0 if F["ftype"][r][0] else 1
         d_type, d_taps, d_sgr = _dev(torch, F["utype"][r]), _dev(torch, F["utaps"][r]), _dev(torch, F["usgr"][r])
         _ready(torch)
@@ -251,7 +231,7 @@ def test_bad_parameters_are_refused_on_the_device(hip_ctx, bad):
     """a set above 15 or an xqd outside its range: counted once, nothing of the unit written, the other units as the fixture has them"""
     torch = pytest.importorskip("torch")
     F = fixture_case(1)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     sgr = F["usgr"][0].copy()
     sgr[1] = bad
     assert hip_ctx.inter_pred_refused() == 0
@@ -282,7 +262,7 @@ def test_missing_taps_or_parameters_are_refused_on_the_device(hip_ctx):
     F = fixture_case(1)
     types = F["utype"][1]
     for missing, kind in (("taps", svtav1_hip.RESTORE_WIENER), ("sgr", svtav1_hip.RESTORE_SGRPROJ)):
-        D = DevCase(torch, F)
+        D = _case(torch, F)
         d_type, d_taps, d_sgr = _dev(torch, types), _dev(torch, F["utaps"][1]), _dev(torch, F["usgr"][1])
         _ready(torch)
         hip_ctx.av1_lr_filter_frame_dev(D.pic, D.out.ptr, D.out.stride, 0, 3, d_type.data_ptr(), None if missing == "taps" else d_taps.data_ptr(),
@@ -307,7 +287,7 @@ def test_refusals(hip_ctx):
     """refused on the host, before any launch: nothing is written"""
     torch = pytest.importorskip("torch")
     F = fixture_case(0)
-    D = DevCase(torch, F)
+    D = _case(torch, F)
     n = D.n
     d64 = torch.full((n * 16 * 10 + 8,), -1, dtype=torch.int64, device="cuda:0")
     d32 = torch.full((64 * 80,), -1, dtype=torch.int32, device="cuda:0")

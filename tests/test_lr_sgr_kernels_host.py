@@ -1,9 +1,10 @@
-"""CPU: the self-guided kernel bodies of svt-av1-1_amd/csrc/lr_wiener.hip compiled for the host behind the shim of
-tests/test_lr_kernels_host.py (one lane per workgroup, blockIdx / threadIdx as globals, atomicAdd as a plain add) and run against the
-reference's fixture (tests/golden/lr_sgr.npz): the box filter over the planes, the whole search with its records, the SSE trial and the
-frame filter of the mixed run, and the solve on the constructed sums.  A stand-alone program with its own main, built with
--fsanitize=address,undefined: an index past an LDS array, a plane or the workspace ends the run.  What this cannot show -- lanes racing,
-the launch code, the device's floating point -- is what tests/test_lr_sgr_gpu.py is for."""
+"""CPU: the self-guided kernels of svt-av1-1_amd/csrc/lr_sgrproj_kernels.h compiled for the host and run against the reference's fixture
+(tests/golden/lr_sgr.npz): the box filter over the planes, the whole search with its records, the SSE trial and the frame filter of the
+mixed run, and the solve on the constructed sums.  tests/host_kernels/lr_sgrproj_host.cpp includes the kernel headers behind
+tests/host_kernels/hip_on_host.h (one lane per workgroup, blockIdx / threadIdx as globals, atomicAdd as a plain add) and runs every kernel
+over the grid function the launch code calls.  A stand-alone program with its own main, built with -fsanitize=address,undefined: an index
+past an LDS array, a plane or the workspace ends the run.  What this cannot show -- lanes racing, the launch code's arguments, the device's
+floating point -- is what tests/test_lr_sgr_gpu.py is for."""
 import os
 import subprocess
 import sys
@@ -15,129 +16,14 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path[:0] = [os.path.join(ROOT, "tests")]
 
 import lr_sgr_util as su  # noqa: E402
-from test_lr_kernels_host import SHIM  # noqa: E402
+from lr_host_util import build_host_program  # noqa: E402
 from test_lr_sgr_vs_ref import N_CASES, fixture, fixture_case  # noqa: E402
-
-DRIVER = r"""
-template <typename T> static std::vector<T> rd(FILE* f, size_t n) { std::vector<T> v(n); if (n && fread(v.data(), sizeof(T), n, f) != n) abort(); return v; }
-template <typename T> static void wr(FILE* f, const std::vector<T>& v) { fwrite(v.data(), sizeof(T), v.size(), f); }
-
-template <typename T> static int run(FILE* in, FILE* out, int w, int h, int bd, const uint32_t* unit, int n_units)
-{
-    std::vector<T> cdef[3], dbk[3], src[3], res[3];
-    for (int p = 0; p < 3; p++) { const size_t n = (size_t)(w >> (p > 0)) * (h >> (p > 0)); cdef[p] = rd<T>(in, n); dbk[p] = rd<T>(in, n); src[p] = rd<T>(in, n); res[p].assign(n, 7); }
-    std::vector<int16_t> taps = rd<int16_t>(in, 16 * n_units);
-    std::vector<uint8_t> types = rd<uint8_t>(in, n_units);
-    std::vector<int32_t> usgr = rd<int32_t>(in, 4 * n_units);
-    const size_t jobs = (size_t)n_units * kSgrParams;
-    std::vector<int64_t> sums(jobs * 5, -1), err(jobs, -1), fsums(3 * 16 * 4, 0);
-    std::vector<int32_t> size(jobs, -1), ep(jobs, -1), ntr(jobs, -1), xq(jobs * 2, -1), start(jobs * 2, -1), fin(jobs * 2, -1), sgrproj(4 * n_units, -1);
-    std::vector<svthip_sgrproj_detail> detail(jobs);
-    std::vector<unsigned long long> sse(n_units, 0);
-    std::vector<int32_t> dump;
-    uint32_t refused = 0;
-    blockDim.x = 1;
-    for (int p = 0; p < 3; p++) {
-        const PlaneGeom g = plane_geom(w, h, unit, p);
-        const int n = g.nx * g.ny, side = g.unit * 3 / 2, pu = 64 >> g.ss, gx = (side + pu - 1) / pu, gy = (side + kSgrTileH - 1) / kSgrTileH;
-        const size_t plane = (size_t)g.w * g.h;
-        // the plane entry, every set: sums of flt and flt^2; the samples minus u for sets 0, 12, 15
-        for (int e = 0; e < kSgrParams; e++) {
-            std::vector<int32_t> f0(plane, -7), f1(plane, -7);
-            for (blockIdx.z = 0; (int)blockIdx.z < n; blockIdx.z++)
-                for (blockIdx.y = 0; (int)blockIdx.y < gy; blockIdx.y++)
-                    for (blockIdx.x = 0; (int)blockIdx.x < gx; blockIdx.x++)
-                        sgr_box_kernel<T, false>(cdef[p].data(), g.w, (const T*)nullptr, 0, g, bd, e, e + 1, f0.data(), f1.data(), g.w, nullptr, nullptr);
-            for (size_t i = 0; i < plane; i++) {
-                if (sgr_r(e, 0)) fsums[(p * 16 + e) * 4] += f0[i], fsums[(p * 16 + e) * 4 + 1] += (int64_t)f0[i] * f0[i]; else if (f0[i] != -7) abort();
-                if (sgr_r(e, 1)) fsums[(p * 16 + e) * 4 + 2] += f1[i], fsums[(p * 16 + e) * 4 + 3] += (int64_t)f1[i] * f1[i]; else if (f1[i] != -7) abort();
-            }
-            if (e == 0 || e == 12 || e == 15)
-                for (int k = 0; k < 2; k++)
-                    for (size_t i = 0; i < plane; i++) dump.push_back(sgr_r(e, k) ? (k ? f1 : f0)[i] - ((int32_t)cdef[p][i] << 4) : 0);
-        }
-        // the search
-        std::vector<int16_t> f16(plane * kSgrParams * 2, 0x7777);
-        blockIdx.y = blockIdx.z = 0;
-        for (blockIdx.x = 0; (int)blockIdx.x < n * kSgrParams; blockIdx.x++) sgr_search_init_kernel(g, sums.data(), size.data(), ep.data());
-        for (blockIdx.z = 0; (int)blockIdx.z < n; blockIdx.z++)
-            for (blockIdx.y = 0; (int)blockIdx.y < gy; blockIdx.y++)
-                for (blockIdx.x = 0; (int)blockIdx.x < gx; blockIdx.x++)
-                    sgr_box_kernel<T, true>(cdef[p].data(), g.w, src[p].data(), g.w, g, bd, 0, kSgrParams, nullptr, nullptr, 0, f16.data(),
-                                            (unsigned long long*)sums.data());
-        const size_t j0 = (size_t)g.base * kSgrParams;
-        blockIdx.y = blockIdx.z = 0;
-        for (blockIdx.x = 0; (int)blockIdx.x < n * kSgrParams; blockIdx.x++)
-            sgr_solve_kernel(sums.data() + j0 * 5, size.data() + j0, ep.data() + j0, n * kSgrParams, xq.data() + j0 * 2, start.data() + j0 * 2);
-        for (blockIdx.y = 0; (int)blockIdx.y < n; blockIdx.y++)
-            for (blockIdx.x = 0; (int)blockIdx.x < kSgrParams; blockIdx.x++)
-                sgr_walk_kernel<T>(cdef[p].data(), g.w, src[p].data(), g.w, g, f16.data(), start.data(), fin.data(), err.data(), ntr.data());
-        blockIdx.y = 0;
-        for (blockIdx.x = 0; (int)blockIdx.x < n; blockIdx.x++)
-            sgr_pick_kernel(sums.data(), xq.data(), start.data(), fin.data(), err.data(), ntr.data(), g.base, g.base + n, sgrproj.data(), detail.data());
-        // the SSE of the search's filter, then the frame filter with the run's types
-        const int sh = 64 >> g.ss, fy = ((side + sh - 1) / sh + 1) * (sh / kSgrTileH);
-        for (int wr_ = 0; wr_ < 2; wr_++)
-            for (blockIdx.z = 0; (int)blockIdx.z < n; blockIdx.z++)
-                for (blockIdx.y = 0; (int)blockIdx.y < fy; blockIdx.y++)
-                    for (blockIdx.x = 0; (int)blockIdx.x < gx; blockIdx.x++) {
-                        if (wr_)
-                            sgr_filter_kernel<T, true>(cdef[p].data(), g.w, dbk[p].data(), g.w, (const T*)nullptr, 0, res[p].data(), g.w, g, bd, usgr.data(),
-                                                       types.data(), nullptr, &refused);
-                        else
-                            sgr_filter_kernel<T, false>(cdef[p].data(), g.w, dbk[p].data(), g.w, src[p].data(), g.w, nullptr, 0, g, bd, sgrproj.data(),
-                                                        nullptr, sse.data(), nullptr);
-                    }
-        for (blockIdx.z = 0; (int)blockIdx.z < n; blockIdx.z++)
-            for (blockIdx.y = 0; (int)blockIdx.y < (side + sh - 1) / sh + 1; blockIdx.y++)
-                for (blockIdx.x = 0; (int)blockIdx.x < (side + kFiltCols - 1) / kFiltCols; blockIdx.x++)
-                    lr_filter_kernel<T, true>(cdef[p].data(), g.w, dbk[p].data(), g.w, (const T*)nullptr, 0, res[p].data(), g.w, g, bd,
-                                              (const uint8_t*)taps.data(), 32, types.data(), 1, nullptr, &refused, 1);
-    }
-    wr(out, fsums), wr(out, dump);
-    fwrite(detail.data(), sizeof(svthip_sgrproj_detail), detail.size(), out);
-    wr(out, sgrproj), wr(out, sse);
-    for (int p = 0; p < 3; p++) wr(out, res[p]);
-    return (int)refused;
-}
-
-int main(int argc, char** argv)
-{
-    FILE* in = fopen(argv[1], "rb");
-    FILE* out = fopen(argv[2], "wb");
-    int32_t hd[8];
-    if (argc < 3 || !in || !out || fread(hd, 4, 8, in) != 8) return 2;
-    int refused = 0;
-    if (hd[7]) {   // the solve alone: hd[6] jobs
-        const int n = hd[6];
-        std::vector<int64_t> sums = rd<int64_t>(in, 5 * n);
-        std::vector<int32_t> size = rd<int32_t>(in, n), ep = rd<int32_t>(in, n), xq(2 * n, -1), xqd(2 * n, -1);
-        blockDim.x = 1;
-        for (blockIdx.x = 0; (int)blockIdx.x < n; blockIdx.x++) sgr_solve_kernel(sums.data(), size.data(), ep.data(), n, xq.data(), xqd.data());
-        wr(out, xq), wr(out, xqd);
-    } else {
-        const uint32_t unit[3] = {(uint32_t)hd[3], (uint32_t)hd[4], (uint32_t)hd[5]};
-        refused = hd[2] > 8 ? run<uint16_t>(in, out, hd[0], hd[1], hd[2], unit, hd[6]) : run<uint8_t>(in, out, hd[0], hd[1], hd[2], unit, hd[6]);
-    }
-    fclose(out);
-    return refused ? 3 : 0;
-}
-"""
 
 
 @pytest.fixture(scope="module")
 def host_kernels(tmp_path_factory):
-    src = open(os.path.join(ROOT, "svt-av1-1_amd", "csrc", "lr_wiener.hip")).read()
-    a, b = src.index("namespace {\n"), src.index("// ---------------------------------------------------------------- host side")
-    shim = SHIM[:SHIM.index("template <typename T> static std::vector<T> rd")]     # the shim without the Wiener test's driver
     tmp = tmp_path_factory.mktemp("lr_sgr_host")
-    cpp, exe = str(tmp / "lr_sgr_host.cpp"), str(tmp / "lr_sgr_host")
-    with open(cpp, "w") as f:
-        f.write(shim.replace("@@KERNELS@@", src[a:b]) + DRIVER)
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-                        "-o", exe, cpp], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe, str(tmp)
+    return build_host_program(tmp, "lr_sgrproj_host"), str(tmp)
 
 
 @pytest.mark.parametrize("c", (0, 2, 4, 7))
