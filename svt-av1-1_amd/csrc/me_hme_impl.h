@@ -186,9 +186,47 @@ __device__ void wave_sad_loop_generic(const uint8_t* src, uint32_t src_stride, c
 // Copies `wrows` plane rows of `pitch` dwords each, starting at the (unaligned) address `base`, into LDS (row r at win + r * pitch).
 // Reads up to pitch * 4 + 19 bytes per row (the pool's tail slack covers the last row of the last plane).  pitch <= 256 (a band of at
 // least 15 rows has to fit the 7 KB slice, so pitch <= 119 here).
+// QUAD: the caller guarantees a pitch that is a multiple of four dwords and a 16-byte aligned `win`, so a lane's four dwords are all
+// inside the row or all outside it and go to LDS as ONE 16-byte store.  `base` is wave-uniform and the window lies inside one plane of a
+// pool below 2^31 bytes (checked at the entry), so the row address is base (scalar) + a 32-bit per-lane offset that is stepped from row
+// piece to row piece: no 64-bit multiply-add per load, no multiplication at all.  The clamp of the surplus rows is taken on the offset
+// (offsets grow with the row).
+template <bool QUAD = false>
 __device__ __forceinline__ void stage_window_rows(const uint8_t* base, uint32_t ref_stride_raw, int wrows, int pitch, uint32_t* win,
                                                   int lane)
 {
+    if constexpr (QUAD) {
+        constexpr int NP = 6;
+        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+        typedef const __attribute__((address_space(1))) uint8_t gmem_u8;
+        const int lpr = pitch >> 2;
+        const int rpp = lpr < 64 ? 64 / lpr : 1;
+        const int g = (int)(((uint32_t)lane * ((1u << 16) / (uint32_t)lpr + 1u)) >> 16), q4 = 4 * (lane - g * lpr);
+        const bool lane_ok = g < rpp;
+        gmem_u8* b = (gmem_u8*)base;
+        const uint32_t step = (uint32_t)rpp * ref_stride_raw;
+        const uint32_t last = (uint32_t)(wrows - 1) * ref_stride_raw + 4u * (uint32_t)q4;  // this lane's piece of the last row
+        uint32_t off = (uint32_t)g * ref_stride_raw + 4u * (uint32_t)q4;
+        uint32_t* o = win + g * pitch + q4;
+        for (int r0 = g; r0 < wrows; r0 += NP * rpp) {
+            gmem_u32x4 w[NP];
+#pragma unroll
+            for (int u = 0; u < NP; u++) {
+                const __attribute__((address_space(1))) gmem_u32x4* q =
+                    (const __attribute__((address_space(1))) gmem_u32x4*)(b + min(off + (uint32_t)u * step, last));
+#pragma unroll
+                for (int k = 0; k < 4; k++) w[u].v[k] = q->v[k];
+            }
+            asm volatile("" ::: "memory");  // all six loads are issued before the first store waits for one
+#pragma unroll
+            for (int u = 0; u < NP; u++)
+                if (lane_ok && r0 < wrows - u * rpp)
+                    *reinterpret_cast<u32x4_t*>(o + u * rpp * pitch) = u32x4_t{w[u].v[0], w[u].v[1], w[u].v[2], w[u].v[3]};
+            off += NP * step;
+            o += NP * rpp * pitch;
+        }
+        return;
+    }
     // A lane moves FOUR consecutive dwords of a row: one 16-byte global load at the row's own byte alignment (no alignment needed on
     // this target; round 2 used five aligned dwords + four v_alignbyte) and four LDS stores.  lpr lanes per row, rpp rows per wave
     // pass, NP passes in flight: the level-1 / level-2 windows (46 / 70 rows) are then ONE round trip to memory instead of two / three
@@ -399,7 +437,7 @@ __device__ void wave_sad_loop_fixed(const uint8_t* ref, uint32_t ref_stride_raw,
 
     uint32_t* win = reinterpret_cast<uint32_t*>(lds);
     HME_PRIO(3);
-    stage_window_rows(ref, ref_stride_raw, WROWS, PITCH, win, lane);
+    stage_window_rows<true>(ref, ref_stride_raw, WROWS, PITCH, win, lane);
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     HME_PRIO(0);
@@ -477,6 +515,114 @@ __device__ void wave_sad_loop_fixed(const uint8_t* ref, uint32_t ref_stride_raw,
     *bx = (int)(pos % (uint32_t)SW);
 }
 
+// One block row of a level-0 item: window dwords wr[0..7] (two ds_read_b128) against the four source dwords of the row, 16 v_qsad.
+// The odd window pairs (1,2) (3,4) (5,6) are assembled in registers.  Reading them a second time from LDS as aligned pairs, as
+// wave_sad_loop_fixed does, was measured and is slower here: at this loop's 16-byte lane stride every ds_read2_b32 is a four-way bank
+// conflict.
+__device__ __forceinline__ void l0_row_sads(const uint32_t* wr, const uint32_t* sr, uint64_t* acc)
+{
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    const u32x4_t da = *reinterpret_cast<const u32x4_t*>(wr);
+    const u32x4_t db = *reinterpret_cast<const u32x4_t*>(wr + 4);
+    const uint4 sv = *reinterpret_cast<const uint4*>(sr);
+    const uint32_t d[8] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w};
+    const uint32_t s4[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int g = 0; g < 4; g++) acc[g] = __builtin_amdgcn_qsad_pk_u16_u8(pack64(d[c + g], d[c + g + 1]), s4[c], acc[g]);
+}
+
+// Minimum of the 16 keys (sad << 16 | j), j = 0..15, of an item whose 16 positions are all valid: one v_lshl_or / v_and_or with an
+// inline constant per key, one v_min3 per two keys.
+__device__ __forceinline__ uint32_t l0_item_min(const uint64_t* acc)
+{
+    uint32_t lb = 0xffffffffu;
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const uint32_t lo = (uint32_t)acc[g], hi = (uint32_t)(acc[g] >> 32);
+        lb = min3u((lo << 16) | (uint32_t)(4 * g), (lo & 0xffff0000u) | (uint32_t)(4 * g + 1), lb);
+        lb = min3u((hi << 16) | (uint32_t)(4 * g + 2), (hi & 0xffff0000u) | (uint32_t)(4 * g + 3), lb);
+    }
+    return lb;
+}
+
+// Level 0 of a full SB whose clipped search width is a multiple of 16 (sw = 16 * nit) and whose whole window fits the slice in one
+// band (the reference's 100 % and 200 % areas): wave_sad_loop_l0's items, passes and remainder, with what that shape makes constant.
+//   * Item i of the raster of items is search row iy = i / nit, column item io = i % nit; its raster base iy * sw + 16 * io is 16 * i
+//     and its window address (iy * pitch + 4 * io dwords, pitch = 4 * nit + 4) is 16 * (i + iy) bytes.  A lane computes (iy, io)
+//     once and steps them from pass to pass: i + 64 is io + 64 % nit with a carry into iy.  No multiplication in the main loop.
+//   * The 16 keys of an item are relative (l0_item_min); the base 16 * i is added once to the item's minimum.  It is a multiple of
+//     16 and j < 16, so the sum cannot carry into the SAD field: the key stays sad << 16 | raster index, the strict-'<' raster rule.
+//   * The window is staged with one 16-byte LDS store per load (stage_window_rows<true>).
+// `srcbuf` is the block staged by the workgroup ([8][4] dwords); `lds` (16-byte aligned) holds the window; nit * sh * 16 <= 65536.
+__device__ void wave_sad_loop_l0_oneband(const uint8_t* ref, uint32_t ref_stride_raw, int nit, int sh, int lane, uint8_t* lds,
+                                         const uint32_t* srcbuf, uint32_t* best_sad, int* bx, int* by)
+{
+    constexpr int H = 8, WD = 4;
+    const int pitch = 4 * nit + 4;
+    const uint32_t* win = reinterpret_cast<const uint32_t*>(lds);
+    HME_PRIO(3);
+    stage_window_rows<true>(ref, ref_stride_raw, sh + 2 * H - 2, pitch, reinterpret_cast<uint32_t*>(lds), lane);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    HME_PRIO(0);
+
+    const int nitems = nit * sh;
+    const uint32_t inv_nit = (1u << 20) / (uint32_t)nit + 1u;
+    const uint32_t qs = (64u * inv_nit) >> 20, rs = 64u - qs * (uint32_t)nit;  // 64 = qs * nit + rs (scalar)
+    uint32_t best = 0xffffffffu;
+    uint32_t item = (uint32_t)lane;
+    uint32_t iy = (item * inv_nit) >> 20, io = item - iy * (uint32_t)nit;
+    int it0 = 0;
+    // whole passes: a lane owns an item (all 8 block rows, 128 v_qsad); lanes past the last item read item 0 and never win
+    for (; nitems - it0 >= 57; it0 += 64) {
+        const bool valid = item < (uint32_t)nitems;
+        const uint32_t* w0 = win + (valid ? 4u * (item + iy) : 0u);
+        uint64_t acc[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int r = 0; r < H; r++) l0_row_sads(w0 + 2 * r * pitch, srcbuf + r * WD, acc);
+        const uint32_t key = l0_item_min(acc) + 16u * item;
+        best = min(best, valid ? key : 0xffffffffu);
+        item += 64;
+        io += rs;
+        const bool carry = io >= (uint32_t)nit;
+        io -= carry ? (uint32_t)nit : 0u;
+        iy += qs + (carry ? 1u : 0u);
+    }
+    // the remainder, as in wave_sad_loop_l0: 2 / 4 / 8 lanes share an item and split its block rows; the 16-bit partial sums of an
+    // item's lanes are added as packed pairs.  At most two rounds per wave: their (iy) comes from one multiplication each.
+    while (it0 < nitems) {
+        const int rem = nitems - it0;
+        const int rp_shift = rem > 16 ? 1 : rem > 8 ? 2 : 3;
+        const int RP = 1 << rp_shift, take = min(rem, 64 >> rp_shift);
+        const int slot = lane >> rp_shift, part = lane & (RP - 1);
+        const uint32_t ri = (uint32_t)(it0 + min(slot, take - 1));
+        const uint32_t* w0 = win + 4u * (ri + ((ri * inv_nit) >> 20));
+        uint64_t acc[4] = {0, 0, 0, 0};
+        for (int r = part; r < H; r += RP) l0_row_sads(w0 + 2 * r * pitch, srcbuf + r * WD, acc);
+        for (int m = 1; m < RP; m <<= 1) {
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const uint32_t lo = (uint32_t)acc[g] + (uint32_t)__shfl_xor((int)(uint32_t)acc[g], m);
+                const uint32_t hi = (uint32_t)(acc[g] >> 32) + (uint32_t)__shfl_xor((int)(uint32_t)(acc[g] >> 32), m);
+                acc[g] = pack64(lo, hi);
+            }
+        }
+        const uint32_t key = l0_item_min(acc) + 16u * ri;
+        best = min(best, (slot < take && part == 0) ? key : 0xffffffffu);
+        it0 += take;
+    }
+    __builtin_amdgcn_wave_barrier();  // the next level's staging overwrites the window
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, m));
+    best = (uint32_t)__builtin_amdgcn_readfirstlane((int)best);  // wave-uniform: scalar from here on
+    const uint32_t pos = best & 0xffffu, sw = 16u * (uint32_t)nit;
+    *best_sad = best >> 16;
+    *by = (int)(pos / sw);
+    *bx = (int)(pos - (uint32_t)(*by) * sw);
+}
+
 // SadLoopKernel of HME level 0 (16 x 8-row block on the 1/16 plane; ~70 % of the search-centre work), one wave.
 // An item is 16 consecutive search positions of one search row = 16 bytes = one ds_read_b128 step along the window, so lane
 // i of a row reads window dwords 4i .. 4i+7 with two conflict-free b128 loads per block row and issues 16 v_qsad_pk_u16_u8
@@ -498,6 +644,10 @@ __device__ void wave_sad_loop_l0(const uint8_t* src, uint32_t src_stride, const 
     if (band > sh) band = sh;
     if (band < 1 || sw * sh > 65536) {
         wave_sad_loop_lds<16>(src, src_stride, ref, ref_stride_raw, H, sw, sh, lane, lds, lds_bytes, best_sad, bx, by, shared_src);
+        return;
+    }
+    if (shared_src && (sw & 15) == 0 && band == sh) {  // wave-uniform; every other shape keeps the loops below
+        wave_sad_loop_l0_oneband(ref, ref_stride_raw, nit, sh, lane, lds, shared_src, best_sad, bx, by);
         return;
     }
     if (!shared_src && lane < H * WD)
