@@ -890,15 +890,95 @@ int32_t svthip_av1_highbd_pick_filter_level_dev(svthip_ctx *ctx, const svthip_lf
                                                 uint64_t *d_visited, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * CDEF, the stage between deblocking and loop restoration (Codec/EbCdef.c, EbCdefProcess.c): the strength search over all filter
+ * blocks, the strength pick and the frame filter.  CDEF_M = 1, fast = 0, 4:2:0, 64x64 superblocks, three planes, one tile, 8 and 10 bits.
+ * Every result is the reference's C form bit for bit, the double-precision luma distortion included.
+ * NOT covered, and staying on the host or unsupported: 128x128 superblocks, the `fast` search, 12 bits, 4:2:2 / 4:4:0, more than one tile.
+ *
+ *   filter block (fb)      64x64 luma samples; nhfb = (width / 4 + 15) / 16, nvfb likewise, nfb = nhfb * nvfb, raster order.
+ *   svthip_cdef_picture    device pointers to sample (0, 0) of the deblocked planes (read only), the source planes (search entries) and the
+ *                          output planes (frame entries), strides in samples, the luma size (multiples of 8), and d_skip: one byte per
+ *                          4x4 luma cell, non-zero meaning mbmi->skip, height / 4 rows of skip_stride >= width / 4 bytes.  No plane needs a
+ *                          border: what lies outside the picture is CDEF_VERY_LARGE, and every other sample a filter reads is a deblocked one.
+ *   svthip_cdef_result     what finish_cdef_search leaves in the picture parent control set, in DEVICE memory, so that the pick feeds the
+ *                          frame filter without a host round trip: cdef_bits, nb_cdef_strengths, cdef_strengths[8], cdef_uv_strengths[8]
+ *                          (index = pri * 4 + sec_idx; entries past nb_cdef_strengths are 0), pri_damping, sec_damping, sb_count.
+ *   d_fb_strength          int8 [nfb]: the picked index per fb (mbmi.cdef_strength of its first cell), -1 for an fb the search left out.
+ *
+ * svthip_av1_[highbd_]cdef_search_mse_dev   cdef_seg_search[16bit] (EbCdefProcess.c:89-248, :249-410) over all fbs, with cdef_filter_fb,
+ *     cdef_find_dir_c, cdef_filter_block_c, adjust_strength (EbCdef.c:103-357), sb_all_skip, sb_compute_cdef_list (:359-428), dist_8x8_16bit_c,
+ *     mse_4x4_16bit_c and compute_cdef_dist (:1321-1425): d_mse[2][nfb][64] uint64 = mse_seg[0] (luma) and mse_seg[1] (Cb + Cr),
+ *     d_fb_counted[nfb] = 1 where sb_all_skip is false.  Entries of fbs left out are written as 0.  The chroma sum of squares is the plain
+ *     one of mse_4x4_16bit_c (the reference's AVX2 form adds in 16-bit lanes and wraps).
+ * svthip_cdef_pick_strengths_dev   finish_cdef_search (EbCdef.c:1427-1589) with search_one_dual_c and joint_strength_search_dual
+ *     (:1196-1293) on the two tables: the counted fbs compacted, the four joint searches, both lambda terms in double, the per-fb pick.
+ *     lambda = .12 * q * q / 256 with q = av1_ac_quant_Q3(base_qindex, 0, bit_depth) >> (bit_depth - 8) is computed on the host side of the
+ *     entry.  Ties go to the first (j, k) pair in row-major order and to the smallest number of bits, as the reference's strict <.
+ *     nfb is at most SVTHIP_CDEF_PICK_MAX_FB (16384 x 16384 luma samples are 65536 fbs: pictures above 4096 fbs pick on the host).
+ * svthip_av1_[highbd_]cdef_search_dev   the two above on one stream with no host synchronisation; d_mse and d_fb_counted are workspace
+ *     that keeps the tables.
+ * svthip_av1_[highbd_]cdef_frame_dev   av1_cdef_frame[16bit] (EbCdef.c:470-808 and its twin) for planes [plane_start, plane_end), out of
+ *     place from the deblocked planes into picture->out: an fb whose pair is (0, 0) for luma and chroma or whose list is empty, and every
+ *     unlisted 8x8 block, is copied; every sample of the output planes is written.  Strengths, dampings and per-fb indices are read from
+ *     device memory.  The output planes are what svthip_lr_picture.cdef[] takes.
+ * svthip_cdef_dist_8x8_batch_dev   dist_8x8_16bit_c (:1321-1347) on n pairs of contiguous 8x8 16-bit blocks with the search kernel's own
+ *     device function: d_out[n] uint64.  It exists so that the one floating-point expression can be tested on its own.
+ * Refused with svthip_last_error text and without a launch: a null pointer (frame entries: of the deblocked luma plane and of the
+ * deblocked and output planes in range only; they never look at the source planes), a width or height that is 0 or no multiple of 8, a stride
+ * smaller than its plane (skip_stride < width / 4), an output plane that overlaps a deblocked plane, base_qindex > 255, a bit depth
+ * other than 10 for the highbd entries (8 or 10 for the pick), 16-bit planes not 2-byte aligned, 64-bit tables not 8-byte and d_result not
+ * 4-byte aligned, plane_start > plane_end or plane_end > 3, coeff_shift > 2, nfb of the pick 0 or above SVTHIP_CDEF_PICK_MAX_FB. */
+#define SVTHIP_CDEF_STRENGTHS 64
+#define SVTHIP_CDEF_PICK_MAX_FB 4096
+
+typedef struct svthip_cdef_picture {
+    const void *deblocked[3];
+    const void *source[3];
+    void *out[3];
+    uint32_t deblocked_stride[3], source_stride[3], out_stride[3];
+    uint32_t width, height;
+    const uint8_t *d_skip;
+    uint32_t skip_stride;
+} svthip_cdef_picture;
+
+typedef struct svthip_cdef_result {
+    int32_t cdef_bits, nb_cdef_strengths;
+    int32_t cdef_strengths[8], cdef_uv_strengths[8];
+    int32_t pri_damping, sec_damping;
+    int32_t sb_count;
+} svthip_cdef_result;
+
+int32_t svthip_av1_cdef_search_mse_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint64_t *d_mse,
+                                       uint8_t *d_fb_counted, void *stream);
+int32_t svthip_av1_highbd_cdef_search_mse_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint32_t bit_depth,
+                                              uint64_t *d_mse, uint8_t *d_fb_counted, void *stream);
+int32_t svthip_cdef_pick_strengths_dev(svthip_ctx *ctx, const uint64_t *d_mse, const uint8_t *d_fb_counted, uint32_t nhfb, uint32_t nvfb,
+                                       uint32_t base_qindex, uint32_t bit_depth, svthip_cdef_result *d_result, int8_t *d_fb_strength,
+                                       void *stream);
+int32_t svthip_av1_cdef_search_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint64_t *d_mse,
+                                   uint8_t *d_fb_counted, svthip_cdef_result *d_result, int8_t *d_fb_strength, void *stream);
+int32_t svthip_av1_highbd_cdef_search_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint32_t bit_depth,
+                                          uint64_t *d_mse, uint8_t *d_fb_counted, svthip_cdef_result *d_result, int8_t *d_fb_strength,
+                                          void *stream);
+int32_t svthip_av1_cdef_frame_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, const svthip_cdef_result *d_result,
+                                  const int8_t *d_fb_strength, uint32_t plane_start, uint32_t plane_end, void *stream);
+int32_t svthip_av1_highbd_cdef_frame_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, const svthip_cdef_result *d_result,
+                                         const int8_t *d_fb_strength, uint32_t plane_start, uint32_t plane_end, uint32_t bit_depth,
+                                         void *stream);
+int32_t svthip_cdef_dist_8x8_batch_dev(svthip_ctx *ctx, const uint16_t *d_dst, const uint16_t *d_src, uint32_t n, uint32_t coeff_shift,
+                                       uint64_t *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Wiener loop restoration (Codec/EbRestorationPick.c, EbRestoration.c, convolve.c): the Wiener arm of restoration_seg_search
  * (search_norestore_seg :1884-1896, search_wiener_seg :1742-1824) and av1_loop_restoration_filter_frame (EbRestoration.c:1283-1341) for
  * units of type RESTORE_NONE and RESTORE_WIENER, 8 and 10 bits, one tile (the reference's whole_frame_rect), no superres.  Every step is
  * integer arithmetic, the solve included, and every result is the reference's bit for bit.
  * NOT covered, and staying on the host: rest_finish_search (bit counts and the double-precision RD decisions, which consume what these
- * entries produce), CDEF, 12-bit video (get_conv_params_wiener changes round_0 there).  Self-guided restoration (search_sgrproj_seg,
+ * entries produce), 12-bit video (get_conv_params_wiener changes round_0 there); CDEF is the block above, and its output planes are cdef[].  Self-guided restoration (search_sgrproj_seg,
  * RESTORE_SGRPROJ units) is the next block.
  *
- *   svthip_lr_picture   device pointers to sample (0, 0) of the CDEF'd planes (the pictures restoration filters), the deblocked planes
+ *   svthip_lr_picture   device pointers to sample (0, 0) of the CDEF'd planes (the pictures restoration filters: what
+ *                       svthip_av1_[highbd_]cdef_frame_dev wrote, or a host CDEF's upload), the deblocked planes
  *                       (stripe boundary rows; av1_loop_restoration_save_boundary_lines is not needed on the host for this path: with one
  *                       tile the CDEF boundary lines it saves are never read) and the source planes, strides in samples, the luma size
  *                       (multiples of 8) and the restoration unit size per plane (EbPictureControlSet.c:32-47: luma 256 when
@@ -1014,7 +1094,7 @@ int32_t svthip_av1_highbd_loop_restoration_filter_frame_dev(svthip_ctx *ctx, con
  * on the svthip_lr_picture, unit geometry and per-unit indexing of the Wiener block above; 8 and 10 bits.  Every result is the reference's
  * bit for bit: the filter is integer arithmetic, the five sums of the projection are exact integers (the reference adds them in double,
  * where they are exact too), and the 2 x 2 solve is IEEE double in the reference's order of operations without fused multiply-adds.
- * NOT covered, and staying on the host: rest_finish_search, CDEF, 12-bit video, superres, more than one tile.
+ * NOT covered, and staying on the host: rest_finish_search, 12-bit video, superres, more than one tile.
  *
  * Two geometries.  The search filters a unit in processing units (64 x 64 luma, 32 x 32 chroma) anchored at the unit's corner and reads
  * its 3-sample border from the CDEF'd plane itself (apply_sgr :602-625).  The unit filter and its SSE trial work stripe by stripe with

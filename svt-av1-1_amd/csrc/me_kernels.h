@@ -233,6 +233,15 @@ hipError_t launch_sgr_trial(const svthip_lr_picture& pic, int plane_start, int p
 SVTHIP_LOCAL hipError_t launch_sgr_filter_frame(const svthip_lr_picture& pic, void* const out[3], const uint32_t out_stride[3], int plane_start,
                                                 int plane_end, int bd, const uint8_t* unit_type, const int32_t* sgrproj, uint32_t* refused,
                                                 hipStream_t s);
+// cf_cdef.hip: CDEF -- the strength search over all filter blocks, the strength pick, the frame filter, dist_8x8 on block pairs
+// (kernels: cf_cdef_kernels.h)
+double cdef_lambda(int base_qindex, int bd);
+hipError_t launch_cdef_search_mse(const svthip_cdef_picture& pic, int base_qindex, int bd, uint64_t* mse, uint8_t* counted, hipStream_t s);
+hipError_t launch_cdef_pick(const uint64_t* mse, const uint8_t* counted, uint32_t nfb, int base_qindex, int bd, svthip_cdef_result* result,
+                            int8_t* fb_strength, hipStream_t s);
+hipError_t launch_cdef_frame(const svthip_cdef_picture& pic, const svthip_cdef_result* result, const int8_t* fb_strength, int plane_start,
+                             int plane_end, int bd, hipStream_t s);
+hipError_t launch_cdef_dist_8x8(const uint16_t* dst, const uint16_t* src, uint32_t n, int coeff_shift, uint64_t* out, hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

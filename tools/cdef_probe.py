@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Times the CDEF entries on a synthetic 1920 x 1080 picture (30 x 17 filter blocks), 8 and 10 bits: the strength search of all filter
+blocks, the strength pick, the frame filter of the three planes with the search's own result, and, next to them, the two copies of the
+three planes that a host CDEF between two device stages costs (device to pinned host memory and back, hipMemcpyAsync on the same stream).
+
+    python tools/cdef_probe.py [--iters N] [--out FILE]          device times (needs a GPU)
+    python tools/cdef_probe.py --cpu [--out FILE]                the CPU yardstick (build container only, where the reference exists)
+    python tools/cdef_probe.py --resources FILE                  registers, LDS and scratch of the kernels from the code object's notes
+
+Device times are microseconds: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as
+tools/inter_pred_probe.py takes them.  The pictures are the synthetic ones of tests/golden/make_golden_cdef.py with 30 % of the cells skipped.
+--cpu times the reference's own cdef_seg_search, finish_cdef_search and av1_cdef_frame over the same pictures, one thread, through the
+fixture driver (tests/golden/ref_cdef_driver.c; leaf functions as the encoder dispatches them, AVX2, but the C mse_4x4_16bit): seconds per
+picture, best of two.
+For a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/cdef_probe.py --iters 2"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+
+import make_golden_cdef as gen  # noqa: E402
+
+W, H, QINDEX = 1920, 1080, 100
+
+
+def pictures(bd):
+    rng = np.random.default_rng(bd)
+    dbk, src = gen.make_pictures(rng, W, H, bd)
+    return dbk, src, (rng.random((H // 4, W // 4)) < 0.3).astype(np.uint8)
+
+
+def cpu_yardstick(lines):
+    assert gen.reference_available(), "the CPU yardstick needs the reference sources and oracle/_ref/obj_all"
+    with tempfile.TemporaryDirectory() as tmp:
+        L = gen.build_driver(tmp)
+        for bd in (8, 10):
+            dbk, src, skip = pictures(bd)
+            R = gen.Reference(L, W, H, bd, dbk, src, skip)
+            total, parts = min((R.time(QINDEX) for _ in range(2)), key=lambda t: t[0])
+            R.close()
+            for name, t in zip(("cdef_seg_search", "finish_cdef_search", "av1_cdef_frame"), parts):
+                lines.append({"entry": f"reference {name}, 1 thread", "bit_depth": bd, "us": round(float(t) * 1e6, 1)})
+                print(json.dumps(lines[-1]), flush=True)
+            lines.append({"entry": "reference search + finish + frame, 1 thread", "bit_depth": bd, "us": round(total * 1e6, 1)})
+            print(json.dumps(lines[-1]), flush=True)
+
+
+def device_times(lines, iters):
+    import torch
+
+    import svtav1_hip
+    from inter_pred_probe import timed
+    ctx = svtav1_hip.Context(0)
+    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
+    torch.cuda.set_stream(torch_stream)
+    stream = torch_stream.cuda_stream
+    assert stream
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    nh, nv = svtav1_hip.cdef_filter_blocks(W, H)
+    nfb = nh * nv
+
+    def report(name, bd, fn, reps, **more):
+        row = {"entry": name, "bit_depth": bd, "us": round(timed(torch, fn, iters, reps), 1), **more}
+        lines.append(row)
+        print(json.dumps(row), flush=True)
+
+    for bd in (8, 10):
+        dbk, src, skip = pictures(bd)
+        d_dbk, d_src, d_skip = [dev(p) for p in dbk], [dev(p) for p in src], dev(skip)
+        d_out = [torch.zeros_like(t) for t in d_dbk]
+        strides = [W, W // 2, W // 2]
+        pic = svtav1_hip.make_cdef_picture(W, H, [t.data_ptr() for t in d_dbk], strides, d_skip.data_ptr(), W // 4, [t.data_ptr() for t in d_src], strides,
+                                           [t.data_ptr() for t in d_out], strides)
+        d_mse = torch.zeros(2 * nfb * 64, dtype=torch.int64, device="cuda:0")
+        d_cnt = torch.zeros(nfb, dtype=torch.uint8, device="cuda:0")
+        d_res = torch.zeros(21, dtype=torch.int32, device="cuda:0")
+        d_fbs = torch.zeros(nfb, dtype=torch.int8, device="cuda:0")
+        pinned = [torch.zeros(t.shape, dtype=t.dtype).pin_memory() for t in d_dbk]
+        torch.cuda.synchronize()
+        report("cdef_search_mse (all fbs, 3 planes)", bd,
+               lambda: ctx.av1_cdef_search_mse_dev(pic, QINDEX, d_mse.data_ptr(), d_cnt.data_ptr(), bit_depth=bd, stream=stream), 2, fbs=nfb)
+        report("cdef_pick_strengths", bd,
+               lambda: ctx.cdef_pick_strengths_dev(d_mse.data_ptr(), d_cnt.data_ptr(), nh, nv, QINDEX, bd, d_res.data_ptr(), d_fbs.data_ptr(), stream=stream), 2)
+        torch.cuda.synchronize()
+        res = d_res.cpu().numpy().view(svtav1_hip.CDEF_RESULT_DTYPE)[0]
+        lines[-1].update(sb_count=int(res["sb_count"]), cdef_bits=int(res["cdef_bits"]))
+        report("cdef_frame (3 planes, the search's result)", bd,
+               lambda: ctx.av1_cdef_frame_dev(pic, d_res.data_ptr(), d_fbs.data_ptr(), 0, 3, bit_depth=bd, stream=stream), 5)
+        report("cdef_search (search + pick, one call)", bd,
+               lambda: ctx.av1_cdef_search_dev(pic, QINDEX, d_mse.data_ptr(), d_cnt.data_ptr(), d_res.data_ptr(), d_fbs.data_ptr(), bit_depth=bd,
+                                               stream=stream), 2)
+
+        def copies():
+            for h, d in zip(pinned, d_dbk):
+                h.copy_(d, non_blocking=True)
+            for h, d in zip(pinned, d_out):
+                d.copy_(h, non_blocking=True)
+
+        report("the two plane copies a host CDEF costs (3 planes down, 3 up, pinned)", bd, copies, 5, bytes=2 * sum(t.numel() for t in d_dbk))
+    ctx.synchronize()
+    ctx.close()
+
+
+def resources(path):
+    """the kernels' notes of the built library: the compiler's own resource remarks for csrc/cf_cdef.hip"""
+    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "cf_cdef.hip")
+    with tempfile.TemporaryDirectory() as tmp:
+        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
+                            os.path.join(tmp, "cf_cdef.o")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    keep = ("Function Name", "TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS Size")
+    with open(path, "w") as f:
+        for ln in r.stderr.split("\n"):
+            if "remark:" in ln and any(k in ln for k in keep):
+                t = ln.split("remark:", 1)[1].split("[-Rpass")[0].rstrip()
+                f.write(("Name:" + t.split("Function Name:")[1] if "Function Name" in t else "   " + t.strip()) + "\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--cpu", action="store_true")
+    ap.add_argument("--resources", default=None)
+    a = ap.parse_args()
+    lines = []
+    if a.resources:
+        return resources(a.resources)
+    if a.cpu:
+        cpu_yardstick(lines)
+    else:
+        device_times(lines, a.iters)
+    if a.out:
+        with open(a.out, "a") as f:
+            for row in lines:
+                f.write(json.dumps(row) + "\n")
+
+
+if __name__ == "__main__":
+    main()
