@@ -1,6 +1,9 @@
 // svt-av1-1_amd/csrc/me_hme_impl.h -- search-centre derivation of one superblock by one 256-thread workgroup (device code).
-// Included inside namespace svthip { namespace { ... } } by me_hme.hip, which includes me_sad_common.h (pack64, min3u, wave_min_u64) first.  (A kernel fusing this chain with the full-pel
-// search of the same superblock was bit-identical but slower -- both halves are VALU-bound -- and was removed.)  See me_hme.hip for the mapping and the reference citations.
+// Included inside namespace svthip { namespace { ... } } by me_hme.hip, which includes me_sad_common.h (pack64, min3u, wave_min_u32 / _u64,
+// u32x4_t, unaligned_u32x4) first.  (A kernel fusing this chain with the full-pel search of the same superblock was bit-identical but
+// slower -- both halves are VALU-bound -- and was removed.)  See me_hme.hip for the mapping and the reference citations.
+// Which search loop a level of a superblock takes is decided in hme_level0_search and hme_level_search alone; the header comment of each
+// loop names the shapes that reach it.  The LDS loops read the source block that the workgroup staged (HmeShared::src0 / 1 / 2).
 #pragma once
 
 
@@ -12,7 +15,7 @@
 // integer-to-pointer cast yields a generic pointer and every load becomes a flat_load (which also ties the loads to the LDS
 // counter).  Everything these helpers read lives in the picture pool.
 typedef const __attribute__((address_space(1))) uint32_t gmem_u32;
-struct __attribute__((packed, aligned(1))) gmem_u32x4 { uint32_t v[4]; };  // 16 bytes at byte alignment: one global_load_dwordx4
+typedef const __attribute__((address_space(1))) unaligned_u32x4 gmem_u32x4;  // 16 bytes at byte alignment: one global_load_dwordx4
 
 __device__ __forceinline__ uint32_t ldu32(const uint8_t* p)
 {
@@ -141,7 +144,32 @@ __device__ uint32_t wave_block_sad(const uint8_t* src, uint32_t src_stride, cons
     return wave_sum_u32(acc);
 }
 
-// Generic SadLoopKernel by one wave straight from global memory (any block shape; used for partial SBs).
+// The tail of every search loop.  The best key is made wave-uniform first, so that the decode, and the origin arithmetic, window clipping
+// and loop bounds of the next level, are scalar code instead of vector code under exec masks.
+__device__ __forceinline__ void store_best(uint32_t sad, uint32_t pos, uint32_t sw, uint32_t* best_sad, int* bx, int* by)
+{
+    *best_sad = sad;
+    *by = (int)(pos / sw);
+    *bx = (int)(pos - (uint32_t)(*by) * sw);
+}
+
+// key = sad << pos_bits | raster index
+__device__ __forceinline__ void wave_best_u32(uint32_t key, int pos_bits, int sw, uint32_t* best_sad, int* bx, int* by)
+{
+    key = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_min_u32(key));
+    store_best(key >> pos_bits, key & ((1u << pos_bits) - 1u), (uint32_t)sw, best_sad, bx, by);
+}
+
+// key = sad << 32 | raster index
+__device__ __forceinline__ void wave_best_u64(unsigned long long key, int sw, uint32_t* best_sad, int* bx, int* by)
+{
+    key = wave_min_u64(key);
+    store_best((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(key >> 32)), (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)key),
+               (uint32_t)sw, best_sad, bx, by);
+}
+
+// Generic SadLoopKernel by one wave straight from global memory (any block shape): partial SBs, and full SBs whose window rows are so wide
+// that no band fits the LDS slice (hme_bands).
 __device__ void wave_sad_loop_generic(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride,
                                       uint32_t H, uint32_t W, uint32_t ref_stride_raw, int sw, int sh, int lane,
                                       uint32_t* best_sad, int* bx, int* by)
@@ -174,13 +202,7 @@ __device__ void wave_sad_loop_generic(const uint8_t* src, uint32_t src_stride, c
         const unsigned long long key = ((unsigned long long)acc << 32) | (uint32_t)pos;
         best = key < best ? key : best;  // a lane visits its positions in raster order
     }
-    best = wave_min_u64(best);
-    // every lane holds the same minimum: hand it on in scalar registers, so that the origin arithmetic, window clipping and loop bounds
-    // of the next level are scalar code instead of vector code under exec masks
-    const uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)best);
-    *best_sad = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(best >> 32));
-    *by = (int)(pos / (uint32_t)sw);
-    *bx = (int)(pos - (uint32_t)(*by) * (uint32_t)sw);
+    wave_best_u64(best, sw, best_sad, bx, by);
 }
 
 // Copies `wrows` plane rows of `pitch` dwords each, starting at the (unaligned) address `base`, into LDS (row r at win + r * pitch).
@@ -197,7 +219,6 @@ __device__ __forceinline__ void stage_window_rows(const uint8_t* base, uint32_t 
 {
     if constexpr (QUAD) {
         constexpr int NP = 6;
-        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
         typedef const __attribute__((address_space(1))) uint8_t gmem_u8;
         const int lpr = pitch >> 2;
         const int rpp = lpr < 64 ? 64 / lpr : 1;
@@ -209,11 +230,10 @@ __device__ __forceinline__ void stage_window_rows(const uint8_t* base, uint32_t 
         uint32_t off = (uint32_t)g * ref_stride_raw + 4u * (uint32_t)q4;
         uint32_t* o = win + g * pitch + q4;
         for (int r0 = g; r0 < wrows; r0 += NP * rpp) {
-            gmem_u32x4 w[NP];
+            unaligned_u32x4 w[NP];
 #pragma unroll
             for (int u = 0; u < NP; u++) {
-                const __attribute__((address_space(1))) gmem_u32x4* q =
-                    (const __attribute__((address_space(1))) gmem_u32x4*)(b + min(off + (uint32_t)u * step, last));
+                gmem_u32x4* q = (gmem_u32x4*)(b + min(off + (uint32_t)u * step, last));
 #pragma unroll
                 for (int k = 0; k < 4; k++) w[u].v[k] = q->v[k];
             }
@@ -238,11 +258,11 @@ __device__ __forceinline__ void stage_window_rows(const uint8_t* base, uint32_t 
     const bool lane_ok = g < rpp;
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(base) + 4u * (uint32_t)q4;
     for (int r0 = g; r0 < wrows; r0 += NP * rpp) {
-        gmem_u32x4 w[NP];
+        unaligned_u32x4 w[NP];
 #pragma unroll
         for (int u = 0; u < NP; u++) {
             const int r = min(r0 + u * rpp, wrows - 1);  // clamped: the loads stay unconditional and in flight together
-            const __attribute__((address_space(1))) gmem_u32x4* q = (const __attribute__((address_space(1))) gmem_u32x4*)(a0 + (size_t)r * ref_stride_raw);
+            gmem_u32x4* q = (gmem_u32x4*)(a0 + (size_t)r * ref_stride_raw);
 #pragma unroll
             for (int k = 0; k < 4; k++) w[u].v[k] = q->v[k];
         }
@@ -259,67 +279,67 @@ __device__ __forceinline__ void stage_window_rows(const uint8_t* base, uint32_t 
     }
 }
 
-// SadLoopKernel by one wave for the full-SB block shapes (W = 16 / 32 / 64 px, H rows taken every second plane
-// row), LDS-staged:
-//   * the W x H source block and a band of the search window are copied to this wave's LDS slice with aligned,
-//     coalesced dword loads (the window is re-aligned with v_alignbyte so search column 0 sits on a dword);
+// stage_window_rows, complete and visible to the wave.  The copy is a memory round trip that the search waits for: it is issued at raised
+// priority, ahead of the other waves' search loops.
+template <bool QUAD>
+__device__ __forceinline__ void stage_window(const uint8_t* base, uint32_t ref_stride_raw, int wrows, int pitch, uint32_t* win, int lane)
+{
+    HME_PRIO(3);
+    stage_window_rows<QUAD>(base, ref_stride_raw, wrows, pitch, win, lane);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    HME_PRIO(0);
+}
+
+// Window geometry of the banded LDS loops: a W-pixel block of H rows (every second plane row) over `sw` search columns, in items of `item`
+// positions (8: wave_sad_loop_lds, one pad dword so that the odd pitch spreads rows over banks; 16: the level-0 loops, pitch a multiple
+// of four dwords so that items stay 16-byte aligned).  `band` is the number of search rows whose window (band + 2 * H - 2 rows) fits the
+// wave's slice; below 1 no band fits and the caller takes wave_sad_loop_generic.
+struct HmeBands { int pitch, band; };
+__device__ __forceinline__ HmeBands hme_bands(int W, int H, int sw, int item)
+{
+    const int pitch = (item / 4) * (int)((uint32_t)(sw + item - 1) / (uint32_t)item) + W / 4 + (item == 8 ? 1 : 0);
+    return {pitch, kHmeLdsPerWave / 4 / pitch - (2 * H - 2)};
+}
+
+__device__ __forceinline__ void add_u16x4(uint32_t* sad, uint64_t acc)  // four packed u16 sums onto four 32-bit ones
+{
+    sad[0] += (uint32_t)acc & 0xffffu; sad[1] += ((uint32_t)acc) >> 16;
+    sad[2] += (uint32_t)(acc >> 32) & 0xffffu; sad[3] += (uint32_t)(acc >> 48);
+}
+
+// SadLoopKernel by one wave for the full-SB block shapes (W = 16 / 32 / 64 px, H rows taken every second plane row), LDS-staged.  It
+// takes level 1 / 2 of full SBs whose area is not the fixed shape (clipped windows, other parameters) and level 0 where the 16-position
+// items do not apply (hme_level_search, hme_level0_search); the caller has checked that a band fits: hme_bands(W, H, sw, 8).band >= 1.
+//   * a band of the search window is copied to this wave's LDS slice `lds` (stage_window_rows; search column 0 sits on a dword), the
+//     search area is processed in bands of rows that fit;
 //   * an item is 8 horizontally consecutive search positions of one search row; its lanes read W/4 + 2 window
 //     dwords per block row and issue 2 * W/4 v_qsad_pk_u16_u8 (4 positions x 4 pixels each);
 //   * when a level has fewer than 64 items (HME L1 / L2), RP lanes share an item and split its block rows;
 //   * best position: 64-bit key (sad << 32 | raster index), lane-local strict min, then a wave min.
-// `lds` is this wave's private slice of `lds_bytes` bytes; the search area is processed in bands of rows that fit.
-// `shared_src` (may be null): the H x W source block already staged in LDS by the workgroup ([H][W / 4] dwords, shared by the
-// four region waves); then the whole slice holds the window.
+// `srcbuf`: the H x W source block staged by the workgroup ([H][W / 4] dwords, shared by the four region waves).
 // KEY32: the caller guarantees sw * sh <= 4096 (the reference's level-1 / level-2 areas are 256 / 64 positions) and every W x H here has
 // SAD < 2^20, so the best position is a 32-bit minimum of sad << 12 | position instead of a 64-bit one.
 template <int W, bool KEY32 = false>
-__device__ void wave_sad_loop_lds(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride_raw,
-                                  int H, int sw, int sh, int lane, uint8_t* lds, int lds_bytes, uint32_t* best_sad,
-                                  int* bx, int* by, const uint32_t* shared_src = nullptr)
+__device__ void wave_sad_loop_lds(const uint8_t* ref, uint32_t ref_stride_raw, int H, int sw, int sh, int lane, uint8_t* lds,
+                                  const uint32_t* srcbuf, uint32_t* best_sad, int* bx, int* by)
 {
     constexpr int WD = W / 4;                 // source dwords per block row
     constexpr int FLUSH = (W == 16) ? 16 : (W == 32 ? 8 : 4);  // rows a u16 accumulator can take: rows*W*255 < 65536
-    const int own_src = shared_src ? 0 : H * WD;
-    const uint32_t* srcbuf = shared_src ? shared_src : reinterpret_cast<const uint32_t*>(lds);  // [H][WD]
-    const int noct = (sw + 7) >> 3;
-    const int pitch = 2 * noct + WD + 1;      // window dwords per row (+1: odd pitch spreads rows over banks)
-    uint32_t* win = reinterpret_cast<uint32_t*>(lds) + own_src;
-    const int avail_rows = (lds_bytes / 4 - own_src) / pitch;
-    int band = avail_rows - (2 * H - 2);      // search rows per band
-    if (band > sh) band = sh;
-    if (band < 1) {  // window row wider than the slice (cannot happen for the reference's parameter ranges)
-        wave_sad_loop_generic(src, src_stride, ref, ref_stride_raw * 2, (uint32_t)H, (uint32_t)W, ref_stride_raw, sw, sh, lane,
-                              best_sad, bx, by);
-        return;
-    }
-
-    // source block -> LDS (rows are src_stride apart, already the doubled stride); 4 dwords per lane in flight
-    for (int i0 = 0; !shared_src && i0 < H * WD; i0 += 256) {
-        uint32_t v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int i = min(i0 + k * 64 + lane, H * WD - 1);  // clamped: no branches, loads stay in flight together
-            const int r = i / WD, c = i - r * WD;                // WD is a power of two: shifts
-            v[k] = ldu32_nb(src + (uint32_t)r * src_stride + 4u * (uint32_t)c);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) reinterpret_cast<uint32_t*>(lds)[min(i0 + k * 64 + lane, H * WD - 1)] = v[k];
-    }
+    const HmeBands g = hme_bands(W, H, sw, 8);
+    const int pitch = g.pitch;                // window dwords per row
+    const int band = min(g.band, sh);         // search rows per band
+    uint32_t* win = reinterpret_cast<uint32_t*>(lds);
 
     // items and row-parts
-    const int items_row = noct;
+    const int items_row = (sw + 7) >> 3;
     unsigned long long best = ~0ull;
     uint32_t best32 = 0xffffffffu;
 
     for (int y0 = 0; y0 < sh; y0 += band) {
         const int bh = min(band, sh - y0);
-        const int wrows = bh + 2 * H - 2;
         HME_LOOP_T(t_a);
-        HME_PRIO(3);  // the window copy is a memory round trip the search below waits for: issue it ahead of the other waves' search loops
-        stage_window_rows(ref + (size_t)y0 * ref_stride_raw, ref_stride_raw, wrows, pitch, win, lane);
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        HME_PRIO(0);
+        stage_window<false>(ref + (size_t)y0 * ref_stride_raw, ref_stride_raw, bh + 2 * H - 2, pitch, win, lane);
         HME_LOOP_T(t_b);
         HME_LOOP_ADD(0, t_b, t_a);
 
@@ -353,17 +373,13 @@ __device__ void wave_sad_loop_lds(const uint8_t* src, uint32_t src_stride, const
                 }
                 if (++since == FLUSH) {
                     since = 0;
-                    sad[0] += (uint32_t)acc0 & 0xffffu; sad[1] += ((uint32_t)acc0) >> 16;
-                    sad[2] += (uint32_t)(acc0 >> 32) & 0xffffu; sad[3] += (uint32_t)(acc0 >> 48);
-                    sad[4] += (uint32_t)acc1 & 0xffffu; sad[5] += ((uint32_t)acc1) >> 16;
-                    sad[6] += (uint32_t)(acc1 >> 32) & 0xffffu; sad[7] += (uint32_t)(acc1 >> 48);
+                    add_u16x4(sad, acc0);
+                    add_u16x4(sad + 4, acc1);
                     acc0 = acc1 = 0;
                 }
             }
-            sad[0] += (uint32_t)acc0 & 0xffffu; sad[1] += ((uint32_t)acc0) >> 16;
-            sad[2] += (uint32_t)(acc0 >> 32) & 0xffffu; sad[3] += (uint32_t)(acc0 >> 48);
-            sad[4] += (uint32_t)acc1 & 0xffffu; sad[5] += ((uint32_t)acc1) >> 16;
-            sad[6] += (uint32_t)(acc1 >> 32) & 0xffffu; sad[7] += (uint32_t)(acc1 >> 48);
+            add_u16x4(sad, acc0);
+            add_u16x4(sad + 4, acc1);
             // sum the row-parts of an item (its RP lanes are consecutive)
             for (int m = 1; m < RP; m <<= 1) {
 #pragma unroll
@@ -390,17 +406,10 @@ __device__ void wave_sad_loop_lds(const uint8_t* src, uint32_t src_stride, const
         HME_LOOP_ADD(1, t_c, t_b);
     }
     HME_LOOP_T(t_d);
-    if (KEY32) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) best32 = min(best32, (uint32_t)__shfl_xor((int)best32, m));
-        best = ((unsigned long long)(best32 >> 12) << 32) | (best32 & 0xfffu);
-    } else {
-        best = wave_min_u64(best);
-    }
-    const uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)best);  // wave-uniform: scalar from here on
-    *best_sad = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(best >> 32));
-    *by = (int)(pos / (uint32_t)sw);
-    *bx = (int)(pos - (uint32_t)(*by) * (uint32_t)sw);
+    if (KEY32)
+        wave_best_u32(best32, 12, sw, best_sad, bx, by);
+    else
+        wave_best_u64(best, sw, best_sad, bx, by);
     HME_LOOP_T(t_e);
     HME_LOOP_ADD(2, t_e, t_d);
     HME_LOOP_ADD(3, 1ull, 0ull);
@@ -432,15 +441,10 @@ __device__ void wave_sad_loop_fixed(const uint8_t* ref, uint32_t ref_stride_raw,
     static_assert(ROWS * W * 255 < 65536 && H * W * 255 < (1 << 20) && SW * SH <= 4096 && (SW & (SW - 1)) == 0, "u16 sums, 32-bit keys");
     static_assert(WROWS * PITCH * 4 <= kHmeLdsPerWave, "the window fits the slice");
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
     uint32_t* win = reinterpret_cast<uint32_t*>(lds);
-    HME_PRIO(3);
-    stage_window_rows<true>(ref, ref_stride_raw, WROWS, PITCH, win, lane);
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    HME_PRIO(0);
+    stage_window<true>(ref, ref_stride_raw, WROWS, PITCH, win, lane);
 
     const int iy = lane / RP, part = lane & (RP - 1);
     const uint32_t* w0 = win + (iy + 2 * part) * PITCH;  // window row of block row `part`; block row part + RP * i is 2 * RP * i rows below
@@ -509,10 +513,7 @@ __device__ void wave_sad_loop_fixed(const uint8_t* ref, uint32_t ref_stride_raw,
     key = min(key, dpp_fetch<0x128>(key));  // row_ror:8: every lane of a row of 16 holds the row's minimum
     const uint32_t best = min(min((uint32_t)__builtin_amdgcn_readlane((int)key, 0), (uint32_t)__builtin_amdgcn_readlane((int)key, 16)),
                               min((uint32_t)__builtin_amdgcn_readlane((int)key, 32), (uint32_t)__builtin_amdgcn_readlane((int)key, 48)));
-    const uint32_t pos = best & 0xfffu;
-    *best_sad = best >> 12;
-    *by = (int)(pos / (uint32_t)SW);
-    *bx = (int)(pos % (uint32_t)SW);
+    store_best(best >> 12, best & 0xfffu, (uint32_t)SW, best_sad, bx, by);
 }
 
 // One block row of a level-0 item: window dwords wr[0..7] (two ds_read_b128) against the four source dwords of the row, 16 v_qsad.
@@ -521,7 +522,6 @@ __device__ void wave_sad_loop_fixed(const uint8_t* ref, uint32_t ref_stride_raw,
 // conflict.
 __device__ __forceinline__ void l0_row_sads(const uint32_t* wr, const uint32_t* sr, uint64_t* acc)
 {
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     const u32x4_t da = *reinterpret_cast<const u32x4_t*>(wr);
     const u32x4_t db = *reinterpret_cast<const u32x4_t*>(wr + 4);
     const uint4 sv = *reinterpret_cast<const uint4*>(sr);
@@ -531,6 +531,16 @@ __device__ __forceinline__ void l0_row_sads(const uint32_t* wr, const uint32_t* 
     for (int c = 0; c < 4; c++)
 #pragma unroll
         for (int g = 0; g < 4; g++) acc[g] = __builtin_amdgcn_qsad_pk_u16_u8(pack64(d[c + g], d[c + g + 1]), s4[c], acc[g]);
+}
+
+// A whole level-0 item by one lane: the 8 block rows fully unrolled (128 v_qsad), so that every LDS offset is an immediate or a scalar
+// multiple of the pitch.  `w0`: the item's first window row; `srcbuf`: the [8][4]-dword source block.
+__device__ __forceinline__ void l0_item_sads(const uint32_t* w0, int pitch, const uint32_t* srcbuf, uint64_t* acc)
+{
+#pragma unroll
+    for (int g = 0; g < 4; g++) acc[g] = 0;
+#pragma unroll
+    for (int r = 0; r < 8; r++) l0_row_sads(w0 + 2 * r * pitch, srcbuf + r * 4, acc);
 }
 
 // Minimum of the 16 keys (sad << 16 | j), j = 0..15, of an item whose 16 positions are all valid: one v_lshl_or / v_and_or with an
@@ -547,6 +557,60 @@ __device__ __forceinline__ uint32_t l0_item_min(const uint64_t* acc)
     return lb;
 }
 
+// The same for the last item of a search row whose width is not a multiple of 16: only positions j < nvalid can win.
+__device__ __forceinline__ uint32_t l0_item_min_masked(const uint64_t* acc, int nvalid)
+{
+    uint32_t lb = 0xffffffffu;
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const uint32_t lo = (uint32_t)acc[g], hi = (uint32_t)(acc[g] >> 32);
+        const uint32_t sad4[4] = {lo << 16, lo & 0xffff0000u, hi << 16, hi & 0xffff0000u};
+#pragma unroll
+        for (int j = 0; j < 4; j++) lb = min(lb, 4 * g + j < nvalid ? sad4[j] | (uint32_t)(4 * g + j) : 0xffffffffu);
+    }
+    return lb;
+}
+
+// Key of item `item` (search row iy of the band that starts at search row y0, nit items per row) of an area of any width: the minimum of
+// its relative keys plus its raster base (y0 + iy) * sw + 16 * io.  The choice between the two minima is wave-uniform.
+__device__ __forceinline__ uint32_t l0_band_item_key(const uint64_t* acc, int sw, int nit, int y0, uint32_t item, uint32_t iy)
+{
+    const int io = (int)(item - iy * (uint32_t)nit);
+    const uint32_t lb = (sw & 15) == 0 ? l0_item_min(acc) : l0_item_min_masked(acc, sw - 16 * io);
+    return lb + (uint32_t)((y0 + (int)iy) * sw + 16 * io);
+}
+
+// One remainder round of a level-0 loop: 2 / 4 / 8 lanes share an item and split its block rows, so that a handful of left-over items
+// does not cost a whole 128-v_qsad pass with most lanes idle (the reference's 100 % level-0 area is 72 items: 64 + 8; the 1080p 200 %
+// area 288 = 4 x 64 + 32; banded areas have a remainder per band).  The 16-bit partial sums of an item's lanes are added as packed pairs (a
+// 16 x 8 SAD is < 2^16).  Takes up to 32 / 16 / 8 of the items from `it0` on and returns how many.  Every lane gets the sums `acc` of its
+// item `*item` of search row `*iy` (one multiplication: at most two rounds per wave and band); `*mine`: this lane reports the item.
+// The item's window address, iy * pitch + 4 * io dwords, is 4 * (item + iy) for pitch = 4 * nit + 4.
+__device__ __forceinline__ int l0_remainder_round(const uint32_t* win, int pitch, const uint32_t* srcbuf, uint32_t inv_nit, int it0,
+                                                  int nitems, int lane, uint64_t* acc, uint32_t* item, uint32_t* iy, bool* mine)
+{
+    const int rem = nitems - it0;
+    const int rp_shift = rem > 16 ? 1 : rem > 8 ? 2 : 3;
+    const int RP = 1 << rp_shift, take = min(rem, 64 >> rp_shift);
+    const int slot = lane >> rp_shift, part = lane & (RP - 1);
+    *item = (uint32_t)(it0 + min(slot, take - 1));
+    *iy = (*item * inv_nit) >> 20;
+    const uint32_t* w0 = win + 4u * (*item + *iy);
+#pragma unroll
+    for (int g = 0; g < 4; g++) acc[g] = 0;
+    for (int r = part; r < 8; r += RP) l0_row_sads(w0 + 2 * r * pitch, srcbuf + r * 4, acc);
+    for (int m = 1; m < RP; m <<= 1) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const uint32_t lo = (uint32_t)acc[g] + (uint32_t)__shfl_xor((int)(uint32_t)acc[g], m);
+            const uint32_t hi = (uint32_t)(acc[g] >> 32) + (uint32_t)__shfl_xor((int)(uint32_t)(acc[g] >> 32), m);
+            acc[g] = pack64(lo, hi);
+        }
+    }
+    *mine = slot < take && part == 0;
+    return take;
+}
+
 // Level 0 of a full SB whose clipped search width is a multiple of 16 (sw = 16 * nit) and whose whole window fits the slice in one
 // band (the reference's 100 % and 200 % areas): wave_sad_loop_l0's items, passes and remainder, with what that shape makes constant.
 //   * Item i of the raster of items is search row iy = i / nit, column item io = i % nit; its raster base iy * sw + 16 * io is 16 * i
@@ -559,14 +623,9 @@ __device__ __forceinline__ uint32_t l0_item_min(const uint64_t* acc)
 __device__ void wave_sad_loop_l0_oneband(const uint8_t* ref, uint32_t ref_stride_raw, int nit, int sh, int lane, uint8_t* lds,
                                          const uint32_t* srcbuf, uint32_t* best_sad, int* bx, int* by)
 {
-    constexpr int H = 8, WD = 4;
-    const int pitch = 4 * nit + 4;
+    const int pitch = 4 * nit + 4;  // hme_bands(16, 8, 16 * nit, 16).pitch
     const uint32_t* win = reinterpret_cast<const uint32_t*>(lds);
-    HME_PRIO(3);
-    stage_window_rows<true>(ref, ref_stride_raw, sh + 2 * H - 2, pitch, reinterpret_cast<uint32_t*>(lds), lane);
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    HME_PRIO(0);
+    stage_window<true>(ref, ref_stride_raw, sh + 2 * 8 - 2, pitch, reinterpret_cast<uint32_t*>(lds), lane);
 
     const int nitems = nit * sh;
     const uint32_t inv_nit = (1u << 20) / (uint32_t)nit + 1u;
@@ -575,180 +634,109 @@ __device__ void wave_sad_loop_l0_oneband(const uint8_t* ref, uint32_t ref_stride
     uint32_t item = (uint32_t)lane;
     uint32_t iy = (item * inv_nit) >> 20, io = item - iy * (uint32_t)nit;
     int it0 = 0;
-    // whole passes: a lane owns an item (all 8 block rows, 128 v_qsad); lanes past the last item read item 0 and never win
+    // whole passes: a lane owns an item; lanes past the last item read item 0 and never win
     for (; nitems - it0 >= 57; it0 += 64) {
         const bool valid = item < (uint32_t)nitems;
-        const uint32_t* w0 = win + (valid ? 4u * (item + iy) : 0u);
-        uint64_t acc[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int r = 0; r < H; r++) l0_row_sads(w0 + 2 * r * pitch, srcbuf + r * WD, acc);
-        const uint32_t key = l0_item_min(acc) + 16u * item;
-        best = min(best, valid ? key : 0xffffffffu);
+        uint64_t acc[4];
+        l0_item_sads(win + (valid ? 4u * (item + iy) : 0u), pitch, srcbuf, acc);
+        best = min(best, valid ? l0_item_min(acc) + 16u * item : 0xffffffffu);
         item += 64;
         io += rs;
         const bool carry = io >= (uint32_t)nit;
         io -= carry ? (uint32_t)nit : 0u;
         iy += qs + (carry ? 1u : 0u);
     }
-    // the remainder, as in wave_sad_loop_l0: 2 / 4 / 8 lanes share an item and split its block rows; the 16-bit partial sums of an
-    // item's lanes are added as packed pairs.  At most two rounds per wave: their (iy) comes from one multiplication each.
     while (it0 < nitems) {
-        const int rem = nitems - it0;
-        const int rp_shift = rem > 16 ? 1 : rem > 8 ? 2 : 3;
-        const int RP = 1 << rp_shift, take = min(rem, 64 >> rp_shift);
-        const int slot = lane >> rp_shift, part = lane & (RP - 1);
-        const uint32_t ri = (uint32_t)(it0 + min(slot, take - 1));
-        const uint32_t* w0 = win + 4u * (ri + ((ri * inv_nit) >> 20));
-        uint64_t acc[4] = {0, 0, 0, 0};
-        for (int r = part; r < H; r += RP) l0_row_sads(w0 + 2 * r * pitch, srcbuf + r * WD, acc);
-        for (int m = 1; m < RP; m <<= 1) {
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const uint32_t lo = (uint32_t)acc[g] + (uint32_t)__shfl_xor((int)(uint32_t)acc[g], m);
-                const uint32_t hi = (uint32_t)(acc[g] >> 32) + (uint32_t)__shfl_xor((int)(uint32_t)(acc[g] >> 32), m);
-                acc[g] = pack64(lo, hi);
-            }
-        }
-        const uint32_t key = l0_item_min(acc) + 16u * ri;
-        best = min(best, (slot < take && part == 0) ? key : 0xffffffffu);
-        it0 += take;
+        uint64_t acc[4];
+        uint32_t ri, ry;
+        bool mine;
+        it0 += l0_remainder_round(win, pitch, srcbuf, inv_nit, it0, nitems, lane, acc, &ri, &ry, &mine);
+        best = min(best, mine ? l0_item_min(acc) + 16u * ri : 0xffffffffu);
     }
     __builtin_amdgcn_wave_barrier();  // the next level's staging overwrites the window
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, m));
-    best = (uint32_t)__builtin_amdgcn_readfirstlane((int)best);  // wave-uniform: scalar from here on
-    const uint32_t pos = best & 0xffffu, sw = 16u * (uint32_t)nit;
-    *best_sad = best >> 16;
-    *by = (int)(pos / sw);
-    *bx = (int)(pos - (uint32_t)(*by) * sw);
+    wave_best_u32(best, 16, 16 * nit, best_sad, bx, by);
 }
 
-// SadLoopKernel of HME level 0 (16 x 8-row block on the 1/16 plane; ~70 % of the search-centre work), one wave.
+// SadLoopKernel of HME level 0 (16 x 8-row block on the 1/16 plane; ~70 % of the search-centre work), one wave: full SBs whose width is
+// not a multiple of 16 (the 140 % area, clipped windows) or whose window needs more than one band (4K, the 350 / 525 % multipliers).
+// The caller (hme_level0_search) has checked hme_bands(16, 8, sw, 16).band >= 1 and sw * sh <= 65536.
 // An item is 16 consecutive search positions of one search row = 16 bytes = one ds_read_b128 step along the window, so lane
 // i of a row reads window dwords 4i .. 4i+7 with two conflict-free b128 loads per block row and issues 16 v_qsad_pk_u16_u8
-// (4 source dwords x 4 position groups); the 8 block rows are fully unrolled so every LDS offset is an immediate or a
-// scalar multiple of the pitch.  A 16x8 SAD is < 2^16 and the area has < 2^16 positions, so the best position is a 32-bit
-// (sad << 16 | raster index) minimum, which is the reference's strict-'<' raster rule.
-__device__ void wave_sad_loop_l0(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride_raw, int sw, int sh,
-                                 int lane, uint8_t* lds, int lds_bytes, uint32_t* best_sad, int* bx, int* by,
-                                 const uint32_t* shared_src = nullptr)
+// (4 source dwords x 4 position groups).  A 16x8 SAD is < 2^16 and the area has < 2^16 positions, so the best position is a 32-bit
+// (sad << 16 | raster index) minimum, which is the reference's strict-'<' raster rule: an item's 16 keys are relative to the item
+// (l0_item_min, or l0_item_min_masked where the width is not a multiple of 16: positions beyond it never win) and its raster base is
+// added to their minimum, which cannot carry into the SAD field since every raster index is below 2^16.
+__device__ void wave_sad_loop_l0(const uint8_t* ref, uint32_t ref_stride_raw, int sw, int sh, int lane, uint8_t* lds,
+                                 const uint32_t* srcbuf, uint32_t* best_sad, int* bx, int* by)
 {
-    constexpr int H = 8, WD = 4;
-    const int own_src = shared_src ? 0 : H * WD;
-    const uint32_t* srcbuf = shared_src ? shared_src : reinterpret_cast<const uint32_t*>(lds);  // [8][4], 16-byte aligned
+    constexpr int H = 8;
+    const HmeBands g = hme_bands(16, H, sw, 16);
     const int nit = (sw + 15) >> 4;                       // items per search row
-    const int pitch = 4 * nit + 4;                        // window dwords per row (multiple of 4: items stay 16-byte aligned)
-    uint32_t* win = reinterpret_cast<uint32_t*>(lds) + own_src;
-    const int avail_rows = (lds_bytes / 4 - own_src) / pitch;
-    int band = avail_rows - (2 * H - 2);
-    if (band > sh) band = sh;
-    if (band < 1 || sw * sh > 65536) {
-        wave_sad_loop_lds<16>(src, src_stride, ref, ref_stride_raw, H, sw, sh, lane, lds, lds_bytes, best_sad, bx, by, shared_src);
-        return;
-    }
-    if (shared_src && (sw & 15) == 0 && band == sh) {  // wave-uniform; every other shape keeps the loops below
-        wave_sad_loop_l0_oneband(ref, ref_stride_raw, nit, sh, lane, lds, shared_src, best_sad, bx, by);
-        return;
-    }
-    if (!shared_src && lane < H * WD)
-        reinterpret_cast<uint32_t*>(lds)[lane] = ldu32_nb(src + (uint32_t)(lane >> 2) * src_stride + 4u * (uint32_t)(lane & 3));
+    const int pitch = g.pitch, band = min(g.band, sh);
+    uint32_t* win = reinterpret_cast<uint32_t*>(lds);
     uint32_t best = 0xffffffffu;
     const uint32_t inv_nit = (1u << 20) / (uint32_t)nit + 1u;
     for (int y0 = 0; y0 < sh; y0 += band) {
         const int bh = min(band, sh - y0);
-        HME_PRIO(3);
-        stage_window_rows(ref + (size_t)y0 * ref_stride_raw, ref_stride_raw, bh + 2 * H - 2, pitch, win, lane);
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        HME_PRIO(0);
+        stage_window<false>(ref + (size_t)y0 * ref_stride_raw, ref_stride_raw, bh + 2 * H - 2, pitch, win, lane);
         const int nitems = nit * bh;
-        // 16 keys of one item: (sad << 16) + raster index; positions beyond the search width and lanes without an item never win
-        auto track = [&](const uint64_t* acc, int iy, int io, bool valid) {
-            const int xs0 = 16 * io;
-            const uint32_t base = (uint32_t)((y0 + iy) * sw + xs0);
-            if ((sw & 15) == 0) {
-                // every item is 16 valid positions (wave-uniform case; the reference's default areas): one v_lshl_or / v_and_or per key and
-                // one v_min3 per two keys instead of compare + select + add + min per position; only the padding lanes are masked, once
-                uint32_t lb = 0xffffffffu;
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const uint32_t lo = (uint32_t)acc[g], hi = (uint32_t)(acc[g] >> 32), ix = base + 4u * (uint32_t)g;
-                    lb = min3u((lo << 16) | ix, (lo & 0xffff0000u) | (ix + 1u), lb);
-                    lb = min3u((hi << 16) | (ix + 2u), (hi & 0xffff0000u) | (ix + 3u), lb);
-                }
-                best = min(best, valid ? lb : 0xffffffffu);
-                return;
-            }
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const uint32_t lo = (uint32_t)acc[g], hi = (uint32_t)(acc[g] >> 32);
-                const uint32_t sad4[4] = {lo << 16, lo & 0xffff0000u, hi << 16, hi & 0xffff0000u};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int xs = xs0 + 4 * g + j;
-                    const uint32_t key = (valid && xs < sw) ? (sad4[j] + base + (uint32_t)(4 * g + j)) : 0xffffffffu;
-                    best = min(best, key);
-                }
-            }
-        };
-        auto row_sads = [&](const uint32_t* wr, int r, uint64_t* acc) {
-            const uint4 da = *reinterpret_cast<const uint4*>(wr);
-            const uint4 db = *reinterpret_cast<const uint4*>(wr + 4);
-            const uint4 sv = *reinterpret_cast<const uint4*>(srcbuf + r * WD);
-            const uint32_t d[8] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w};
-            const uint32_t s4[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-            for (int c = 0; c < WD; c++)
-#pragma unroll
-                for (int g = 0; g < 4; g++)
-                    acc[g] = __builtin_amdgcn_qsad_pk_u16_u8(pack64(d[c + g], d[c + g + 1]), s4[c], acc[g]);
-        };
         int it0 = 0;
-        // whole passes: a lane owns an item (all 8 block rows, 128 v_qsad)
+        // whole passes: a lane owns an item
         for (; nitems - it0 >= 57; it0 += 64) {
-            const int item = min(it0 + lane, nitems - 1);
-            const bool valid = it0 + lane < nitems;
-            const int iy = (int)(((uint32_t)item * inv_nit) >> 20), io = item - iy * nit;
-            const uint32_t* w0 = win + iy * pitch + 4 * io;
-            uint64_t acc[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int r = 0; r < H; r++) row_sads(w0 + 2 * r * pitch, r, acc);
-            track(acc, iy, io, valid);
+            const uint32_t item = (uint32_t)min(it0 + lane, nitems - 1);
+            const uint32_t iy = (item * inv_nit) >> 20;
+            uint64_t acc[4];
+            l0_item_sads(win + 4u * (item + iy), pitch, srcbuf, acc);
+            best = min(best, it0 + lane < nitems ? l0_band_item_key(acc, sw, nit, y0, item, iy) : 0xffffffffu);
         }
-        // the remainder: 2 / 4 / 8 lanes share an item and split its block rows, so that a handful of left-over items does not cost a
-        // whole 128-v_qsad pass with most lanes idle (the reference's 100 % level-0 area is 72 items: 64 + 8; the 1080p 200 % area, one band
-        // since the slice is 7 KB, 288 = 4 x 64 + 32; larger areas -- 4K, the 350 / 525 % multipliers -- run in bands, each with its remainder).
-        // The 16-bit partial sums of an item's lanes are added as packed pairs (a 16 x 8 SAD is < 2^16).
         while (it0 < nitems) {
-            const int rem = nitems - it0;
-            const int rp_shift = rem > 32 ? 1 : rem > 16 ? 1 : rem > 8 ? 2 : 3;
-            const int RP = 1 << rp_shift, take = min(rem, 64 >> rp_shift);
-            const int slot = lane >> rp_shift, part = lane & (RP - 1);
-            const int item = it0 + min(slot, take - 1);
-            const int iy = (int)(((uint32_t)item * inv_nit) >> 20), io = item - iy * nit;
-            const uint32_t* w0 = win + iy * pitch + 4 * io;
-            uint64_t acc[4] = {0, 0, 0, 0};
-            for (int r = part; r < H; r += RP) row_sads(w0 + 2 * r * pitch, r, acc);
-            for (int m = 1; m < RP; m <<= 1) {
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const uint32_t lo = (uint32_t)acc[g] + (uint32_t)__shfl_xor((int)(uint32_t)acc[g], m);
-                    const uint32_t hi = (uint32_t)(acc[g] >> 32) + (uint32_t)__shfl_xor((int)(uint32_t)(acc[g] >> 32), m);
-                    acc[g] = pack64(lo, hi);
-                }
-            }
-            track(acc, iy, io, slot < take && part == 0);
-            it0 += take;
+            uint64_t acc[4];
+            uint32_t item, iy;
+            bool mine;
+            it0 += l0_remainder_round(win, pitch, srcbuf, inv_nit, it0, nitems, lane, acc, &item, &iy, &mine);
+            best = min(best, mine ? l0_band_item_key(acc, sw, nit, y0, item, iy) : 0xffffffffu);
         }
         __builtin_amdgcn_wave_barrier();
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, m));
-    best = (uint32_t)__builtin_amdgcn_readfirstlane((int)best);  // wave-uniform: scalar from here on
-    const uint32_t pos = best & 0xffffu;
-    *best_sad = best >> 16;
-    *by = (int)(pos / (uint32_t)sw);
-    *bx = (int)(pos - (uint32_t)(*by) * (uint32_t)sw);
+    wave_best_u32(best, 16, sw, best_sad, bx, by);
+}
+
+// Level 0 of one region by one wave: a 16 x 8-row block of the 1/16 plane, `bw` pixels wide in this SB (16: a full SB, whose block the
+// workgroup staged in `srcbuf`).  The one place that says which level-0 loop a shape takes.
+__device__ __forceinline__ void hme_level0_search(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride_raw, int bw,
+                                                  int sw, int sh, int lane, uint8_t* lds, const uint32_t* srcbuf, uint32_t* best_sad,
+                                                  int* bx, int* by)
+{
+    const int band16 = hme_bands(16, 8, sw, 16).band;
+    if (bw == 16 && band16 >= 1 && sw * sh <= 65536) {
+        if ((sw & 15) == 0 && band16 >= sh)
+            wave_sad_loop_l0_oneband(ref, ref_stride_raw, sw >> 4, sh, lane, lds, srcbuf, best_sad, bx, by);
+        else
+            wave_sad_loop_l0(ref, ref_stride_raw, sw, sh, lane, lds, srcbuf, best_sad, bx, by);
+    } else if (bw == 16 && hme_bands(16, 8, sw, 8).band >= 1) {
+        wave_sad_loop_lds<16>(ref, ref_stride_raw, 8, sw, sh, lane, lds, srcbuf, best_sad, bx, by);
+    } else {
+        wave_sad_loop_generic(src, src_stride, ref, ref_stride_raw * 2, 8, (uint32_t)bw, ref_stride_raw, sw, sh, lane, best_sad, bx, by);
+    }
+}
+
+// Level 1 or 2 of one region by one wave: a W x H-row block (32 x 16 of the 1/4 plane, 64 x 32 of the full plane), `bw` pixels wide in
+// this SB (W: a full SB, whose block the workgroup staged in `srcbuf`); FSW x FSH is the reference's own area at this level, which has the
+// fixed-shape loop.  The one place that says which loop a level-1 / level-2 shape takes.
+template <int W, int H, int FSW, int FSH>
+__device__ __forceinline__ void hme_level_search(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride_raw, int bw,
+                                                 int sw, int sh, int lane, uint8_t* lds, const uint32_t* srcbuf, uint32_t* best_sad,
+                                                 int* bx, int* by)
+{
+    const bool fits = bw == W && hme_bands(W, H, sw, 8).band >= 1;
+    if (bw == W && sw == FSW && sh == FSH)
+        wave_sad_loop_fixed<W, H, FSW, FSH>(ref, ref_stride_raw, lane, lds, srcbuf, best_sad, bx, by);
+    else if (fits && sw * sh <= 4096)
+        wave_sad_loop_lds<W, true>(ref, ref_stride_raw, H, sw, sh, lane, lds, srcbuf, best_sad, bx, by);
+    else if (fits)
+        wave_sad_loop_lds<W>(ref, ref_stride_raw, H, sw, sh, lane, lds, srcbuf, best_sad, bx, by);
+    else
+        wave_sad_loop_generic(src, src_stride, ref, ref_stride_raw * 2, H, (uint32_t)bw, ref_stride_raw, sw, sh, lane, best_sad, bx, by);
 }
 
 __device__ __forceinline__ void clamp_center(int& x, int& y, int ox, int oy, int pw, int ph)
@@ -890,7 +878,7 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
             else { xc = 0; yc = th; }
         }
 
-        if (P.enable_hme_flag && sb_h == 64) {  // :6323
+        if (P.enable_hme_flag && sb_h == 64) {  // :6323; full height: the blocks of the three levels have 8 / 16 / 32 rows
             const int nreg = nw * nh;
             const int16_t* st = hme_state ? hme_state + 25 * (size_t)sbi : nullptr;
             const bool carried = st && list_index == 1 && st[24];
@@ -915,12 +903,8 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
                     const uint8_t* s = pool + cur.sixteenth_offset + (size_t)(16 + o_y) * cur.sixteenth_stride + 16 + o_x;
                     const uint8_t* r = pool + ref.sixteenth_offset + (size_t)(16 + o_y + yo) * ref.sixteenth_stride + 16 + o_x + xo;
                     int bx, by;
-                    if (sb_w == 64)
-                        wave_sad_loop_l0(s, cur.sixteenth_stride * 2, r, ref.sixteenth_stride, sw, shh, lane, wlds, kHmeLdsPerWave, &sad0,
-                                         &bx, &by, sh.src0);
-                    else
-                        wave_sad_loop_generic(s, cur.sixteenth_stride * 2, r, ref.sixteenth_stride * 2, (sb_h >> 2) >> 1, sb_w >> 2,
-                                              ref.sixteenth_stride, sw, shh, lane, &sad0, &bx, &by);
+                    hme_level0_search(s, cur.sixteenth_stride * 2, r, ref.sixteenth_stride, (int)(sb_w >> 2), sw, shh, lane, wlds, sh.src0, &sad0,
+                                      &bx, &by);
                     x0 = s16(s16(bx + xo) * 4);
                     y0 = s16(s16(by + yo) * 4);
                 }
@@ -934,17 +918,8 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
                     const uint8_t* s = pool + cur.quarter_offset + (size_t)(32 + o_y) * cur.quarter_stride + 32 + o_x;
                     const uint8_t* r = pool + ref.quarter_offset + (size_t)(32 + o_y + yo) * ref.quarter_stride + 32 + o_x + xo;
                     int bx, by;
-                    if (sb_w == 64 && sw == 16 && shh == 16)
-                        wave_sad_loop_fixed<32, 16, 16, 16>(r, ref.quarter_stride, lane, wlds, sh.src1, &sad1, &bx, &by);
-                    else if (sb_w == 64 && sw * shh <= 4096)
-                        wave_sad_loop_lds<32, true>(s, cur.quarter_stride * 2, r, ref.quarter_stride, 16, sw, shh, lane, wlds,
-                                                    kHmeLdsPerWave, &sad1, &bx, &by, sh.src1);
-                    else if (sb_w == 64)
-                        wave_sad_loop_lds<32>(s, cur.quarter_stride * 2, r, ref.quarter_stride, 16, sw, shh, lane, wlds,
-                                              kHmeLdsPerWave, &sad1, &bx, &by, sh.src1);
-                    else
-                        wave_sad_loop_generic(s, cur.quarter_stride * 2, r, ref.quarter_stride * 2, (sb_h >> 1) >> 1, sb_w >> 1,
-                                              ref.quarter_stride, sw, shh, lane, &sad1, &bx, &by);
+                    hme_level_search<32, 16, 16, 16>(s, cur.quarter_stride * 2, r, ref.quarter_stride, (int)(sb_w >> 1), sw, shh, lane, wlds,
+                                                     sh.src1, &sad1, &bx, &by);
                     x1 = s16(s16(bx + xo) * 2);
                     y1 = s16(s16(by + yo) * 2);
                 }
@@ -956,17 +931,8 @@ __device__ __forceinline__ void hme_center_sb(const uint8_t* __restrict__ pool, 
                     clip_window(xo, yo, sw, shh, ox, oy, 63, 63, ref.width, ref.height);
                     const uint8_t* r = ref_full + (size_t)(oy + yo) * ref.full_stride + ox + xo;
                     int bx, by;
-                    if (sb_w == 64 && sw == 8 && shh == 8)
-                        wave_sad_loop_fixed<64, 32, 8, 8>(r, ref.full_stride, lane, wlds, sh.src2, &sad2, &bx, &by);
-                    else if (sb_w == 64 && sw * shh <= 4096)
-                        wave_sad_loop_lds<64, true>(src, cur.full_stride * 2, r, ref.full_stride, 32, sw, shh, lane, wlds,
-                                                    kHmeLdsPerWave, &sad2, &bx, &by, sh.src2);
-                    else if (sb_w == 64)
-                        wave_sad_loop_lds<64>(src, cur.full_stride * 2, r, ref.full_stride, 32, sw, shh, lane, wlds,
-                                              kHmeLdsPerWave, &sad2, &bx, &by, sh.src2);
-                    else
-                        wave_sad_loop_generic(src, cur.full_stride * 2, r, ref.full_stride * 2, sb_h >> 1, sb_w, ref.full_stride, sw,
-                                              shh, lane, &sad2, &bx, &by);
+                    hme_level_search<64, 32, 8, 8>(src, cur.full_stride * 2, r, ref.full_stride, (int)sb_w, sw, shh, lane, wlds, sh.src2, &sad2,
+                                                   &bx, &by);
                     x2 = s16(bx + xo);
                     y2 = s16(by + yo);
                 }
