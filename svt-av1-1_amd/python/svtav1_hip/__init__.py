@@ -1,1315 +1,33 @@
 """ctypes binding of libsvtav1_hip.so (the C ABI in include/svtav1_hip.h) for tests and bench.py.
 
-The product is the shared library; this module only marshals numpy / torch device pointers into it.
+The product is the shared library; this package only marshals numpy / torch device pointers into it.
 There is no Python or CPU fallback: if the library is missing, import of `lib()` raises.
+
+Signatures come from the header (_abi).  One module per family of the header holds its descriptors, dtypes, constants, helpers and the
+Context methods of that family; everything public is re-exported here.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-
-import numpy as np
-
-_PKG_ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
-# SVTAV1_HIP_LIB: A/B tooling only (tools/kernel_times.py loads experimental builds of the library side by side)
-LIB_PATH = os.environ.get("SVTAV1_HIP_LIB") or os.path.join(_PKG_ROOT, "libsvtav1_hip.so")
-
-NUM_SQ_PU = 85
-MAX_SAD_VALUE = 128 * 128 * 255
-
-u8p = C.POINTER(C.c_uint8)
-u32p = C.POINTER(C.c_uint32)
-
-
-class FullpelDesc(C.Structure):
-    _fields_ = [("src_offset", C.c_int32), ("ref_offset", C.c_int32), ("x_search_area_origin", C.c_int32),
-                ("y_search_area_origin", C.c_int32), ("search_area_width", C.c_int32), ("search_area_height", C.c_int32)]
-
-
-_lib = None
+from ._core import (LIB_PATH, OPT_CONVOLVE_VALU, OPT_SADLOOP_GENERIC, OPT_TQ_MAX_WORKGROUPS, ContextCore, SvtHipError, lib, u8p,
+                    u32p)
+from ._me import (FRACTIONAL_FULL_SAD_SEARCH, FRACTIONAL_SSD_SEARCH, FRACTIONAL_SUB_SAD_SEARCH, HME_LEVEL0_MULTIPLIER, HME_MAX_JOBS,
+                  MAX_SAD_VALUE, ME_CU_RESULT_DTYPE, NUM_SQ_PU, FullpelDesc, MeCuResult, MeParams, MotionEstimation, PaPictureDesc, SbOrigin,
+                  build_picture_pool, default_me_params, make_fullpel_desc, sb_origins, shard_sb_rows)
+from ._tq import (COEFF_RATE_DESC_DTYPE, COEFF_RATE_TABLES_DTYPE, ITXFM_DESC_DTYPE, LV_MAP_COEFF_COST_DTYPE, QUANT_DESC_DTYPE,
+                  TU_DESC_DTYPE, TU_RECON_SCRATCH, TX_SIZES_WH, TXFM_DESC_DTYPE, TransformQuant, TuBatcher, TuResult, TxSearchResult,
+                  TxSearchTu, tx_search_type_mask, valid_tx_types)
+from ._analysis import OisParams, PictureAnalysis
+from ._pred import (AV1_BLOCK_SIZES_WH, BI_PRED, CONVOLVE_COMPOUND_DESC_DTYPE, CONVOLVE_DESC_DTYPE, INTER_PU_DESC_DTYPE, INTRA_DESC_DTYPE,
+                    UNI_PRED_LIST_0, UNI_PRED_LIST_1, WARP_AFFINE, WARP_BLOCK_SIZES_WH, WARP_PU_DESC_DTYPE, WARP_ROTZOOM, InterPlanes,
+                    Prediction)
+from ._cfl import CFL_DECISION_DTYPE, CFL_DECISION_JOB_DTYPE, CFL_DESC_DTYPE, CFL_LUMA_SIZES_WH, Cfl
+from ._deblock import LF_MI_DTYPE, Deblocking, LfPicture, make_lf_picture
+from ._cdef import CDEF_PICK_MAX_FB, CDEF_RESULT_DTYPE, Cdef, CdefPicture, cdef_filter_blocks, make_cdef_picture
+from ._restoration import (RESTORE_NONE, RESTORE_SGRPROJ, RESTORE_WIENER, SGRPROJ_DETAIL_DTYPE, SGRPROJ_PARAMS, WIENER_WALK_STATE_DTYPE,
+                           LrPicture, Restoration, lr_unit_geometry, lr_unit_sizes, lr_workspace_bytes, make_lr_picture,
+                           sgrproj_walk_max_trials, sgrproj_workspace_bytes, wiener_walk_max_trials)
+from ._host import ME_CU_RESULT_REF_DTYPE, HostForms, HostPicture
 
 
-def lib() -> C.CDLL:
-    """Load libsvtav1_hip.so (built in-tree by `make -C svt-av1-1_amd` / __graft_entry__.build())."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} not built: run `make -C svt-av1-1_amd` (there is no CPU fallback)")
-    # The PyTorch wheel bundles its own libamdhip64/libhsa-runtime64.  Two HIP runtimes in one process
-    # cannot both own the GPU (measured: loading this library first makes torch report "No HIP GPUs"),
-    # so when torch is installed it is imported first and this library binds to the runtime torch loaded.
-    # A C host (the real integration) links the system ROCm runtime and never sees torch.
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = C.CDLL(LIB_PATH)
-    L.svthip_last_error.restype = C.c_char_p
-    L.svthip_create.restype = C.c_int32
-    L.svthip_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
-    L.svthip_destroy.restype = None
-    L.svthip_destroy.argtypes = [C.c_void_p]
-    L.svthip_stream.restype = C.c_void_p
-    L.svthip_stream.argtypes = [C.c_void_p]
-    L.svthip_synchronize.restype = C.c_int32
-    L.svthip_synchronize.argtypes = [C.c_void_p]
-    L.svthip_set_option.restype = C.c_int32
-    L.svthip_set_option.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-    L.svthip_reserve.restype = C.c_int32
-    L.svthip_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32]
-    L.svthip_me_fullpel_search.restype = C.c_int32
-    L.svthip_me_fullpel_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
-                                           C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.svthip_me_fullpel_search_dev.restype = C.c_int32
-    L.svthip_me_fullpel_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
-                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_me_fullpel_search_time_dev.restype = C.c_int32
-    L.svthip_me_fullpel_search_time_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
-                                                    C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
-                                                    C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
-    L.svthip_me_hme_search_center_dev.restype = C.c_int32
-    L.svthip_me_hme_search_center_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
-                                                  C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]
-    L.svthip_me_hme_search_center_batch_dev.restype = C.c_int32
-    L.svthip_me_hme_search_center_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                        C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_motion_estimate_picture_dev.restype = C.c_int32
-    L.svthip_motion_estimate_picture_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p]
-    L.svthip_me_fullpel_search209_dev.restype = C.c_int32
-    L.svthip_me_fullpel_search209_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
-                                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_motion_estimate_batch_dev.restype = C.c_int32
-    L.svthip_motion_estimate_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                   C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p]
-    L.svthip_me_subpel_refine_dev.restype = C.c_int32
-    L.svthip_me_subpel_refine_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
-                                              C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_me_bipred_pack_dev.restype = C.c_int32
-    L.svthip_me_bipred_pack_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                            C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
-    L.svthip_me_subpel_refine209_dev.restype = C.c_int32
-    L.svthip_me_subpel_refine209_dev.argtypes = L.svthip_me_subpel_refine_dev.argtypes
-    L.svthip_me_subpel_search_dev.restype = C.c_int32
-    L.svthip_me_subpel_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
-                                              C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_me_bipred_pack209_dev.restype = C.c_int32
-    L.svthip_me_bipred_pack209_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                               C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.svthip_motion_estimate209_batch_dev.restype = C.c_int32
-    L.svthip_motion_estimate209_batch_dev.argtypes = L.svthip_motion_estimate_batch_dev.argtypes
-    L.svthip_quantize_b_batch_dev.restype = C.c_int32
-    L.svthip_quantize_b_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_fwd_txfm2d_batch_dev.restype = C.c_int32
-    L.svthip_fwd_txfm2d_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                              C.c_void_p, C.c_void_p]
-    L.svthip_inv_txfm2d_add_batch_dev.restype = C.c_int32
-    L.svthip_inv_txfm2d_add_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                  C.c_uint32, C.c_void_p, C.c_void_p]
-    L.svthip_encode_tu16_batch_dev.restype = C.c_int32
-    L.svthip_encode_tu16_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                               C.c_uint32] + [C.c_void_p] * 9
-    L.svthip_encode_tu_batch_dev.restype = C.c_int32
-    L.svthip_encode_tu_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                             C.c_uint32] + [C.c_void_p] * 9
-    L.svthip_pa_derive_planes_dev.restype = C.c_int32
-    L.svthip_pa_derive_planes_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p]
-    L.svthip_open_loop_intra_search_batch_dev.restype = C.c_int32
-    L.svthip_open_loop_intra_search_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
-                                                          C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_pad_plane_dev.restype = C.c_int32
-    L.svthip_pad_plane_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.svthip_av1_convolve_sr_batch_dev.restype = C.c_int32
-    L.svthip_av1_convolve_sr_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                   C.c_uint32, C.c_void_p]
-    L.svthip_av1_convolve_compound_batch_dev.restype = C.c_int32
-    L.svthip_av1_convolve_compound_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.svthip_av1_highbd_convolve_batch_dev.restype = C.c_int32
-    L.svthip_av1_highbd_convolve_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                       C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.svthip_av1_inter_pred_batch_dev.restype = C.c_int32
-    L.svthip_av1_inter_pred_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                  C.c_void_p]
-    L.svthip_av1_highbd_inter_pred_batch_dev.restype = C.c_int32
-    L.svthip_av1_highbd_inter_pred_batch_dev.argtypes = L.svthip_av1_inter_pred_batch_dev.argtypes[:-1] + [C.c_uint32, C.c_void_p]
-    L.svthip_av1_warped_pred_batch_dev.restype = C.c_int32
-    L.svthip_av1_warped_pred_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                   C.c_uint32, C.c_void_p]
-    L.svthip_av1_highbd_warped_pred_batch_dev.restype = C.c_int32
-    L.svthip_av1_highbd_warped_pred_batch_dev.argtypes = L.svthip_av1_warped_pred_batch_dev.argtypes[:-1] + [C.c_uint32, C.c_void_p]
-    L.svthip_av1_intra_pred_batch_dev.restype = C.c_int32
-    L.svthip_av1_intra_pred_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p]
-    L.svthip_av1_highbd_intra_pred_batch_dev.restype = C.c_int32
-    L.svthip_av1_highbd_intra_pred_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                         C.c_void_p]
-    L.svthip_av1_cfl_pred_batch_dev.restype = C.c_int32
-    L.svthip_av1_cfl_pred_batch_dev.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.svthip_av1_highbd_cfl_pred_batch_dev.restype = C.c_int32
-    L.svthip_av1_highbd_cfl_pred_batch_dev.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.svthip_av1_cfl_alpha_candidates_batch_dev.restype = C.c_int32
-    L.svthip_av1_cfl_alpha_candidates_batch_dev.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.svthip_cfl_alpha_decision_batch_dev.restype = C.c_int32
-    L.svthip_cfl_alpha_decision_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
-                                                      C.c_void_p, C.c_void_p]
-    for name, args in (("svthip_av1_loop_filter_frame_dev", [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
-                       ("svthip_av1_highbd_loop_filter_frame_dev", [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p]),
-                       ("svthip_av1_loop_filter_sse_table_dev", [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
-                       ("svthip_av1_highbd_loop_filter_sse_table_dev",
-                        [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
-                       ("svthip_lf_level_walk_dev", [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
-                       ("svthip_av1_pick_filter_level_dev", [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4),
-                       ("svthip_av1_highbd_pick_filter_level_dev",
-                        [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4)):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = args
-    L.svthip_inter_pred_refused.restype = C.c_int32
-    V, U = C.c_void_p, C.c_uint32
-    for name, args in (("svthip_av1_wiener_stats_dev", [V, V, U, U] + [V] * 6), ("svthip_av1_highbd_wiener_stats_dev", [V, V, U, U, U] + [V] * 6),
-                       ("svthip_wiener_solve_dev", [V, V, V, U, U, U, V, V, V]),
-                       ("svthip_av1_wiener_trial_sse_dev", [V, V, U, U, V, V, V, V]), ("svthip_av1_highbd_wiener_trial_sse_dev", [V, V, U, U, U, V, V, V, V]),
-                       ("svthip_wiener_walk_init_dev", [V, V, V, V, U, U, U, V]), ("svthip_wiener_walk_step_dev", [V, V, V, U, U, V, V]),
-                       ("svthip_av1_search_wiener_dev", [V, V, U, U, U, U] + [V] * 6),
-                       ("svthip_av1_highbd_search_wiener_dev", [V, V, U, U, U, U, U] + [V] * 6),
-                       ("svthip_av1_loop_restoration_filter_frame_dev", [V, V, V, V, U, U, V, V, V]),
-                       ("svthip_av1_highbd_loop_restoration_filter_frame_dev", [V, V, V, V, U, U, U, V, V, V]),
-                       ("svthip_av1_selfguided_restoration_dev", [V, V, U, U, V, V, U, V]),
-                       ("svthip_av1_highbd_selfguided_restoration_dev", [V, V, U, U, U, V, V, U, V]),
-                       ("svthip_sgrproj_solve_dev", [V, V, V, V, U, V, V, V]), ("svthip_sgrproj_walk_table_dev", [V, V, V, V, U, V, V, V, V]),
-                       ("svthip_av1_search_sgrproj_dev", [V, V, U, U] + [V] * 5), ("svthip_av1_highbd_search_sgrproj_dev", [V, V, U, U, U] + [V] * 5),
-                       ("svthip_av1_sgrproj_trial_sse_dev", [V, V, U, U, V, V, V, V]),
-                       ("svthip_av1_highbd_sgrproj_trial_sse_dev", [V, V, U, U, U, V, V, V, V]),
-                       ("svthip_av1_lr_filter_frame_dev", [V, V, V, V, U, U, V, V, V, V]),
-                       ("svthip_av1_highbd_lr_filter_frame_dev", [V, V, V, V, U, U, U, V, V, V, V])):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = args
-    for name, args in (("svthip_av1_cdef_search_mse_dev", [V, V, U, V, V, V]), ("svthip_av1_highbd_cdef_search_mse_dev", [V, V, U, U, V, V, V]),
-                       ("svthip_cdef_pick_strengths_dev", [V, V, V, U, U, U, U, V, V, V]),
-                       ("svthip_av1_cdef_search_dev", [V, V, U, V, V, V, V, V]), ("svthip_av1_highbd_cdef_search_dev", [V, V, U, U, V, V, V, V, V]),
-                       ("svthip_av1_cdef_frame_dev", [V, V, V, V, U, U, V]), ("svthip_av1_highbd_cdef_frame_dev", [V, V, V, V, U, U, U, V]),
-                       ("svthip_cdef_dist_8x8_batch_dev", [V, V, V, U, U, V, V])):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = args
-    L.svthip_lr_unit_geometry.restype = C.c_uint32
-    L.svthip_lr_unit_geometry.argtypes = [U, U, V, V, V]
-    L.svthip_lr_workspace_bytes.restype = C.c_size_t
-    L.svthip_lr_workspace_bytes.argtypes = [U]
-    L.svthip_wiener_walk_max_trials.restype = C.c_uint32
-    L.svthip_wiener_walk_max_trials.argtypes = [U]
-    L.svthip_sgrproj_workspace_bytes.restype = C.c_size_t
-    L.svthip_sgrproj_workspace_bytes.argtypes = [U, U]
-    L.svthip_sgrproj_walk_max_trials.restype = C.c_uint32
-    L.svthip_sgrproj_walk_max_trials.argtypes = []
-    L.svthip_inter_pred_refused.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    L.svthip_motion_estimate_picture.restype = C.c_int32
-    L.svthip_motion_estimate_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32,
-                                                 C.c_void_p]
-    L.svthip_open_loop_intra_search_picture.restype = C.c_int32
-    L.svthip_open_loop_intra_search_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.svthip_encode_tu_batch.restype = C.c_int32
-    L.svthip_encode_tu_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32,
-                                         C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_size_t] + [C.c_void_p] * 6
-    L.svthip_sad_loop_batch_dev.restype = C.c_int32
-    L.svthip_sad_loop_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
-                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_tu_batcher_create.restype = C.c_int32
-    L.svthip_tu_batcher_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-    L.svthip_tu_batcher_destroy.restype = None
-    L.svthip_tu_batcher_destroy.argtypes = [C.c_void_p]
-    L.svthip_tu_batcher_begin.restype = C.c_int32
-    L.svthip_tu_batcher_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.svthip_tu_batcher_add.restype = C.c_int32
-    L.svthip_tu_batcher_add.argtypes = [C.c_void_p] + [C.c_uint32] * 10 + [C.POINTER(C.c_uint32)]
-    L.svthip_tu_batcher_flush.restype = C.c_int32
-    L.svthip_tu_batcher_flush.argtypes = [C.c_void_p]
-    L.svthip_tu_batcher_result.restype = C.c_int32
-    L.svthip_tu_batcher_result.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-    L.svthip_tu_batcher_read_coeffs.restype = C.c_int32
-    L.svthip_tu_batcher_read_coeffs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.svthip_tu_batcher_pools.restype = C.c_int32
-    L.svthip_tu_batcher_pools.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-    L.svthip_coeff_rate_batch_dev.restype = C.c_int32
-    L.svthip_coeff_rate_batch_dev.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.svthip_tu_batcher_set_tx_search.restype = C.c_int32
-    L.svthip_tu_batcher_set_tx_search.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.svthip_tu_batcher_add_tx_search.restype = C.c_int32
-    L.svthip_tu_batcher_add_tx_search.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
-    L.svthip_tu_batcher_tx_search_result.restype = C.c_int32
-    L.svthip_tu_batcher_tx_search_result.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-    L.svthip_tx_search_type_mask.restype = C.c_uint16
-    L.svthip_tx_search_type_mask.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32]
-    _lib = L
-    return L
-
-
-OPT_SADLOOP_GENERIC = 0
-OPT_CONVOLVE_VALU = 1
-OPT_TQ_MAX_WORKGROUPS = 2
-
-
-class SvtHipError(RuntimeError):
-    pass
-
-
-def _check(rc: int):
-    if rc != 0:
-        raise SvtHipError(f"svthip error 0x{rc & 0xFFFFFFFF:08x}: {lib().svthip_last_error().decode()}")
-
-
-class Context:
+class Context(ContextCore, MotionEstimation, TransformQuant, PictureAnalysis, Prediction, Cfl, Deblocking, Cdef, Restoration, HostForms):
     """One svthip_ctx (stream + scratch), the analogue of one MeContext_t."""
-
-    def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
-        _check(lib().svthip_create(device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().svthip_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def stream(self) -> int:
-        return lib().svthip_stream(self._h)
-
-    def synchronize(self):
-        _check(lib().svthip_synchronize(self._h))
-
-    def set_option(self, option: int, value: int):
-        """svthip_set_option: kernel-selection override of this context (OPT_SADLOOP_GENERIC / OPT_CONVOLVE_VALU / OPT_TQ_MAX_WORKGROUPS)."""
-        _check(lib().svthip_set_option(self._h, option, value))
-
-    def reserve(self, width: int, height: int, n_pu: int = 85, n_jobs: int = 1, host_forms: bool = False):
-        _check(lib().svthip_reserve(self._h, width, height, n_pu, n_jobs, int(host_forms)))
-
-    # -- host-pointer form (numpy in / numpy out) ------------------------------------------------
-    def fullpel_search(self, src_plane: np.ndarray, ref_plane: np.ndarray, desc: np.ndarray):
-        """desc int32 [n,6] -> (best_sad [n,85] uint32, best_mv [n,85] uint32)."""
-        assert src_plane.dtype == np.uint8 and ref_plane.dtype == np.uint8
-        src_plane = np.ascontiguousarray(src_plane)
-        ref_plane = np.ascontiguousarray(ref_plane)
-        desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 6)
-        n = desc.shape[0]
-        sad = np.zeros((n, NUM_SQ_PU), dtype=np.uint32)
-        mv = np.zeros((n, NUM_SQ_PU), dtype=np.uint32)
-        _check(lib().svthip_me_fullpel_search(self._h, src_plane.ctypes.data, src_plane.nbytes, src_plane.shape[1],
-                                               ref_plane.ctypes.data, ref_plane.nbytes, ref_plane.shape[1],
-                                               desc.ctypes.data, n, sad.ctypes.data, mv.ctypes.data))
-        return sad, mv
-
-    # -- device-pointer form (raw addresses, e.g. torch tensors' data_ptr()) -----------------------
-    def fullpel_search_dev(self, d_src: int, src_stride: int, d_ref: int, ref_stride: int, d_desc: int, n_sb: int,
-                           max_sw: int, max_sh: int, d_sad: int, d_mv: int, stream: int | None = None):
-        _check(lib().svthip_me_fullpel_search_dev(self._h, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw,
-                                                  max_sh, d_sad, d_mv, stream))
-
-    def fullpel_search_time_dev(self, d_src: int, src_stride: int, d_ref: int, ref_stride: int, d_desc: int, n_sb: int,
-                                max_sw: int, max_sh: int, d_sad: int, d_mv: int, iters: int) -> float:
-        ms = C.c_float(0)
-        _check(lib().svthip_me_fullpel_search_time_dev(self._h, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb,
-                                                       max_sw, max_sh, d_sad, d_mv, iters, C.byref(ms)))
-        return ms.value
-
-
-def _hme_search_center_dev(self, d_pool, cur, ref, params, list_index, d_sb, n_sb, d_l0_mv64, d_desc, d_center=None,
-                           d_state=None, stream=None, l0_mv_stride=1):
-    """cur/ref: PaPictureDesc, params: MeParams (host structs); the rest are device addresses."""
-    _check(lib().svthip_me_hme_search_center_dev(self._h, d_pool, C.byref(cur), C.byref(ref), C.byref(params), list_index,
-                                                 d_sb, n_sb, d_l0_mv64, l0_mv_stride, d_desc, d_center, d_state, stream))
-
-
-def _hme_search_center_batch_dev(self, d_pool, curs, refs, params, list_index, d_sb, n_sb, d_l0_mv64, d_desc, d_center=None,
-                                 d_state=None, stream=None, l0_mv_stride=1):
-    """curs/refs: sequences of PaPictureDesc (one pair per job); per-SB device arrays hold the jobs back to back."""
-    n = len(curs)
-    ca = (PaPictureDesc * n)(*curs)
-    ra = (PaPictureDesc * n)(*refs)
-    _check(lib().svthip_me_hme_search_center_batch_dev(self._h, d_pool, ca, ra, n, C.byref(params), list_index, d_sb, n_sb, d_l0_mv64,
-                                                       l0_mv_stride, d_desc, d_center, d_state, stream))
-
-
-def _motion_estimate_picture_dev(self, d_pool, cur, ref0, ref1, params, d_sb, n_sb, d_out, use_subpel=True, cu8x8_mode=0,
-                                 d_list_sad=None, d_list_mv=None, stream=None):
-    """Whole-picture ME (MotionEstimateLcu over all SBs): ref1=None for P pictures."""
-    _check(lib().svthip_motion_estimate_picture_dev(self._h, d_pool, C.byref(cur), C.byref(ref0),
-                                                    C.byref(ref1) if ref1 is not None else None, C.byref(params),
-                                                    int(use_subpel), int(cu8x8_mode), d_sb, n_sb, d_out, d_list_sad, d_list_mv,
-                                                    stream))
-
-
-Context.motion_estimate_picture_dev = _motion_estimate_picture_dev
-
-
-def _motion_estimate_batch_dev(self, d_pool, curs, refs0, refs1, params, d_sb, n_sb, d_out, use_subpel=True, cu8x8_mode=0,
-                               d_list_sad=None, d_list_mv=None, stream=None):
-    """Whole-picture ME of len(curs) pictures in one call; refs1=None for P pictures."""
-    n = len(curs)
-    ca, r0 = (PaPictureDesc * n)(*curs), (PaPictureDesc * n)(*refs0)
-    r1 = (PaPictureDesc * n)(*refs1) if refs1 is not None else None
-    _check(lib().svthip_motion_estimate_batch_dev(self._h, d_pool, ca, r0, r1, n, C.byref(params), int(use_subpel), int(cu8x8_mode),
-                                                  d_sb, n_sb, d_out, d_list_sad, d_list_mv, stream))
-
-
-Context.motion_estimate_batch_dev = _motion_estimate_batch_dev
-
-
-def _fullpel_search209_dev(self, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh, d_sad, d_mv, stream=None):
-    """209-PU full-pel search (squares + rectangles); d_sad / d_mv: [n_sb][209] uint32 device arrays."""
-    _check(lib().svthip_me_fullpel_search209_dev(self._h, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh, d_sad, d_mv,
-                                                 stream))
-
-
-Context.fullpel_search209_dev = _fullpel_search209_dev
-Context.hme_search_center_dev = _hme_search_center_dev
-Context.hme_search_center_batch_dev = _hme_search_center_batch_dev
-
-
-def _subpel_refine_dev(self, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh, d_sad, d_mv, disable_8x8=False,
-                       stream=None):
-    _check(lib().svthip_me_subpel_refine_dev(self._h, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh,
-                                             int(disable_8x8), d_sad, d_mv, stream))
-
-
-Context.subpel_refine_dev = _subpel_refine_dev
-
-
-def _bipred_pack_dev(self, d_src, src_stride, d_ref0, ref0_stride, d_desc0, d_ref1, ref1_stride, d_desc1, n_sb, max_sw, max_sh,
-                     d_sad0, d_mv0, d_sad1, d_mv1, n_lists, d_out, bipred_8x8=True, stream=None):
-    _check(lib().svthip_me_bipred_pack_dev(self._h, d_src, src_stride, d_ref0, ref0_stride, d_desc0, d_ref1, ref1_stride, d_desc1,
-                                           n_sb, max_sw, max_sh, d_sad0, d_mv0, d_sad1, d_mv1, n_lists, int(bipred_8x8), d_out,
-                                           stream))
-
-
-Context.bipred_pack_dev = _bipred_pack_dev
-
-
-def _subpel_refine209_dev(self, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh, d_sad, d_mv, disable_8x8=False,
-                          stream=None):
-    """Sub-pel refinement of all 209 PUs; d_sad / d_mv: [n_sb][209] uint32 device arrays (ME-buffer order), in place."""
-    _check(lib().svthip_me_subpel_refine209_dev(self._h, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh,
-                                                int(disable_8x8), d_sad, d_mv, stream))
-
-
-FRACTIONAL_SUB_SAD_SEARCH, FRACTIONAL_FULL_SAD_SEARCH, FRACTIONAL_SSD_SEARCH = 0, 1, 2  # MeContext_t::fractionalSearchMethod
-
-
-def _subpel_search_dev(self, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh, d_sad, d_mv, method, all_pu,
-                       disable_8x8=False, stream=None):
-    """The refinement under one of the reference's fractional search methods; d_sad / d_mv: [n_sb][209 if all_pu else 85], in place."""
-    _check(lib().svthip_me_subpel_search_dev(self._h, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh,
-                                             int(disable_8x8), int(all_pu), int(method), d_sad, d_mv, stream))
-
-
-Context.subpel_search_dev = _subpel_search_dev
-
-
-def _bipred_pack209_dev(self, d_src, src_stride, d_ref0, ref0_stride, d_desc0, d_ref1, ref1_stride, d_desc1, n_sb, max_sw, max_sh,
-                        d_sad0, d_mv0, d_sad1, d_mv1, n_lists, d_out, stream=None):
-    """Bi-prediction + packing over all 209 PUs; d_out: [n_sb][209] ME_CU_RESULT_DTYPE in raster PU order."""
-    _check(lib().svthip_me_bipred_pack209_dev(self._h, d_src, src_stride, d_ref0, ref0_stride, d_desc0, d_ref1, ref1_stride, d_desc1,
-                                              n_sb, max_sw, max_sh, d_sad0, d_mv0, d_sad1, d_mv1, n_lists, d_out, stream))
-
-
-def _motion_estimate209_batch_dev(self, d_pool, curs, refs0, refs1, params, d_sb, n_sb, d_out, use_subpel=True, cu8x8_mode=0,
-                                  d_list_sad=None, d_list_mv=None, stream=None):
-    """Whole-picture ME in the 209-PU mode of len(curs) pictures in one call; refs1=None for P pictures."""
-    n = len(curs)
-    ca, r0 = (PaPictureDesc * n)(*curs), (PaPictureDesc * n)(*refs0)
-    r1 = (PaPictureDesc * n)(*refs1) if refs1 is not None else None
-    _check(lib().svthip_motion_estimate209_batch_dev(self._h, d_pool, ca, r0, r1, n, C.byref(params), int(use_subpel), int(cu8x8_mode),
-                                                     d_sb, n_sb, d_out, d_list_sad, d_list_mv, stream))
-
-
-Context.subpel_refine209_dev = _subpel_refine209_dev
-Context.bipred_pack209_dev = _bipred_pack209_dev
-Context.motion_estimate209_batch_dev = _motion_estimate209_batch_dev
-
-
-def _quantize_b_batch_dev(self, d_coeff, d_desc, n_tu, d_qparams, d_iscan, d_qcoeff, d_dqcoeff, d_eob, stream=None):
-    _check(lib().svthip_quantize_b_batch_dev(self._h, d_coeff, d_desc, n_tu, d_qparams, d_iscan, d_qcoeff, d_dqcoeff, d_eob, stream))
-
-
-Context.quantize_b_batch_dev = _quantize_b_batch_dev
-
-
-def _fwd_txfm2d_batch_dev(self, d_residual, d_desc, n_tu, tx_width, tx_height, bit_depth, d_coeff, stream=None):
-    _check(lib().svthip_fwd_txfm2d_batch_dev(self._h, d_residual, d_desc, n_tu, tx_width, tx_height, bit_depth, d_coeff, stream))
-
-
-Context.fwd_txfm2d_batch_dev = _fwd_txfm2d_batch_dev
-
-
-def _inv_txfm2d_add_batch_dev(self, d_coeff, d_desc, n_tu, tx_width, tx_height, bit_depth, recon_16bit, d_recon, stream=None):
-    _check(lib().svthip_inv_txfm2d_add_batch_dev(self._h, d_coeff, d_desc, n_tu, tx_width, tx_height, bit_depth, int(recon_16bit),
-                                                 d_recon, stream))
-
-
-Context.inv_txfm2d_add_batch_dev = _inv_txfm2d_add_batch_dev
-
-
-def _encode_tu_batch_dev(self, d_src, d_pred, d_recon, d_desc, n_tu, tx_width, tx_height, d_qparams, d_iscan, d_coeff, d_qcoeff,
-                         d_dqcoeff, d_eob, d_energy=None, d_dist=None, stream=None, planes_16bit=False):
-    fn = lib().svthip_encode_tu16_batch_dev if planes_16bit else lib().svthip_encode_tu_batch_dev
-    _check(fn(self._h, d_src, d_pred, d_recon, d_desc, n_tu, tx_width, tx_height, d_qparams, d_iscan,
-              d_coeff, d_qcoeff, d_dqcoeff, d_eob, d_energy, d_dist, stream))
-
-
-Context.encode_tu_batch_dev = _encode_tu_batch_dev
-
-
-def _pa_derive_planes_dev(self, d_pool, pics, want_quarter=True, want_sixteenth=True, stream=None):
-    """Pad the full-resolution planes and build the 1/4 and 1/16 planes of `pics` (PaPictureDesc list) inside the device pool."""
-    n = len(pics)
-    _check(lib().svthip_pa_derive_planes_dev(self._h, d_pool, (PaPictureDesc * n)(*pics), n, int(want_quarter), int(want_sixteenth), stream))
-
-
-def _pad_plane_dev(self, d_plane, stride, width, height, pad_w, pad_h, sample_bytes=1, stream=None):
-    """generate_padding / generate_padding16_bit of one device plane in place (all quantities in samples)."""
-    _check(lib().svthip_pad_plane_dev(self._h, d_plane, stride, width, height, pad_w, pad_h, sample_bytes, stream))
-
-
-HME_MAX_JOBS = 32  # SVTHIP_HME_MAX_JOBS: pictures per kernel launch of the batch entries
-
-
-class OisParams(C.Structure):
-    _fields_ = [("slice_is_intra", C.c_uint8), ("temporal_layer_index", C.c_uint8), ("is_used_as_reference_flag", C.c_uint8),
-                ("input_resolution_4k", C.c_uint8), ("limit_ois_to_dc_mode_flag", C.c_uint8), ("cu8x8_mode", C.c_uint8),
-                ("enc_mode", C.c_uint8), ("reserved", C.c_uint8)]
-
-
-def _open_loop_intra_search_batch_dev(self, d_pool, curs, params, d_sb, n_sb, d_me, me_pu_stride, d_cand, d_total, stream=None):
-    """OpenLoopIntraSearchLcu over len(curs) pictures: d_cand [n][n_sb][85][18] u32 OisCandidate_t words, d_total [n][n_sb][85] u8."""
-    n = len(curs)
-    _check(lib().svthip_open_loop_intra_search_batch_dev(self._h, d_pool, (PaPictureDesc * n)(*curs), n, C.byref(params), d_sb, n_sb,
-                                                         d_me, me_pu_stride, d_cand, d_total, stream))
-
-
-Context.open_loop_intra_search_batch_dev = _open_loop_intra_search_batch_dev
-Context.pa_derive_planes_dev = _pa_derive_planes_dev
-Context.pad_plane_dev = _pad_plane_dev
-
-
-class TuResult(C.Structure):
-    _fields_ = [("distortion", C.c_uint64 * 2), ("three_quad_energy", C.c_uint64), ("coeff_offset", C.c_uint32), ("eob", C.c_uint16),
-                ("tx_size", C.c_uint8), ("tx_type", C.c_uint8)]
-
-
-TU_RECON_SCRATCH = 0xffffffff
-
-
-class TuBatcher:
-    """svthip_tu_batcher: host-side gather / scatter of (TU, tx_type) candidates for the fused T/Q chain."""
-
-    def __init__(self, ctx: "Context", max_candidates: int, max_coeff_samples: int):
-        self._h = C.c_void_p()
-        self._ctx = ctx
-        _check(lib().svthip_tu_batcher_create(ctx._h, max_candidates, max_coeff_samples, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().svthip_tu_batcher_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def begin(self, d_src, d_pred, d_recon, planes_16bit, d_qparams, d_iscan):
-        _check(lib().svthip_tu_batcher_begin(self._h, d_src, d_pred, d_recon, int(planes_16bit), d_qparams, d_iscan))
-
-    def add(self, tx_size, tx_type, src_offset, src_stride, pred_offset, pred_stride, recon_offset, recon_stride, qparam_index, iscan_offset) -> int:
-        h = C.c_uint32(0)
-        _check(lib().svthip_tu_batcher_add(self._h, tx_size, tx_type, src_offset, src_stride, pred_offset, pred_stride, recon_offset, recon_stride,
-                                           qparam_index, iscan_offset, C.byref(h)))
-        return h.value
-
-    def flush(self):
-        _check(lib().svthip_tu_batcher_flush(self._h))
-
-    def result(self, handle) -> TuResult:
-        r = TuResult()
-        _check(lib().svthip_tu_batcher_result(self._h, handle, C.byref(r)))
-        return r
-
-    def read_coeffs(self, handle, n):
-        q = np.zeros(n, np.int32); dq = np.zeros(n, np.int32)
-        _check(lib().svthip_tu_batcher_read_coeffs(self._h, handle, q.ctypes.data, dq.ctypes.data))
-        return q, dq
-
-    def pools(self):
-        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _check(lib().svthip_tu_batcher_pools(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return a.value, b.value, c.value
-
-    def set_tx_search(self, d_tables, iscan_offsets):
-        """d_tables: device address of a COEFF_RATE_TABLES_DTYPE record; iscan_offsets: [19][16] (or 304) iscan-pool offsets"""
-        off = np.ascontiguousarray(np.asarray(iscan_offsets, np.uint32).reshape(19 * 16))
-        _check(lib().svthip_tu_batcher_set_tx_search(self._h, d_tables, off.ctypes.data))
-
-    def add_tx_search(self, tu: "TxSearchTu" = None, **fields) -> int:
-        """one TU of the RD transform-type search (a TxSearchTu, or its fields as keywords); returns the TU handle"""
-        if tu is None:
-            tu = TxSearchTu(**fields)
-        h = C.c_uint32(0)
-        _check(lib().svthip_tu_batcher_add_tx_search(self._h, C.byref(tu), C.byref(h)))
-        return h.value
-
-    def tx_search_result(self, tu_handle) -> "TxSearchResult":
-        r = TxSearchResult()
-        _check(lib().svthip_tu_batcher_tx_search_result(self._h, tu_handle, C.byref(r)))
-        return r
-
-
-# ---- coefficient rate and the RD transform-type search (include/svtav1_hip.h) ----
-LV_MAP_COEFF_COST_DTYPE = np.dtype([("txb_skip_cost", "<i4", (13, 2)), ("base_eob_cost", "<i4", (4, 3)), ("base_cost", "<i4", (42, 4)),
-                                    ("eob_extra_cost", "<i4", (22, 2)), ("dc_sign_cost", "<i4", (3, 2)), ("lps_cost", "<i4", (21, 13))])
-assert LV_MAP_COEFF_COST_DTYPE.itemsize == 2116
-# svthip_coeff_rate_tables: eobFracBits is [7][2] LV_MAP_EOB_COST { eob_cost[2][11] }
-COEFF_RATE_TABLES_DTYPE = np.dtype([("coeffFacBits", LV_MAP_COEFF_COST_DTYPE, (5, 2)), ("eobFracBits", "<i4", (7, 2, 2, 11)),
-                                    ("interTxTypeFacBits", "<i4", (4, 4, 17)), ("intraTxTypeFacBits", "<i4", (3, 4, 13, 17))])
-assert COEFF_RATE_TABLES_DTYPE.itemsize == 34088
-COEFF_RATE_DESC_DTYPE = np.dtype([("coeff_offset", "<u4"), ("iscan_offset", "<u4"), ("tx_type", "u1"), ("plane_type", "u1"),
-                                  ("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("is_inter", "u1"), ("intra_mode", "u1"),
-                                  ("reduced_tx_set", "u1"), ("reserved", "u1")])
-assert COEFF_RATE_DESC_DTYPE.itemsize == 16
-
-
-class TxSearchTu(C.Structure):
-    _fields_ = [("lambda_", C.c_uint64), ("src_offset", C.c_uint32), ("src_stride", C.c_uint32), ("pred_offset", C.c_uint32),
-                ("pred_stride", C.c_uint32), ("qparam_index", C.c_uint32), ("type_mask", C.c_uint16), ("tx_size", C.c_uint8),
-                ("is_inter", C.c_uint8), ("intra_mode", C.c_uint8), ("reduced_tx_set", C.c_uint8), ("txb_skip_ctx", C.c_uint8),
-                ("dc_sign_ctx", C.c_uint8), ("reserved", C.c_uint8 * 4)]
-
-
-assert C.sizeof(TxSearchTu) == 40
-
-
-class TxSearchResult(C.Structure):
-    _fields_ = [("full_cost", C.c_uint64), ("distortion", C.c_uint64 * 2), ("coeff_bits", C.c_uint64), ("candidate", C.c_uint32),
-                ("eob", C.c_uint16), ("tx_type", C.c_uint8), ("reserved", C.c_uint8)]
-
-
-assert C.sizeof(TxSearchResult) == 40
-
-
-def tx_search_type_mask(tx_size: int, is_inter: bool, reduced_tx_set: bool, fast_tx_search: bool) -> int:
-    """the reference's transform-type candidate mask of ProductFullLoopTxSearch (bit t = TxType t)"""
-    return int(lib().svthip_tx_search_type_mask(tx_size, int(bool(is_inter)), int(bool(reduced_tx_set)), int(bool(fast_tx_search))))
-
-
-def _coeff_rate_batch_dev(self, d_tables, d_qcoeff, d_eob, d_iscan, d_desc, n_tu, tx_size, d_bits, stream=None):
-    """Av1TuEstimateCoeffBits of n_tu TUs of one TxSize (COEFF_RATE_DESC_DTYPE descriptors, uint16 eobs) -> uint32 bits per TU"""
-    _check(lib().svthip_coeff_rate_batch_dev(self._h, d_tables, d_qcoeff, d_eob, d_iscan, d_desc, n_tu, tx_size, d_bits, stream))
-
-
-Context.coeff_rate_batch_dev = _coeff_rate_batch_dev
-
-
-CONVOLVE_COMPOUND_DESC_DTYPE = np.dtype([("src0_offset", "<u4"), ("src1_offset", "<u4"), ("dst_offset", "<u4"), ("subpel0", "u1"), ("subpel1", "u1"),
-                                         ("filter_x", "u1"), ("filter_y", "u1")])
-assert CONVOLVE_COMPOUND_DESC_DTYPE.itemsize == 16
-
-
-def _av1_convolve_compound_batch_dev(self, d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_desc, n_blocks, width, height, stream=None):
-    """BI_PRED luma prediction of n_blocks blocks of one size (CONVOLVE_COMPOUND_DESC_DTYPE descriptors; subpel = x | y << 4)."""
-    _check(lib().svthip_av1_convolve_compound_batch_dev(self._h, d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_desc, n_blocks, width,
-                                                        height, stream))
-
-
-Context.av1_convolve_compound_batch_dev = _av1_convolve_compound_batch_dev
-
-
-def _av1_highbd_convolve_batch_dev(self, d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_desc, compound, n_blocks, width, height,
-                                   bit_depth=10, stream=None):
-    """10-bit inter prediction in 16-bit planes (offsets / strides in samples); compound selects the descriptor type."""
-    _check(lib().svthip_av1_highbd_convolve_batch_dev(self._h, d_src0, src0_stride, d_src1, src1_stride, d_dst, dst_stride, d_desc, int(compound),
-                                                      n_blocks, width, height, bit_depth, stream))
-
-
-Context.av1_highbd_convolve_batch_dev = _av1_highbd_convolve_batch_dev
-
-
-def _sad_loop_batch_dev(self, d_src, src_stride, d_ref, ref_stride, ref_stride_raw, d_desc, n_blocks, width, height, sw, sh, d_best_sad, d_best_xy,
-                        stream=None):
-    """SadLoopKernel over n_blocks (src_offset, ref_offset) uint32 pairs; d_best_sad uint32 [n], d_best_xy int16 [n][2] = (x, y) index."""
-    _check(lib().svthip_sad_loop_batch_dev(self._h, d_src, src_stride, d_ref, ref_stride, ref_stride_raw, d_desc, n_blocks, width, height, sw, sh,
-                                           d_best_sad, d_best_xy, stream))
-
-
-Context.sad_loop_batch_dev = _sad_loop_batch_dev
-
-
-CONVOLVE_DESC_DTYPE = np.dtype([("src_offset", "<u4"), ("dst_offset", "<u4"), ("subpel_x", "u1"), ("subpel_y", "u1"), ("filter_x", "u1"),
-                                ("filter_y", "u1"), ("reserved", "<u4")])
-assert CONVOLVE_DESC_DTYPE.itemsize == 16
-# the 22 AV1 block sizes (width, height)
-AV1_BLOCK_SIZES_WH = [(4, 4), (4, 8), (8, 4), (8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16), (32, 32), (32, 64), (64, 32), (64, 64),
-                      (64, 128), (128, 64), (128, 128), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
-
-
-def _av1_convolve_sr_batch_dev(self, d_src, src_stride, d_dst, dst_stride, d_desc, n_blocks, width, height, stream=None):
-    """8-bit single-reference AV1 convolution (2-D / x / y / copy by phase) of n_blocks blocks of one size."""
-    _check(lib().svthip_av1_convolve_sr_batch_dev(self._h, d_src, src_stride, d_dst, dst_stride, d_desc, n_blocks, width, height, stream))
-
-
-Context.av1_convolve_sr_batch_dev = _av1_convolve_sr_batch_dev
-
-
-def make_fullpel_desc(cur, ref, centers=None, search_w=64, search_h=64) -> np.ndarray:
-    """Descriptors for every SB of a picture the way MotionEstimateLcu derives them
-    (Codec/EbMotionEstimation.c:6667-6738): window centred on `centers[sb] = (x, y)` (default 0,0),
-    clipped to the picture, source block at the SB origin."""
-    from . import synth
-
-    nx, ny = cur.sb_grid()
-    out = np.zeros((nx * ny, 6), dtype=np.int32)
-    for sy in range(ny):
-        for sx in range(nx):
-            i = sy * nx + sx
-            ox, oy = sx * 64, sy * 64
-            cx, cy = (0, 0) if centers is None else centers[i]
-            xo, yo, sw, sh = synth.clamp_search_window(ox, oy, int(cx), int(cy), search_w, search_h, cur.width, cur.height)
-            out[i] = [(synth.PAD_FULL + oy) * cur.stride + synth.PAD_FULL + ox,
-                      (synth.PAD_FULL + oy + yo) * ref.stride + synth.PAD_FULL + ox + xo, xo, yo, sw, sh]
-    return out
-
-
-# ------------------------------------------------------------------------------------------------
-# Hierarchical ME: ctypes mirrors of the parameter blocks in include/svtav1_hip.h
-# ------------------------------------------------------------------------------------------------
-class PaPictureDesc(C.Structure):
-    _fields_ = [("full_offset", C.c_int64), ("quarter_offset", C.c_int64), ("sixteenth_offset", C.c_int64),
-                ("full_stride", C.c_uint32), ("quarter_stride", C.c_uint32), ("sixteenth_stride", C.c_uint32),
-                ("width", C.c_uint16), ("height", C.c_uint16)]
-
-
-class MeParams(C.Structure):
-    _fields_ = [("search_area_width", C.c_uint16), ("search_area_height", C.c_uint16),
-                ("number_hme_search_region_in_width", C.c_uint16), ("number_hme_search_region_in_height", C.c_uint16),
-                ("hme_level0_total_search_area_width", C.c_uint16), ("hme_level0_total_search_area_height", C.c_uint16),
-                ("hme_level0_search_area_in_width_array", C.c_uint16 * 2), ("hme_level0_search_area_in_height_array", C.c_uint16 * 2),
-                ("hme_level1_search_area_in_width_array", C.c_uint16 * 2), ("hme_level1_search_area_in_height_array", C.c_uint16 * 2),
-                ("hme_level2_search_area_in_width_array", C.c_uint16 * 2), ("hme_level2_search_area_in_height_array", C.c_uint16 * 2),
-                ("hme_level0_multiplier_x", C.c_uint32), ("hme_level0_multiplier_y", C.c_uint32),
-                ("enable_hme_flag", C.c_uint8), ("enable_hme_level0_flag", C.c_uint8), ("enable_hme_level1_flag", C.c_uint8),
-                ("enable_hme_level2_flag", C.c_uint8), ("temporal_layer_index", C.c_uint8),
-                ("is_used_as_reference_flag", C.c_uint8), ("ref_poc_equal", C.c_uint8), ("reserved", C.c_uint8)]
-
-
-class MeCuResult(C.Structure):
-    _fields_ = [("xMvL0", C.c_int16), ("yMvL0", C.c_int16), ("xMvL1", C.c_int16), ("yMvL1", C.c_int16),
-                ("distortion", C.c_uint32 * 3), ("direction", C.c_uint8 * 3), ("totalMeCandidateIndex", C.c_uint8)]
-
-
-ME_CU_RESULT_DTYPE = np.dtype([("xMvL0", "<i2"), ("yMvL0", "<i2"), ("xMvL1", "<i2"), ("yMvL1", "<i2"), ("distortion", "<u4", 3),
-                               ("direction", "u1", 3), ("totalMeCandidateIndex", "u1")])
-assert ME_CU_RESULT_DTYPE.itemsize == C.sizeof(MeCuResult) == 24
-
-
-QUANT_DESC_DTYPE = np.dtype([("coeff_offset", "<u4"), ("iscan_offset", "<u4"), ("qparam_index", "<u4"), ("n_coeffs", "<u2"),
-                             ("log_scale", "u1"), ("highbd", "u1")])
-assert QUANT_DESC_DTYPE.itemsize == 16
-
-
-TXFM_DESC_DTYPE = np.dtype([("in_offset", "<u4"), ("out_offset", "<u4"), ("in_stride", "<u2"), ("tx_type", "u1"), ("reserved", "u1")])
-assert TXFM_DESC_DTYPE.itemsize == 12
-ITXFM_DESC_DTYPE = np.dtype([("coeff_offset", "<u4"), ("recon_offset", "<u4"), ("recon_stride", "<u2"), ("tx_type", "u1"),
-                             ("reserved", "u1")])
-assert ITXFM_DESC_DTYPE.itemsize == 12
-TU_DESC_DTYPE = np.dtype([("src_offset", "<u4"), ("pred_offset", "<u4"), ("recon_offset", "<u4"), ("coeff_offset", "<u4"),
-                          ("iscan_offset", "<u4"), ("src_stride", "<u2"), ("pred_stride", "<u2"), ("recon_stride", "<u2"),
-                          ("qparam_index", "<u2"), ("tx_type", "u1"), ("reserved", "u1", (3,))])
-assert TU_DESC_DTYPE.itemsize == 32
-
-# the 19 AV1 transform sizes (width, height), TxSize order (Codec/EbDefinitions.h)
-TX_SIZES_WH = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 8), (8, 4), (8, 16), (16, 8), (16, 32), (32, 16), (32, 64),
-               (64, 32), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
-_VTX = [0, 1, 0, 1, 2, 0, 2, 1, 2, 3, 0, 3, 1, 3, 2, 3]  # vtx_tab / htx_tab (Codec/EbTransforms.h:88-97): 0 DCT 1 ADST 2 FLIPADST 3 IDTX
-_HTX = [0, 0, 1, 1, 0, 2, 2, 2, 1, 3, 3, 0, 3, 1, 3, 2]
-
-
-def valid_tx_types(w: int, h: int):
-    """TxTypes for which the reference has 1-D networks at this size (ADST up to 16 points, identity up to 32, 64 DCT only)."""
-    out = []
-    for t in range(16):
-        kc, kr = _VTX[t], _HTX[t]
-        if (kc in (1, 2) and h > 16) or (kr in (1, 2) and w > 16) or (kc == 3 and h > 32) or (kr == 3 and w > 32):
-            continue
-        out.append(t)
-    return out
-
-
-class SbOrigin(C.Structure):
-    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16)]
-
-
-# HME_LEVEL_0_SEARCH_AREA_MULTIPLIER_X / _Y [hierarchical_levels][temporal_layer_index]
-# (Codec/EbDefinitions.h:2980-2996); X and Y tables are identical in the reference.
-HME_LEVEL0_MULTIPLIER = [[100], [100, 100], [100, 100, 100], [200, 140, 100, 70], [350, 200, 100, 100, 100],
-                         [525, 350, 200, 100, 100, 100]]
-
-
-def default_me_params(width: int, height: int, hierarchical_levels: int = 3, temporal_layer_index: int = 0,
-                      is_ref: bool = True, ref_poc_equal: bool = False) -> MeParams:
-    """set_me_hme_params_oq() for enc modes M0..M3 (column 0 of the tables, Codec/EbDefinitions.h:3332-3465;
-    resolution class per Codec/EbMotionEstimationProcess.c:104-110)."""
-    px = width * height
-    ratio = width // height
-    if px < 1280 * 720 * 0.75:  # INPUT_SIZE_576p_RANGE_OR_LOWER (Codec/EbDefinitions.h input-size thresholds)
-        ri = 0
-    elif px < 1920 * 1080 * 0.75 and ratio < 2:
-        ri = 1
-    elif px <= 1920 * 1088 * 1.5:
-        ri = 3
-    else:
-        ri = 4
-    tot_w = [48, 64, 96, 96, 128][ri]
-    tot_h = [40, 48, 48, 48, 80][ri]
-    p = MeParams()
-    p.search_area_width, p.search_area_height = 64, 64
-    p.number_hme_search_region_in_width = p.number_hme_search_region_in_height = 2
-    p.hme_level0_total_search_area_width, p.hme_level0_total_search_area_height = tot_w, tot_h
-    for k in range(2):
-        p.hme_level0_search_area_in_width_array[k] = tot_w // 2
-        p.hme_level0_search_area_in_height_array[k] = tot_h // 2
-        p.hme_level1_search_area_in_width_array[k] = 16
-        p.hme_level1_search_area_in_height_array[k] = 16
-        p.hme_level2_search_area_in_width_array[k] = 8
-        p.hme_level2_search_area_in_height_array[k] = 8
-    m = HME_LEVEL0_MULTIPLIER[hierarchical_levels][temporal_layer_index]
-    p.hme_level0_multiplier_x = p.hme_level0_multiplier_y = m
-    p.enable_hme_flag = p.enable_hme_level0_flag = p.enable_hme_level1_flag = p.enable_hme_level2_flag = 1
-    p.temporal_layer_index = temporal_layer_index
-    p.is_used_as_reference_flag = int(is_ref)
-    p.ref_poc_equal = int(ref_poc_equal)
-    return p
-
-
-def build_picture_pool(pictures):
-    """Stack the three planes of each PaPicture into one uint8 pool (4-byte aligned planes).
-    Returns (pool, [PaPictureDesc])."""
-    chunks, descs, off = [], [], 0
-    for p in pictures:
-        d = PaPictureDesc()
-        for name, arr in (("full", p.full), ("quarter", p.quarter), ("sixteenth", p.sixteenth)):
-            flat = arr.reshape(-1)
-            padn = (-flat.size) % 16
-            setattr(d, name + "_offset", off)
-            setattr(d, name + "_stride", arr.shape[1])
-            chunks.append(flat)
-            if padn:
-                chunks.append(np.zeros(padn, np.uint8))
-            off += flat.size + padn
-        d.width, d.height = p.width, p.height
-        descs.append(d)
-    chunks.append(np.zeros(256, np.uint8))   # the kernels' aligned-group loads may run up to 64 bytes past the last plane
-    return np.concatenate(chunks), descs
-
-
-def sb_origins(width: int, height: int) -> np.ndarray:
-    nx, ny = (width + 63) // 64, (height + 63) // 64
-    out = np.zeros((nx * ny, 2), dtype=np.uint16)
-    for sy in range(ny):
-        for sx in range(nx):
-            out[sy * nx + sx] = (sx * 64, sy * 64)
-    return out
-
-
-def shard_sb_rows(width: int, height: int, world: int, rank: int) -> np.ndarray:
-    """Contiguous SB-ROW partition of one picture across `world` ranks (1080p -> 17 rows -> 3/2/2/...): the indices
-    (into sb_origins(width, height)) of the SBs rank `rank` owns.  See svtav1_hip.sharded for the multi-GPU layer built on it."""
-    from .sharded import shard_sb_indices
-
-    return shard_sb_indices(width, height, world, rank, "row")
-
-
-# ---- whole-PU inter prediction (svthip_av1_inter_pred_batch_dev / svthip_av1_highbd_inter_pred_batch_dev) ----
-INTER_PU_DESC_DTYPE = np.dtype([("pu_origin_x", "<u2"), ("pu_origin_y", "<u2"), ("dst_origin_x", "<u2"), ("dst_origin_y", "<u2"),
-                                ("mb_to_left_edge", "<i4"), ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"),
-                                ("interp_filters", "<u4"), ("pred_direction", "u1"), ("has_uv", "u1"), ("own_list", "u1"), ("reserved0", "u1"),
-                                ("mv", "<i2", (2, 2)), ("nb_is_inter", "u1", (3,)), ("nb_list", "u1", (3,)), ("nb_mv", "<i2", (3, 2)),
-                                ("reserved1", "u1", (6,))])
-assert INTER_PU_DESC_DTYPE.itemsize == 64
-UNI_PRED_LIST_0, UNI_PRED_LIST_1, BI_PRED = 0, 1, 2
-
-
-class InterPlanes(C.Structure):
-    """svthip_inter_planes: device pointers at picture sample (0, 0) of Y / Cb / Cr, strides in samples (Cb and Cr share c_stride)."""
-    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_uint32), ("c_stride", C.c_uint32)]
-
-
-def _planes_arg(p):
-    return None if p is None else C.byref(p)
-
-
-def _av1_inter_pred_batch_dev(self, ref0, ref1, dst, d_desc, n_pu, bwidth, bheight, stream=None):
-    """8-bit whole-PU inter prediction (Y, Cb, Cr) of n_pu PUs of one luma size; ref0 / ref1 / dst are InterPlanes, d_desc a device
-    array of INTER_PU_DESC_DTYPE."""
-    _check(lib().svthip_av1_inter_pred_batch_dev(self._h, _planes_arg(ref0), _planes_arg(ref1), _planes_arg(dst), d_desc, n_pu, bwidth, bheight,
-                                                 stream))
-
-
-def _av1_highbd_inter_pred_batch_dev(self, ref0, ref1, dst, d_desc, n_pu, bwidth, bheight, bit_depth=10, stream=None):
-    """The same for 16-bit planes holding 10-bit samples."""
-    _check(lib().svthip_av1_highbd_inter_pred_batch_dev(self._h, _planes_arg(ref0), _planes_arg(ref1), _planes_arg(dst), d_desc, n_pu, bwidth,
-                                                        bheight, bit_depth, stream))
-
-
-def _inter_pred_refused(self):
-    """Synchronises with the last inter-prediction call; raises SvtHipError naming the count if the device refused PUs since the last query."""
-    n = C.c_uint32(0)
-    _check(lib().svthip_inter_pred_refused(self._h, C.byref(n)))
-    return n.value
-
-
-Context.av1_inter_pred_batch_dev = _av1_inter_pred_batch_dev
-Context.av1_highbd_inter_pred_batch_dev = _av1_highbd_inter_pred_batch_dev
-Context.inter_pred_refused = _inter_pred_refused
-
-
-# ---- warped-motion prediction of whole PUs (svthip_av1_warped_pred_batch_dev / svthip_av1_highbd_warped_pred_batch_dev) ----
-WARP_PU_DESC_DTYPE = np.dtype([("pu_origin_x", "<u2"), ("pu_origin_y", "<u2"), ("dst_origin_x", "<u2"), ("dst_origin_y", "<u2"),
-                               ("mb_to_left_edge", "<i4"), ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"),
-                               ("wmmat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"),
-                               ("mv", "<i2", (2,)), ("wmtype", "u1"), ("has_uv", "u1"), ("reserved", "u1", (2,))])
-assert WARP_PU_DESC_DTYPE.itemsize == 64
-WARP_ROTZOOM, WARP_AFFINE = 2, 3
-WARP_BLOCK_SIZES_WH = [s for s in AV1_BLOCK_SIZES_WH if min(s) >= 8]
-
-
-def _av1_warped_pred_batch_dev(self, ref, dst, pic_width, pic_height, d_desc, n_pu, bwidth, bheight, stream=None):
-    """8-bit warped-motion prediction (Y, Cb, Cr) of n_pu PUs of one luma size; ref / dst are InterPlanes, d_desc a device array of
-    WARP_PU_DESC_DTYPE, pic_width x pic_height the reference picture's size (the warp clamps its reads to it)."""
-    _check(lib().svthip_av1_warped_pred_batch_dev(self._h, _planes_arg(ref), _planes_arg(dst), pic_width, pic_height, d_desc, n_pu, bwidth,
-                                                  bheight, stream))
-
-
-def _av1_highbd_warped_pred_batch_dev(self, ref, dst, pic_width, pic_height, d_desc, n_pu, bwidth, bheight, bit_depth=10, stream=None):
-    """The same for 16-bit planes holding 10-bit samples."""
-    _check(lib().svthip_av1_highbd_warped_pred_batch_dev(self._h, _planes_arg(ref), _planes_arg(dst), pic_width, pic_height, d_desc, n_pu,
-                                                         bwidth, bheight, bit_depth, stream))
-
-
-Context.av1_warped_pred_batch_dev = _av1_warped_pred_batch_dev
-Context.av1_highbd_warped_pred_batch_dev = _av1_highbd_warped_pred_batch_dev
-
-
-# ---- intra prediction of transform blocks (svthip_av1_intra_pred_batch_dev / svthip_av1_highbd_intra_pred_batch_dev) ----
-INTRA_DESC_DTYPE = np.dtype([("above_offset", "<u4"), ("left_offset", "<u4"), ("left_stride", "<u4"), ("dst_offset", "<u4"), ("dst_stride", "<u4"),
-                             ("n_top_px", "u1"), ("n_topright_px", "u1"), ("n_left_px", "u1"), ("n_bottomleft_px", "u1"), ("mode", "u1"),
-                             ("angle_delta", "i1"), ("src_stride", "<u2"), ("src_offset", "<u4")])
-assert INTRA_DESC_DTYPE.itemsize == 32
-# (width, height) of TxSize 0 .. 18 (TX_4X4 .. TX_64X16)
-TX_SIZES_WH = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 8), (8, 4), (8, 16), (16, 8), (16, 32), (32, 16), (32, 64), (64, 32), (4, 16),
-               (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
-
-
-def _av1_intra_pred_batch_dev(self, d_edge, d_dst, d_desc, n_blocks, tx_size, d_src=None, d_sad=None, stream=None):
-    """8-bit intra prediction of n_blocks transform blocks of one TxSize; d_desc a device array of INTRA_DESC_DTYPE, d_edge the samples
-    the edges are read from, d_dst where the blocks go (may be d_edge); d_sad (uint32 per block) asks for the SAD against d_src."""
-    _check(lib().svthip_av1_intra_pred_batch_dev(self._h, d_edge, d_dst, d_desc, n_blocks, tx_size, d_src, d_sad, stream))
-
-
-def _av1_highbd_intra_pred_batch_dev(self, d_edge, d_dst, d_desc, n_blocks, tx_size, bit_depth=10, stream=None):
-    """The same for 16-bit samples holding 10-bit values (no SAD)."""
-    _check(lib().svthip_av1_highbd_intra_pred_batch_dev(self._h, d_edge, d_dst, d_desc, n_blocks, tx_size, bit_depth, stream))
-
-
-Context.av1_intra_pred_batch_dev = _av1_intra_pred_batch_dev
-Context.av1_highbd_intra_pred_batch_dev = _av1_highbd_intra_pred_batch_dev
-
-
-# ---- chroma-from-luma prediction and its alpha search (svthip_av1_[highbd_]cfl_pred_batch_dev, svthip_av1_cfl_alpha_candidates_batch_dev,
-# svthip_cfl_alpha_decision_batch_dev) ----
-CFL_DESC_DTYPE = np.dtype([("luma_offset", "<u4"), ("luma_stride", "<u4"), ("cb_offset", "<u4"), ("cr_offset", "<u4"), ("chroma_stride", "<u4"),
-                           ("alpha_idx", "u1"), ("alpha_signs", "u1"), ("reserved", "u1", (10,))])
-CFL_DECISION_JOB_DTYPE = np.dtype([("lambda", "<u8"), ("cfl_mode_bits", "<i4"), ("dc_mode_bits", "<i4")])
-CFL_DECISION_DTYPE = np.dtype([("intra_chroma_mode", "u1"), ("cfl_alpha_idx", "u1"), ("cfl_alpha_signs", "u1"), ("reserved", "u1", (13,)),
-                               ("evaluated_mask", "<u8", (2,))])
-assert CFL_DESC_DTYPE.itemsize == 32 and CFL_DECISION_JOB_DTYPE.itemsize == 16 and CFL_DECISION_DTYPE.itemsize == 32
-# the luma sizes the reference uses CfL with
-CFL_LUMA_SIZES_WH = [(8, 8), (16, 8), (8, 16), (16, 16), (32, 8), (8, 32), (32, 16), (16, 32), (32, 32)]
-
-
-def _av1_cfl_pred_batch_dev(self, d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst, d_desc, n_blocks, luma_w, luma_h, stream=None):
-    """8-bit CfL prediction of n_blocks blocks of one luma size over the DC prediction in d_cb / d_cr; d_desc a device array of
-    CFL_DESC_DTYPE; d_cb_dst / d_cr_dst may be d_cb / d_cr."""
-    _check(lib().svthip_av1_cfl_pred_batch_dev(self._h, d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst, d_desc, n_blocks, luma_w, luma_h, stream))
-
-
-def _av1_highbd_cfl_pred_batch_dev(self, d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst, d_desc, n_blocks, luma_w, luma_h, bit_depth=10, stream=None):
-    """The same for 16-bit samples holding 10-bit values."""
-    _check(lib().svthip_av1_highbd_cfl_pred_batch_dev(self._h, d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst, d_desc, n_blocks, luma_w, luma_h, bit_depth,
-                                                      stream))
-
-
-def _av1_cfl_alpha_candidates_batch_dev(self, d_luma, d_cb_dc, d_cr_dc, d_desc, n_blocks, luma_w, luma_h, d_candidates, stream=None):
-    """The 2 x 33 candidate tiles per block (alpha_q3 = -16 .. 16 on Cb, then on Cr) into the pool d_candidates."""
-    _check(lib().svthip_av1_cfl_alpha_candidates_batch_dev(self._h, d_luma, d_cb_dc, d_cr_dc, d_desc, n_blocks, luma_w, luma_h, d_candidates, stream))
-
-
-def _cfl_alpha_decision_batch_dev(self, d_distortion, d_bits, dist_shift, d_alpha_bits, d_job, n_blocks, d_out, stream=None):
-    """cfl_rd_pick_alpha's walk over the candidates' costs: d_job of CFL_DECISION_JOB_DTYPE, d_out of CFL_DECISION_DTYPE."""
-    _check(lib().svthip_cfl_alpha_decision_batch_dev(self._h, d_distortion, d_bits, dist_shift, d_alpha_bits, d_job, n_blocks, d_out, stream))
-
-
-Context.av1_cfl_pred_batch_dev = _av1_cfl_pred_batch_dev
-Context.av1_highbd_cfl_pred_batch_dev = _av1_highbd_cfl_pred_batch_dev
-Context.av1_cfl_alpha_candidates_batch_dev = _av1_cfl_alpha_candidates_batch_dev
-Context.cfl_alpha_decision_batch_dev = _cfl_alpha_decision_batch_dev
-
-
-# ---- the deblocking filter and its level search (svthip_av1_[highbd_]loop_filter_frame_dev, .._loop_filter_sse_table_dev,
-# svthip_lf_level_walk_dev, svthip_av1_[highbd_]pick_filter_level_dev) ----
-LF_MI_DTYPE = np.dtype([("sb_type", "u1"), ("tx_size", "u1"), ("flags", "u1"), ("reserved", "u1")])
-assert LF_MI_DTYPE.itemsize == 4
-
-
-class LfPicture(C.Structure):
-    """svthip_lf_picture: device pointers to sample (0, 0) of the planes, strides in samples, the luma size"""
-    _fields_ = [("recon", C.c_void_p * 3), ("source", C.c_void_p * 3), ("recon_stride", C.c_uint32 * 3), ("source_stride", C.c_uint32 * 3),
-                ("width", C.c_uint32), ("height", C.c_uint32)]
-
-
-def make_lf_picture(width, height, recon, recon_stride, source=(None, None, None), source_stride=(0, 0, 0)):
-    p = LfPicture()
-    for i in range(3):
-        p.recon[i], p.source[i], p.recon_stride[i], p.source_stride[i] = recon[i], source[i], recon_stride[i], source_stride[i]
-    p.width, p.height = width, height
-    return p
-
-
-def _picture_ref(picture):
-    return C.cast(C.byref(picture), C.c_void_p) if picture is not None else None
-
-
-def _av1_loop_filter_frame_dev(self, picture, d_mi, mi_stride, d_levels, sharpness, plane_start, plane_end, bit_depth=8, stream=None):
-    """av1_loop_filter_frame on planes [plane_start, plane_end) in place; d_mi a device grid of LF_MI_DTYPE, d_levels four int32 on the device."""
-    if bit_depth == 8:
-        _check(lib().svthip_av1_loop_filter_frame_dev(self._h, _picture_ref(picture), d_mi, mi_stride, d_levels, sharpness, plane_start, plane_end, stream))
-    else:
-        _check(lib().svthip_av1_highbd_loop_filter_frame_dev(self._h, _picture_ref(picture), d_mi, mi_stride, d_levels, sharpness, plane_start,
-                                                             plane_end, bit_depth, stream))
-
-
-def _av1_loop_filter_sse_table_dev(self, picture, d_mi, mi_stride, plane, direction, d_levels, sharpness, d_sse, bit_depth=8, stream=None):
-    """d_sse[64] (uint64): try_filter_frame's result for every level of (plane, direction)."""
-    if bit_depth == 8:
-        _check(lib().svthip_av1_loop_filter_sse_table_dev(self._h, _picture_ref(picture), d_mi, mi_stride, plane, direction, d_levels, sharpness, d_sse,
-                                                          stream))
-    else:
-        _check(lib().svthip_av1_highbd_loop_filter_sse_table_dev(self._h, _picture_ref(picture), d_mi, mi_stride, plane, direction, d_levels, sharpness,
-                                                                 bit_depth, d_sse, stream))
-
-
-def _lf_level_walk_dev(self, d_sse, start_level, only_4x4, d_level_out, d_visited=None, stream=None):
-    """search_filter_level's walk over a table of 64 sums: the level (int32) and the mask of the levels it asked for (uint64)."""
-    _check(lib().svthip_lf_level_walk_dev(self._h, d_sse, start_level, int(only_4x4), d_level_out, d_visited, stream))
-
-
-def _av1_pick_filter_level_dev(self, picture, d_mi, mi_stride, last_levels, sharpness, only_4x4, d_levels, d_sse_tables, d_visited=None, bit_depth=8,
-                               stream=None):
-    """av1_pick_filter_level(LPF_PICK_FROM_FULL_IMAGE): the four levels into d_levels, the five tables into d_sse_tables[5][64]."""
-    last = (C.c_int32 * 4)(*[int(v) for v in last_levels]) if last_levels is not None else None
-    if bit_depth == 8:
-        _check(lib().svthip_av1_pick_filter_level_dev(self._h, _picture_ref(picture), d_mi, mi_stride, last, sharpness, int(only_4x4), d_levels,
-                                                      d_sse_tables, d_visited, stream))
-    else:
-        _check(lib().svthip_av1_highbd_pick_filter_level_dev(self._h, _picture_ref(picture), d_mi, mi_stride, last, sharpness, int(only_4x4), bit_depth,
-                                                             d_levels, d_sse_tables, d_visited, stream))
-
-
-Context.av1_loop_filter_frame_dev = _av1_loop_filter_frame_dev
-Context.av1_loop_filter_sse_table_dev = _av1_loop_filter_sse_table_dev
-Context.lf_level_walk_dev = _lf_level_walk_dev
-Context.av1_pick_filter_level_dev = _av1_pick_filter_level_dev
-
-
-# ---- Wiener loop restoration (svthip_av1_[highbd_]wiener_stats_dev, svthip_wiener_solve_dev, .._wiener_trial_sse_dev,
-# svthip_wiener_walk_init_dev / _step_dev, .._search_wiener_dev, .._loop_restoration_filter_frame_dev): pointer marshalling only ----
-RESTORE_NONE, RESTORE_WIENER, RESTORE_SGRPROJ = 0, 1, 2
-WIENER_WALK_STATE_DTYPE = np.dtype([("err", "<i8"), ("taps", "<i2", (16,)), ("step", "i1"), ("filt", "i1"), ("tap", "i1"), ("dir", "i1"), ("skip", "i1"),
-                                    ("first_tap", "i1"), ("started", "i1"), ("done", "u1"), ("n_trials", "<i4"), ("reserved", "<i4")])
-assert WIENER_WALK_STATE_DTYPE.itemsize == 56
-
-
-class LrPicture(C.Structure):
-    """svthip_lr_picture: device pointers to sample (0, 0) of the CDEF'd, deblocked and source planes, strides in samples, the luma size, the
-    restoration unit size per plane"""
-    _fields_ = [("cdef", C.c_void_p * 3), ("deblocked", C.c_void_p * 3), ("source", C.c_void_p * 3), ("cdef_stride", C.c_uint32 * 3),
-                ("deblocked_stride", C.c_uint32 * 3), ("source_stride", C.c_uint32 * 3), ("width", C.c_uint32), ("height", C.c_uint32),
-                ("unit_size", C.c_uint32 * 3)]
-
-
-def lr_unit_sizes(width, height):
-    """the reference's choice (EbPictureControlSet.c:32-47)"""
-    luma = 256 if width * height > 352 * 288 else 128
-    return (luma, luma // 2, luma // 2)
-
-
-def make_lr_picture(width, height, cdef, cdef_stride, deblocked, deblocked_stride, source=(None, None, None), source_stride=(0, 0, 0), unit_size=None):
-    p = LrPicture()
-    unit_size = unit_size or lr_unit_sizes(width, height)
-    for i in range(3):
-        p.cdef[i], p.deblocked[i], p.source[i] = cdef[i], deblocked[i], source[i]
-        p.cdef_stride[i], p.deblocked_stride[i], p.source_stride[i], p.unit_size[i] = cdef_stride[i], deblocked_stride[i], source_stride[i], unit_size[i]
-    p.width, p.height = width, height
-    return p
-
-
-def lr_unit_geometry(width, height, unit_size=None):
-    """(unit_base[4], limits[units][4] = h_start, h_end, v_start, v_end) from the library's own geometry (the one the kernels launch with)"""
-    us = (C.c_uint32 * 3)(*(unit_size or lr_unit_sizes(width, height)))
-    base = (C.c_uint32 * 4)()
-    n = lib().svthip_lr_unit_geometry(width, height, us, base, None)
-    limits = np.zeros((n, 4), np.int32)
-    lib().svthip_lr_unit_geometry(width, height, us, base, limits.ctypes.data)
-    return [int(b) for b in base], limits
-
-
-def lr_workspace_bytes(n_units):
-    return int(lib().svthip_lr_workspace_bytes(n_units))
-
-
-def wiener_walk_max_trials(wiener_win=7):
-    return int(lib().svthip_wiener_walk_max_trials(wiener_win))
-
-
-def _hbd(bit_depth, name):
-    return (getattr(lib(), "svthip_av1_" + name), ()) if bit_depth == 8 else (getattr(lib(), "svthip_av1_highbd_" + name), (bit_depth,))
-
-
-def _av1_wiener_stats_dev(self, picture, plane_start, plane_end, d_M, d_H, d_avg, d_sse_none, d_work, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "wiener_stats_dev")
-    _check(f(self._h, _picture_ref(picture), plane_start, plane_end, *bd, d_M, d_H, d_avg, d_sse_none, d_work, stream))
-
-
-def _wiener_solve_dev(self, d_M, d_H, unit_begin, unit_end, wiener_win, d_taps, d_rejected, stream=None):
-    _check(lib().svthip_wiener_solve_dev(self._h, d_M, d_H, unit_begin, unit_end, wiener_win, d_taps, d_rejected, stream))
-
-
-def _av1_wiener_trial_sse_dev(self, picture, plane_start, plane_end, d_taps, d_sse, d_skip=None, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "wiener_trial_sse_dev")
-    _check(f(self._h, _picture_ref(picture), plane_start, plane_end, *bd, d_taps, d_skip, d_sse, stream))
-
-
-def _wiener_walk_init_dev(self, d_state, d_taps, d_rejected, unit_begin, unit_end, wiener_win, stream=None):
-    _check(lib().svthip_wiener_walk_init_dev(self._h, d_state, d_taps, d_rejected, unit_begin, unit_end, wiener_win, stream))
-
-
-def _wiener_walk_step_dev(self, d_state, d_trial_sse, unit_begin, unit_end, d_pending=None, stream=None):
-    _check(lib().svthip_wiener_walk_step_dev(self._h, d_state, d_trial_sse, unit_begin, unit_end, d_pending, stream))
-
-
-def _av1_search_wiener_dev(self, picture, plane_start, plane_end, d_work, d_sse, d_taps, d_n_trials, d_pending, n_steps=0, resume=False, bit_depth=8,
-                           stream=None):
-    f, bd = _hbd(bit_depth, "search_wiener_dev")
-    _check(f(self._h, _picture_ref(picture), plane_start, plane_end, *bd, n_steps, int(resume), d_work, d_sse, d_taps, d_n_trials, d_pending, stream))
-
-
-def _av1_loop_restoration_filter_frame_dev(self, picture, d_out, out_stride, plane_start, plane_end, d_unit_type, d_taps, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "loop_restoration_filter_frame_dev")
-    out = (C.c_void_p * 3)(*d_out) if d_out is not None else None
-    strides = (C.c_uint32 * 3)(*out_stride) if out_stride is not None else None
-    _check(f(self._h, _picture_ref(picture), out, strides, plane_start, plane_end, *bd, d_unit_type, d_taps, stream))
-
-
-Context.av1_wiener_stats_dev = _av1_wiener_stats_dev
-Context.wiener_solve_dev = _wiener_solve_dev
-Context.av1_wiener_trial_sse_dev = _av1_wiener_trial_sse_dev
-Context.wiener_walk_init_dev = _wiener_walk_init_dev
-Context.wiener_walk_step_dev = _wiener_walk_step_dev
-Context.av1_search_wiener_dev = _av1_search_wiener_dev
-Context.av1_loop_restoration_filter_frame_dev = _av1_loop_restoration_filter_frame_dev
-
-
-# ---- self-guided loop restoration (svthip_av1_[highbd_]selfguided_restoration_dev, svthip_sgrproj_solve_dev, svthip_sgrproj_walk_table_dev,
-# .._search_sgrproj_dev, .._sgrproj_trial_sse_dev, .._lr_filter_frame_dev): pointer marshalling only ----
-SGRPROJ_DETAIL_DTYPE = np.dtype([("sums", "<i8", (5,)), ("exq", "<i4", (2,)), ("start_xqd", "<i4", (2,)), ("xqd", "<i4", (2,)), ("err", "<i8"),
-                                 ("n_trials", "<i4"), ("reserved", "<i4")])
-assert SGRPROJ_DETAIL_DTYPE.itemsize == 80
-SGRPROJ_PARAMS = 16
-
-
-def sgrproj_workspace_bytes(width, height):
-    return int(lib().svthip_sgrproj_workspace_bytes(width, height))
-
-
-def sgrproj_walk_max_trials():
-    return int(lib().svthip_sgrproj_walk_max_trials())
-
-
-def _av1_selfguided_restoration_dev(self, picture, plane, ep, d_flt0, d_flt1, flt_stride, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "selfguided_restoration_dev")
-    _check(f(self._h, _picture_ref(picture), plane, *bd, ep, d_flt0, d_flt1, flt_stride, stream))
-
-
-def _sgrproj_solve_dev(self, d_sums, d_size, d_ep, n, d_xq, d_xqd, stream=None):
-    _check(lib().svthip_sgrproj_solve_dev(self._h, d_sums, d_size, d_ep, n, d_xq, d_xqd, stream))
-
-
-def _sgrproj_walk_table_dev(self, d_err, d_ep, d_start_xqd, n, d_xqd, d_best_err, d_n_trials, stream=None):
-    _check(lib().svthip_sgrproj_walk_table_dev(self._h, d_err, d_ep, d_start_xqd, n, d_xqd, d_best_err, d_n_trials, stream))
-
-
-def _av1_search_sgrproj_dev(self, picture, plane_start, plane_end, d_work, d_sgrproj, d_sse, d_detail=None, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "search_sgrproj_dev")
-    _check(f(self._h, _picture_ref(picture), plane_start, plane_end, *bd, d_work, d_sgrproj, d_sse, d_detail, stream))
-
-
-def _av1_sgrproj_trial_sse_dev(self, picture, plane_start, plane_end, d_sgrproj, d_sse, d_skip=None, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "sgrproj_trial_sse_dev")
-    _check(f(self._h, _picture_ref(picture), plane_start, plane_end, *bd, d_sgrproj, d_skip, d_sse, stream))
-
-
-def _av1_lr_filter_frame_dev(self, picture, d_out, out_stride, plane_start, plane_end, d_unit_type, d_taps, d_sgrproj, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "lr_filter_frame_dev")
-    out = (C.c_void_p * 3)(*d_out) if d_out is not None else None
-    strides = (C.c_uint32 * 3)(*out_stride) if out_stride is not None else None
-    _check(f(self._h, _picture_ref(picture), out, strides, plane_start, plane_end, *bd, d_unit_type, d_taps, d_sgrproj, stream))
-
-
-Context.av1_selfguided_restoration_dev = _av1_selfguided_restoration_dev
-Context.sgrproj_solve_dev = _sgrproj_solve_dev
-Context.sgrproj_walk_table_dev = _sgrproj_walk_table_dev
-Context.av1_search_sgrproj_dev = _av1_search_sgrproj_dev
-Context.av1_sgrproj_trial_sse_dev = _av1_sgrproj_trial_sse_dev
-Context.av1_lr_filter_frame_dev = _av1_lr_filter_frame_dev
-
-
-# ---- CDEF (svthip_av1_[highbd_]cdef_search_mse_dev, svthip_cdef_pick_strengths_dev, .._cdef_search_dev, .._cdef_frame_dev,
-# svthip_cdef_dist_8x8_batch_dev): pointer marshalling only ----
-CDEF_RESULT_DTYPE = np.dtype([("cdef_bits", "<i4"), ("nb_cdef_strengths", "<i4"), ("cdef_strengths", "<i4", (8,)), ("cdef_uv_strengths", "<i4", (8,)),
-                              ("pri_damping", "<i4"), ("sec_damping", "<i4"), ("sb_count", "<i4")])
-assert CDEF_RESULT_DTYPE.itemsize == 84
-CDEF_PICK_MAX_FB = 4096
-
-
-class CdefPicture(C.Structure):
-    """svthip_cdef_picture: device pointers to sample (0, 0) of the deblocked, source and output planes, strides in samples, the luma size,
-    the skip map (one byte per 4x4 luma cell) and its stride"""
-    _fields_ = [("deblocked", C.c_void_p * 3), ("source", C.c_void_p * 3), ("out", C.c_void_p * 3), ("deblocked_stride", C.c_uint32 * 3),
-                ("source_stride", C.c_uint32 * 3), ("out_stride", C.c_uint32 * 3), ("width", C.c_uint32), ("height", C.c_uint32),
-                ("d_skip", C.c_void_p), ("skip_stride", C.c_uint32)]
-
-
-def cdef_filter_blocks(width, height):
-    """(nhfb, nvfb): 64x64 filter blocks each way"""
-    return (width // 4 + 15) // 16, (height // 4 + 15) // 16
-
-
-def make_cdef_picture(width, height, deblocked, deblocked_stride, d_skip, skip_stride, source=(None, None, None), source_stride=(0, 0, 0),
-                      out=(None, None, None), out_stride=(0, 0, 0)):
-    p = CdefPicture()
-    for i in range(3):
-        p.deblocked[i], p.source[i], p.out[i] = deblocked[i], source[i], out[i]
-        p.deblocked_stride[i], p.source_stride[i], p.out_stride[i] = deblocked_stride[i], source_stride[i], out_stride[i]
-    p.width, p.height, p.d_skip, p.skip_stride = width, height, d_skip, skip_stride
-    return p
-
-
-def _av1_cdef_search_mse_dev(self, picture, base_qindex, d_mse, d_fb_counted, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "cdef_search_mse_dev")
-    _check(f(self._h, _picture_ref(picture), base_qindex, *bd, d_mse, d_fb_counted, stream))
-
-
-def _cdef_pick_strengths_dev(self, d_mse, d_fb_counted, nhfb, nvfb, base_qindex, bit_depth, d_result, d_fb_strength, stream=None):
-    _check(lib().svthip_cdef_pick_strengths_dev(self._h, d_mse, d_fb_counted, nhfb, nvfb, base_qindex, bit_depth, d_result, d_fb_strength, stream))
-
-
-def _av1_cdef_search_dev(self, picture, base_qindex, d_mse, d_fb_counted, d_result, d_fb_strength, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "cdef_search_dev")
-    _check(f(self._h, _picture_ref(picture), base_qindex, *bd, d_mse, d_fb_counted, d_result, d_fb_strength, stream))
-
-
-def _av1_cdef_frame_dev(self, picture, d_result, d_fb_strength, plane_start, plane_end, bit_depth=8, stream=None):
-    f, bd = _hbd(bit_depth, "cdef_frame_dev")
-    _check(f(self._h, _picture_ref(picture), d_result, d_fb_strength, plane_start, plane_end, *bd, stream))
-
-
-def _cdef_dist_8x8_batch_dev(self, d_dst, d_src, n, coeff_shift, d_out, stream=None):
-    _check(lib().svthip_cdef_dist_8x8_batch_dev(self._h, d_dst, d_src, n, coeff_shift, d_out, stream))
-
-
-Context.av1_cdef_search_mse_dev = _av1_cdef_search_mse_dev
-Context.cdef_pick_strengths_dev = _cdef_pick_strengths_dev
-Context.av1_cdef_search_dev = _av1_cdef_search_dev
-Context.av1_cdef_frame_dev = _av1_cdef_frame_dev
-Context.cdef_dist_8x8_batch_dev = _cdef_dist_8x8_batch_dev
-
-
-# ---- host-pointer picture and TU forms (svthip_motion_estimate_picture / svthip_open_loop_intra_search_picture / svthip_encode_tu_batch) ----
-class HostPicture(C.Structure):
-    """svthip_host_picture: a host luma plane (the caller keeps the buffer alive), the sample at (origin_x, origin_y) is picture (0, 0)."""
-    _fields_ = [("buffer_y", C.c_void_p), ("stride_y", C.c_uint32), ("origin_x", C.c_uint16), ("origin_y", C.c_uint16), ("width", C.c_uint16),
-                ("height", C.c_uint16)]
-
-
-assert C.sizeof(HostPicture) == 24
-# svthip_me_cu_result_ref: the reference's MeCuResults_t (40 bytes; `direction` words hold 0..2, padding is written as 0)
-ME_CU_RESULT_REF_DTYPE = np.dtype({"names": ["xMvL0", "yMvL0", "xMvL1", "yMvL1", "distortionDirection", "totalMeCandidateIndex"],
-                                   "formats": ["<i2", "<i2", "<i2", "<i2", (np.dtype([("distortion", "<u4"), ("direction", "<u4")]), (3,)), "u1"],
-                                   "offsets": [0, 2, 4, 6, 8, 32], "itemsize": 40})
-
-
-def _row_pointers(rows):
-    return (C.c_void_p * rows.shape[0])(*[rows.ctypes.data + i * rows.strides[0] for i in range(rows.shape[0])])
-
-
-def _motion_estimate_picture(self, cur, ref0, ref1, params, use_subpel=True, cu8x8_mode=0, n_pu=85):
-    """Whole-picture ME with host buffers (HostPicture cur / ref0 / ref1, ref1=None for P pictures; synchronous).  Returns the
-    MeCuResults_t rows: ME_CU_RESULT_REF_DTYPE [n_sb][n_pu], SBs in raster order."""
-    n_sb = ((cur.width + 63) // 64) * ((cur.height + 63) // 64)
-    rows = np.zeros((n_sb, n_pu), ME_CU_RESULT_REF_DTYPE)
-    _check(lib().svthip_motion_estimate_picture(self._h, C.byref(cur), C.byref(ref0), C.byref(ref1) if ref1 is not None else None, C.byref(params),
-                                                int(use_subpel), int(cu8x8_mode), n_pu, _row_pointers(rows)))
-    return rows
-
-
-def _open_loop_intra_search_picture(self, cur, params, me_rows=None, n_pu=85):
-    """OpenLoopIntraSearchLcu over every SB of a HostPicture (synchronous).  me_rows: the [n_sb][n_pu] ME_CU_RESULT_REF_DTYPE rows of
-    motion_estimate_picture, or None on the branches that do not read them.  Returns (cand [n_sb][85][18] u32, total [n_sb][85] u8)."""
-    n_sb = ((cur.width + 63) // 64) * ((cur.height + 63) // 64)
-    cand = np.zeros((n_sb, 85, 18), np.uint32)
-    total = np.zeros((n_sb, 85), np.uint8)
-    ptrs = None
-    if me_rows is not None:
-        assert me_rows.dtype == ME_CU_RESULT_REF_DTYPE and me_rows.shape == (n_sb, n_pu)
-        ptrs = _row_pointers(me_rows)
-    _check(lib().svthip_open_loop_intra_search_picture(self._h, C.byref(cur), C.byref(params), ptrs, n_pu, cand.ctypes.data, total.ctypes.data))
-    return cand, total
-
-
-def _encode_tu_batch(self, src, pred, recon, desc, tx_width, tx_height, qparams, iscan, coeff_samples):
-    """The fused T/Q chain with host buffers (synchronous).  src / pred / recon: contiguous planes of one dtype, uint8 or uint16 (16-bit
-    planes); recon may be pred itself (in-place reconstruction) and is written in place.  Returns dict coeff / qcoeff / dqcoeff (int32
-    [coeff_samples]), eob (uint16 [n]), energy (uint64 [n]), dist (uint64 [n][2])."""
-    assert src.dtype in (np.uint8, np.uint16) and pred.dtype == recon.dtype == src.dtype and pred.size == recon.size == src.size
-    assert all(a.flags.c_contiguous for a in (src, pred, recon))
-    desc = np.ascontiguousarray(desc, TU_DESC_DTYPE)
-    qparams = np.ascontiguousarray(qparams, np.int16).reshape(-1, 10)
-    iscan = np.ascontiguousarray(iscan, np.int16)
-    n = len(desc)
-    out = {"coeff": np.zeros(coeff_samples, np.int32), "qcoeff": np.zeros(coeff_samples, np.int32), "dqcoeff": np.zeros(coeff_samples, np.int32),
-           "eob": np.zeros(n, np.uint16), "energy": np.zeros(n, np.uint64), "dist": np.zeros((n, 2), np.uint64)}
-    _check(lib().svthip_encode_tu_batch(self._h, src.ctypes.data, pred.ctypes.data, recon.ctypes.data, src.size, int(src.dtype == np.uint16),
-                                        desc.ctypes.data, n, tx_width, tx_height, qparams.ctypes.data, qparams.shape[0], iscan.ctypes.data, iscan.size,
-                                        coeff_samples, out["coeff"].ctypes.data, out["qcoeff"].ctypes.data, out["dqcoeff"].ctypes.data,
-                                        out["eob"].ctypes.data, out["energy"].ctypes.data, out["dist"].ctypes.data))
-    return out
-
-
-Context.motion_estimate_picture = _motion_estimate_picture
-Context.open_loop_intra_search_picture = _open_loop_intra_search_picture
-Context.encode_tu_batch = _encode_tu_batch

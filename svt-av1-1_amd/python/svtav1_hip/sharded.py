@@ -21,7 +21,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import lib, sb_origins, _check
+from ._core import lib
+from ._me import sb_origins
 
 
 class ReconPicture(C.Structure):
@@ -36,37 +37,9 @@ class Xfer(C.Structure):
     _fields_ = [("peer", C.c_int32), ("plane", C.c_uint32), ("send", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
 
 
-def _bind():
-    L = lib()
-    if getattr(L, "_sharded_bound", False):
-        return L
-    u32p = C.POINTER(C.c_uint32)
-    L.svthip_shard_range.restype = None
-    L.svthip_shard_range.argtypes = [C.c_uint32, C.c_int32, C.c_int32, u32p, u32p]
-    L.svthip_recon_slab_rows.restype = None
-    L.svthip_recon_slab_rows.argtypes = [C.c_uint32, C.c_int32, C.c_int32, u32p, u32p]
-    L.svthip_recon_exchange_plan.restype = C.c_int32
-    L.svthip_recon_exchange_plan.argtypes = [C.POINTER(ReconPicture), C.c_int32, C.c_int32, C.POINTER(Xfer), C.c_uint32, u32p]
-    L.svthip_me_gather_plan.restype = C.c_int32
-    L.svthip_me_gather_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(Xfer), C.c_uint32, u32p]
-    L.svthip_comm_get_unique_id.restype = C.c_int32
-    L.svthip_comm_get_unique_id.argtypes = [C.c_void_p]
-    L.svthip_comm_create.restype = C.c_int32
-    L.svthip_comm_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
-    L.svthip_comm_destroy.restype = None
-    L.svthip_comm_destroy.argtypes = [C.c_void_p]
-    L.svthip_comm_last_error.restype = C.c_char_p
-    L.svthip_recon_exchange_dev.restype = C.c_int32
-    L.svthip_recon_exchange_dev.argtypes = [C.c_void_p, C.POINTER(ReconPicture), C.c_void_p]
-    L.svthip_me_gather_results_dev.restype = C.c_int32
-    L.svthip_me_gather_results_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    L._sharded_bound = True
-    return L
-
-
 def _ccheck(rc: int):
     if rc != 0:
-        raise RuntimeError(f"svthip multi-GPU error 0x{rc & 0xFFFFFFFF:08x}: {_bind().svthip_comm_last_error().decode()}")
+        raise RuntimeError(f"svthip multi-GPU error 0x{rc & 0xFFFFFFFF:08x}: {lib().svthip_comm_last_error().decode()}")
 
 
 def sb_grid(width: int, height: int):
@@ -76,7 +49,7 @@ def sb_grid(width: int, height: int):
 def shard_range(n_units: int, world: int, rank: int):
     """svthip_shard_range: contiguous share of n_units, balanced to one unit -> (first, count)."""
     f, c = C.c_uint32(0), C.c_uint32(0)
-    _bind().svthip_shard_range(n_units, world, rank, C.byref(f), C.byref(c))
+    lib().svthip_shard_range(n_units, world, rank, C.byref(f), C.byref(c))
     return f.value, c.value
 
 
@@ -101,23 +74,23 @@ def shard_sb_indices(width: int, height: int, world: int, rank: int, granularity
 def recon_slab_rows(height: int, world: int, rank: int):
     """svthip_recon_slab_rows: luma rows (first, count) of rank's SB-row slab."""
     f, c = C.c_uint32(0), C.c_uint32(0)
-    _bind().svthip_recon_slab_rows(height, world, rank, C.byref(f), C.byref(c))
+    lib().svthip_recon_slab_rows(height, world, rank, C.byref(f), C.byref(c))
     return f.value, c.value
 
 
 def recon_exchange_plan(pic: ReconPicture, world: int, rank: int):
     n = C.c_uint32(0)
-    _ccheck(_bind().svthip_recon_exchange_plan(C.byref(pic), world, rank, None, 0, C.byref(n)))
+    _ccheck(lib().svthip_recon_exchange_plan(C.byref(pic), world, rank, None, 0, C.byref(n)))
     plan = (Xfer * max(1, n.value))()
-    _ccheck(_bind().svthip_recon_exchange_plan(C.byref(pic), world, rank, plan, n.value, C.byref(n)))
+    _ccheck(lib().svthip_recon_exchange_plan(C.byref(pic), world, rank, plan, n.value, C.byref(n)))
     return [plan[i] for i in range(n.value)]
 
 
 def me_gather_plan(n_sb_total: int, n_jobs: int, record_bytes: int, world: int, rank: int):
     n = C.c_uint32(0)
-    _ccheck(_bind().svthip_me_gather_plan(n_sb_total, n_jobs, record_bytes, world, rank, None, 0, C.byref(n)))
+    _ccheck(lib().svthip_me_gather_plan(n_sb_total, n_jobs, record_bytes, world, rank, None, 0, C.byref(n)))
     plan = (Xfer * max(1, n.value))()
-    _ccheck(_bind().svthip_me_gather_plan(n_sb_total, n_jobs, record_bytes, world, rank, plan, n.value, C.byref(n)))
+    _ccheck(lib().svthip_me_gather_plan(n_sb_total, n_jobs, record_bytes, world, rank, plan, n.value, C.byref(n)))
     return [plan[i] for i in range(n.value)]
 
 
@@ -140,16 +113,15 @@ class Comm:
     """svthip_comm of this rank (RCCL).  With torch.distributed initialised the unique id travels through the launcher's store."""
 
     def __init__(self, ctx, rank: int = 0, world: int = 1, unique_id: bytes | None = None):
-        L = _bind()
         self.ctx, self.rank, self.world = ctx, rank, world
         self._h = C.c_void_p()
         buf = C.create_string_buffer(unique_id, 128) if unique_id is not None else None
-        _ccheck(L.svthip_comm_create(ctx._h, buf, rank, world, C.byref(self._h)))
+        _ccheck(lib().svthip_comm_create(ctx._h, buf, rank, world, C.byref(self._h)))
 
     @staticmethod
     def unique_id() -> bytes:
         buf = C.create_string_buffer(128)
-        _ccheck(_bind().svthip_comm_get_unique_id(buf))
+        _ccheck(lib().svthip_comm_get_unique_id(buf))
         return buf.raw
 
     @classmethod
@@ -167,14 +139,14 @@ class Comm:
 
     def close(self):
         if self._h:
-            _bind().svthip_comm_destroy(self._h)
+            lib().svthip_comm_destroy(self._h)
             self._h = C.c_void_p()
 
     def recon_exchange_dev(self, pic: ReconPicture, stream=None):
-        _ccheck(_bind().svthip_recon_exchange_dev(self._h, C.byref(pic), stream))
+        _ccheck(lib().svthip_recon_exchange_dev(self._h, C.byref(pic), stream))
 
     def me_gather_results_dev(self, d_local: int, d_full: int, n_jobs: int, n_sb_total: int, record_bytes: int, stream=None):
-        _ccheck(_bind().svthip_me_gather_results_dev(self._h, d_local, d_full, n_jobs, n_sb_total, record_bytes, stream))
+        _ccheck(lib().svthip_me_gather_results_dev(self._h, d_local, d_full, n_jobs, n_sb_total, record_bytes, stream))
 
 
 class ShardedMotionEstimation:

@@ -88,8 +88,6 @@ def test_4k_host_pointer_picture_entry(hip_ctx, oracle, pics4k):
     hp = [HostPicture(p.full.ctypes.data, p.stride, 68, 68, W, H) for p in pics4k[:2]]
     rows = np.zeros((2040, 85, 40), np.uint8)
     ptrs = (C.c_void_p * 2040)(*[rows.ctypes.data + i * 85 * 40 for i in range(2040)])
-    L.svthip_motion_estimate_picture.restype = C.c_int32
-    L.svthip_motion_estimate_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]
     hip_ctx.reserve(W, H, 85, 1, True)
     rc = L.svthip_motion_estimate_picture(hip_ctx._h, C.byref(hp[0]), C.byref(hp[1]), None, C.byref(P), 1, 0, 85, ptrs)
     assert rc == 0, L.svthip_last_error()

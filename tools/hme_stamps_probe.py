@@ -16,9 +16,9 @@ SO = "/tmp/libsvtav1_hip_stamps.so"
 if not os.path.exists(SO):
     srcs = sorted(glob.glob(os.path.join(ROOT, "svt-av1-1_amd", "csrc", "*.hip")))
     subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-DSVTHIP_HME_STAMPS", "-shared", *srcs, "-o", SO])
+os.environ["SVTAV1_HIP_LIB"] = SO   # read when the package is imported
 import torch  # noqa: E402
 import svtav1_hip  # noqa: E402
-svtav1_hip.LIB_PATH = SO
 import bench  # noqa: E402
 
 dev = torch.device("cuda:0")
