@@ -1,5 +1,5 @@
 """Writes tests/golden/cdef.npz from the reference's own CDEF strength search, strength pick and frame filter (tests/golden/ref_cdef_driver.c,
-linked by make_golden_lr.build_driver's recipe against the reference objects of the oracle build, oracle/_ref/obj_all).  Run in the build
+linked by the recipe of oracle/ref_driver.py against the reference objects of the oracle build, oracle/_ref/obj_all).  Run in the build
 container only, where the reference exists: the fixture is data.
 
     python tests/golden/make_golden_cdef.py
@@ -27,7 +27,6 @@ C against AVX2.  Coverage: coverage() below, asserted here and by tests/test_cde
 import ctypes as C
 import io
 import os
-import subprocess
 import sys
 import tempfile
 import zipfile
@@ -36,46 +35,22 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [HERE, os.path.join(ROOT, "tests")]
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), ROOT]
 
 import cdef_util as cu  # noqa: E402
+from make_golden_lr import _ptrs, delta  # noqa: E402
+from oracle import ref_driver  # noqa: E402
+from oracle.ref_driver import reference_available  # noqa: E402
 
-REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
-OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
 OUT = os.path.join(HERE, "cdef.npz")
 CASES = ((64, 64, 8), (200, 136, 8), (136, 200, 8), (64, 64, 10), (200, 136, 10), (136, 200, 10))
 QINDEX = (20, 100, 255)
 N_RUNS = 3
 
 
-def reference_available():
-    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL)
-
-
 def build_driver(out_dir):
-    """The recipe of make_golden_lr.build_driver for ref_cdef_driver.c: every reference object but EbEncHandle.o, sections collected, the
-    driver's still-undefined symbols weakened."""
-    S = os.path.join(REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(HERE, "ref_cdef_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_cdef.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL) if o.endswith(".o") and o != "EbEncHandle.o")
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, o, *objs, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """ref_cdef_driver.c by the recipe of oracle/ref_driver.py, with its signatures."""
+    L = ref_driver.build_driver(os.path.join(HERE, "ref_cdef_driver.c"), out_dir)
     V = C.c_void_p
     L.drv_cdef_open.argtypes = [C.c_int] * 3 + [V] * 3
     L.drv_cdef_search.argtypes = [C.c_int, V]
@@ -86,10 +61,6 @@ def build_driver(out_dir):
     L.drv_cdef_time.restype = C.c_double
     L.drv_cdef_time.argtypes = [C.c_int, V]
     return L
-
-
-def _ptrs(planes):
-    return (C.c_void_p * 3)(*[p.ctypes.data for p in planes])
 
 
 class Reference:
@@ -130,11 +101,6 @@ class Reference:
     def time(self, q):
         parts = np.zeros(3)
         return self.L.drv_cdef_time(q, parts.ctypes.data), parts
-
-
-def delta(a, b):
-    d = a.astype(np.int32) - b.astype(np.int32)
-    return d.astype(np.int8 if np.abs(d).max(initial=0) < 128 else np.int16)
 
 
 def make_pictures(rng, w, h, bd):

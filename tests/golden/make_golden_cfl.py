@@ -27,7 +27,6 @@ maximum, a block sum whose rounding term decides the average; decision tables th
 early exit, a tie on this_rd >= best_rd_uv, a tie on dc_rd <= best_rd (DC wins), each of the eight joint signs as winner, DC as winner."""
 import ctypes as C
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -35,50 +34,22 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python"), ROOT]
 
 import cfl_util as cu  # noqa: E402
+from oracle import ref_driver  # noqa: E402
+from oracle.ref_driver import reference_available  # noqa: E402
 
-REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
-OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
 OUT = os.path.join(HERE, "cfl.npz")
 BUF_LINE = 32   # CFL_BUF_LINE
 N_DEC_RANDOM, N_DEC_TIES = 144, 16
 
 
-def reference_available():
-    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL)
-
-
 def build_driver(out_dir):
-    """The recipe of make_golden_intra_pred.build_driver (--gc-sections from the drv_* roots, EbEncHandle.o left out, NASM-only symbols that
-    stay unresolved made weak), with EbProductCodingLoop.o left out (the driver includes that source) and a copy of EbFullLoop.o in which
-    the two functions the driver replaces are weak."""
-    S = os.path.join(REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(HERE, "ref_cfl_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_cfl.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    full_loop = os.path.join(out_dir, "EbFullLoop_weak.o")
-    subprocess.check_call(["objcopy", "--weaken-symbol=FullLoop_R", "--weaken-symbol=CuFullDistortionFastTuMode_R",
-                           os.path.join(OBJ_ALL, "EbFullLoop.o"), full_loop])
-    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL)
-                  if o.endswith(".o") and o not in ("EbEncHandle.o", "EbProductCodingLoop.o", "EbFullLoop.o")) + [full_loop]
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, o, *objs, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """ref_cfl_driver.c by the recipe of oracle/ref_driver.py, with EbProductCodingLoop.o left out (the driver includes that source) and a copy of
+    EbFullLoop.o in which the two functions the driver replaces are weak."""
+    L = ref_driver.build_driver(os.path.join(HERE, "ref_cfl_driver.c"), out_dir, leave_out=("EbProductCodingLoop.o",),
+                                weaken={"EbFullLoop.o": ("FullLoop_R", "CuFullDistortionFastTuMode_R")})
     L.drv_subsample.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.drv_subtract_average.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int]
     L.drv_predict.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]

@@ -24,7 +24,6 @@ every equality with this fixture is also a check of C against SSE2.
 Coverage: coverage() below, asserted again by tests/test_dlf_vs_ref.py::test_fixture_covers_the_ground."""
 import ctypes as C
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -32,12 +31,12 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [HERE, os.path.join(ROOT, "tests")]
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), ROOT]
 
 import dlf_util as du  # noqa: E402
+from oracle import ref_driver  # noqa: E402
+from oracle.ref_driver import reference_available  # noqa: E402
 
-REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
-OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
 OUT = os.path.join(HERE, "dlf.npz")
 SIZES = ((64, 64), (136, 72), (200, 136))
 RUNS = ((20, 33, 12, 50, 0, 0, 3), (0, 9, 0, 3, 0, 0, 3), (40, 25, 30, 63, 3, 0, 3), (12, 12, 7, 9, 0, 1, 3), (0, 0, 5, 5, 0, 0, 3), (7, 0, 63, 0, 5, 0, 2))
@@ -45,34 +44,9 @@ PICKS = ((0, 0, 0, 0, 0), (10, 10, 20, 5, 0), (63, 40, 2, 60, 1), (30, 17, 63, 1
 N_EXTRA = 10
 
 
-def reference_available():
-    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL)
-
-
 def build_driver(out_dir):
-    """The recipe of make_golden_cfl.build_driver: --gc-sections from the drv_* roots, EbEncHandle.o left out, symbols that stay unresolved
-    (NASM code) made weak."""
-    S = os.path.join(REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(HERE, "ref_dlf_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_dlf.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL) if o.endswith(".o") and o != "EbEncHandle.o")
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, o, *objs, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """ref_dlf_driver.c by the recipe of oracle/ref_driver.py, with its signature."""
+    L = ref_driver.build_driver(os.path.join(HERE, "ref_dlf_driver.c"), out_dir)
     L.drv_dlf.restype = C.c_int
     L.drv_dlf.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     return L

@@ -15,7 +15,6 @@ The cases cover the 22 sizes, the five sub-8x8 shapes with every intra / inter n
 vectors clamped on every edge, neighbours whose ref_frame[0] is not LAST_FRAME, 8 and 10 bits."""
 import ctypes as C
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -23,47 +22,22 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python"), ROOT]
 
 import inter_pred_util as ipu  # noqa: E402
 import svtav1_hip  # noqa: E402
+from oracle import ref_driver  # noqa: E402
+from oracle.ref_driver import reference_available  # noqa: E402
 
-REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
-OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
 OUT = os.path.join(HERE, "inter_pred.npz")
 PIC, BORDER = 128, 144
 FILL = {8: 0x55, 10: 0x155}
 INTRA, LAST, LAST2, BWDREF, ALTREF = 0, 1, 2, 5, 7
 
 
-def reference_available():
-    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL)
-
-
 def build_driver(out_dir):
-    """Compile the driver and link it with the reference objects (oracle/build_ref.sh's recipe: --gc-sections from the drv_* roots, the
-    RTCD pointers defined by the driver, so EbEncHandle.o is left out; NASM-only symbols that stay unresolved are made weak)."""
-    S = os.path.join(REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(HERE, "ref_inter_pred_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_inter.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL) if o.endswith(".o") and o != "EbEncHandle.o")
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, *objs, o, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """ref_inter_pred_driver.c by the recipe of oracle/ref_driver.py, with its signatures."""
+    L = ref_driver.build_driver(os.path.join(HERE, "ref_inter_pred_driver.c"), out_dir)
     L.drv_init.restype = C.c_int
     L.drv_own_list.restype = C.c_int
     L.drv_own_list.argtypes = [C.c_int]

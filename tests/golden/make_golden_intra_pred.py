@@ -26,7 +26,6 @@ zone 1 past max_base (zone 3 cannot get there: its steepest legal angle, 212 deg
 its base stays below txw + txh - 1), zone 2 reading both edges in one row, outputs 0 and the maximum."""
 import ctypes as C
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -34,46 +33,21 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python"), ROOT]
 
 import intra_pred_util as iu  # noqa: E402
+from oracle import ref_driver  # noqa: E402
+from oracle.ref_driver import reference_available  # noqa: E402
 
-REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
-OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
 OUT = os.path.join(HERE, "intra_pred.npz")
 PIC_W, PIC_H = 200, 136
 DIR_SIZES = (0, 1, 14, 13, 3, 4)   # 4x4, 8x8, 16x4, 4x16, 32x32, 64x64
 PART_N, PART_H, PART_V, PART_H4, PART_V4 = 0, 1, 2, 7, 8
 
 
-def reference_available():
-    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL)
-
-
 def build_driver(out_dir):
-    """The recipe of make_golden_inter_pred.build_driver (--gc-sections from the drv_* roots, EbEncHandle.o left out, NASM-only symbols that
-    stay unresolved made weak), with EbIntraPrediction.o left out as well: the driver includes that source."""
-    S = os.path.join(REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(HERE, "ref_intra_pred_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_intra.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL) if o.endswith(".o") and o not in ("EbEncHandle.o", "EbIntraPrediction.o"))
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, *objs, o, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """ref_intra_pred_driver.c by the recipe of oracle/ref_driver.py, with EbIntraPrediction.o left out: the driver includes that source."""
+    L = ref_driver.build_driver(os.path.join(HERE, "ref_intra_pred_driver.c"), out_dir, leave_out=("EbIntraPrediction.o",))
     L.drv_init.restype = C.c_int
     L.drv_build.restype = C.c_int
     L.drv_build.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]

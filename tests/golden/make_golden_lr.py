@@ -32,8 +32,8 @@ and aom_mse16x16_avx2; tests/lr_util.py restates the C forms, so every equality 
 Coverage: coverage() below, asserted again by tests/test_lr_vs_ref.py::test_fixture_covers_the_ground.  Arms the pictures do not reach are
 listed in `unreached` (names of lr_util's statistics) and are covered by the synthetic cases."""
 import ctypes as C
+import io
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -41,44 +41,20 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [HERE, os.path.join(ROOT, "tests")]
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), ROOT]
 
 import lr_util as lu  # noqa: E402
+from oracle import ref_driver  # noqa: E402
+from oracle.ref_driver import reference_available  # noqa: E402
 
-REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
-OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
 OUT = os.path.join(HERE, "lr.npz")
 CASES = ((64, 64, 8), (200, 136, 8), (136, 200, 8), (392, 264, 8), (64, 64, 10), (200, 136, 10), (136, 200, 10))
 TRACE_CAP = 128
 
 
-def reference_available():
-    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL)
-
-
 def build_driver(out_dir):
-    """The recipe of make_golden_dlf.build_driver, with EbRestorationPick.o left out: the driver is that file."""
-    S = os.path.join(REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(HERE, "ref_lr_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_lr.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL) if o.endswith(".o") and o not in ("EbEncHandle.o", "EbRestorationPick.o"))
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, o, *objs, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """ref_lr_driver.c by the recipe of oracle/ref_driver.py, with EbRestorationPick.o left out: the driver is that file."""
+    L = ref_driver.build_driver(os.path.join(HERE, "ref_lr_driver.c"), out_dir, leave_out=("EbRestorationPick.o",))
     L.drv_lr_open.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4
     L.drv_lr_units.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     L.drv_lr_search.argtypes = [C.c_int] + [C.c_void_p] * 10
@@ -138,6 +114,17 @@ def delta(a, b):
     """a - b as int16 (int8 where it fits): the planes differ little from each other, so the differences compress"""
     d = a.astype(np.int32) - b.astype(np.int32)
     return d.astype(np.int8 if np.abs(d).max(initial=0) < 128 else np.int16)
+
+
+def print_sizes(out):
+    """the eight largest groups of arrays by compressed size, the per-case arrays c{c}_* / x{c}_* of one name taken together"""
+    sizes = {}
+    for k, v in out.items():
+        bio = io.BytesIO()
+        np.savez_compressed(bio, a=v)
+        g = k.split("_", 1)[1].rstrip("0123456789") if k[0] in "cx" and k[1].isdigit() else k
+        sizes[g] = sizes.get(g, 0) + bio.getbuffer().nbytes
+    print(sorted(sizes.items(), key=lambda kv: -kv[1])[:8])
 
 
 def make_pictures(rng, w, h, bd):
@@ -343,14 +330,7 @@ def main():
     out["syn_M"], out["syn_H"], out["syn_win"] = np.array(sM), np.array(sH), np.array(sw_, np.int32)
     out["syn_start"], out["syn_rejected"] = np.array(ss_, np.int16), np.array(sr, np.int32)
     np.savez_compressed(OUT, **out)
-    import io
-    sizes = {}
-    for k, v in out.items():
-        bio = io.BytesIO()
-        np.savez_compressed(bio, a=v)
-        g = k.split("_", 1)[1].rstrip("0123456789") if k[0] == "c" and k[1].isdigit() else k
-        sizes[g] = sizes.get(g, 0) + bio.getbuffer().nbytes
-    print(sorted(sizes.items(), key=lambda kv: -kv[1])[:8])
+    print_sizes(out)
     print(f"wrote {OUT}: {os.path.getsize(OUT) / 1e6:.2f} MB")
 
 

@@ -1,6 +1,6 @@
 """Writes tests/golden/lr_sgr.npz from the reference's own self-guided restoration search and frame filter (tests/golden/ref_lr_sgr_driver.c:
 tests/golden/ref_lr_driver.c, i.e. the reference's EbRestorationPick.c included where it lies, plus calls; linked by the recipe of
-make_golden_lr.build_driver against oracle/_ref/obj_all without EbRestorationPick.o).  Run in the build container only, where the reference
+oracle/ref_driver.py against oracle/_ref/obj_all without EbRestorationPick.o).  Run in the build container only, where the reference
 exists: the fixture is data.
 
     python tests/golden/make_golden_lr_sgr.py
@@ -33,9 +33,7 @@ fixture is also a check of C against AVX2.
 Coverage: counted by the restatement while it reproduces the reference's run trial by trial; arms the pictures do not reach are listed in
 `unreached` and must be reached by the synthetic cases (asserted here and by tests/test_lr_sgr_vs_ref.py::test_fixture_covers_the_ground)."""
 import ctypes as C
-import io
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -43,11 +41,13 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [HERE, os.path.join(ROOT, "tests")]
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), ROOT]
 
 import lr_sgr_util as su  # noqa: E402
 import lr_util as lu  # noqa: E402
 import make_golden_lr as mg  # noqa: E402
+from oracle import ref_driver  # noqa: E402
+from oracle.ref_driver import reference_available  # noqa: E402
 
 OUT = os.path.join(HERE, "lr_sgr.npz")
 LR_CASES = (0, 1, 2, 4, 5, 6, -1, -1)
@@ -57,31 +57,8 @@ TRACE_CAP = 48
 
 
 def build_driver(out_dir):
-    """make_golden_lr.build_driver's recipe for ref_lr_sgr_driver.c.  A copy with another source, library name and entry points, because
-    make_golden_lr.py names its source inside the function: a change of the recipe there (flags, the objects left out, the weakening of
-    undefined symbols) has to be made here as well."""
-    S = os.path.join(mg.REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(HERE, "ref_lr_sgr_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_lr_sgr.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, f"-I{HERE}", "-c", src,
-                           "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    objs = sorted(os.path.join(mg.OBJ_ALL, o) for o in os.listdir(mg.OBJ_ALL) if o.endswith(".o") and o not in ("EbEncHandle.o", "EbRestorationPick.o"))
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, o, *objs, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """ref_lr_sgr_driver.c, which includes ref_lr_driver.c, by the recipe of oracle/ref_driver.py, with EbRestorationPick.o left out."""
+    L = ref_driver.build_driver(os.path.join(HERE, "ref_lr_sgr_driver.c"), out_dir, leave_out=("EbRestorationPick.o",), include=(HERE,))
     L.drv_lr_open.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4
     L.drv_lr_units.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     L.drv_sgr_search.argtypes = [C.c_int] + [C.c_void_p] * 8
@@ -205,7 +182,7 @@ def synthetic_walks(rng):
 
 
 def main():
-    assert mg.reference_available(), "needs the reference sources and oracle/_ref/obj_all (python -c 'import __graft_entry__ as g; g.build()')"
+    assert reference_available(), "needs the reference sources and oracle/_ref/obj_all (python -c 'import __graft_entry__ as g; g.build()')"
     rng = np.random.default_rng(20261019)
     lrz = dict(np.load(os.path.join(HERE, "lr.npz")))
     out = {"lr_case": np.array(LR_CASES, np.int32), "dump_ep": np.array(DUMP_EP, np.int32), "trace_cap": np.array(TRACE_CAP, np.int32)}
@@ -312,13 +289,7 @@ def main():
     out["syn_walk_ep"], out["syn_walk_start"] = np.array([s[2] for s in syn], np.int32), np.array([s[3] for s in syn], np.int32)
     out["syn_walk_xqd"], out["syn_walk_err"], out["syn_walk_ntrials"] = np.array(fin, np.int32), np.array(errs, np.int64), np.array(ntr, np.int32)
     np.savez_compressed(OUT, **out)
-    sizes = {}
-    for k, v in out.items():
-        bio = io.BytesIO()
-        np.savez_compressed(bio, a=v)
-        g = k.split("_", 1)[1].rstrip("0123456789") if k[0] in "cx" and k[1].isdigit() else k
-        sizes[g] = sizes.get(g, 0) + bio.getbuffer().nbytes
-    print(sorted(sizes.items(), key=lambda kv: -kv[1])[:8])
+    mg.print_sizes(out)
     print(f"wrote {OUT}: {os.path.getsize(OUT) / 1e6:.2f} MB")
 
 

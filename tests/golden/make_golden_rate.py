@@ -18,7 +18,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python"), ROOT]
 
 import rate_util  # noqa: E402
 import svtav1_hip  # noqa: E402

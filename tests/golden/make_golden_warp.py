@@ -16,7 +16,6 @@ fractions next to 0 and next to 1), windows clamped at each picture edge in luma
 on every edge.  The filter table itself is not stored: it is pinned through these outputs."""
 import ctypes as C
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -24,14 +23,15 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+sys.path[:0] = [HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python"), ROOT]
 
 import make_golden_inter_pred as mgi  # noqa: E402
 import warp_util as wu  # noqa: E402
+from oracle import ref_driver  # noqa: E402
+from oracle.ref_driver import reference_available  # noqa: E402
 
-REF_ROOT, OBJ_ALL, PIC, BORDER, FILL = mgi.REF_ROOT, mgi.OBJ_ALL, mgi.PIC, mgi.BORDER, mgi.FILL
+PIC, BORDER, FILL = mgi.PIC, mgi.BORDER, mgi.FILL
 OUT = os.path.join(HERE, "warp.npz")
-reference_available = mgi.reference_available
 
 
 def reference_picture(bd):
@@ -39,29 +39,8 @@ def reference_picture(bd):
 
 
 def build_driver(out_dir):
-    """Compile the driver and link it with the reference objects: the recipe of make_golden_inter_pred.build_driver (--gc-sections from the
-    drv_* roots, EbEncHandle.o left out, NASM-only symbols that stay unresolved made weak)."""
-    S = os.path.join(REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(HERE, "ref_warp_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_warp.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL) if o.endswith(".o") and o != "EbEncHandle.o")
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, *objs, o, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """ref_warp_driver.c by the recipe of oracle/ref_driver.py, with its signatures."""
+    L = ref_driver.build_driver(os.path.join(HERE, "ref_warp_driver.c"), out_dir)
     L.drv_init.restype = C.c_int
     L.drv_shear.restype = C.c_int
     L.drv_shear.argtypes = [C.c_void_p, C.c_void_p]

@@ -4,9 +4,11 @@ reference (Source/Lib/Codec/...).  Each TU is vectorised over its coefficients: 
 the mask iscan < eob."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from oracle import ref_driver
+from oracle.ref_driver import reference_available  # noqa: F401
 
 # TxSize tables (EbDefinitions.h:1178-1219, EbTransforms.h:61-81, EbPictureControlSet.h:63)
 TX_W = np.array([4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64])
@@ -201,40 +203,11 @@ def decide(tx_size, lam, cands):
 # the reference driver (tests/golden/ref_coeff_rate_driver.c), built where the reference and the oracle's objects exist
 # ---------------------------------------------------------------------------------------------------------------------
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_ROOT = os.environ.get("SVT_REFERENCE_ROOT", "/root/reference")
-OBJ_ALL = os.path.join(ROOT, "oracle", "_ref", "obj_all")
-
-
-def reference_available():
-    return os.path.isdir(os.path.join(REF_ROOT, "Source", "Lib", "Codec")) and os.path.isdir(OBJ_ALL) and bool(os.listdir(OBJ_ALL))
 
 
 def build_reference_driver(out_dir):
-    """Compile the driver and link it with the reference objects into out_dir/libref_rate.so (the recipe of oracle/build_ref.sh for
-    libsvtref_me.so: --gc-sections from the exported drv_* roots).  The driver defines the RTCD pointers itself, so the encoder's
-    EbEncHandle.o is left out; the handful of NASM-only functions whose ADDRESSES setup_rtcd_internal stores (none of them is called
-    here) are made weak references, which resolve to NULL."""
-    S = os.path.join(REF_ROOT, "Source")
-    inc = [f"-I{os.path.join(S, d)}" for d in ("API", "Lib/Codec", "Lib/C_DEFAULT", "Lib/ASM_SSE2", "Lib/ASM_SSSE3", "Lib/ASM_SSE4_1", "Lib/ASM_AVX2")]
-    src = os.path.join(ROOT, "tests", "golden", "ref_coeff_rate_driver.c")
-    obj, wobj = os.path.join(out_dir, "drv.o"), os.path.join(out_dir, "drv_weak.o")
-    so, vmap, weak = os.path.join(out_dir, "libref_rate.so"), os.path.join(out_dir, "drv.map"), os.path.join(out_dir, "weak.txt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu99", "-w", "-mavx2", "-fPIC", "-ffunction-sections", "-fdata-sections", *inc, "-c", src, "-o", obj])
-    with open(vmap, "w") as f:
-        f.write("{ global: drv_*; local: *; };\n")
-    objs = sorted(os.path.join(OBJ_ALL, o) for o in os.listdir(OBJ_ALL) if o.endswith(".o") and o != "EbEncHandle.o")
-
-    def link(o):
-        subprocess.check_call(["gcc", "-shared", "-o", so, *objs, o, "-Wl,--gc-sections", f"-Wl,--version-script={vmap}", "-lm", "-lpthread"])
-
-    link(obj)
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", so], text=True).split("\n")
-    names = [ln.split()[-1] for ln in und if ln.strip() and "@" not in ln.split()[-1]]
-    with open(weak, "w") as f:
-        f.write("\n".join(names) + "\n")
-    subprocess.check_call(["objcopy", f"--weaken-symbols={weak}", obj, wobj])
-    link(wobj)
-    L = C.CDLL(so, mode=os.RTLD_LAZY)
+    """The driver by the recipe of oracle/ref_driver.py, with its signatures."""
+    L = ref_driver.build_driver(os.path.join(ROOT, "tests", "golden", "ref_coeff_rate_driver.c"), out_dir)
     L.drv_init.restype = C.c_int
     L.drv_init.argtypes = [C.c_int]
     L.drv_tables.restype = None
