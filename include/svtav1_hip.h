@@ -466,6 +466,55 @@ int32_t svthip_pad_plane_dev(svthip_ctx *ctx, void *d_plane, uint32_t stride, ui
                              uint32_t pad_height, uint32_t sample_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Picture-analysis statistics of pictures that lie in the device pool: GatheringPictureStatistics
+ * (Codec/EbPictureAnalysisProcess.c:4742-4796, called at :5028) in three entries, 8-bit planes (the reference analyses the 8-bit
+ * planes at every bit depth).  All three take n_pics pictures of EQUAL dimensions per call, at most SVTHIP_HME_MAX_JOBS; pics and
+ * chroma_offsets are HOST arrays, every d_ pointer is device memory.  chroma_offsets[n_pics][2]: byte offsets in d_pool of Cb and
+ * Cr sample (0, 0), rows chroma_stride apart.  The reference finds a chroma block or region at ((origin + luma position) >> 1); with
+ * these offsets the origin is gone and the luma positions used (SB origins, region origins of pictures whose dimensions are
+ * multiples of 8) are even, so nothing is lost in the shift.  The offsets and chroma_stride must be EVEN, as the reference's
+ * (origin >> 1) of its even origins is; an odd one is refused.  Width and height must be multiples of 8 and at least 16.
+ * Rows are read as whole aligned dwords: a chroma row that does not start on a 4-byte boundary reads to the end of the dword in which
+ * its last sample lies.
+ *
+ * Out of scope, host code that reads the few KB these entries leave: EdgeDetectionMeanLumaChroma16x16 and EdgeDetection
+ * (:4269-4487, serial walks over the per-SB tables with potential_logo_sb and a picture-number gate); the SCD_MODE_0 arm of
+ * CalculateInputAverageIntensity (:4701-4726, which reads from the buffer's first byte, border samples this library is never given);
+ * noise detection, denoising (:1273-1625, :3007-4037) and film-grain estimation.
+ *
+ * svthip_pa_block_stats_dev -- ComputeBlockMeanComputeVariance (:1986-3005), ComputeChromaBlockMean / ZeroOutChromaBlockMean
+ * (:1626-1979) and the SB loop of ComputePictureSpatialStatistics (:4633-4670), leaves as ASM_SSE2/EbComputeMean_Intrinsic_SSE2.c:9-146.
+ * sub_precision: 0 = BLOCK_MEAN_PREC_FULL, 1 = BLOCK_MEAN_PREC_SUB (rows 0, 2, 4, 6 of every 8x8; the reference's setting outside
+ * M0, Codec/EbResourceCoordinationProcess.c:875-877).  Outputs for n_sb = ceil(width / 64) * ceil(height / 64) SBs in raster order, entries
+ * in ME_TIER_ZERO_PU order (64x64, four 32x32, sixteen 16x16, sixty-four 8x8, each in raster order):
+ *   d_y_mean [n_pics][n_sb][85] yMean, d_variance [n_pics][n_sb][85] variance, d_cb_mean / d_cr_mean [n_pics][n_sb][21] cbMean / crMean.
+ * Luma is computed for every SB; an incomplete one reads up to 56 samples into the replicated border of the full-resolution plane,
+ * so svthip_pa_derive_planes_dev must have run on the pictures.  Chroma means of an SB that is not wholly inside the picture are 0.
+ * Bit-identical to the reference, its 64x64 chroma mean (m32[0] + m32[1] + m32[3] + m32[3]) >> 2 (:1926-1927) included. */
+int32_t svthip_pa_block_stats_dev(svthip_ctx *ctx, const uint8_t *d_pool, const svthip_pa_picture *pics, uint32_t n_pics,
+                                  const int64_t *chroma_offsets, uint32_t chroma_stride, uint32_t sub_precision, uint8_t *d_y_mean,
+                                  uint16_t *d_variance, uint8_t *d_cb_mean, uint8_t *d_cr_mean, void *stream);
+
+/* DetermineHomogeneousRegionInPicture (Codec/EbPictureAnalysisProcess.c:4491-4607) and pic_avg_variance (:4669-4672) from the
+ * d_variance table of svthip_pa_block_stats_dev:
+ *   d_var_of_var32x32 [n_pics][n_sb][4] var_of_var32x32_based_sb_array (all ones for an incomplete SB),
+ *   d_homogeneous [n_pics][n_sb] sb_homogeneous_area_array,
+ *   d_picture [n_pics][4] = pic_avg_variance, very_low_var_pic_flag, logo_pic_flag, the number of complete SBs.
+ * Width and height must be at least 64: the reference divides by the number of complete SBs. */
+int32_t svthip_pa_homogeneity_dev(svthip_ctx *ctx, const uint16_t *d_variance, uint32_t width, uint32_t height, uint32_t n_pics,
+                                  uint64_t *d_var_of_var32x32, uint8_t *d_homogeneous, uint32_t *d_picture, void *stream);
+
+/* The region histograms and average intensities of scene-change detection, SCD_MODE_1 (Codec/EbPictureAnalysisProcess.c:4728-4732):
+ * CalculateHistogram (:131-155), SubSampleLumaGeneratePixelIntensityHistogramBins (:4129-4184, every sample of the 1/16 plane, so
+ * svthip_pa_derive_planes_dev must have built it), SubSampleChromaGeneratePixelIntensityHistogramBins (:4186-4267, every 4th column of
+ * every 4th row of the chroma planes) and CalculateInputAverageIntensity (:4691-4735), 4 x 4 regions:
+ *   d_histogram [n_pics][4][4][3][256] picture_histogram[region x][region y][plane], d_region_intensity [n_pics][4][4][3]
+ *   average_intensity_per_region, d_average_intensity [n_pics][3] average_intensity (the uint8_t values the reference stores). */
+int32_t svthip_pa_histograms_dev(svthip_ctx *ctx, const uint8_t *d_pool, const svthip_pa_picture *pics, uint32_t n_pics,
+                                 const int64_t *chroma_offsets, uint32_t chroma_stride, uint32_t *d_histogram,
+                                 uint32_t *d_region_intensity, uint32_t *d_average_intensity, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SadLoopKernel for a batch of blocks: NxMSadLoopKernel_funcPtrArray[asm_type] (Codec/EbComputeSAD.h:183-189) = SadLoopKernel
  * (C_DEFAULT/EbComputeSAD_C.c:73-119; signature EB_SADLOOPKERNELNxM_TYPE, Codec/EbComputeSAD.h:38-51) with the reference's full
  * argument set, for n_blocks blocks per launch.  Block i: source block at d_src + src_offset (rows src_stride apart), search grid

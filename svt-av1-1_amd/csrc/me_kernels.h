@@ -242,6 +242,14 @@ hipError_t launch_cdef_pick(const uint64_t* mse, const uint8_t* counted, uint32_
 hipError_t launch_cdef_frame(const svthip_cdef_picture& pic, const svthip_cdef_result* result, const int8_t* fb_strength, int plane_start,
                              int plane_end, int bd, hipStream_t s);
 hipError_t launch_cdef_dist_8x8(const uint16_t* dst, const uint16_t* src, uint32_t n, int coeff_shift, uint64_t* out, hipStream_t s);
+// pa_stats.hip: picture-analysis statistics -- block means / variances, homogeneity, histograms (kernels: pa_stats_kernels.h)
+hipError_t launch_pa_block_stats(const uint8_t* pool, const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n, uint32_t chroma_stride,
+                                 int sub_precision, uint32_t n_sb, uint8_t* y_mean, uint16_t* variance, uint8_t* cb_mean, uint8_t* cr_mean, hipStream_t s);
+hipError_t launch_pa_homogeneity(const uint16_t* variance, uint32_t width, uint32_t height, uint32_t n, uint32_t n_sb, uint64_t* var_of_var32x32,
+                                 uint8_t* homogeneous, uint32_t* picture, hipStream_t s);
+inline size_t pa_region_sum_bytes(size_t n) { return sizeof(uint32_t) * 16 * 3 * n; }  // SLOT_PA_REGION_SUMS: [n][16][3]
+hipError_t launch_pa_histograms(const uint8_t* pool, const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n, uint32_t chroma_stride,
+                                uint32_t* histogram, uint32_t* region_intensity, uint32_t* average_intensity, uint32_t* region_sum, hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

@@ -1,0 +1,64 @@
+// svt-av1-1_amd/csrc/pa_stats.hip
+//
+// Picture-analysis statistics of pictures that are already in device memory, gfx950: the launches of pa_stats_kernels.h.
+// Replaces GatheringPictureStatistics (Codec/EbPictureAnalysisProcess.c:4742-4796) of the reference in three entries: the per-SB block
+// means and variances of luma and the block means of chroma, the homogeneity flags and picture variance derived from that variance
+// table, and the region histograms with the region and picture average intensities.  One read pass over the padded luma plane, the
+// chroma planes and the 1/16 plane that svthip_pa_derive_planes_dev left in the pool; a few KB written per picture.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/svtav1_hip.h"
+#include "me_kernels.h"
+#include "pa_stats_kernels.h"
+
+namespace svthip {
+
+namespace {
+
+PaStatsJobTable pa_stats_job_table(const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n)
+{
+    PaStatsJobTable jt;
+    memset(&jt, 0, sizeof(jt));
+    for (uint32_t j = 0; j < n; j++) {
+        jt.pic[j] = pics[j];
+        jt.chroma[j][0] = chroma_offsets[2 * j];
+        jt.chroma[j][1] = chroma_offsets[2 * j + 1];
+    }
+    return jt;
+}
+
+}  // namespace
+
+hipError_t launch_pa_block_stats(const uint8_t* pool, const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n, uint32_t chroma_stride,
+                                 int sub_precision, uint32_t n_sb, uint8_t* y_mean, uint16_t* variance, uint8_t* cb_mean, uint8_t* cr_mean, hipStream_t s)
+{
+    const PaStatsJobTable jt = pa_stats_job_table(pics, chroma_offsets, n);
+    if (sub_precision)
+        hipLaunchKernelGGL(pa_block_stats_kernel<1>, dim3(n_sb, n), dim3(64), 0, s, pool, jt, chroma_stride, y_mean, variance, cb_mean, cr_mean);
+    else
+        hipLaunchKernelGGL(pa_block_stats_kernel<0>, dim3(n_sb, n), dim3(64), 0, s, pool, jt, chroma_stride, y_mean, variance, cb_mean, cr_mean);
+    return hipGetLastError();
+}
+
+hipError_t launch_pa_homogeneity(const uint16_t* variance, uint32_t width, uint32_t height, uint32_t n, uint32_t n_sb, uint64_t* var_of_var32x32,
+                                 uint8_t* homogeneous, uint32_t* picture, hipStream_t s)
+{
+    hipLaunchKernelGGL(pa_homogeneity_kernel, dim3(n), dim3(256), 0, s, variance, width, height, n_sb, var_of_var32x32, homogeneous, picture);
+    return hipGetLastError();
+}
+
+// region_sum: [n][16][3] uint32 of scratch between the two launches
+hipError_t launch_pa_histograms(const uint8_t* pool, const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n, uint32_t chroma_stride,
+                                uint32_t* histogram, uint32_t* region_intensity, uint32_t* average_intensity, uint32_t* region_sum, hipStream_t s)
+{
+    const PaStatsJobTable jt = pa_stats_job_table(pics, chroma_offsets, n);
+    hipLaunchKernelGGL(pa_histogram_kernel, dim3(16, 3, n), dim3(256), 0, s, pool, jt, chroma_stride, histogram, region_intensity, region_sum);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pa_average_kernel, dim3(n), dim3(64), 0, s, (const uint32_t*)region_sum, jt, average_intensity);
+    return hipGetLastError();
+}
+
+}  // namespace svthip

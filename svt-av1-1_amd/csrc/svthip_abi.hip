@@ -32,6 +32,7 @@ enum Slot {
     SLOT_TU_PLANES, SLOT_TU_TABLES, SLOT_TU_COEFFS, SLOT_TU_OUTPUTS,  // svthip_encode_tu_batch, three arrays each: slot3
     SLOT_INTER_JOBS,      // job lists of the whole-PU inter prediction / warped prediction entries
     SLOT_INTER_REFUSED,   // their refused-PU counter
+    SLOT_PA_REGION_SUMS,  // region sums of svthip_pa_histograms_dev on their way to the picture averages: pa_region_sum_bytes
     SLOT_COUNT
 };
 
@@ -489,6 +490,31 @@ int32_t encode_tu_common(svthip_ctx* ctx, const void* d_src, const void* d_pred,
 bool ois_reads_me(const svthip_ois_params* p)
 {
     return !p->slice_is_intra && !(p->temporal_layer_index == 0 && !p->input_resolution_4k) && !p->limit_ois_to_dc_mode_flag;
+}
+
+// what the block-statistics and histogram entries check of their pictures: one geometry per launch, planes the kernels may read as dwords
+int32_t check_pa_stats_pictures(const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, const int64_t* chroma_offsets,
+                                uint32_t chroma_stride, bool reads_sixteenth)
+{
+    if (n_pics > SVTHIP_HME_MAX_JOBS) return fail(SVTHIP_ERR_BAD_PARAMETER, "at most %d pictures per call (got %u)", SVTHIP_HME_MAX_JOBS, (unsigned)n_pics);
+    const uint32_t w = pics[0].width, h = pics[0].height;
+    if ((w & 7) || (h & 7) || w < 16 || h < 16)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be multiples of 8, at least 16 (%ux%u)", (unsigned)w, (unsigned)h);
+    if (!aligned(d_pool, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "the pool must be 4-byte aligned");
+    if ((chroma_stride & 1u) || chroma_stride < w / 2)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "chroma stride must be even and >= width/2 (got %u)", (unsigned)chroma_stride);
+    for (uint32_t j = 0; j < n_pics; j++) {
+        const svthip_pa_picture& p = pics[j];
+        if (p.width != w || p.height != h) return fail(SVTHIP_ERR_BAD_PARAMETER, "the pictures of one call must have equal dimensions (picture %d)", (int)j);
+        if (p.full_stride < w + 136u || (p.full_stride & 3u) || (p.full_offset & 3) || p.full_offset < 0)
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "full-resolution stride must be a multiple of 4 and >= width + 136, offset a multiple of 4 (picture %d)", (int)j);
+        if (reads_sixteenth && (p.sixteenth_stride < (w >> 2) + 32u || p.sixteenth_offset < 0))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "sixteenth stride must be >= width/4 + 32 (picture %d)", (int)j);
+        for (int c = 0; c < 2; c++)
+            if (chroma_offsets[2 * j + c] < 0 || (chroma_offsets[2 * j + c] & 1))
+                return fail(SVTHIP_ERR_BAD_PARAMETER, "chroma offsets must be even and not negative (picture %d)", (int)j);
+    }
+    return SVTHIP_OK;
 }
 
 // ---------------------------------------------------------------- prediction
@@ -979,6 +1005,7 @@ int32_t svthip_reserve(svthip_ctx* ctx, uint32_t width, uint32_t height, uint32_
     TRY(ensure_scratch(ctx, SLOT_ME_CHAIN, me_chain_layout(n, n_pu).total));
     TRY(ensure_scratch(ctx, SLOT_BIPRED_SQ, bipred_sq_bytes(n)));
     TRY(ensure_scratch(ctx, SLOT_ME_PRED, me_pred_bytes(n, n_pu)));
+    TRY(ensure_scratch(ctx, SLOT_PA_REGION_SUMS, svthip::pa_region_sum_bytes(SVTHIP_HME_MAX_JOBS)));
     if (host_forms) {
         TRY(ensure_scratch(ctx, SLOT_HOST_POOL, host_pool_layout(width, height).total(3)));
         TRY(ensure_scratch(ctx, SLOT_SB_TABLE, sb_table_bytes(n_sb)));
@@ -1351,6 +1378,55 @@ int32_t svthip_open_loop_intra_search_batch_dev(svthip_ctx* ctx, const uint8_t* 
                            n_sb, nj, d_me ? d_me + first * me_pu_stride : nullptr, me_pu_stride, d_cand + first * 85 * 18, d_total + first * 85);
         HIP_TRY(hipGetLastError());
     }
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_block_stats_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics,
+                                  const int64_t* chroma_offsets, uint32_t chroma_stride, uint32_t sub_precision, uint8_t* d_y_mean,
+                                  uint16_t* d_variance, uint8_t* d_cb_mean, uint8_t* d_cr_mean, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics, chroma_offsets, d_y_mean, d_variance, d_cb_mean, d_cr_mean}));
+    if (sub_precision > 1) return fail(SVTHIP_ERR_BAD_PARAMETER, "sub_precision must be 0 (FULL) or 1 (SUB), got %u", (unsigned)sub_precision);
+    if (!aligned(d_variance, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "the variance table must be 2-byte aligned");
+    TRY(check_pa_stats_pictures(d_pool, pics, n_pics, chroma_offsets, chroma_stride, false));
+    HIP_TRY(svthip::launch_pa_block_stats(d_pool, pics, chroma_offsets, n_pics, chroma_stride, (int)sub_precision, sb_count(pics[0].width, pics[0].height),
+                                          d_y_mean, d_variance, d_cb_mean, d_cr_mean, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_homogeneity_dev(svthip_ctx* ctx, const uint16_t* d_variance, uint32_t width, uint32_t height, uint32_t n_pics,
+                                  uint64_t* d_var_of_var32x32, uint8_t* d_homogeneous, uint32_t* d_picture, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_variance, d_var_of_var32x32, d_homogeneous, d_picture}));
+    if (n_pics > SVTHIP_HME_MAX_JOBS) return fail(SVTHIP_ERR_BAD_PARAMETER, "at most %d pictures per call (got %u)", SVTHIP_HME_MAX_JOBS, (unsigned)n_pics);
+    // a picture without a complete SB has nothing to take the low-variance percentage of (the reference divides by zero)
+    if ((width & 7) || (height & 7) || width < 64 || height < 64 || width > 65535 || height > 65535)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be multiples of 8, at least 64 (%ux%u)", (unsigned)width, (unsigned)height);
+    if (!aligned(d_variance, 2) || !aligned(d_var_of_var32x32, 8) || !aligned(d_picture, 4))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_variance must be 2-byte, d_var_of_var32x32 8-byte, d_picture 4-byte aligned");
+    HIP_TRY(svthip::launch_pa_homogeneity(d_variance, width, height, n_pics, sb_count(width, height), d_var_of_var32x32, d_homogeneous, d_picture,
+                                          call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_histograms_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics,
+                                 const int64_t* chroma_offsets, uint32_t chroma_stride, uint32_t* d_histogram, uint32_t* d_region_intensity,
+                                 uint32_t* d_average_intensity, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics, chroma_offsets, d_histogram, d_region_intensity, d_average_intensity}));
+    if (!aligned({d_histogram, d_region_intensity, d_average_intensity}, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "the output arrays must be 4-byte aligned");
+    TRY(check_pa_stats_pictures(d_pool, pics, n_pics, chroma_offsets, chroma_stride, true));
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(ensure_scratch(ctx, SLOT_PA_REGION_SUMS, svthip::pa_region_sum_bytes(SVTHIP_HME_MAX_JOBS)));  // 6 KB, sized once for the largest call
+    TRY(scratch_on_stream(ctx, s));
+    HIP_TRY(svthip::launch_pa_histograms(d_pool, pics, chroma_offsets, n_pics, chroma_stride, d_histogram, d_region_intensity, d_average_intensity,
+                                         slot_ptr<uint32_t>(ctx, SLOT_PA_REGION_SUMS), s));
     return SVTHIP_OK;
 }
 

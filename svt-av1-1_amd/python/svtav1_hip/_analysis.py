@@ -30,3 +30,29 @@ class PictureAnalysis:
         n = len(curs)
         _check(lib().svthip_open_loop_intra_search_batch_dev(self._h, d_pool, (PaPictureDesc * n)(*curs), n, C.byref(params), d_sb, n_sb,
                                                              d_me, me_pu_stride, d_cand, d_total, stream))
+
+    def pa_block_stats_dev(self, d_pool, pics, chroma_offsets, chroma_stride, sub_precision, d_y_mean, d_variance, d_cb_mean, d_cr_mean, stream=None):
+        """ComputeBlockMeanComputeVariance / ComputeChromaBlockMean over len(pics) pictures of equal size: d_y_mean, d_variance [n][n_sb][85],
+        d_cb_mean, d_cr_mean [n][n_sb][21].  chroma_offsets: per picture the pool offsets of Cb and Cr sample (0, 0)."""
+        n = len(pics)
+        _check(lib().svthip_pa_block_stats_dev(self._h, d_pool, (PaPictureDesc * n)(*pics), n, _chroma_offsets(chroma_offsets, n), chroma_stride,
+                                               int(sub_precision), d_y_mean, d_variance, d_cb_mean, d_cr_mean, stream))
+
+    def pa_homogeneity_dev(self, d_variance, width, height, n_pics, d_var_of_var32x32, d_homogeneous, d_picture, stream=None):
+        """DetermineHomogeneousRegionInPicture and pic_avg_variance from d_variance: d_var_of_var32x32 [n][n_sb][4] u64, d_homogeneous
+        [n][n_sb] u8, d_picture [n][4] u32 = pic_avg_variance, very_low_var_pic_flag, logo_pic_flag, complete SBs."""
+        _check(lib().svthip_pa_homogeneity_dev(self._h, d_variance, width, height, n_pics, d_var_of_var32x32, d_homogeneous, d_picture, stream))
+
+    def pa_histograms_dev(self, d_pool, pics, chroma_offsets, chroma_stride, d_histogram, d_region_intensity, d_average_intensity, stream=None):
+        """The SCD_MODE_1 histograms and intensities: d_histogram [n][4][4][3][256] u32, d_region_intensity [n][4][4][3] u32,
+        d_average_intensity [n][3] u32."""
+        n = len(pics)
+        _check(lib().svthip_pa_histograms_dev(self._h, d_pool, (PaPictureDesc * n)(*pics), n, _chroma_offsets(chroma_offsets, n), chroma_stride,
+                                              d_histogram, d_region_intensity, d_average_intensity, stream))
+
+
+def _chroma_offsets(chroma_offsets, n):
+    """[n][2] pool offsets as the int64_t array the entries take"""
+    flat = [int(v) for pair in chroma_offsets for v in pair]
+    assert len(flat) == 2 * n, "one (Cb, Cr) offset pair per picture"
+    return (C.c_int64 * (2 * n))(*flat)
