@@ -480,7 +480,9 @@ int32_t svthip_pad_plane_dev(svthip_ctx *ctx, void *d_plane, uint32_t stride, ui
  * Out of scope, host code that reads the few KB these entries leave: EdgeDetectionMeanLumaChroma16x16 and EdgeDetection
  * (:4269-4487, serial walks over the per-SB tables with potential_logo_sb and a picture-number gate); the SCD_MODE_0 arm of
  * CalculateInputAverageIntensity (:4701-4726, which reads from the buffer's first byte, border samples this library is never given);
- * noise detection, denoising (:1273-1625, :3007-4037) and film-grain estimation.
+ * film-grain estimation (aom_denoise_and_model_run), the decimated noise detectors (QuarterSampleDenoise / SubSampleDenoise,
+ * :3412-4037, dead under ENCODER_MODE_CLEANUP) and the strong denoising filters (:1273-1408, :3024-3098).  Full-sample noise detection
+ * and the weak denoising arms are svthip_pa_noise_detect_dev and svthip_pa_denoise_dev below.
  *
  * svthip_pa_block_stats_dev -- ComputeBlockMeanComputeVariance (:1986-3005), ComputeChromaBlockMean / ZeroOutChromaBlockMean
  * (:1626-1979) and the SB loop of ComputePictureSpatialStatistics (:4633-4670), leaves as ASM_SSE2/EbComputeMean_Intrinsic_SSE2.c:9-146.
@@ -513,6 +515,49 @@ int32_t svthip_pa_homogeneity_dev(svthip_ctx *ctx, const uint16_t *d_variance, u
 int32_t svthip_pa_histograms_dev(svthip_ctx *ctx, const uint8_t *d_pool, const svthip_pa_picture *pics, uint32_t n_pics,
                                  const int64_t *chroma_offsets, uint32_t chroma_stride, uint32_t *d_histogram,
                                  uint32_t *d_region_intensity, uint32_t *d_average_intensity, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Input-picture noise detection and denoising: FullSampleDenoise (Codec/EbPictureAnalysisProcess.c:3357-3410), which
+ * PicturePreProcessingOperations (:4057-4123) runs on every input picture BEFORE padding and decimation (:5005 precedes :5017-5025).
+ * Both entries read and write only the width x height interior of the planes, never a border sample, so they run on a pool whose
+ * borders are not built yet.  Call order for a device-resident front end: upload the interiors -> svthip_pa_noise_detect_dev ->
+ * (svthip_pa_denoise_dev) -> svthip_pa_derive_planes_dev -> the statistics entries above.  n_pics pictures of EQUAL dimensions per call,
+ * at most SVTHIP_HME_MAX_JOBS; width and height multiples of 8 and at least 64 (the reference divides by the number of complete SBs).
+ *
+ * svthip_pa_noise_detect_dev -- DetectInputPictureNoise (:3181-3320) with the resets of FullSampleDenoise (:3373-3378).  The weak luma
+ * filter of noiseExtractLumaWeak (:1501-1561, getFilteredTypes type 0 :1207-1213): for every luma sample not on the picture's first or
+ * last row or column den = (up + left + 4 c + right + down) / 8 and noise = max(c - den, 0); on those rows and columns den = c and
+ * noise = 0.  Per complete SB, with ComputeVariance64x64 (:360-1197; sub_precision as in svthip_pa_block_stats_dev):
+ *   d_sb_var [n_pics][n_sb][2]   the noise variance (raw 16.16) and the denoised variance >> 16; 0, 0 for an incomplete SB
+ *   d_flat_noise [n_pics][n_sb]  sb_flat_noise_array: denoised variance < FLAT_MAX_VAR (50) && noise variance > NOISE_MIN_LEVEL_M6_M7
+ *                                (120000, the constant the `if (0)` of :3254-3261 selects); 0 for an incomplete SB
+ *   d_picture [n_pics][4]        the sum over complete SBs of (noise variance >> 16); the number of complete SBs; pic_noise_class
+ *                                (EbDefinitions.h:2753-2764: the ladder of :3286-3316 on sum / count with noiseTh = 25 for heights up to
+ *                                720, classes >= PIC_NOISE_CLASS_4 clamped to PIC_NOISE_CLASS_3_1 as :3315); sum >= count, which is
+ *                                picNoiseVarianceFloat >= 1.0 (the double itself is sum / count)
+ * d_denoised: NULL, or [n_pics][height][denoised_stride] for the denoised luma of the whole picture, incomplete SBs included; nothing is
+ * written past `width` in a row.  8-byte aligned, denoised_stride a multiple of 8.  NULL is detection only, the configuration of the
+ * reference's own encoder (enable_denoise_flag is forced to 0, EbEncHandle.c:2120).  The reference's one-SB-row noise picture (:76,
+ * :3217) is not materialised.  Bit-identical to the reference's C and AVX2 paths, which agree. */
+int32_t svthip_pa_noise_detect_dev(svthip_ctx *ctx, const uint8_t *d_pool, const svthip_pa_picture *pics, uint32_t n_pics,
+                                   uint32_t sub_precision, uint8_t *d_denoised, uint32_t denoised_stride, uint64_t *d_sb_var,
+                                   uint8_t *d_flat_noise, uint32_t *d_picture, void *stream);
+
+/* DenoiseInputPicture (Codec/EbPictureAnalysisProcess.c:3007-3179) in place on the pool, from d_denoised, d_flat_noise and d_picture of
+ * svthip_pa_noise_detect_dev.  The arm is chosen per picture ON THE DEVICE from d_picture, without a host round trip:
+ *   pic_noise_class >= PIC_NOISE_CLASS_3_1 (:3099-3150): the luma interior becomes the denoised luma; Cb and Cr become
+ *     noiseExtractChromaWeak of themselves (:1414-1495, type 4: 1 2 1 / 2 4 2 / 1 2 1 over 16, outermost chroma rows and columns copied);
+ *   else sum >= count (:3151-3176): the luma of every SB with flat noise becomes the denoised luma, clipped to the picture;
+ *   else nothing is written.
+ * chroma_offsets / chroma_stride as for the statistics entries.  The chroma filter reads neighbours, so it does not run in place: after
+ * the luma has been copied out of it, d_denoised serves as the scratch (Cb in columns 0 .. width/2 - 1, Cr in width/2 .. width - 1 of
+ * the first height/2 rows of a whole-picture picture's part), as the reference's denoised chroma aliases its denoised luma (:71-73);
+ * a later launch on the same stream copies the chroma back.  d_denoised is therefore NOT the denoised luma any more afterwards.
+ * The strong-filter arm (:3024-3098) cannot be reached through the detector because of the clamp at :3315 and is not built.
+ * Borders and derived planes are stale afterwards, as in the reference: run svthip_pa_derive_planes_dev next. */
+int32_t svthip_pa_denoise_dev(svthip_ctx *ctx, uint8_t *d_pool, const svthip_pa_picture *pics, uint32_t n_pics,
+                              const int64_t *chroma_offsets, uint32_t chroma_stride, uint8_t *d_denoised, uint32_t denoised_stride,
+                              const uint8_t *d_flat_noise, const uint32_t *d_picture, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SadLoopKernel for a batch of blocks: NxMSadLoopKernel_funcPtrArray[asm_type] (Codec/EbComputeSAD.h:183-189) = SadLoopKernel

@@ -250,6 +250,11 @@ hipError_t launch_pa_homogeneity(const uint16_t* variance, uint32_t width, uint3
 inline size_t pa_region_sum_bytes(size_t n) { return sizeof(uint32_t) * 16 * 3 * n; }  // SLOT_PA_REGION_SUMS: [n][16][3]
 hipError_t launch_pa_histograms(const uint8_t* pool, const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n, uint32_t chroma_stride,
                                 uint32_t* histogram, uint32_t* region_intensity, uint32_t* average_intensity, uint32_t* region_sum, hipStream_t s);
+// pa_noise.hip: input-picture noise detection and the weak denoising arms (kernels: pa_noise_kernels.h)
+hipError_t launch_pa_noise_detect(const uint8_t* pool, const svthip_pa_picture* pics, uint32_t n, int sub_precision, uint32_t n_sb, uint8_t* denoised,
+                                  uint32_t denoised_stride, uint64_t* sb_var, uint8_t* flat_noise, uint32_t* picture, hipStream_t s);
+hipError_t launch_pa_denoise(uint8_t* pool, const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n, uint32_t chroma_stride, uint32_t n_sb,
+                             uint8_t* denoised, uint32_t denoised_stride, const uint8_t* flat_noise, const uint32_t* picture, hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

@@ -217,6 +217,9 @@ struct PaStatsJobTable {
     int64_t chroma[SVTHIP_HME_MAX_JOBS][2];
 };
 
+// pa_noise_kernels.h takes the arithmetic above and the job table and leaves the kernels to pa_stats.hip, their one translation unit
+#ifndef SVTHIP_PA_STATS_WITHOUT_KERNELS
+
 // grid (n_sb, n pictures), one wave per SB.  Lane l owns luma leaf l (row l >> 3, column l & 7: 8 neighbouring lanes read one 64-byte
 // row segment per load); lanes 0..31 also own a chroma leaf (Cb 0..15, Cr 16..31) of a complete SB.  The three levels above go
 // through LDS: luma nodes on lanes 0.., chroma nodes on lanes 32.. in the same step.
@@ -346,6 +349,7 @@ __global__ void __launch_bounds__(64) pa_average_kernel(const uint32_t* __restri
     average_intensity[blockIdx.x * 3 + threadIdx.x] = pa_average_intensity(t, jobs.pic[blockIdx.x].width, jobs.pic[blockIdx.x].height, (int)threadIdx.x);
 }
 
+#endif  // SVTHIP_PA_STATS_WITHOUT_KERNELS
 #endif  // __HIPCC__
 
 }  // namespace svthip

@@ -492,28 +492,48 @@ bool ois_reads_me(const svthip_ois_params* p)
     return !p->slice_is_intra && !(p->temporal_layer_index == 0 && !p->input_resolution_4k) && !p->limit_ois_to_dc_mode_flag;
 }
 
-// what the block-statistics and histogram entries check of their pictures: one geometry per launch, planes the kernels may read as dwords
-int32_t check_pa_stats_pictures(const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, const int64_t* chroma_offsets,
-                                uint32_t chroma_stride, bool reads_sixteenth)
+// what every picture-analysis entry that reads the full-resolution luma checks of its pictures: one geometry per launch, planes the kernels
+// may read as dwords
+int32_t check_pa_luma_pictures(const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, uint32_t min_dim)
 {
     if (n_pics > SVTHIP_HME_MAX_JOBS) return fail(SVTHIP_ERR_BAD_PARAMETER, "at most %d pictures per call (got %u)", SVTHIP_HME_MAX_JOBS, (unsigned)n_pics);
     const uint32_t w = pics[0].width, h = pics[0].height;
-    if ((w & 7) || (h & 7) || w < 16 || h < 16)
-        return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be multiples of 8, at least 16 (%ux%u)", (unsigned)w, (unsigned)h);
+    if ((w & 7) || (h & 7) || w < min_dim || h < min_dim)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be multiples of 8, at least %u (%ux%u)", (unsigned)min_dim, (unsigned)w, (unsigned)h);
     if (!aligned(d_pool, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "the pool must be 4-byte aligned");
-    if ((chroma_stride & 1u) || chroma_stride < w / 2)
-        return fail(SVTHIP_ERR_BAD_PARAMETER, "chroma stride must be even and >= width/2 (got %u)", (unsigned)chroma_stride);
     for (uint32_t j = 0; j < n_pics; j++) {
         const svthip_pa_picture& p = pics[j];
         if (p.width != w || p.height != h) return fail(SVTHIP_ERR_BAD_PARAMETER, "the pictures of one call must have equal dimensions (picture %d)", (int)j);
         if (p.full_stride < w + 136u || (p.full_stride & 3u) || (p.full_offset & 3) || p.full_offset < 0)
             return fail(SVTHIP_ERR_BAD_PARAMETER, "full-resolution stride must be a multiple of 4 and >= width + 136, offset a multiple of 4 (picture %d)", (int)j);
+    }
+    return SVTHIP_OK;
+}
+
+// and what the entries that read chroma (and the 1/16 plane) check on top
+int32_t check_pa_stats_pictures(const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, const int64_t* chroma_offsets,
+                                uint32_t chroma_stride, bool reads_sixteenth, uint32_t min_dim = 16)
+{
+    TRY(check_pa_luma_pictures(d_pool, pics, n_pics, min_dim));
+    const uint32_t w = pics[0].width;
+    if ((chroma_stride & 1u) || chroma_stride < w / 2)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "chroma stride must be even and >= width/2 (got %u)", (unsigned)chroma_stride);
+    for (uint32_t j = 0; j < n_pics; j++) {
+        const svthip_pa_picture& p = pics[j];
         if (reads_sixteenth && (p.sixteenth_stride < (w >> 2) + 32u || p.sixteenth_offset < 0))
             return fail(SVTHIP_ERR_BAD_PARAMETER, "sixteenth stride must be >= width/4 + 32 (picture %d)", (int)j);
         for (int c = 0; c < 2; c++)
             if (chroma_offsets[2 * j + c] < 0 || (chroma_offsets[2 * j + c] & 1))
                 return fail(SVTHIP_ERR_BAD_PARAMETER, "chroma offsets must be even and not negative (picture %d)", (int)j);
     }
+    return SVTHIP_OK;
+}
+
+// d_denoised of the noise entries: [n_pics][height][denoised_stride], rows written and read as 8-byte pieces
+int32_t check_pa_denoised(const uint8_t* d_denoised, uint32_t denoised_stride, uint32_t width)
+{
+    if (denoised_stride < width || (denoised_stride & 7u) || !aligned(d_denoised, 8))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_denoised must be 8-byte aligned, its stride a multiple of 8 and >= width (got %u)", (unsigned)denoised_stride);
     return SVTHIP_OK;
 }
 
@@ -1427,6 +1447,38 @@ int32_t svthip_pa_histograms_dev(svthip_ctx* ctx, const uint8_t* d_pool, const s
     TRY(scratch_on_stream(ctx, s));
     HIP_TRY(svthip::launch_pa_histograms(d_pool, pics, chroma_offsets, n_pics, chroma_stride, d_histogram, d_region_intensity, d_average_intensity,
                                          slot_ptr<uint32_t>(ctx, SLOT_PA_REGION_SUMS), s));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_noise_detect_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, uint32_t sub_precision,
+                                   uint8_t* d_denoised, uint32_t denoised_stride, uint64_t* d_sb_var, uint8_t* d_flat_noise, uint32_t* d_picture,
+                                   void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics, d_sb_var, d_flat_noise, d_picture}));
+    if (sub_precision > 1) return fail(SVTHIP_ERR_BAD_PARAMETER, "sub_precision must be 0 (FULL) or 1 (SUB), got %u", (unsigned)sub_precision);
+    if (!aligned(d_sb_var, 8) || !aligned(d_picture, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sb_var must be 8-byte, d_picture 4-byte aligned");
+    // a picture without a complete SB has no average noise variance (the reference divides by zero)
+    TRY(check_pa_luma_pictures(d_pool, pics, n_pics, 64));
+    if (d_denoised) TRY(check_pa_denoised(d_denoised, denoised_stride, pics[0].width));
+    HIP_TRY(svthip::launch_pa_noise_detect(d_pool, pics, n_pics, (int)sub_precision, sb_count(pics[0].width, pics[0].height), d_denoised, denoised_stride,
+                                           d_sb_var, d_flat_noise, d_picture, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_denoise_dev(svthip_ctx* ctx, uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, const int64_t* chroma_offsets,
+                              uint32_t chroma_stride, uint8_t* d_denoised, uint32_t denoised_stride, const uint8_t* d_flat_noise,
+                              const uint32_t* d_picture, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics, chroma_offsets, d_denoised, d_flat_noise, d_picture}));
+    if (!aligned(d_picture, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_picture must be 4-byte aligned");
+    TRY(check_pa_stats_pictures(d_pool, pics, n_pics, chroma_offsets, chroma_stride, false, 64));
+    TRY(check_pa_denoised(d_denoised, denoised_stride, pics[0].width));
+    HIP_TRY(svthip::launch_pa_denoise(d_pool, pics, chroma_offsets, n_pics, chroma_stride, sb_count(pics[0].width, pics[0].height), d_denoised,
+                                      denoised_stride, d_flat_noise, d_picture, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 

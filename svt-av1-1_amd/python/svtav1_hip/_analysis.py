@@ -50,6 +50,20 @@ class PictureAnalysis:
         _check(lib().svthip_pa_histograms_dev(self._h, d_pool, (PaPictureDesc * n)(*pics), n, _chroma_offsets(chroma_offsets, n), chroma_stride,
                                               d_histogram, d_region_intensity, d_average_intensity, stream))
 
+    def pa_noise_detect_dev(self, d_pool, pics, sub_precision, d_denoised, denoised_stride, d_sb_var, d_flat_noise, d_picture, stream=None):
+        """DetectInputPictureNoise over len(pics) pictures of equal size, before the borders exist: d_sb_var [n][n_sb][2] u64 (noise variance
+        raw, denoised variance >> 16), d_flat_noise [n][n_sb] u8, d_picture [n][4] u32 = sum, complete SBs, pic_noise_class, sum >= count.
+        d_denoised: None (detection only) or [n][height][denoised_stride] u8 for the denoised luma."""
+        n = len(pics)
+        _check(lib().svthip_pa_noise_detect_dev(self._h, d_pool, (PaPictureDesc * n)(*pics), n, int(sub_precision), d_denoised, denoised_stride,
+                                                d_sb_var, d_flat_noise, d_picture, stream))
+
+    def pa_denoise_dev(self, d_pool, pics, chroma_offsets, chroma_stride, d_denoised, denoised_stride, d_flat_noise, d_picture, stream=None):
+        """DenoiseInputPicture in place on the pool, the arm chosen on the device from d_picture; d_denoised is used up as chroma scratch."""
+        n = len(pics)
+        _check(lib().svthip_pa_denoise_dev(self._h, d_pool, (PaPictureDesc * n)(*pics), n, _chroma_offsets(chroma_offsets, n), chroma_stride,
+                                           d_denoised, denoised_stride, d_flat_noise, d_picture, stream))
+
 
 def _chroma_offsets(chroma_offsets, n):
     """[n][2] pool offsets as the int64_t array the entries take"""
