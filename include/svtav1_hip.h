@@ -1260,6 +1260,111 @@ int32_t svthip_av1_highbd_lr_filter_frame_dev(svthip_ctx *ctx, const svthip_lr_p
                                               const uint8_t *d_unit_type, const int16_t *d_taps, const int32_t *d_sgrproj, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * AV1 film-grain synthesis: av1_add_film_grain (Codec/EbEncDecProcess.c:2001-2069) -> av1_add_film_grain_run
+ * (Codec/grainSynthesis.c:995-1382), the last thing ReconOutput (Codec/EbEncDecProcess.c:680-700) does to a reconstructed picture when
+ * film_grain_params_present is set.  Pure integer arithmetic, bit-identical to the reference.  4:2:0 (the reference's wrapper hard-wires
+ * chroma_subsamp_x = chroma_subsamp_y = 1, :2012-2030), 8 and 10 bits, one picture per call, OUT OF PLACE as the reference (its wrapper
+ * copies the reconstruction into film_grain_picture_ptr, :2035-2051, and adds the grain there): d_dst stands in for that picture.
+ *
+ * svthip_film_grain_params mirrors aom_film_grain_t (Codec/grainSynthesis.h:29-81) field for field; the trailing reserved word makes the
+ * padding the compiler adds there explicit, so a reference host passes &pcs->film_grain_params unchanged.  It is read from HOST memory
+ * during the call.  apply_grain, update_parameters and bit_depth are IGNORED: the reference's av1_add_film_grain never looks at
+ * apply_grain (the caller gates on film_grain_params_present) and overwrites bit_depth from the buffer's (:2010-2030); here the entry
+ * (8-bit or highbd) and its bit_depth argument decide.
+ *
+ * What of the reference's behaviour is reproduced (Codec/grainSynthesis.c):
+ *  templates   1. the luma template draws on from random_register = random_seed with no row mix (:1014); Cb is re-seeded with
+ *                 init_random_generator(7 << 5), Cr with (11 << 5) (:515, :525)
+ *              2. Gaussian entries are rounded by 12 - bit_depth + grain_scale_shift (:472-482)
+ *              3. the autoregressive filter runs over rows 3.., columns 3 .. W - 4 in raster order and clamps to [grain_min, grain_max]
+ *                 at every sample (:484-497, :535-585)
+ *              4. the chroma luma term is the rounded 2x2 mean of the luma template at rows and columns ((i - 3) << 1) + 3 (:551-566); it
+ *                 exists only when num_y_points > 0 (:320, :368, :511)
+ *  offsets     5. every 32-row block row is seeded by init_random_generator(2 y), so luma_num is the block-row index (:1090, :459)
+ *              6. one 8-bit draw per block, left to right: offset_y the low nibble, offset_x the high; luma windows start at
+ *                 9 + 2 * offset, chroma windows at 6 + offset (:1093-1103)
+ *  overlap     7. the left 2 luma columns (1 chroma column) blend the left neighbour's RAW template columns 32, 33 (16) with this
+ *                 block's columns 0, 1 (0): 27/17 and 17/27 for luma, 23/22 for chroma, + 16 >> 5, clamped (:1105-1129, :931-959)
+ *              8. the top 2 rows (1 chroma row) blend the same way with the block above (:1185-1218, :961-991)
+ *              9. the 2x2 corner is the vertical blend of two horizontally blended strips: the upper row's strip rows 32, 33 and this
+ *                 row's strip rows 0, 1 (:1167-1182, :1304-1319)
+ *             10. blocks cut by the right or bottom edge use the AOMMIN of :1111, :1190, :1275-1276, a block that consists of the
+ *                 overlap strip only (width or height remainder 2) included
+ *  noise      11. chroma uses (luma[2i][2j] + luma[2i][2j + 1] + 1) >> 1 of the UN-NOISED luma, the even row only (:673-681)
+ *             12. index = ((average * luma_mult + mult * chroma) >> 6) + offset, clamped to the sample range; chroma_scaling_from_luma
+ *                 replaces the three constants by 64, 0, 0 and both chroma scaling tables by the luma table (:647-655, :1079-1082)
+ *             13. at 10 bits the offset is (offset << 2) - 1024 (:744, :749); at 8 bits offset - 256 (:635, :639)
+ *             14. the scaling table is indexed directly at 8 bits and interpolated at 10, with the x == 255 arm (:613-623)
+ *             15. clip_to_restricted_range clips to 16..235 (luma) and 16..240 (chroma), shifted by bit_depth - 8 (:659-669, :769-779)
+ *  scaling    16. init_scaling_function divides in integers and multiplies in 64 bits; entries are flat before the first and after the
+ *                 last point; a plane without points has an all-zero table and is copied unchanged (:588-609, :643-645)
+ * With num_y_points == 0 the reference's dealloc_arrays frees one pointer more than init_arrays allocated (:409 against :320); the
+ * arithmetic before that is well defined (luma copied, chroma filtered without the luma term) and is what this library computes.
+ *
+ * The table block, SVTHIP_FILM_GRAIN_TABLES_BYTES of int16_t (every value fits at 10 bits), in this order:
+ *   luma template [73][82] | Cb template [38][44] | Cr template [38][44] | scaling tables [3][256] (Y, Cb, Cr)
+ * The templates are the reference's luma_grain_block, cb_grain_block, cr_grain_block after generate_*_grain_block[s], the scaling
+ * tables its scaling_lut_y / _cb / _cr.  The template of a plane without scaling points is all zero.
+ *
+ * svthip_film_grain_tables_dev      builds the block for `params` at bit_depth 8 or 10 into d_tables (2-byte aligned): one launch
+ * svthip_av1_add_film_grain_dev     d_src[p] / d_dst[p]: device pointers to sample (0, 0) of plane p (Y, Cb, Cr), 8-bit samples; strides in
+ * svthip_av1_highbd_add_film_grain_dev   samples; uint16_t samples (2-byte aligned) for the highbd entry.  d_tables: the block built for the
+ *                                   same params and bit depth, or NULL: the entry then builds it in context scratch on the same stream
+ *                                   first (the one-call form).  Rows are moved as 8 luma / 4 chroma samples at once where the plane
+ *                                   pointers and strides are multiples of that, sample by sample otherwise.  Nothing outside the
+ *                                   width x height (chroma width/2 x height/2) interiors is read or written.
+ * Refused with SVTHIP_ERR_BAD_PARAMETER before any launch: a NULL context, parameter or plane pointer; d_dst[p] == d_src[p]; odd or zero
+ * width or height, or one above 65536; a stride smaller than the plane width; a bit depth other than 8 (8-bit entry) or 10 (highbd entry);
+ * num_y_points > 14, num_cb_points or num_cr_points > 10 (or negative); scaling-point x values not strictly increasing or outside 0..255
+ * (the reference divides by delta_x, :599) or y values outside 0..255; scaling_shift outside 8..11, ar_coeff_lag outside 0..3,
+ * ar_coeff_shift outside 6..9, grain_scale_shift outside 0..3; an AR coefficient outside -128..127; cb_mult, cr_mult, cb_luma_mult or
+ * cr_luma_mult outside 0..255; cb_offset or cr_offset outside 0..511. */
+typedef struct {
+    int32_t apply_grain;       /* ignored */
+    int32_t update_parameters; /* ignored */
+    int32_t scaling_points_y[14][2];
+    int32_t num_y_points;
+    int32_t scaling_points_cb[10][2];
+    int32_t num_cb_points;
+    int32_t scaling_points_cr[10][2];
+    int32_t num_cr_points;
+    int32_t scaling_shift;
+    int32_t ar_coeff_lag;
+    int32_t ar_coeffs_y[24];
+    int32_t ar_coeffs_cb[25];
+    int32_t ar_coeffs_cr[25];
+    int32_t ar_coeff_shift;
+    int32_t cb_mult;
+    int32_t cb_luma_mult;
+    int32_t cb_offset;
+    int32_t cr_mult;
+    int32_t cr_luma_mult;
+    int32_t cr_offset;
+    int32_t overlap_flag;
+    int32_t clip_to_restricted_range;
+    int32_t bit_depth; /* ignored */
+    int32_t chroma_scaling_from_luma;
+    int32_t grain_scale_shift;
+    uint16_t random_seed;
+    uint16_t reserved;
+} svthip_film_grain_params;
+
+#define SVTHIP_FILM_GRAIN_LUMA_H 73
+#define SVTHIP_FILM_GRAIN_LUMA_W 82
+#define SVTHIP_FILM_GRAIN_CHROMA_H 38
+#define SVTHIP_FILM_GRAIN_CHROMA_W 44
+#define SVTHIP_FILM_GRAIN_TABLES_BYTES 20196 /* 2 * (73 * 82 + 2 * 38 * 44 + 3 * 256) */
+
+int32_t svthip_film_grain_tables_dev(svthip_ctx *ctx, const svthip_film_grain_params *params, uint32_t bit_depth, int16_t *d_tables,
+                                     void *stream);
+int32_t svthip_av1_add_film_grain_dev(svthip_ctx *ctx, const svthip_film_grain_params *params, const void *const d_src[3],
+                                      const uint32_t src_stride[3], void *const d_dst[3], const uint32_t dst_stride[3], uint32_t width,
+                                      uint32_t height, const int16_t *d_tables, void *stream);
+int32_t svthip_av1_highbd_add_film_grain_dev(svthip_ctx *ctx, const svthip_film_grain_params *params, const void *const d_src[3],
+                                             const uint32_t src_stride[3], void *const d_dst[3], const uint32_t dst_stride[3], uint32_t width,
+                                             uint32_t height, uint32_t bit_depth, const int16_t *d_tables, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one
  * transform type at a time from ProductFullLoopTxSearch (Codec/EbFullLoop.c:1138-1352: for every tx_type candidate of a TU:
  * Av1EstimateTransform -> Av1QuantizeInvQuantize -> distortion -> cost), encode_pass_tx_search (:1354-1550) and Av1EncodeLoop

@@ -255,6 +255,10 @@ hipError_t launch_pa_noise_detect(const uint8_t* pool, const svthip_pa_picture* 
                                   uint32_t denoised_stride, uint64_t* sb_var, uint8_t* flat_noise, uint32_t* picture, hipStream_t s);
 hipError_t launch_pa_denoise(uint8_t* pool, const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n, uint32_t chroma_stride, uint32_t n_sb,
                              uint8_t* denoised, uint32_t denoised_stride, const uint8_t* flat_noise, const uint32_t* picture, hipStream_t s);
+// fg_grain.hip: AV1 film-grain synthesis -- the templates and scaling tables, the frame pass (kernels: fg_grain_kernels.h)
+hipError_t launch_film_grain_tables(const svthip_film_grain_params& params, int bit_depth, int16_t* tables, hipStream_t s);
+hipError_t launch_film_grain_frame(const svthip_film_grain_params& params, int bit_depth, const void* const src[3], const uint32_t src_stride[3],
+                                   void* const dst[3], const uint32_t dst_stride[3], uint32_t width, uint32_t height, const int16_t* tables, hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

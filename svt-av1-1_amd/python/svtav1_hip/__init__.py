@@ -26,8 +26,9 @@ from ._cdef import CDEF_PICK_MAX_FB, CDEF_RESULT_DTYPE, Cdef, CdefPicture, cdef_
 from ._restoration import (RESTORE_NONE, RESTORE_SGRPROJ, RESTORE_WIENER, SGRPROJ_DETAIL_DTYPE, SGRPROJ_PARAMS, WIENER_WALK_STATE_DTYPE,
                            LrPicture, Restoration, lr_unit_geometry, lr_unit_sizes, lr_workspace_bytes, make_lr_picture,
                            sgrproj_walk_max_trials, sgrproj_workspace_bytes, wiener_walk_max_trials)
+from ._grain import FILM_GRAIN_PARAMS_BYTES, FILM_GRAIN_TABLES_BYTES, FilmGrain, film_grain_param_offsets, film_grain_params
 from ._host import ME_CU_RESULT_REF_DTYPE, HostForms, HostPicture
 
 
-class Context(ContextCore, MotionEstimation, TransformQuant, PictureAnalysis, Prediction, Cfl, Deblocking, Cdef, Restoration, HostForms):
+class Context(ContextCore, MotionEstimation, TransformQuant, PictureAnalysis, Prediction, Cfl, Deblocking, Cdef, Restoration, FilmGrain, HostForms):
     """One svthip_ctx (stream + scratch), the analogue of one MeContext_t."""
