@@ -10,7 +10,8 @@
 // Mapping (see DESIGN.md "full-pel kernel"):
 //   * the (sw+63) x (sh+63) reference window is staged once into LDS (pitch 192 B, conflict-free for
 //     the 16-lane ds_read_b128 groups): staging reads the plane at the search origin's own byte
-//     alignment and writes ds_write_b128, so window byte 0 is search column 0;
+//     alignment and writes ds_write_b128, so window byte 0 is search column 0 (the two-image form of
+//     me_fullpel_img2.h: pitch 144 B, both images from one load per slot, shape fixed to a width of 64);
 //   * wave w of the 256-thread workgroup owns 32x32 quadrant w of the SB, so its source pixels are
 //     wave-uniform and live in SGPRs (scalar loads straight from the source plane);
 //   * lane l owns 16 horizontally consecutive search positions of one row; a 16-pixel block row
@@ -22,9 +23,14 @@
 //     pay the key once per (PU, ITEM), an item being a lane's 16 positions: the item's SADs are first
 //     reduced to their minimum (v_pk_min_u16 for the 8x8 and 16x16 PUs, v_min3_u32 for the 32x32), and
 //     key = min << 16 | y * 128 + 16 * xg  (32x32: << 14) names the first item that attains the
-//     minimum.  After the search, once per superblock, resolve_items (me_fullpel_common.h) recomputes
-//     the winning items' SADs -- lane = 4 * (8x8 part) + position quad, three passes of 8 v_qsad for
-//     the 8x8, 16x16 and 32x32 winners -- and takes the first position that equals the minimum.
+//     minimum.  The 8x8 PUs reduce an item with the three-input packed f16 minimum, exact on their SADs
+//     (<= 8160 = 0x1fe0 < 0x7c00: patterns of non-negative finite f16), and the two-image form (search
+//     width 64) tags instead of forming keys: a lane's items are rows 16 * it + lane_row, so one running
+//     packed u16 minimum of  4 * sad + it  (<= 0x7f83) per PU names the lane's first best item, and the key
+//     is formed from it once, after the passes.  After the search, once per superblock, resolve_items
+//     (me_fullpel_common.h) recomputes the winning items' SADs -- lane = 4 * (8x8 part) + position quad,
+//     three passes of 8 v_qsad for the 8x8, 16x16 and 32x32 winners -- and takes the first position that
+//     equals the minimum.
 //     Clipped areas keep one key  sad << 16 | raster_index  per (PU, position);
 //   * 64x64 sums cross the four waves through a 16 KB LDS exchange buffer, each wave finishing a
 //     quarter of the positions.  Up to 64x64 positions the 64x64 PU's key is  sum << 12 | y * 64 + x

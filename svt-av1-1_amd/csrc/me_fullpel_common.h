@@ -1,5 +1,6 @@
 // svt-av1-1_amd/csrc/me_fullpel_common.h -- what the 85-PU (me_fullpel_impl.h) and the 209-PU (me_fullpel209_impl.h) full-pel search of
-// one superblock by one 256-thread workgroup have in common: descriptor decode, window staging, the raster lane -> item map, the
+// one superblock by one 256-thread workgroup have in common: descriptor decode, window staging (general and, for the two-image form,
+// fixed to a search width of 64), the raster lane -> item map, the
 // square-PU key steps, the 8x8 class resolver, the per-item minima of the 85-PU class forms with their resolver and the 64x64 publish.  The row-step loops are NOT here: the three forms (one image
 // pipelined, two images pipelined, 209-PU unpipelined with v_pk_mov_b32) differ for measured reasons.
 #pragma once
@@ -71,6 +72,43 @@ __device__ __forceinline__ void stage_window(uint8_t* win, const uint8_t* base, 
     }
 }
 
+// The same for the two-image form, which runs only at sw == 64 (me_fullpel.hip): a window row has 32 dwords, so image 0 takes eight full
+// 16-byte slots, image 1 dwords 1..32 of which the last is past the window and stays zero, and slot 8 of both images is zero.  The LDS
+// contents equal stage_window<PITCH, IMAGE1>(win, base, ref_stride, 64, sh, tid)'s byte for byte and no other byte of the plane is read.
+// Thread -> (row = tid >> 3, + 32 per pass, slot = tid & 7), MAX_PASSES unrolled passes (sh + 63 <= 32 * MAX_PASSES): no division, and
+// the row pointer advances by an add.  Image 1's slot is dwords 1..3 of the thread's own image-0 slot and ONE more dword (none in
+// slot 7), not a second 16-byte load.
+template <int PITCH, int IMAGE1, int MAX_PASSES>
+__device__ __forceinline__ void stage_window64(uint8_t* win, const uint8_t* base, uint32_t ref_stride, int sh, int tid)
+{
+    static_assert(PITCH == 144 && IMAGE1 != 0, "nine 16-byte slots per row, two images");
+    const int rows = sh + 63;
+    const int c4 = tid & 7;
+    const int r0 = tid >> 3;
+    const uint8_t* p = base + (size_t)r0 * ref_stride + 16 * c4;
+    uint8_t* w = win + r0 * PITCH + 16 * c4;
+    // every pass's loads go out before the first LDS write waits for one
+    unaligned_u32x4 u[MAX_PASSES];
+    uint32_t next[MAX_PASSES];
+#pragma unroll
+    for (int k = 0; k < MAX_PASSES; k++, p += 32 * (size_t)ref_stride) {
+        u[k] = unaligned_u32x4{{0u, 0u, 0u, 0u}};
+        next[k] = 0u;
+        if (r0 + 32 * k < rows) {
+            u[k] = *reinterpret_cast<const unaligned_u32x4*>(p);
+            if (c4 < 7) next[k] = reinterpret_cast<const unaligned_u32*>(p + 16)->v;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < MAX_PASSES; k++) {
+        if (r0 + 32 * k < rows) {
+            *reinterpret_cast<uint4*>(w + 32 * k * PITCH) = make_uint4(u[k].v[0], u[k].v[1], u[k].v[2], u[k].v[3]);
+            *reinterpret_cast<uint4*>(w + 32 * k * PITCH + IMAGE1) = make_uint4(u[k].v[1], u[k].v[2], u[k].v[3], next[k]);
+        }
+    }
+    if (tid < 2 * rows) *reinterpret_cast<uint4*>(win + (tid & 1) * IMAGE1 + (tid >> 1) * PITCH + 128) = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // Raster map of search iteration `it`: lane l holds item 64 it + l, an item being 16 horizontally consecutive positions (column group
 // xg of search row y).  A lane past the last item repeats item 0: its keys duplicate a first-pass lane's and change no minimum
 // (whatever is not a plain minimum checks the returned lane_valid).
@@ -136,6 +174,44 @@ __device__ __forceinline__ uint32_t track_item16(uint32_t best, const uint32_t (
     const uint32_t m = pk_min_u16_tree(pk_min_u16_tree(pk_min_u16_tree(d[0], d[1]), pk_min_u16_tree(d[2], d[3])),
                                        pk_min_u16_tree(pk_min_u16_tree(d[4], d[5]), pk_min_u16_tree(d[6], d[7])));
     return min3u(best, (m << 16) | idx0, (m & himask) | idx0);
+}
+
+// The 8x8 PUs reduce an item in four instructions instead of seven.  A raw 8x8 SAD (32 pixels) is at most 32 * 255 = 8160 = 0x1fe0, and
+// every u16 below 0x7c00 is the bit pattern of a non-negative finite f16 whose order is the integer order, so v_pk_minimum3_f16 is an
+// exact three-input packed u16 minimum on such values (1..1023 are denormals: the kernels run with f16 denormals on, the default,
+// and a minimum returns one of its operands unchanged).  The 16x16 sums reach 4 * 8160 = 0x7f80 >= 0x7c00 (infinity and NaN patterns)
+// and keep track_item16.  Never feed it anything but raw 8x8 SADs: 0xffff, the trackers' initial value, is a NaN.
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_min3_f16bits(uint32_t a, uint32_t b, uint32_t c)
+{
+    const f16x2_t x = __builtin_bit_cast(f16x2_t, a), y = __builtin_bit_cast(f16x2_t, b), z = __builtin_bit_cast(f16x2_t, c);
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_minimum(__builtin_elementwise_minimum(x, y), z));
+}
+// packed u16 raw 8x8 SADs of an item's 16 positions: the minimum over the even positions in the low half, over the odd ones in the high half
+__device__ __forceinline__ uint32_t item_min8(const uint32_t (&d)[8])
+{
+    return pk_min_u16_tree(pk_min3_f16bits(d[0], d[1], d[2]), pk_min3_f16bits(pk_min3_f16bits(d[3], d[4], d[5]), d[6], d[7]));
+}
+// one-image class form: key per pass as in track_item16 -- 7 instructions per PU and item
+__device__ __forceinline__ uint32_t track_item8(uint32_t best, const uint32_t (&d)[8], uint32_t idx0, uint32_t himask)
+{
+    const uint32_t m = item_min8(d);
+    return min3u(best, (m << 16) | idx0, (m & himask) | idx0);
+}
+// Two-image class form: a lane's items are search rows 16 it + lane_row, it = 0..3, so among a lane's OWN items the raster order is the
+// order of `it`, and 4 * 8160 + 3 = 0x7f83 fits 16 bits: the running value is the packed u16 minimum of 4 * sad + it (run starts at
+// 0xffffffff, tag = it * 0x00010001; m << 2 cannot carry between the halves because m.lo <= 0x1fe0) -- 6 instructions per PU and item.
+// item_key8 turns it, once per superblock, into the key that track_item16 would have left: the lane's minimum SAD with the first raster
+// index (idx0) of the first of its items that attains it.
+__device__ __forceinline__ uint32_t track_item8_tagged(uint32_t run, const uint32_t (&d)[8], uint32_t tag)
+{
+    return pk_min_u16_tree(run, (item_min8(d) << 2) | tag);
+}
+// lane_idx0: fullpel_idx0(lane_row, column group), the lane's item of pass 0 (below 2048; a pass adds 16 rows = 2048)
+__device__ __forceinline__ uint32_t item_key8(uint32_t run, uint32_t lane_idx0)
+{
+    const uint32_t r = min(run & 0xffffu, run >> 16);
+    return ((r >> 2) << 16) | ((r & 3u) << 11) | lane_idx0;
 }
 
 // 32x32 PU of a quadrant: the 16 widened sums of an item (raw <= 130560 < 2^17), key = min << 14 | idx0 -- 7 v_min3, two keys, one v_min3

@@ -22,13 +22,16 @@ constexpr unsigned long long kRowLut = 0xFEAB6732DC894510ull;
 // d: the superblock's descriptor (6 int32: src_offset, ref_offset, x/y search origin, search width/height), any address space;
 // smem: SVTHIP_FULLPEL_LDS_FIXED + (sh + 63) * SVTHIP_FULLPEL_LDS_PITCH bytes of workgroup LDS, 16-byte aligned (IMG2: fullpel_img2_lds_bytes()).
 // Results go to out_sad / out_mv [85 * sbi ...].  Must be called by all 256 threads.
-// CLS (search width a multiple of 16, the usual case; wave-uniform): the 8x8, 16x16 and 32x32 PUs are tracked per ITEM (track_item16 /
-// track_item32: the minimum of the item's 16 SADs with the item's first raster index) and the winners' positions inside their items are
-// found after the search (resolve_items); up to 64x64 positions the 64x64 PU is tracked as one 32-bit key per position (track_quad64).
+// CLS (search width a multiple of 16, the usual case; wave-uniform): the 8x8, 16x16 and 32x32 PUs are tracked per ITEM (track_item8 /
+// track_item16 / track_item32: the minimum of the item's 16 SADs with the item's first raster index) and the winners' positions inside
+// their items are found after the search (resolve_items); up to 64x64 positions the 64x64 PU is tracked as one 32-bit key per position
+// (track_quad64).
 // IMG2 (with CLS, search width exactly 64, height <= 64): the window is staged twice at pitch kPitch2, image 1 four bytes later than
 // image 0, and a row step reads W0..7 from image 0 and W1..8 from image 1, so that every dword pair a v_qsad takes starts at an even
 // register of an aligned ds_read_b128 and the six v_mov_b32 per row step that formed the odd pairs are gone.  The lane -> item map is
-// (row = 16 it + kRowLut[lane >> 2], column group = lane & 3): results depend on the item, not on the lane that holds it.
+// (row = 16 it + kRowLut[lane >> 2], column group = lane & 3): results depend on the item, not on the lane that holds it.  A lane's
+// items being in raster order by `it`, the 8x8 PUs keep a packed minimum of 4 * sad + it through the passes (track_item8_tagged) and
+// form their keys once, after the loop (item_key8).  The window is staged by stage_window64, which knows the row's 32 dwords.
 template <bool CLS, bool IMG2 = false>
 __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_plane, uint32_t src_stride,
                                              const uint8_t* __restrict__ ref_plane, uint32_t ref_stride, const int32_t* d, uint32_t sbi,
@@ -50,7 +53,8 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
     const int xo = D.xo, yo = D.yo, sw = D.sw, sh = D.sh, n_xg = D.n_xg;
 
     // ---- stage the reference window: rows 0..sh+62, bytes 0..sw+62 valid, zero beyond ----
-    stage_window<P, IMG2 ? kImage1 : 0>(win, ref_plane + D.ref_off, ref_stride, sw, sh, tid);
+    if constexpr (IMG2) stage_window64<P, kImage1, (SVTHIP_FULLPEL_IMG2_ROWS + 31) / 32>(win, ref_plane + D.ref_off, ref_stride, sh, tid);  // sw == 64: fixed shape
+    else stage_window<P, 0>(win, ref_plane + D.ref_off, ref_stride, sw, sh, tid);
     if (tid == 0) *best64_lds = ~0ull;
     __syncthreads();
 
@@ -99,7 +103,7 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
         }
 
         // A lane past the last item repeats item 0 (IMG2: row 0 of its column group): its keys duplicate a first-pass lane's and change
-        // no minimum.  CLS: every position of an item is inside the area, and the keys carry the item's first raster index alone.
+        // no minimum (the tagged 8x8 values of IMG2: see item_key8's call below).  CLS: every position of an item is inside the area, and the keys carry the item's first raster index alone.
         // General form: per-position raster index; positions outside the search area get idx = ~0 so that every key OR-ed with it is
         // 0xffffffff and can never win (at least one position is always valid).
         uint32_t idx[16];
@@ -192,7 +196,9 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
                 if constexpr (CLS) {
                     const uint32_t d[8] = {(uint32_t)acc[k][0], (uint32_t)(acc[k][0] >> 32), (uint32_t)acc[k][1], (uint32_t)(acc[k][1] >> 32),
                                            (uint32_t)acc[k][2], (uint32_t)(acc[k][2] >> 32), (uint32_t)acc[k][3], (uint32_t)(acc[k][3] >> 32)};
-                    best8[4 * zz + k] = track_item16(best8[4 * zz + k], d, idx0, himask);
+                    // IMG2: best8 holds the packed running minima of 4 * sad + it until item_key8 after the loop
+                    if constexpr (IMG2) best8[4 * zz + k] = track_item8_tagged(best8[4 * zz + k], d, (uint32_t)it * 0x00010001u);
+                    else best8[4 * zz + k] = track_item8(best8[4 * zz + k], d, idx0, himask);
                 } else {
 #pragma unroll
                     for (int q = 0; q < 4; q++) best8[4 * zz + k] = track4(best8[4 * zz + k], acc[k][q], &idx[4 * q], himask);
@@ -252,6 +258,15 @@ __device__ __forceinline__ void fullpel85_sb(const uint8_t* __restrict__ src_pla
                 }
             }
         }
+    }
+
+    if constexpr (IMG2) {
+        // A lane past the last row ran row 0 of its column group under the pass's tag, so its key may name a row that is not the item's.
+        // Such a key never wins the wave minimum: the lane that holds row 0 of that column group has the same SAD in pass 0, and its
+        // key carries row 0, the smallest index of the column group.
+        const uint32_t lane_idx0 = fullpel_idx0(lane_row, lane & 3);
+#pragma unroll
+        for (int i = 0; i < 16; i++) best8[i] = item_key8(best8[i], lane_idx0);
     }
 
     // ---- reduce across the wave and publish ----
