@@ -1365,6 +1365,124 @@ int32_t svthip_av1_highbd_add_film_grain_dev(svthip_ctx *ctx, const svthip_film_
                                              uint32_t height, uint32_t bit_depth, const int16_t *d_tables, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mode decision's fast loop: the second loop of ProductPerformFastLoop (Codec/EbProductCodingLoop.c:1282-1459) after the predictions,
+ * which the prediction entries above leave in device memory, and PreModeDecision (Codec/EbModeDecision.c:393-471) behind it.  8-bit
+ * planes only, as the reference's fast loop (it runs on 8-bit planes for 10-bit input too).  Pure integer arithmetic, bit-identical.
+ *
+ * svthip_md_fast_cost_batch_dev: per candidate of a batch of predicted PUs of ONE luma size
+ *   1. the three plain SADs against the source picture through NxMSadKernelSubSampled_funcPtrArray with sub_sampled_pred == 0
+ *      (:1337-1370; sub_sampled_pred is always EB_FALSE, :1296-1297): Y of bwidth x bheight, Cb and Cr of bwidth_uv x bheight_uv =
+ *      max(4, bwidth / 2) x max(4, bheight / 2), chroma = SAD(Cb) + SAD(Cr);
+ *   2. the fast cost RDCOST(fast_lambda, rate, luma + chroma) of Av1IntraFastCost / Av1InterFastCost
+ *      (Codec/EbRateDistortionCost.c:764-771, :1321-1343; RDCOST: Codec/EbRateDistortionCost.h:215-217):
+ *      ROUND_POWER_OF_TWO((uint64_t)min(rate, merge_rate) * lambda, 9) + (luma + chroma) * 128 (LUMA_WEIGHT 1, AV1_COST_PRECISION 0).
+ * src, pred: 8-bit planes as svthip_inter_planes, pointers at sample (0, 0), strides in samples, any pointer and any stride: a row that
+ * does not start on a 4-byte boundary is read byte by byte.  The entry reads exactly the samples of each block and no byte more (the
+ * 16-byte over-read rule of the convolution entries does NOT apply): a tile or a picture may end where its allocation ends.
+ *
+ * svthip_md_fast_desc (32 bytes, the array 16-byte aligned), field by field:
+ *   src_x, src_y     luma position of the block in the source picture (cu_origin + the picture's origin, :2469); Cb / Cr are read at
+ *                    ((src >> 3) << 3) / 2, the round_origin >> 1 of :2471
+ *   pred_x, pred_y   luma position of the candidate's tile in the prediction planes: the dst_origin the prediction entry was given.
+ *                    Cb / Cr at ((pred >> 3) << 3) / 2, where those entries write them (ROUND_UV, :2473).  The reference's per-candidate
+ *                    prediction_ptr becomes a position in one pool plane: every candidate has its own tile
+ *   rate             lumaRate + chromaRate as the fast-cost function sums them (table look-ups: host work)
+ *   merge_rate       skipModeFacBits[skipModeCtx][1] when merge_flag is set, else 0xffffffff: the cost takes min(rate, merge_rate), which
+ *                    is what :1336-1342 of EbRateDistortionCost.c does
+ *   lambda           context_ptr->fast_lambda
+ *   luma_given       candidate_ptr->me_distortion; read only with SVTHIP_MD_FAST_LUMA_GIVEN
+ *   has_uv           blk_geom->has_uv: 0 leaves chroma 0 and reads no chroma sample
+ *   flags            SVTHIP_MD_FAST_LUMA_GIVEN       the best candidate of the first loop when it is INTRA_MODE: luma = luma_given, chroma is
+ *                                                    still measured (:1333-1334)
+ *                    SVTHIP_MD_FAST_SKIP_DISTORTION  mpm_flag: luma = chroma = 0, nothing is read (:1332); wins over LUMA_GIVEN
+ *                    SVTHIP_MD_FAST_INVALID          WARPED_CAUSAL with local_warp_valid == 0: nothing is read, luma = chroma = 0 and
+ *                                                    cost = 0xffffffffffffffff (:1332, :1390-1391)
+ *                    SVTHIP_MD_FAST_CHROMA_QUARTER   isCandzz of a 64x64 INTER_MODE candidate in a CMPLX_NOISE SB: chroma >>= 2 after
+ *                                                    Cb + Cr (:1375-1387)
+ *                    SVTHIP_MD_FAST_TYPE_INTER       candidate_ptr->type == INTER_MODE (else INTRA_MODE); read by the pick entry only
+ *   reserved         ignored
+ * svthip_md_fast_result (16 bytes, the array 16-byte aligned): luma, chroma (lumaFastDistortion, chromaFastDistortion), cost
+ * (*fast_cost_ptr).
+ * The first fast loop (:1231-1280) stays on the host: it reads no sample, and decides which candidates enter this one.
+ * Refused with SVTHIP_ERR_BAD_PARAMETER and svthip_last_error text before any launch: a size that is not one of the 22 AV1 block sizes;
+ * with n_cand > 0 (n_cand == 0 returns OK) a null src, pred, d_desc or d_result; a null plane pointer -- has_uv lives in device memory,
+ * so every call may touch chroma and a null Cb or Cr plane is always refused --; a d_desc or d_result that is not 16-byte aligned.
+ * Nothing in the call synchronises with the host.
+ *
+ * svthip_md_fast_pick_batch_dev: which candidates of a block go to the full loop.  One svthip_md_fast_group is one block:
+ *   first, count         the block's rows of d_result / d_desc, listed in the order the reference walks them: descending
+ *                        fastLoopCandidateIndex, only the candidates that enter the second loop (:1304)
+ *   buffer_total_count   as ProductGenerateMdCandidatesCu returned it (:2513-2522), 1..12 (MAX_NFL; full_recon_search_count, :655)
+ *   buffer_width         context_ptr->buffer_depth_index_width[0], 1..13 (MAX_NFL + 1)
+ * The device replays, per group:
+ *   1. maxBuffers = MIN(buffer_total_count + 1, buffer_width) (:2525);
+ *   2. the walk of :1284-1459 over 13 buffers whose costs start at 0xffffffffffffffff: a candidate is written into buffer
+ *      highestCostIndex (0 at first), then -- not after the last candidate (:1425) -- highestCostIndex is searched again from buffer 0:
+ *      the search stops at a current highest cost equal to ~0 (:1447) and moves on a strictly greater cost (:1451).  Its do-while runs
+ *      once even when maxBuffers is 1 and then looks at buffer 1, which here is always empty;
+ *   3. PreModeDecision with the arguments of :2547-2561: buffer_total_count = MIN(count, buffer_total_count); when count equals that,
+ *      the first buffer_total_count buffers in order, otherwise the maxBuffers buffers without the worst, the worst found with >= from
+ *      buffer 1 (:433); then the pass that swaps an INTRA_MODE entry with a later INTER_MODE entry (:449-458) and disable_merge_index
+ *      (:463-468).  A buffer no candidate was written into (a cost of ~0 keeps highestCostIndex where it is, so a later candidate
+ *      replaces that one) is neither INTRA_MODE nor INTER_MODE here; the reference reads the candidate_ptr an earlier block left there.
+ * svthip_md_fast_pick (32 bytes, the array 16-byte aligned): best[i] = best_candidate_index_array[i] for i < full_count, buffer indices;
+ * buffer_cand[b] = the offset within the group (0 .. count - 1) of the candidate buffer b holds, 0xff for an empty buffer; full_count =
+ * *full_candidate_total_count_ptr as PreModeDecision leaves it (the caller takes MIN(full_count, MIN(count, buffer_total_count)),
+ * :2573); disable_merge_index.  Unused best[] entries and reserved bytes are 0xff and 0.
+ * d_result and d_desc are the arrays of n_cand rows the cost entry read and wrote; only cost and flags are read.
+ * Refused before any launch: a null pointer with n_groups > 0 (n_groups == 0 returns OK); d_result, d_desc or d_pick not 16-byte
+ * aligned, d_group not 8-byte aligned.  The groups are in device memory, so these are refused ON THE DEVICE, as the prediction entries
+ * refuse a descriptor: count == 0, count > 113, buffer_width == 0 or > 13, buffer_total_count == 0 or > 12, first + count > n_cand.
+ * Such a group gets full_count = 0 with every best[] and buffer_cand[] 0xff, the context counts it, and svthip_inter_pred_refused
+ * reports the count.  Nothing in the call synchronises with the host. */
+#define SVTHIP_MD_FAST_LUMA_GIVEN 1u
+#define SVTHIP_MD_FAST_SKIP_DISTORTION 2u
+#define SVTHIP_MD_FAST_INVALID 4u
+#define SVTHIP_MD_FAST_CHROMA_QUARTER 8u
+#define SVTHIP_MD_FAST_TYPE_INTER 16u
+#define SVTHIP_MD_FAST_MAX_CANDIDATES 113 /* MODE_DECISION_CANDIDATE_MAX_COUNT (Codec/EbModeDecisionProcess.h:27) */
+#define SVTHIP_MD_FAST_MAX_BUFFERS 13     /* MAX_NFL + 1 */
+
+typedef struct svthip_md_fast_desc {
+    uint16_t src_x, src_y;
+    uint16_t pred_x, pred_y;
+    uint32_t rate;
+    uint32_t merge_rate;
+    uint32_t lambda;
+    uint32_t luma_given;
+    uint8_t has_uv;
+    uint8_t flags;
+    uint8_t reserved[6];
+} svthip_md_fast_desc;
+
+typedef struct svthip_md_fast_result {
+    uint32_t luma, chroma;
+    uint64_t cost;
+} svthip_md_fast_result;
+
+typedef struct svthip_md_fast_group {
+    uint32_t first;
+    uint16_t count;
+    uint8_t buffer_total_count;
+    uint8_t buffer_width;
+} svthip_md_fast_group;
+
+typedef struct svthip_md_fast_pick {
+    uint8_t best[13];
+    uint8_t buffer_cand[13];
+    uint8_t full_count;
+    uint8_t disable_merge_index;
+    uint8_t reserved[4];
+} svthip_md_fast_pick;
+
+int32_t svthip_md_fast_cost_batch_dev(svthip_ctx *ctx, const svthip_inter_planes *src, const svthip_inter_planes *pred,
+                                      const svthip_md_fast_desc *d_desc, uint32_t n_cand, uint32_t bwidth, uint32_t bheight,
+                                      svthip_md_fast_result *d_result, void *stream);
+int32_t svthip_md_fast_pick_batch_dev(svthip_ctx *ctx, const svthip_md_fast_result *d_result, const svthip_md_fast_desc *d_desc,
+                                      uint32_t n_cand, const svthip_md_fast_group *d_group, uint32_t n_groups, svthip_md_fast_pick *d_pick,
+                                      void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batching layer for the transform / quantisation callers.  The reference calls its T/Q kernels one TU and one
  * transform type at a time from ProductFullLoopTxSearch (Codec/EbFullLoop.c:1138-1352: for every tx_type candidate of a TU:
  * Av1EstimateTransform -> Av1QuantizeInvQuantize -> distortion -> cost), encode_pass_tx_search (:1354-1550) and Av1EncodeLoop

@@ -1,0 +1,283 @@
+// svt-av1-1_amd/csrc/md_fast_kernels.h
+//
+// Mode decision's fast loop on the device, gfx950: the kernels of md_fast.hip and the arithmetic they share with the host test
+// (tests/host_kernels/md_fast_host.cpp compiles this header with g++ and calls the __device__ functions below on plain arrays).
+// Replaces (paths under Source/Lib of the reference):
+//   the second loop of ProductPerformFastLoop, after the prediction      Codec/EbProductCodingLoop.c:1282-1459
+//   NxMSadKernelSubSampled_funcPtrArray with sub_sampled_pred == 0      Codec/EbComputeSAD.h:96-124
+//   the cost of Av1IntraFastCost / Av1InterFastCost                     Codec/EbRateDistortionCost.c:764-771, :1321-1343
+//   PreModeDecision with the arguments of :2547-2561                    Codec/EbModeDecision.c:393-471
+//
+//   mapping   md_fast_cost_kernel<G>: a lane takes four consecutive samples of a row (a quad).  A block of W x H luma samples is
+//             W / 4 * H quads and is worked by G = min(64, quads) lanes, so a wave holds 64 / G candidates: sixteen 4x4, eight 4x8 /
+//             8x4, four 8x8 / 4x16 / 16x4, two 8x16 / 16x8, one of 16x16 and above.  The lanes of a candidate walk its luma quads, then
+//             the quads of Cb and Cr as one list, G at a time.  A candidate never spans waves: luma and chroma are summed over its
+//             lanes in one butterfly (luma in the low, chroma in the high word of group_sum_u64) and lane 0 writes SADs and cost.
+//   reads     a quad is one dword load when its address is a multiple of 4, four byte loads otherwise; no byte outside the block.
+//   SAD       v_sad_u8 of the two packed quads.
+//   pick      md_fast_pick_kernel: one lane per group; the 13 buffers of a lane and its list of picks are columns of LDS arrays.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/svtav1_hip.h"
+#ifdef __HIPCC__
+#include "tq_tile.h"   // group_sum_u64
+#endif
+
+namespace svthip {
+
+static_assert(sizeof(svthip_md_fast_desc) == 32 && sizeof(svthip_md_fast_result) == 16 && sizeof(svthip_md_fast_group) == 8 &&
+                  sizeof(svthip_md_fast_pick) == 32, "the layouts of include/svtav1_hip.h");
+
+constexpr uint64_t MD_FAST_MAX_COST = ~0ull;
+constexpr int MD_FAST_BUFFERS = SVTHIP_MD_FAST_MAX_BUFFERS;
+constexpr int MD_FAST_PICK_THREADS = 64;
+
+// ------------------------------------------------------------------------------------------------ geometry
+
+// one call: the planes and the block size as shifts (every AV1 block side is a power of two)
+struct MdFastArgs {
+    const uint8_t* src[3];
+    const uint8_t* pred[3];
+    uint32_t src_stride[2], pred_stride[2];  // [0] Y, [1] Cb and Cr
+    const svthip_md_fast_desc* desc;
+    svthip_md_fast_result* result;
+    uint32_t n;
+    int log2_qw, log2_h;    // luma: quads per row, rows
+    int log2_cqw, log2_ch;  // Cb / Cr of max(4, W / 2) x max(4, H / 2)
+};
+
+__host__ __device__ __forceinline__ int md_fast_log2(uint32_t v)
+{
+    int s = 0;
+    while ((1u << s) < v) s++;
+    return s;
+}
+
+// lanes per candidate: min(64, luma quads)
+__host__ __device__ __forceinline__ int md_fast_group_lanes(uint32_t bwidth, uint32_t bheight)
+{
+    const uint32_t quads = bwidth / 4u * bheight;
+    return quads < 64u ? (int)quads : 64;
+}
+
+inline MdFastArgs md_fast_make_args(const svthip_inter_planes& src, const svthip_inter_planes& pred, const svthip_md_fast_desc* desc, uint32_t n,
+                                    uint32_t bwidth, uint32_t bheight, svthip_md_fast_result* result)
+{
+    const uint32_t cw = bwidth / 2u < 4u ? 4u : bwidth / 2u, ch = bheight / 2u < 4u ? 4u : bheight / 2u;
+    MdFastArgs A;
+    A.src[0] = static_cast<const uint8_t*>(src.y), A.src[1] = static_cast<const uint8_t*>(src.cb), A.src[2] = static_cast<const uint8_t*>(src.cr);
+    A.pred[0] = static_cast<const uint8_t*>(pred.y), A.pred[1] = static_cast<const uint8_t*>(pred.cb), A.pred[2] = static_cast<const uint8_t*>(pred.cr);
+    A.src_stride[0] = src.y_stride, A.src_stride[1] = src.c_stride;
+    A.pred_stride[0] = pred.y_stride, A.pred_stride[1] = pred.c_stride;
+    A.desc = desc, A.result = result, A.n = n;
+    A.log2_qw = md_fast_log2(bwidth / 4u), A.log2_h = md_fast_log2(bheight);
+    A.log2_cqw = md_fast_log2(cw / 4u), A.log2_ch = md_fast_log2(ch);
+    return A;
+}
+
+// ------------------------------------------------------------------------------------------------ SADs
+
+// four samples of a row, packed; nothing before p[0] or after p[3] is read
+__device__ __forceinline__ uint32_t md_fast_load_quad(const uint8_t* p)
+{
+    if ((reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return *reinterpret_cast<const uint32_t*>(p);
+#else
+        uint32_t v;
+        memcpy(&v, p, 4);
+        return v;
+#endif
+    }
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+__device__ __forceinline__ uint32_t md_fast_sad_quad(uint32_t a, uint32_t b, uint32_t acc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_sad_u8(a, b, acc);
+#else
+    for (int k = 0; k < 4; k++) {
+        const int x = (int)((a >> (8 * k)) & 0xffu), y = (int)((b >> (8 * k)) & 0xffu);
+        acc += (uint32_t)(x > y ? x - y : y - x);
+    }
+    return acc;
+#endif
+}
+
+__device__ __forceinline__ bool md_fast_measures(uint32_t flags) { return !(flags & (SVTHIP_MD_FAST_SKIP_DISTORTION | SVTHIP_MD_FAST_INVALID)); }
+
+// what lane `l` of the `lanes` lanes of a candidate adds up: its share of the luma SAD and of SAD(Cb) + SAD(Cr)
+__device__ __forceinline__ void md_fast_lane_sads(const MdFastArgs& A, const svthip_md_fast_desc& d, int l, int lanes, uint32_t* luma, uint32_t* chroma)
+{
+    uint32_t ly = 0, lc = 0;
+    if (md_fast_measures(d.flags)) {
+        if (!(d.flags & SVTHIP_MD_FAST_LUMA_GIVEN)) {
+            const uint8_t* s = A.src[0] + (size_t)d.src_y * A.src_stride[0] + d.src_x;
+            const uint8_t* p = A.pred[0] + (size_t)d.pred_y * A.pred_stride[0] + d.pred_x;
+            const int quads = 1 << (A.log2_qw + A.log2_h), qmask = (1 << A.log2_qw) - 1;
+#pragma unroll 4
+            for (int q = l; q < quads; q += lanes) {
+                const size_t r = (size_t)(q >> A.log2_qw), c = (size_t)(q & qmask) * 4u;
+                ly = md_fast_sad_quad(md_fast_load_quad(s + r * A.src_stride[0] + c), md_fast_load_quad(p + r * A.pred_stride[0] + c), ly);
+            }
+        }
+        if (d.has_uv) {
+            const size_t so = (size_t)((d.src_y >> 3) << 2) * A.src_stride[1] + ((d.src_x >> 3) << 2);
+            const size_t po = (size_t)((d.pred_y >> 3) << 2) * A.pred_stride[1] + ((d.pred_x >> 3) << 2);
+            const int log2_cq = A.log2_cqw + A.log2_ch, quads = 2 << log2_cq, qmask = (1 << A.log2_cqw) - 1;
+#pragma unroll 2
+            for (int q = l; q < quads; q += lanes) {
+                const int plane = 1 + (q >> log2_cq), k = q & ((1 << log2_cq) - 1);
+                const size_t r = (size_t)(k >> A.log2_cqw), c = (size_t)(k & qmask) * 4u;
+                lc = md_fast_sad_quad(md_fast_load_quad(A.src[plane] + so + r * A.src_stride[1] + c),
+                                      md_fast_load_quad(A.pred[plane] + po + r * A.pred_stride[1] + c), lc);
+            }
+        }
+    }
+    *luma = ly, *chroma = lc;
+}
+
+// the candidate's result from the sums over its lanes
+__device__ __forceinline__ svthip_md_fast_result md_fast_finish(const svthip_md_fast_desc& d, uint32_t luma_sum, uint32_t chroma_sum)
+{
+    svthip_md_fast_result r;
+    r.luma = md_fast_measures(d.flags) ? ((d.flags & SVTHIP_MD_FAST_LUMA_GIVEN) ? d.luma_given : luma_sum) : 0u;
+    r.chroma = (d.flags & SVTHIP_MD_FAST_CHROMA_QUARTER) ? chroma_sum >> 2 : chroma_sum;
+    const uint32_t rate = d.rate < d.merge_rate ? d.rate : d.merge_rate;
+    r.cost = (d.flags & SVTHIP_MD_FAST_INVALID) ? MD_FAST_MAX_COST
+                                                : (((uint64_t)rate * d.lambda + 256u) >> 9) + (((uint64_t)r.luma + r.chroma) << 7);
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------ pick
+
+__device__ __forceinline__ bool md_fast_group_valid(const svthip_md_fast_group& g, uint32_t n_cand)
+{
+    return g.count >= 1 && g.count <= SVTHIP_MD_FAST_MAX_CANDIDATES && g.buffer_width >= 1 && g.buffer_width <= MD_FAST_BUFFERS &&
+           g.buffer_total_count >= 1 && g.buffer_total_count <= MD_FAST_BUFFERS - 1 && (uint64_t)g.first + g.count <= n_cand;
+}
+
+// One group.  cost[b * stride], cand[b * stride], best[b * stride], b < 13: the group's buffers and its best_candidate_index_array
+// (columns of LDS arrays on the device, so that nothing is indexed in registers).  Returns false, with the refused pick in *out, for a
+// group md_fast_group_valid turns down.
+__device__ __forceinline__ bool md_fast_pick_group(const svthip_md_fast_result* result, const svthip_md_fast_desc* desc, uint32_t n_cand,
+                                                   const svthip_md_fast_group& g, uint64_t* cost, uint8_t* cand, uint8_t* best, int stride,
+                                                   svthip_md_fast_pick* out)
+{
+    for (int b = 0; b < MD_FAST_BUFFERS; b++) cost[b * stride] = MD_FAST_MAX_COST, cand[b * stride] = best[b * stride] = 0xff;
+    const bool valid = md_fast_group_valid(g, n_cand);
+    uint32_t full = 0, disable_merge = 0;
+    if (valid) {
+        const uint32_t first = g.first, count = g.count;
+        const uint32_t max_buffers = min((uint32_t)g.buffer_total_count + 1u, (uint32_t)g.buffer_width);
+
+        // the walk: the candidate goes where the highest cost is, then the highest cost is looked for again
+        uint32_t hi = 0;
+        for (uint32_t k = 0; k < count; k++) {
+            cost[hi * stride] = result[first + k].cost;
+            cand[hi * stride] = (uint8_t)k;
+            if (k + 1u < count) {
+                hi = 0;
+                uint32_t b = 1;
+                do {
+                    const uint64_t highest = cost[hi * stride];
+                    if (highest == MD_FAST_MAX_COST) break;
+                    if (cost[b * stride] > highest) hi = b;
+                } while (++b < max_buffers);
+            }
+        }
+
+        // PreModeDecision
+        const uint32_t total_count = min(count, (uint32_t)g.buffer_total_count);
+        const bool same = count == total_count;
+        const uint32_t total = same ? total_count : max_buffers;
+        full = same ? max(1u, total) : max(1u, total - 1u);
+        if (total > 1u) {
+            uint32_t worst = total;   // none left out
+            if (!same) {
+                uint64_t highest = cost[0];
+                worst = 0;
+                for (uint32_t i = 1; i < total; i++)
+                    if (cost[i * stride] >= highest) highest = cost[i * stride], worst = i;
+            }
+            uint32_t n = 0;
+            for (uint32_t i = 0; i < total; i++)
+                if (i != worst) best[n++ * stride] = (uint8_t)i;
+        } else {
+            best[0] = 0;
+        }
+        // 0 neither (an empty buffer), 1 INTER_MODE, 2 INTRA_MODE
+        auto type_of = [&](uint32_t entry) -> int {
+            const uint8_t k = cand[best[entry * stride] * stride];
+            return k == 0xff ? 0 : (desc[first + k].flags & SVTHIP_MD_FAST_TYPE_INTER) ? 1 : 2;
+        };
+        for (uint32_t i = 0; i + 1u < full; i++)
+            for (uint32_t j = i + 1u; j < full; j++)
+                if (type_of(i) == 2 && type_of(j) == 1) {
+                    const uint8_t t = best[i * stride];
+                    best[i * stride] = best[j * stride], best[j * stride] = t;
+                }
+        for (uint32_t i = 0; i < full; i++)
+            if (type_of(i) == 1) disable_merge = 1;
+    }
+#pragma unroll
+    for (int b = 0; b < MD_FAST_BUFFERS; b++) out->best[b] = best[b * stride], out->buffer_cand[b] = valid ? cand[b * stride] : (uint8_t)0xff;
+    out->full_count = (uint8_t)full, out->disable_merge_index = (uint8_t)disable_merge;
+    out->reserved[0] = out->reserved[1] = out->reserved[2] = out->reserved[3] = 0;
+    return valid;
+}
+
+#ifdef __HIPCC__
+
+// ------------------------------------------------------------------------------------------------ kernels
+
+// G lanes per candidate, 64 / G candidates per wave, 4 waves per workgroup
+template <int G>
+__global__ void __launch_bounds__(256) md_fast_cost_kernel(MdFastArgs A)
+{
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t job = (blockIdx.x * 4u + wave) * (64u / G) + lane / G;
+    if (job >= A.n) return;   // whole groups of G lanes leave together
+    const uint4* dp = reinterpret_cast<const uint4*>(A.desc + job);
+    union {
+        uint4 q[2];
+        svthip_md_fast_desc d;
+    } u;
+    u.q[0] = dp[0], u.q[1] = dp[1];
+    uint32_t luma, chroma;
+    md_fast_lane_sads(A, u.d, (int)(lane % G), G, &luma, &chroma);
+    const uint64_t both = group_sum_u64<G>(((uint64_t)chroma << 32) | luma);   // neither word can carry: 128 * 128 * 255 < 2^32
+    if (lane % G == 0) {
+        const svthip_md_fast_result r = md_fast_finish(u.d, (uint32_t)both, (uint32_t)(both >> 32));
+        uint4 w;
+        w.x = r.luma, w.y = r.chroma, w.z = (uint32_t)r.cost, w.w = (uint32_t)(r.cost >> 32);
+        *reinterpret_cast<uint4*>(A.result + job) = w;
+    }
+}
+
+__global__ void __launch_bounds__(MD_FAST_PICK_THREADS)
+md_fast_pick_kernel(const svthip_md_fast_result* result, const svthip_md_fast_desc* desc, uint32_t n_cand, const svthip_md_fast_group* group,
+                    uint32_t n_groups, svthip_md_fast_pick* pick, uint32_t* refused)
+{
+    __shared__ uint64_t cost[MD_FAST_BUFFERS][MD_FAST_PICK_THREADS];
+    __shared__ uint8_t cand[MD_FAST_BUFFERS][MD_FAST_PICK_THREADS];
+    __shared__ uint8_t best[MD_FAST_BUFFERS][MD_FAST_PICK_THREADS];
+    const uint32_t i = blockIdx.x * MD_FAST_PICK_THREADS + threadIdx.x;
+    if (i >= n_groups) return;
+    union {
+        uint4 q[2];
+        svthip_md_fast_pick p;
+    } o;
+    if (!md_fast_pick_group(result, desc, n_cand, group[i], &cost[0][threadIdx.x], &cand[0][threadIdx.x], &best[0][threadIdx.x],
+                            MD_FAST_PICK_THREADS, &o.p))
+        atomicAdd(refused, 1u);
+    uint4* dst = reinterpret_cast<uint4*>(pick + i);
+    dst[0] = o.q[0], dst[1] = o.q[1];
+}
+
+#endif  // __HIPCC__
+
+}  // namespace svthip

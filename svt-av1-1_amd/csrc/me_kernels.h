@@ -259,6 +259,11 @@ hipError_t launch_pa_denoise(uint8_t* pool, const svthip_pa_picture* pics, const
 hipError_t launch_film_grain_tables(const svthip_film_grain_params& params, int bit_depth, int16_t* tables, hipStream_t s);
 hipError_t launch_film_grain_frame(const svthip_film_grain_params& params, int bit_depth, const void* const src[3], const uint32_t src_stride[3],
                                    void* const dst[3], const uint32_t dst_stride[3], uint32_t width, uint32_t height, const int16_t* tables, hipStream_t s);
+// md_fast.hip: mode decision's fast loop -- SADs and fast cost of predicted PUs, the pick for the full loop (kernels: md_fast_kernels.h)
+hipError_t launch_md_fast_cost(const svthip_inter_planes& src, const svthip_inter_planes& pred, const svthip_md_fast_desc* desc, uint32_t n_cand,
+                               uint32_t bwidth, uint32_t bheight, svthip_md_fast_result* result, hipStream_t s);
+hipError_t launch_md_fast_pick(const svthip_md_fast_result* result, const svthip_md_fast_desc* desc, uint32_t n_cand, const svthip_md_fast_group* group,
+                               uint32_t n_groups, svthip_md_fast_pick* pick, uint32_t* refused, hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

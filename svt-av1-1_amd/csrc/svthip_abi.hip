@@ -2042,7 +2042,7 @@ int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
     if (!n) return SVTHIP_OK;
     HIP_TRY(hipMemsetAsync(d_refused, 0, sizeof(n), s));
     *out_count = n;
-    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) or unit(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, a CfL descriptor with alpha_signs > 7, or a restoration unit that is neither RESTORE_NONE nor RESTORE_WIENER (svthip_av1_[highbd_]lr_filter_frame_dev: a unit of an unknown type, one whose taps or self-guided parameters the call was not given, or self-guided parameters out of range)", (int)n);
+    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) or unit(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, a CfL descriptor with alpha_signs > 7, a fast-loop group out of range (svthip_md_fast_pick_batch_dev), or a restoration unit that is neither RESTORE_NONE nor RESTORE_WIENER (svthip_av1_[highbd_]lr_filter_frame_dev: a unit of an unknown type, one whose taps or self-guided parameters the call was not given, or self-guided parameters out of range)", (int)n);
 }
 
 // ---------------------------------------------------------------- film grain
@@ -2073,6 +2073,37 @@ int32_t svthip_av1_highbd_add_film_grain_dev(svthip_ctx* ctx, const svthip_film_
     TRY(enter(ctx));
     TRY(check_bit_depth_10(bit_depth));
     return add_film_grain_entry(ctx, params, d_src, src_stride, d_dst, dst_stride, width, height, 10, d_tables, stream);
+}
+
+// ---------------------------------------------------------------- mode decision's fast loop
+
+int32_t svthip_md_fast_cost_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* src, const svthip_inter_planes* pred, const svthip_md_fast_desc* d_desc,
+                                      uint32_t n_cand, uint32_t bwidth, uint32_t bheight, svthip_md_fast_result* d_result, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_av1_block(bwidth, bheight));
+    if (n_cand == 0) return SVTHIP_OK;
+    TRY(pred_check_args({src, pred}, d_desc));   // has_uv is device data: every call may touch chroma, so no plane may be null
+    TRY(check_non_null({d_result}));
+    if (!aligned(d_result, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "result array must be 16-byte aligned");
+    HIP_TRY(svthip::launch_md_fast_cost(*src, *pred, d_desc, n_cand, bwidth, bheight, d_result, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_md_fast_pick_batch_dev(svthip_ctx* ctx, const svthip_md_fast_result* d_result, const svthip_md_fast_desc* d_desc, uint32_t n_cand,
+                                      const svthip_md_fast_group* d_group, uint32_t n_groups, svthip_md_fast_pick* d_pick, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_groups == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_result, d_desc, d_group, d_pick}));
+    if (!aligned({d_result, d_desc, d_pick}, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "result, descriptor and pick arrays must be 16-byte aligned");
+    if (!aligned(d_group, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "group array must be 8-byte aligned");
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(scratch_on_stream(ctx, s));
+    TRY(ensure_refused_counter(ctx, s));
+    HIP_TRY(svthip::launch_md_fast_pick(d_result, d_desc, n_cand, d_group, n_groups, d_pick, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
+    ctx->inter_stream = s;
+    return SVTHIP_OK;
 }
 
 // ---------------------------------------------------------------- host-pointer forms (run_queued: no transfer outlives a failed call)
