@@ -97,7 +97,8 @@ __device__ __forceinline__ void alloc_slots(uint4* lists, uint32_t n_pu, const b
 }
 
 __global__ void __launch_bounds__(256) inter_pred_expand_kernel(const svthip_inter_pu_desc* __restrict__ desc, uint32_t n_pu, ExpandArgs A,
-                                                                uint4* __restrict__ lists, uint32_t* __restrict__ refused)
+                                                                uint4* __restrict__ lists, uint32_t* __restrict__ refused,
+                                                                uint8_t* __restrict__ refused_rows)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n_pu;
@@ -177,7 +178,10 @@ __global__ void __launch_bounds__(256) inter_pred_expand_kernel(const svthip_int
                 piece[py * 2 + px] = piece_job((uint32_t)so, cdst + (uint32_t)y * A.cd + (uint32_t)x, c & 15, r & 15, list, fxi, fyi);
             }
     }
-    if (live && !ok) atomicAdd(refused, 1u);
+    if (live && !ok) {
+        atomicAdd(refused, 1u);
+        if (refused_rows) refused_rows[i] = 1;   // for a caller inside the library that has to know which (md_ifs.hip)
+    }
 
     // ---- jobs ----
     const uint32_t np = (uint32_t)(npx * npy);
@@ -311,7 +315,7 @@ size_t inter_pred_scratch_bytes(uint32_t n_pu) { return list_offset(L_PIECE, n_p
 
 hipError_t launch_inter_pred(const svthip_inter_planes& ref0, const svthip_inter_planes& ref1, const svthip_inter_planes& dst,
                              const svthip_inter_pu_desc* desc, uint32_t n_pu, int bw, int bh, int bd, bool use_mfma, void* scratch,
-                             uint32_t* refused, hipStream_t s)
+                             uint32_t* refused, hipStream_t s, uint8_t* refused_rows)
 {
     const int SB = bd > 8 ? 2 : 1;
     const int bwu = chroma_side(bw), bhu = chroma_side(bh);
@@ -325,7 +329,7 @@ hipError_t launch_inter_pred(const svthip_inter_planes& ref0, const svthip_inter
     // the seven list lengths: one strided memset
     hipError_t e = hipMemset2DAsync(sc + count_offset(0, n_pu), list_pitch(n_pu), 0, sizeof(uint32_t), N_LISTS, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(inter_pred_expand_kernel, dim3((n_pu + 255) / 256), dim3(256), 0, s, desc, n_pu, A, reinterpret_cast<uint4*>(sc), refused);
+    hipLaunchKernelGGL(inter_pred_expand_kernel, dim3((n_pu + 255) / 256), dim3(256), 0, s, desc, n_pu, A, reinterpret_cast<uint4*>(sc), refused, refused_rows);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
     auto rb = [SB](const void* p, int64_t k) { return static_cast<const uint8_t*>(p) - k * SB; };

@@ -230,7 +230,7 @@ __device__ __forceinline__ bool md_fast_pick_group(const svthip_md_fast_result* 
     return valid;
 }
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && !defined(SVTHIP_MD_FAST_NO_KERNELS)   // md_ifs_kernels.h takes the readers and the geometry above, not the kernels
 
 // ------------------------------------------------------------------------------------------------ kernels
 

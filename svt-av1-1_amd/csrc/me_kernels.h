@@ -163,7 +163,7 @@ size_t sad_loop_slice_bytes(int w, int h, int sw, int sh, int k);
 // ip_inter_pred.hip: the descriptor expansion and the 2-wide / 2-high chroma pieces
 hipError_t launch_inter_pred(const svthip_inter_planes& ref0, const svthip_inter_planes& ref1, const svthip_inter_planes& dst,
                              const svthip_inter_pu_desc* desc, uint32_t n_pu, int bw, int bh, int bd, bool use_mfma, void* scratch,
-                             uint32_t* refused, hipStream_t s);
+                             uint32_t* refused, hipStream_t s, uint8_t* refused_rows = nullptr);   // refused_rows[i] = 1 for a refused PU i
 size_t inter_pred_scratch_bytes(uint32_t n_pu);
 bool inter_pred_has_pieces(int bw, int bh);
 // ip_warp.hip: warped-motion prediction of whole PUs (the warp kernel; translational chroma through the counted convolution kernels)
@@ -264,6 +264,21 @@ hipError_t launch_md_fast_cost(const svthip_inter_planes& src, const svthip_inte
                                uint32_t bwidth, uint32_t bheight, svthip_md_fast_result* result, hipStream_t s);
 hipError_t launch_md_fast_pick(const svthip_md_fast_result* result, const svthip_md_fast_desc* desc, uint32_t n_cand, const svthip_md_fast_group* group,
                                uint32_t n_groups, svthip_md_fast_pick* pick, uint32_t* refused, hipStream_t s);
+// md_ifs.hip: mode decision's interpolation-filter search -- SSE and modelled rate / distortion of predicted tiles, the search over the
+// filter pairs through launch_inter_pred (kernels: md_ifs_kernels.h)
+struct MdIfsLayout {
+    size_t t_pu, t_desc, t_result, t_refused, unread_counter, y, cb, cr, total;   // byte offsets into the search's scratch, its size
+    uint32_t tiles_per_row, y_stride, c_stride;                                  // the grid of trial tiles
+};
+bool md_ifs_size_ok(uint32_t bwidth, uint32_t bheight);
+uint32_t md_ifs_trials(int32_t search_mode, int32_t enable_dual_filter);   // trial tiles per candidate: 9 full, 3 fast or without the dual filter
+bool md_ifs_layout(uint64_t n_tiles, uint32_t bw, uint32_t bh, MdIfsLayout* L);   // false: more tiles than 16-bit positions address
+hipError_t launch_md_model_rd(const svthip_inter_planes& src, const svthip_inter_planes& pred, const svthip_md_model_rd_desc* desc, uint32_t n_tiles,
+                              uint32_t bwidth, uint32_t bheight, int16_t quantizer, svthip_md_model_rd_result* result, uint32_t* refused, hipStream_t s);
+hipError_t launch_md_ifs_search(const svthip_inter_planes& ref0, const svthip_inter_planes& ref1, const svthip_inter_planes& src,
+                                svthip_inter_pu_desc* pu, const svthip_md_ifs_desc* ifs, uint32_t n_cand, uint32_t bwidth, uint32_t bheight,
+                                int32_t search_mode, int32_t enable_dual_filter, int16_t quantizer, int32_t write_back, svthip_md_ifs_result* result,
+                                bool use_mfma, void* scratch, const MdIfsLayout& L, void* jobs_scratch, uint32_t* refused, hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

@@ -34,6 +34,7 @@ enum Slot {
     SLOT_INTER_REFUSED,   // their refused-PU counter
     SLOT_PA_REGION_SUMS,  // region sums of svthip_pa_histograms_dev on their way to the picture averages: pa_region_sum_bytes
     SLOT_FILM_GRAIN_TABLES,  // the table block of the one-call film-grain form: SVTHIP_FILM_GRAIN_TABLES_BYTES
+    SLOT_MD_IFS,          // trial descriptors, results and tiles of svthip_md_interp_filter_search_batch_dev: svthip::md_ifs_layout
     SLOT_COUNT
 };
 
@@ -281,6 +282,17 @@ int32_t check_av1_block(uint32_t w, uint32_t h)
 {
     return svthip::convolve_size_valid((int)w, (int)h) ? SVTHIP_OK
                                                        : fail(SVTHIP_ERR_BAD_PARAMETER, "not an AV1 block size (width %d)", (int)w);
+}
+int32_t check_md_ifs_size(uint32_t bwidth, uint32_t bheight)
+{
+    if (!svthip::md_ifs_size_ok(bwidth, bheight))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "not one of the 17 AV1 block sizes with both sides above 4 (%d x %d)", (int)bwidth, (int)bheight);
+    return SVTHIP_OK;
+}
+int32_t check_md_ifs_quantizer(int32_t quantizer)   // the reference's int16_t, an int32_t in the ABI
+{
+    if (quantizer < -32768 || quantizer > 32767) return fail(SVTHIP_ERR_BAD_PARAMETER, "quantizer %d is not an int16_t value", (int)quantizer);
+    return SVTHIP_OK;
 }
 int32_t check_tx_size(uint32_t w, uint32_t h)
 {
@@ -1087,6 +1099,14 @@ int32_t svthip_reserve(svthip_ctx* ctx, uint32_t width, uint32_t height, uint32_
     TRY(ensure_scratch(ctx, SLOT_ME_PRED, me_pred_bytes(n, n_pu)));
     TRY(ensure_scratch(ctx, SLOT_PA_REGION_SUMS, svthip::pa_region_sum_bytes(SVTHIP_HME_MAX_JOBS)));
     TRY(ensure_scratch(ctx, SLOT_FILM_GRAIN_TABLES, SVTHIP_FILM_GRAIN_TABLES_BYTES));
+    {   // the interpolation-filter search in its fast mode, one 8x8 candidate per 8x8 block of a picture
+        const uint64_t n_cand = (uint64_t)(width / 8) * (height / 8);
+        svthip::MdIfsLayout L;
+        if (svthip::md_ifs_layout(3 * n_cand, 8, 8, &L)) {
+            TRY(ensure_scratch(ctx, SLOT_MD_IFS, L.total));
+            TRY(ensure_scratch(ctx, SLOT_INTER_JOBS, svthip::inter_pred_scratch_bytes((uint32_t)(3 * n_cand))));
+        }
+    }
     if (host_forms) {
         TRY(ensure_scratch(ctx, SLOT_HOST_POOL, host_pool_layout(width, height).total(3)));
         TRY(ensure_scratch(ctx, SLOT_SB_TABLE, sb_table_bytes(n_sb)));
@@ -2042,7 +2062,7 @@ int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
     if (!n) return SVTHIP_OK;
     HIP_TRY(hipMemsetAsync(d_refused, 0, sizeof(n), s));
     *out_count = n;
-    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) or unit(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, a CfL descriptor with alpha_signs > 7, a fast-loop group out of range (svthip_md_fast_pick_batch_dev), or a restoration unit that is neither RESTORE_NONE nor RESTORE_WIENER (svthip_av1_[highbd_]lr_filter_frame_dev: a unit of an unknown type, one whose taps or self-guided parameters the call was not given, or self-guided parameters out of range)", (int)n);
+    return fail(SVTHIP_ERR_BAD_PARAMETER, "%d PU(s) or unit(s) refused: BI_PRED with sub-8x8 chroma, a block outside the border its edges describe, an invalid warp model, an intra descriptor the reference would assert on, a CfL descriptor with alpha_signs > 7, a fast-loop group out of range (svthip_md_fast_pick_batch_dev), a tile at an odd position (svthip_md_model_rd_batch_dev) or a candidate whose source position is odd or whose PU the prediction refuses (svthip_md_interp_filter_search_batch_dev), or a restoration unit that is neither RESTORE_NONE nor RESTORE_WIENER (svthip_av1_[highbd_]lr_filter_frame_dev: a unit of an unknown type, one whose taps or self-guided parameters the call was not given, or self-guided parameters out of range)", (int)n);
 }
 
 // ---------------------------------------------------------------- film grain
@@ -2102,6 +2122,53 @@ int32_t svthip_md_fast_pick_batch_dev(svthip_ctx* ctx, const svthip_md_fast_resu
     TRY(scratch_on_stream(ctx, s));
     TRY(ensure_refused_counter(ctx, s));
     HIP_TRY(svthip::launch_md_fast_pick(d_result, d_desc, n_cand, d_group, n_groups, d_pick, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
+    ctx->inter_stream = s;
+    return SVTHIP_OK;
+}
+
+// ---------------------------------------------------------------- mode decision's interpolation-filter search
+
+int32_t svthip_md_model_rd_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* src, const svthip_inter_planes* pred, const svthip_md_model_rd_desc* d_desc,
+                                     uint32_t n_tiles, uint32_t bwidth, uint32_t bheight, int32_t quantizer, svthip_md_model_rd_result* d_result, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_md_ifs_size(bwidth, bheight));
+    TRY(check_md_ifs_quantizer(quantizer));
+    if (n_tiles == 0) return SVTHIP_OK;
+    TRY(pred_check_args({src, pred}, d_desc));
+    TRY(check_non_null({d_result}));
+    if (!aligned(d_result, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "result array must be 16-byte aligned");
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(scratch_on_stream(ctx, s));
+    TRY(ensure_refused_counter(ctx, s));
+    HIP_TRY(svthip::launch_md_model_rd(*src, *pred, d_desc, n_tiles, bwidth, bheight, (int16_t)quantizer, d_result, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
+    ctx->inter_stream = s;
+    return SVTHIP_OK;
+}
+
+int32_t svthip_md_interp_filter_search_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* ref0, const svthip_inter_planes* ref1,
+                                                 const svthip_inter_planes* src, svthip_inter_pu_desc* d_pu_desc, const svthip_md_ifs_desc* d_ifs_desc,
+                                                 uint32_t n_cand, uint32_t bwidth, uint32_t bheight, int32_t search_mode, int32_t enable_dual_filter,
+                                                 int32_t quantizer, int32_t write_back, svthip_md_ifs_result* d_result, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_md_ifs_size(bwidth, bheight));
+    if (search_mode != 1 && search_mode != 2) return fail(SVTHIP_ERR_BAD_PARAMETER, "search_mode must be 1 (fast) or 2 (full), not %d", (int)search_mode);
+    TRY(check_md_ifs_quantizer(quantizer));
+    if (n_cand == 0) return SVTHIP_OK;
+    TRY(pred_check_args({ref0, ref1, src}, d_pu_desc));
+    TRY(check_non_null({d_ifs_desc, d_result}));
+    if (!aligned({d_ifs_desc, d_result}, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "search descriptor and result arrays must be 16-byte aligned");
+    const uint64_t n_tiles = (uint64_t)n_cand * svthip::md_ifs_trials(search_mode, enable_dual_filter);
+    svthip::MdIfsLayout L;
+    if (n_tiles > 0x0fffffffu || !svthip::md_ifs_layout(n_tiles, bwidth, bheight, &L))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "too many candidates in one call (%d): their trial tiles pass what 16-bit tile positions address", (int)n_cand);
+    hipStream_t s;
+    TRY(pred_begin(ctx, {ref0, ref1, src}, 8, (uint32_t)n_tiles, 0x0fffffffu, svthip::inter_pred_scratch_bytes, stream, &s));
+    TRY(ensure_scratch(ctx, SLOT_MD_IFS, L.total));
+    HIP_TRY(svthip::launch_md_ifs_search(*ref0, *ref1, *src, d_pu_desc, d_ifs_desc, n_cand, bwidth, bheight, search_mode, enable_dual_filter, (int16_t)quantizer,
+                                         write_back, d_result, !ctx->opt[SVTHIP_OPT_CONVOLVE_VALU], ctx->scratch[SLOT_MD_IFS], L,
+                                         ctx->scratch[SLOT_INTER_JOBS], slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
     ctx->inter_stream = s;
     return SVTHIP_OK;
 }

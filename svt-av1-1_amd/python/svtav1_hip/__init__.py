@@ -28,9 +28,11 @@ from ._restoration import (RESTORE_NONE, RESTORE_SGRPROJ, RESTORE_WIENER, SGRPRO
                            sgrproj_walk_max_trials, sgrproj_workspace_bytes, wiener_walk_max_trials)
 from ._grain import FILM_GRAIN_PARAMS_BYTES, FILM_GRAIN_TABLES_BYTES, FilmGrain, film_grain_param_offsets, film_grain_params
 from ._md import (MD_FAST_CHROMA_QUARTER, MD_FAST_INVALID, MD_FAST_LUMA_GIVEN, MD_FAST_MAX_BUFFERS, MD_FAST_MAX_CANDIDATES, MD_FAST_SKIP_DISTORTION,
-                  MD_FAST_TYPE_INTER, ModeDecisionFast, md_fast_desc_dtype, md_fast_group_dtype, md_fast_pick_dtype, md_fast_result_dtype)
+                  MD_FAST_TYPE_INTER, MD_IFS_REFUSED, MD_IFS_SEARCH_FAST, MD_IFS_SEARCH_FULL, InterpFilterSearch, ModeDecisionFast, md_fast_desc_dtype,
+                  md_fast_group_dtype, md_fast_pick_dtype, md_fast_result_dtype, md_ifs_desc_dtype, md_ifs_result_dtype, md_model_rd_desc_dtype,
+                  md_model_rd_result_dtype)
 from ._host import ME_CU_RESULT_REF_DTYPE, HostForms, HostPicture
 
 
-class Context(ContextCore, MotionEstimation, TransformQuant, PictureAnalysis, Prediction, Cfl, Deblocking, Cdef, Restoration, FilmGrain, ModeDecisionFast, HostForms):
+class Context(ContextCore, MotionEstimation, TransformQuant, PictureAnalysis, Prediction, Cfl, Deblocking, Cdef, Restoration, FilmGrain, ModeDecisionFast, InterpFilterSearch, HostForms):
     """One svthip_ctx (stream + scratch), the analogue of one MeContext_t."""

@@ -1,7 +1,10 @@
-"""Mode decision's fast loop (svthip_md_fast_cost_batch_dev, svthip_md_fast_pick_batch_dev): pointer marshalling only.
+"""Mode decision's fast loop (svthip_md_fast_cost_batch_dev, svthip_md_fast_pick_batch_dev) and its interpolation-filter search
+(svthip_md_model_rd_batch_dev, svthip_md_interp_filter_search_batch_dev): pointer marshalling only.
 
 The four structs cross Python as numpy arrays in device memory; md_fast_desc_dtype() / md_fast_result_dtype() / md_fast_group_dtype() /
-md_fast_pick_dtype() give their layouts (svthip_md_fast_desc, _result, _group, _pick of include/svtav1_hip.h)."""
+md_fast_pick_dtype() give their layouts (svthip_md_fast_desc, _result, _group, _pick of include/svtav1_hip.h); md_model_rd_desc_dtype() /
+md_model_rd_result_dtype() / md_ifs_desc_dtype() / md_ifs_result_dtype() those of the search (svthip_md_model_rd_desc, _result,
+svthip_md_ifs_desc, _result)."""
 from __future__ import annotations
 
 import numpy as np
@@ -47,3 +50,47 @@ class ModeDecisionFast:
         """the buffer walk of the fast loop and PreModeDecision for n_groups blocks: d_group an array of md_fast_group_dtype(), d_pick
         one of md_fast_pick_dtype(); a group out of range is counted (inter_pred_refused)"""
         _check(lib().svthip_md_fast_pick_batch_dev(self._h, d_result, d_desc, n_cand, d_group, n_groups, d_pick, stream))
+
+
+MD_IFS_SEARCH_FAST, MD_IFS_SEARCH_FULL = 1, 2
+MD_IFS_REFUSED = 0xFF   # best_trial of a candidate refused on the device
+
+
+def md_model_rd_desc_dtype() -> np.dtype:
+    """svthip_md_model_rd_desc, 16 bytes; `lambda` is spelled lambda_"""
+    return np.dtype([("src_x", "<u2"), ("src_y", "<u2"), ("pred_x", "<u2"), ("pred_y", "<u2"), ("lambda_", "<u4"), ("rate", "<i4")])
+
+
+def md_model_rd_result_dtype() -> np.dtype:
+    """svthip_md_model_rd_result, 32 bytes"""
+    return np.dtype([("sse", "<u4", (3,)), ("rate", "<i4"), ("dist", "<i8"), ("rd", "<i8")])
+
+
+def md_ifs_desc_dtype() -> np.dtype:
+    """svthip_md_ifs_desc, 32 bytes; filter_rate[dir][filter], dir 0 the vertical (y) filter"""
+    return np.dtype([("src_x", "<u2"), ("src_y", "<u2"), ("lambda_", "<u4"), ("filter_rate", "<i4", (2, 3))])
+
+
+def md_ifs_result_dtype() -> np.dtype:
+    """svthip_md_ifs_result, 32 bytes"""
+    return np.dtype([("interp_filters", "<u4"), ("switchable_rate", "<i4"), ("rd", "<i8"), ("skip_sse_sb", "<i8"), ("skip_txfm_sb", "u1"),
+                     ("best_trial", "u1"), ("reserved", "u1", (6,))])
+
+
+class InterpFilterSearch:
+    """the interpolation-filter search entries as Context methods; planes are InterPlanes of 8-bit planes, the arrays device pointers"""
+
+    def md_model_rd_batch_dev(self, src, pred, d_desc, n_tiles, bwidth, bheight, quantizer, d_result, stream=None):
+        """SSE, modelled rate and distortion and RDCOST of n_tiles predicted tiles of one luma size (8x8 .. 128x128): d_desc an array of
+        md_model_rd_desc_dtype(), d_result one of md_model_rd_result_dtype(); a tile at an odd position is counted (inter_pred_refused)"""
+        _check(lib().svthip_md_model_rd_batch_dev(self._h, _planes_arg(src), _planes_arg(pred), d_desc, n_tiles, bwidth, bheight, quantizer, d_result,
+                                                  stream))
+
+    def md_interp_filter_search_batch_dev(self, ref0, ref1, src, d_pu_desc, d_ifs_desc, n_cand, bwidth, bheight, search_mode, enable_dual_filter,
+                                          quantizer, write_back, d_result, stream=None):
+        """interpolation_filter_search of n_cand candidates of one luma size: d_pu_desc a device array of INTER_PU_DESC_DTYPE (its
+        interp_filters written when write_back), d_ifs_desc one of md_ifs_desc_dtype(), d_result one of md_ifs_result_dtype(); a refused
+        candidate is counted (inter_pred_refused)"""
+        _check(lib().svthip_md_interp_filter_search_batch_dev(self._h, _planes_arg(ref0), _planes_arg(ref1), _planes_arg(src), d_pu_desc, d_ifs_desc,
+                                                              n_cand, bwidth, bheight, search_mode, enable_dual_filter, quantizer, write_back,
+                                                              d_result, stream))
