@@ -1730,6 +1730,147 @@ int32_t svthip_tu_batcher_tx_search_result(const svthip_tu_batcher *b, uint32_t 
 uint16_t svthip_tx_search_type_mask(uint32_t tx_size, int32_t is_inter, int32_t reduced_tx_set, int32_t fast_tx_search);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mode decision's full loop: AV1PerformFullLoop (Codec/EbProductCodingLoop.c:2004-2307) on the candidates svthip_md_fast_pick_batch_dev
+ * left in device memory, and product_full_mode_decision's loop (Codec/EbModeDecision.c:1989-2012) behind it.  8-bit planes, 4:2:0, the 19
+ * block sizes with both sides <= 64 (txb_count == 1: one luma TU of av1_get_tx_size(bsize, 0) = bwidth x bheight and one TU per chroma
+ * plane of txsize_uv = max(4, bwidth / 2) x max(4, bheight / 2), Codec/EbUtility.c:781-817).  Pure integer arithmetic, bit-identical.
+ *
+ * svthip_md_full_loop_batch_dev: the blocks (groups) of ONE luma size.  Per group and slot i < max_full the candidate is row
+ * group.first + pick.buffer_cand[pick.best[i]] of d_fast / d_full; slot i is ACTIVE when i < MIN(pick.full_count, MIN(group.count,
+ * group.buffer_total_count)) (:2573) and that buffer holds a candidate.  Every launch has the shape n_groups * max_full whatever the
+ * picks say -- nothing is read back and nothing in the call synchronises with the host --, so an inactive slot repeats a valid row (the
+ * group's slot 0, or row 0 of the call) and gets row = 0xffffffff and full_cost = ~0 in its result; nothing else of it means anything.
+ * `stages` selects what runs (a mask, at least one bit):
+ *   SVTHIP_MD_FULL_LUMA    ProductFullLoopTxSearch and ProductFullLoop (Codec/EbFullLoop.c:1138-1351, :946-1092): the fused chain of
+ *                          svthip_encode_tu_batch_dev and the rate of svthip_coeff_rate_batch_dev on the luma TU of every slot.  When
+ *                          type_mask_inter or type_mask_intra has more than bit 0, every slot runs every TxType of the two masks' union
+ *                          (into tiles inside d_work), the decision of the batcher's tx-type search picks among the types of the slot's
+ *                          OWN mask (INTER or INTRA candidate), and the chain runs once more with the winner, which leaves the slot's levels
+ *                          and its reconstruction; the numbers are the search candidate's, which is what ProductFullLoop recomputes.  An
+ *                          INTER slot's chroma type then becomes its luma type (TX_TYPE_FIX, :1345-1347).  With both masks == 1 (the
+ *                          reference above ENC_M1, EbProductCodingLoop.c:2129-2151) tx_type_y / tx_type_uv are used as given.
+ *   SVTHIP_MD_FULL_CHROMA  FullLoop_R and CuFullDistortionFastTuMode_R (:1763-2083) on Cb and Cr of the slots whose candidate has has_uv:
+ *                          source and prediction at ((p >> 3) << 3) / 2, distortion >> (MAX_TX_SCALE - av1_get_tx_scale(txsize_uv)) * 2,
+ *                          no three_quad_energy (the reference adds none there), plane_type 1.
+ *   SVTHIP_MD_FULL_DECIDE  per slot Av1TuCalcCostLuma as built with CBF_ZERO_OFF (Codec/EbRateDistortionCost.c:2152-2230: the zero-cbf
+ *                          cost is ~0, so bits and residual distortion stand unless the non-zero cost is ~0 too), luma distortion =
+ *                          (sum + three_quad_energy) >> shift (:1039-1045), then Av1FullCost (:1485-1563) or, with skip_mode_rate !=
+ *                          0xffffffff, Av1MergeSkipFullCost (:1580-1721; skip_cost <= merge_cost takes skip), RDCOST as in the fast loop
+ *                          above; per group the loop of product_full_mode_decision; then the winner's slot tile (Y, and Cb / Cr when
+ *                          has_uv) is copied to `recon` at recon_x / recon_y (chroma at ((p >> 3) << 3) / 2), which is what
+ *                          AV1PerformInverseTransformRecon (EbProductCodingLoop.c:885-1038) leaves there: the chain's clip(pred +
+ *                          inverse) IS the prediction when the eob is 0.
+ * stages = LUMA, then a second call with CHROMA | DECIDE and otherwise the same arguments gives what one call with all three gives: the
+ * state in between lives in d_work and slot_recon.  Between the two a caller may overwrite a slot's chroma PREDICTION tile and its
+ * chroma_rate (UV_CFL_PRED: its luma reconstruction is in the slot tile after LUMA); both are read by the later stages only.
+ *
+ * src: the source picture; pred: the pool the prediction entries wrote; both as for svthip_md_fast_cost_batch_dev, but every stride
+ * (slot_recon's and recon's too) must be <= 65535 (svthip_tu_desc holds 16-bit strides).  A TU's rows are read and written W bytes at a time
+ * and no byte more.
+ * d_fast [n_cand]: the fast loop's rows; src_x/y, pred_x/y, has_uv and the flags TYPE_INTER and INVALID are read.
+ * d_group, d_pick [n_groups]: what svthip_md_fast_pick_batch_dev read and wrote.
+ * svthip_md_full_desc (48 bytes = 3 x 16, the array 16-byte aligned, parallel to d_fast), field by field:
+ *   luma_rate         candidate_ptr->fast_luma_rate
+ *   chroma_rate       fast_chroma_rate, plus the CfL terms of EbRateDistortionCost.c:1522-1535 when they apply (table look-ups: host work)
+ *   skip_mode_rate    skipModeFacBits[skip_flag_context][1] for an INTER candidate with merge_flag, else 0xffffffff: selects
+ *                     Av1MergeSkipFullCost or Av1FullCost as Av1InterFullCost / Av1IntraFullCost do (:1737-1840)
+ *   lambda            context_ptr->full_lambda
+ *   recon_x, recon_y  luma position of the block in `recon`
+ *   qparam_index[3]   row of d_qparams for Y, Cb, Cr
+ *   tx_type_y, tx_type_uv   candidate_ptr->transform_type[PLANE_TYPE_Y / _UV]; tx_type_y is ignored when a search runs
+ *   txb_skip_ctx[3], dc_sign_ctx[3]   cu_ptr->luma_txb_skip_context, cb_, cr_ and luma_dc_sign_context, cb_, cr_ (:1377-1382)
+ *   intra_mode        candidate_ptr->pred_mode of an INTRA candidate (tx-type rate, best_intra_mode)
+ *   reserved          ignored
+ * d_qparams, d_iscan, iscan_offsets[tx_size * 16 + tx_type] (a HOST array, read during the call): as for the batcher's tx-type search;
+ * d_tables: as for svthip_coeff_rate_batch_dev; reduced_tx_set: reduced_tx_set_used.
+ * type_mask_inter / _intra: svthip_tx_search_type_mask of the luma TxSize.  max_full: slots per group, 1..12 (MAX_NFL); a group with
+ * more picks than that has its first max_full evaluated.
+ * slot_recon, tiles_per_row: a caller-owned pool; slot k = group * max_full + i reconstructs into the tile at ((k % tiles_per_row) *
+ * max(8, bwidth), (k / tiles_per_row) * max(8, bheight)), Cb / Cr at half that.  The pitch of at least 8 keeps the chroma tiles of two
+ * 4-wide slots apart.  No two TUs of a launch overlap: that is why the slots do not reconstruct into `recon`.
+ * d_work: svthip_md_full_workspace_bytes(n_groups, max_full, bwidth, bheight, type_mask_inter, type_mask_intra) bytes, 16-byte aligned.
+ * svthip_md_full_result (144 bytes = 9 x 16, [n_groups * max_full], 16-byte aligned), written by DECIDE:
+ *   full_cost         *full_cost_ptr; ~0 for an inactive slot, for an INVALID candidate (WARPED_CAUSAL with local_warp_valid == 0:
+ *                     the reference `continue`s, :2083-2084, and leaves a stale cost) and for a slot whose tx_type the chain has no
+ *                     network for; the other numbers of such a row are 0
+ *   merge_cost, skip_cost   *full_cost_merge_ptr, *full_cost_skip_ptr (Av1MergeSkipFullCost; 0 otherwise)
+ *   full_lambda_rate  as the reference forms it: full_cost minus the UNSCALED distortion sum (:1558, :1707)
+ *   full_cost_luma    Av1FullCost only (0 otherwise)
+ *   y_, cb_, cr_distortion   {DIST_CALC_RESIDUAL, DIST_CALC_PREDICTION} after the shifts (chroma 0 without has_uv)
+ *   coeff_bits[3]     y_coeff_bits, cb_coeff_bits, cr_coeff_bits
+ *   quantized_dc[3], eob[3]   candidate_ptr->quantized_dc, ->eob[plane][0]
+ *   row               the candidate's row, 0xffffffff for an inactive slot
+ *   tx_type_y, tx_type_uv     the types used
+ *   y_, u_, v_has_coeff       eob != 0; block_has_coeff = y | u | v.  The reference assigns block_has_coeff only when has_uv (:2229)
+ *                             and leaves the previous value otherwise; this field is always y | u | v
+ *   skip_flag         skip_cost <= merge_cost (Av1MergeSkipFullCost), else 0
+ * svthip_md_full_decision (16 bytes, [n_groups], 16-byte aligned): winner_slot (the i of the lowest full_cost: starts at slot 0, strict
+ * <), winner_buffer = pick.best[winner_slot] (the reference's lowestCostIndex), winner_row, cost, best_intra_mode (pred_mode of the INTRA
+ * slot with the lowest cost, strict <, 0xff without one), n_full (the active slot count).
+ * Refused with SVTHIP_ERR_BAD_PARAMETER and text before any launch: a size not among the 19; stages 0 or with unknown bits; max_full
+ * outside 1..12; tiles_per_row 0; a mask that is 0, has bits above 15 or names a TxType the luma size has no network for; with n_groups
+ * > 0 (n_groups == 0 returns OK) a null pointer or plane, n_cand 0, an array not 16-byte aligned (d_group 8), a stride above 65535, tiles
+ * or coefficients beyond 32-bit offsets.  Refused ON THE DEVICE, counted once each and reported by svthip_inter_pred_refused: a group
+ * the pick refused (its decision: winner_slot = winner_buffer = best_intra_mode = 0xff, winner_row = 0xffffffff, cost = ~0, n_full = 0;
+ * nothing is copied), and an active slot whose tx_type_uv -- or, without a search, tx_type_y -- the chain has no network for (it runs as
+ * DCT_DCT and cannot win). */
+#define SVTHIP_MD_FULL_LUMA 1u
+#define SVTHIP_MD_FULL_CHROMA 2u
+#define SVTHIP_MD_FULL_DECIDE 4u
+#define SVTHIP_MD_FULL_MAX_SLOTS 12 /* MAX_NFL */
+
+typedef struct svthip_md_full_desc {
+    uint32_t luma_rate;
+    uint32_t chroma_rate;
+    uint32_t skip_mode_rate;
+    uint32_t lambda;
+    uint16_t recon_x, recon_y;
+    uint16_t qparam_index[3];
+    uint8_t tx_type_y, tx_type_uv;
+    uint8_t txb_skip_ctx[3];
+    uint8_t dc_sign_ctx[3];
+    uint8_t intra_mode;
+    uint8_t reserved[13];
+} svthip_md_full_desc;
+
+typedef struct svthip_md_full_result {
+    uint64_t full_cost;
+    uint64_t merge_cost, skip_cost;
+    uint64_t full_lambda_rate;
+    uint64_t full_cost_luma;
+    uint64_t y_distortion[2], cb_distortion[2], cr_distortion[2];
+    uint64_t coeff_bits[3];
+    int32_t quantized_dc[3];
+    uint32_t row;
+    uint16_t eob[3];
+    uint8_t tx_type_y, tx_type_uv;
+    uint8_t y_has_coeff, u_has_coeff, v_has_coeff, block_has_coeff;
+    uint8_t skip_flag;
+    uint8_t reserved[3];
+} svthip_md_full_result;
+
+typedef struct svthip_md_full_decision {
+    uint64_t cost;
+    uint32_t winner_row;
+    uint8_t winner_slot;
+    uint8_t winner_buffer;
+    uint8_t best_intra_mode;
+    uint8_t n_full;
+} svthip_md_full_decision;
+
+size_t svthip_md_full_workspace_bytes(uint32_t n_groups, uint32_t max_full, uint32_t bwidth, uint32_t bheight, uint32_t type_mask_inter,
+                                      uint32_t type_mask_intra); /* 0 for arguments the entry refuses */
+int32_t svthip_md_full_loop_batch_dev(svthip_ctx *ctx, const svthip_inter_planes *src, const svthip_inter_planes *pred,
+                                      const svthip_md_fast_desc *d_fast, const svthip_md_full_desc *d_full, uint32_t n_cand,
+                                      const svthip_md_fast_group *d_group, const svthip_md_fast_pick *d_pick, uint32_t n_groups,
+                                      uint32_t bwidth, uint32_t bheight, const int16_t *d_qparams, const int16_t *d_iscan,
+                                      const uint32_t iscan_offsets[19 * 16], const svthip_coeff_rate_tables *d_tables, int32_t reduced_tx_set,
+                                      uint32_t type_mask_inter, uint32_t type_mask_intra, uint32_t max_full,
+                                      const svthip_inter_planes *slot_recon, uint32_t tiles_per_row, const svthip_inter_planes *recon,
+                                      void *d_work, uint32_t stages, svthip_md_full_result *d_result, svthip_md_full_decision *d_decision,
+                                      void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Reference-layout results and host-pointer forms (what a C host that owns host memory binds).
  *
  * svthip_me_cu_result_ref has the memory layout of the reference's MeCuResults_t (Codec/EbMotionEstimationLcuResults.h:56-76) as

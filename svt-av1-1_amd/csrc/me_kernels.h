@@ -5,6 +5,7 @@
 
 #include "../../include/svtav1_hip.h"
 #include "tq_tile.h"
+#include "tq_tx_search_tu.h"
 
 // LDS row pitch of the staged reference window.  192 B: >= 16*8 + 64 (widest lane footprint at
 // search_area_width 127) and == 48 dwords, which puts rows y, y+3, y+5, y+6 (one ds_read_b128 lane
@@ -116,14 +117,7 @@ __host__ __device__ inline int tx_h(int tx_size)
 }
 
 // tq_coeff_rate.hip: the rate kernel (svthip_coeff_rate_batch_dev) and the batcher's RD decision.  A search TU on the device:
-// index[t] = the position of its TxType-t candidate inside the (tx_size, t) run of the launch order (0xffffffff: not a candidate),
-// bases[tx_size * 16 + t] = where that run starts.
-struct tx_search_tu_dev {
-    uint64_t lambda;
-    uint32_t index[16];
-    uint32_t tx_size;
-    uint32_t reserved;
-};
+// tx_search_tu_dev (tq_tx_search_tu.h).
 hipError_t launch_coeff_rate(const svthip_coeff_rate_tables* tables, const int32_t* qcoeff, const uint16_t* eob, const int16_t* iscan,
                              const svthip_coeff_rate_desc* desc, uint32_t n_tu, int tx_size, uint32_t* bits, hipStream_t s);
 hipError_t launch_tx_decision(const tx_search_tu_dev* tus, uint32_t n_tus, const uint32_t* bases, const uint16_t* eob, const uint64_t* energy,
@@ -279,6 +273,34 @@ hipError_t launch_md_ifs_search(const svthip_inter_planes& ref0, const svthip_in
                                 svthip_inter_pu_desc* pu, const svthip_md_ifs_desc* ifs, uint32_t n_cand, uint32_t bwidth, uint32_t bheight,
                                 int32_t search_mode, int32_t enable_dual_filter, int16_t quantizer, int32_t write_back, svthip_md_ifs_result* result,
                                 bool use_mfma, void* scratch, const MdIfsLayout& L, void* jobs_scratch, uint32_t* refused, hipStream_t s);
+// md_full.hip: mode decision's full loop -- per slot the fused chain and the rate on Y, Cb and Cr with the tx-type search, the full cost,
+// the decision per block, the winner's reconstruction (kernels: md_full_kernels.h)
+struct MdFullLayout {   // byte offsets into the caller's workspace, its size, and the TxTypes a search runs
+    size_t slots, tu[3], rate[3], eob[3], dist[3], bits[3], qcoeff[3], energy_y;
+    size_t s_tu, s_rate, s_eob, s_energy, s_dist, s_bits, s_qcoeff, s_recon, s_tus, s_bases, s_out, total;
+    uint32_t n_slots, n_types;   // n_types 0: no search
+    uint8_t types[16];
+};
+struct MdFullCall {   // the arguments of svthip_md_full_loop_batch_dev
+    svthip_inter_planes src, pred, slot_recon, recon;
+    const svthip_md_fast_desc* fast;
+    const svthip_md_full_desc* full;
+    const svthip_md_fast_group* group;
+    const svthip_md_fast_pick* pick;
+    uint32_t n_cand, n_groups, bwidth, bheight, max_full, tiles_per_row, type_mask_inter, type_mask_intra, stages;
+    int32_t reduced_tx_set;
+    const int16_t *qparams, *iscan;
+    const uint32_t* iscan_offsets;   // host, [19 * 16]
+    const svthip_coeff_rate_tables* tables;
+    void* work;
+    svthip_md_full_result* result;
+    svthip_md_full_decision* decision;
+    uint32_t* refused;
+    uint32_t max_workgroups;         // SVTHIP_OPT_TQ_MAX_WORKGROUPS
+};
+bool md_full_size_ok(uint32_t bwidth, uint32_t bheight);
+bool md_full_layout(uint32_t n_groups, uint32_t max_full, uint32_t bw, uint32_t bh, uint32_t mask_inter, uint32_t mask_intra, MdFullLayout* L);
+hipError_t launch_md_full_loop(const MdFullCall& C, const MdFullLayout& L, hipStream_t s);
 
 inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
 

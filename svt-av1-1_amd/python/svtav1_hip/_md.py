@@ -1,10 +1,11 @@
-"""Mode decision's fast loop (svthip_md_fast_cost_batch_dev, svthip_md_fast_pick_batch_dev) and its interpolation-filter search
-(svthip_md_model_rd_batch_dev, svthip_md_interp_filter_search_batch_dev): pointer marshalling only.
+"""Mode decision's fast loop (svthip_md_fast_cost_batch_dev, svthip_md_fast_pick_batch_dev), its interpolation-filter search
+(svthip_md_model_rd_batch_dev, svthip_md_interp_filter_search_batch_dev) and its full loop (svthip_md_full_loop_batch_dev): pointer
+marshalling only.
 
 The four structs cross Python as numpy arrays in device memory; md_fast_desc_dtype() / md_fast_result_dtype() / md_fast_group_dtype() /
 md_fast_pick_dtype() give their layouts (svthip_md_fast_desc, _result, _group, _pick of include/svtav1_hip.h); md_model_rd_desc_dtype() /
 md_model_rd_result_dtype() / md_ifs_desc_dtype() / md_ifs_result_dtype() those of the search (svthip_md_model_rd_desc, _result,
-svthip_md_ifs_desc, _result)."""
+svthip_md_ifs_desc, _result); md_full_desc_dtype() / md_full_result_dtype() / md_full_decision_dtype() those of the full loop."""
 from __future__ import annotations
 
 import numpy as np
@@ -94,3 +95,50 @@ class InterpFilterSearch:
         _check(lib().svthip_md_interp_filter_search_batch_dev(self._h, _planes_arg(ref0), _planes_arg(ref1), _planes_arg(src), d_pu_desc, d_ifs_desc,
                                                               n_cand, bwidth, bheight, search_mode, enable_dual_filter, quantizer, write_back,
                                                               d_result, stream))
+
+
+MD_FULL_LUMA, MD_FULL_CHROMA, MD_FULL_DECIDE = 1, 2, 4
+MD_FULL_MAX_SLOTS = 12
+MD_FULL_NONE = 0xFFFFFFFF   # row of an inactive slot, winner_row of a refused group
+
+
+def md_full_desc_dtype() -> np.dtype:
+    """svthip_md_full_desc, 48 bytes; `lambda` is spelled lambda_"""
+    return np.dtype([("luma_rate", "<u4"), ("chroma_rate", "<u4"), ("skip_mode_rate", "<u4"), ("lambda_", "<u4"), ("recon_x", "<u2"), ("recon_y", "<u2"),
+                     ("qparam_index", "<u2", (3,)), ("tx_type_y", "u1"), ("tx_type_uv", "u1"), ("txb_skip_ctx", "u1", (3,)), ("dc_sign_ctx", "u1", (3,)),
+                     ("intra_mode", "u1"), ("reserved", "u1", (13,))])
+
+
+def md_full_result_dtype() -> np.dtype:
+    """svthip_md_full_result, 144 bytes"""
+    return np.dtype([("full_cost", "<u8"), ("merge_cost", "<u8"), ("skip_cost", "<u8"), ("full_lambda_rate", "<u8"), ("full_cost_luma", "<u8"),
+                     ("y_distortion", "<u8", (2,)), ("cb_distortion", "<u8", (2,)), ("cr_distortion", "<u8", (2,)), ("coeff_bits", "<u8", (3,)),
+                     ("quantized_dc", "<i4", (3,)), ("row", "<u4"), ("eob", "<u2", (3,)), ("tx_type_y", "u1"), ("tx_type_uv", "u1"), ("y_has_coeff", "u1"),
+                     ("u_has_coeff", "u1"), ("v_has_coeff", "u1"), ("block_has_coeff", "u1"), ("skip_flag", "u1"), ("reserved", "u1", (3,))])
+
+
+def md_full_decision_dtype() -> np.dtype:
+    """svthip_md_full_decision, 16 bytes"""
+    return np.dtype([("cost", "<u8"), ("winner_row", "<u4"), ("winner_slot", "u1"), ("winner_buffer", "u1"), ("best_intra_mode", "u1"), ("n_full", "u1")])
+
+
+def md_full_workspace_bytes(n_groups, max_full, bwidth, bheight, type_mask_inter, type_mask_intra) -> int:
+    """bytes of d_work for a call of md_full_loop_batch_dev; 0 for arguments the entry refuses"""
+    return int(lib().svthip_md_full_workspace_bytes(n_groups, max_full, bwidth, bheight, type_mask_inter, type_mask_intra))
+
+
+class ModeDecisionFull:
+    """the full-loop entry as a Context method; planes are InterPlanes of 8-bit planes, the arrays device pointers"""
+
+    def md_full_loop_batch_dev(self, src, pred, d_fast, d_full, n_cand, d_group, d_pick, n_groups, bwidth, bheight, d_qparams, d_iscan, iscan_offsets,
+                               d_tables, reduced_tx_set, type_mask_inter, type_mask_intra, max_full, slot_recon, tiles_per_row, recon, d_work, stages,
+                               d_result, d_decision, stream=None):
+        """T/Q, rate, full cost, decision and the winner's reconstruction for n_groups blocks of one luma size: d_fast / d_group / d_pick the
+        arrays of the fast loop, d_full one of md_full_desc_dtype(), iscan_offsets [19][16] host integers, d_work md_full_workspace_bytes(..)
+        bytes, d_result n_groups * max_full rows of md_full_result_dtype(), d_decision n_groups of md_full_decision_dtype(); a group the pick
+        refused or a TxType without a network is counted (inter_pred_refused)"""
+        offsets = None if iscan_offsets is None else np.ascontiguousarray(np.asarray(iscan_offsets, np.uint32).reshape(19 * 16))
+        _check(lib().svthip_md_full_loop_batch_dev(self._h, _planes_arg(src), _planes_arg(pred), d_fast, d_full, n_cand, d_group, d_pick, n_groups, bwidth,
+                                                   bheight, d_qparams, d_iscan, None if offsets is None else offsets.ctypes.data, d_tables, reduced_tx_set,
+                                                   type_mask_inter, type_mask_intra, max_full, _planes_arg(slot_recon), tiles_per_row, _planes_arg(recon),
+                                                   d_work, stages, d_result, d_decision, stream))
