@@ -21,13 +21,14 @@ def _ready(torch):
 
 
 class Guarded:
-    """three planes embedded in larger allocations filled with a guard pattern"""
+    """three planes embedded in larger allocations filled with a guard pattern; `extra` widens every row, so that two buffers of one
+    picture can have different strides"""
 
-    def __init__(self, torch, planes, bd):
-        self.bd, self.host, self.dev, self.ptr, self.stride = bd, [], [], [], []
+    def __init__(self, torch, planes, bd, extra=0):
+        self.bd, self.extra, self.host, self.dev, self.ptr, self.stride = bd, extra, [], [], [], []
         for p, pl in enumerate(planes):
             ph, pw = pl.shape
-            big = np.full((ph + 2 * GUARD, pw + 2 * GUARD + p), FILL[bd] + p, pl.dtype)
+            big = np.full((ph + 2 * GUARD, pw + 2 * GUARD + p + extra), FILL[bd] + p, pl.dtype)
             big[GUARD:GUARD + ph, GUARD:GUARD + pw] = pl
             d = _dev(torch, big)
             self.host.append(big), self.dev.append(d)
@@ -39,7 +40,7 @@ class Guarded:
         out, ok = [], True
         for p in range(3):
             big = self.dev[p].cpu().numpy().view(self.host[p].dtype).reshape(self.host[p].shape)
-            ph, pw = big.shape[0] - 2 * GUARD, big.shape[1] - 2 * GUARD - p
+            ph, pw = big.shape[0] - 2 * GUARD, big.shape[1] - 2 * GUARD - p - self.extra
             out.append(big[GUARD:GUARD + ph, GUARD:GUARD + pw].copy())
             mask = np.ones(big.shape, bool)
             mask[GUARD:GUARD + ph, GUARD:GUARD + pw] = False

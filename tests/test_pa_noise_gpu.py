@@ -51,8 +51,9 @@ def _chroma_view(pool, at, cstride, w, h):
 class _Run:
     """the pictures of one launch on the device, the outputs pre-filled"""
 
-    def __init__(self, torch, ctx, planes, write=True):
-        self.torch, self.ctx, self.planes = torch, ctx, planes
+    def __init__(self, torch, ctx, planes, write=True, s=None):
+        self.torch, self.ctx, self.planes, self.s = torch, ctx, planes, s
+        self.stream = s.cuda_stream if s is not None else None
         self.pool, self.descs, self.offsets, self.cstride = _pool(planes)
         self.h, self.w = planes[0][0].shape
         self.n, self.n_sb = len(planes), pu.sb_grid(self.w, self.h)[0] * pu.sb_grid(self.w, self.h)[1]
@@ -63,12 +64,22 @@ class _Run:
         self.d_var = torch.full((self.n, self.n_sb, 2), FILL64, dtype=torch.int64, device=dev)
         self.d_flat = torch.full((self.n, self.n_sb), FILL8, dtype=torch.uint8, device=dev)
         self.d_pic = torch.full((self.n, 4), FILL32, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize()
+        if s is None:
+            torch.cuda.synchronize()
+        else:
+            s.wait_stream(torch.cuda.current_stream())   # stream order behind the upload and the fills, not a host wait
+
+    def _wait(self):
+        """the context's stream, or the caller's stream alone when the run has one"""
+        if self.s is None:
+            self.ctx.synchronize()
+        else:
+            self.s.synchronize()
 
     def detect(self, sub):
         self.ctx.pa_noise_detect_dev(self.d_pool.data_ptr(), self.descs, sub, self.d_den.data_ptr() if self.d_den is not None else None, self.dstride,
-                                     self.d_var.data_ptr(), self.d_flat.data_ptr(), self.d_pic.data_ptr())
-        self.ctx.synchronize()
+                                     self.d_var.data_ptr(), self.d_flat.data_ptr(), self.d_pic.data_ptr(), stream=self.stream)
+        self._wait()
         out = {"sb_var": self.d_var.cpu().numpy().view(np.uint64), "flat_noise": self.d_flat.cpu().numpy(), "picture": self.d_pic.cpu().numpy().view(np.uint32)}
         if self.d_den is not None:
             out["denoised"] = self.d_den.cpu().numpy()
@@ -76,8 +87,8 @@ class _Run:
 
     def denoise(self):
         self.ctx.pa_denoise_dev(self.d_pool.data_ptr(), self.descs, self.offsets, self.cstride, self.d_den.data_ptr(), self.dstride, self.d_flat.data_ptr(),
-                                self.d_pic.data_ptr())
-        self.ctx.synchronize()
+                                self.d_pic.data_ptr(), stream=self.stream)
+        self._wait()
         return self.d_pool.cpu().numpy()
 
     def expected_pool(self, outs):
@@ -179,6 +190,21 @@ def test_chain_detect_denoise_derive_statistics(hip_ctx):
     want = pu.all_stats(o["out_luma"], o["out_cb"], o["out_cr"], sub)
     for k in pu.OUTPUTS:
         assert np.array_equal(d[k][0].cpu().numpy().view(want[k].dtype).reshape(want[k].shape), want[k]), k
+
+
+def test_caller_stream_without_synchronisation(hip_ctx):
+    """detection and denoising of one fixture case on a caller's stream; the host waits on that stream alone"""
+    torch = pytest.importorskip("torch")
+    w, h, pics = nu.fixture_cases()[1]      # 136x72
+    sub = 1
+    run = _Run(torch, hip_ctx, [p[:3] for p in pics], s=torch.cuda.Stream())
+    got = run.detect(sub)
+    for i, (_, _, _, outs) in enumerate(pics):
+        for k in nu.DETECT_OUTPUTS:
+            assert np.array_equal(got[k][i], outs[sub][k]), (i, k)
+        assert np.array_equal(got["denoised"][i][:, :w], outs[sub]["denoised"]), i
+    after = run.denoise()
+    assert np.array_equal(after, run.expected_pool([(p[3][sub]["out_luma"], p[3][sub]["out_cb"], p[3][sub]["out_cr"]) for p in pics]))
 
 
 def test_refused_arguments(hip_ctx):

@@ -41,8 +41,9 @@ def _pool(planes):
     return pool, descs, offsets, cstride
 
 
-def _run(torch, ctx, planes, sub, entries=(1, 2, 3)):
-    """the three entries over the pictures of one launch -> {output: [n] + shape}"""
+def _run(torch, ctx, planes, sub, entries=(1, 2, 3), s=None):
+    """the three entries over the pictures of one launch -> {output: [n] + shape}.  s: a torch stream that every call is given; the
+    outputs are then read back behind the calls on that stream and the context is not synchronised"""
     pool, descs, offsets, cstride = _pool(planes)
     h, w = planes[0][0].shape
     n, n_sb = len(planes), pu.sb_grid(w, h)[0] * pu.sb_grid(w, h)[1]
@@ -53,19 +54,28 @@ def _run(torch, ctx, planes, sub, entries=(1, 2, 3)):
               "average_intensity": ((n, 3), torch.int32)}
     d = {k: torch.full(s, 0xAA if t == torch.uint8 else -1431655766 if t == torch.int32 else -21846 if t == torch.int16 else -6148914691236517206,
                        dtype=t, device="cuda:0") for k, (s, t) in shapes.items()}
-    torch.cuda.synchronize()
-    ctx.pa_derive_planes_dev(d_pool.data_ptr(), descs)
+    stream = s.cuda_stream if s is not None else None
+    if s is None:
+        torch.cuda.synchronize()
+    else:
+        s.wait_stream(torch.cuda.current_stream())   # stream order behind the upload and the fills, not a host wait
+    ctx.pa_derive_planes_dev(d_pool.data_ptr(), descs, stream=stream)
     if 1 in entries:
         ctx.pa_block_stats_dev(d_pool.data_ptr(), descs, offsets, cstride, sub, d["y_mean"].data_ptr(), d["variance"].data_ptr(), d["cb_mean"].data_ptr(),
-                               d["cr_mean"].data_ptr())
+                               d["cr_mean"].data_ptr(), stream=stream)
     if 2 in entries:
-        ctx.pa_homogeneity_dev(d["variance"].data_ptr(), w, h, n, d["var_of_var"].data_ptr(), d["homogeneous"].data_ptr(), d["picture"].data_ptr())
+        ctx.pa_homogeneity_dev(d["variance"].data_ptr(), w, h, n, d["var_of_var"].data_ptr(), d["homogeneous"].data_ptr(), d["picture"].data_ptr(),
+                               stream=stream)
     if 3 in entries:
         ctx.pa_histograms_dev(d_pool.data_ptr(), descs, offsets, cstride, d["histogram"].data_ptr(), d["region_intensity"].data_ptr(),
-                              d["average_intensity"].data_ptr())
-    ctx.synchronize()
+                              d["average_intensity"].data_ptr(), stream=stream)
     unsigned = {torch.uint8: np.uint8, torch.int16: np.uint16, torch.int32: np.uint32, torch.int64: np.uint64}
-    return {k: t.cpu().numpy().view(unsigned[shapes[k][1]]) for k, t in d.items()}
+    if s is None:
+        ctx.synchronize()
+        return {k: t.cpu().numpy().view(unsigned[shapes[k][1]]) for k, t in d.items()}
+    with torch.cuda.stream(s):
+        host = {k: t.to("cpu") for k, t in d.items()}   # enqueued on s behind the entries
+    return {k: t.numpy().view(unsigned[shapes[k][1]]) for k, t in host.items()}
 
 
 @pytest.mark.parametrize("sub", (0, 1))
@@ -93,6 +103,18 @@ def test_batch_of_three_equals_three_single_launches(hip_ctx):
         single = _run(torch, hip_ctx, [planes], 1)
         for k in pu.OUTPUTS:
             assert np.array_equal(batch[k][i], single[k][0]), (i, k)
+
+
+def test_caller_stream_without_synchronisation(hip_ctx):
+    """one fixture picture through svthip_pa_derive_planes_dev and the three entries on a caller's stream, svthip_pa_histograms_dev with
+    its region sums in context scratch among them; twice, so that the second run finds the scratch as the first left it"""
+    torch = pytest.importorskip("torch")
+    w, h, pics = pu.fixture_cases()[3]      # 200x136
+    luma, cb, cr, outs = pics[1]
+    for _ in range(2):
+        got = _run(torch, hip_ctx, [(luma, cb, cr)], 1, s=torch.cuda.Stream())
+        for k in pu.OUTPUTS:
+            assert np.array_equal(got[k][0], outs[1][k]), k
 
 
 def test_refused_arguments(hip_ctx):
