@@ -2,7 +2,7 @@
 // over all filter blocks, the strength pick, the frame filter, the luma distortion of a batch of block pairs) and lambda from the
 // quantiser table.  The contract is in include/svtav1_hip.h.  Not here: 128x128 superblocks, the fast search, 12 bits, 4:2:2 / 4:4:0,
 // more than one tile.
-#include "me_kernels.h"
+#include "cf_launch.h"
 
 #include "cf_cdef_kernels.h"
 

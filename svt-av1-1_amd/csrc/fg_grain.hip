@@ -9,7 +9,7 @@
 #include <string.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "fg_launch.h"
 #include "fg_grain_kernels.h"
 
 namespace svthip {

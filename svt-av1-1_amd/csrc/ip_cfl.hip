@@ -26,7 +26,7 @@
 #include <type_traits>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "ip_launch.h"
 
 static_assert(sizeof(svthip_cfl_desc) == 32, "svthip_cfl_desc is 32 bytes (include/svtav1_hip.h)");
 static_assert(sizeof(svthip_cfl_decision_job) == 16, "svthip_cfl_decision_job is 16 bytes (include/svtav1_hip.h)");

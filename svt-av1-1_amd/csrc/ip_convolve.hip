@@ -20,7 +20,7 @@
 
 #include "../../include/svtav1_hip.h"
 #include "ip_common.h"
-#include "me_kernels.h"
+#include "ip_launch.h"
 
 namespace svthip {
 
@@ -195,10 +195,12 @@ const ConvolveKernel kConvolveKernels[2][2][2][2] = {{SVTHIP_CONV_ROW(4, false),
 #undef SVTHIP_CONV_ROW
 }  // namespace
 
-void convolve_dynamic_lds_kernels(const void** list)
+hipError_t convolve_raise_dynamic_lds()
 {
-    static_assert(sizeof(kConvolveKernels[1]) / sizeof(ConvolveKernel) == kConvolveDynamicLdsKernels, "the compound half of the table");
-    for (int i = 0; i < kConvolveDynamicLdsKernels; i++) list[i] = reinterpret_cast<const void*>(kConvolveKernels[1][i >> 2][(i >> 1) & 1][i & 1]);
+    constexpr int n = sizeof(kConvolveKernels[1]) / sizeof(ConvolveKernel);  // the compound half of the table
+    const void* list[n];
+    for (int i = 0; i < n; i++) list[i] = reinterpret_cast<const void*>(kConvolveKernels[1][i >> 2][(i >> 1) & 1][i & 1]);
+    return raise_dynamic_lds(list);
 }
 
 hipError_t launch_convolve_valu(const ConvolveLaunch& L, hipStream_t s)

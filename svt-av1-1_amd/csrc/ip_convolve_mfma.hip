@@ -24,7 +24,7 @@
 
 #include "../../include/svtav1_hip.h"
 #include "ip_common.h"
-#include "me_kernels.h"
+#include "ip_launch.h"
 
 namespace svthip {
 

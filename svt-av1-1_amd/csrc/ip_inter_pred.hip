@@ -22,7 +22,7 @@
 
 #include "../../include/svtav1_hip.h"
 #include "ip_common.h"
-#include "me_kernels.h"
+#include "ip_launch.h"
 
 static_assert(sizeof(svthip_inter_pu_desc) == 64, "svthip_inter_pu_desc is 64 bytes (include/svtav1_hip.h)");
 

@@ -28,7 +28,7 @@
 #include <type_traits>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "ip_launch.h"
 
 static_assert(sizeof(svthip_intra_desc) == 32, "svthip_intra_desc is 32 bytes (include/svtav1_hip.h)");
 

@@ -26,7 +26,7 @@
 
 #include "../../include/svtav1_hip.h"
 #include "ip_common.h"
-#include "me_kernels.h"
+#include "ip_launch.h"
 
 static_assert(sizeof(svthip_warp_pu_desc) == 64, "svthip_warp_pu_desc is 64 bytes (include/svtav1_hip.h)");
 

@@ -30,7 +30,7 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "lf_launch.h"
 
 static_assert(sizeof(svthip_lf_mi) == 4, "svthip_lf_mi is 4 bytes (include/svtav1_hip.h)");
 

@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "md_launch.h"
 #include "md_fast_kernels.h"
 
 namespace svthip {

@@ -10,7 +10,8 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "md_launch.h"
+#include "tq_launch.h"
 #include "md_full_kernels.h"
 
 namespace svthip {

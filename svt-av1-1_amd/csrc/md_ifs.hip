@@ -9,7 +9,8 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "ip_launch.h"
+#include "md_launch.h"
 #include "md_ifs_kernels.h"
 
 namespace svthip {

@@ -1,0 +1,56 @@
+// svt-av1-1_amd/csrc/md_launch.h -- launch boundary of the mode-decision family (md_*.hip): what the C-ABI glue calls.
+#pragma once
+#include "svthip_internal.h"
+
+namespace svthip {
+
+// md_fast.hip: mode decision's fast loop -- SADs and fast cost of predicted PUs, the pick for the full loop (kernels: md_fast_kernels.h)
+hipError_t launch_md_fast_cost(const svthip_inter_planes& src, const svthip_inter_planes& pred, const svthip_md_fast_desc* desc, uint32_t n_cand,
+                               uint32_t bwidth, uint32_t bheight, svthip_md_fast_result* result, hipStream_t s);
+hipError_t launch_md_fast_pick(const svthip_md_fast_result* result, const svthip_md_fast_desc* desc, uint32_t n_cand, const svthip_md_fast_group* group,
+                               uint32_t n_groups, svthip_md_fast_pick* pick, uint32_t* refused, hipStream_t s);
+// md_ifs.hip: mode decision's interpolation-filter search -- SSE and modelled rate / distortion of predicted tiles, the search over the
+// filter pairs through launch_inter_pred (kernels: md_ifs_kernels.h)
+struct MdIfsLayout {
+    size_t t_pu, t_desc, t_result, t_refused, unread_counter, y, cb, cr, total;   // byte offsets into the search's scratch, its size
+    uint32_t tiles_per_row, y_stride, c_stride;                                  // the grid of trial tiles
+};
+bool md_ifs_size_ok(uint32_t bwidth, uint32_t bheight);
+uint32_t md_ifs_trials(int32_t search_mode, int32_t enable_dual_filter);   // trial tiles per candidate: 9 full, 3 fast or without the dual filter
+bool md_ifs_layout(uint64_t n_tiles, uint32_t bw, uint32_t bh, MdIfsLayout* L);   // false: more tiles than 16-bit positions address
+hipError_t launch_md_model_rd(const svthip_inter_planes& src, const svthip_inter_planes& pred, const svthip_md_model_rd_desc* desc, uint32_t n_tiles,
+                              uint32_t bwidth, uint32_t bheight, int16_t quantizer, svthip_md_model_rd_result* result, uint32_t* refused, hipStream_t s);
+hipError_t launch_md_ifs_search(const svthip_inter_planes& ref0, const svthip_inter_planes& ref1, const svthip_inter_planes& src,
+                                svthip_inter_pu_desc* pu, const svthip_md_ifs_desc* ifs, uint32_t n_cand, uint32_t bwidth, uint32_t bheight,
+                                int32_t search_mode, int32_t enable_dual_filter, int16_t quantizer, int32_t write_back, svthip_md_ifs_result* result,
+                                bool use_mfma, void* scratch, const MdIfsLayout& L, void* jobs_scratch, uint32_t* refused, hipStream_t s);
+// md_full.hip: mode decision's full loop -- per slot the fused chain and the rate on Y, Cb and Cr with the tx-type search, the full cost,
+// the decision per block, the winner's reconstruction (kernels: md_full_kernels.h)
+struct MdFullLayout {   // byte offsets into the caller's workspace, its size, and the TxTypes a search runs
+    size_t slots, tu[3], rate[3], eob[3], dist[3], bits[3], qcoeff[3], energy_y;
+    size_t s_tu, s_rate, s_eob, s_energy, s_dist, s_bits, s_qcoeff, s_recon, s_tus, s_bases, s_out, total;
+    uint32_t n_slots, n_types;   // n_types 0: no search
+    uint8_t types[16];
+};
+struct MdFullCall {   // the arguments of svthip_md_full_loop_batch_dev
+    svthip_inter_planes src, pred, slot_recon, recon;
+    const svthip_md_fast_desc* fast;
+    const svthip_md_full_desc* full;
+    const svthip_md_fast_group* group;
+    const svthip_md_fast_pick* pick;
+    uint32_t n_cand, n_groups, bwidth, bheight, max_full, tiles_per_row, type_mask_inter, type_mask_intra, stages;
+    int32_t reduced_tx_set;
+    const int16_t *qparams, *iscan;
+    const uint32_t* iscan_offsets;   // host, [19 * 16]
+    const svthip_coeff_rate_tables* tables;
+    void* work;
+    svthip_md_full_result* result;
+    svthip_md_full_decision* decision;
+    uint32_t* refused;
+    uint32_t max_workgroups;         // SVTHIP_OPT_TQ_MAX_WORKGROUPS
+};
+bool md_full_size_ok(uint32_t bwidth, uint32_t bheight);
+bool md_full_layout(uint32_t n_groups, uint32_t max_full, uint32_t bw, uint32_t bh, uint32_t mask_inter, uint32_t mask_intra, MdFullLayout* L);
+hipError_t launch_md_full_loop(const MdFullCall& C, const MdFullLayout& L, hipStream_t s);
+
+}  // namespace svthip

@@ -15,8 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "me_launch.h"
 
 namespace svthip {
 
@@ -453,6 +452,8 @@ __global__ void __launch_bounds__(256) bipred_stored_pack_kernel(const uint8_t* 
     }
 }
 
+namespace {
+
 size_t subpel_window_bytes(uint32_t max_sw, uint32_t max_sh)
 {
     const size_t pitch = (max_sw + 63 + 2 * kMargin + 3) & ~(size_t)3;
@@ -468,4 +469,51 @@ size_t bipred_nsq_lds_bytes(uint32_t max_sw, uint32_t max_sh)
 {
     return 4096 + kNsqPredOff[kNsqRoles] + kNsqTileOff[kNsqRoles] + 2 * subpel_window_bytes(max_sw, max_sh) + 16;
 }
+
+}  // namespace
+
+bool bipred_windows_fit(uint32_t max_sw, uint32_t max_sh, int n_pu)
+{
+    return bipred_lds_bytes(max_sw, max_sh) <= 160 * 1024 && (n_pu != 209 || bipred_nsq_lds_bytes(max_sw, max_sh) <= 160 * 1024);
+}
+
+hipError_t launch_bipred_pack(const uint8_t* src, uint32_t src_stride, const uint8_t* ref0, uint32_t ref0_stride, const svthip_fullpel_desc* desc0,
+                              const uint8_t* ref1, uint32_t ref1_stride, const svthip_fullpel_desc* desc1, uint32_t n_sb, uint32_t max_sw,
+                              uint32_t max_sh, const uint32_t* sad0, const uint32_t* mv0, const uint32_t* sad1, const uint32_t* mv1, int n_lists,
+                              bool bipred_8x8, int n_pu, uint32_t* bisad_sq, svthip_me_cu_result* out, hipStream_t s)
+{
+    // one list: no window is staged
+    const size_t lds = n_lists == 2 ? bipred_lds_bytes(max_sw, max_sh) : 0, lds_nsq = n_lists == 2 ? bipred_nsq_lds_bytes(max_sw, max_sh) : 0;
+    const int win_bytes = n_lists == 2 ? (int)subpel_window_bytes(max_sw, max_sh) : 0;
+    const int32_t *d0 = reinterpret_cast<const int32_t*>(desc0), *d1 = reinterpret_cast<const int32_t*>(desc1);
+    if (n_pu == 85) {
+        hipLaunchKernelGGL(bipred_pack_kernel, dim3(n_sb), dim3(256), lds, s, src, src_stride, ref0, ref0_stride, d0, ref1, ref1_stride, d1, sad0, mv0,
+                           sad1, mv1, n_lists, (int)bipred_8x8, win_bytes, 85, (uint32_t*)nullptr, out);
+        return hipGetLastError();
+    }
+    if (n_lists == 2) {
+        hipLaunchKernelGGL(bipred_pack_kernel, dim3(n_sb), dim3(256), lds, s, src, src_stride, ref0, ref0_stride, d0, ref1, ref1_stride, d1, sad0, mv0,
+                           sad1, mv1, 2, 1, win_bytes, 209, bisad_sq, (svthip_me_cu_result*)nullptr);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(bipred_nsq_pack_kernel, dim3(n_sb), dim3(320), lds_nsq, s, src, src_stride, ref0, ref0_stride, d0, ref1, ref1_stride, d1, sad0,
+                       mv0, sad1, mv1, n_lists, win_bytes, (const uint32_t*)(n_lists == 2 ? bisad_sq : nullptr), out);
+    return hipGetLastError();
+}
+
+hipError_t launch_bipred_stored_pack(const uint8_t* src, uint32_t src_stride, const svthip_fullpel_desc* desc0, const uint8_t* pred0,
+                                     const uint8_t* pred1, const uint32_t* sad0, const uint32_t* mv0, const uint32_t* sad1, const uint32_t* mv1,
+                                     uint32_t n_sb, int n_pu, bool bipred_8x8, svthip_me_cu_result* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(bipred_stored_pack_kernel, dim3(n_sb), dim3(256), 0, s, src, src_stride, reinterpret_cast<const int32_t*>(desc0), pred0, pred1,
+                       sad0, mv0, sad1, mv1, n_pu, (int)bipred_8x8, out);
+    return hipGetLastError();
+}
+
+hipError_t bipred_raise_dynamic_lds()
+{
+    return raise_dynamic_lds({reinterpret_cast<const void*>(bipred_pack_kernel), reinterpret_cast<const void*>(bipred_nsq_pack_kernel)});
+}
+
 }  // namespace svthip

@@ -41,7 +41,7 @@
 
 #include "me_fullpel_img2.h"
 #include "me_fullpel_impl.h"
-#include "me_kernels.h"
+#include "me_launch.h"
 
 namespace svthip {
 
@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256, kFullpelMinWaves) fullpel85_kernel(
     uint32_t* __restrict__ out_mv)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t sb = xcd_item(blockIdx.x, n_sb);  // raster neighbours share an XCD's L2 (me_kernels.h)
+    const uint32_t sb = xcd_item(blockIdx.x, n_sb);  // raster neighbours share an XCD's L2 (svthip_internal.h)
     if (sb >= n_sb) return;
     // wave-uniform choice of the search-loop form (me_fullpel_impl.h): windows clipped at the picture's left / right edge take the general one
     if ((desc[6 * sb + 4] & 15) == 0) fullpel85_sb<true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
@@ -76,5 +76,24 @@ __global__ void __launch_bounds__(256, kFullpelMinWaves) fullpel85_img2_kernel(
     else if ((sw & 15) == 0) fullpel85_sb<true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
     else fullpel85_sb<false>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
 }
+
+// same arguments, grid and block for all three kernels; the kernels read a svthip_fullpel_desc as 6 int32
+hipError_t launch_fullpel(uint32_t n_pu, const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride,
+                          const svthip_fullpel_desc* desc, uint32_t n_sb, uint32_t max_sw, uint32_t max_sh, uint32_t* out_sad,
+                          uint32_t* out_mv, hipStream_t s)
+{
+    if (n_pu == 209) return launch_fullpel209(src, src_stride, ref, ref_stride, desc, n_sb, max_sh, out_sad, out_mv, s);
+    const int32_t* d = reinterpret_cast<const int32_t*>(desc);
+    if (fullpel_img2_fits(max_sw, max_sh))
+        hipLaunchKernelGGL(fullpel85_img2_kernel, dim3(xcd_grid(n_sb)), dim3(256), fullpel_img2_lds_bytes(), s, src, src_stride, ref, ref_stride, d,
+                           n_sb, out_sad, out_mv);
+    else
+        hipLaunchKernelGGL(fullpel85_kernel, dim3(xcd_grid(n_sb)), dim3(256), fullpel_lds_bytes(max_sh), s, src, src_stride, ref, ref_stride, d, n_sb,
+                           out_sad, out_mv);
+    return hipGetLastError();
+}
+
+// the two-image kernel stays below 64 KB (me_fullpel_img2.h)
+hipError_t fullpel85_raise_dynamic_lds() { return raise_dynamic_lds({reinterpret_cast<const void*>(fullpel85_kernel)}); }
 
 }  // namespace svthip

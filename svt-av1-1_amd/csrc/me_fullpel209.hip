@@ -3,7 +3,7 @@
 #include <stdint.h>
 
 #include "me_fullpel209_impl.h"
-#include "me_kernels.h"
+#include "me_launch.h"
 
 namespace svthip {
 
@@ -15,13 +15,22 @@ __global__ void __launch_bounds__(256, kFp209MinWaves) fullpel209_kernel(const u
                                                             uint32_t* __restrict__ out_mv)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t sb = xcd_item(blockIdx.x, n_sb);  // raster neighbours share an XCD's L2 (me_kernels.h)
+    const uint32_t sb = xcd_item(blockIdx.x, n_sb);  // raster neighbours share an XCD's L2 (svthip_internal.h)
     if (sb >= n_sb) return;
     // wave-uniform choice of the search-loop form (me_fullpel209_impl.h): clipped windows at the picture's left / right edge take the general one
     if ((desc[6 * sb + 4] & 15) == 0) fullpel209_sb<true>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
     else fullpel209_sb<false>(src_plane, src_stride, ref_plane, ref_stride, desc + 6 * sb, sb, out_sad, out_mv, smem);
 }
 
-size_t fullpel209_lds_bytes(uint32_t max_sh) { return (size_t)kFp209Fixed + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
+hipError_t launch_fullpel209(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, const svthip_fullpel_desc* desc,
+                             uint32_t n_sb, uint32_t max_sh, uint32_t* out_sad, uint32_t* out_mv, hipStream_t s)
+{
+    const size_t lds = (size_t)kFp209Fixed + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH;
+    hipLaunchKernelGGL(fullpel209_kernel, dim3(xcd_grid(n_sb)), dim3(256), lds, s, src, src_stride, ref, ref_stride,
+                       reinterpret_cast<const int32_t*>(desc), n_sb, out_sad, out_mv);
+    return hipGetLastError();
+}
+
+hipError_t fullpel209_raise_dynamic_lds() { return raise_dynamic_lds({reinterpret_cast<const void*>(fullpel209_kernel)}); }
 
 }  // namespace svthip

@@ -18,7 +18,6 @@
 #include <stdint.h>
 
 #include "me_fullpel_common.h"
-#include "me_kernels.h"
 #include "me_wave_reduce.h"
 
 namespace svthip {

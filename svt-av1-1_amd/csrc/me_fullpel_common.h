@@ -7,10 +7,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "me_kernels.h"
+#include "me_launch.h"
 #include "me_sad_common.h"
 
+// LDS row pitch of the staged reference window.  192 B: >= 16*8 + 64 (widest lane footprint at
+// search_area_width 127) and == 48 dwords, which puts rows y, y+3, y+5, y+6 (one ds_read_b128 lane
+// group) on four distinct bank quarters.
+#define SVTHIP_FULLPEL_LDS_PITCH 192
+// fixed LDS in front of the window: 16 KB exchange buffer + 64 B
+#define SVTHIP_FULLPEL_LDS_FIXED (16384 + 64)
+
 namespace svthip {
+
+inline size_t fullpel_lds_bytes(uint32_t max_sh) { return SVTHIP_FULLPEL_LDS_FIXED + (size_t)(max_sh + 63) * SVTHIP_FULLPEL_LDS_PITCH; }
+
+// me_fullpel209.hip: the 209-PU arm of launch_fullpel (me_fullpel.hip), same arguments
+SVTHIP_LOCAL hipError_t launch_fullpel209(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride,
+                                          const svthip_fullpel_desc* desc, uint32_t n_sb, uint32_t max_sh, uint32_t* out_sad, uint32_t* out_mv,
+                                          hipStream_t s);
 
 constexpr int kPitch = SVTHIP_FULLPEL_LDS_PITCH;  // bytes per window row in LDS (one-image plans)
 

@@ -1,7 +1,7 @@
-// svt-av1-1_amd/csrc/me_fullpel_img2.h -- the two-image entry of the 85-PU full-pel search (me_fullpel.hip): its LDS plan, declaration and
-// the host's choice between it and fullpel85_kernel.  Shared by the kernel and the C-ABI glue.
+// svt-av1-1_amd/csrc/me_fullpel_img2.h -- the two-image entry of the 85-PU full-pel search (me_fullpel.hip): its LDS plan and
+// launch_fullpel's choice between it and fullpel85_kernel.
 #pragma once
-#include "me_kernels.h"
+#include "me_fullpel_common.h"
 
 // Launches whose search areas are at most 64x64 keep TWO images of the reference window in LDS, the second one read 4 bytes later, so
 // that the odd dword pairs of a window row (W1,W2), (W3,W4), (W5,W6) are naturally aligned wide reads like the even ones and no
@@ -18,11 +18,8 @@
 
 namespace svthip {
 
-// same arguments and results as fullpel85_kernel; every superblock of the launch must have a search area of at most 64x64
-__global__ void fullpel85_img2_kernel(const uint8_t* __restrict__ src_plane, uint32_t src_stride, const uint8_t* __restrict__ ref_plane,
-                                      uint32_t ref_stride, const int32_t* __restrict__ desc, uint32_t n_sb, uint32_t* __restrict__ out_sad,
-                                      uint32_t* __restrict__ out_mv);
-
+// fullpel85_img2_kernel: same arguments and results as fullpel85_kernel; every superblock of the launch must have a search area of at
+// most 64x64
 inline bool fullpel_img2_fits(uint32_t max_sw, uint32_t max_sh)
 {
     return max_sw <= SVTHIP_FULLPEL_IMG2_MAX_AREA && max_sh <= SVTHIP_FULLPEL_IMG2_MAX_AREA;

@@ -6,7 +6,6 @@
 
 #include "me_fullpel_common.h"
 #include "me_fullpel_img2.h"
-#include "me_kernels.h"
 #include "me_wave_reduce.h"
 
 namespace svthip {

@@ -1,0 +1,59 @@
+// svt-av1-1_amd/csrc/me_launch.h -- launch boundary of the motion-estimation family (me_*.hip): what the C-ABI glue calls.  Grid, block,
+// LDS bytes, job chunking and kernel choice live next to the kernels; the glue validates, sizes scratch and calls.
+#pragma once
+#include "svthip_internal.h"
+
+namespace svthip {
+
+// me_hme.hip: the search centres of one reference list for n_jobs (current, reference) picture pairs of n_sb superblocks each, in launches
+// of up to SVTHIP_HME_MAX_JOBS pairs.  cur / ref: host arrays [n_jobs]; every per-SB array holds job j at [j * n_sb ...].  l0_best_mv64,
+// out_center and hme_state may be null.
+hipError_t launch_hme_centers(const uint8_t* pool, const svthip_pa_picture* cur, const svthip_pa_picture* ref, uint32_t n_jobs,
+                              const svthip_me_params& P, uint32_t list_index, const svthip_sb_origin* sbs, uint32_t n_sb,
+                              const uint32_t* l0_best_mv64, uint32_t l0_mv_stride, svthip_fullpel_desc* out_desc, int16_t* out_center,
+                              int16_t* hme_state, hipStream_t s);
+
+// me_fullpel.hip, me_fullpel209.hip: the full-pel search of n_sb superblocks, 85 or 209 PUs each.  209: fullpel209_kernel; 85: the
+// two-image kernel (me_fullpel_img2.h) for areas up to 64x64, chosen once per launch, else fullpel85_kernel.
+hipError_t launch_fullpel(uint32_t n_pu, const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride,
+                          const svthip_fullpel_desc* desc, uint32_t n_sb, uint32_t max_sw, uint32_t max_sh, uint32_t* out_sad,
+                          uint32_t* out_mv, hipStream_t s);
+SVTHIP_LOCAL hipError_t fullpel85_raise_dynamic_lds();
+SVTHIP_LOCAL hipError_t fullpel209_raise_dynamic_lds();
+
+// me_subpel_planes.hip: the half-pel planes of the whole (bounded) search region interpolated once per (SB, list) in LDS, all PUs in one
+// launch; the planes of the largest legal area (127 x 127) take 152.6 KB, so every legal call fits.  pred_out may be null.
+bool subpel_planes_fit(uint32_t max_sw, uint32_t max_sh);
+hipError_t launch_subpel_planes(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, const svthip_fullpel_desc* desc,
+                                uint32_t n_sb, uint32_t max_sw, uint32_t max_sh, bool disable_8x8, int n_pu, uint32_t* io_sad, uint32_t* io_mv,
+                                uint32_t* pred_out, int method, hipStream_t s);
+SVTHIP_LOCAL hipError_t subpel_planes_raise_dynamic_lds();
+
+// me_bipred.hip: bi-prediction and packing.  n_lists 1: only list 0 is read (ref1, desc1, sad1, mv1 may be null) and no window is
+// staged.  209-PU mode: the squares' bi-pred SADs go through bisad_sq ([n_sb][85], needed with two lists) to the kernel that packs all
+// 209 PUs.  The stored form averages the predictions the sub-pel kernel left in pred0 / pred1 instead of interpolating again.
+bool bipred_windows_fit(uint32_t max_sw, uint32_t max_sh, int n_pu);
+hipError_t launch_bipred_pack(const uint8_t* src, uint32_t src_stride, const uint8_t* ref0, uint32_t ref0_stride, const svthip_fullpel_desc* desc0,
+                              const uint8_t* ref1, uint32_t ref1_stride, const svthip_fullpel_desc* desc1, uint32_t n_sb, uint32_t max_sw,
+                              uint32_t max_sh, const uint32_t* sad0, const uint32_t* mv0, const uint32_t* sad1, const uint32_t* mv1, int n_lists,
+                              bool bipred_8x8, int n_pu, uint32_t* bisad_sq, svthip_me_cu_result* out, hipStream_t s);
+hipError_t launch_bipred_stored_pack(const uint8_t* src, uint32_t src_stride, const svthip_fullpel_desc* desc0, const uint8_t* pred0,
+                                     const uint8_t* pred1, const uint32_t* sad0, const uint32_t* mv0, const uint32_t* sad1, const uint32_t* mv1,
+                                     uint32_t n_sb, int n_pu, bool bipred_8x8, svthip_me_cu_result* out, hipStream_t s);
+SVTHIP_LOCAL hipError_t bipred_raise_dynamic_lds();
+
+// me_sadloop.hip: the SAD loop over blocks of one size.  Widths 4 / 8 / 16 / 32 / 64 take the packed-SAD kernel (8 / 12 / 16 positions
+// per lane, several blocks per workgroup) unless force_generic (SVTHIP_OPT_SADLOOP_GENERIC) or its slightly wider window rows do not fit;
+// every other case takes the generic kernel.  sad_loop_fits: false when neither fits, with the generic kernel's slice for the refusal's
+// text.  k = ref_stride / ref_stride_raw.
+bool sad_loop_fits(int w, int h, int sw, int sh, int k, bool force_generic, size_t* generic_slice_bytes);
+hipError_t launch_sad_loop(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, uint32_t ref_stride_raw,
+                           const svthip_sad_loop_desc* desc, uint32_t n_blocks, int w, int h, int sw, int sh, bool force_generic, uint32_t* best_sad,
+                           int16_t* best_xy, hipStream_t s);
+
+// me_ois.hip: the open-loop intra search of n_jobs pictures (host array cur) of n_sb superblocks each, in launches of up to
+// SVTHIP_HME_MAX_JOBS pictures.  me may be null on the branches that do not read the ME distortions.
+hipError_t launch_ois(const uint8_t* pool, const svthip_pa_picture* cur, uint32_t n_jobs, const svthip_ois_params& P, const svthip_sb_origin* sbs,
+                      uint32_t n_sb, const svthip_me_cu_result* me, uint32_t me_stride, uint32_t* out_cand, uint8_t* out_total, hipStream_t s);
+
+}  // namespace svthip

@@ -24,8 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "me_launch.h"
+#include "pa_job_table.h"
 
 namespace svthip {
 
@@ -413,6 +413,20 @@ __global__ void __launch_bounds__(256) ois_kernel(const uint8_t* __restrict__ po
     uint32_t* oc = out_cand + (size_t)item * 85 * kCand;
     for (int i = tid; i < 85 * kCand; i += 256) oc[i] = L.cand[i];
     if (tid < 85) out_total[(size_t)item * 85 + tid] = L.total[tid];
+}
+
+hipError_t launch_ois(const uint8_t* pool, const svthip_pa_picture* cur, uint32_t n_jobs, const svthip_ois_params& P, const svthip_sb_origin* sbs,
+                      uint32_t n_sb, const svthip_me_cu_result* me, uint32_t me_stride, uint32_t* out_cand, uint8_t* out_total, hipStream_t s)
+{
+    for (uint32_t j0 = 0; j0 < n_jobs; j0 += SVTHIP_HME_MAX_JOBS) {
+        const uint32_t nj = jobs_in_chunk(n_jobs, j0);
+        const size_t first = (size_t)j0 * n_sb;
+        hipLaunchKernelGGL(ois_kernel, dim3(xcd_grid(n_sb * nj)), dim3(256), 0, s, pool, pa_job_table(cur + j0, nj), P, sbs, n_sb, nj,
+                           me ? me + first * me_stride : nullptr, me_stride, out_cand + first * 85 * kCand, out_total + first * 85);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace svthip

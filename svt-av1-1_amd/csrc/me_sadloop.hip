@@ -14,8 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "me_launch.h"
 #include "me_sad_common.h"
 
 namespace svthip {
@@ -301,13 +300,21 @@ __global__ void __launch_bounds__(256) sad_loop_qsad_kernel(const uint8_t* __res
     }
 }
 
-size_t sad_loop_qsad_lds_bytes(int w, int h, int sw, int sh, int k) { return sad_loop_plan(w, h, sw, sh, k).lds_bytes; }
+namespace {
+
+// the packed-SAD kernel takes this shape, with plan *p: a width it has a form for, not overridden, and a plan within the default dynamic
+// LDS limit (its window rows are slightly wider than the generic kernel's)
+bool sad_loop_takes_qsad(int w, int h, int sw, int sh, int k, bool force_generic, SadLoopPlan* p)
+{
+    if (!(w == 4 || w == 8 || w == 16 || w == 32 || w == 64) || force_generic) return false;
+    *p = sad_loop_plan(w, h, sw, sh, k);
+    return p->lds_bytes <= 64 * 1024;
+}
 
 hipError_t launch_sad_loop_qsad(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, uint32_t ref_stride_raw,
-                                const svthip_sad_loop_desc* desc, uint32_t n_blocks, int w, int h, int sw, int sh, uint32_t* best_sad,
-                                int16_t* best_xy, hipStream_t s)
+                                const svthip_sad_loop_desc* desc, uint32_t n_blocks, int w, int h, int sw, int sh, const SadLoopPlan& p,
+                                uint32_t* best_sad, int16_t* best_xy, hipStream_t s)
 {
-    const SadLoopPlan p = sad_loop_plan(w, h, sw, sh, (int)(ref_stride / ref_stride_raw));
     const dim3 grid((n_blocks + p.gb - 1) / p.gb), block(256);
 #define SVTHIP_SADLOOP_CASE(W4, NQ)                                                                                                         \
     case 16 * W4 + NQ:                                                                                                                      \
@@ -328,10 +335,35 @@ hipError_t launch_sad_loop_qsad(const uint8_t* src, uint32_t src_stride, const u
     return hipGetLastError();
 }
 
+// LDS of one block of the generic kernel (a workgroup holds four)
 size_t sad_loop_slice_bytes(int w, int h, int sw, int sh, int k)
 {
     const int wrows = (sh - 1) + (h - 1) * k + 1, pitch = (w + sw - 1 + 3 + 4) & ~3;
     return ((size_t)h * w + (size_t)wrows * pitch + 15) & ~(size_t)15;
+}
+
+}  // namespace
+
+bool sad_loop_fits(int w, int h, int sw, int sh, int k, bool force_generic, size_t* generic_slice_bytes)
+{
+    SadLoopPlan p;
+    if (sad_loop_takes_qsad(w, h, sw, sh, k, force_generic, &p)) return true;
+    *generic_slice_bytes = sad_loop_slice_bytes(w, h, sw, sh, k);
+    return *generic_slice_bytes * 4 <= 64 * 1024;
+}
+
+hipError_t launch_sad_loop(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, uint32_t ref_stride_raw,
+                           const svthip_sad_loop_desc* desc, uint32_t n_blocks, int w, int h, int sw, int sh, bool force_generic, uint32_t* best_sad,
+                           int16_t* best_xy, hipStream_t s)
+{
+    const int k = (int)(ref_stride / ref_stride_raw);
+    SadLoopPlan p;
+    if (sad_loop_takes_qsad(w, h, sw, sh, k, force_generic, &p))
+        return launch_sad_loop_qsad(src, src_stride, ref, ref_stride, ref_stride_raw, desc, n_blocks, w, h, sw, sh, p, best_sad, best_xy, s);
+    const size_t slice = sad_loop_slice_bytes(w, h, sw, sh, k);
+    hipLaunchKernelGGL(sad_loop_kernel, dim3((n_blocks + 3) / 4), dim3(256), slice * 4, s, src, src_stride, ref, ref_stride, ref_stride_raw, desc, n_blocks,
+                       w, h, sw, sh, (int)slice, best_sad, best_xy);
+    return hipGetLastError();
 }
 
 }  // namespace svthip

@@ -21,8 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "me_launch.h"
 
 namespace svthip {
 
@@ -467,7 +466,7 @@ __global__ void __launch_bounds__(512, 4) subpel_planes_kernel(const uint8_t* __
     if (sb >= n_sb) continue;
     __syncthreads();  // the previous superblock's readers are done with the planes and the hand-shake words
 #else
-    const uint32_t sb = xcd_item(blockIdx.x, n_sb);  // raster neighbours share an XCD's L2 (me_kernels.h)
+    const uint32_t sb = xcd_item(blockIdx.x, n_sb);  // raster neighbours share an XCD's L2 (svthip_internal.h)
     if (sb >= n_sb) return;
 #endif
     const int32_t* d = desc + 6 * sb;
@@ -676,6 +675,8 @@ extern "C" int svthip_debug_subpel_stamps(void* host, size_t bytes)
 }
 #endif
 
+namespace {
+
 uint32_t subpel_planes_grid(uint32_t n_sb)
 {
 #ifdef SVTHIP_SUBPEL_PERSISTENT
@@ -690,5 +691,21 @@ size_t subpel_planes_lds_bytes(uint32_t max_sw, uint32_t max_sh)
     const size_t pitch = subpel_plane_pitch((int)max_sw + 69), rows = max_sh + 69;
     return 128 + 4 * ((pitch * rows + 15) & ~(size_t)15) + 32 + 4 * (512 + 209 + 3);  // + slack (the 3-dword reads run up to 11 bytes past a sample) + the PUs' starting values
 }
+
+}  // namespace
+
+bool subpel_planes_fit(uint32_t max_sw, uint32_t max_sh) { return subpel_planes_lds_bytes(max_sw, max_sh) <= 160 * 1024 - 512; }
+
+hipError_t launch_subpel_planes(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, const svthip_fullpel_desc* desc,
+                                uint32_t n_sb, uint32_t max_sw, uint32_t max_sh, bool disable_8x8, int n_pu, uint32_t* io_sad, uint32_t* io_mv,
+                                uint32_t* pred_out, int method, hipStream_t s)
+{
+    hipLaunchKernelGGL(subpel_planes_kernel, dim3(subpel_planes_grid(n_sb)), dim3(n_pu == 209 ? 448 : 512), subpel_planes_lds_bytes(max_sw, max_sh), s,
+                       src, src_stride, ref, ref_stride, reinterpret_cast<const int32_t*>(desc), n_sb, (int)disable_8x8, n_pu, io_sad, io_mv, pred_out,
+                       method);
+    return hipGetLastError();
+}
+
+hipError_t subpel_planes_raise_dynamic_lds() { return raise_dynamic_lds({reinterpret_cast<const void*>(subpel_planes_kernel)}); }
 
 }  // namespace svthip

@@ -10,7 +10,7 @@
 #include <string.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "pa_launch.h"
 #include "pa_noise_kernels.h"
 
 namespace svthip {

@@ -16,8 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "pa_job_table.h"
+#include "pa_launch.h"
 
 namespace svthip {
 
@@ -80,6 +80,25 @@ __global__ void __launch_bounds__(256) pa_derive_planes_kernel(uint8_t* __restri
     }
 }
 
+// one grid for all pictures of the call: sized by the largest full-resolution plane, capped at 1024 blocks (the kernel strides)
+hipError_t launch_pa_derive_planes(uint8_t* pool, const svthip_pa_picture* pics, uint32_t n, bool do_quarter, bool do_sixteenth, hipStream_t s)
+{
+    uint32_t max_dw = 0;
+    for (uint32_t j = 0; j < n; j++) {
+        const uint32_t dw = ((uint32_t)pics[j].width + 136u + 3u) / 4u * ((uint32_t)pics[j].height + 136u);
+        if (dw > max_dw) max_dw = dw;
+    }
+    const uint32_t bx = (max_dw + 255u) / 256u;
+    for (uint32_t j0 = 0; j0 < n; j0 += SVTHIP_HME_MAX_JOBS) {
+        const uint32_t nj = jobs_in_chunk(n, j0);
+        hipLaunchKernelGGL(pa_derive_planes_kernel, dim3(bx < 1024u ? bx : 1024u, 3, nj), dim3(256), 0, s, pool, pa_job_table(pics + j0, nj),
+                           (int)do_quarter, (int)do_sixteenth);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // generate_padding (sample_bytes = 1) / generate_padding16_bit (sample_bytes = 2) of one plane in place: the interior
 // (width x height samples at (pad_w, pad_h)) is read, everything else of the (width + 2 pad_w) x (height + 2 pad_h) area is written.
 template <typename T>
@@ -136,6 +155,12 @@ __global__ void __launch_bounds__(256) me_results_ref_layout_kernel(const svthip
 #pragma unroll
     for (int k = 0; k < 7; k++) o.pad_[k] = 0;
     out[i] = o;
+}
+
+hipError_t launch_me_results_ref_layout(const svthip_me_cu_result* in, uint32_t n, svthip_me_cu_result_ref* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(me_results_ref_layout_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in, n, out);
+    return hipGetLastError();
 }
 
 }  // namespace svthip

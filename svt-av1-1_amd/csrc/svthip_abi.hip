@@ -15,8 +15,15 @@
 #include <new>
 
 #include "../../include/svtav1_hip.h"
-#include "me_fullpel_img2.h"
-#include "me_kernels.h"
+#include "cf_launch.h"
+#include "fg_launch.h"
+#include "ip_launch.h"
+#include "lf_launch.h"
+#include "lr_launch.h"
+#include "md_launch.h"
+#include "me_launch.h"
+#include "pa_launch.h"
+#include "tq_launch.h"
 
 // Grow-only device scratch of a context, one slot per owner.  A slot that holds several arrays has ONE layout function below that
 // gives both its size (svthip_reserve, ensure_scratch) and the offsets inside it.
@@ -31,7 +38,7 @@ enum Slot {
     SLOT_ME_RESULTS_REF,  // ME results in the reference's layout (host ME form), cand | total (host OIS form)
     SLOT_TU_PLANES, SLOT_TU_TABLES, SLOT_TU_COEFFS, SLOT_TU_OUTPUTS,  // svthip_encode_tu_batch, three arrays each: slot3
     SLOT_INTER_JOBS,      // job lists of the whole-PU inter prediction / warped prediction entries
-    SLOT_INTER_REFUSED,   // their refused-PU counter
+    SLOT_REFUSED,         // the refusal counter of every entry that can refuse on the device: refused_counter
     SLOT_PA_REGION_SUMS,  // region sums of svthip_pa_histograms_dev on their way to the picture averages: pa_region_sum_bytes
     SLOT_FILM_GRAIN_TABLES,  // the table block of the one-call film-grain form: SVTHIP_FILM_GRAIN_TABLES_BYTES
     SLOT_MD_IFS,          // trial descriptors, results and tiles of svthip_md_interp_filter_search_batch_dev: svthip::md_ifs_layout
@@ -43,8 +50,8 @@ struct svthip_ctx {
     hipStream_t stream;
     void* scratch[SLOT_COUNT];
     size_t scratch_bytes[SLOT_COUNT];
-    // stream of the last whole-PU inter prediction call (svthip_inter_pred_refused synchronises with it)
-    hipStream_t inter_stream;
+    // stream of the last call that took the refusal counter (svthip_inter_pred_refused synchronises with it)
+    hipStream_t refused_stream;
     // the stream the context-owned scratch was last used on, and an event to order a different stream behind it
     hipStream_t scratch_stream;
     hipEvent_t scratch_event;
@@ -78,28 +85,19 @@ __attribute__((format(printf, 2, 3))) int32_t fail(int32_t code, const char* fmt
 #define TRY(expr) do { int32_t rc_ = (expr); if (rc_) return rc_; } while (0)
 
 // One-time, process-wide, per device: every kernel that takes dynamic LDS gets its limit raised to what the largest legal launch needs
-// (160 KB minus the kernel's static LDS).  hipFuncSetAttribute is per-FUNCTION state, so it must not be cached per context: a second
-// context with a smaller search area would lower the limit under a first one's launches (round-1 defect).
+// (160 KB minus the kernel's static LDS; each file does it for its own kernels, svthip_internal.h).  hipFuncSetAttribute is
+// per-FUNCTION state, so it must not be cached per context: a second context with a smaller search area would lower the limit under a
+// first one's launches (round-1 defect).
 std::once_flag g_attr_once[16];
 hipError_t g_attr_status[16];
 
 void set_kernel_attrs(int device)
 {
-    constexpr int kTq = 5 + svthip::kConvolveDynamicLdsKernels, kInv = kTq + svthip::kFwdTxfmDynamicLdsKernels,
-                  kEnc = kInv + svthip::kInvTxfmDynamicLdsKernels;
-    const void* kernels[kEnc + svthip::kEncodeTuDynamicLdsKernels] = {
-        reinterpret_cast<const void*>(svthip::fullpel85_kernel), reinterpret_cast<const void*>(svthip::fullpel209_kernel),
-        reinterpret_cast<const void*>(svthip::bipred_pack_kernel), reinterpret_cast<const void*>(svthip::bipred_nsq_pack_kernel),
-        reinterpret_cast<const void*>(svthip::subpel_planes_kernel)};
-    svthip::convolve_dynamic_lds_kernels(kernels + 5);
-    svthip::fwd_txfm_dynamic_lds_kernels(kernels + kTq);
-    svthip::inv_txfm_dynamic_lds_kernels(kernels + kInv);
-    svthip::encode_tu_dynamic_lds_kernels(kernels + kEnc);
     hipError_t st = hipSuccess;
-    for (const void* k : kernels) {
-        hipFuncAttributes fa;
-        hipError_t e = hipFuncGetAttributes(&fa, k);
-        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes);
+    for (hipError_t (*raise)() : {svthip::fullpel85_raise_dynamic_lds, svthip::fullpel209_raise_dynamic_lds, svthip::bipred_raise_dynamic_lds,
+                                  svthip::subpel_planes_raise_dynamic_lds, svthip::convolve_raise_dynamic_lds, svthip::fwd_txfm_raise_dynamic_lds,
+                                  svthip::inv_txfm_raise_dynamic_lds, svthip::encode_tu_raise_dynamic_lds}) {
+        const hipError_t e = raise();
         if (e != hipSuccess) st = e;
     }
     g_attr_status[device] = st;
@@ -312,33 +310,27 @@ int32_t check_tq_pools(const void* coeff, const void* qcoeff, const void* dqcoef
 
 // ---------------------------------------------------------------- motion estimation
 
-// The full-pel search of n_sb superblocks, 85 or 209 PUs each.  209: fullpel209_kernel; 85: the two-image kernel (me_fullpel_img2.h)
-// for areas up to 64x64, chosen once per launch, else fullpel85_kernel.  Same arguments, grid and block for all three.
-int32_t launch_fullpel(svthip_ctx* ctx, uint32_t n_pu, const uint8_t* d_src, uint32_t src_stride, const uint8_t* d_ref, uint32_t ref_stride,
-                       const svthip_fullpel_desc* d_desc, uint32_t n_sb, uint32_t max_sw, uint32_t max_sh, uint32_t* d_sad, uint32_t* d_mv,
-                       void* stream)
+// The full-pel search of n_sb superblocks, 85 or 209 PUs each
+int32_t fullpel_entry(svthip_ctx* ctx, uint32_t n_pu, const uint8_t* d_src, uint32_t src_stride, const uint8_t* d_ref, uint32_t ref_stride,
+                      const svthip_fullpel_desc* d_desc, uint32_t n_sb, uint32_t max_sw, uint32_t max_sh, uint32_t* d_sad, uint32_t* d_mv,
+                      void* stream)
 {
     TRY(enter(ctx));
     if (n_sb == 0) return SVTHIP_OK;
     TRY(check_plane_search({d_src, d_ref, d_desc, d_sad, d_mv}, max_sw, max_sh, d_src, src_stride, ref_stride));
-#define LAUNCH_FULLPEL(kernel, lds)                                                                                                       \
-    hipLaunchKernelGGL(svthip::kernel, dim3(svthip::xcd_grid(n_sb)), dim3(256), lds, call_stream(ctx, stream), d_src, src_stride, d_ref, \
-                       ref_stride, reinterpret_cast<const int32_t*>(d_desc), n_sb, d_sad, d_mv)
-    if (n_pu == 209)
-        LAUNCH_FULLPEL(fullpel209_kernel, svthip::fullpel209_lds_bytes(max_sh));
-    else if (svthip::fullpel_img2_fits(max_sw, max_sh))
-        LAUNCH_FULLPEL(fullpel85_img2_kernel, svthip::fullpel_img2_lds_bytes());
-    else
-        LAUNCH_FULLPEL(fullpel85_kernel, svthip::fullpel_lds_bytes(max_sh));
-#undef LAUNCH_FULLPEL
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(svthip::launch_fullpel(n_pu, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh, d_sad, d_mv, call_stream(ctx, stream)));
     return SVTHIP_OK;
+}
+
+int32_t check_subpel_planes_fit(uint32_t max_sw, uint32_t max_sh)
+{
+    return svthip::subpel_planes_fit(max_sw, max_sh) ? SVTHIP_OK : fail(SVTHIP_ERR_BAD_PARAMETER, "search area too large for the LDS planes");
 }
 
 int32_t subpel_refine_common(svthip_ctx* ctx, const uint8_t* d_src_plane, uint32_t src_stride, const uint8_t* d_ref_plane, uint32_t ref_stride,
                              const svthip_fullpel_desc* d_desc, uint32_t n_sb, uint32_t max_search_area_width, uint32_t max_search_area_height,
                              int32_t disable_8x8_refinement, int n_pu, uint32_t* d_best_sad, uint32_t* d_best_mv, void* stream,
-                             uint32_t* d_pred = nullptr, int32_t method = SVTHIP_FRACTIONAL_SSD_SEARCH)
+                             int32_t method = SVTHIP_FRACTIONAL_SSD_SEARCH)
 {
     TRY(enter(ctx));
     if (method != SVTHIP_FRACTIONAL_SUB_SAD_SEARCH && method != SVTHIP_FRACTIONAL_FULL_SAD_SEARCH && method != SVTHIP_FRACTIONAL_SSD_SEARCH)
@@ -346,14 +338,29 @@ int32_t subpel_refine_common(svthip_ctx* ctx, const uint8_t* d_src_plane, uint32
     if (n_sb == 0) return SVTHIP_OK;
     TRY(check_plane_search({d_src_plane, d_ref_plane, d_desc, d_best_sad, d_best_mv}, max_search_area_width, max_search_area_height, d_src_plane,
                            src_stride, ref_stride));
-    // the half-pel planes of the whole (bounded) search region interpolated once per (SB, list) in LDS, all PUs in one launch; the planes
-    // of the largest legal area (127 x 127) take 152.6 KB, so every legal call fits
-    const size_t lds_planes = svthip::subpel_planes_lds_bytes(max_search_area_width, max_search_area_height);
-    if (lds_planes > 160 * 1024 - 512) return fail(SVTHIP_ERR_BAD_PARAMETER, "search area too large for the LDS planes");
-    hipLaunchKernelGGL(svthip::subpel_planes_kernel, dim3(svthip::subpel_planes_grid(n_sb)), dim3(n_pu == 209 ? 448 : 512), lds_planes,
-                       call_stream(ctx, stream), d_src_plane, src_stride, d_ref_plane, ref_stride, reinterpret_cast<const int32_t*>(d_desc), n_sb,
-                       (int)(disable_8x8_refinement != 0), n_pu, d_best_sad, d_best_mv, d_pred, (int)method);
-    HIP_TRY(hipGetLastError());
+    TRY(check_subpel_planes_fit(max_search_area_width, max_search_area_height));
+    HIP_TRY(svthip::launch_subpel_planes(d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, max_search_area_width, max_search_area_height,
+                                         disable_8x8_refinement != 0, n_pu, d_best_sad, d_best_mv, nullptr, (int)method, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+// what bi-prediction of two lists checks on top of check_plane_search: both windows of the area in LDS
+int32_t check_bipred_windows(std::initializer_list<const void*> ptrs, uint32_t sw, uint32_t sh, const void* src_plane, uint32_t src_stride,
+                             uint32_t ref0_stride, uint32_t ref1_stride, int n_pu)
+{
+    TRY(check_plane_search(ptrs, sw, sh, src_plane, src_stride, ref0_stride, ref1_stride));
+    if (!svthip::bipred_windows_fit(sw, sh, n_pu)) return fail(SVTHIP_ERR_BAD_PARAMETER, "search area too large for the LDS windows");
+    return SVTHIP_OK;
+}
+
+// 209-PU mode with two lists: the squares' bi-pred SADs go through SLOT_BIPRED_SQ ([n_sb][85]) to the kernel that packs all 209 PUs
+int32_t bipred_sq_scratch(svthip_ctx* ctx, size_t n_sb, int n_pu, uint32_t n_lists, hipStream_t s, uint32_t** out)
+{
+    *out = nullptr;
+    if (n_pu != 209 || n_lists != 2) return SVTHIP_OK;
+    TRY(ensure_scratch(ctx, SLOT_BIPRED_SQ, bipred_sq_bytes(n_sb)));
+    TRY(scratch_on_stream(ctx, s));
+    *out = slot_ptr<uint32_t>(ctx, SLOT_BIPRED_SQ);
     return SVTHIP_OK;
 }
 
@@ -367,52 +374,36 @@ int32_t bipred_pack_common(svthip_ctx* ctx, const uint8_t* d_src_plane, uint32_t
     if (n_sb == 0) return SVTHIP_OK;
     if (n_lists < 1 || n_lists > 2) return fail(SVTHIP_ERR_BAD_PARAMETER, "n_lists must be 1 or 2");
     TRY(check_non_null({d_sad0, d_mv0, d_out}));
-    size_t lds = 0, lds_nsq = 0;
-    int win_bytes = 0;
-    if (n_lists == 2) {
-        TRY(check_plane_search({d_src_plane, d_ref0_plane, d_ref1_plane, d_desc0, d_desc1, d_sad1, d_mv1}, max_search_area_width,
-                               max_search_area_height, d_src_plane, src_stride, ref0_stride, ref1_stride));
-        lds = svthip::bipred_lds_bytes(max_search_area_width, max_search_area_height);
-        lds_nsq = svthip::bipred_nsq_lds_bytes(max_search_area_width, max_search_area_height);
-        win_bytes = (int)svthip::subpel_window_bytes(max_search_area_width, max_search_area_height);
-        if (lds > 160 * 1024 || (n_pu == 209 && lds_nsq > 160 * 1024))
-            return fail(SVTHIP_ERR_BAD_PARAMETER, "search area too large for the LDS windows");
-    }
+    if (n_lists == 2)
+        TRY(check_bipred_windows({d_src_plane, d_ref0_plane, d_ref1_plane, d_desc0, d_desc1, d_sad1, d_mv1}, max_search_area_width,
+                                 max_search_area_height, d_src_plane, src_stride, ref0_stride, ref1_stride, n_pu));
     hipStream_t s = call_stream(ctx, stream);
-    const int32_t *desc0 = reinterpret_cast<const int32_t*>(d_desc0), *desc1 = reinterpret_cast<const int32_t*>(d_desc1);
-    if (n_pu == 85) {
-        hipLaunchKernelGGL(svthip::bipred_pack_kernel, dim3(n_sb), dim3(256), lds, s, d_src_plane, src_stride, d_ref0_plane, ref0_stride, desc0,
-                           d_ref1_plane, ref1_stride, desc1, d_sad0, d_mv0, d_sad1, d_mv1, (int)n_lists, (int)bipred_8x8, win_bytes, 85,
-                           (uint32_t*)nullptr, d_out);
-        HIP_TRY(hipGetLastError());
-        return SVTHIP_OK;
-    }
-    // 209-PU mode: the squares' bi-pred SADs go through SLOT_BIPRED_SQ ([n_sb][85]) to the kernel that packs all 209 PUs
-    uint32_t* bisad_sq = nullptr;
-    if (n_lists == 2) {
-        TRY(ensure_scratch(ctx, SLOT_BIPRED_SQ, bipred_sq_bytes(n_sb)));
-        TRY(scratch_on_stream(ctx, s));
-        bisad_sq = slot_ptr<uint32_t>(ctx, SLOT_BIPRED_SQ);
-        hipLaunchKernelGGL(svthip::bipred_pack_kernel, dim3(n_sb), dim3(256), lds, s, d_src_plane, src_stride, d_ref0_plane, ref0_stride, desc0,
-                           d_ref1_plane, ref1_stride, desc1, d_sad0, d_mv0, d_sad1, d_mv1, 2, 1, win_bytes, 209, bisad_sq,
-                           (svthip_me_cu_result*)nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(svthip::bipred_nsq_pack_kernel, dim3(n_sb), dim3(320), lds_nsq, s, d_src_plane, src_stride, d_ref0_plane, ref0_stride, desc0,
-                       d_ref1_plane, ref1_stride, desc1, d_sad0, d_mv0, d_sad1, d_mv1, (int)n_lists, win_bytes, (const uint32_t*)bisad_sq, d_out);
-    HIP_TRY(hipGetLastError());
+    uint32_t* bisad_sq;
+    TRY(bipred_sq_scratch(ctx, n_sb, n_pu, n_lists, s, &bisad_sq));
+    HIP_TRY(svthip::launch_bipred_pack(d_src_plane, src_stride, d_ref0_plane, ref0_stride, d_desc0, d_ref1_plane, ref1_stride, d_desc1, n_sb,
+                                       max_search_area_width, max_search_area_height, d_sad0, d_mv0, d_sad1, d_mv1, (int)n_lists, bipred_8x8 != 0, n_pu,
+                                       bisad_sq, d_out, s));
     return SVTHIP_OK;
 }
 
-// pictures j0 .. of n that share one launch: the kernels take their job tables by value, SVTHIP_HME_MAX_JOBS entries each
-uint32_t jobs_in_chunk(uint32_t n, uint32_t j0) { return n - j0 < SVTHIP_HME_MAX_JOBS ? n - j0 : SVTHIP_HME_MAX_JOBS; }
-
-svthip::PaJobTable pa_job_table(const svthip_pa_picture* pics, uint32_t nj)
+// what the search-centre derivation checks of its parameters and of the (current, reference) picture pairs of one list
+int32_t check_hme_pictures(const svthip_pa_picture* cur, const svthip_pa_picture* ref, uint32_t n_jobs, const svthip_me_params& P)
 {
-    svthip::PaJobTable jt;
-    memset(&jt, 0, sizeof(jt));
-    for (uint32_t j = 0; j < nj; j++) jt.pic[j] = pics[j];
-    return jt;
+    if (P.number_hme_search_region_in_width < 1 || P.number_hme_search_region_in_width > 2 ||
+        P.number_hme_search_region_in_height < 1 || P.number_hme_search_region_in_height > 2)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "HME search regions must be 1..2 per axis");
+    for (uint32_t j = 0; j < n_jobs; j++) {
+        const svthip_pa_picture *c = cur + j, *r = ref + j;
+        if ((c->width & 7) || (c->height & 7) || c->width != r->width || c->height != r->height || c->width != cur->width ||
+            c->height != cur->height)
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be equal multiples of 8 (job %d)", (int)j);
+        if ((c->full_stride & 3u) || (r->full_stride & 3u) || (c->full_offset & 3))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "full-resolution strides / current-plane offset must be multiples of 4 (job %d)", (int)j);
+        const int64_t max_off = (c->full_offset > r->full_offset ? c->full_offset : r->full_offset) +
+                                (int64_t)(c->height + 136) * (c->full_stride > r->full_stride ? c->full_stride : r->full_stride);
+        if (max_off > 0x7fffffffLL) return fail(SVTHIP_ERR_BAD_PARAMETER, "picture pool offsets must fit 31 bits (job %d)", (int)j);
+    }
+    return SVTHIP_OK;
 }
 
 // the whole ME chain of n_jobs pictures, 85 or 209 PUs per SB
@@ -429,6 +420,18 @@ int32_t motion_estimate_batch_common(svthip_ctx* ctx, const uint8_t* d_pool, con
             (ref1 && ref1[j].full_stride != ref1[0].full_stride))
             return fail(SVTHIP_ERR_BAD_PARAMETER, "all pictures of a batch must share their full-resolution strides (job %d)", (int)j);
     const uint32_t n_lists = ref1 ? 2u : 1u;
+    const uint32_t sw = params->search_area_width < 127 ? params->search_area_width : 127;
+    const uint32_t sh = params->search_area_height < 127 ? params->search_area_height : 127;
+    const svthip_pa_picture* refs[2] = {ref0, ref1};
+    const bool stored_pred = n_lists == 2 && use_subpel_flag;
+    // what the steps check, list by list, before anything is launched
+    for (uint32_t l = 0; l < n_lists; l++) {
+        TRY(check_hme_pictures(cur, refs[l], n_jobs, *params));
+        TRY(check_plane_search({d_pool}, sw, sh, d_pool, cur->full_stride, refs[l]->full_stride));
+        if (use_subpel_flag) TRY(check_subpel_planes_fit(sw, sh));
+    }
+    if (n_lists == 2 && !stored_pred)
+        TRY(check_bipred_windows({d_pool}, sw, sh, d_pool, cur->full_stride, ref0->full_stride, ref1->full_stride, (int)n_pu));
     const size_t n = (size_t)n_jobs * n_sb;
     const MeChainLayout L = me_chain_layout(n, n_pu);
     TRY(ensure_scratch(ctx, SLOT_ME_CHAIN, L.total));
@@ -443,37 +446,34 @@ int32_t motion_estimate_batch_common(svthip_ctx* ctx, const uint8_t* d_pool, con
     int16_t* state = slot_ptr<int16_t>(ctx, SLOT_ME_CHAIN, L.state);
     hipStream_t s = call_stream(ctx, stream);
     TRY(scratch_on_stream(ctx, s));  // SLOT_ME_CHAIN / SLOT_ME_PRED are about to be used by work on `s`
-    const uint32_t sw = params->search_area_width < 127 ? params->search_area_width : 127;
-    const uint32_t sh = params->search_area_height < 127 ? params->search_area_height : 127;
-    const svthip_pa_picture* refs[2] = {ref0, ref1};
     // B pictures with sub-pel on: the sub-pel kernels also store each PU's prediction at its refined MV (SLOT_ME_PRED) and the
     // bi-prediction stage averages the stored blocks instead of interpolating again
     uint8_t* pred[2] = {nullptr, nullptr};
-    if (n_lists == 2 && use_subpel_flag) {
+    if (stored_pred) {
         TRY(ensure_scratch(ctx, SLOT_ME_PRED, me_pred_bytes(n, n_pu)));
         pred[0] = slot_ptr<uint8_t>(ctx, SLOT_ME_PRED);
         pred[1] = pred[0] + me_pred_list_bytes(n, n_pu);
     }
     // seven launches whatever the number of pictures: per list search centres -> full-pel -> sub-pel, then bi-prediction + packing
     for (uint32_t l = 0; l < n_lists; l++) {
-        TRY(svthip_me_hme_search_center_batch_dev(ctx, d_pool, cur, refs[l], n_jobs, params, l, d_sb, n_sb, l ? mv[0] : nullptr, n_pu, desc[l],
-                                                  nullptr, state, s));
-        TRY(launch_fullpel(ctx, n_pu, d_pool, cur->full_stride, d_pool, refs[l]->full_stride, desc[l], (uint32_t)n, sw, sh, sad[l], mv[l], s));
+        HIP_TRY(svthip::launch_hme_centers(d_pool, cur, refs[l], n_jobs, *params, l, d_sb, n_sb, l ? mv[0] : nullptr, n_pu, desc[l], nullptr, state, s));
+        HIP_TRY(svthip::launch_fullpel(n_pu, d_pool, cur->full_stride, d_pool, refs[l]->full_stride, desc[l], (uint32_t)n, sw, sh, sad[l], mv[l], s));
         if (use_subpel_flag)
-            TRY(subpel_refine_common(ctx, d_pool, cur->full_stride, d_pool, refs[l]->full_stride, desc[l], (uint32_t)n, sw, sh, cu8x8_mode == 1,
-                                     (int)n_pu, sad[l], mv[l], s, reinterpret_cast<uint32_t*>(pred[l])));
+            HIP_TRY(svthip::launch_subpel_planes(d_pool, cur->full_stride, d_pool, refs[l]->full_stride, desc[l], (uint32_t)n, sw, sh, cu8x8_mode == 1,
+                                                 (int)n_pu, sad[l], mv[l], reinterpret_cast<uint32_t*>(pred[l]), SVTHIP_FRACTIONAL_SSD_SEARCH, s));
     }
-    if (pred[0]) {
-        hipLaunchKernelGGL(svthip::bipred_stored_pack_kernel, dim3((uint32_t)n), dim3(256), 0, s, d_pool, cur->full_stride,
-                           reinterpret_cast<const int32_t*>(desc[0]), (const uint8_t*)pred[0], (const uint8_t*)pred[1],
-                           (const uint32_t*)sad[0], (const uint32_t*)mv[0], (const uint32_t*)sad[1], (const uint32_t*)mv[1], (int)n_pu,
-                           (int)(cu8x8_mode == 0), d_out);
-        HIP_TRY(hipGetLastError());
+    if (stored_pred) {
+        HIP_TRY(svthip::launch_bipred_stored_pack(d_pool, cur->full_stride, desc[0], pred[0], pred[1], sad[0], mv[0], sad[1], mv[1], (uint32_t)n,
+                                                  (int)n_pu, cu8x8_mode == 0, d_out, s));
         return SVTHIP_OK;
     }
-    return bipred_pack_common(ctx, d_pool, cur->full_stride, d_pool, ref0->full_stride, desc[0], n_lists == 2 ? d_pool : nullptr,
-                              n_lists == 2 ? ref1->full_stride : 0, n_lists == 2 ? desc[1] : nullptr, (uint32_t)n, sw, sh, sad[0], mv[0],
-                              n_lists == 2 ? sad[1] : nullptr, n_lists == 2 ? mv[1] : nullptr, n_lists, cu8x8_mode == 0, (int)n_pu, d_out, s);
+    uint32_t* bisad_sq;
+    TRY(bipred_sq_scratch(ctx, n, (int)n_pu, n_lists, s, &bisad_sq));
+    HIP_TRY(svthip::launch_bipred_pack(d_pool, cur->full_stride, d_pool, ref0->full_stride, desc[0], n_lists == 2 ? d_pool : nullptr,
+                                       n_lists == 2 ? ref1->full_stride : 0, n_lists == 2 ? desc[1] : nullptr, (uint32_t)n, sw, sh, sad[0], mv[0],
+                                       n_lists == 2 ? sad[1] : nullptr, n_lists == 2 ? mv[1] : nullptr, (int)n_lists, cu8x8_mode == 0, (int)n_pu,
+                                       bisad_sq, d_out, s));
+    return SVTHIP_OK;
 }
 
 // ---------------------------------------------------------------- transform / quantisation
@@ -553,9 +553,9 @@ int32_t check_pa_denoised(const uint8_t* d_denoised, uint32_t denoised_stride, u
 // ---------------------------------------------------------------- prediction
 
 // The two whole-PU prediction families (translational, warped) share SLOT_INTER_JOBS (job list; for the warped entries that of the
-// translational chroma) and the refusal counter of SLOT_INTER_REFUSED.  pred_check_args: the checks both make first, once there is
-// work.  pred_begin: the rest of both prologues -- 16-bit plane alignment, the family's PU cap, scratch ordered on the call's stream
-// and sized by the family's function, the counter cleared on its first use.
+// translational chroma).  pred_check_args: the checks both make first, once there is work.  pred_begin: the rest of both prologues --
+// 16-bit plane alignment, the family's PU cap, the call's stream and the refusal counter (refused_counter), the job list sized by the
+// family's function.
 typedef std::initializer_list<const svthip_inter_planes*> InterPlanesList;
 
 int32_t pred_check_args(InterPlanesList planes, const void* d_desc)
@@ -568,27 +568,31 @@ int32_t pred_check_args(InterPlanesList planes, const void* d_desc)
     return SVTHIP_OK;
 }
 
-// the refusal counter of SLOT_INTER_REFUSED on the call's stream (scratch_on_stream has run), cleared on its first use
-int32_t ensure_refused_counter(svthip_ctx* ctx, hipStream_t s)
+// What every entry that can refuse work on the device does last before it launches: the call's stream (the caller's, or the context's
+// own), the context's scratch ordered on it, and on it the refusal counter of SLOT_REFUSED, cleared on its first use.
+// svthip_inter_pred_refused synchronises with the stream of the last such call.
+int32_t refused_counter(svthip_ctx* ctx, void* stream, hipStream_t* out_s, uint32_t** out_refused)
 {
-    const bool first = ctx->scratch[SLOT_INTER_REFUSED] == nullptr;
-    TRY(ensure_scratch(ctx, SLOT_INTER_REFUSED, 256));
-    if (first) HIP_TRY(hipMemsetAsync(ctx->scratch[SLOT_INTER_REFUSED], 0, 256, s));
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(scratch_on_stream(ctx, s));
+    const bool first = ctx->scratch[SLOT_REFUSED] == nullptr;
+    TRY(ensure_scratch(ctx, SLOT_REFUSED, 256));
+    if (first) HIP_TRY(hipMemsetAsync(ctx->scratch[SLOT_REFUSED], 0, 256, s));
+    ctx->refused_stream = s;
+    *out_s = s;
+    *out_refused = slot_ptr<uint32_t>(ctx, SLOT_REFUSED);
     return SVTHIP_OK;
 }
 
 int32_t pred_begin(svthip_ctx* ctx, InterPlanesList planes, int bd, uint32_t n_pu, uint32_t n_pu_cap, size_t (*scratch_bytes)(uint32_t),
-                   void* stream, hipStream_t* out_s)
+                   void* stream, hipStream_t* out_s, uint32_t** out_refused)
 {
     if (bd > 8)
         for (const svthip_inter_planes* p : planes)
             if (!aligned({p->y, p->cb, p->cr}, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
     if (n_pu > n_pu_cap) return fail(SVTHIP_ERR_BAD_PARAMETER, "too many PUs in one call (%d)", (int)n_pu);
-    hipStream_t s = call_stream(ctx, stream);
-    TRY(scratch_on_stream(ctx, s));
+    TRY(refused_counter(ctx, stream, out_s, out_refused));
     TRY(ensure_scratch(ctx, SLOT_INTER_JOBS, scratch_bytes(n_pu)));
-    TRY(ensure_refused_counter(ctx, s));
-    *out_s = s;
     return SVTHIP_OK;
 }
 
@@ -599,10 +603,10 @@ int32_t inter_pred_entry(svthip_ctx* ctx, const svthip_inter_planes* ref0, const
     if (n_pu == 0) return SVTHIP_OK;
     TRY(pred_check_args({ref0, ref1, dst}, d_desc));
     hipStream_t s;
-    TRY(pred_begin(ctx, {ref0, ref1, dst}, bd, n_pu, 0x0fffffffu, svthip::inter_pred_scratch_bytes, stream, &s));
+    uint32_t* d_refused;
+    TRY(pred_begin(ctx, {ref0, ref1, dst}, bd, n_pu, 0x0fffffffu, svthip::inter_pred_scratch_bytes, stream, &s, &d_refused));
     HIP_TRY(svthip::launch_inter_pred(*ref0, *ref1, *dst, d_desc, n_pu, (int)bwidth, (int)bheight, bd, !ctx->opt[SVTHIP_OPT_CONVOLVE_VALU],
-                                      ctx->scratch[SLOT_INTER_JOBS], slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
-    ctx->inter_stream = s;
+                                      ctx->scratch[SLOT_INTER_JOBS], d_refused, s));
     return SVTHIP_OK;
 }
 
@@ -616,10 +620,10 @@ int32_t warped_pred_entry(svthip_ctx* ctx, const svthip_inter_planes* ref, const
     if (!pic_width || !pic_height || pic_width > 65535u || pic_height > 65535u)
         return fail(SVTHIP_ERR_BAD_PARAMETER, "pic_width and pic_height must be 1..65535 (width %d)", (int)pic_width);
     hipStream_t s;
-    TRY(pred_begin(ctx, {ref, dst}, bd, n_pu, 0x00ffffffu, svthip::warp_scratch_bytes, stream, &s));
+    uint32_t* d_refused;
+    TRY(pred_begin(ctx, {ref, dst}, bd, n_pu, 0x00ffffffu, svthip::warp_scratch_bytes, stream, &s, &d_refused));
     HIP_TRY(svthip::launch_warped_pred(*ref, *dst, (int)pic_width, (int)pic_height, d_desc, n_pu, (int)bwidth, (int)bheight, bd,
-                                       ctx->scratch[SLOT_INTER_JOBS], slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
-    ctx->inter_stream = s;
+                                       ctx->scratch[SLOT_INTER_JOBS], d_refused, s));
     return SVTHIP_OK;
 }
 
@@ -634,11 +638,10 @@ int32_t intra_pred_entry(svthip_ctx* ctx, const void* d_edge, void* d_dst, const
     if (bd > 8 && !aligned({d_edge, d_dst}, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
     if (d_sad && !d_src) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sad needs d_src");
     if (d_sad && !aligned(d_sad, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sad must be 4-byte aligned");
-    hipStream_t s = call_stream(ctx, stream);
-    TRY(scratch_on_stream(ctx, s));
-    TRY(ensure_refused_counter(ctx, s));
-    HIP_TRY(svthip::launch_intra_pred(d_edge, d_dst, d_desc, n_blocks, (int)tx_size, bd, d_src, d_sad, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
-    ctx->inter_stream = s;
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
+    HIP_TRY(svthip::launch_intra_pred(d_edge, d_dst, d_desc, n_blocks, (int)tx_size, bd, d_src, d_sad, d_refused, s));
     return SVTHIP_OK;
 }
 
@@ -665,12 +668,11 @@ int32_t cfl_pred_entry(svthip_ctx* ctx, const void* d_luma, const void* d_cb, co
     TRY(check_cfl_luma_size(luma_w, luma_h));
     if (n_blocks == 0) return SVTHIP_OK;
     TRY(check_cfl_args({d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst}, d_desc, bd));
-    hipStream_t s = call_stream(ctx, stream);
-    TRY(scratch_on_stream(ctx, s));
-    TRY(ensure_refused_counter(ctx, s));
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
     HIP_TRY(svthip::launch_cfl_pred(d_luma, d_cb, d_cr, d_cb_dst, d_cr_dst, d_desc, n_blocks, (int)luma_w, (int)luma_h, bd,
-                                    slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
-    ctx->inter_stream = s;
+                                    d_refused, s));
     return SVTHIP_OK;
 }
 
@@ -824,11 +826,10 @@ int32_t lr_filter_frame_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, voi
             return fail(SVTHIP_ERR_BAD_PARAMETER, "output stride of plane %d is smaller than its width", (int)p);
         if (bd > 8 && !aligned(d_out[p], 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
     }
-    hipStream_t s = call_stream(ctx, stream);
-    TRY(scratch_on_stream(ctx, s));
-    TRY(ensure_refused_counter(ctx, s));
-    HIP_TRY(svthip::launch_lr_filter_frame(*pic, d_out, out_stride, (int)ps, (int)pe, bd, d_unit_type, d_taps, d_sgrproj, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
-    ctx->inter_stream = s;
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
+    HIP_TRY(svthip::launch_lr_filter_frame(*pic, d_out, out_stride, (int)ps, (int)pe, bd, d_unit_type, d_taps, d_sgrproj, d_refused, s));
     return SVTHIP_OK;
 }
 
@@ -1123,7 +1124,7 @@ int32_t svthip_me_fullpel_search_dev(svthip_ctx* ctx, const uint8_t* d_src_plane
                                      uint32_t n_sb, uint32_t max_search_area_width, uint32_t max_search_area_height,
                                      uint32_t* d_best_sad, uint32_t* d_best_mv, void* stream)
 {
-    return launch_fullpel(ctx, 85, d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, max_search_area_width,
+    return fullpel_entry(ctx, 85, d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, max_search_area_width,
                           max_search_area_height, d_best_sad, d_best_mv, stream);
 }
 
@@ -1132,7 +1133,7 @@ int32_t svthip_me_fullpel_search209_dev(svthip_ctx* ctx, const uint8_t* d_src_pl
                                         uint32_t max_search_area_width, uint32_t max_search_area_height, uint32_t* d_best_sad,
                                         uint32_t* d_best_mv, void* stream)
 {
-    return launch_fullpel(ctx, 209, d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, max_search_area_width,
+    return fullpel_entry(ctx, 209, d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, max_search_area_width,
                           max_search_area_height, d_best_sad, d_best_mv, stream);
 }
 
@@ -1160,7 +1161,7 @@ int32_t svthip_me_subpel_search_dev(svthip_ctx* ctx, const uint8_t* d_src_plane,
                                     int32_t fractional_search_method, uint32_t* d_best_sad, uint32_t* d_best_mv, void* stream)
 {
     return subpel_refine_common(ctx, d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, max_search_area_width,
-                                max_search_area_height, disable_8x8_refinement, all_pu ? 209 : 85, d_best_sad, d_best_mv, stream, nullptr,
+                                max_search_area_height, disable_8x8_refinement, all_pu ? 209 : 85, d_best_sad, d_best_mv, stream,
                                 fractional_search_method);
 }
 
@@ -1199,39 +1200,9 @@ int32_t svthip_me_hme_search_center_batch_dev(svthip_ctx* ctx, const uint8_t* d_
     if (list_index > 1) return fail(SVTHIP_ERR_BAD_PARAMETER, "list_index must be 0 or 1");
     if (list_index == 1 && !d_l0_best_mv64 && params->temporal_layer_index > 0)
         return fail(SVTHIP_ERR_BAD_PARAMETER, "list 1 needs the list-0 64x64 MVs (hme_mv_center_check direct candidate)");
-    const svthip_me_params& P = *params;
-    if (P.number_hme_search_region_in_width < 1 || P.number_hme_search_region_in_width > 2 ||
-        P.number_hme_search_region_in_height < 1 || P.number_hme_search_region_in_height > 2)
-        return fail(SVTHIP_ERR_BAD_PARAMETER, "HME search regions must be 1..2 per axis");
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        const svthip_pa_picture *c = cur + j, *r = ref + j;
-        if ((c->width & 7) || (c->height & 7) || c->width != r->width || c->height != r->height || c->width != cur->width ||
-            c->height != cur->height)
-            return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be equal multiples of 8 (job %d)", (int)j);
-        if ((c->full_stride & 3u) || (r->full_stride & 3u) || (c->full_offset & 3))
-            return fail(SVTHIP_ERR_BAD_PARAMETER, "full-resolution strides / current-plane offset must be multiples of 4 (job %d)", (int)j);
-        const int64_t max_off = (c->full_offset > r->full_offset ? c->full_offset : r->full_offset) +
-                                (int64_t)(c->height + 136) * (c->full_stride > r->full_stride ? c->full_stride : r->full_stride);
-        if (max_off > 0x7fffffffLL) return fail(SVTHIP_ERR_BAD_PARAMETER, "picture pool offsets must fit 31 bits (job %d)", (int)j);
-    }
-    hipStream_t s = call_stream(ctx, stream);
-    const uint32_t mvs = l0_mv_stride ? l0_mv_stride : 1u;
-    for (uint32_t j0 = 0; j0 < n_jobs; j0 += SVTHIP_HME_MAX_JOBS) {
-        const uint32_t nj = jobs_in_chunk(n_jobs, j0);
-        svthip::HmeJobTable jt;
-        memset(&jt, 0, sizeof(jt));
-        for (uint32_t j = 0; j < nj; j++) {
-            jt.cur[j] = cur[j0 + j];
-            jt.ref[j] = ref[j0 + j];
-        }
-        const size_t base = (size_t)j0 * n_sb;
-        const uint32_t* mv64 = d_l0_best_mv64 ? d_l0_best_mv64 + base * mvs : nullptr;
-        int16_t* cen = d_center ? d_center + 2 * base : nullptr;
-        int16_t* st = d_hme_state ? d_hme_state + SVTHIP_HME_STATE_INT16 * base : nullptr;
-        hipLaunchKernelGGL(svthip::hme_center_kernel, dim3(svthip::xcd_grid(n_sb * nj)), dim3(256), 0, s, d_pool, jt, P, list_index, d_sb, n_sb, nj, mv64,
-                           mvs, d_desc + base, cen, st);
-        HIP_TRY(hipGetLastError());
-    }
+    TRY(check_hme_pictures(cur, ref, n_jobs, *params));
+    HIP_TRY(svthip::launch_hme_centers(d_pool, cur, ref, n_jobs, *params, list_index, d_sb, n_sb, d_l0_best_mv64, l0_mv_stride, d_desc, d_center,
+                                       d_hme_state, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 
@@ -1281,8 +1252,7 @@ int32_t svthip_me_results_to_ref_layout_dev(svthip_ctx* ctx, const svthip_me_cu_
     TRY(enter(ctx));
     if (n == 0) return SVTHIP_OK;
     TRY(check_non_null({d_in, d_out}));
-    hipLaunchKernelGGL(svthip::me_results_ref_layout_kernel, dim3((n + 255) / 256), dim3(256), 0, call_stream(ctx, stream), d_in, n, d_out);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(svthip::launch_me_results_ref_layout(d_in, n, d_out, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 
@@ -1299,24 +1269,12 @@ int32_t svthip_sad_loop_batch_dev(svthip_ctx* ctx, const uint8_t* d_src, uint32_
         return fail(SVTHIP_ERR_BAD_PARAMETER, "ref_stride must be ref_stride_raw or twice it (got %d)", (int)ref_stride);
     if (n_blocks == 0) return SVTHIP_OK;
     TRY(check_non_null({d_src, d_ref, d_desc, d_best_sad, d_best_xy}));
-    hipStream_t s = call_stream(ctx, stream);
-    if ((width == 4 || width == 8 || width == 16 || width == 32 || width == 64) && !ctx->opt[SVTHIP_OPT_SADLOOP_GENERIC]) {
-        // packed-SAD kernel (8 / 12 / 16 positions per lane, several blocks per workgroup); falls through to the generic one when its
-        // slightly wider window rows do not fit
-        const size_t qs = svthip::sad_loop_qsad_lds_bytes((int)width, (int)height, (int)search_area_width, (int)search_area_height,
-                                                          (int)(ref_stride / ref_stride_raw));
-        if (qs <= 64 * 1024) {
-            HIP_TRY(svthip::launch_sad_loop_qsad(d_src, src_stride, d_ref, ref_stride, ref_stride_raw, d_desc, n_blocks, (int)width, (int)height,
-                                                 (int)search_area_width, (int)search_area_height, d_best_sad, d_best_xy, s));
-            return SVTHIP_OK;
-        }
-    }
-    const size_t slice = svthip::sad_loop_slice_bytes((int)width, (int)height, (int)search_area_width, (int)search_area_height,
-                                                      (int)(ref_stride / ref_stride_raw));
-    if (slice * 4 > 64 * 1024) return fail(SVTHIP_ERR_BAD_PARAMETER, "block + search window too large for the LDS slice (%d bytes)", (int)slice);
-    hipLaunchKernelGGL(svthip::sad_loop_kernel, dim3((n_blocks + 3) / 4), dim3(256), slice * 4, s, d_src, src_stride, d_ref, ref_stride, ref_stride_raw,
-                       d_desc, n_blocks, (int)width, (int)height, (int)search_area_width, (int)search_area_height, (int)slice, d_best_sad, d_best_xy);
-    HIP_TRY(hipGetLastError());
+    const bool generic = ctx->opt[SVTHIP_OPT_SADLOOP_GENERIC] != 0;
+    size_t slice = 0;
+    if (!svthip::sad_loop_fits((int)width, (int)height, (int)search_area_width, (int)search_area_height, (int)(ref_stride / ref_stride_raw), generic, &slice))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "block + search window too large for the LDS slice (%d bytes)", (int)slice);
+    HIP_TRY(svthip::launch_sad_loop(d_src, src_stride, d_ref, ref_stride, ref_stride_raw, d_desc, n_blocks, (int)width, (int)height, (int)search_area_width,
+                                    (int)search_area_height, generic, d_best_sad, d_best_xy, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 
@@ -1360,10 +1318,7 @@ int32_t svthip_quantize_b_batch_dev(svthip_ctx* ctx, const int32_t* d_coeff, con
     if (n_tu == 0) return SVTHIP_OK;
     TRY(check_non_null({d_coeff, d_desc, d_qparams, d_iscan, d_qcoeff, d_dqcoeff, d_eob}));
     TRY(check_tq_pools(d_coeff, d_qcoeff, d_dqcoeff, d_iscan));
-    const uint32_t waves = n_tu < 8192u ? n_tu : 8192u;  // grid-stride beyond 2048 workgroups
-    hipLaunchKernelGGL(svthip::quantize_b_batch_kernel, dim3((waves + 3) / 4), dim3(256), 0, call_stream(ctx, stream), d_coeff, d_desc, n_tu,
-                       d_qparams, d_iscan, d_qcoeff, d_dqcoeff, d_eob);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(svthip::launch_quantize_b(d_coeff, d_desc, n_tu, d_qparams, d_iscan, d_qcoeff, d_dqcoeff, d_eob, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 
@@ -1413,7 +1368,6 @@ int32_t svthip_pa_derive_planes_dev(svthip_ctx* ctx, uint8_t* d_pool, const svth
     TRY(enter(ctx));
     if (n_pics == 0) return SVTHIP_OK;
     TRY(check_non_null({d_pool, pics}));
-    uint32_t max_dw = 0;
     for (uint32_t j = 0; j < n_pics; j++) {
         const svthip_pa_picture& p = pics[j];
         if ((p.width & 7) || (p.height & 7) || p.width == 0 || p.height == 0)
@@ -1424,17 +1378,8 @@ int32_t svthip_pa_derive_planes_dev(svthip_ctx* ctx, uint8_t* d_pool, const svth
             return fail(SVTHIP_ERR_BAD_PARAMETER, "quarter stride must be >= width/2 + 64 (picture %d)", (int)j);
         if (want_sixteenth && p.sixteenth_stride < (uint32_t)(p.width >> 2) + 32u)
             return fail(SVTHIP_ERR_BAD_PARAMETER, "sixteenth stride must be >= width/4 + 32 (picture %d)", (int)j);
-        const uint32_t dw = ((uint32_t)p.width + 136u + 3u) / 4u * ((uint32_t)p.height + 136u);
-        if (dw > max_dw) max_dw = dw;
     }
-    hipStream_t s = call_stream(ctx, stream);
-    const uint32_t bx = (max_dw + 255u) / 256u;
-    for (uint32_t j0 = 0; j0 < n_pics; j0 += SVTHIP_HME_MAX_JOBS) {
-        const uint32_t nj = jobs_in_chunk(n_pics, j0);
-        hipLaunchKernelGGL(svthip::pa_derive_planes_kernel, dim3(bx < 1024u ? bx : 1024u, 3, nj), dim3(256), 0, s, d_pool, pa_job_table(pics + j0, nj),
-                           (int)want_quarter, (int)want_sixteenth);
-        HIP_TRY(hipGetLastError());
-    }
+    HIP_TRY(svthip::launch_pa_derive_planes(d_pool, pics, n_pics, want_quarter != 0, want_sixteenth != 0, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 
@@ -1471,14 +1416,7 @@ int32_t svthip_open_loop_intra_search_batch_dev(svthip_ctx* ctx, const uint8_t* 
         if (p.full_stride < (uint32_t)p.width + 136u || (p.full_stride & 3u) || (p.full_offset & 3) || p.full_offset < 0)
             return fail(SVTHIP_ERR_BAD_PARAMETER, "full-resolution stride must be a multiple of 4 and >= width + 136, offset a multiple of 4 (picture %d)", (int)j);
     }
-    hipStream_t s = call_stream(ctx, stream);
-    for (uint32_t j0 = 0; j0 < n_jobs; j0 += SVTHIP_HME_MAX_JOBS) {
-        const uint32_t nj = jobs_in_chunk(n_jobs, j0);
-        const size_t first = (size_t)j0 * n_sb;
-        hipLaunchKernelGGL(svthip::ois_kernel, dim3(svthip::xcd_grid(n_sb * nj)), dim3(256), 0, s, d_pool, pa_job_table(cur + j0, nj), *params, d_sb,
-                           n_sb, nj, d_me ? d_me + first * me_pu_stride : nullptr, me_pu_stride, d_cand + first * 85 * 18, d_total + first * 85);
-        HIP_TRY(hipGetLastError());
-    }
+    HIP_TRY(svthip::launch_ois(d_pool, cur, n_jobs, *params, d_sb, n_sb, d_me, me_pu_stride, d_cand, d_total, call_stream(ctx, stream)));
     return SVTHIP_OK;
 }
 
@@ -2053,9 +1991,9 @@ int32_t svthip_inter_pred_refused(svthip_ctx* ctx, uint32_t* out_count)
     TRY(enter(ctx));
     TRY(check_non_null({out_count}));
     *out_count = 0;
-    uint32_t* d_refused = slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED);
+    uint32_t* d_refused = slot_ptr<uint32_t>(ctx, SLOT_REFUSED);
     if (!d_refused) return SVTHIP_OK;
-    hipStream_t s = ctx->inter_stream ? ctx->inter_stream : ctx->stream;
+    hipStream_t s = ctx->refused_stream ? ctx->refused_stream : ctx->stream;
     uint32_t n = 0;
     HIP_TRY(hipMemcpyAsync(&n, d_refused, sizeof(n), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2118,11 +2056,10 @@ int32_t svthip_md_fast_pick_batch_dev(svthip_ctx* ctx, const svthip_md_fast_resu
     TRY(check_non_null({d_result, d_desc, d_group, d_pick}));
     if (!aligned({d_result, d_desc, d_pick}, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "result, descriptor and pick arrays must be 16-byte aligned");
     if (!aligned(d_group, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "group array must be 8-byte aligned");
-    hipStream_t s = call_stream(ctx, stream);
-    TRY(scratch_on_stream(ctx, s));
-    TRY(ensure_refused_counter(ctx, s));
-    HIP_TRY(svthip::launch_md_fast_pick(d_result, d_desc, n_cand, d_group, n_groups, d_pick, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
-    ctx->inter_stream = s;
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
+    HIP_TRY(svthip::launch_md_fast_pick(d_result, d_desc, n_cand, d_group, n_groups, d_pick, d_refused, s));
     return SVTHIP_OK;
 }
 
@@ -2138,11 +2075,10 @@ int32_t svthip_md_model_rd_batch_dev(svthip_ctx* ctx, const svthip_inter_planes*
     TRY(pred_check_args({src, pred}, d_desc));
     TRY(check_non_null({d_result}));
     if (!aligned(d_result, 16)) return fail(SVTHIP_ERR_BAD_PARAMETER, "result array must be 16-byte aligned");
-    hipStream_t s = call_stream(ctx, stream);
-    TRY(scratch_on_stream(ctx, s));
-    TRY(ensure_refused_counter(ctx, s));
-    HIP_TRY(svthip::launch_md_model_rd(*src, *pred, d_desc, n_tiles, bwidth, bheight, (int16_t)quantizer, d_result, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
-    ctx->inter_stream = s;
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
+    HIP_TRY(svthip::launch_md_model_rd(*src, *pred, d_desc, n_tiles, bwidth, bheight, (int16_t)quantizer, d_result, d_refused, s));
     return SVTHIP_OK;
 }
 
@@ -2164,12 +2100,12 @@ int32_t svthip_md_interp_filter_search_batch_dev(svthip_ctx* ctx, const svthip_i
     if (n_tiles > 0x0fffffffu || !svthip::md_ifs_layout(n_tiles, bwidth, bheight, &L))
         return fail(SVTHIP_ERR_BAD_PARAMETER, "too many candidates in one call (%d): their trial tiles pass what 16-bit tile positions address", (int)n_cand);
     hipStream_t s;
-    TRY(pred_begin(ctx, {ref0, ref1, src}, 8, (uint32_t)n_tiles, 0x0fffffffu, svthip::inter_pred_scratch_bytes, stream, &s));
+    uint32_t* d_refused;
+    TRY(pred_begin(ctx, {ref0, ref1, src}, 8, (uint32_t)n_tiles, 0x0fffffffu, svthip::inter_pred_scratch_bytes, stream, &s, &d_refused));
     TRY(ensure_scratch(ctx, SLOT_MD_IFS, L.total));
     HIP_TRY(svthip::launch_md_ifs_search(*ref0, *ref1, *src, d_pu_desc, d_ifs_desc, n_cand, bwidth, bheight, search_mode, enable_dual_filter, (int16_t)quantizer,
                                          write_back, d_result, !ctx->opt[SVTHIP_OPT_CONVOLVE_VALU], ctx->scratch[SLOT_MD_IFS], L,
-                                         ctx->scratch[SLOT_INTER_JOBS], slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), s));
-    ctx->inter_stream = s;
+                                         ctx->scratch[SLOT_INTER_JOBS], d_refused, s));
     return SVTHIP_OK;
 }
 
@@ -2221,14 +2157,13 @@ int32_t svthip_md_full_loop_batch_dev(svthip_ctx* ctx, const svthip_inter_planes
         tile_rows * tile_h * slot_recon->y_stride > 0xffffffffull)
         return fail(SVTHIP_ERR_BAD_PARAMETER, "too many slots in one call (%d groups of %d): their tiles or coefficients pass 32-bit offsets", (int)n_groups,
                     (int)max_full);
-    hipStream_t s = call_stream(ctx, stream);
-    TRY(scratch_on_stream(ctx, s));
-    TRY(ensure_refused_counter(ctx, s));
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
     svthip::MdFullCall call = {*src, *pred, *slot_recon, *recon, d_fast, d_full, d_group, d_pick, n_cand, n_groups, bwidth, bheight, max_full, tiles_per_row,
                                type_mask_inter, type_mask_intra, stages, reduced_tx_set, d_qparams, d_iscan, iscan_offsets, d_tables, d_work, d_result,
-                               d_decision, slot_ptr<uint32_t>(ctx, SLOT_INTER_REFUSED), (uint32_t)ctx->opt[SVTHIP_OPT_TQ_MAX_WORKGROUPS]};
+                               d_decision, d_refused, (uint32_t)ctx->opt[SVTHIP_OPT_TQ_MAX_WORKGROUPS]};
     HIP_TRY(svthip::launch_md_full_loop(call, L, s));
-    ctx->inter_stream = s;
     return SVTHIP_OK;
 }
 
@@ -2269,7 +2204,7 @@ int32_t svthip_me_fullpel_search(svthip_ctx* ctx, const uint8_t* src_plane, size
         HIP_TRY(hipMemcpyAsync(d_src, src_plane, src_plane_bytes, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_ref, ref_plane, ref_plane_bytes, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_desc, desc, desc_b, hipMemcpyHostToDevice, s));
-        TRY(launch_fullpel(ctx, 85, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh, d_sad, d_mv, s));
+        TRY(fullpel_entry(ctx, 85, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, max_sw, max_sh, d_sad, d_mv, s));
         HIP_TRY(hipMemcpyAsync(best_sad, d_sad, out_b, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(best_mv, d_mv, out_b, hipMemcpyDeviceToHost, s));
         return SVTHIP_OK;
@@ -2481,7 +2416,7 @@ int32_t svthip_me_fullpel_search_time_dev(svthip_ctx* ctx, const uint8_t* d_src_
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipEventRecord(e0, s);
     for (uint32_t i = 0; e == hipSuccess && i < iters && rc == SVTHIP_OK; i++)
-        rc = launch_fullpel(ctx, 85, d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, max_search_area_width,
+        rc = fullpel_entry(ctx, 85, d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, max_search_area_width,
                             max_search_area_height, d_best_sad, d_best_mv, s);
     if (e == hipSuccess) e = hipEventRecord(e1, s);
     if (e == hipSuccess) e = hipEventSynchronize(e1);

@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "tq_launch.h"
 
 namespace {
 

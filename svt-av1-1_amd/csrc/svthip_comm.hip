@@ -19,7 +19,6 @@
 #include <new>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
 
 static_assert(SVTHIP_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
 

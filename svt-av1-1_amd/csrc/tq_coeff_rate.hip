@@ -18,7 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "me_kernels.h"
+#include "tq_launch.h"
+#include "tq_tile.h"
 
 namespace svthip {
 namespace {

@@ -31,7 +31,8 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "tq_launch.h"
+#include "tq_tile.h"
 
 namespace svthip {
 
@@ -502,15 +503,18 @@ hipError_t launch_encode_tu(const void* src, const void* pred, void* recon, int 
                                  n_tu, w, h, qparams, iscan, coeff, qcoeff, dqcoeff, eob, energy, dist, max_workgroups, s);
 }
 
-void encode_tu_dynamic_lds_kernels(const void** list)
+hipError_t encode_tu_raise_dynamic_lds()
 {
+    const void* list[4 * 19];
+    size_t n = 0;
 #define ADD(WL, HL)                                                                                                                             \
     if (TxTile<WL, HL>::lds_bytes(true) > kDefaultDynamicLdsLimit)                                                                              \
         for (const void* k : {(const void*)&encode_tu_kernel<WL, HL, uint8_t, false>, (const void*)&encode_tu_kernel<WL, HL, uint8_t, true>,    \
                               (const void*)&encode_tu_kernel<WL, HL, uint16_t, false>, (const void*)&encode_tu_kernel<WL, HL, uint16_t, true>}) \
-            *list++ = k;
+            list[n++] = k;
     SVTHIP_TX_SIZES(ADD)
 #undef ADD
+    return raise_dynamic_lds(list, n);
 }
 
 }  // namespace svthip

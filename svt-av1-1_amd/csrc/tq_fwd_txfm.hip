@@ -22,7 +22,8 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "tq_launch.h"
+#include "tq_tile.h"
 
 namespace svthip {
 
@@ -149,12 +150,15 @@ hipError_t launch_fwd_txfm2d(const int16_t* residual, const svthip_txfm_desc* de
     });
 }
 
-void fwd_txfm_dynamic_lds_kernels(const void** list)
+hipError_t fwd_txfm_raise_dynamic_lds()
 {
+    const void* list[19];
+    size_t n = 0;
 #define ADD(WL, HL) \
-    if (TxTile<WL, HL>::lds_bytes() > kDefaultDynamicLdsLimit) *list++ = reinterpret_cast<const void*>(&fwd_txfm2d_kernel<WL, HL>);
+    if (TxTile<WL, HL>::lds_bytes() > kDefaultDynamicLdsLimit) list[n++] = reinterpret_cast<const void*>(&fwd_txfm2d_kernel<WL, HL>);
     SVTHIP_TX_SIZES(ADD)
 #undef ADD
+    return raise_dynamic_lds(list, n);
 }
 
 }  // namespace svthip

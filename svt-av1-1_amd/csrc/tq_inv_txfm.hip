@@ -19,7 +19,8 @@
 #include <stdint.h>
 
 #include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "tq_launch.h"
+#include "tq_tile.h"
 
 namespace svthip {
 
@@ -193,14 +194,17 @@ hipError_t launch_inv_txfm2d_add(const int32_t* coeff, const svthip_itxfm_desc* 
     return launch_sized<uint8_t>(coeff, desc, n_tu, w, h, bd, static_cast<uint8_t*>(recon), s);
 }
 
-void inv_txfm_dynamic_lds_kernels(const void** list)
+hipError_t inv_txfm_raise_dynamic_lds()
 {
+    const void* list[2 * 19];
+    size_t n = 0;
 #define ADD(WL, HL)                                                                                                                     \
     if (TxTile<WL, HL>::lds_bytes() > kDefaultDynamicLdsLimit)                                                                          \
         for (const void* k : {(const void*)&inv_txfm2d_add_kernel<WL, HL, uint8_t>, (const void*)&inv_txfm2d_add_kernel<WL, HL, uint16_t>}) \
-            *list++ = k;
+            list[n++] = k;
     SVTHIP_TX_SIZES(ADD)
 #undef ADD
+    return raise_dynamic_lds(list, n);
 }
 
 }  // namespace svthip

@@ -13,8 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/svtav1_hip.h"
-#include "me_kernels.h"
+#include "tq_launch.h"
+#include "tq_tile.h"
 
 namespace svthip {
 
@@ -59,6 +59,14 @@ __global__ void __launch_bounds__(256) quantize_b_batch_kernel(const int32_t* __
         last = group_max_i32<64>(last);
         if (lane == 0) eob[tu] = (uint16_t)last;
     }
+}
+
+hipError_t launch_quantize_b(const int32_t* coeff, const svthip_quant_desc* desc, uint32_t n_tu, const int16_t* qparams, const int16_t* iscan_pool,
+                             int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob, hipStream_t s)
+{
+    const uint32_t waves = n_tu < 8192u ? n_tu : 8192u;  // grid-stride beyond 2048 workgroups
+    hipLaunchKernelGGL(quantize_b_batch_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, coeff, desc, n_tu, qparams, iscan_pool, qcoeff, dqcoeff, eob);
+    return hipGetLastError();
 }
 
 }  // namespace svthip

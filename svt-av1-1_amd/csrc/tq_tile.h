@@ -51,14 +51,9 @@ inline R tx_size_dispatch(int w, int h, R none, F&& f)
     return none;
 }
 
-// sizes whose dynamic LDS passes what a kernel may take without a raised limit (svthip_abi.hip raises it once per device)
+// what a kernel may take as dynamic LDS without a raised limit: the three transform files raise it for the sizes that pass it
+// (<name>_raise_dynamic_lds, once per device)
 constexpr size_t kDefaultDynamicLdsLimit = 64 * 1024;
-constexpr int tx_dynamic_lds_sizes(bool staged)
-{
-#define SVTHIP_TX_CASE(WL, HL) +(TxTile<WL, HL>::lds_bytes(staged) > kDefaultDynamicLdsLimit ? 1 : 0)
-    return 0 SVTHIP_TX_SIZES(SVTHIP_TX_CASE);
-#undef SVTHIP_TX_CASE
-}
 
 #ifdef __HIPCC__
 // the lanes of a wave exchange data through LDS: everything written before is visible to every lane after

@@ -1,4 +1,4 @@
-// svt-av1-1_amd/csrc/tq_tx_search_tu.h -- a search TU of the RD transform-type decision on the device (launch_tx_decision, me_kernels.h), in a
+// svt-av1-1_amd/csrc/tq_tx_search_tu.h -- a search TU of the RD transform-type decision on the device (launch_tx_decision, tq_launch.h), in a
 // header of its own so that md_full_kernels.h, which the host test compiles without the HIP runtime, can fill it.
 #pragma once
 #include <stdint.h>
