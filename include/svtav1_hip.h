@@ -1067,9 +1067,9 @@ int32_t svthip_cdef_dist_8x8_batch_dev(svthip_ctx *ctx, const uint16_t *d_dst, c
  * (search_norestore_seg :1884-1896, search_wiener_seg :1742-1824) and av1_loop_restoration_filter_frame (EbRestoration.c:1283-1341) for
  * units of type RESTORE_NONE and RESTORE_WIENER, 8 and 10 bits, one tile (the reference's whole_frame_rect), no superres.  Every step is
  * integer arithmetic, the solve included, and every result is the reference's bit for bit.
- * NOT covered, and staying on the host: rest_finish_search (bit counts and the double-precision RD decisions, which consume what these
- * entries produce), 12-bit video (get_conv_params_wiener changes round_0 there); CDEF is the block above, and its output planes are cdef[].  Self-guided restoration (search_sgrproj_seg,
- * RESTORE_SGRPROJ units) is the next block.
+ * NOT covered: 12-bit video (get_conv_params_wiener changes round_0 there); CDEF is the block above, and its output planes are cdef[].
+ * Self-guided restoration (search_sgrproj_seg, RESTORE_SGRPROJ units) is the next block; rest_finish_search (the bit counts and the
+ * double-precision RD decisions, which consume what these entries produce) is the block after it.
  *
  *   svthip_lr_picture   device pointers to sample (0, 0) of the CDEF'd planes (the pictures restoration filters: what
  *                       svthip_av1_[highbd_]cdef_frame_dev wrote, or a host CDEF's upload), the deblocked planes
@@ -1188,7 +1188,7 @@ int32_t svthip_av1_highbd_loop_restoration_filter_frame_dev(svthip_ctx *ctx, con
  * on the svthip_lr_picture, unit geometry and per-unit indexing of the Wiener block above; 8 and 10 bits.  Every result is the reference's
  * bit for bit: the filter is integer arithmetic, the five sums of the projection are exact integers (the reference adds them in double,
  * where they are exact too), and the 2 x 2 solve is IEEE double in the reference's order of operations without fused multiply-adds.
- * NOT covered, and staying on the host: rest_finish_search, 12-bit video, superres, more than one tile.
+ * NOT covered: 12-bit video, superres, more than one tile.  rest_finish_search is the next block.
  *
  * Two geometries.  The search filters a unit in processing units (64 x 64 luma, 32 x 32 chroma) anchored at the unit's corner and reads
  * its 3-sample border from the CDEF'd plane itself (apply_sgr :602-625).  The unit filter and its SSE trial work stripe by stripe with
@@ -1258,6 +1258,76 @@ int32_t svthip_av1_lr_filter_frame_dev(svthip_ctx *ctx, const svthip_lr_picture 
 int32_t svthip_av1_highbd_lr_filter_frame_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, void *const d_out[3],
                                               const uint32_t out_stride[3], uint32_t plane_start, uint32_t plane_end, uint32_t bit_depth,
                                               const uint8_t *d_unit_type, const int16_t *d_taps, const int32_t *d_sgrproj, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The restoration decision: rest_finish_search (Codec/EbRestorationPick.c:1971-2040, called at Codec/EbRestProcess.c:307) on the tables the
+ * two searches above leave on the device, and the whole restoration stage in one call.  Per plane the reference walks the units in raster
+ * order once per frame type: RESTORE_NONE (search_norestore_finish :1897-1909), RESTORE_WIENER (search_wiener_finish :1825-1883),
+ * RESTORE_SGRPROJ (search_sgrproj_finish :1708-1740) and, for a plane of more than one unit, RESTORE_SWITCHABLE (search_switchable
+ * :1486-1547); the plane takes the first minimum of the walks' costs (:2011-2026) and every unit the type that walk gave it
+ * (copy_unit_info :2032-2036).  Bit counts are count_wiener_bits (:1107-1143), count_sgrproj_bits (:673-688) and
+ * aom_count_primitive_refsubexpfin (Codec/EbEntropyCoding.c:3488-3540), integer; every cost is RDCOST_DBL (EbRestoration.h:387-389)
+ * evaluated in IEEE double in the reference's order without fused multiply-adds, so ties and roundings fall as they do there.  Bits are
+ * summed in 64 bits (the reference adds a cost and a shifted count in 32 bits first: the same number while it stays below 2^31).
+ * NOT covered: 12-bit video, superres, more than one tile, force_restore_type (a compile-time constant equal to RESTORE_TYPES in the
+ * reference), writing the restoration syntax.
+ *
+ *   svthip_rest_finish_rates    HOST memory, read during the call: rdmult = full_lambda (Codec/EbEncDecProcess.c:1780-1783) and
+ *                               md_rate_estimation_ptr->{wiener,sgrproj,switchable}RestoreFacBits.
+ *   svthip_rest_finish_result   one per plane, indexed by frame type (3 = RESTORE_SWITCHABLE): rsc->sse and rsc->bits after that walk, its
+ *                               cost, the plane's frame_restoration_type and the number of walks tried (3 for a plane of one unit, else
+ *                               4); entries at or above n_tried are 0.
+ *
+ * svthip_rest_finish_search_dev   rest_finish_search for planes [plane_start, plane_end), one workgroup per plane, on the caller's stream with
+ *     no host synchronisation.  Inputs in the layouts the searches write: d_wiener_sse[unit][2] and d_taps[unit][16] of
+ *     svthip_av1_[highbd_]search_wiener_dev, d_sgr_sse[unit] and d_sgrproj[unit][4] of svthip_av1_[highbd_]search_sgrproj_dev; units are
+ *     indexed as everywhere above, unit_base[4] from svthip_lr_unit_geometry, and raster order is index order, so no picture is needed.
+ *     Outputs: d_unit_type[unit], which is what svthip_av1_[highbd_]lr_filter_frame_dev reads (all 0 in a plane whose frame type is
+ *     RESTORE_NONE: the frame filter, which writes out of place, then copies that plane, where the reference leaves it unfiltered);
+ *     d_result[plane]; d_best_rtype[unit][4] (may be null): best_rtype of the WIENER, SGRPROJ and SWITCHABLE walks (0 for a walk not
+ *     tried), then 0.  Nothing is written for planes outside the range.  The bitstream needs d_unit_type, d_result[].frame_type and the
+ *     coefficient arrays.
+ *     Refused ON THE DEVICE, counted once per unit in the context's refusal counter (svthip_inter_pred_refused reports and clears it), as
+ *     the frame filter refuses such units: data the reference's uint16_t casts would scramble -- a counted tap (win 5 leaves tap 0 out)
+ *     outside WIENER_FILT_TAPn_MINV..MAXV on a unit that is not rejected (Wiener SSE INT64_MAX), a set above 15, an xqd outside
+ *     SGRPROJ_PRJ_MIN..MAX.  The plane of such a unit gets frame type RESTORE_NONE, all unit types and best_rtype 0 and an all-zero result
+ *     (n_tried 0).
+ * svthip_lr_pick_workspace_bytes   bytes of d_work of the one-call entry: both searches' workspaces and the tables between the stages; 0 for
+ *     a size or unit size the entries refuse.
+ * svthip_av1_[highbd_]pick_filter_restoration_dev   restoration_seg_search + rest_finish_search + av1_loop_restoration_filter_frame for the
+ *     three planes of a picture on one stream with no host synchronisation: the Wiener search with its bound of trials (n_steps = 0, after
+ *     which no unit is pending), the self-guided search, the decision, the frame filter of all three planes into d_out.  It launches what
+ *     those four entries launch and nothing else.  Outputs: d_out, d_unit_type[unit], d_taps[unit][16], d_sgrproj[unit][4], d_result[3].
+ *     d_work: svthip_lr_pick_workspace_bytes bytes, 8-byte aligned.
+ * Refused with svthip_last_error text and without a launch: a null pointer (d_best_rtype may be null), plane_start >= plane_end or
+ * plane_end > 3, a unit_base that does not ascend or a plane in range with no unit, arrays not aligned to their element, a negative
+ * rdmult or cost; the one-call entries refuse what the search and frame-filter entries refuse. */
+#define SVTHIP_RESTORE_SWITCHABLE 3
+
+typedef struct svthip_rest_finish_rates {
+    int32_t rdmult;
+    int32_t wiener_cost[2], sgrproj_cost[2], switchable_cost[3];
+} svthip_rest_finish_rates;
+
+typedef struct svthip_rest_finish_result {
+    int64_t sse[4], bits[4];
+    double cost[4];
+    int32_t frame_type;
+    int32_t n_tried;
+} svthip_rest_finish_result;
+
+size_t svthip_lr_pick_workspace_bytes(uint32_t width, uint32_t height, const uint32_t unit_size[3]);
+int32_t svthip_rest_finish_search_dev(svthip_ctx *ctx, const svthip_rest_finish_rates *rates, const uint32_t unit_base[4], uint32_t plane_start,
+                                      uint32_t plane_end, const int64_t *d_wiener_sse, const int16_t *d_taps, const int64_t *d_sgr_sse,
+                                      const int32_t *d_sgrproj, uint8_t *d_unit_type, uint8_t *d_best_rtype,
+                                      svthip_rest_finish_result *d_result, void *stream);
+int32_t svthip_av1_pick_filter_restoration_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, const svthip_rest_finish_rates *rates,
+                                               void *d_work, void *const d_out[3], const uint32_t out_stride[3], uint8_t *d_unit_type,
+                                               int16_t *d_taps, int32_t *d_sgrproj, svthip_rest_finish_result *d_result, void *stream);
+int32_t svthip_av1_highbd_pick_filter_restoration_dev(svthip_ctx *ctx, const svthip_lr_picture *picture, uint32_t bit_depth,
+                                                      const svthip_rest_finish_rates *rates, void *d_work, void *const d_out[3],
+                                                      const uint32_t out_stride[3], uint8_t *d_unit_type, int16_t *d_taps, int32_t *d_sgrproj,
+                                                      svthip_rest_finish_result *d_result, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * AV1 film-grain synthesis: av1_add_film_grain (Codec/EbEncDecProcess.c:2001-2069) -> av1_add_film_grain_run

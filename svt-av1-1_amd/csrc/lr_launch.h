@@ -44,5 +44,18 @@ hipError_t launch_sgr_trial(const svthip_lr_picture& pic, int plane_start, int p
 SVTHIP_LOCAL hipError_t launch_sgr_filter_frame(const svthip_lr_picture& pic, void* const out[3], const uint32_t out_stride[3], int plane_start,
                                                 int plane_end, int bd, const uint8_t* unit_type, const int32_t* sgrproj, uint32_t* refused,
                                                 hipStream_t s);
+// lr_finish.hip: the restoration decision (rest_finish_search) -- the walks over the searches' tables, the frame type and the unit types of
+// each plane; and the restoration stage as one sequence of the launches above and this one (kernel: lr_finish_kernels.h)
+struct LrPickWorkspace {   // byte offsets into the caller's workspace, and its size
+    size_t wiener, sgr, wiener_sse, sgr_sse, n_trials, pending, total;
+};
+SVTHIP_LOCAL LrPickWorkspace lr_pick_workspace(uint32_t width, uint32_t height, const uint32_t unit_size[3]);
+SVTHIP_LOCAL hipError_t launch_rest_finish(const svthip_rest_finish_rates& rates, const uint32_t unit_base[4], int plane_start, int plane_end,
+                                           const int64_t* wiener_sse, const int16_t* taps, const int64_t* sgr_sse, const int32_t* sgrproj,
+                                           uint8_t* unit_type, uint8_t* best_rtype, svthip_rest_finish_result* result, uint32_t* refused,
+                                           hipStream_t s);
+SVTHIP_LOCAL hipError_t launch_lr_pick_filter(const svthip_lr_picture& pic, int bd, const svthip_rest_finish_rates& rates, void* work,
+                                              void* const out[3], const uint32_t out_stride[3], uint8_t* unit_type, int16_t* taps, int32_t* sgrproj,
+                                              svthip_rest_finish_result* result, uint32_t* refused, hipStream_t s);
 
 }  // namespace svthip

@@ -1,6 +1,6 @@
 // svt-av1-1_amd/csrc/lr_wiener.hip -- Wiener loop restoration on the device, host side: the unit geometry through the ABI, the workspace,
 // the launches of the kernels of lr_wiener_kernels.h, the whole search and the frame filter of the three unit types.  The contract is in
-// include/svtav1_hip.h.  Not here: rest_finish_search, CDEF, 12 bits, superres, more than one tile.
+// include/svtav1_hip.h.  Not here: rest_finish_search (lr_finish.hip), CDEF (cf_cdef.hip), 12 bits, superres, more than one tile.
 #include "lr_launch.h"
 
 #include "lr_wiener_kernels.h"

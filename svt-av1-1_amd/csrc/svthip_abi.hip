@@ -870,6 +870,39 @@ int32_t sgr_trial_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, uint32_t 
     return SVTHIP_OK;
 }
 
+// the decision's rate tables, host memory: nothing negative
+int32_t check_rest_finish_rates(const svthip_rest_finish_rates* r)
+{
+    TRY(check_non_null({r}));
+    const int32_t v[8] = {r->rdmult, r->wiener_cost[0], r->wiener_cost[1], r->sgrproj_cost[0], r->sgrproj_cost[1], r->switchable_cost[0],
+                          r->switchable_cost[1], r->switchable_cost[2]};
+    for (int i = 0; i < 8; i++)
+        if (v[i] < 0) return fail(SVTHIP_ERR_BAD_PARAMETER, i ? "a restoration cost is negative (%d)" : "rdmult is negative (%d)", (int)v[i]);
+    return SVTHIP_OK;
+}
+
+int32_t lr_pick_filter_entry(svthip_ctx* ctx, const svthip_lr_picture* pic, int bd, const svthip_rest_finish_rates* rates, void* d_work,
+                             void* const d_out[3], const uint32_t out_stride[3], uint8_t* d_unit_type, int16_t* d_taps, int32_t* d_sgrproj,
+                             svthip_rest_finish_result* d_result, void* stream)
+{
+    TRY(check_lr_args(pic, bd, true, 0, 3));
+    TRY(check_rest_finish_rates(rates));
+    TRY(check_non_null({d_work, d_out, out_stride, d_unit_type, d_taps, d_sgrproj, d_result}));
+    if (!aligned({d_work, d_result}, 8) || !aligned(d_sgrproj, 4) || !aligned(d_taps, 2))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_work and d_result must be 8-byte, d_sgrproj 4-byte, d_taps 2-byte aligned");
+    for (uint32_t p = 0; p < 3; p++) {
+        TRY(check_non_null({d_out[p]}));
+        if (out_stride[p] < (p ? pic->width / 2 : pic->width))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "output stride of plane %d is smaller than its width", (int)p);
+        if (bd > 8 && !aligned(d_out[p], 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
+    }
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
+    HIP_TRY(svthip::launch_lr_pick_filter(*pic, bd, *rates, d_work, d_out, out_stride, d_unit_type, d_taps, d_sgrproj, d_result, d_refused, s));
+    return SVTHIP_OK;
+}
+
 // The CDEF entries: one check of the picture for all of them.  The source planes are looked at by the search entries, the output planes
 // [plane_start, plane_end) by the frame entries.
 int32_t check_cdef_picture(const svthip_cdef_picture* pic, int bd, bool search, uint32_t plane_start, uint32_t plane_end)
@@ -1917,6 +1950,57 @@ int32_t svthip_av1_highbd_lr_filter_frame_dev(svthip_ctx* ctx, const svthip_lr_p
     TRY(enter(ctx));
     TRY(check_bit_depth_10(bit_depth));
     return lr_filter_frame_entry(ctx, picture, d_out, out_stride, plane_start, plane_end, 10, d_unit_type, d_taps, d_sgrproj, true, stream);
+}
+
+size_t svthip_lr_pick_workspace_bytes(uint32_t width, uint32_t height, const uint32_t unit_size[3])
+{
+    if (!unit_size || width == 0 || height == 0 || (width | height) % 8 != 0 || width > 16384 || height > 16384) return 0;
+    for (int p = 0; p < 3; p++)
+        if (unit_size[p] != 64 && unit_size[p] != 128 && unit_size[p] != 256) return 0;
+    return svthip::lr_pick_workspace(width, height, unit_size).total;
+}
+
+int32_t svthip_rest_finish_search_dev(svthip_ctx* ctx, const svthip_rest_finish_rates* rates, const uint32_t unit_base[4], uint32_t plane_start,
+                                      uint32_t plane_end, const int64_t* d_wiener_sse, const int16_t* d_taps, const int64_t* d_sgr_sse,
+                                      const int32_t* d_sgrproj, uint8_t* d_unit_type, uint8_t* d_best_rtype, svthip_rest_finish_result* d_result,
+                                      void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_rest_finish_rates(rates));
+    TRY(check_non_null({unit_base, d_wiener_sse, d_taps, d_sgr_sse, d_sgrproj, d_unit_type, d_result}));
+    if (plane_start >= plane_end || plane_end > 3)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "planes [%u, %u) are empty or not within 0..3", (unsigned)plane_start, (unsigned)plane_end);
+    for (uint32_t p = 0; p < 3; p++) {
+        if (unit_base[p] > unit_base[p + 1]) return fail(SVTHIP_ERR_BAD_PARAMETER, "unit_base does not ascend at plane %d", (int)p);
+        if (p >= plane_start && p < plane_end && unit_base[p] == unit_base[p + 1])
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "plane %d has no unit", (int)p);
+    }
+    if (!aligned({d_wiener_sse, d_sgr_sse, d_result}, 8) || !aligned(d_sgrproj, 4) || !aligned(d_taps, 2))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_wiener_sse, d_sgr_sse and d_result must be 8-byte, d_sgrproj 4-byte, d_taps 2-byte aligned");
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
+    HIP_TRY(svthip::launch_rest_finish(*rates, unit_base, (int)plane_start, (int)plane_end, d_wiener_sse, d_taps, d_sgr_sse, d_sgrproj, d_unit_type,
+                                       d_best_rtype, d_result, d_refused, s));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_av1_pick_filter_restoration_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, const svthip_rest_finish_rates* rates, void* d_work,
+                                               void* const d_out[3], const uint32_t out_stride[3], uint8_t* d_unit_type, int16_t* d_taps,
+                                               int32_t* d_sgrproj, svthip_rest_finish_result* d_result, void* stream)
+{
+    TRY(enter(ctx));
+    return lr_pick_filter_entry(ctx, picture, 8, rates, d_work, d_out, out_stride, d_unit_type, d_taps, d_sgrproj, d_result, stream);
+}
+
+int32_t svthip_av1_highbd_pick_filter_restoration_dev(svthip_ctx* ctx, const svthip_lr_picture* picture, uint32_t bit_depth,
+                                                      const svthip_rest_finish_rates* rates, void* d_work, void* const d_out[3],
+                                                      const uint32_t out_stride[3], uint8_t* d_unit_type, int16_t* d_taps, int32_t* d_sgrproj,
+                                                      svthip_rest_finish_result* d_result, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return lr_pick_filter_entry(ctx, picture, 10, rates, d_work, d_out, out_stride, d_unit_type, d_taps, d_sgrproj, d_result, stream);
 }
 
 // ---------------------------------------------------------------- CDEF

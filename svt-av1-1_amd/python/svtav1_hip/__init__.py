@@ -23,9 +23,10 @@ from ._pred import (AV1_BLOCK_SIZES_WH, BI_PRED, CONVOLVE_COMPOUND_DESC_DTYPE, C
 from ._cfl import CFL_DECISION_DTYPE, CFL_DECISION_JOB_DTYPE, CFL_DESC_DTYPE, CFL_LUMA_SIZES_WH, Cfl
 from ._deblock import LF_MI_DTYPE, Deblocking, LfPicture, make_lf_picture
 from ._cdef import CDEF_PICK_MAX_FB, CDEF_RESULT_DTYPE, Cdef, CdefPicture, cdef_filter_blocks, make_cdef_picture
-from ._restoration import (RESTORE_NONE, RESTORE_SGRPROJ, RESTORE_WIENER, SGRPROJ_DETAIL_DTYPE, SGRPROJ_PARAMS, WIENER_WALK_STATE_DTYPE,
-                           LrPicture, Restoration, lr_unit_geometry, lr_unit_sizes, lr_workspace_bytes, make_lr_picture,
-                           sgrproj_walk_max_trials, sgrproj_workspace_bytes, wiener_walk_max_trials)
+from ._restoration import (RESTORE_NONE, RESTORE_SGRPROJ, RESTORE_SWITCHABLE, RESTORE_WIENER, SGRPROJ_DETAIL_DTYPE, SGRPROJ_PARAMS,
+                           WIENER_WALK_STATE_DTYPE, LrPicture, Restoration, lr_pick_workspace_bytes, lr_unit_geometry, lr_unit_sizes,
+                           lr_workspace_bytes, make_lr_picture, rest_finish_rates_dtype, rest_finish_result_dtype, sgrproj_walk_max_trials,
+                           sgrproj_workspace_bytes, wiener_walk_max_trials)
 from ._grain import FILM_GRAIN_PARAMS_BYTES, FILM_GRAIN_TABLES_BYTES, FilmGrain, film_grain_param_offsets, film_grain_params
 from ._md import (MD_FAST_CHROMA_QUARTER, MD_FAST_INVALID, MD_FAST_LUMA_GIVEN, MD_FAST_MAX_BUFFERS, MD_FAST_MAX_CANDIDATES, MD_FAST_SKIP_DISTORTION,
                   MD_FAST_TYPE_INTER, MD_IFS_REFUSED, MD_IFS_SEARCH_FAST, MD_IFS_SEARCH_FULL, InterpFilterSearch, ModeDecisionFast, md_fast_desc_dtype,

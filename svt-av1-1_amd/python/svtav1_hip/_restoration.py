@@ -1,7 +1,8 @@
 """Loop restoration, pointer marshalling only.  Wiener: svthip_av1_[highbd_]wiener_stats_dev, svthip_wiener_solve_dev, .._wiener_trial_sse_dev,
 svthip_wiener_walk_init_dev / _step_dev, .._search_wiener_dev, .._loop_restoration_filter_frame_dev.  Self-guided:
 svthip_av1_[highbd_]selfguided_restoration_dev, svthip_sgrproj_solve_dev, svthip_sgrproj_walk_table_dev, .._search_sgrproj_dev,
-.._sgrproj_trial_sse_dev, .._lr_filter_frame_dev."""
+.._sgrproj_trial_sse_dev, .._lr_filter_frame_dev.  The decision: svthip_rest_finish_search_dev, and the whole stage in one call:
+svthip_av1_[highbd_]pick_filter_restoration_dev."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,6 +12,7 @@ import numpy as np
 from ._core import _check, _hbd, _picture_ref, lib
 
 RESTORE_NONE, RESTORE_WIENER, RESTORE_SGRPROJ = 0, 1, 2
+RESTORE_SWITCHABLE = 3
 WIENER_WALK_STATE_DTYPE = np.dtype([("err", "<i8"), ("taps", "<i2", (16,)), ("step", "i1"), ("filt", "i1"), ("tap", "i1"), ("dir", "i1"), ("skip", "i1"),
                                     ("first_tap", "i1"), ("started", "i1"), ("done", "u1"), ("n_trials", "<i4"), ("reserved", "<i4")])
 assert WIENER_WALK_STATE_DTYPE.itemsize == 56
@@ -71,6 +73,33 @@ def sgrproj_walk_max_trials():
     return int(lib().svthip_sgrproj_walk_max_trials())
 
 
+def lr_pick_workspace_bytes(width, height, unit_size=None):
+    """bytes of d_work for av1_pick_filter_restoration_dev; 0 for a size the entries refuse"""
+    return int(lib().svthip_lr_pick_workspace_bytes(width, height, (C.c_uint32 * 3)(*(unit_size or lr_unit_sizes(width, height)))))
+
+
+def rest_finish_rates_dtype() -> np.dtype:
+    """svthip_rest_finish_rates, 32 bytes, host memory"""
+    return np.dtype([("rdmult", "<i4"), ("wiener_cost", "<i4", (2,)), ("sgrproj_cost", "<i4", (2,)), ("switchable_cost", "<i4", (3,))])
+
+
+def rest_finish_result_dtype() -> np.dtype:
+    """svthip_rest_finish_result, 104 bytes, one per plane; sse, bits and cost are indexed by frame type"""
+    return np.dtype([("sse", "<i8", (4,)), ("bits", "<i8", (4,)), ("cost", "<f8", (4,)), ("frame_type", "<i4"), ("n_tried", "<i4")])
+
+
+def _rates_ref(rates):
+    """a pointer to one svthip_rest_finish_rates from a record of rest_finish_rates_dtype(), a mapping or (rdmult, wiener, sgrproj, switchable);
+    the second value keeps the memory alive for the call"""
+    if rates is None:
+        return None, None
+    if isinstance(rates, dict):
+        rates = (rates["rdmult"], rates["wiener_cost"], rates["sgrproj_cost"], rates["switchable_cost"])
+    a = np.zeros(1, rest_finish_rates_dtype())
+    a[0] = tuple(rates) if not isinstance(rates, np.void) else rates
+    return a.ctypes.data, a
+
+
 class Restoration:
     """the loop-restoration entries as Context methods; bit_depth selects the 8-bit or the highbd entry"""
 
@@ -125,3 +154,21 @@ class Restoration:
         out = (C.c_void_p * 3)(*d_out) if d_out is not None else None
         strides = (C.c_uint32 * 3)(*out_stride) if out_stride is not None else None
         _check(f(self._h, _picture_ref(picture), out, strides, plane_start, plane_end, *bd, d_unit_type, d_taps, d_sgrproj, stream))
+
+    def rest_finish_search_dev(self, rates, unit_base, plane_start, plane_end, d_wiener_sse, d_taps, d_sgr_sse, d_sgrproj, d_unit_type, d_result,
+                               d_best_rtype=None, stream=None):
+        """rest_finish_search on the searches' tables: unit types, frame types and results of planes [plane_start, plane_end)"""
+        r, keep = _rates_ref(rates)
+        base = (C.c_uint32 * 4)(*unit_base) if unit_base is not None else None
+        _check(lib().svthip_rest_finish_search_dev(self._h, r, base, plane_start, plane_end, d_wiener_sse, d_taps, d_sgr_sse, d_sgrproj, d_unit_type,
+                                                   d_best_rtype, d_result, stream))
+        del keep
+
+    def av1_pick_filter_restoration_dev(self, picture, rates, d_work, d_out, out_stride, d_unit_type, d_taps, d_sgrproj, d_result, bit_depth=8, stream=None):
+        """both searches, the decision and the frame filter of the three planes in one call"""
+        f, bd = _hbd(bit_depth, "pick_filter_restoration_dev")
+        r, keep = _rates_ref(rates)
+        out = (C.c_void_p * 3)(*d_out) if d_out is not None else None
+        strides = (C.c_uint32 * 3)(*out_stride) if out_stride is not None else None
+        _check(f(self._h, _picture_ref(picture), *bd, r, d_work, out, strides, d_unit_type, d_taps, d_sgrproj, d_result, stream))
+        del keep
