@@ -1,0 +1,163 @@
+// svt-av1-1_amd/csrc/cf_abi.hip -- C-ABI glue of CDEF: the exported entries that launch through
+// cf_launch.h, with their validators and shared bodies.  Host code only.
+#include "svthip_glue.h"
+#include "cf_launch.h"
+
+namespace {
+
+// The CDEF entries: one check of the picture for all of them.  The source planes are looked at by the search entries, the output planes
+// [plane_start, plane_end) by the frame entries.
+int32_t check_cdef_picture(const svthip_cdef_picture* pic, int bd, bool search, uint32_t plane_start, uint32_t plane_end)
+{
+    TRY(check_non_null({pic}));
+    TRY(check_filter_bit_depth(bd));
+    if (plane_start > plane_end || plane_end > 3)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "planes [%u, %u) are not within 0..3", (unsigned)plane_start, (unsigned)plane_end);
+    TRY(check_filter_picture_size(pic->width, pic->height));
+    TRY(check_non_null({pic->d_skip}));
+    if (pic->skip_stride < pic->width / 4) return fail(SVTHIP_ERR_BAD_PARAMETER, "skip_stride is smaller than width / 4 = %u", (unsigned)(pic->width / 4));
+    const size_t b = bd > 8 ? 2 : 1;
+    // the deblocked planes: all three for the search; for the frame filter luma (chroma directions come from it) and the planes in range
+    for (uint32_t p = 0; p < 3; p++) {
+        if (!search && p != 0 && (p < plane_start || p >= plane_end)) continue;
+        const FilterPlane planes[2] = {{pic->deblocked[p], pic->deblocked_stride[p]}, {pic->source[p], pic->source_stride[p]}};
+        TRY(check_filter_planes(p, p ? pic->width / 2 : pic->width, bd, planes, search ? 2 : 1));
+    }
+    for (uint32_t p = search ? 3 : plane_start; p < plane_end; p++) {
+        const uint32_t pw = p ? pic->width / 2 : pic->width, ph = p ? pic->height / 2 : pic->height;
+        TRY(check_non_null({pic->out[p]}));
+        if (pic->out_stride[p] < pw) return fail(SVTHIP_ERR_BAD_PARAMETER, "output stride of plane %d is smaller than its width %u", (int)p, (unsigned)pw);
+        if (bd > 8 && !aligned(pic->out[p], 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned");
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(pic->out[p]), o1 = o0 + (((size_t)ph - 1) * pic->out_stride[p] + pw) * b;
+        for (uint32_t q = 0; q < 3; q++) {
+            const uint32_t qw = q ? pic->width / 2 : pic->width, qh = q ? pic->height / 2 : pic->height;
+            const uintptr_t d0 = reinterpret_cast<uintptr_t>(pic->deblocked[q]), d1 = d0 + (((size_t)qh - 1) * pic->deblocked_stride[q] + qw) * b;
+            if (d0 && o0 < d1 && d0 < o1) return fail(SVTHIP_ERR_BAD_PARAMETER, "output plane %d overlaps deblocked plane %d: the filter works out of place", (int)p, (int)q);
+        }
+    }
+    return SVTHIP_OK;
+}
+
+int32_t check_cdef_tables(const void* d_mse, const void* d_fb_counted, uint32_t base_qindex)
+{
+    TRY(check_non_null({d_mse, d_fb_counted}));
+    if (!aligned(d_mse, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_mse must be 8-byte aligned");
+    if (base_qindex > 255) return fail(SVTHIP_ERR_BAD_PARAMETER, "base_qindex must be 0..255 (got %u)", (unsigned)base_qindex);
+    return SVTHIP_OK;
+}
+
+int32_t check_cdef_pick(const void* d_mse, const void* d_fb_counted, uint32_t nhfb, uint32_t nvfb, uint32_t base_qindex, int bd, const void* d_result,
+                        const void* d_fb_strength)
+{
+    TRY(check_cdef_tables(d_mse, d_fb_counted, base_qindex));
+    TRY(check_non_null({d_result, d_fb_strength}));
+    TRY(check_filter_bit_depth(bd));
+    if (!aligned(d_result, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_result must be 4-byte aligned");
+    if (nhfb == 0 || nvfb == 0 || nhfb > 256 || nvfb > 256 || nhfb * nvfb > SVTHIP_CDEF_PICK_MAX_FB)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "the pick takes 1..%d filter blocks (got %u x %u)", SVTHIP_CDEF_PICK_MAX_FB, (unsigned)nhfb, (unsigned)nvfb);
+    return SVTHIP_OK;
+}
+
+int32_t cdef_search_mse_entry(svthip_ctx* ctx, const svthip_cdef_picture* pic, uint32_t base_qindex, int bd, uint64_t* d_mse, uint8_t* d_fb_counted,
+                              void* stream)
+{
+    TRY(check_cdef_picture(pic, bd, true, 0, 3));
+    TRY(check_cdef_tables(d_mse, d_fb_counted, base_qindex));
+    HIP_TRY(svthip::launch_cdef_search_mse(*pic, (int)base_qindex, bd, d_mse, d_fb_counted, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t cdef_search_entry(svthip_ctx* ctx, const svthip_cdef_picture* pic, uint32_t base_qindex, int bd, uint64_t* d_mse, uint8_t* d_fb_counted,
+                          svthip_cdef_result* d_result, int8_t* d_fb_strength, void* stream)
+{
+    TRY(check_cdef_picture(pic, bd, true, 0, 3));
+    const uint32_t nhfb = (pic->width / 4 + 15) / 16, nvfb = (pic->height / 4 + 15) / 16;
+    TRY(check_cdef_pick(d_mse, d_fb_counted, nhfb, nvfb, base_qindex, bd, d_result, d_fb_strength));
+    hipStream_t s = call_stream(ctx, stream);
+    HIP_TRY(svthip::launch_cdef_search_mse(*pic, (int)base_qindex, bd, d_mse, d_fb_counted, s));
+    HIP_TRY(svthip::launch_cdef_pick(d_mse, d_fb_counted, nhfb * nvfb, (int)base_qindex, bd, d_result, d_fb_strength, s));
+    return SVTHIP_OK;
+}
+
+int32_t cdef_frame_entry(svthip_ctx* ctx, const svthip_cdef_picture* pic, const svthip_cdef_result* d_result, const int8_t* d_fb_strength,
+                         uint32_t ps, uint32_t pe, int bd, void* stream)
+{
+    TRY(check_cdef_picture(pic, bd, false, ps, pe));
+    TRY(check_non_null({d_result, d_fb_strength}));
+    if (!aligned(d_result, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_result must be 4-byte aligned");
+    HIP_TRY(svthip::launch_cdef_frame(*pic, d_result, d_fb_strength, (int)ps, (int)pe, bd, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---------------------------------------------------------------- CDEF
+
+int32_t svthip_av1_cdef_search_mse_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, uint32_t base_qindex, uint64_t* d_mse,
+                                       uint8_t* d_fb_counted, void* stream)
+{
+    TRY(enter(ctx));
+    return cdef_search_mse_entry(ctx, picture, base_qindex, 8, d_mse, d_fb_counted, stream);
+}
+
+int32_t svthip_av1_highbd_cdef_search_mse_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, uint32_t base_qindex, uint32_t bit_depth,
+                                              uint64_t* d_mse, uint8_t* d_fb_counted, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return cdef_search_mse_entry(ctx, picture, base_qindex, 10, d_mse, d_fb_counted, stream);
+}
+
+int32_t svthip_cdef_pick_strengths_dev(svthip_ctx* ctx, const uint64_t* d_mse, const uint8_t* d_fb_counted, uint32_t nhfb, uint32_t nvfb,
+                                       uint32_t base_qindex, uint32_t bit_depth, svthip_cdef_result* d_result, int8_t* d_fb_strength, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_cdef_pick(d_mse, d_fb_counted, nhfb, nvfb, base_qindex, (int)bit_depth, d_result, d_fb_strength));
+    HIP_TRY(svthip::launch_cdef_pick(d_mse, d_fb_counted, nhfb * nvfb, (int)base_qindex, (int)bit_depth, d_result, d_fb_strength, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_av1_cdef_search_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, uint32_t base_qindex, uint64_t* d_mse, uint8_t* d_fb_counted,
+                                   svthip_cdef_result* d_result, int8_t* d_fb_strength, void* stream)
+{
+    TRY(enter(ctx));
+    return cdef_search_entry(ctx, picture, base_qindex, 8, d_mse, d_fb_counted, d_result, d_fb_strength, stream);
+}
+
+int32_t svthip_av1_highbd_cdef_search_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, uint32_t base_qindex, uint32_t bit_depth,
+                                          uint64_t* d_mse, uint8_t* d_fb_counted, svthip_cdef_result* d_result, int8_t* d_fb_strength, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return cdef_search_entry(ctx, picture, base_qindex, 10, d_mse, d_fb_counted, d_result, d_fb_strength, stream);
+}
+
+int32_t svthip_av1_cdef_frame_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, const svthip_cdef_result* d_result,
+                                  const int8_t* d_fb_strength, uint32_t plane_start, uint32_t plane_end, void* stream)
+{
+    TRY(enter(ctx));
+    return cdef_frame_entry(ctx, picture, d_result, d_fb_strength, plane_start, plane_end, 8, stream);
+}
+
+int32_t svthip_av1_highbd_cdef_frame_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, const svthip_cdef_result* d_result,
+                                         const int8_t* d_fb_strength, uint32_t plane_start, uint32_t plane_end, uint32_t bit_depth, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return cdef_frame_entry(ctx, picture, d_result, d_fb_strength, plane_start, plane_end, 10, stream);
+}
+
+int32_t svthip_cdef_dist_8x8_batch_dev(svthip_ctx* ctx, const uint16_t* d_dst, const uint16_t* d_src, uint32_t n, uint32_t coeff_shift,
+                                       uint64_t* d_out, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_non_null({d_dst, d_src, d_out}));
+    if (!aligned({d_dst, d_src}, 2) || !aligned(d_out, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_dst and d_src must be 2-byte, d_out 8-byte aligned");
+    if (coeff_shift > 2) return fail(SVTHIP_ERR_BAD_PARAMETER, "coeff_shift must be 0..2 (got %u)", (unsigned)coeff_shift);
+    HIP_TRY(svthip::launch_cdef_dist_8x8(d_dst, d_src, n, (int)coeff_shift, d_out, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,187 @@
+// svt-av1-1_amd/csrc/pa_abi.hip -- C-ABI glue of picture analysis: the exported entries that launch through
+// pa_launch.h, with their validators and shared bodies.  Host code only.
+#include "svthip_glue.h"
+#include "pa_launch.h"
+
+namespace {
+
+// what every picture-analysis entry that reads the full-resolution luma checks of its pictures: one geometry per launch, planes the kernels
+// may read as dwords
+int32_t check_pa_luma_pictures(const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, uint32_t min_dim)
+{
+    if (n_pics > SVTHIP_HME_MAX_JOBS) return fail(SVTHIP_ERR_BAD_PARAMETER, "at most %d pictures per call (got %u)", SVTHIP_HME_MAX_JOBS, (unsigned)n_pics);
+    const uint32_t w = pics[0].width, h = pics[0].height;
+    if ((w & 7) || (h & 7) || w < min_dim || h < min_dim)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be multiples of 8, at least %u (%ux%u)", (unsigned)min_dim, (unsigned)w, (unsigned)h);
+    if (!aligned(d_pool, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "the pool must be 4-byte aligned");
+    for (uint32_t j = 0; j < n_pics; j++) {
+        const svthip_pa_picture& p = pics[j];
+        if (p.width != w || p.height != h) return fail(SVTHIP_ERR_BAD_PARAMETER, "the pictures of one call must have equal dimensions (picture %d)", (int)j);
+        if (p.full_stride < w + 136u || (p.full_stride & 3u) || (p.full_offset & 3) || p.full_offset < 0)
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "full-resolution stride must be a multiple of 4 and >= width + 136, offset a multiple of 4 (picture %d)", (int)j);
+    }
+    return SVTHIP_OK;
+}
+
+// and what the entries that read chroma (and the 1/16 plane) check on top
+int32_t check_pa_stats_pictures(const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, const int64_t* chroma_offsets,
+                                uint32_t chroma_stride, bool reads_sixteenth, uint32_t min_dim = 16)
+{
+    TRY(check_pa_luma_pictures(d_pool, pics, n_pics, min_dim));
+    const uint32_t w = pics[0].width;
+    if ((chroma_stride & 1u) || chroma_stride < w / 2)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "chroma stride must be even and >= width/2 (got %u)", (unsigned)chroma_stride);
+    for (uint32_t j = 0; j < n_pics; j++) {
+        const svthip_pa_picture& p = pics[j];
+        if (reads_sixteenth && (p.sixteenth_stride < (w >> 2) + 32u || p.sixteenth_offset < 0))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "sixteenth stride must be >= width/4 + 32 (picture %d)", (int)j);
+        for (int c = 0; c < 2; c++)
+            if (chroma_offsets[2 * j + c] < 0 || (chroma_offsets[2 * j + c] & 1))
+                return fail(SVTHIP_ERR_BAD_PARAMETER, "chroma offsets must be even and not negative (picture %d)", (int)j);
+    }
+    return SVTHIP_OK;
+}
+
+// d_denoised of the noise entries: [n_pics][height][denoised_stride], rows written and read as 8-byte pieces
+int32_t check_pa_denoised(const uint8_t* d_denoised, uint32_t denoised_stride, uint32_t width)
+{
+    if (denoised_stride < width || (denoised_stride & 7u) || !aligned(d_denoised, 8))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_denoised must be 8-byte aligned, its stride a multiple of 8 and >= width (got %u)", (unsigned)denoised_stride);
+    return SVTHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---------------------------------------------------------------- planes, padding, the ME results in the reference's layout (pa_planes.hip)
+
+int32_t svthip_pa_derive_planes_dev(svthip_ctx* ctx, uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, int32_t want_quarter,
+                                    int32_t want_sixteenth, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics}));
+    for (uint32_t j = 0; j < n_pics; j++) {
+        const svthip_pa_picture& p = pics[j];
+        if ((p.width & 7) || (p.height & 7) || p.width == 0 || p.height == 0)
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be non-zero multiples of 8 (picture %d)", (int)j);
+        if (p.full_stride < (uint32_t)p.width + 136u || (p.full_stride & 3u) || (p.full_offset & 3))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "full-resolution stride must be a multiple of 4 and >= width + 136 (picture %d)", (int)j);
+        if (want_quarter && p.quarter_stride < (uint32_t)(p.width >> 1) + 64u)
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "quarter stride must be >= width/2 + 64 (picture %d)", (int)j);
+        if (want_sixteenth && p.sixteenth_stride < (uint32_t)(p.width >> 2) + 32u)
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "sixteenth stride must be >= width/4 + 32 (picture %d)", (int)j);
+    }
+    HIP_TRY(svthip::launch_pa_derive_planes(d_pool, pics, n_pics, want_quarter != 0, want_sixteenth != 0, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pad_plane_dev(svthip_ctx* ctx, void* d_plane, uint32_t stride, uint32_t width, uint32_t height, uint32_t pad_width,
+                             uint32_t pad_height, uint32_t sample_bytes, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_non_null({d_plane}));
+    if (sample_bytes != 1 && sample_bytes != 2) return fail(SVTHIP_ERR_BAD_PARAMETER, "sample_bytes must be 1 or 2 (got %d)", (int)sample_bytes);
+    if (width == 0 || height == 0 || stride < width + 2 * pad_width || width > 16384 || height > 16384 || pad_width > 1024 || pad_height > 1024)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "bad plane geometry (stride %d)", (int)stride);
+    if (sample_bytes == 2 && !aligned(d_plane, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit plane must be 2-byte aligned");
+    HIP_TRY(svthip::launch_pad_plane(d_plane, stride, (int)width, (int)height, (int)pad_width, (int)pad_height, (int)sample_bytes,
+                                     call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_me_results_to_ref_layout_dev(svthip_ctx* ctx, const svthip_me_cu_result* d_in, uint32_t n, svthip_me_cu_result_ref* d_out,
+                                            void* stream)
+{
+    TRY(enter(ctx));
+    if (n == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_in, d_out}));
+    HIP_TRY(svthip::launch_me_results_ref_layout(d_in, n, d_out, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+// ---------------------------------------------------------------- statistics, noise detection and denoising
+
+int32_t svthip_pa_block_stats_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics,
+                                  const int64_t* chroma_offsets, uint32_t chroma_stride, uint32_t sub_precision, uint8_t* d_y_mean,
+                                  uint16_t* d_variance, uint8_t* d_cb_mean, uint8_t* d_cr_mean, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics, chroma_offsets, d_y_mean, d_variance, d_cb_mean, d_cr_mean}));
+    if (sub_precision > 1) return fail(SVTHIP_ERR_BAD_PARAMETER, "sub_precision must be 0 (FULL) or 1 (SUB), got %u", (unsigned)sub_precision);
+    if (!aligned(d_variance, 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "the variance table must be 2-byte aligned");
+    TRY(check_pa_stats_pictures(d_pool, pics, n_pics, chroma_offsets, chroma_stride, false));
+    HIP_TRY(svthip::launch_pa_block_stats(d_pool, pics, chroma_offsets, n_pics, chroma_stride, (int)sub_precision, sb_count(pics[0].width, pics[0].height),
+                                          d_y_mean, d_variance, d_cb_mean, d_cr_mean, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_homogeneity_dev(svthip_ctx* ctx, const uint16_t* d_variance, uint32_t width, uint32_t height, uint32_t n_pics,
+                                  uint64_t* d_var_of_var32x32, uint8_t* d_homogeneous, uint32_t* d_picture, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_variance, d_var_of_var32x32, d_homogeneous, d_picture}));
+    if (n_pics > SVTHIP_HME_MAX_JOBS) return fail(SVTHIP_ERR_BAD_PARAMETER, "at most %d pictures per call (got %u)", SVTHIP_HME_MAX_JOBS, (unsigned)n_pics);
+    // a picture without a complete SB has nothing to take the low-variance percentage of (the reference divides by zero)
+    if ((width & 7) || (height & 7) || width < 64 || height < 64 || width > 65535 || height > 65535)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be multiples of 8, at least 64 (%ux%u)", (unsigned)width, (unsigned)height);
+    if (!aligned(d_variance, 2) || !aligned(d_var_of_var32x32, 8) || !aligned(d_picture, 4))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "d_variance must be 2-byte, d_var_of_var32x32 8-byte, d_picture 4-byte aligned");
+    HIP_TRY(svthip::launch_pa_homogeneity(d_variance, width, height, n_pics, sb_count(width, height), d_var_of_var32x32, d_homogeneous, d_picture,
+                                          call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_histograms_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics,
+                                 const int64_t* chroma_offsets, uint32_t chroma_stride, uint32_t* d_histogram, uint32_t* d_region_intensity,
+                                 uint32_t* d_average_intensity, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics, chroma_offsets, d_histogram, d_region_intensity, d_average_intensity}));
+    if (!aligned({d_histogram, d_region_intensity, d_average_intensity}, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "the output arrays must be 4-byte aligned");
+    TRY(check_pa_stats_pictures(d_pool, pics, n_pics, chroma_offsets, chroma_stride, true));
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(ensure_scratch(ctx, SLOT_PA_REGION_SUMS, svthip::pa_region_sum_bytes(SVTHIP_HME_MAX_JOBS)));  // 6 KB, sized once for the largest call
+    TRY(scratch_on_stream(ctx, s));
+    HIP_TRY(svthip::launch_pa_histograms(d_pool, pics, chroma_offsets, n_pics, chroma_stride, d_histogram, d_region_intensity, d_average_intensity,
+                                         slot_ptr<uint32_t>(ctx, SLOT_PA_REGION_SUMS), s));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_noise_detect_dev(svthip_ctx* ctx, const uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, uint32_t sub_precision,
+                                   uint8_t* d_denoised, uint32_t denoised_stride, uint64_t* d_sb_var, uint8_t* d_flat_noise, uint32_t* d_picture,
+                                   void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics, d_sb_var, d_flat_noise, d_picture}));
+    if (sub_precision > 1) return fail(SVTHIP_ERR_BAD_PARAMETER, "sub_precision must be 0 (FULL) or 1 (SUB), got %u", (unsigned)sub_precision);
+    if (!aligned(d_sb_var, 8) || !aligned(d_picture, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sb_var must be 8-byte, d_picture 4-byte aligned");
+    // a picture without a complete SB has no average noise variance (the reference divides by zero)
+    TRY(check_pa_luma_pictures(d_pool, pics, n_pics, 64));
+    if (d_denoised) TRY(check_pa_denoised(d_denoised, denoised_stride, pics[0].width));
+    HIP_TRY(svthip::launch_pa_noise_detect(d_pool, pics, n_pics, (int)sub_precision, sb_count(pics[0].width, pics[0].height), d_denoised, denoised_stride,
+                                           d_sb_var, d_flat_noise, d_picture, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_denoise_dev(svthip_ctx* ctx, uint8_t* d_pool, const svthip_pa_picture* pics, uint32_t n_pics, const int64_t* chroma_offsets,
+                              uint32_t chroma_stride, uint8_t* d_denoised, uint32_t denoised_stride, const uint8_t* d_flat_noise,
+                              const uint32_t* d_picture, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_pics == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_pool, pics, chroma_offsets, d_denoised, d_flat_noise, d_picture}));
+    if (!aligned(d_picture, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_picture must be 4-byte aligned");
+    TRY(check_pa_stats_pictures(d_pool, pics, n_pics, chroma_offsets, chroma_stride, false, 64));
+    TRY(check_pa_denoised(d_denoised, denoised_stride, pics[0].width));
+    HIP_TRY(svthip::launch_pa_denoise(d_pool, pics, chroma_offsets, n_pics, chroma_stride, sb_count(pics[0].width, pics[0].height), d_denoised,
+                                      denoised_stride, d_flat_noise, d_picture, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 """GPU: the state a svthip_ctx carries from one call to the next, each test on contexts of its own.
 
 A context keeps grow-only scratch slots, the SB-origin table of the host-pointer picture forms (slot 9, SLOT_SB_TABLE in
-svthip_abi.hip's `enum Slot`, whose order gives the slot numbers quoted here; rebuilt when the geometry changes), the stream that last used its scratch, and the inter-prediction refusal counter.  Every other GPU test shares one session
+svthip_glue.h's `enum Slot`, whose order gives the slot numbers quoted here; rebuilt when the geometry changes), the stream that last used its scratch, and the inter-prediction refusal counter.  Every other GPU test shares one session
 context in a fixed order, so none of them sees a call that follows a different one: another geometry, PU count, list count or stream,
 or an svthip_reserve.  Here every step of such sequences is compared bit-exactly with the oracle (the numpy restatement for inter
 prediction); expected results are computed once per (pictures, geometry, PU count, list count) and reused by every step that repeats
