@@ -560,6 +560,81 @@ int32_t svthip_pa_denoise_dev(svthip_ctx *ctx, uint8_t *d_pool, const svthip_pa_
                               const uint8_t *d_flat_noise, const uint32_t *d_picture, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The 10-bit picture forms: the crossings between the 8-bit front end (the entries above, motion estimation, mode decision) and the
+ * 16-bit svthip_av1_highbd_* / svthip_encode_tu16_batch_dev half of the library.  The reference keeps a 10-bit input picture as an
+ * 8-bit plane (sample >> 2) and a "2-bit" plane per component; the 2-bit plane comes in two layouts:
+ *   unpacked    one byte per sample, the two bits in bits 7..6 (the byte is (uint8_t)(sample << 6)), rows a stride apart;
+ *   compressed  (ten_bit_format == 1) four samples per byte, the first in bits 7..6, the fourth in bits 1..0, and the bytes SB-TILED:
+ *               the plane is cut into SBs of 64 x 64 luma (32 x 32 chroma) samples, clipped to the plane at its right and bottom edge,
+ *               in raster order; all bytes of an SB are contiguous, sb_w / 4 bytes per SB row.  With pw x ph the plane's dimensions,
+ *               the SB whose first sample is (sb_x, sb_y) starts at byte  sb_y * (pw / 4) + (sb_x / 4) * sb_h  of the plane and the
+ *               byte of its samples (sb_x + 4 i .. + 3, sb_y + r) is  r * (sb_w / 4) + i  further on (Codec/EbCodingLoop.c:2894-2923
+ *               in luma units: chroma at (sb_origin_y / 2) * (width / 8) + (sb_origin_x / 8) * (sb_height / 2), row stride sb_width / 8).
+ *               A plane holds pw * ph / 4 bytes and has no stride and no border.
+ *
+ * All five entries work on the three planes (Y, Cb, Cr) of n_pics 4:2:0 pictures of EQUAL dimensions in one launch, 1 <= n_pics <=
+ * SVTHIP_HME_MAX_JOBS; width and height are luma, multiples of 8, 8..16384.  A set of planes is a device base pointer and a HOST array
+ * of n_pics svthip_planes: offset[p] the offset of sample (0, 0) of plane p from the base, stride[p] its row stride, both in SAMPLES of
+ * the base's type (never negative, stride >= the plane's width).  Of a compressed set offset[p] is the byte offset of the plane's first
+ * byte and stride[p] is not read.  16-bit bases must be 2-byte aligned; nothing else has to be aligned: rows move as 16-byte accesses
+ * with a head and a tail wherever they start.  Only the width x height interiors are read and written, not one byte more. */
+typedef struct svthip_planes {
+    int64_t offset[3];    /* Y, Cb, Cr: sample (0, 0), in samples from the base pointer */
+    uint32_t stride[3];   /* in samples */
+    uint32_t reserved;
+} svthip_planes;
+
+/* EB_ENC_msbUnPack2D (C_DEFAULT/EbPackUnPack_C.c:127-151) over the interiors of Y, Cb and Cr, as the reference unpacks its 16-bit input
+ * (Codec/EbEncHandle.c:2954-2985): out8 = (uint8_t)(in >> 2), outn = (uint8_t)(in << 6).  Bits above bit 9 are not the caller's
+ * promise: the casts decide, 0xFFFF gives 0xFF and 0xC0.  With the 8-bit planes inside the picture pool this is the "upload the
+ * interiors" step of the front end's call order for 10-bit input.
+ * d_outn == NULL (outn is then not read): UnPack8BitData (:152-174), the copy extract8_bitdata_safe_sub makes of a 16-bit reference
+ * block for 8-bit mode decision (Av1UnPackReferenceBlock, Codec/EbInterPrediction.c:1447-1473).  Called once on a PADDED 16-bit reference
+ * -- width and height enlarged by the borders, the offsets those of the padded plane's first sample -- it leaves the 8-bit reference on
+ * which svthip_av1_inter_pred_batch_dev and the mode-decision entries are AV1InterPrediction10BitMD (:1477-), bit for bit -- wherever
+ * that function is defined: for the sub-8x8 chroma pieces of a block 4 wide its block copy leaves columns of the local buffer unwritten
+ * that the filter then reads (ASM_SSE2/EbPackUnPack_Intrinsic_SSE2.c:736-761 steps by four over a width of ten and rewinds by ten), so the
+ * reference's Cb / Cr there depend on an earlier call; this path gives the prediction from the samples that belong there. */
+int32_t svthip_pa_unpack_10bit_dev(svthip_ctx *ctx, const uint16_t *d_in16, const svthip_planes *in16, uint8_t *d_out8,
+                                   const svthip_planes *out8, uint8_t *d_outn, const svthip_planes *outn, uint32_t width,
+                                   uint32_t height, uint32_t n_pics, void *stream);
+
+/* EB_ENC_msbPack2D (C_DEFAULT/EbPackUnPack_C.c:12-38) for whole pictures, what Pack2D_SRC makes SB by SB of the 8-bit and unpacked
+ * 2-bit input for the 16-bit encode pass (Codec/EbCodingLoop.c:2941-2974): out16 = (in8 << 2) | ((inn >> 6) & 3); the low six bits of
+ * the 2-bit byte are ignored.  The reference passes strideCr and strideBitIncCr with the Cb planes (:2955-2957), which are equal to
+ * Cb's in every picture it allocates; this entry takes each plane's own stride. */
+int32_t svthip_pa_pack_10bit_dev(svthip_ctx *ctx, const uint8_t *d_in8, const svthip_planes *in8, const uint8_t *d_inn,
+                                 const svthip_planes *inn, uint16_t *d_out16, const svthip_planes *out16, uint32_t width,
+                                 uint32_t height, uint32_t n_pics, void *stream);
+
+/* CompressedPackmsb (C_DEFAULT/EbPackUnPack_C.c:44-86) for whole pictures, what CompressedPackLcu makes SB by SB of the 8-bit planes and
+ * the compressed 2-bit planes (layout above; Codec/EbCodingLoop.c:2888-2929).  The output is ordinary 16-bit planes. */
+int32_t svthip_pa_pack_10bit_compressed_dev(svthip_ctx *ctx, const uint8_t *d_in8, const svthip_planes *in8, const uint8_t *d_inn,
+                                            const svthip_planes *inn_compressed, uint16_t *d_out16, const svthip_planes *out16,
+                                            uint32_t width, uint32_t height, uint32_t n_pics, void *stream);
+
+/* PsnrCalculations (Codec/EbEncDecProcess.c:775-1133): d_sse[n_pics][3], the sums of squared differences of reconstruction and source
+ * over the interiors of Y, Cb and Cr as unsigned 64-bit numbers, left on the device (8-byte aligned; no host synchronisation).
+ * svthip_picture_sse_dev compares two 8-bit sets (:781-861).  svthip_highbd_picture_sse_dev compares a 16-bit set with a source in
+ * one of three forms (source_form):
+ *   SVTHIP_SSE_SRC_16BIT       d_src is uint16_t planes, d_srcn / srcn are not read;
+ *   SVTHIP_SSE_SRC_UNPACKED    d_src is the 8-bit planes, d_srcn the unpacked 2-bit planes (:1058-1124);
+ *   SVTHIP_SSE_SRC_COMPRESSED  d_src is the 8-bit planes, d_srcn the compressed 2-bit planes (:880-1054).
+ * The split forms pack in registers; no 16-bit source is written.  What the reference does with the sums, for a caller that has to
+ * reproduce it: it truncates each to uint32_t, and it stores the Cb sum in cr_sse and the Cr sum in cb_sse (:858-860, :1129-1131).
+ * d_sse keeps the full sums in plane order Y, Cb, Cr. */
+#define SVTHIP_SSE_SRC_16BIT 0
+#define SVTHIP_SSE_SRC_UNPACKED 1
+#define SVTHIP_SSE_SRC_COMPRESSED 2
+int32_t svthip_picture_sse_dev(svthip_ctx *ctx, const uint8_t *d_recon, const svthip_planes *recon, const uint8_t *d_src,
+                               const svthip_planes *src, uint32_t width, uint32_t height, uint32_t n_pics, uint64_t *d_sse,
+                               void *stream);
+int32_t svthip_highbd_picture_sse_dev(svthip_ctx *ctx, const uint16_t *d_recon, const svthip_planes *recon, uint32_t source_form,
+                                      const void *d_src, const svthip_planes *src, const uint8_t *d_srcn,
+                                      const svthip_planes *srcn, uint32_t width, uint32_t height, uint32_t n_pics, uint64_t *d_sse,
+                                      void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SadLoopKernel for a batch of blocks: NxMSadLoopKernel_funcPtrArray[asm_type] (Codec/EbComputeSAD.h:183-189) = SadLoopKernel
  * (C_DEFAULT/EbComputeSAD_C.c:73-119; signature EB_SADLOOPKERNELNxM_TYPE, Codec/EbComputeSAD.h:38-51) with the reference's full
  * argument set, for n_blocks blocks per launch.  Block i: source block at d_src + src_offset (rows src_stride apart), search grid

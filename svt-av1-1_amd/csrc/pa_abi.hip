@@ -50,6 +50,50 @@ int32_t check_pa_denoised(const uint8_t* d_denoised, uint32_t denoised_stride, u
     return SVTHIP_OK;
 }
 
+// what the five entries of the 10-bit picture forms check before anything else: the geometry and the number of pictures
+int32_t check_bitdepth_pictures(uint32_t width, uint32_t height, uint32_t n_pics)
+{
+    if (n_pics == 0 || n_pics > SVTHIP_HME_MAX_JOBS)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "between 1 and %d pictures per call (got %u)", SVTHIP_HME_MAX_JOBS, (unsigned)n_pics);
+    if ((width & 7) || (height & 7) || width < 8 || height < 8 || width > 16384 || height > 16384)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be multiples of 8 between 8 and 16384 (%ux%u)", (unsigned)width, (unsigned)height);
+    return SVTHIP_OK;
+}
+
+// one set of planes: the base pointer, the host array, and of every picture offsets that are not negative and, unless the set is a
+// compressed one, strides that hold a row
+int32_t check_bitdepth_planes(const char* what, const void* d_base, const svthip_planes* planes, uint32_t width, uint32_t n_pics, size_t sample_bytes,
+                              bool compressed = false)
+{
+    if (!d_base || !planes) return fail(SVTHIP_ERR_BAD_PARAMETER, "%s: null pointer", what);
+    if (!aligned(d_base, sample_bytes)) return fail(SVTHIP_ERR_BAD_PARAMETER, "%s: 16-bit planes must be 2-byte aligned", what);
+    for (uint32_t j = 0; j < n_pics; j++)
+        for (uint32_t p = 0; p < 3; p++) {
+            if (planes[j].offset[p] < 0) return fail(SVTHIP_ERR_BAD_PARAMETER, "%s: negative offset (picture %u, plane %u)", what, (unsigned)j, (unsigned)p);
+            if (!compressed && planes[j].stride[p] < (p ? width / 2 : width))
+                return fail(SVTHIP_ERR_BAD_PARAMETER, "%s: stride %u below the plane's width (picture %u, plane %u)", what, (unsigned)planes[j].stride[p],
+                            (unsigned)j, (unsigned)p);
+        }
+    return SVTHIP_OK;
+}
+
+// the body the two SSE entries share; form as launch_pa_picture_sse takes it
+int32_t picture_sse(svthip_ctx* ctx, int form, const void* d_recon, const svthip_planes* recon, const void* d_src, const svthip_planes* src,
+                    const uint8_t* d_srcn, const svthip_planes* srcn, uint32_t width, uint32_t height, uint32_t n_pics, uint64_t* d_sse, void* stream)
+{
+    TRY(check_bitdepth_pictures(width, height, n_pics));
+    TRY(check_bitdepth_planes("reconstruction", d_recon, recon, width, n_pics, form == 0 ? 1 : 2));
+    TRY(check_bitdepth_planes("source", d_src, src, width, n_pics, form == 1 + SVTHIP_SSE_SRC_16BIT ? 2 : 1));
+    if (form > 1 + SVTHIP_SSE_SRC_16BIT) TRY(check_bitdepth_planes("2-bit source", d_srcn, srcn, width, n_pics, 1, form == 1 + SVTHIP_SSE_SRC_COMPRESSED));
+    if (!d_sse || !aligned(d_sse, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_sse must not be null and must be 8-byte aligned");
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(ensure_scratch(ctx, SLOT_PA_SSE_PARTIALS, svthip::pa_sse_partial_bytes(width, height, n_pics)));
+    TRY(scratch_on_stream(ctx, s));
+    HIP_TRY(svthip::launch_pa_picture_sse(form, d_recon, recon, d_src, src, d_srcn, srcn, width, height, n_pics, slot_ptr<uint64_t>(ctx, SLOT_PA_SSE_PARTIALS),
+                                          d_sse, s));
+    return SVTHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -182,6 +226,61 @@ int32_t svthip_pa_denoise_dev(svthip_ctx* ctx, uint8_t* d_pool, const svthip_pa_
     HIP_TRY(svthip::launch_pa_denoise(d_pool, pics, chroma_offsets, n_pics, chroma_stride, sb_count(pics[0].width, pics[0].height), d_denoised,
                                       denoised_stride, d_flat_noise, d_picture, call_stream(ctx, stream)));
     return SVTHIP_OK;
+}
+
+// ---------------------------------------------------------------- the 10-bit picture forms (pa_bitdepth.hip)
+
+int32_t svthip_pa_unpack_10bit_dev(svthip_ctx* ctx, const uint16_t* d_in16, const svthip_planes* in16, uint8_t* d_out8, const svthip_planes* out8,
+                                   uint8_t* d_outn, const svthip_planes* outn, uint32_t width, uint32_t height, uint32_t n_pics, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bitdepth_pictures(width, height, n_pics));
+    TRY(check_bitdepth_planes("16-bit input", d_in16, in16, width, n_pics, 2));
+    TRY(check_bitdepth_planes("8-bit output", d_out8, out8, width, n_pics, 1));
+    if (d_outn) TRY(check_bitdepth_planes("2-bit output", d_outn, outn, width, n_pics, 1));
+    HIP_TRY(svthip::launch_pa_unpack_10bit(d_in16, in16, d_out8, out8, d_outn, outn, width, height, n_pics, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_pack_10bit_dev(svthip_ctx* ctx, const uint8_t* d_in8, const svthip_planes* in8, const uint8_t* d_inn, const svthip_planes* inn,
+                                 uint16_t* d_out16, const svthip_planes* out16, uint32_t width, uint32_t height, uint32_t n_pics, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bitdepth_pictures(width, height, n_pics));
+    TRY(check_bitdepth_planes("8-bit input", d_in8, in8, width, n_pics, 1));
+    TRY(check_bitdepth_planes("2-bit input", d_inn, inn, width, n_pics, 1));
+    TRY(check_bitdepth_planes("16-bit output", d_out16, out16, width, n_pics, 2));
+    HIP_TRY(svthip::launch_pa_pack_10bit(d_in8, in8, d_inn, inn, false, d_out16, out16, width, height, n_pics, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_pa_pack_10bit_compressed_dev(svthip_ctx* ctx, const uint8_t* d_in8, const svthip_planes* in8, const uint8_t* d_inn,
+                                            const svthip_planes* inn_compressed, uint16_t* d_out16, const svthip_planes* out16, uint32_t width,
+                                            uint32_t height, uint32_t n_pics, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bitdepth_pictures(width, height, n_pics));
+    TRY(check_bitdepth_planes("8-bit input", d_in8, in8, width, n_pics, 1));
+    TRY(check_bitdepth_planes("compressed 2-bit input", d_inn, inn_compressed, width, n_pics, 1, true));
+    TRY(check_bitdepth_planes("16-bit output", d_out16, out16, width, n_pics, 2));
+    HIP_TRY(svthip::launch_pa_pack_10bit(d_in8, in8, d_inn, inn_compressed, true, d_out16, out16, width, height, n_pics, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_picture_sse_dev(svthip_ctx* ctx, const uint8_t* d_recon, const svthip_planes* recon, const uint8_t* d_src, const svthip_planes* src,
+                               uint32_t width, uint32_t height, uint32_t n_pics, uint64_t* d_sse, void* stream)
+{
+    TRY(enter(ctx));
+    return picture_sse(ctx, 0, d_recon, recon, d_src, src, nullptr, nullptr, width, height, n_pics, d_sse, stream);
+}
+
+int32_t svthip_highbd_picture_sse_dev(svthip_ctx* ctx, const uint16_t* d_recon, const svthip_planes* recon, uint32_t source_form, const void* d_src,
+                                      const svthip_planes* src, const uint8_t* d_srcn, const svthip_planes* srcn, uint32_t width, uint32_t height,
+                                      uint32_t n_pics, uint64_t* d_sse, void* stream)
+{
+    TRY(enter(ctx));
+    if (source_form > SVTHIP_SSE_SRC_COMPRESSED) return fail(SVTHIP_ERR_BAD_PARAMETER, "source_form must be one of SVTHIP_SSE_SRC_* (got %u)", (unsigned)source_form);
+    return picture_sse(ctx, 1 + (int)source_form, d_recon, recon, d_src, src, d_srcn, srcn, width, height, n_pics, d_sse, stream);
 }
 
 }  // extern "C"

@@ -25,4 +25,17 @@ hipError_t launch_pa_noise_detect(const uint8_t* pool, const svthip_pa_picture* 
 hipError_t launch_pa_denoise(uint8_t* pool, const svthip_pa_picture* pics, const int64_t* chroma_offsets, uint32_t n, uint32_t chroma_stride, uint32_t n_sb,
                              uint8_t* denoised, uint32_t denoised_stride, const uint8_t* flat_noise, const uint32_t* picture, hipStream_t s);
 
+// pa_bitdepth.hip: the 10-bit picture forms over the three planes of n 4:2:0 pictures of w x h luma samples, one launch each (kernels:
+// pa_bitdepth_kernels.h).  The svthip_planes arrays are host arrays of n entries.  outn == nullptr: the 8-bit plane alone.  `compressed`:
+// inn is the SB-tiled compressed plane.  form: 0 = 8-bit planes, 1 + SVTHIP_SSE_SRC_* = 16-bit reconstruction against that source form;
+// partial: pa_sse_partial_bytes(w, h, n) of scratch for the workgroups' sums (SLOT_PA_SSE_PARTIALS)
+hipError_t launch_pa_unpack_10bit(const uint16_t* in16, const svthip_planes* in16_planes, uint8_t* out8, const svthip_planes* out8_planes, uint8_t* outn,
+                                  const svthip_planes* outn_planes, uint32_t w, uint32_t h, uint32_t n, hipStream_t s);
+hipError_t launch_pa_pack_10bit(const uint8_t* in8, const svthip_planes* in8_planes, const uint8_t* inn, const svthip_planes* inn_planes, bool compressed,
+                                uint16_t* out16, const svthip_planes* out16_planes, uint32_t w, uint32_t h, uint32_t n, hipStream_t s);
+size_t pa_sse_partial_bytes(uint32_t w, uint32_t h, uint32_t n);
+hipError_t launch_pa_picture_sse(int form, const void* recon, const svthip_planes* recon_planes, const void* src, const svthip_planes* src_planes,
+                                 const uint8_t* srcn, const svthip_planes* srcn_planes, uint32_t w, uint32_t h, uint32_t n, uint64_t* partial, uint64_t* sse,
+                                 hipStream_t s);
+
 }  // namespace svthip

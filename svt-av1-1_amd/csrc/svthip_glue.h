@@ -26,6 +26,7 @@ enum Slot {
     SLOT_PA_REGION_SUMS,  // region sums of svthip_pa_histograms_dev on their way to the picture averages: pa_region_sum_bytes
     SLOT_FILM_GRAIN_TABLES,  // the table block of the one-call film-grain form: SVTHIP_FILM_GRAIN_TABLES_BYTES
     SLOT_MD_IFS,          // trial descriptors, results and tiles of svthip_md_interp_filter_search_batch_dev: svthip::md_ifs_layout
+    SLOT_PA_SSE_PARTIALS, // workgroup sums of the picture SSE entries on their way to d_sse: svthip::pa_sse_partial_bytes
     SLOT_COUNT
 };
 

@@ -16,7 +16,7 @@ from ._me import (FRACTIONAL_FULL_SAD_SEARCH, FRACTIONAL_SSD_SEARCH, FRACTIONAL_
 from ._tq import (COEFF_RATE_DESC_DTYPE, COEFF_RATE_TABLES_DTYPE, ITXFM_DESC_DTYPE, LV_MAP_COEFF_COST_DTYPE, QUANT_DESC_DTYPE,
                   TU_DESC_DTYPE, TU_RECON_SCRATCH, TX_SIZES_WH, TXFM_DESC_DTYPE, TransformQuant, TuBatcher, TuResult, TxSearchResult,
                   TxSearchTu, tx_search_type_mask, valid_tx_types)
-from ._analysis import OisParams, PictureAnalysis
+from ._analysis import SSE_SRC_16BIT, SSE_SRC_COMPRESSED, SSE_SRC_UNPACKED, OisParams, PictureAnalysis, make_planes
 from ._pred import (AV1_BLOCK_SIZES_WH, BI_PRED, CONVOLVE_COMPOUND_DESC_DTYPE, CONVOLVE_DESC_DTYPE, INTER_PU_DESC_DTYPE, INTRA_DESC_DTYPE,
                     UNI_PRED_LIST_0, UNI_PRED_LIST_1, WARP_AFFINE, WARP_BLOCK_SIZES_WH, WARP_PU_DESC_DTYPE, WARP_ROTZOOM, InterPlanes,
                     Prediction)

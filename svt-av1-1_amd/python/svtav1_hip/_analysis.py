@@ -65,6 +65,53 @@ class PictureAnalysis:
                                            d_denoised, denoised_stride, d_flat_noise, d_picture, stream))
 
 
+    def pa_unpack_10bit_dev(self, d_in16, in16, d_out8, out8, d_outn, outn, width, height, stream=None):
+        """EB_ENC_msbUnPack2D over Y, Cb, Cr of len(in16) pictures: out8 = in >> 2, outn = in << 6 (bytes).  d_outn None: the 8-bit planes alone
+        (UnPack8BitData).  in16 / out8 / outn: lists of make_planes(...), offsets and strides in samples from the base pointers."""
+        n = len(in16)
+        _check(lib().svthip_pa_unpack_10bit_dev(self._h, d_in16, _planes(in16, n), d_out8, _planes(out8, n), d_outn,
+                                                _planes(outn, n) if d_outn else None, width, height, n, stream))
+
+    def pa_pack_10bit_dev(self, d_in8, in8, d_inn, inn, d_out16, out16, width, height, compressed=False, stream=None):
+        """EB_ENC_msbPack2D (compressed=False: inn unpacked 2-bit planes) or CompressedPackmsb (compressed=True: inn the SB-tiled compressed
+        planes, offsets in bytes, strides not read) over Y, Cb, Cr of len(in8) pictures: out16 = (in8 << 2) | 2-bit."""
+        n = len(in8)
+        fn = lib().svthip_pa_pack_10bit_compressed_dev if compressed else lib().svthip_pa_pack_10bit_dev
+        _check(fn(self._h, d_in8, _planes(in8, n), d_inn, _planes(inn, n), d_out16, _planes(out16, n), width, height, n, stream))
+
+    def picture_sse_dev(self, d_recon, recon, d_src, src, width, height, d_sse, stream=None):
+        """PsnrCalculations at 8 bits: d_sse [len(recon)][3] u64, the sums of squared differences of Y, Cb, Cr."""
+        n = len(recon)
+        _check(lib().svthip_picture_sse_dev(self._h, d_recon, _planes(recon, n), d_src, _planes(src, n), width, height, n, d_sse, stream))
+
+    def highbd_picture_sse_dev(self, d_recon, recon, source_form, d_src, src, d_srcn, srcn, width, height, d_sse, stream=None):
+        """PsnrCalculations at 16 bits against a source in form SSE_SRC_16BIT (d_src 16-bit planes), SSE_SRC_UNPACKED (d_src 8-bit, d_srcn
+        unpacked 2-bit planes) or SSE_SRC_COMPRESSED (d_srcn the compressed planes): d_sse [len(recon)][3] u64."""
+        n = len(recon)
+        _check(lib().svthip_highbd_picture_sse_dev(self._h, d_recon, _planes(recon, n), source_form, d_src, _planes(src, n), d_srcn,
+                                                   _planes(srcn, n) if srcn is not None else None, width, height, n, d_sse, stream))
+
+
+SSE_SRC_16BIT, SSE_SRC_UNPACKED, SSE_SRC_COMPRESSED = 0, 1, 2
+
+
+class _Planes(C.Structure):
+    """svthip_planes"""
+    _fields_ = [("offset", C.c_int64 * 3), ("stride", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+def make_planes(offsets, strides):
+    """One svthip_planes: the offsets of sample (0, 0) of Y, Cb, Cr from a base pointer and the strides, in samples."""
+    p = _Planes()
+    p.offset[:], p.stride[:] = [int(v) for v in offsets], [int(v) for v in strides]
+    return p
+
+
+def _planes(planes, n):
+    assert len(planes) == n, "one svthip_planes per picture in every set"
+    return (_Planes * n)(*planes)
+
+
 def _chroma_offsets(chroma_offsets, n):
     """[n][2] pool offsets as the int64_t array the entries take"""
     flat = [int(v) for pair in chroma_offsets for v in pair]
