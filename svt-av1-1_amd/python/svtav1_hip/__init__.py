@@ -3,8 +3,9 @@
 The product is the shared library; this package only marshals numpy / torch device pointers into it.
 There is no Python or CPU fallback: if the library is missing, import of `lib()` raises.
 
-Signatures come from the header (_abi).  One module per family of the header holds its descriptors, dtypes, constants, helpers and the
-Context methods of that family; everything public is re-exported here.
+Signatures, struct layouts and the constants that mirror a #define all come from the header (_abi).  One module per family of the header
+names its descriptors, dtypes and constants and holds its helpers and the Context methods of that family; everything public is
+re-exported here.
 """
 from __future__ import annotations
 

@@ -3,14 +3,11 @@ from __future__ import annotations
 
 import ctypes as C
 
+from . import _abi
 from ._core import _check, lib
 from ._me import PaPictureDesc
 
-
-class OisParams(C.Structure):
-    _fields_ = [("slice_is_intra", C.c_uint8), ("temporal_layer_index", C.c_uint8), ("is_used_as_reference_flag", C.c_uint8),
-                ("input_resolution_4k", C.c_uint8), ("limit_ois_to_dc_mode_flag", C.c_uint8), ("cu8x8_mode", C.c_uint8),
-                ("enc_mode", C.c_uint8), ("reserved", C.c_uint8)]
+OisParams = _abi.structure("svthip_ois_params")
 
 
 class PictureAnalysis:
@@ -92,12 +89,10 @@ class PictureAnalysis:
                                                    _planes(srcn, n) if srcn is not None else None, width, height, n, d_sse, stream))
 
 
-SSE_SRC_16BIT, SSE_SRC_UNPACKED, SSE_SRC_COMPRESSED = 0, 1, 2
-
-
-class _Planes(C.Structure):
-    """svthip_planes"""
-    _fields_ = [("offset", C.c_int64 * 3), ("stride", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+SSE_SRC_16BIT = _abi.define("SVTHIP_SSE_SRC_16BIT")
+SSE_SRC_UNPACKED = _abi.define("SVTHIP_SSE_SRC_UNPACKED")
+SSE_SRC_COMPRESSED = _abi.define("SVTHIP_SSE_SRC_COMPRESSED")
+_Planes = _abi.structure("svthip_planes")
 
 
 def make_planes(offsets, strides):

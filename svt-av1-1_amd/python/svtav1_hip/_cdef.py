@@ -2,24 +2,14 @@
 svthip_cdef_dist_8x8_batch_dev): pointer marshalling only."""
 from __future__ import annotations
 
-import ctypes as C
-
-import numpy as np
-
+from . import _abi
 from ._core import _check, _hbd, _picture_ref, lib
 
-CDEF_RESULT_DTYPE = np.dtype([("cdef_bits", "<i4"), ("nb_cdef_strengths", "<i4"), ("cdef_strengths", "<i4", (8,)), ("cdef_uv_strengths", "<i4", (8,)),
-                              ("pri_damping", "<i4"), ("sec_damping", "<i4"), ("sb_count", "<i4")])
-assert CDEF_RESULT_DTYPE.itemsize == 84
-CDEF_PICK_MAX_FB = 4096
-
-
-class CdefPicture(C.Structure):
-    """svthip_cdef_picture: device pointers to sample (0, 0) of the deblocked, source and output planes, strides in samples, the luma size,
-    the skip map (one byte per 4x4 luma cell) and its stride"""
-    _fields_ = [("deblocked", C.c_void_p * 3), ("source", C.c_void_p * 3), ("out", C.c_void_p * 3), ("deblocked_stride", C.c_uint32 * 3),
-                ("source_stride", C.c_uint32 * 3), ("out_stride", C.c_uint32 * 3), ("width", C.c_uint32), ("height", C.c_uint32),
-                ("d_skip", C.c_void_p), ("skip_stride", C.c_uint32)]
+CDEF_RESULT_DTYPE = _abi.dtype("svthip_cdef_result")
+CDEF_PICK_MAX_FB = _abi.define("SVTHIP_CDEF_PICK_MAX_FB")
+# svthip_cdef_picture: device pointers to sample (0, 0) of the deblocked, source and output planes, strides in samples, the luma size,
+# the skip map (one byte per 4x4 luma cell) and its stride
+CdefPicture = _abi.structure("svthip_cdef_picture")
 
 
 def cdef_filter_blocks(width, height):

@@ -2,16 +2,12 @@
 svthip_cfl_alpha_decision_batch_dev)."""
 from __future__ import annotations
 
-import numpy as np
-
+from . import _abi
 from ._core import _check, lib
 
-CFL_DESC_DTYPE = np.dtype([("luma_offset", "<u4"), ("luma_stride", "<u4"), ("cb_offset", "<u4"), ("cr_offset", "<u4"), ("chroma_stride", "<u4"),
-                           ("alpha_idx", "u1"), ("alpha_signs", "u1"), ("reserved", "u1", (10,))])
-CFL_DECISION_JOB_DTYPE = np.dtype([("lambda", "<u8"), ("cfl_mode_bits", "<i4"), ("dc_mode_bits", "<i4")])
-CFL_DECISION_DTYPE = np.dtype([("intra_chroma_mode", "u1"), ("cfl_alpha_idx", "u1"), ("cfl_alpha_signs", "u1"), ("reserved", "u1", (13,)),
-                               ("evaluated_mask", "<u8", (2,))])
-assert CFL_DESC_DTYPE.itemsize == 32 and CFL_DECISION_JOB_DTYPE.itemsize == 16 and CFL_DECISION_DTYPE.itemsize == 32
+CFL_DESC_DTYPE = _abi.dtype("svthip_cfl_desc")
+CFL_DECISION_JOB_DTYPE = _abi.dtype("svthip_cfl_decision_job")   # `lambda` keeps its C spelling here
+CFL_DECISION_DTYPE = _abi.dtype("svthip_cfl_decision")
 # the luma sizes the reference uses CfL with
 CFL_LUMA_SIZES_WH = [(8, 8), (16, 8), (8, 16), (16, 16), (32, 8), (8, 32), (32, 16), (16, 32), (32, 32)]
 

@@ -37,9 +37,9 @@ def lib() -> C.CDLL:
     return L
 
 
-OPT_SADLOOP_GENERIC = 0
-OPT_CONVOLVE_VALU = 1
-OPT_TQ_MAX_WORKGROUPS = 2
+OPT_SADLOOP_GENERIC = _abi.define("SVTHIP_OPT_SADLOOP_GENERIC")
+OPT_CONVOLVE_VALU = _abi.define("SVTHIP_OPT_CONVOLVE_VALU")
+OPT_TQ_MAX_WORKGROUPS = _abi.define("SVTHIP_OPT_TQ_MAX_WORKGROUPS")
 
 
 class SvtHipError(RuntimeError):

@@ -4,18 +4,12 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
+from . import _abi
 from ._core import _check, _picture_ref, lib
 
-LF_MI_DTYPE = np.dtype([("sb_type", "u1"), ("tx_size", "u1"), ("flags", "u1"), ("reserved", "u1")])
-assert LF_MI_DTYPE.itemsize == 4
-
-
-class LfPicture(C.Structure):
-    """svthip_lf_picture: device pointers to sample (0, 0) of the planes, strides in samples, the luma size"""
-    _fields_ = [("recon", C.c_void_p * 3), ("source", C.c_void_p * 3), ("recon_stride", C.c_uint32 * 3), ("source_stride", C.c_uint32 * 3),
-                ("width", C.c_uint32), ("height", C.c_uint32)]
+LF_MI_DTYPE = _abi.dtype("svthip_lf_mi")
+# svthip_lf_picture: device pointers to sample (0, 0) of the planes, strides in samples, the luma size
+LfPicture = _abi.structure("svthip_lf_picture")
 
 
 def make_lf_picture(width, height, recon, recon_stride, source=(None, None, None), source_stride=(0, 0, 0)):

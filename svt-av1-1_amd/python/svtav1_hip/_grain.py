@@ -7,26 +7,23 @@ from __future__ import annotations
 import ctypes as C
 import struct
 
+import numpy as np
+
+from . import _abi
 from ._core import _check, lib
 
-# (field, number of int32) in the order of the C struct; a [n][2] array of scaling points counts 2 n
-_FILM_GRAIN_FIELDS = (("apply_grain", 1), ("update_parameters", 1), ("scaling_points_y", 28), ("num_y_points", 1), ("scaling_points_cb", 20),
-                      ("num_cb_points", 1), ("scaling_points_cr", 20), ("num_cr_points", 1), ("scaling_shift", 1), ("ar_coeff_lag", 1),
-                      ("ar_coeffs_y", 24), ("ar_coeffs_cb", 25), ("ar_coeffs_cr", 25), ("ar_coeff_shift", 1), ("cb_mult", 1), ("cb_luma_mult", 1),
-                      ("cb_offset", 1), ("cr_mult", 1), ("cr_luma_mult", 1), ("cr_offset", 1), ("overlap_flag", 1), ("clip_to_restricted_range", 1),
-                      ("bit_depth", 1), ("chroma_scaling_from_luma", 1), ("grain_scale_shift", 1))
-FILM_GRAIN_PARAMS_BYTES = 4 * sum(n for _, n in _FILM_GRAIN_FIELDS) + 4
-FILM_GRAIN_TABLES_BYTES = 2 * (73 * 82 + 2 * 38 * 44 + 3 * 256)
+_LAYOUT = _abi.dtype("svthip_film_grain_params")
+# (field, struct code, number of values) in the order of the C struct; a [n][2] array of scaling points counts 2 n
+_FILM_GRAIN_FIELDS = [(name, _LAYOUT[name].base.char, int(np.prod(_LAYOUT[name].shape, dtype=int))) for name in _LAYOUT.names]
+_PACKED = "<" + "".join(f"{n}{code}" for _, code, n in _FILM_GRAIN_FIELDS)
+FILM_GRAIN_PARAMS_BYTES = _LAYOUT.itemsize
+assert struct.calcsize(_PACKED) == FILM_GRAIN_PARAMS_BYTES   # the C struct has no implicit padding: the packed words are its layout
+FILM_GRAIN_TABLES_BYTES = _abi.define("SVTHIP_FILM_GRAIN_TABLES_BYTES")
 
 
 def film_grain_param_offsets() -> dict:
     """{field: byte offset} of svthip_film_grain_params, random_seed and reserved included"""
-    out, at = {}, 0
-    for name, n in _FILM_GRAIN_FIELDS:
-        out[name] = at
-        at += 4 * n
-    out["random_seed"], out["reserved"] = at, at + 2
-    return out
+    return {name: _LAYOUT.fields[name][1] for name in _LAYOUT.names}
 
 
 def _flat(v):
@@ -38,17 +35,16 @@ def _flat(v):
 def film_grain_params(**fields):
     """svthip_film_grain_params as a buffer the film-grain methods take: every field that is not named is 0; arrays may be shorter than
     the C array (the rest is 0) and scaling points are given as [[x, y], ...]"""
-    unknown = set(fields) - {n for n, _ in _FILM_GRAIN_FIELDS} - {"random_seed"}
+    unknown = set(fields) - set(_LAYOUT.names) | set(fields) & {"reserved"}
     if unknown:
         raise TypeError(f"svthip_film_grain_params has no field {sorted(unknown)}")
     words = []
-    for name, n in _FILM_GRAIN_FIELDS:
+    for name, _, n in _FILM_GRAIN_FIELDS:
         v = _flat(fields.get(name, 0))
         if len(v) > n:
             raise ValueError(f"{name} holds {n} values (got {len(v)})")
         words += v + [0] * (n - len(v))
-    raw = struct.pack(f"<{len(words)}i", *words) + struct.pack("<HH", int(fields.get("random_seed", 0)), 0)
-    return C.create_string_buffer(raw, FILM_GRAIN_PARAMS_BYTES)
+    return C.create_string_buffer(struct.pack(_PACKED, *words), FILM_GRAIN_PARAMS_BYTES)
 
 
 def _planes(ptrs, strides):

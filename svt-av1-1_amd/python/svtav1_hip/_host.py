@@ -5,18 +5,14 @@ import ctypes as C
 
 import numpy as np
 
+from . import _abi
 from ._core import _check, lib
 from ._tq import TU_DESC_DTYPE
 
-
-class HostPicture(C.Structure):
-    """svthip_host_picture: a host luma plane (the caller keeps the buffer alive), the sample at (origin_x, origin_y) is picture (0, 0)."""
-    _fields_ = [("buffer_y", C.c_void_p), ("stride_y", C.c_uint32), ("origin_x", C.c_uint16), ("origin_y", C.c_uint16), ("width", C.c_uint16),
-                ("height", C.c_uint16)]
-
-
-assert C.sizeof(HostPicture) == 24
+# svthip_host_picture: a host luma plane (the caller keeps the buffer alive), the sample at (origin_x, origin_y) is picture (0, 0).
+HostPicture = _abi.structure("svthip_host_picture")
 # svthip_me_cu_result_ref: the reference's MeCuResults_t (40 bytes; `direction` words hold 0..2, padding is written as 0)
+# hand-written: the recorded form leaves the trailing pad_[7] unnamed, the header names it
 ME_CU_RESULT_REF_DTYPE = np.dtype({"names": ["xMvL0", "yMvL0", "xMvL1", "yMvL1", "distortionDirection", "totalMeCandidateIndex"],
                                    "formats": ["<i2", "<i2", "<i2", "<i2", (np.dtype([("distortion", "<u4"), ("direction", "<u4")]), (3,)), "u1"],
                                    "offsets": [0, 2, 4, 6, 8, 32], "itemsize": 40})

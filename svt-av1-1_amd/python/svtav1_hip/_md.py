@@ -10,33 +10,32 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _abi
 from ._core import _check, lib
 from ._pred import _planes_arg
 
-MD_FAST_LUMA_GIVEN, MD_FAST_SKIP_DISTORTION, MD_FAST_INVALID, MD_FAST_CHROMA_QUARTER, MD_FAST_TYPE_INTER = 1, 2, 4, 8, 16
-MD_FAST_MAX_CANDIDATES, MD_FAST_MAX_BUFFERS = 113, 13
+MD_FAST_LUMA_GIVEN, MD_FAST_SKIP_DISTORTION, MD_FAST_INVALID, MD_FAST_CHROMA_QUARTER, MD_FAST_TYPE_INTER, MD_FAST_MAX_CANDIDATES, MD_FAST_MAX_BUFFERS = (
+    _abi.define("SVTHIP_MD_FAST_" + t) for t in ("LUMA_GIVEN", "SKIP_DISTORTION", "INVALID", "CHROMA_QUARTER", "TYPE_INTER", "MAX_CANDIDATES", "MAX_BUFFERS"))
 
 
 def md_fast_desc_dtype() -> np.dtype:
     """svthip_md_fast_desc, 32 bytes; `lambda` is spelled lambda_"""
-    return np.dtype([("src_x", "<u2"), ("src_y", "<u2"), ("pred_x", "<u2"), ("pred_y", "<u2"), ("rate", "<u4"), ("merge_rate", "<u4"),
-                     ("lambda_", "<u4"), ("luma_given", "<u4"), ("has_uv", "u1"), ("flags", "u1"), ("reserved", "u1", (6,))])
+    return _abi.dtype("svthip_md_fast_desc", lambda_="lambda")
 
 
 def md_fast_result_dtype() -> np.dtype:
     """svthip_md_fast_result, 16 bytes"""
-    return np.dtype([("luma", "<u4"), ("chroma", "<u4"), ("cost", "<u8")])
+    return _abi.dtype("svthip_md_fast_result")
 
 
 def md_fast_group_dtype() -> np.dtype:
     """svthip_md_fast_group, 8 bytes"""
-    return np.dtype([("first", "<u4"), ("count", "<u2"), ("buffer_total_count", "u1"), ("buffer_width", "u1")])
+    return _abi.dtype("svthip_md_fast_group")
 
 
 def md_fast_pick_dtype() -> np.dtype:
     """svthip_md_fast_pick, 32 bytes"""
-    return np.dtype([("best", "u1", (13,)), ("buffer_cand", "u1", (13,)), ("full_count", "u1"), ("disable_merge_index", "u1"),
-                     ("reserved", "u1", (4,))])
+    return _abi.dtype("svthip_md_fast_pick")
 
 
 class ModeDecisionFast:
@@ -59,23 +58,22 @@ MD_IFS_REFUSED = 0xFF   # best_trial of a candidate refused on the device
 
 def md_model_rd_desc_dtype() -> np.dtype:
     """svthip_md_model_rd_desc, 16 bytes; `lambda` is spelled lambda_"""
-    return np.dtype([("src_x", "<u2"), ("src_y", "<u2"), ("pred_x", "<u2"), ("pred_y", "<u2"), ("lambda_", "<u4"), ("rate", "<i4")])
+    return _abi.dtype("svthip_md_model_rd_desc", lambda_="lambda")
 
 
 def md_model_rd_result_dtype() -> np.dtype:
     """svthip_md_model_rd_result, 32 bytes"""
-    return np.dtype([("sse", "<u4", (3,)), ("rate", "<i4"), ("dist", "<i8"), ("rd", "<i8")])
+    return _abi.dtype("svthip_md_model_rd_result")
 
 
 def md_ifs_desc_dtype() -> np.dtype:
     """svthip_md_ifs_desc, 32 bytes; filter_rate[dir][filter], dir 0 the vertical (y) filter"""
-    return np.dtype([("src_x", "<u2"), ("src_y", "<u2"), ("lambda_", "<u4"), ("filter_rate", "<i4", (2, 3))])
+    return _abi.dtype("svthip_md_ifs_desc", lambda_="lambda")
 
 
 def md_ifs_result_dtype() -> np.dtype:
     """svthip_md_ifs_result, 32 bytes"""
-    return np.dtype([("interp_filters", "<u4"), ("switchable_rate", "<i4"), ("rd", "<i8"), ("skip_sse_sb", "<i8"), ("skip_txfm_sb", "u1"),
-                     ("best_trial", "u1"), ("reserved", "u1", (6,))])
+    return _abi.dtype("svthip_md_ifs_result")
 
 
 class InterpFilterSearch:
@@ -97,29 +95,23 @@ class InterpFilterSearch:
                                                               d_result, stream))
 
 
-MD_FULL_LUMA, MD_FULL_CHROMA, MD_FULL_DECIDE = 1, 2, 4
-MD_FULL_MAX_SLOTS = 12
+MD_FULL_LUMA, MD_FULL_CHROMA, MD_FULL_DECIDE, MD_FULL_MAX_SLOTS = (_abi.define("SVTHIP_MD_FULL_" + t) for t in ("LUMA", "CHROMA", "DECIDE", "MAX_SLOTS"))
 MD_FULL_NONE = 0xFFFFFFFF   # row of an inactive slot, winner_row of a refused group
 
 
 def md_full_desc_dtype() -> np.dtype:
     """svthip_md_full_desc, 48 bytes; `lambda` is spelled lambda_"""
-    return np.dtype([("luma_rate", "<u4"), ("chroma_rate", "<u4"), ("skip_mode_rate", "<u4"), ("lambda_", "<u4"), ("recon_x", "<u2"), ("recon_y", "<u2"),
-                     ("qparam_index", "<u2", (3,)), ("tx_type_y", "u1"), ("tx_type_uv", "u1"), ("txb_skip_ctx", "u1", (3,)), ("dc_sign_ctx", "u1", (3,)),
-                     ("intra_mode", "u1"), ("reserved", "u1", (13,))])
+    return _abi.dtype("svthip_md_full_desc", lambda_="lambda")
 
 
 def md_full_result_dtype() -> np.dtype:
     """svthip_md_full_result, 144 bytes"""
-    return np.dtype([("full_cost", "<u8"), ("merge_cost", "<u8"), ("skip_cost", "<u8"), ("full_lambda_rate", "<u8"), ("full_cost_luma", "<u8"),
-                     ("y_distortion", "<u8", (2,)), ("cb_distortion", "<u8", (2,)), ("cr_distortion", "<u8", (2,)), ("coeff_bits", "<u8", (3,)),
-                     ("quantized_dc", "<i4", (3,)), ("row", "<u4"), ("eob", "<u2", (3,)), ("tx_type_y", "u1"), ("tx_type_uv", "u1"), ("y_has_coeff", "u1"),
-                     ("u_has_coeff", "u1"), ("v_has_coeff", "u1"), ("block_has_coeff", "u1"), ("skip_flag", "u1"), ("reserved", "u1", (3,))])
+    return _abi.dtype("svthip_md_full_result")
 
 
 def md_full_decision_dtype() -> np.dtype:
     """svthip_md_full_decision, 16 bytes"""
-    return np.dtype([("cost", "<u8"), ("winner_row", "<u4"), ("winner_slot", "u1"), ("winner_buffer", "u1"), ("best_intra_mode", "u1"), ("n_full", "u1")])
+    return _abi.dtype("svthip_md_full_decision")
 
 
 def md_full_workspace_bytes(n_groups, max_full, bwidth, bheight, type_mask_inter, type_mask_intra) -> int:

@@ -6,53 +6,24 @@ import ctypes as C
 
 import numpy as np
 
+from . import _abi
 from ._core import _check, lib
 
-NUM_SQ_PU = 85
-MAX_SAD_VALUE = 128 * 128 * 255
+NUM_SQ_PU = _abi.define("SVTHIP_NUM_SQ_PU")
+MAX_SAD_VALUE = _abi.define("SVTHIP_MAX_SAD_VALUE")
+HME_MAX_JOBS = _abi.define("SVTHIP_HME_MAX_JOBS")  # pictures per kernel launch of the batch entries
+# MeContext_t::fractionalSearchMethod
+FRACTIONAL_SUB_SAD_SEARCH = _abi.define("SVTHIP_FRACTIONAL_SUB_SAD_SEARCH")
+FRACTIONAL_FULL_SAD_SEARCH = _abi.define("SVTHIP_FRACTIONAL_FULL_SAD_SEARCH")
+FRACTIONAL_SSD_SEARCH = _abi.define("SVTHIP_FRACTIONAL_SSD_SEARCH")
 
-HME_MAX_JOBS = 32  # SVTHIP_HME_MAX_JOBS: pictures per kernel launch of the batch entries
-
-FRACTIONAL_SUB_SAD_SEARCH, FRACTIONAL_FULL_SAD_SEARCH, FRACTIONAL_SSD_SEARCH = 0, 1, 2  # MeContext_t::fractionalSearchMethod
-
-
-class FullpelDesc(C.Structure):
-    _fields_ = [("src_offset", C.c_int32), ("ref_offset", C.c_int32), ("x_search_area_origin", C.c_int32),
-                ("y_search_area_origin", C.c_int32), ("search_area_width", C.c_int32), ("search_area_height", C.c_int32)]
-
-
-class PaPictureDesc(C.Structure):
-    _fields_ = [("full_offset", C.c_int64), ("quarter_offset", C.c_int64), ("sixteenth_offset", C.c_int64),
-                ("full_stride", C.c_uint32), ("quarter_stride", C.c_uint32), ("sixteenth_stride", C.c_uint32),
-                ("width", C.c_uint16), ("height", C.c_uint16)]
-
-
-class MeParams(C.Structure):
-    _fields_ = [("search_area_width", C.c_uint16), ("search_area_height", C.c_uint16),
-                ("number_hme_search_region_in_width", C.c_uint16), ("number_hme_search_region_in_height", C.c_uint16),
-                ("hme_level0_total_search_area_width", C.c_uint16), ("hme_level0_total_search_area_height", C.c_uint16),
-                ("hme_level0_search_area_in_width_array", C.c_uint16 * 2), ("hme_level0_search_area_in_height_array", C.c_uint16 * 2),
-                ("hme_level1_search_area_in_width_array", C.c_uint16 * 2), ("hme_level1_search_area_in_height_array", C.c_uint16 * 2),
-                ("hme_level2_search_area_in_width_array", C.c_uint16 * 2), ("hme_level2_search_area_in_height_array", C.c_uint16 * 2),
-                ("hme_level0_multiplier_x", C.c_uint32), ("hme_level0_multiplier_y", C.c_uint32),
-                ("enable_hme_flag", C.c_uint8), ("enable_hme_level0_flag", C.c_uint8), ("enable_hme_level1_flag", C.c_uint8),
-                ("enable_hme_level2_flag", C.c_uint8), ("temporal_layer_index", C.c_uint8),
-                ("is_used_as_reference_flag", C.c_uint8), ("ref_poc_equal", C.c_uint8), ("reserved", C.c_uint8)]
-
-
-class MeCuResult(C.Structure):
-    _fields_ = [("xMvL0", C.c_int16), ("yMvL0", C.c_int16), ("xMvL1", C.c_int16), ("yMvL1", C.c_int16),
-                ("distortion", C.c_uint32 * 3), ("direction", C.c_uint8 * 3), ("totalMeCandidateIndex", C.c_uint8)]
-
-
-ME_CU_RESULT_DTYPE = np.dtype([("xMvL0", "<i2"), ("yMvL0", "<i2"), ("xMvL1", "<i2"), ("yMvL1", "<i2"), ("distortion", "<u4", 3),
-                               ("direction", "u1", 3), ("totalMeCandidateIndex", "u1")])
+FullpelDesc = _abi.structure("svthip_fullpel_desc")
+PaPictureDesc = _abi.structure("svthip_pa_picture")
+MeParams = _abi.structure("svthip_me_params")
+MeCuResult = _abi.structure("svthip_me_cu_result")
+ME_CU_RESULT_DTYPE = _abi.dtype("svthip_me_cu_result")
 assert ME_CU_RESULT_DTYPE.itemsize == C.sizeof(MeCuResult) == 24
-
-
-class SbOrigin(C.Structure):
-    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16)]
-
+SbOrigin = _abi.structure("svthip_sb_origin")
 
 # HME_LEVEL_0_SEARCH_AREA_MULTIPLIER_X / _Y [hierarchical_levels][temporal_layer_index]
 # (Codec/EbDefinitions.h:2980-2996); X and Y tables are identical in the reference.

@@ -3,34 +3,21 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
+from . import _abi
 from ._core import _check, lib
 
-CONVOLVE_DESC_DTYPE = np.dtype([("src_offset", "<u4"), ("dst_offset", "<u4"), ("subpel_x", "u1"), ("subpel_y", "u1"), ("filter_x", "u1"),
-                                ("filter_y", "u1"), ("reserved", "<u4")])
-assert CONVOLVE_DESC_DTYPE.itemsize == 16
+CONVOLVE_DESC_DTYPE = _abi.dtype("svthip_convolve_desc")
 # the 22 AV1 block sizes (width, height)
 AV1_BLOCK_SIZES_WH = [(4, 4), (4, 8), (8, 4), (8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16), (32, 32), (32, 64), (64, 32), (64, 64),
                       (64, 128), (128, 64), (128, 128), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
 
-CONVOLVE_COMPOUND_DESC_DTYPE = np.dtype([("src0_offset", "<u4"), ("src1_offset", "<u4"), ("dst_offset", "<u4"), ("subpel0", "u1"), ("subpel1", "u1"),
-                                         ("filter_x", "u1"), ("filter_y", "u1")])
-assert CONVOLVE_COMPOUND_DESC_DTYPE.itemsize == 16
+CONVOLVE_COMPOUND_DESC_DTYPE = _abi.dtype("svthip_convolve_compound_desc")
 
 # ---- whole-PU inter prediction (svthip_av1_inter_pred_batch_dev / svthip_av1_highbd_inter_pred_batch_dev) ----
-INTER_PU_DESC_DTYPE = np.dtype([("pu_origin_x", "<u2"), ("pu_origin_y", "<u2"), ("dst_origin_x", "<u2"), ("dst_origin_y", "<u2"),
-                                ("mb_to_left_edge", "<i4"), ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"),
-                                ("interp_filters", "<u4"), ("pred_direction", "u1"), ("has_uv", "u1"), ("own_list", "u1"), ("reserved0", "u1"),
-                                ("mv", "<i2", (2, 2)), ("nb_is_inter", "u1", (3,)), ("nb_list", "u1", (3,)), ("nb_mv", "<i2", (3, 2)),
-                                ("reserved1", "u1", (6,))])
-assert INTER_PU_DESC_DTYPE.itemsize == 64
+INTER_PU_DESC_DTYPE = _abi.dtype("svthip_inter_pu_desc")
 UNI_PRED_LIST_0, UNI_PRED_LIST_1, BI_PRED = 0, 1, 2
-
-
-class InterPlanes(C.Structure):
-    """svthip_inter_planes: device pointers at picture sample (0, 0) of Y / Cb / Cr, strides in samples (Cb and Cr share c_stride)."""
-    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_uint32), ("c_stride", C.c_uint32)]
+# svthip_inter_planes: device pointers at picture sample (0, 0) of Y / Cb / Cr, strides in samples (Cb and Cr share c_stride).
+InterPlanes = _abi.structure("svthip_inter_planes")
 
 
 def _planes_arg(p):
@@ -38,19 +25,12 @@ def _planes_arg(p):
 
 
 # ---- warped-motion prediction of whole PUs (svthip_av1_warped_pred_batch_dev / svthip_av1_highbd_warped_pred_batch_dev) ----
-WARP_PU_DESC_DTYPE = np.dtype([("pu_origin_x", "<u2"), ("pu_origin_y", "<u2"), ("dst_origin_x", "<u2"), ("dst_origin_y", "<u2"),
-                               ("mb_to_left_edge", "<i4"), ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"),
-                               ("wmmat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"),
-                               ("mv", "<i2", (2,)), ("wmtype", "u1"), ("has_uv", "u1"), ("reserved", "u1", (2,))])
-assert WARP_PU_DESC_DTYPE.itemsize == 64
+WARP_PU_DESC_DTYPE = _abi.dtype("svthip_warp_pu_desc")
 WARP_ROTZOOM, WARP_AFFINE = 2, 3
 WARP_BLOCK_SIZES_WH = [s for s in AV1_BLOCK_SIZES_WH if min(s) >= 8]
 
 # ---- intra prediction of transform blocks (svthip_av1_intra_pred_batch_dev / svthip_av1_highbd_intra_pred_batch_dev) ----
-INTRA_DESC_DTYPE = np.dtype([("above_offset", "<u4"), ("left_offset", "<u4"), ("left_stride", "<u4"), ("dst_offset", "<u4"), ("dst_stride", "<u4"),
-                             ("n_top_px", "u1"), ("n_topright_px", "u1"), ("n_left_px", "u1"), ("n_bottomleft_px", "u1"), ("mode", "u1"),
-                             ("angle_delta", "i1"), ("src_stride", "<u2"), ("src_offset", "<u4")])
-assert INTRA_DESC_DTYPE.itemsize == 32
+INTRA_DESC_DTYPE = _abi.dtype("svthip_intra_desc")
 
 
 class Prediction:

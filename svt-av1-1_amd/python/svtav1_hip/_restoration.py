@@ -9,26 +9,17 @@ import ctypes as C
 
 import numpy as np
 
+from . import _abi
 from ._core import _check, _hbd, _picture_ref, lib
 
-RESTORE_NONE, RESTORE_WIENER, RESTORE_SGRPROJ = 0, 1, 2
-RESTORE_SWITCHABLE = 3
-WIENER_WALK_STATE_DTYPE = np.dtype([("err", "<i8"), ("taps", "<i2", (16,)), ("step", "i1"), ("filt", "i1"), ("tap", "i1"), ("dir", "i1"), ("skip", "i1"),
-                                    ("first_tap", "i1"), ("started", "i1"), ("done", "u1"), ("n_trials", "<i4"), ("reserved", "<i4")])
-assert WIENER_WALK_STATE_DTYPE.itemsize == 56
+RESTORE_NONE, RESTORE_WIENER, RESTORE_SGRPROJ, RESTORE_SWITCHABLE = (_abi.define("SVTHIP_RESTORE_" + t) for t in ("NONE", "WIENER", "SGRPROJ", "SWITCHABLE"))
+WIENER_WALK_STATE_DTYPE = _abi.dtype("svthip_wiener_walk_state")
 
-SGRPROJ_DETAIL_DTYPE = np.dtype([("sums", "<i8", (5,)), ("exq", "<i4", (2,)), ("start_xqd", "<i4", (2,)), ("xqd", "<i4", (2,)), ("err", "<i8"),
-                                 ("n_trials", "<i4"), ("reserved", "<i4")])
-assert SGRPROJ_DETAIL_DTYPE.itemsize == 80
+SGRPROJ_DETAIL_DTYPE = _abi.dtype("svthip_sgrproj_detail")
 SGRPROJ_PARAMS = 16
-
-
-class LrPicture(C.Structure):
-    """svthip_lr_picture: device pointers to sample (0, 0) of the CDEF'd, deblocked and source planes, strides in samples, the luma size, the
-    restoration unit size per plane"""
-    _fields_ = [("cdef", C.c_void_p * 3), ("deblocked", C.c_void_p * 3), ("source", C.c_void_p * 3), ("cdef_stride", C.c_uint32 * 3),
-                ("deblocked_stride", C.c_uint32 * 3), ("source_stride", C.c_uint32 * 3), ("width", C.c_uint32), ("height", C.c_uint32),
-                ("unit_size", C.c_uint32 * 3)]
+# svthip_lr_picture: device pointers to sample (0, 0) of the CDEF'd, deblocked and source planes, strides in samples, the luma size, the
+# restoration unit size per plane
+LrPicture = _abi.structure("svthip_lr_picture")
 
 
 def lr_unit_sizes(width, height):
@@ -80,12 +71,12 @@ def lr_pick_workspace_bytes(width, height, unit_size=None):
 
 def rest_finish_rates_dtype() -> np.dtype:
     """svthip_rest_finish_rates, 32 bytes, host memory"""
-    return np.dtype([("rdmult", "<i4"), ("wiener_cost", "<i4", (2,)), ("sgrproj_cost", "<i4", (2,)), ("switchable_cost", "<i4", (3,))])
+    return _abi.dtype("svthip_rest_finish_rates")
 
 
 def rest_finish_result_dtype() -> np.dtype:
     """svthip_rest_finish_result, 104 bytes, one per plane; sse, bits and cost are indexed by frame type"""
-    return np.dtype([("sse", "<i8", (4,)), ("bits", "<i8", (4,)), ("cost", "<f8", (4,)), ("frame_type", "<i4"), ("n_tried", "<i4")])
+    return _abi.dtype("svthip_rest_finish_result")
 
 
 def _rates_ref(rates):

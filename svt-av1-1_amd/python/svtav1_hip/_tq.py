@@ -6,21 +6,14 @@ import ctypes as C
 
 import numpy as np
 
+from . import _abi
 from ._core import _check, lib
 
-QUANT_DESC_DTYPE = np.dtype([("coeff_offset", "<u4"), ("iscan_offset", "<u4"), ("qparam_index", "<u4"), ("n_coeffs", "<u2"),
-                             ("log_scale", "u1"), ("highbd", "u1")])
-assert QUANT_DESC_DTYPE.itemsize == 16
+QUANT_DESC_DTYPE = _abi.dtype("svthip_quant_desc")
 
-TXFM_DESC_DTYPE = np.dtype([("in_offset", "<u4"), ("out_offset", "<u4"), ("in_stride", "<u2"), ("tx_type", "u1"), ("reserved", "u1")])
-assert TXFM_DESC_DTYPE.itemsize == 12
-ITXFM_DESC_DTYPE = np.dtype([("coeff_offset", "<u4"), ("recon_offset", "<u4"), ("recon_stride", "<u2"), ("tx_type", "u1"),
-                             ("reserved", "u1")])
-assert ITXFM_DESC_DTYPE.itemsize == 12
-TU_DESC_DTYPE = np.dtype([("src_offset", "<u4"), ("pred_offset", "<u4"), ("recon_offset", "<u4"), ("coeff_offset", "<u4"),
-                          ("iscan_offset", "<u4"), ("src_stride", "<u2"), ("pred_stride", "<u2"), ("recon_stride", "<u2"),
-                          ("qparam_index", "<u2"), ("tx_type", "u1"), ("reserved", "u1", (3,))])
-assert TU_DESC_DTYPE.itemsize == 32
+TXFM_DESC_DTYPE = _abi.dtype("svthip_txfm_desc")
+ITXFM_DESC_DTYPE = _abi.dtype("svthip_itxfm_desc")
+TU_DESC_DTYPE = _abi.dtype("svthip_tu_desc")
 
 # the 19 AV1 transform sizes (width, height), TxSize order (Codec/EbDefinitions.h)
 TX_SIZES_WH = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 8), (8, 4), (8, 16), (16, 8), (16, 32), (32, 16), (32, 64),
@@ -40,12 +33,8 @@ def valid_tx_types(w: int, h: int):
     return out
 
 
-class TuResult(C.Structure):
-    _fields_ = [("distortion", C.c_uint64 * 2), ("three_quad_energy", C.c_uint64), ("coeff_offset", C.c_uint32), ("eob", C.c_uint16),
-                ("tx_size", C.c_uint8), ("tx_type", C.c_uint8)]
-
-
-TU_RECON_SCRATCH = 0xffffffff
+TuResult = _abi.structure("svthip_tu_result")
+TU_RECON_SCRATCH = _abi.define("SVTHIP_TU_RECON_SCRATCH")
 
 
 class TuBatcher:
@@ -108,35 +97,13 @@ class TuBatcher:
 
 
 # ---- coefficient rate and the RD transform-type search (include/svtav1_hip.h) ----
-LV_MAP_COEFF_COST_DTYPE = np.dtype([("txb_skip_cost", "<i4", (13, 2)), ("base_eob_cost", "<i4", (4, 3)), ("base_cost", "<i4", (42, 4)),
-                                    ("eob_extra_cost", "<i4", (22, 2)), ("dc_sign_cost", "<i4", (3, 2)), ("lps_cost", "<i4", (21, 13))])
-assert LV_MAP_COEFF_COST_DTYPE.itemsize == 2116
-# svthip_coeff_rate_tables: eobFracBits is [7][2] LV_MAP_EOB_COST { eob_cost[2][11] }
+LV_MAP_COEFF_COST_DTYPE = _abi.dtype("svthip_lv_map_coeff_cost")
+# svthip_coeff_rate_tables; hand-written: the recorded form gives eobFracBits, [7][2] of svthip_lv_map_eob_cost { eob_cost[2][11] }, as one array
 COEFF_RATE_TABLES_DTYPE = np.dtype([("coeffFacBits", LV_MAP_COEFF_COST_DTYPE, (5, 2)), ("eobFracBits", "<i4", (7, 2, 2, 11)),
                                     ("interTxTypeFacBits", "<i4", (4, 4, 17)), ("intraTxTypeFacBits", "<i4", (3, 4, 13, 17))])
-assert COEFF_RATE_TABLES_DTYPE.itemsize == 34088
-COEFF_RATE_DESC_DTYPE = np.dtype([("coeff_offset", "<u4"), ("iscan_offset", "<u4"), ("tx_type", "u1"), ("plane_type", "u1"),
-                                  ("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("is_inter", "u1"), ("intra_mode", "u1"),
-                                  ("reduced_tx_set", "u1"), ("reserved", "u1")])
-assert COEFF_RATE_DESC_DTYPE.itemsize == 16
-
-
-class TxSearchTu(C.Structure):
-    _fields_ = [("lambda_", C.c_uint64), ("src_offset", C.c_uint32), ("src_stride", C.c_uint32), ("pred_offset", C.c_uint32),
-                ("pred_stride", C.c_uint32), ("qparam_index", C.c_uint32), ("type_mask", C.c_uint16), ("tx_size", C.c_uint8),
-                ("is_inter", C.c_uint8), ("intra_mode", C.c_uint8), ("reduced_tx_set", C.c_uint8), ("txb_skip_ctx", C.c_uint8),
-                ("dc_sign_ctx", C.c_uint8), ("reserved", C.c_uint8 * 4)]
-
-
-assert C.sizeof(TxSearchTu) == 40
-
-
-class TxSearchResult(C.Structure):
-    _fields_ = [("full_cost", C.c_uint64), ("distortion", C.c_uint64 * 2), ("coeff_bits", C.c_uint64), ("candidate", C.c_uint32),
-                ("eob", C.c_uint16), ("tx_type", C.c_uint8), ("reserved", C.c_uint8)]
-
-
-assert C.sizeof(TxSearchResult) == 40
+COEFF_RATE_DESC_DTYPE = _abi.dtype("svthip_coeff_rate_desc")
+TxSearchTu = _abi.structure("svthip_tx_search_tu", lambda_="lambda")
+TxSearchResult = _abi.structure("svthip_tx_search_result")
 
 
 def tx_search_type_mask(tx_size: int, is_inter: bool, reduced_tx_set: bool, fast_tx_search: bool) -> int:

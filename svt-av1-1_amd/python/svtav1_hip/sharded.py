@@ -21,20 +21,12 @@ import ctypes as C
 
 import numpy as np
 
+from . import _abi
 from ._core import lib
 from ._me import sb_origins
 
-
-class ReconPicture(C.Structure):
-    """svthip_recon_picture"""
-    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("stride_y", C.c_uint32), ("stride_cb", C.c_uint32),
-                ("stride_cr", C.c_uint32), ("width", C.c_uint16), ("height", C.c_uint16), ("origin_x", C.c_uint16), ("origin_y", C.c_uint16),
-                ("sample_bytes", C.c_uint8), ("reserved", C.c_uint8 * 3)]
-
-
-class Xfer(C.Structure):
-    """svthip_xfer"""
-    _fields_ = [("peer", C.c_int32), ("plane", C.c_uint32), ("send", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+ReconPicture = _abi.structure("svthip_recon_picture")
+Xfer = _abi.structure("svthip_xfer")
 
 
 def _ccheck(rc: int):

@@ -11,6 +11,8 @@ import os
 
 import numpy as np
 
+from abi_util import svtav1_hip
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 VERY_LARGE = 30000
 PAD = 3
@@ -20,8 +22,7 @@ PRI_TAPS = np.array(((4, 2), (3, 3)), np.int64)
 SEC_TAPS = (2, 1)
 DIV_TABLE = (0, 840, 420, 280, 210, 168, 140, 120, 105)
 MSB = np.array([0] + [int(v).bit_length() - 1 for v in range(1, 1024)], np.int64)
-RESULT_DTYPE = np.dtype([("cdef_bits", "<i4"), ("nb_cdef_strengths", "<i4"), ("cdef_strengths", "<i4", (8,)), ("cdef_uv_strengths", "<i4", (8,)),
-                         ("pri_damping", "<i4"), ("sec_damping", "<i4"), ("sb_count", "<i4")])
+RESULT_DTYPE = svtav1_hip.CDEF_RESULT_DTYPE   # read from include/svtav1_hip.h by the package
 STAT_KEYS = ("copy", "pri0_sec", "adj0", "taps0", "taps1") + tuple(f"dir{d}" for d in range(8)) + (
     "clamp_min", "clamp_max", "border_top", "border_left", "border_bottom", "border_right", "frame_zero_pair", "frame_empty_list", "frame_filtered")
 

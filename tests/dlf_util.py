@@ -15,7 +15,9 @@ Planes are 2-D arrays of the plane's size (luma w x h, chroma w/2 x h/2); levels
 """
 import numpy as np
 
-LF_MI_DTYPE = np.dtype([("sb_type", "u1"), ("tx_size", "u1"), ("flags", "u1"), ("reserved", "u1")])
+from abi_util import svtav1_hip
+
+LF_MI_DTYPE = svtav1_hip.LF_MI_DTYPE   # read from include/svtav1_hip.h by the package
 
 # BlockSize and TxSize in the reference's enum order (Codec/EbDefinitions.h)
 BLOCK_W = np.array([4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64, 128, 128, 4, 16, 8, 32, 16, 64])

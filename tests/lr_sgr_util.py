@@ -8,6 +8,7 @@ from fractions import Fraction
 import numpy as np
 
 import lr_util as lu
+from abi_util import svtav1_hip
 
 RST_BITS, PRJ_BITS, SGR_BITS, MTABLE_BITS, RECIP_BITS = 4, 7, 8, 20, 12
 PRJ_MIN = (-96, -32)            # SGRPROJ_PRJ_MIN0, MIN1
@@ -21,8 +22,7 @@ SGR_S = ((140, 3236), (112, 2158), (93, 1618), (80, 1438), (70, 1295), (58, 1177
 X_BY_XPLUS1 = np.array([1] + [(256 * z + (z + 1) // 2) // (z + 1) for z in range(1, 255)] + [256], np.int64)
 ONE_BY_X = {9: 455, 25: 164}    # one_by_x[n - 1] = round(4096 / n)
 U32 = 0xffffffff
-DETAIL_DTYPE = np.dtype([("sums", "<i8", (5,)), ("exq", "<i4", (2,)), ("start_xqd", "<i4", (2,)), ("xqd", "<i4", (2,)), ("err", "<i8"),
-                         ("n_trials", "<i4"), ("reserved", "<i4")])
+DETAIL_DTYPE = svtav1_hip.SGRPROJ_DETAIL_DTYPE   # read from include/svtav1_hip.h by the package
 
 
 def new_box_stats():

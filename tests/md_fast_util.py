@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from abi_util import svtav1_hip
+
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "md_fast.npz")
 
 # the 22 AV1 block sizes, (width, height)
@@ -20,13 +22,9 @@ MAX_CANDIDATES, MAX_BUFFERS = 113, 13
 MAX_COST = np.uint64(0xFFFFFFFFFFFFFFFF)
 NO_MERGE = 0xFFFFFFFF
 
-DESC_DTYPE = np.dtype([("src_x", "<u2"), ("src_y", "<u2"), ("pred_x", "<u2"), ("pred_y", "<u2"), ("rate", "<u4"), ("merge_rate", "<u4"),
-                       ("lambda_", "<u4"), ("luma_given", "<u4"), ("has_uv", "u1"), ("flags", "u1"), ("reserved", "u1", (6,))])
-RESULT_DTYPE = np.dtype([("luma", "<u4"), ("chroma", "<u4"), ("cost", "<u8")])
-GROUP_DTYPE = np.dtype([("first", "<u4"), ("count", "<u2"), ("buffer_total_count", "u1"), ("buffer_width", "u1")])
-PICK_DTYPE = np.dtype([("best", "u1", (13,)), ("buffer_cand", "u1", (13,)), ("full_count", "u1"), ("disable_merge_index", "u1"),
-                       ("reserved", "u1", (4,))])
-assert (DESC_DTYPE.itemsize, RESULT_DTYPE.itemsize, GROUP_DTYPE.itemsize, PICK_DTYPE.itemsize) == (32, 16, 8, 32)
+# the layouts are the package's, which reads them from include/svtav1_hip.h
+DESC_DTYPE, RESULT_DTYPE, GROUP_DTYPE, PICK_DTYPE = (svtav1_hip.md_fast_desc_dtype(), svtav1_hip.md_fast_result_dtype(), svtav1_hip.md_fast_group_dtype(),
+                                                     svtav1_hip.md_fast_pick_dtype())
 
 
 def chroma_size(w, h):

@@ -16,6 +16,7 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 import inter_pred_util as ipu  # noqa: E402
 import md_fast_util as mfu  # noqa: E402
+from abi_util import svtav1_hip  # noqa: E402
 from gen_model_rd_tables import DIST, RATE, XSQ  # noqa: E402
 from md_fast_util import _texture  # noqa: E402
 
@@ -31,12 +32,9 @@ QUANTIZERS = (4, 8, 260, 1828)   # quantizer >> 3 == 0; the smallest step; a mid
 REFUSED = 0xFF
 MAX_XSQ_Q10 = 245727
 
-MODEL_DESC_DTYPE = np.dtype([("src_x", "<u2"), ("src_y", "<u2"), ("pred_x", "<u2"), ("pred_y", "<u2"), ("lambda_", "<u4"), ("rate", "<i4")])
-MODEL_RESULT_DTYPE = np.dtype([("sse", "<u4", (3,)), ("rate", "<i4"), ("dist", "<i8"), ("rd", "<i8")])
-IFS_DESC_DTYPE = np.dtype([("src_x", "<u2"), ("src_y", "<u2"), ("lambda_", "<u4"), ("filter_rate", "<i4", (2, 3))])
-IFS_RESULT_DTYPE = np.dtype([("interp_filters", "<u4"), ("switchable_rate", "<i4"), ("rd", "<i8"), ("skip_sse_sb", "<i8"), ("skip_txfm_sb", "u1"),
-                             ("best_trial", "u1"), ("reserved", "u1", (6,))])
-assert (MODEL_DESC_DTYPE.itemsize, MODEL_RESULT_DTYPE.itemsize, IFS_DESC_DTYPE.itemsize, IFS_RESULT_DTYPE.itemsize) == (16, 32, 32, 32)
+# the layouts are the package's, which reads them from include/svtav1_hip.h
+MODEL_DESC_DTYPE, MODEL_RESULT_DTYPE, IFS_DESC_DTYPE, IFS_RESULT_DTYPE = (svtav1_hip.md_model_rd_desc_dtype(), svtav1_hip.md_model_rd_result_dtype(),
+                                                                          svtav1_hip.md_ifs_desc_dtype(), svtav1_hip.md_ifs_result_dtype())
 
 
 def _i32(v):

@@ -1,6 +1,6 @@
-"""The Python package against include/svtav1_hip.h (no GPU needed): the signatures the package sets on the library are the header's, every
-struct mirror has the C struct's size and offsets, every constant that mirrors a #define equals it, and the package's public surface is
-the one recorded in tests/golden/binding_surface.json before the signatures were read from the header."""
+"""The Python package against include/svtav1_hip.h (no GPU needed): the signatures the package sets on the library are the header's, the
+layouts and constants the package reads from the header (_abi) are the compiler's for every struct and #define, every layout the package
+offers is one of those, and the package's public surface is the one recorded in tests/golden/binding_surface.json before the signatures were read from the header."""
 import ctypes as C
 import inspect
 import json
@@ -56,69 +56,104 @@ def test_every_prototype_is_bound_with_the_headers_types():
             _assert_is(fn.restype, ret, f"{name} returns")
 
 
-def _mirrors():
-    """(C struct, Python mirror) of every ctypes Structure and numpy dtype of the package"""
-    import svtav1_hip as s
-    from svtav1_hip import sharded as sh
-    return [("svthip_fullpel_desc", s.FullpelDesc), ("svthip_pa_picture", s.PaPictureDesc), ("svthip_me_params", s.MeParams),
-            ("svthip_sb_origin", s.SbOrigin), ("svthip_me_cu_result", s.MeCuResult), ("svthip_me_cu_result", s.ME_CU_RESULT_DTYPE),
-            ("svthip_quant_desc", s.QUANT_DESC_DTYPE), ("svthip_txfm_desc", s.TXFM_DESC_DTYPE), ("svthip_itxfm_desc", s.ITXFM_DESC_DTYPE),
-            ("svthip_tu_desc", s.TU_DESC_DTYPE), ("svthip_convolve_desc", s.CONVOLVE_DESC_DTYPE),
-            ("svthip_convolve_compound_desc", s.CONVOLVE_COMPOUND_DESC_DTYPE), ("svthip_inter_planes", s.InterPlanes),
-            ("svthip_inter_pu_desc", s.INTER_PU_DESC_DTYPE), ("svthip_warp_pu_desc", s.WARP_PU_DESC_DTYPE), ("svthip_intra_desc", s.INTRA_DESC_DTYPE),
-            ("svthip_cfl_desc", s.CFL_DESC_DTYPE), ("svthip_cfl_decision_job", s.CFL_DECISION_JOB_DTYPE), ("svthip_cfl_decision", s.CFL_DECISION_DTYPE),
-            ("svthip_lf_mi", s.LF_MI_DTYPE), ("svthip_lf_picture", s.LfPicture), ("svthip_cdef_picture", s.CdefPicture),
-            ("svthip_cdef_result", s.CDEF_RESULT_DTYPE), ("svthip_lr_picture", s.LrPicture), ("svthip_wiener_walk_state", s.WIENER_WALK_STATE_DTYPE),
-            ("svthip_sgrproj_detail", s.SGRPROJ_DETAIL_DTYPE), ("svthip_tu_result", s.TuResult), ("svthip_lv_map_coeff_cost", s.LV_MAP_COEFF_COST_DTYPE),
-            ("svthip_coeff_rate_tables", s.COEFF_RATE_TABLES_DTYPE), ("svthip_coeff_rate_desc", s.COEFF_RATE_DESC_DTYPE),
-            ("svthip_tx_search_tu", s.TxSearchTu), ("svthip_tx_search_result", s.TxSearchResult), ("svthip_me_cu_result_ref", s.ME_CU_RESULT_REF_DTYPE),
-            ("svthip_host_picture", s.HostPicture), ("svthip_ois_params", s.OisParams), ("svthip_recon_picture", sh.ReconPicture),
-            ("svthip_xfer", sh.Xfer)]
+# mirrors the recorded surface keeps in a form the header does not give: Python name -> C struct (the reason stands beside each in the package)
+HAND_WRITTEN = {"ME_CU_RESULT_REF_DTYPE": "svthip_me_cu_result_ref", "COEFF_RATE_TABLES_DTYPE": "svthip_coeff_rate_tables"}
+RENAMES = ({}, {"lambda_": "lambda"})   # the spellings of the C field `lambda` the package uses: dtype(x) and dtype(x, lambda_="lambda")
 
 
-RENAMED_FIELDS = {"lambda_": "lambda"}   # Python field -> C field
-# Python constant -> the #define it mirrors
-CONSTANTS = {"NUM_SQ_PU": "SVTHIP_NUM_SQ_PU", "MAX_SAD_VALUE": "SVTHIP_MAX_SAD_VALUE", "OPT_SADLOOP_GENERIC": "SVTHIP_OPT_SADLOOP_GENERIC",
-             "OPT_CONVOLVE_VALU": "SVTHIP_OPT_CONVOLVE_VALU", "OPT_TQ_MAX_WORKGROUPS": "SVTHIP_OPT_TQ_MAX_WORKGROUPS",
-             "HME_MAX_JOBS": "SVTHIP_HME_MAX_JOBS", "FRACTIONAL_SUB_SAD_SEARCH": "SVTHIP_FRACTIONAL_SUB_SAD_SEARCH",
-             "FRACTIONAL_FULL_SAD_SEARCH": "SVTHIP_FRACTIONAL_FULL_SAD_SEARCH", "FRACTIONAL_SSD_SEARCH": "SVTHIP_FRACTIONAL_SSD_SEARCH",
-             "CDEF_PICK_MAX_FB": "SVTHIP_CDEF_PICK_MAX_FB", "RESTORE_NONE": "SVTHIP_RESTORE_NONE", "RESTORE_WIENER": "SVTHIP_RESTORE_WIENER",
-             "RESTORE_SGRPROJ": "SVTHIP_RESTORE_SGRPROJ", "TU_RECON_SCRATCH": "SVTHIP_TU_RECON_SCRATCH"}
+def _header_struct_names():
+    """the name of every `typedef struct {...} name;`, read here a second time, independently of the package"""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    names, open_braces = [], []
+    for m in re.finditer(r"typedef\s+struct\b[^;{]*\{|[{}]", text):
+        if m.group(0) != "}":
+            open_braces.append(m.group(0) != "{")
+        elif open_braces.pop():   # the brace that closes a typedef struct: its name follows
+            names.append(re.match(r"\s*(\w+)\s*;", text[m.end():]).group(1))
+    return names
 
 
-def test_no_mirror_is_missing_from_the_table():
-    import svtav1_hip
-    from svtav1_hip import sharded
-    mirrors = _mirrors()
-    assert len(mirrors) == 37
-    for module in (svtav1_hip, sharded):
-        for name, v in vars(module).items():
-            if name.endswith("_DTYPE") or (isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure):
-                assert any(v is m for _, m in mirrors), f"{module.__name__}.{name} mirrors a C struct and is not in the table of this test"
+def _offsets(dt, prefix=""):
+    """(C member designator, offset) of every field of a dtype; the fields of a nested struct through its element [0] or the member itself"""
+    for k in dt.names:
+        sub, at = dt.fields[k][0], dt.fields[k][1]
+        yield prefix + k, at
+        if sub.base.names:
+            first = prefix + k + "[0]" * len(sub.shape) + "."
+            yield from ((name, at + o) for name, o in _offsets(sub.base, first))
 
 
-def test_layouts_and_constants_equal_the_headers():
-    import svtav1_hip
-    lines = ["#include <stddef.h>", '#include "svtav1_hip.h"']
-    for i, (cname, py) in enumerate(_mirrors()):
-        if isinstance(py, np.dtype):
-            size, fields = py.itemsize, [(k, py.fields[k][1]) for k in py.names]
-        else:
-            size, fields = C.sizeof(py), [(k, getattr(py, k).offset) for k, _ in py._fields_]
-        lines.append(f"typedef char m{i}_size[sizeof({cname}) == {size} ? 1 : -1];")
-        lines += [f"typedef char m{i}_{k}[offsetof({cname}, {RENAMED_FIELDS.get(k, k)}) == {o} ? 1 : -1];" for k, o in fields]
-    for py_name, define in CONSTANTS.items():
-        value = getattr(svtav1_hip, py_name)
-        assert isinstance(value, int)
-        lines.append(f"typedef char c_{py_name}[({define}) == {value} ? 1 : -1];")
-    lines.append("int main(void) { return 0; }")
+def _compile(lines, what):
     with tempfile.TemporaryDirectory() as tmp:
         c = os.path.join(tmp, "binding_layout.c")
         with open(c, "w") as f:
-            f.write("\n".join(lines) + "\n")
-        r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", c],
+            f.write("\n".join(["#include <stddef.h>", '#include "svtav1_hip.h"'] + [line for _, line in lines] + ["int main(void) { return 0; }"]) + "\n")
+        r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.dirname(HEADER), "-fsyntax-only", c],
                            capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+        # gcc names the failed typedef by its line: 3 is the first of `lines`
+        failed = sorted({lines[int(n) - 3][0] for n in re.findall(r"binding_layout\.c:(\d+):\d+: error", r.stderr) if 3 <= int(n) < 3 + len(lines)})
+        assert r.returncode == 0, f"{what} differ from the header: {failed}\n{r.stderr[:2000]}"
+
+
+def test_structs_are_exactly_the_headers():
+    from svtav1_hip import _abi
+    names = _header_struct_names()
+    assert len(names) == len(set(names)) >= 53
+    assert set(_abi.structs()) == set(names)
+
+
+def test_layouts_and_constants_equal_the_headers():
+    """sizeof and every offsetof of every struct of the header against what _abi derives, as numpy dtype and as ctypes Structure; the same for
+    the hand-written mirrors; every #define with a value against define()"""
+    import svtav1_hip
+    from svtav1_hip import _abi
+    lines = []
+    for cname in _abi.structs():
+        dt, st = _abi.dtype(cname), _abi.structure(cname)
+        assert dt.itemsize == C.sizeof(st) and dt.names == tuple(k for k, _ in st._fields_), cname
+        lines.append((cname, f"typedef char s{len(lines)}[sizeof({cname}) == {dt.itemsize} ? 1 : -1];"))
+        for k, o in _offsets(dt):
+            lines.append((f"{cname}.{k}", f"typedef char s{len(lines)}[offsetof({cname}, {k}) == {o} ? 1 : -1];"))
+        for k, _ in st._fields_:
+            lines.append((f"{cname}.{k}", f"typedef char s{len(lines)}[offsetof({cname}, {k}) == {getattr(st, k).offset} ? 1 : -1];"))
+            lines.append((f"{cname}.{k}", f"typedef char s{len(lines)}[sizeof((({cname} *)0)->{k}) == {getattr(st, k).size} ? 1 : -1];"))
+    for py_name, cname in HAND_WRITTEN.items():
+        dt = getattr(svtav1_hip, py_name)
+        lines.append((py_name, f"typedef char s{len(lines)}[sizeof({cname}) == {dt.itemsize} ? 1 : -1];"))
+        for k, o in _offsets(dt):
+            lines.append((f"{py_name}.{k}", f"typedef char s{len(lines)}[offsetof({cname}, {k}) == {o} ? 1 : -1];"))
+    defines = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SVTHIP_\w+)[ \t]+\S", re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S), flags=re.M)
+    assert len(defines) >= 44
+    mirrored = 0
+    for name in defines:
+        lines.append((name, f"typedef char s{len(lines)}[({name}) == {_abi.define(name)} ? 1 : -1];"))
+        if hasattr(svtav1_hip, name[len("SVTHIP_"):]):   # the package's constant of the same name is that value
+            value = getattr(svtav1_hip, name[len("SVTHIP_"):])
+            assert isinstance(value, int) and value == _abi.define(name), name
+            mirrored += 1
+    assert mirrored >= 30
+    _compile(lines, "layouts or constants")
+
+
+def test_every_layout_of_the_package_is_derived_from_the_header():
+    """every public numpy dtype, function returning one and ctypes Structure of the package is the object _abi derives for a header struct"""
+    import svtav1_hip
+    from svtav1_hip import _abi, sharded
+    derived = [f(cname, **r) for cname in _abi.structs() for r in RENAMES for f in (_abi.dtype, _abi.structure)
+               if set(r.values()) <= {k for k, _, _ in _abi.structs()[cname]}]
+    found = 0
+    for module in (svtav1_hip, sharded):
+        for name, v in vars(module).items():
+            if name.startswith("_"):
+                continue
+            if inspect.isfunction(v) and inspect.signature(v).return_annotation in ("np.dtype", np.dtype):
+                v = v()
+            if isinstance(v, np.dtype) or (isinstance(v, type) and issubclass(v, C.Structure)):
+                found += 1
+                assert name in HAND_WRITTEN or any(v is d for d in derived), f"{module.__name__}.{name} states a layout of its own"
+    assert found >= 50 and all(hasattr(svtav1_hip, k) for k in HAND_WRITTEN)
+    from svtav1_hip import _analysis
+    assert _analysis._Planes is _abi.structure("svthip_planes")
 
 
 def _ints(v):

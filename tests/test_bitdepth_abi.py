@@ -1,11 +1,10 @@
-"""The five entries of the 10-bit picture forms are declared in include/svtav1_hip.h, exported by the library and bound by the package; the
-header still compiles as C99 with the svthip_planes layout and the source-form constants the package assumes (no GPU needed)."""
+"""The five entries of the 10-bit picture forms are declared in include/svtav1_hip.h, exported by the library and bound by the package; 
+svthip_planes has 40 bytes and the source forms their values (no GPU needed; every size, offset and #define is held to the compiler's by
+tests/test_binding_vs_header.py)."""
 import ctypes
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -42,15 +41,4 @@ def test_header_compiles_as_c99_and_svthip_planes_matches_the_binding():
     p = svtav1_hip.make_planes([1, 2, 3], [4, 5, 6])
     t = type(p)
     assert ctypes.sizeof(t) == 40 and [int(v) for v in p.offset] == [1, 2, 3] and [int(v) for v in p.stride] == [4, 5, 6]
-    checks = [f"typedef char planes_size[sizeof(svthip_planes) == {ctypes.sizeof(t)} ? 1 : -1];"]
-    checks += [f"typedef char planes_{k}[offsetof(svthip_planes, {k}) == {getattr(t, k).offset} ? 1 : -1];" for k, _ in t._fields_]
-    for k in ("16BIT", "UNPACKED", "COMPRESSED"):
-        checks.append(f"typedef char form_{k}[SVTHIP_SSE_SRC_{k} == {getattr(svtav1_hip, 'SSE_SRC_' + k)} ? 1 : -1];")
-    src = '#include <stddef.h>\n#include "svtav1_hip.h"\n' + "\n".join(checks) + "\nint main(void) { return 0; }\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        c = os.path.join(tmp, "bitdepth_layout.c")
-        with open(c, "w") as f:
-            f.write(src)
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", c],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+    assert (svtav1_hip.SSE_SRC_16BIT, svtav1_hip.SSE_SRC_UNPACKED, svtav1_hip.SSE_SRC_COMPRESSED) == (0, 1, 2)

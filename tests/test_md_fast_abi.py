@@ -1,11 +1,9 @@
-"""The fast-loop entries are declared in include/svtav1_hip.h, exported by the library and bound by the package; the header still compiles
-as C99 with the struct sizes and offsets the package's layouts and the restatement assume (no GPU needed)."""
+"""The fast-loop entries are declared in include/svtav1_hip.h, exported by the library and bound by the package; the structs have the sizes the
+restatement assumes and the flags its values (no GPU needed; the compiler's sizes, offsets and constants are held for every struct and #define by tests/test_binding_vs_header.py)."""
 import ctypes
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -36,25 +34,12 @@ def test_header_declares_library_exports_and_package_binds_every_entry():
 
 
 def test_header_compiles_as_c99_and_the_structs_match_the_binding():
+    import abi_util
     import md_fast_util as mu
     import svtav1_hip
-    layouts = {"svthip_md_fast_desc": (svtav1_hip.md_fast_desc_dtype(), mu.DESC_DTYPE, 32), "svthip_md_fast_result": (svtav1_hip.md_fast_result_dtype(), mu.RESULT_DTYPE, 16),
-               "svthip_md_fast_group": (svtav1_hip.md_fast_group_dtype(), mu.GROUP_DTYPE, 8), "svthip_md_fast_pick": (svtav1_hip.md_fast_pick_dtype(), mu.PICK_DTYPE, 32)}
-    checks = []
-    for cname, (dt, restated, size) in layouts.items():
-        assert dt == restated and dt.itemsize == size, cname
-        checks.append(f"typedef char {cname}_size[sizeof({cname}) == {size} ? 1 : -1];")
-        checks += [f"typedef char {cname}_{k}[offsetof({cname}, {k.rstrip('_')}) == {dt.fields[k][1]} ? 1 : -1];" for k in dt.names]
+    abi_util.assert_sizes((svtav1_hip.md_fast_desc_dtype(), 32), (svtav1_hip.md_fast_result_dtype(), 16), (svtav1_hip.md_fast_group_dtype(), 8),
+                          (svtav1_hip.md_fast_pick_dtype(), 32))
     flags = {"LUMA_GIVEN": mu.LUMA_GIVEN, "SKIP_DISTORTION": mu.SKIP_DISTORTION, "INVALID": mu.INVALID, "CHROMA_QUARTER": mu.CHROMA_QUARTER,
              "TYPE_INTER": mu.TYPE_INTER, "MAX_CANDIDATES": mu.MAX_CANDIDATES, "MAX_BUFFERS": mu.MAX_BUFFERS}
     for k, v in flags.items():
         assert getattr(svtav1_hip, f"MD_FAST_{k}") == v
-        checks.append(f"typedef char flag_{k}[SVTHIP_MD_FAST_{k} == {v} ? 1 : -1];")
-    src = '#include <stddef.h>\n#include "svtav1_hip.h"\n' + "\n".join(checks) + "\nint main(void) { return 0; }\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        c = os.path.join(tmp, "md_fast_layout.c")
-        with open(c, "w") as f:
-            f.write(src)
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", c],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
