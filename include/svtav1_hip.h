@@ -51,10 +51,11 @@ void *svthip_stream(svthip_ctx *ctx);
 int32_t svthip_synchronize(svthip_ctx *ctx);
 
 /* Pre-size the context-owned device scratch for whole-picture ME calls of up to n_jobs pictures of width x height with n_pu (85 or
- * 209) PUs per SB, so that no later call allocates (where the reference sizes MeContext_t's buffers once in MeContextCtor,
- * Codec/EbMotionEstimationContext.c:28-122).  host_forms != 0 also sizes what svthip_motion_estimate_picture (host pointers) needs.
- * Optional: every entry grows its scratch on demand, stream-ordered (hipMallocAsync / hipFreeAsync on the stream that last used the
- * context's scratch -- never a device-wide synchronisation under other contexts' work). */
+ * 209) PUs per SB (849: for the svthip_me_inloop_* entries alone), so that no later call allocates (where the reference sizes
+ * MeContext_t's buffers once in MeContextCtor, Codec/EbMotionEstimationContext.c:28-122).  host_forms != 0 also sizes what
+ * svthip_motion_estimate_picture (host pointers) needs.  Optional: every entry grows its scratch on demand, stream-ordered
+ * (hipMallocAsync / hipFreeAsync on the stream that last used the context's scratch -- never a device-wide synchronisation under other
+ * contexts' work). */
 int32_t svthip_reserve(svthip_ctx *ctx, uint32_t width, uint32_t height, uint32_t n_pu, uint32_t n_jobs, int32_t host_forms);
 
 /* Kernel-selection overrides of ONE context, default 0.  Two entries have a specialised kernel for the common shapes and a general
@@ -441,6 +442,111 @@ int32_t svthip_motion_estimate209_batch_dev(svthip_ctx *ctx, const uint8_t *d_po
                                             const svthip_me_params *params, int32_t use_subpel_flag, int32_t cu8x8_mode,
                                             const svthip_sb_origin *d_sb, uint32_t n_sb, svthip_me_cu_result *d_out,
                                             uint32_t *d_list_sad, uint32_t *d_list_mv, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * In-loop motion estimation: the second motion search, in front of mode decision, on the RECONSTRUCTED reference pictures.
+ * Replaces in_loop_motion_estimation_sblock (Source/Lib/Codec/EbProductCodingLoop.c:6300-6733) as EncDecKernel calls it
+ * (Codec/EbEncDecProcess.c:1502-1580) for 64x64 superblocks: a vector for each of the 849 blocks of a superblock, 64x64 down to 4x4 with
+ * every rectangular shape, one reference list per call (the caller loops over lists as numOfListToSearch does, :6374).  Mode decision
+ * takes its NEWMV vector from it for every block with a side of 4 (use_close_loop_me, Codec/EbModeDecision.c:1230-1283).
+ *
+ * State of the reference: the search is compiled, linked and exposed as the encoder option -in-loop-me (in_loop_me_flag, default on,
+ * Codec/EbEncHandle.c:2584), but this snapshot sets DISABLE_IN_LOOP_ME 1 (Codec/EbDefinitions.h:129, used at
+ * Codec/EbPictureDecisionProcess.c:1333-1337), so as shipped the flag is forced off.  The function is intact and executes; an integrator
+ * who flips that macro needs these entries, as svthip_me_subpel_search_dev offers arms MotionEstimateLcu does not take.
+ *
+ * Built: the centres (EbEncDecProcess.c:1558-1563), the search-area rules (:6389-6452), the full-pel search with the whole SAD over all
+ * four rows of a 4x4 (Compute4x4SAD_Kernel, :2894-2917) and the sum tree in_loop_me_8xN_Nx8_ .. in_loop_me_64xN_Nx64_distortion_update
+ * (:3025-3528) in the nesting order of in_loop_me_get_search_point_results_block (:3605-3878) over the raster walk of
+ * in_loop_me_fullpel_search_sblock (:3884-3911); for use_subpel_flag = 1 in_loop_me_interpolate_search_region_avc_style (:4007-4094),
+ * in_loop_me_halfpel_search_sblock (:4304-4984) and in_loop_me_quarterpel_search_sblock (:5320-5990) in the arm the reference compiles,
+ * USE_INLOOP_ME_FULL_SAD 0; and the reorder into inloop_me_mv (:6626-6728).  context_ptr->fractionalSearchMethod is assigned at :6367 and
+ * never read.
+ * Left out:
+ *   - 128x128 superblocks (3401 blocks, the quad loops, the area rule of :6412-6423, the averaged centres of EbEncDecProcess.c:1532-1555);
+ *   - the USE_INLOOP_ME_FULL_SAD 1 arm of the refinement; bi-prediction (the reference has only a comment there, :6623);
+ *   - the in-function 10-bit extraction of :6456-6480: a 10-bit caller passes the 8-bit plane svthip_pa_unpack_10bit_dev extracts once per
+ *     reference, which is the same >> 2;
+ *   - get_in_loop_me_info_index, a host table look-up into the order svthip_me_inloop_pack_dev leaves.
+ *
+ * d_best_sad / d_best_mv: [n_sb][849] in the reference's buffer order, that of p_sb_best_sad / p_sb_best_mv with the start_idx_* offsets
+ * of :6346-6363 -- 4x4 at 0, 8x8 at 256, 16x16 at 320, 32x32 at 336, 64x64 at 340, 8x4 at 341, 4x8 at 469, 4x16 at 597, 16x4 at 661,
+ * 16x8 at 725, 8x16 at 757, 32x8 at 789, 8x32 at 805, 32x16 at 821, 16x32 at 829, 64x16 at 837, 16x64 at 841, 64x32 at 845, 32x64 at
+ * 847 -- z-order within a shape.  The vector word is (uint16)(4*y) << 16 | (uint16)(4*x) (:3619-3621); the first minimum in raster order
+ * wins (strict '<' from MAX_SAD_VALUE).  Source samples outside the picture count as 0 against whatever the padded reference holds
+ * (EbEncDecProcess.c:1516-1521) and all 849 blocks are still searched: hence sb_width / sb_height.
+ *
+ * Border of the reference plane: the window of a superblock reaches from 63 samples left of and above the picture (the clip arms of
+ * :6398-6400 and :6431-6433) to 63 samples beyond its right and bottom edge (a first position at most on the last column / row,
+ * :6407-6409 and :6440-6442, plus a 64x64 block); the kernels read exactly that and nothing beyond, so 64 samples each way suffice
+ * (the reference's 160 cover it).  The sub-pel refinement interpolates what its two walks can read and no more -- the reference rounds the
+ * interpolated width up to a multiple of 8, the library does not -- which takes reference samples from 2 before the window to 66 beyond
+ * its last position: 65 samples left of and above the picture, 66 beyond its right and bottom edge; 68 each way cover it.
+ * All entries: device pointers, launches on `stream` (NULL = the context's), no host synchronisation; scratch grows on demand, is
+ * stream-ordered, and svthip_reserve sizes it when asked for n_pu = 849. */
+#define SVTHIP_INLOOP_ME_PU_COUNT 849
+#define SVTHIP_INLOOP_BLOCKS_ALL     0   /* all 849, as the reference computes them */
+#define SVTHIP_INLOOP_BLOCKS_SIDE_4  1   /* the 640 blocks mode decision reads at 64x64 superblocks: 4x4, 8x4, 4x8, 16x4, 4x16 */
+
+typedef struct svthip_inloop_desc {     /* eight int32 per superblock and list */
+    int32_t src_offset, ref_offset;     /* as svthip_fullpel_desc: SB's first source sample; search position (0,0) in the reference plane */
+    int32_t x_search_area_origin, y_search_area_origin, search_area_width, search_area_height;   /* after :6389-6446 */
+    int32_t sb_width, sb_height;        /* samples of the SB inside the picture (EbEncDecProcess.c:1512-1513) */
+} svthip_inloop_desc;
+
+/* The search centres (EbEncDecProcess.c:1558-1563): d_me are the per-superblock result rows svthip_motion_estimate_*_dev leaves, row
+ * stride me_pu_stride = 85 or 209; d_center = int16 [n_sb][2], the 64x64 block's vector of list `list_index` (0 or 1), >> 2. */
+int32_t svthip_me_inloop_centers_dev(svthip_ctx *ctx, const svthip_me_cu_result *d_me, uint32_t me_pu_stride, uint32_t list_index,
+                                     uint32_t n_sb, int16_t *d_center, void *stream);
+
+/* The search areas (:6389-6452 without the 128x128 arm, the MAX(1, ..) arms included), one thread per superblock: d_center as above,
+ * d_sb the superblock origins, the picture's width and height, stride and origin of the source and of the reference plane, the requested
+ * area (1..127 each way: the function clamps with MIN(.., 127), EncDecKernel asks for 64).  Leaves d_desc[n_sb].
+ * Refused, because the windows the rules allow would leave the planes: a reference plane with ref_origin_x or ref_origin_y below 63 or
+ * ref_stride below ref_origin_x + pic_width + 63 (the border stated above; 66 in the one-call entry with use_subpel; the caller
+ * guarantees as many rows below the picture), a source plane with src_stride below src_origin_x + pic_width, and planes whose offsets
+ * do not fit 31 bits. */
+int32_t svthip_me_inloop_area_dev(svthip_ctx *ctx, const int16_t *d_center, const svthip_sb_origin *d_sb, uint32_t n_sb, uint32_t pic_width,
+                                  uint32_t pic_height, uint32_t src_stride, uint32_t src_origin_x, uint32_t src_origin_y, uint32_t ref_stride,
+                                  uint32_t ref_origin_x, uint32_t ref_origin_y, uint32_t search_area_width, uint32_t search_area_height,
+                                  svthip_inloop_desc *d_desc, void *stream);
+
+/* The full-pel search (:3884-3911).  block_set SVTHIP_INLOOP_BLOCKS_ALL: both arrays are fully overwritten.  SVTHIP_INLOOP_BLOCKS_SIDE_4:
+ * the 640 blocks with a side of 4 are written, the sums of the others are not computed and their 209 slots are left untouched.
+ * d_desc is meant to be what svthip_me_inloop_area_dev left: like the other per-SB plane searches this entry cannot see the planes'
+ * sizes and trusts src_offset and ref_offset (the source block and the window of area + 63 samples each way must lie inside the planes);
+ * an area outside 1..127 is searched as the nearest legal one.  The areas are on the device, so the launch asks for the LDS of the largest
+ * legal window (44.8 KB) whatever they are; svthip_me_inloop_search_dev asks for that of the requested area (24.3 KB for 64x64). */
+int32_t svthip_me_inloop_fullpel_search_dev(svthip_ctx *ctx, const uint8_t *d_src_plane, uint32_t src_stride, const uint8_t *d_ref_plane,
+                                            uint32_t ref_stride, const svthip_inloop_desc *d_desc, uint32_t n_sb, int32_t block_set,
+                                            uint32_t *d_best_sad, uint32_t *d_best_mv, void *stream);
+
+/* The sub-pel refinement of use_subpel_flag = 1 (:6575-6619), refining both arrays in place; same arguments as the full-pel entry, whose
+ * results it starts from.  Every candidate costs twice its SAD over every second row (NxMSadKernel / NxMSadAveragingKernel with doubled
+ * strides and half the height; for blocks 4 high that is rows 0 and 2) and is compared, with a strict '<', against a best value the
+ * full-pel stage left as a whole SAD.  The three interpolated planes of a superblock live in context scratch (112 KB per superblock and
+ * list).  Reproduced from the reference: neither of its walks has a loop for 4x16, 16x4, 64x16 or 16x64, so those 136 blocks keep their
+ * full-pel result; the quarter-pel walk of the 32x32 blocks forms block_shift_y without its << 5 (:5965), so the two lower 32x32 blocks
+ * are measured one row below the upper ones; the quarter-pel valid* tables (:5021-5043), the buffer pairs of
+ * set_quarterpel_refinement_inputs_on_the_fly_block (:5229-5314) and the first-match psub_pel_direction order (:4269-4295). */
+int32_t svthip_me_inloop_subpel_search_dev(svthip_ctx *ctx, const uint8_t *d_src_plane, uint32_t src_stride, const uint8_t *d_ref_plane,
+                                           uint32_t ref_stride, const svthip_inloop_desc *d_desc, uint32_t n_sb, int32_t block_set,
+                                           uint32_t *d_best_sad, uint32_t *d_best_mv, void *stream);
+
+/* The reorder into inloop_me_mv (:6626-6728): d_inloop_mv = int16 [n_sb][849][2], x then y in quarter-pel units, in the candidate order of
+ * :6635-6727 (raster within a shape) -- the index get_in_loop_me_info_index addresses.  The reference's tab4x16 (:3005-3010) is not the
+ * inverse of its walk's order, so 32 of the 64 4x16 candidates carry the vector of another 4x16 block; that is what mode decision reads,
+ * and it is reproduced. */
+int32_t svthip_me_inloop_pack_dev(svthip_ctx *ctx, const uint32_t *d_best_mv, uint32_t n_sb, int16_t *d_inloop_mv, void *stream);
+
+/* Areas, full-pel search, the sub-pel refinement when use_subpel != 0, and the reorder of one list in one call on one stream; the
+ * descriptors and the interpolated planes live in context scratch.  With use_subpel the reference plane needs the border of 66.  d_best_sad / d_best_mv as the full-pel entry leaves them; d_inloop_mv as the pack entry leaves it. */
+int32_t svthip_me_inloop_search_dev(svthip_ctx *ctx, const uint8_t *d_src_plane, uint32_t src_stride, uint32_t src_origin_x,
+                                    uint32_t src_origin_y, const uint8_t *d_ref_plane, uint32_t ref_stride, uint32_t ref_origin_x,
+                                    uint32_t ref_origin_y, uint32_t pic_width, uint32_t pic_height, const int16_t *d_center,
+                                    const svthip_sb_origin *d_sb, uint32_t n_sb, uint32_t search_area_width, uint32_t search_area_height,
+                                    int32_t use_subpel, int32_t block_set, uint32_t *d_best_sad, uint32_t *d_best_mv, int16_t *d_inloop_mv,
+                                    void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Picture-analysis producers of the ME inputs, on the device.  The host uploads the padded full-resolution

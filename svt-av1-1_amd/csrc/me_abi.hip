@@ -186,6 +186,36 @@ int32_t motion_estimate_batch_common(svthip_ctx* ctx, const uint8_t* d_pool, con
     return SVTHIP_OK;
 }
 
+// what the in-loop search checks of its planes and its request
+int32_t check_inloop_block_set(int32_t block_set)
+{
+    if (block_set != SVTHIP_INLOOP_BLOCKS_ALL && block_set != SVTHIP_INLOOP_BLOCKS_SIDE_4)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "block_set must be 0 (all 849 blocks) or 1 (the 640 with a side of 4), got %d", (int)block_set);
+    return SVTHIP_OK;
+}
+
+int32_t check_inloop_area(uint32_t sw, uint32_t sh)
+{
+    if (sw < 1 || sw > 127 || sh < 1 || sh > 127) return fail(SVTHIP_ERR_BAD_PARAMETER, "search area must be 1..127 (got %d)", (int)(sw > sh ? sw : sh));
+    return SVTHIP_OK;
+}
+
+// the picture and its two planes: the windows the area rules allow reach `border` samples beyond the picture each way (63 for the
+// full-pel search, 66 with the sub-pel refinement) and must stay in the plane
+int32_t check_inloop_picture(uint32_t w, uint32_t h, uint32_t src_stride, uint32_t src_origin_x, uint32_t src_origin_y, uint32_t ref_stride,
+                             uint32_t ref_origin_x, uint32_t ref_origin_y, uint32_t border = 63)
+{
+    if (!w || !h || w > 16384 || h > 16384) return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be 1..16384 (width %d)", (int)w);
+    if ((uint64_t)src_origin_x + w > src_stride)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "src_stride must be at least src_origin_x + pic_width (got %d)", (int)src_stride);
+    if (ref_origin_x < border || ref_origin_y < border || (uint64_t)ref_origin_x + w + border > ref_stride)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "the reference plane needs a border of %d samples: origins and ref_stride - ref_origin_x - pic_width at least that (got %d)",
+                    (int)border, (int)ref_stride);
+    if (((uint64_t)src_origin_y + h) * src_stride > 0x7fffffffull || ((uint64_t)ref_origin_y + h + border) * ref_stride > 0x7fffffffull)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "plane offsets must fit 31 bits");
+    return SVTHIP_OK;
+}
+
 // the branch of the open-loop intra search that reads the ME distortions
 bool ois_reads_me(const svthip_ois_params* p)
 {
@@ -344,6 +374,103 @@ int32_t svthip_sad_loop_batch_dev(svthip_ctx* ctx, const uint8_t* d_src, uint32_
         return fail(SVTHIP_ERR_BAD_PARAMETER, "block + search window too large for the LDS slice (%d bytes)", (int)slice);
     HIP_TRY(svthip::launch_sad_loop(d_src, src_stride, d_ref, ref_stride, ref_stride_raw, d_desc, n_blocks, (int)width, (int)height, (int)search_area_width,
                                     (int)search_area_height, generic, d_best_sad, d_best_xy, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+// ---------------------------------------------------------------- in-loop motion estimation
+
+int32_t svthip_me_inloop_centers_dev(svthip_ctx* ctx, const svthip_me_cu_result* d_me, uint32_t me_pu_stride, uint32_t list_index, uint32_t n_sb,
+                                     int16_t* d_center, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_n_pu(me_pu_stride));
+    if (list_index > 1) return fail(SVTHIP_ERR_BAD_PARAMETER, "list_index must be 0 or 1");
+    if (n_sb == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_me, d_center}));
+    HIP_TRY(svthip::launch_inloop_centers(d_me, me_pu_stride, list_index, n_sb, d_center, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_me_inloop_area_dev(svthip_ctx* ctx, const int16_t* d_center, const svthip_sb_origin* d_sb, uint32_t n_sb, uint32_t pic_width,
+                                  uint32_t pic_height, uint32_t src_stride, uint32_t src_origin_x, uint32_t src_origin_y, uint32_t ref_stride,
+                                  uint32_t ref_origin_x, uint32_t ref_origin_y, uint32_t search_area_width, uint32_t search_area_height,
+                                  svthip_inloop_desc* d_desc, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_inloop_area(search_area_width, search_area_height));
+    TRY(check_inloop_picture(pic_width, pic_height, src_stride, src_origin_x, src_origin_y, ref_stride, ref_origin_x, ref_origin_y));
+    if (n_sb == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_center, d_sb, d_desc}));
+    HIP_TRY(svthip::launch_inloop_area(d_center, d_sb, n_sb, pic_width, pic_height, src_stride, src_origin_x, src_origin_y, ref_stride, ref_origin_x,
+                                       ref_origin_y, search_area_width, search_area_height, d_desc, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_me_inloop_fullpel_search_dev(svthip_ctx* ctx, const uint8_t* d_src_plane, uint32_t src_stride, const uint8_t* d_ref_plane,
+                                            uint32_t ref_stride, const svthip_inloop_desc* d_desc, uint32_t n_sb, int32_t block_set,
+                                            uint32_t* d_best_sad, uint32_t* d_best_mv, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_inloop_block_set(block_set));
+    if (n_sb == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_src_plane, d_ref_plane, d_desc, d_best_sad, d_best_mv}));
+    // the areas are on the device: the window is sized for the largest legal one
+    HIP_TRY(svthip::launch_inloop_fullpel(d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, 127, 127, block_set == SVTHIP_INLOOP_BLOCKS_ALL,
+                                          d_best_sad, d_best_mv, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_me_inloop_subpel_search_dev(svthip_ctx* ctx, const uint8_t* d_src_plane, uint32_t src_stride, const uint8_t* d_ref_plane,
+                                           uint32_t ref_stride, const svthip_inloop_desc* d_desc, uint32_t n_sb, int32_t block_set,
+                                           uint32_t* d_best_sad, uint32_t* d_best_mv, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_inloop_block_set(block_set));
+    if (n_sb == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_src_plane, d_ref_plane, d_desc, d_best_sad, d_best_mv}));
+    TRY(ensure_scratch(ctx, SLOT_INLOOP_PLANES, svthip::inloop_planes_bytes(n_sb)));
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(scratch_on_stream(ctx, s));
+    HIP_TRY(svthip::launch_inloop_subpel(d_src_plane, src_stride, d_ref_plane, ref_stride, d_desc, n_sb, block_set == SVTHIP_INLOOP_BLOCKS_ALL,
+                                         slot_ptr<uint8_t>(ctx, SLOT_INLOOP_PLANES), d_best_sad, d_best_mv, s));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_me_inloop_pack_dev(svthip_ctx* ctx, const uint32_t* d_best_mv, uint32_t n_sb, int16_t* d_inloop_mv, void* stream)
+{
+    TRY(enter(ctx));
+    if (n_sb == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_best_mv, d_inloop_mv}));
+    HIP_TRY(svthip::launch_inloop_pack(d_best_mv, n_sb, d_inloop_mv, call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_me_inloop_search_dev(svthip_ctx* ctx, const uint8_t* d_src_plane, uint32_t src_stride, uint32_t src_origin_x, uint32_t src_origin_y,
+                                    const uint8_t* d_ref_plane, uint32_t ref_stride, uint32_t ref_origin_x, uint32_t ref_origin_y, uint32_t pic_width,
+                                    uint32_t pic_height, const int16_t* d_center, const svthip_sb_origin* d_sb, uint32_t n_sb,
+                                    uint32_t search_area_width, uint32_t search_area_height, int32_t use_subpel, int32_t block_set,
+                                    uint32_t* d_best_sad, uint32_t* d_best_mv, int16_t* d_inloop_mv, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_inloop_block_set(block_set));
+    TRY(check_inloop_area(search_area_width, search_area_height));
+    TRY(check_inloop_picture(pic_width, pic_height, src_stride, src_origin_x, src_origin_y, ref_stride, ref_origin_x, ref_origin_y, use_subpel ? 66 : 63));
+    if (n_sb == 0) return SVTHIP_OK;
+    TRY(check_non_null({d_src_plane, d_ref_plane, d_center, d_sb, d_best_sad, d_best_mv, d_inloop_mv}));
+    TRY(ensure_scratch(ctx, SLOT_INLOOP_DESC, inloop_desc_bytes(n_sb)));
+    if (use_subpel) TRY(ensure_scratch(ctx, SLOT_INLOOP_PLANES, svthip::inloop_planes_bytes(n_sb)));
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(scratch_on_stream(ctx, s));
+    svthip_inloop_desc* desc = slot_ptr<svthip_inloop_desc>(ctx, SLOT_INLOOP_DESC);
+    HIP_TRY(svthip::launch_inloop_area(d_center, d_sb, n_sb, pic_width, pic_height, src_stride, src_origin_x, src_origin_y, ref_stride, ref_origin_x,
+                                       ref_origin_y, search_area_width, search_area_height, desc, s));
+    // the rules only ever shrink the requested area
+    HIP_TRY(svthip::launch_inloop_fullpel(d_src_plane, src_stride, d_ref_plane, ref_stride, desc, n_sb, search_area_width, search_area_height,
+                                          block_set == SVTHIP_INLOOP_BLOCKS_ALL, d_best_sad, d_best_mv, s));
+    if (use_subpel)
+        HIP_TRY(svthip::launch_inloop_subpel(d_src_plane, src_stride, d_ref_plane, ref_stride, desc, n_sb, block_set == SVTHIP_INLOOP_BLOCKS_ALL,
+                                             slot_ptr<uint8_t>(ctx, SLOT_INLOOP_PLANES), d_best_sad, d_best_mv, s));
+    HIP_TRY(svthip::launch_inloop_pack(d_best_mv, n_sb, d_inloop_mv, s));
     return SVTHIP_OK;
 }
 

@@ -29,6 +29,20 @@ hipError_t launch_subpel_planes(const uint8_t* src, uint32_t src_stride, const u
                                 uint32_t* pred_out, int method, hipStream_t s);
 SVTHIP_LOCAL hipError_t subpel_planes_raise_dynamic_lds();
 
+// me_inloop.hip: in-loop motion estimation of 64x64 superblocks, 849 blocks each (me_inloop_kernels.h).  max_sw / max_sh bound the areas of
+// desc and size the LDS window; all_blocks false: the 640 blocks with a side of 4 only.
+hipError_t launch_inloop_centers(const svthip_me_cu_result* me, uint32_t me_stride, uint32_t list_index, uint32_t n_sb, int16_t* center, hipStream_t s);
+hipError_t launch_inloop_area(const int16_t* center, const svthip_sb_origin* sbs, uint32_t n_sb, uint32_t pic_width, uint32_t pic_height,
+                              uint32_t src_stride, uint32_t src_origin_x, uint32_t src_origin_y, uint32_t ref_stride, uint32_t ref_origin_x,
+                              uint32_t ref_origin_y, uint32_t area_width, uint32_t area_height, svthip_inloop_desc* desc, hipStream_t s);
+hipError_t launch_inloop_fullpel(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, const svthip_inloop_desc* desc,
+                                 uint32_t n_sb, uint32_t max_sw, uint32_t max_sh, bool all_blocks, uint32_t* best_sad, uint32_t* best_mv, hipStream_t s);
+// the sub-pel refinement in place: three half-pel planes per superblock into `planes` (inloop_planes_bytes(n_sb) bytes), then both walks
+size_t inloop_planes_bytes(size_t n_sb);
+hipError_t launch_inloop_subpel(const uint8_t* src, uint32_t src_stride, const uint8_t* ref, uint32_t ref_stride, const svthip_inloop_desc* desc,
+                                uint32_t n_sb, bool all_blocks, uint8_t* planes, uint32_t* best_sad, uint32_t* best_mv, hipStream_t s);
+hipError_t launch_inloop_pack(const uint32_t* best_mv, uint32_t n_sb, int16_t* inloop_mv, hipStream_t s);
+
 // me_bipred.hip: bi-prediction and packing.  n_lists 1: only list 0 is read (ref1, desc1, sad1, mv1 may be null) and no window is
 // staged.  209-PU mode: the squares' bi-pred SADs go through bisad_sq ([n_sb][85], needed with two lists) to the kernel that packs all
 // 209 PUs.  The stored form averages the predictions the sub-pel kernel left in pred0 / pred1 instead of interpolating again.

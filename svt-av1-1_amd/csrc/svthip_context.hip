@@ -302,9 +302,14 @@ int32_t svthip_reserve(svthip_ctx* ctx, uint32_t width, uint32_t height, uint32_
     TRY(enter(ctx));
     if ((width & 7) || (height & 7) || !width || !height || width > 16384 || height > 16384)
         return fail(SVTHIP_ERR_BAD_PARAMETER, "picture dimensions must be non-zero multiples of 8 (width %d)", (int)width);
-    TRY(check_n_pu(n_pu));
     if (n_jobs == 0) n_jobs = 1;
     const size_t n_sb = sb_count(width, height), n = n_sb * n_jobs;
+    if (n_pu == SVTHIP_INLOOP_ME_PU_COUNT)   // the in-loop search: its descriptors are all the scratch it has
+    {
+        TRY(ensure_scratch(ctx, SLOT_INLOOP_DESC, inloop_desc_bytes(n)));
+        return ensure_scratch(ctx, SLOT_INLOOP_PLANES, svthip::inloop_planes_bytes(n));
+    }
+    TRY(check_n_pu(n_pu));
     TRY(ensure_scratch(ctx, SLOT_ME_CHAIN, me_chain_layout(n, n_pu).total));
     TRY(ensure_scratch(ctx, SLOT_BIPRED_SQ, bipred_sq_bytes(n)));
     TRY(ensure_scratch(ctx, SLOT_ME_PRED, me_pred_bytes(n, n_pu)));

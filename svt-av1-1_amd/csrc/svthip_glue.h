@@ -27,6 +27,8 @@ enum Slot {
     SLOT_FILM_GRAIN_TABLES,  // the table block of the one-call film-grain form: SVTHIP_FILM_GRAIN_TABLES_BYTES
     SLOT_MD_IFS,          // trial descriptors, results and tiles of svthip_md_interp_filter_search_batch_dev: svthip::md_ifs_layout
     SLOT_PA_SSE_PARTIALS, // workgroup sums of the picture SSE entries on their way to d_sse: svthip::pa_sse_partial_bytes
+    SLOT_INLOOP_DESC,     // search areas of svthip_me_inloop_search_dev on their way to its full-pel search: inloop_desc_bytes
+    SLOT_INLOOP_PLANES,   // half-pel planes of the in-loop sub-pel refinement, three per (picture, SB): svthip::inloop_planes_bytes
     SLOT_COUNT
 };
 
@@ -84,6 +86,8 @@ SVTHIP_LOCAL inline MeChainLayout me_chain_layout(size_t n, uint32_t n_pu)
     const size_t state_b = ((sizeof(int16_t) * SVTHIP_HME_STATE_INT16 * n) + 15) & ~(size_t)15;
     return {{0, desc_b}, {arrays, arrays + arr_b}, {arrays + 2 * arr_b, arrays + 3 * arr_b}, arrays + 4 * arr_b, arrays + 4 * arr_b + state_b + 64};
 }
+
+SVTHIP_LOCAL inline size_t inloop_desc_bytes(size_t n) { return sizeof(svthip_inloop_desc) * n; }  // SLOT_INLOOP_DESC: one per (picture, SB)
 
 SVTHIP_LOCAL inline size_t bipred_sq_bytes(size_t n) { return sizeof(uint32_t) * 85 * n; }  // SLOT_BIPRED_SQ: [n][85] SADs
 

@@ -12,7 +12,8 @@ from __future__ import annotations
 from ._core import (LIB_PATH, OPT_CONVOLVE_VALU, OPT_SADLOOP_GENERIC, OPT_TQ_MAX_WORKGROUPS, ContextCore, SvtHipError, lib, u8p,
                     u32p)
 from ._me import (FRACTIONAL_FULL_SAD_SEARCH, FRACTIONAL_SSD_SEARCH, FRACTIONAL_SUB_SAD_SEARCH, HME_LEVEL0_MULTIPLIER, HME_MAX_JOBS,
-                  MAX_SAD_VALUE, ME_CU_RESULT_DTYPE, NUM_SQ_PU, FullpelDesc, MeCuResult, MeParams, MotionEstimation, PaPictureDesc, SbOrigin,
+                  INLOOP_BLOCKS_ALL, INLOOP_BLOCKS_SIDE_4, INLOOP_DESC_DTYPE, INLOOP_ME_PU_COUNT, InloopDesc, MAX_SAD_VALUE,
+                  ME_CU_RESULT_DTYPE, NUM_SQ_PU, FullpelDesc, MeCuResult, MeParams, MotionEstimation, PaPictureDesc, SbOrigin,
                   build_picture_pool, default_me_params, make_fullpel_desc, sb_origins, shard_sb_rows)
 from ._tq import (COEFF_RATE_DESC_DTYPE, COEFF_RATE_TABLES_DTYPE, ITXFM_DESC_DTYPE, LV_MAP_COEFF_COST_DTYPE, QUANT_DESC_DTYPE,
                   TU_DESC_DTYPE, TU_RECON_SCRATCH, TX_SIZES_WH, TXFM_DESC_DTYPE, TransformQuant, TuBatcher, TuResult, TxSearchResult,

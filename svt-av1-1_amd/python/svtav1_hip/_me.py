@@ -24,6 +24,12 @@ MeCuResult = _abi.structure("svthip_me_cu_result")
 ME_CU_RESULT_DTYPE = _abi.dtype("svthip_me_cu_result")
 assert ME_CU_RESULT_DTYPE.itemsize == C.sizeof(MeCuResult) == 24
 SbOrigin = _abi.structure("svthip_sb_origin")
+# in-loop motion estimation: 849 blocks per 64x64 superblock
+INLOOP_ME_PU_COUNT = _abi.define("SVTHIP_INLOOP_ME_PU_COUNT")
+INLOOP_BLOCKS_ALL = _abi.define("SVTHIP_INLOOP_BLOCKS_ALL")
+INLOOP_BLOCKS_SIDE_4 = _abi.define("SVTHIP_INLOOP_BLOCKS_SIDE_4")
+InloopDesc = _abi.structure("svthip_inloop_desc")
+INLOOP_DESC_DTYPE = _abi.dtype("svthip_inloop_desc")
 
 # HME_LEVEL_0_SEARCH_AREA_MULTIPLIER_X / _Y [hierarchical_levels][temporal_layer_index]
 # (Codec/EbDefinitions.h:2980-2996); X and Y tables are identical in the reference.
@@ -235,3 +241,30 @@ class MotionEstimation:
         """SadLoopKernel over n_blocks (src_offset, ref_offset) uint32 pairs; d_best_sad uint32 [n], d_best_xy int16 [n][2] = (x, y) index."""
         _check(lib().svthip_sad_loop_batch_dev(self._h, d_src, src_stride, d_ref, ref_stride, ref_stride_raw, d_desc, n_blocks, width, height, sw, sh,
                                                d_best_sad, d_best_xy, stream))
+
+    # -- in-loop motion estimation (849 blocks per 64x64 superblock, one list per call) ---------------
+    def inloop_centers_dev(self, d_me, me_pu_stride, list_index, n_sb, d_center, stream=None):
+        """d_me: [n_sb][me_pu_stride] ME_CU_RESULT_DTYPE rows -> d_center int16 [n_sb][2], the 64x64 block's vector of the list >> 2."""
+        _check(lib().svthip_me_inloop_centers_dev(self._h, d_me, me_pu_stride, list_index, n_sb, d_center, stream))
+
+    def inloop_area_dev(self, d_center, d_sb, n_sb, pic_width, pic_height, src_geom, ref_geom, area_w, area_h, d_desc, stream=None):
+        """src_geom / ref_geom: (stride, origin_x, origin_y) of the planes -> d_desc [n_sb] INLOOP_DESC_DTYPE."""
+        _check(lib().svthip_me_inloop_area_dev(self._h, d_center, d_sb, n_sb, pic_width, pic_height, *src_geom, *ref_geom, area_w, area_h, d_desc, stream))
+
+    def inloop_fullpel_search_dev(self, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, block_set, d_sad, d_mv, stream=None):
+        """d_sad / d_mv: [n_sb][849] uint32 in the reference's buffer order; INLOOP_BLOCKS_SIDE_4 leaves the other 209 slots untouched."""
+        _check(lib().svthip_me_inloop_fullpel_search_dev(self._h, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, int(block_set), d_sad, d_mv, stream))
+
+    def inloop_subpel_search_dev(self, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, block_set, d_sad, d_mv, stream=None):
+        """Half-pel and quarter-pel refinement of the full-pel results, in place; same arguments as inloop_fullpel_search_dev."""
+        _check(lib().svthip_me_inloop_subpel_search_dev(self._h, d_src, src_stride, d_ref, ref_stride, d_desc, n_sb, int(block_set), d_sad, d_mv, stream))
+
+    def inloop_pack_dev(self, d_mv, n_sb, d_inloop_mv, stream=None):
+        """d_mv [n_sb][849] uint32 -> d_inloop_mv int16 [n_sb][849][2], x then y, in the candidate order of inloop_me_mv."""
+        _check(lib().svthip_me_inloop_pack_dev(self._h, d_mv, n_sb, d_inloop_mv, stream))
+
+    def inloop_search_dev(self, d_src, src_geom, d_ref, ref_geom, pic_width, pic_height, d_center, d_sb, n_sb, area_w, area_h, d_sad, d_mv,
+                          d_inloop_mv, use_subpel=False, block_set=0, stream=None):
+        """Areas, full-pel search, sub-pel refinement if asked for, and reorder of one list in one call; src_geom / ref_geom: (stride, origin_x, origin_y)."""
+        _check(lib().svthip_me_inloop_search_dev(self._h, d_src, *src_geom, d_ref, *ref_geom, pic_width, pic_height, d_center, d_sb, n_sb, area_w, area_h,
+                                                 int(use_subpel), int(block_set), d_sad, d_mv, d_inloop_mv, stream))
