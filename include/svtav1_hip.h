@@ -1984,7 +1984,8 @@ uint16_t svthip_tx_search_type_mask(uint32_t tx_size, int32_t is_inter, int32_t 
  * Mode decision's full loop: AV1PerformFullLoop (Codec/EbProductCodingLoop.c:2004-2307) on the candidates svthip_md_fast_pick_batch_dev
  * left in device memory, and product_full_mode_decision's loop (Codec/EbModeDecision.c:1989-2012) behind it.  8-bit planes, 4:2:0, the 19
  * block sizes with both sides <= 64 (txb_count == 1: one luma TU of av1_get_tx_size(bsize, 0) = bwidth x bheight and one TU per chroma
- * plane of txsize_uv = max(4, bwidth / 2) x max(4, bheight / 2), Codec/EbUtility.c:781-817).  Pure integer arithmetic, bit-identical.
+ * plane of txsize_uv = max(4, bwidth / 2) x max(4, bheight / 2), Codec/EbUtility.c:781-817); 128x128, 128x64 and 64x128 (txb_count 4, 2,
+ * 2) go to svthip_md_full_loop128_batch_dev below.  Pure integer arithmetic, bit-identical.
  *
  * svthip_md_full_loop_batch_dev: the blocks (groups) of ONE luma size.  Per group and slot i < max_full the candidate is row
  * group.first + pick.buffer_cand[pick.best[i]] of d_fast / d_full; slot i is ACTIVE when i < MIN(pick.full_count, MIN(group.count,
@@ -2120,6 +2121,55 @@ int32_t svthip_md_full_loop_batch_dev(svthip_ctx *ctx, const svthip_inter_planes
                                       const svthip_inter_planes *slot_recon, uint32_t tiles_per_row, const svthip_inter_planes *recon,
                                       void *d_work, uint32_t stages, svthip_md_full_result *d_result, svthip_md_full_decision *d_decision,
                                       void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mode decision's full loop for the three 128-wide block sizes, 128x128, 128x64 and 64x128: what every superblock of the reference's
+ * shipped configuration starts mode decision with (DISABLE_128X128_SB 0, Codec/EbDefinitions.h:58, Codec/EbEncHandle.c:2027-2031).
+ * These blocks have txb_count = 4, 2 and 2 luma TUs of TX_64X64 at (0,0), (64,0), (0,64), (64,64) / (0,0), (64,0) / (0,0), (0,64), and per
+ * txb_itr one Cb and one Cr TU of txsize_uv = TX_32X32 (Codec/EbUtility.c:781-817) at ((tx_org >> 3) << 3) / 2
+ * (Codec/EbFullLoop.c:1809-1810).  svthip_md_full_loop128_batch_dev is svthip_md_full_loop_batch_dev above for them: the same
+ * argument meanings, descriptors, `stages` split (LUMA, then CHROMA | DECIDE equals one call; the state is in d_work and the slot
+ * tiles), slot-tile pool rule with a tile pitch of bwidth x bheight, refusals and on-device refusal counting, with these differences:
+ *   no type masks      AV1PerformFullLoop skips ProductFullLoopTxSearch when sq_size >= 128 (Codec/EbProductCodingLoop.c:2133):
+ *                      tx_type_y and tx_type_uv are used as given.  A slot whose type has no network for 64x64 (Y) or 32x32 (Cb, Cr) runs
+ *                      as DCT_DCT, cannot win and is counted.
+ *   LUMA               ProductFullLoop's loop over txb_itr (Codec/EbFullLoop.c:968-1091): per TU the chain, distortion = (sum + that
+ *                      TU's three_quad_energy) >> (MAX_TX_SCALE - av1_get_tx_scale(TX_64X64)) * 2 (Av1EstimateTransform assigns the
+ *                      energy per TU, it is not accumulated), the coefficient bits with the block's luma_txb_skip_context and
+ *                      luma_dc_sign_context for every TU (Codec/EbRateDistortionCost.c:1377-1382), Av1TuCalcCostLuma with tu_index =
+ *                      txb_itr (:2223).  All TUs of all slots are ONE launch of the chain and one of the rate.
+ *   CHROMA             FullLoop_R and CuFullDistortionFastTuMode_R (Codec/EbFullLoop.c:1763-2083): the same loop for Cb and Cr, the
+ *                      shift of TX_32X32, no energy, Av1TuCalcCost(COMPONENT_CHROMA, tu_index).
+ *   d_result           svthip_md_full_result with the meanings above, except: y_, u_, v_has_coeff are the reference's bit masks (bit t
+ *                      = TU t), block_has_coeff is whether any mask is non-zero, quantized_dc[p] is the LAST TU's first level (every TU
+ *                      overwrites it), eob[p] is TU 0's (eob[p][0]), distortions and bits are the sums over the TUs.  Av1FullCost,
+ *                      Av1MergeSkipFullCost and product_full_mode_decision's loop see only the sums.
+ *   d_tu               svthip_md_full128_tu (32 bytes, [n_groups * max_full], 16-byte aligned), written by DECIDE: eob[plane][tu], what
+ *                      the host reads back per TU besides the masks (Codec/EbModeDecision.c:2157-2184); unused TUs are 0, and so is the
+ *                      record of a slot whose full_cost is ~0.
+ *   winner copy        the winner's whole slot tile (Y bwidth x bheight, Cb and Cr at half) goes to `recon`: reconstruction is per TU
+ *                      (AV1PerformInverseTransformRecon, Codec/EbProductCodingLoop.c:912-1036), which is the chain's clip(pred +
+ *                      inverse) per TU.
+ * d_work: svthip_md_full128_workspace_bytes(n_groups, max_full, bwidth, bheight) bytes, 16-byte aligned.
+ * Refused with SVTHIP_ERR_BAD_PARAMETER before any launch: a size other than 128x128, 128x64 and 64x128 (the 19 sizes of the entry above
+ * included); everything else as above.
+ * Not here: 16-bit planes; predicting the blocks (the prediction entries take all 22 sizes); the fill of cu_ptr / txb_ptr, which is
+ * host work on d_result and d_tu; CDEF and in-loop motion estimation for 128x128 superblocks, which stay as documented. */
+typedef struct svthip_md_full128_tu {
+    uint16_t eob[3][4]; /* [plane][txb_itr] */
+    uint8_t reserved[8];
+} svthip_md_full128_tu;
+
+size_t svthip_md_full128_workspace_bytes(uint32_t n_groups, uint32_t max_full, uint32_t bwidth, uint32_t bheight); /* 0 for refused arguments */
+int32_t svthip_md_full_loop128_batch_dev(svthip_ctx *ctx, const svthip_inter_planes *src, const svthip_inter_planes *pred,
+                                         const svthip_md_fast_desc *d_fast, const svthip_md_full_desc *d_full, uint32_t n_cand,
+                                         const svthip_md_fast_group *d_group, const svthip_md_fast_pick *d_pick, uint32_t n_groups,
+                                         uint32_t bwidth, uint32_t bheight, const int16_t *d_qparams, const int16_t *d_iscan,
+                                         const uint32_t iscan_offsets[19 * 16], const svthip_coeff_rate_tables *d_tables,
+                                         int32_t reduced_tx_set, uint32_t max_full, const svthip_inter_planes *slot_recon,
+                                         uint32_t tiles_per_row, const svthip_inter_planes *recon, void *d_work, uint32_t stages,
+                                         svthip_md_full_result *d_result, svthip_md_full128_tu *d_tu, svthip_md_full_decision *d_decision,
+                                         void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Reference-layout results and host-pointer forms (what a C host that owns host memory binds).

@@ -18,6 +18,59 @@ int32_t check_md_ifs_quantizer(int32_t quantizer)   // the reference's int16_t, 
     return SVTHIP_OK;
 }
 
+// the two full-loop entries: `wide` takes 128x128, 128x64 and 64x128 and has d_tu, the other takes the 19 sizes with both sides <= 64
+int32_t md_full_loop(bool wide, svthip_ctx* ctx, const svthip_inter_planes* src, const svthip_inter_planes* pred, const svthip_md_fast_desc* d_fast,
+                     const svthip_md_full_desc* d_full, uint32_t n_cand, const svthip_md_fast_group* d_group, const svthip_md_fast_pick* d_pick,
+                     uint32_t n_groups, uint32_t bwidth, uint32_t bheight, const int16_t* d_qparams, const int16_t* d_iscan, const uint32_t* iscan_offsets,
+                     const svthip_coeff_rate_tables* d_tables, int32_t reduced_tx_set, uint32_t type_mask_inter, uint32_t type_mask_intra, uint32_t max_full,
+                     const svthip_inter_planes* slot_recon, uint32_t tiles_per_row, const svthip_inter_planes* recon, void* d_work, uint32_t stages,
+                     svthip_md_full_result* d_result, svthip_md_full128_tu* d_tu, svthip_md_full_decision* d_decision, void* stream)
+{
+    TRY(enter(ctx));
+    if (!svthip::md_full_size_ok(bwidth, bheight, wide))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, wide ? "not one of the block sizes 128x128, 128x64 and 64x128 (%d x %d)"
+                                                   : "not one of the 19 AV1 block sizes with both sides up to 64 (%d x %d)", (int)bwidth, (int)bheight);
+    const uint32_t all_stages = SVTHIP_MD_FULL_LUMA | SVTHIP_MD_FULL_CHROMA | SVTHIP_MD_FULL_DECIDE;
+    if (!stages || (stages & ~all_stages)) return fail(SVTHIP_ERR_BAD_PARAMETER, "stages must be a mask of SVTHIP_MD_FULL_LUMA, _CHROMA, _DECIDE (got %d)", (int)stages);
+    if (max_full < 1 || max_full > SVTHIP_MD_FULL_MAX_SLOTS) return fail(SVTHIP_ERR_BAD_PARAMETER, "max_full must be 1..12 (got %d)", (int)max_full);
+    if (!tiles_per_row) return fail(SVTHIP_ERR_BAD_PARAMETER, "tiles_per_row must not be 0");
+    svthip::MdFullLayout L;
+    if (!type_mask_inter || !type_mask_intra || ((type_mask_inter | type_mask_intra) >> 16) ||
+        !svthip::md_full_layout(0, max_full, bwidth, bheight, wide, type_mask_inter, type_mask_intra, &L))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "a type mask is 0, has bits above 15 or names a TxType %d x %d has no network for (0x%x, 0x%x)", (int)bwidth,
+                    (int)bheight, (unsigned)type_mask_inter, (unsigned)type_mask_intra);
+    if (n_groups == 0) return SVTHIP_OK;
+    TRY(pred_check_args({src, pred, slot_recon, recon}, d_fast));
+    TRY(check_non_null({d_full, d_group, d_pick, d_qparams, d_iscan, iscan_offsets, d_tables, d_work, d_result, d_decision}));
+    if (wide) {
+        TRY(check_non_null({d_tu}));
+    }
+    if (n_cand == 0) return fail(SVTHIP_ERR_BAD_PARAMETER, "n_cand must not be 0: an inactive slot repeats row 0");
+    if (!aligned({d_full, d_pick, d_work, d_result, d_decision, d_tu}, 16))
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor, pick, workspace, result and decision arrays must be 16-byte aligned");
+    if (!aligned(d_group, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "group array must be 8-byte aligned");
+    if (!aligned(d_qparams, 2) || !aligned(d_tables, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "qparams must be 2-byte, tables 4-byte aligned");
+    TRY(check_tq_pools(nullptr, nullptr, nullptr, d_iscan));
+    for (const svthip_inter_planes* p : {src, pred, slot_recon, recon})
+        if (p->y_stride > 65535u || p->c_stride > 65535u)
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "plane strides must be at most 65535: a TU descriptor holds 16-bit strides (got %u)",
+                        (unsigned)(p->y_stride > p->c_stride ? p->y_stride : p->c_stride));
+    const uint64_t n_slots = (uint64_t)n_groups * max_full;
+    const uint64_t tile_w = bwidth < 8 ? 8 : bwidth, tile_h = bheight < 8 ? 8 : bheight, tile_rows = (n_slots + tiles_per_row - 1) / tiles_per_row;
+    if (!svthip::md_full_layout(n_groups, max_full, bwidth, bheight, wide, type_mask_inter, type_mask_intra, &L) || tiles_per_row * tile_w > 65535u ||
+        tile_rows * tile_h * slot_recon->y_stride > 0xffffffffull)
+        return fail(SVTHIP_ERR_BAD_PARAMETER, "too many slots in one call (%d groups of %d): their tiles or coefficients pass 32-bit offsets", (int)n_groups,
+                    (int)max_full);
+    hipStream_t s;
+    uint32_t* d_refused;
+    TRY(refused_counter(ctx, stream, &s, &d_refused));
+    svthip::MdFullCall call = {*src, *pred, *slot_recon, *recon, d_fast, d_full, d_group, d_pick, n_cand, n_groups, bwidth, bheight, max_full, tiles_per_row,
+                               type_mask_inter, type_mask_intra, stages, reduced_tx_set, d_qparams, d_iscan, iscan_offsets, d_tables, d_work, d_result,
+                               d_decision, d_refused, (uint32_t)ctx->opt[SVTHIP_OPT_TQ_MAX_WORKGROUPS], d_tu};
+    HIP_TRY(svthip::launch_md_full_loop(call, L, s));
+    return SVTHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -104,7 +157,7 @@ size_t svthip_md_full_workspace_bytes(uint32_t n_groups, uint32_t max_full, uint
                                       uint32_t type_mask_intra)
 {
     svthip::MdFullLayout L;
-    return svthip::md_full_layout(n_groups, max_full, bwidth, bheight, type_mask_inter, type_mask_intra, &L) ? L.total : 0;
+    return svthip::md_full_layout(n_groups, max_full, bwidth, bheight, false, type_mask_inter, type_mask_intra, &L) ? L.total : 0;
 }
 
 int32_t svthip_md_full_loop_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* src, const svthip_inter_planes* pred, const svthip_md_fast_desc* d_fast,
@@ -115,45 +168,27 @@ int32_t svthip_md_full_loop_batch_dev(svthip_ctx* ctx, const svthip_inter_planes
                                       const svthip_inter_planes* slot_recon, uint32_t tiles_per_row, const svthip_inter_planes* recon, void* d_work,
                                       uint32_t stages, svthip_md_full_result* d_result, svthip_md_full_decision* d_decision, void* stream)
 {
-    TRY(enter(ctx));
-    if (!svthip::md_full_size_ok(bwidth, bheight))
-        return fail(SVTHIP_ERR_BAD_PARAMETER, "not one of the 19 AV1 block sizes with both sides up to 64 (%d x %d)", (int)bwidth, (int)bheight);
-    const uint32_t all_stages = SVTHIP_MD_FULL_LUMA | SVTHIP_MD_FULL_CHROMA | SVTHIP_MD_FULL_DECIDE;
-    if (!stages || (stages & ~all_stages)) return fail(SVTHIP_ERR_BAD_PARAMETER, "stages must be a mask of SVTHIP_MD_FULL_LUMA, _CHROMA, _DECIDE (got %d)", (int)stages);
-    if (max_full < 1 || max_full > SVTHIP_MD_FULL_MAX_SLOTS) return fail(SVTHIP_ERR_BAD_PARAMETER, "max_full must be 1..12 (got %d)", (int)max_full);
-    if (!tiles_per_row) return fail(SVTHIP_ERR_BAD_PARAMETER, "tiles_per_row must not be 0");
+    return md_full_loop(false, ctx, src, pred, d_fast, d_full, n_cand, d_group, d_pick, n_groups, bwidth, bheight, d_qparams, d_iscan, iscan_offsets, d_tables,
+                        reduced_tx_set, type_mask_inter, type_mask_intra, max_full, slot_recon, tiles_per_row, recon, d_work, stages, d_result, nullptr,
+                        d_decision, stream);
+}
+
+size_t svthip_md_full128_workspace_bytes(uint32_t n_groups, uint32_t max_full, uint32_t bwidth, uint32_t bheight)
+{
     svthip::MdFullLayout L;
-    if (!type_mask_inter || !type_mask_intra || ((type_mask_inter | type_mask_intra) >> 16) ||
-        !svthip::md_full_layout(0, max_full, bwidth, bheight, type_mask_inter, type_mask_intra, &L))
-        return fail(SVTHIP_ERR_BAD_PARAMETER, "a type mask is 0, has bits above 15 or names a TxType %d x %d has no network for (0x%x, 0x%x)", (int)bwidth,
-                    (int)bheight, (unsigned)type_mask_inter, (unsigned)type_mask_intra);
-    if (n_groups == 0) return SVTHIP_OK;
-    TRY(pred_check_args({src, pred, slot_recon, recon}, d_fast));
-    TRY(check_non_null({d_full, d_group, d_pick, d_qparams, d_iscan, iscan_offsets, d_tables, d_work, d_result, d_decision}));
-    if (n_cand == 0) return fail(SVTHIP_ERR_BAD_PARAMETER, "n_cand must not be 0: an inactive slot repeats row 0");
-    if (!aligned({d_full, d_pick, d_work, d_result, d_decision}, 16))
-        return fail(SVTHIP_ERR_BAD_PARAMETER, "descriptor, pick, workspace, result and decision arrays must be 16-byte aligned");
-    if (!aligned(d_group, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "group array must be 8-byte aligned");
-    if (!aligned(d_qparams, 2) || !aligned(d_tables, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "qparams must be 2-byte, tables 4-byte aligned");
-    TRY(check_tq_pools(nullptr, nullptr, nullptr, d_iscan));
-    for (const svthip_inter_planes* p : {src, pred, slot_recon, recon})
-        if (p->y_stride > 65535u || p->c_stride > 65535u)
-            return fail(SVTHIP_ERR_BAD_PARAMETER, "plane strides must be at most 65535: a TU descriptor holds 16-bit strides (got %u)",
-                        (unsigned)(p->y_stride > p->c_stride ? p->y_stride : p->c_stride));
-    const uint64_t n_slots = (uint64_t)n_groups * max_full;
-    const uint64_t tile_w = bwidth < 8 ? 8 : bwidth, tile_h = bheight < 8 ? 8 : bheight, tile_rows = (n_slots + tiles_per_row - 1) / tiles_per_row;
-    if (!svthip::md_full_layout(n_groups, max_full, bwidth, bheight, type_mask_inter, type_mask_intra, &L) || tiles_per_row * tile_w > 65535u ||
-        tile_rows * tile_h * slot_recon->y_stride > 0xffffffffull)
-        return fail(SVTHIP_ERR_BAD_PARAMETER, "too many slots in one call (%d groups of %d): their tiles or coefficients pass 32-bit offsets", (int)n_groups,
-                    (int)max_full);
-    hipStream_t s;
-    uint32_t* d_refused;
-    TRY(refused_counter(ctx, stream, &s, &d_refused));
-    svthip::MdFullCall call = {*src, *pred, *slot_recon, *recon, d_fast, d_full, d_group, d_pick, n_cand, n_groups, bwidth, bheight, max_full, tiles_per_row,
-                               type_mask_inter, type_mask_intra, stages, reduced_tx_set, d_qparams, d_iscan, iscan_offsets, d_tables, d_work, d_result,
-                               d_decision, d_refused, (uint32_t)ctx->opt[SVTHIP_OPT_TQ_MAX_WORKGROUPS]};
-    HIP_TRY(svthip::launch_md_full_loop(call, L, s));
-    return SVTHIP_OK;
+    return svthip::md_full_layout(n_groups, max_full, bwidth, bheight, true, 1, 1, &L) ? L.total : 0;
+}
+
+int32_t svthip_md_full_loop128_batch_dev(svthip_ctx* ctx, const svthip_inter_planes* src, const svthip_inter_planes* pred, const svthip_md_fast_desc* d_fast,
+                                         const svthip_md_full_desc* d_full, uint32_t n_cand, const svthip_md_fast_group* d_group,
+                                         const svthip_md_fast_pick* d_pick, uint32_t n_groups, uint32_t bwidth, uint32_t bheight, const int16_t* d_qparams,
+                                         const int16_t* d_iscan, const uint32_t iscan_offsets[19 * 16], const svthip_coeff_rate_tables* d_tables,
+                                         int32_t reduced_tx_set, uint32_t max_full, const svthip_inter_planes* slot_recon, uint32_t tiles_per_row,
+                                         const svthip_inter_planes* recon, void* d_work, uint32_t stages, svthip_md_full_result* d_result,
+                                         svthip_md_full128_tu* d_tu, svthip_md_full_decision* d_decision, void* stream)
+{
+    return md_full_loop(true, ctx, src, pred, d_fast, d_full, n_cand, d_group, d_pick, n_groups, bwidth, bheight, d_qparams, d_iscan, iscan_offsets, d_tables,
+                        reduced_tx_set, 1, 1, max_full, slot_recon, tiles_per_row, recon, d_work, stages, d_result, d_tu, d_decision, stream);
 }
 
 }  // extern "C"

@@ -17,10 +17,15 @@
 //             shape the call's arguments give.
 //   winner    md_full_luma_winner_kernel (search only): a thread per slot takes the decision's winner: its sums and bits become the
 //             slot's, its TxType goes into the slot's TU descriptor for the launch that leaves levels and reconstruction.
-//   cost      md_full_cost_kernel: a thread per slot, 64-bit integer arithmetic on a dozen loaded values.
+//   cost      md_full_cost_kernel: a thread per slot, 64-bit integer arithmetic on a dozen loaded values per TU.
 //   decide    md_full_decide_kernel: a thread per group over at most 12 result rows.
 //   copy      md_full_copy_kernel: a thread per quad (four samples of a row) of the winner's Y, Cb and Cr blocks; a quad is one dword
 //             load / store when its address is a multiple of 4, four byte accesses otherwise; no byte outside the block.
+//
+// A slot has 1 << (tu_log2_cols + tu_log2_rows) luma TUs of bw x bh side by side and as many TUs of cw x ch in Cb and in Cr: one for the 19
+// block sizes with both sides <= 64, 2 or 4 TUs of 64x64 (chroma 32x32) for 128x64, 64x128 and 128x128 (txb_count of EbUtility.c:781-817;
+// the loops over txb_itr of ProductFullLoop, FullLoop_R and CuFullDistortionFastTuMode_R, EbFullLoop.c:968-1091, :1801-1918, :1965-2082).
+// Everything a launch of the chain or the rate reads or writes per TU is indexed by slot * TUs + TU, so all TUs of a plane are one launch.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -34,7 +39,7 @@
 namespace svthip {
 
 static_assert(sizeof(svthip_md_full_desc) == 48 && sizeof(svthip_md_full_result) == 144 && sizeof(svthip_md_full_decision) == 16 &&
-                  sizeof(svthip_tu_desc) == 32 && sizeof(svthip_coeff_rate_desc) == 16 && sizeof(tx_search_tu_dev) == 80,
+                  sizeof(svthip_md_full128_tu) == 32 && sizeof(svthip_tu_desc) == 32 && sizeof(svthip_coeff_rate_desc) == 16 && sizeof(tx_search_tu_dev) == 80,
               "the layouts of include/svtav1_hip.h");
 
 constexpr uint32_t MD_FULL_NONE = 0xffffffffu;   // no candidate row
@@ -104,6 +109,7 @@ struct MdFullArgs {
     const uint8_t* slot_plane[3];
     uint8_t* recon_plane[3];
     uint32_t bw, bh, cw, ch;             // the luma TU and the TU of Cb / Cr
+    uint32_t tu_log2_cols, tu_log2_rows; // the TUs of a slot side by side: 0, 0 for one TU (the block is the TU), 1 for two of 64 in that direction
     uint32_t tile_w, tile_h, tiles_per_row;
     uint32_t ncoef[2];                   // packed coefficients of a luma / chroma TU
     int tx_size_y, shift_y, shift_uv;
@@ -112,7 +118,7 @@ struct MdFullArgs {
     uint8_t types[16];                   // ascending
     uint32_t iscan_y[16], iscan_uv[16];  // iscan_offsets of the two TxSizes
     uint8_t reduced_tx_set;
-    // per slot, in the workspace
+    // per slot (slots) and per (slot, TU) at slot * TUs + TU, in the workspace
     MdFullSlot* slots;
     svthip_tu_desc* tu[3];
     svthip_coeff_rate_desc* rate[3];
@@ -131,9 +137,15 @@ struct MdFullArgs {
     const uint32_t* s_bits;
     const svthip_tx_search_result* s_out;   // [n_slots]
     svthip_md_full_result* result;       // [n_slots]
+    svthip_md_full128_tu* tu_out;        // [n_slots], null where the entry has none
     svthip_md_full_decision* decision;   // [n_groups]
     uint32_t* refused;
 };
+
+// TUs of a slot, and the luma offset of TU t inside the block (tx_org_x / tx_org_y of EbUtility.c:781-817)
+__host__ __device__ __forceinline__ uint32_t md_full_tus(const MdFullArgs& A) { return 1u << (A.tu_log2_cols + A.tu_log2_rows); }
+__host__ __device__ __forceinline__ uint32_t md_full_tu_x(const MdFullArgs& A, uint32_t t) { return (t & ((1u << A.tu_log2_cols) - 1u)) * A.bw; }
+__host__ __device__ __forceinline__ uint32_t md_full_tu_y(const MdFullArgs& A, uint32_t t) { return (t >> A.tu_log2_cols) * A.bh; }
 
 // ------------------------------------------------------------------------------------------------ expand
 
@@ -168,32 +180,34 @@ __device__ __forceinline__ uint32_t md_full_offset(uint32_t x, uint32_t y, uint3
     return plane ? ((y >> 3) << 2) * stride + ((x >> 3) << 2) : y * stride + x;
 }
 
-// the TU and rate descriptors of plane `plane` of slot k with TxType tx_type, reconstructing into its slot tile
-__device__ __forceinline__ void md_full_emit_tu(const MdFullArgs& A, uint32_t k, uint32_t use_row, int plane, uint32_t tx_type)
+// the TU and rate descriptors of TU tu of plane `plane` of slot k with TxType tx_type, reconstructing into its slot tile; every TU of a
+// block has the block's contexts (EbRateDistortionCost.c:1377-1382)
+__device__ __forceinline__ void md_full_emit_tu(const MdFullArgs& A, uint32_t k, uint32_t tu, uint32_t use_row, int plane, uint32_t tx_type)
 {
     const svthip_md_fast_desc* f = A.fast + use_row;
     const svthip_md_full_desc* d = A.full + use_row;
     const int c = plane ? 1 : 0;
+    const uint32_t j = k * md_full_tus(A) + tu, ox = md_full_tu_x(A, tu), oy = md_full_tu_y(A, tu);
     uint32_t tx, ty;
     md_full_tile(A, k, &tx, &ty);
     svthip_tu_desc t;
-    t.src_offset = md_full_offset(f->src_x, f->src_y, A.src_stride[c], plane);
-    t.pred_offset = md_full_offset(f->pred_x, f->pred_y, A.pred_stride[c], plane);
-    t.recon_offset = md_full_offset(tx, ty, A.slot_stride[c], plane);
-    t.coeff_offset = k * A.ncoef[c];
+    t.src_offset = md_full_offset(f->src_x + ox, f->src_y + oy, A.src_stride[c], plane);
+    t.pred_offset = md_full_offset(f->pred_x + ox, f->pred_y + oy, A.pred_stride[c], plane);
+    t.recon_offset = md_full_offset(tx + ox, ty + oy, A.slot_stride[c], plane);
+    t.coeff_offset = j * A.ncoef[c];
     t.iscan_offset = plane ? A.iscan_uv[tx_type] : A.iscan_y[tx_type];
     t.src_stride = (uint16_t)A.src_stride[c], t.pred_stride = (uint16_t)A.pred_stride[c], t.recon_stride = (uint16_t)A.slot_stride[c];
     t.qparam_index = d->qparam_index[plane];
     t.tx_type = (uint8_t)tx_type;
     t.reserved[0] = t.reserved[1] = t.reserved[2] = 0;
-    A.tu[plane][k] = t;
+    A.tu[plane][j] = t;
     svthip_coeff_rate_desc r;
     r.coeff_offset = t.coeff_offset, r.iscan_offset = t.iscan_offset;
     r.tx_type = (uint8_t)tx_type, r.plane_type = (uint8_t)c;
     r.txb_skip_ctx = d->txb_skip_ctx[plane], r.dc_sign_ctx = d->dc_sign_ctx[plane];
     r.is_inter = (f->flags & SVTHIP_MD_FAST_TYPE_INTER) ? 1 : 0;
     r.intra_mode = d->intra_mode, r.reduced_tx_set = A.reduced_tx_set, r.reserved = 0;
-    A.rate[plane][k] = r;
+    A.rate[plane][j] = r;
 }
 
 // Stage LUMA, slot k: its state and its luma descriptors.  Returns what the context counts: 1 for slot 0 of a group the pick refused,
@@ -219,10 +233,11 @@ __device__ __forceinline__ uint32_t md_full_expand_luma(const MdFullArgs& A, uin
     if (s.bad_type) s.tx_type_y = s.tx_type_uv = 0, counted += row != MD_FULL_NONE;
     s.reserved[0] = s.reserved[1] = s.reserved[2] = s.reserved[3] = s.reserved[4] = 0;
     A.slots[k] = s;
-    md_full_emit_tu(A, k, use_row, 0, s.tx_type_y);
+    for (uint32_t t = 0; t < md_full_tus(A); t++) md_full_emit_tu(A, k, t, use_row, 0, s.tx_type_y);
 
     if (A.n_types) {
-        // the search: one candidate per TxType of the union, each with its own tile of bw x bh and its own levels
+        // the search (one TU a slot: the reference runs none from 128 on, EbProductCodingLoop.c:2133): one candidate per TxType of the
+        // union, each with its own tile of bw x bh and its own levels
         const svthip_tu_desc base = A.tu[0][k];
         const svthip_coeff_rate_desc rbase = A.rate[0][k];
         const uint32_t mask = rbase.is_inter ? A.mask_inter : A.mask_intra;
@@ -247,7 +262,7 @@ __device__ __forceinline__ uint32_t md_full_expand_luma(const MdFullArgs& A, uin
     return counted;
 }
 
-// Stage LUMA behind the decision of a search, slot k: the winner's sums and bits become the slot's, its TxType the slot's
+// Stage LUMA behind the decision of a search (one TU a slot), slot k: the winner's sums and bits become the slot's, its TxType the slot's
 __device__ __forceinline__ void md_full_luma_winner(const MdFullArgs& A, uint32_t k)
 {
     const uint32_t pos = A.s_out[k].candidate, t = A.s_out[k].tx_type;
@@ -263,18 +278,60 @@ __device__ __forceinline__ void md_full_luma_winner(const MdFullArgs& A, uint32_
 __device__ __forceinline__ void md_full_expand_chroma(const MdFullArgs& A, uint32_t k)
 {
     const MdFullSlot s = A.slots[k];
-    md_full_emit_tu(A, k, s.use_row, 1, s.tx_type_uv);
-    md_full_emit_tu(A, k, s.use_row, 2, s.tx_type_uv);
+    for (uint32_t t = 0; t < md_full_tus(A); t++) {
+        md_full_emit_tu(A, k, t, s.use_row, 1, s.tx_type_uv);
+        md_full_emit_tu(A, k, t, s.use_row, 2, s.tx_type_uv);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ cost
 
-// Stage DECIDE, slot k: its result row
-__device__ __forceinline__ svthip_md_full_result md_full_cost(const MdFullArgs& A, uint32_t k)
+// what the walk over a slot's TUs of one plane, in the order of txb_itr, leaves: bits and distortions summed, bit t of the has_coeff mask
+// TU t's, the last TU's first level (every TU overwrites quantized_dc), TU 0's eob
+struct MdFullPlaneSums {
+    uint64_t dist0, dist1, bits;   // DIST_CALC_RESIDUAL, DIST_CALC_PREDICTION
+    int32_t quantized_dc;
+    uint16_t eob;
+    uint8_t has_coeff;
+};
+
+// Plane `plane` of slot k.  Luma: ProductFullLoop (EbFullLoop.c:968-1091) with Av1TuCalcCostLuma per TU, three_quad_energy the TU's own;
+// chroma: CuFullDistortionFastTuMode_R (:1965-2082), no energy.  eob_out: the plane's row of the per-TU record.  The loop is unrolled to
+// MAX_TU, the most TUs a slot of the call can have (1 or 4), and nothing is stored inside it, so that the loads of all TUs and planes of a
+// slot are in flight together; with MAX_TU == 1 the walk is the straight line it was before there were slots of several TUs.
+template <uint32_t MAX_TU>
+__device__ __forceinline__ MdFullPlaneSums md_full_plane_sums(const MdFullArgs& A, uint32_t k, int plane, uint64_t lambda, uint16_t eob_out[4])
+{
+    MdFullPlaneSums o = {0, 0, 0, 0, 0, 0};
+    const uint32_t n_tu = MAX_TU == 1u ? 1u : md_full_tus(A);
+    const int shift = plane ? A.shift_uv : A.shift_y;
+#pragma unroll
+    for (uint32_t t = 0; t < MAX_TU; t++) {
+        if (t >= n_tu) break;
+        const uint32_t j = k * n_tu + t;
+        const uint64_t energy = plane ? 0 : A.energy_y[j];
+        uint64_t t0 = md_full_shift(A.dist[plane][2u * j] + energy, shift);
+        const uint64_t t1 = md_full_shift(A.dist[plane][2u * j + 1u] + energy, shift);
+        uint64_t t_bits = A.bits[plane][j];
+        if (plane == 0 && !(md_full_rdcost(lambda, t_bits, t0) < MD_FULL_MAX_COST)) t_bits = 0, t0 = t1;   // against yZeroCbfCost = ~0
+        o.dist0 += t0, o.dist1 += t1, o.bits += t_bits;
+        const uint16_t eob = A.eob[plane][j];
+        if (t == 0u) o.eob = eob;
+        eob_out[t] = eob;
+        o.has_coeff |= (uint8_t)((eob != 0) << t);
+        o.quantized_dc = A.qcoeff[plane][(size_t)j * A.ncoef[plane ? 1 : 0]];
+    }
+    return o;
+}
+
+// Stage DECIDE, slot k: its result row and its per-TU record (all 0 for a slot without a cost; stored only where the entry has one)
+template <uint32_t MAX_TU>
+__device__ __forceinline__ svthip_md_full_result md_full_cost(const MdFullArgs& A, uint32_t k, svthip_md_full128_tu* tu_out)
 {
     const MdFullSlot s = A.slots[k];
     svthip_md_full_result r;
     memset(&r, 0, sizeof(r));
+    memset(tu_out, 0, sizeof(*tu_out));
     r.row = s.row, r.tx_type_y = s.tx_type_y, r.tx_type_uv = s.tx_type_uv;
     r.full_cost = MD_FULL_MAX_COST;
     if (s.row == MD_FULL_NONE) return r;
@@ -283,49 +340,42 @@ __device__ __forceinline__ svthip_md_full_result md_full_cost(const MdFullArgs& 
     if ((f->flags & SVTHIP_MD_FAST_INVALID) || s.bad_type) return r;
     const uint64_t lambda = d->lambda;
 
-    // ProductFullLoop (EbFullLoop.c:1039-1080) and Av1TuCalcCostLuma
-    const uint64_t energy = A.energy_y[k];
-    uint64_t y0 = md_full_shift(A.dist[0][2u * k] + energy, A.shift_y);
-    const uint64_t y1 = md_full_shift(A.dist[0][2u * k + 1u] + energy, A.shift_y);
-    uint64_t y_bits = A.bits[0][k];
-    const bool nz = md_full_rdcost(lambda, y_bits, y0) < MD_FULL_MAX_COST;   // against yZeroCbfCost = ~0
-    if (!nz) y_bits = 0, y0 = y1;
+    const MdFullPlaneSums y = md_full_plane_sums<MAX_TU>(A, k, 0, lambda, tu_out->eob[0]);
+    const uint64_t y0 = y.dist0, y1 = y.dist1, y_bits = y.bits;
+    uint64_t uv0 = 0, uv1 = 0;   // Cb + Cr
     r.y_distortion[0] = y0, r.y_distortion[1] = y1;
-    r.coeff_bits[0] = y_bits;
-    r.eob[0] = A.eob[0][k];
-    r.quantized_dc[0] = A.qcoeff[0][(size_t)k * A.ncoef[0]];
-    r.y_has_coeff = r.eob[0] != 0;
-
-    // CuFullDistortionFastTuMode_R (:1992-2070): no three_quad_energy
+    r.coeff_bits[0] = y_bits, r.eob[0] = y.eob, r.quantized_dc[0] = y.quantized_dc, r.y_has_coeff = y.has_coeff;
     if (f->has_uv) {
-#pragma unroll
-        for (int p = 1; p < 3; p++) {
-            uint64_t* dist = p == 1 ? r.cb_distortion : r.cr_distortion;
-            dist[0] = md_full_shift(A.dist[p][2u * k], A.shift_uv), dist[1] = md_full_shift(A.dist[p][2u * k + 1u], A.shift_uv);
-            r.coeff_bits[p] = A.bits[p][k];
-            r.eob[p] = A.eob[p][k];
-            r.quantized_dc[p] = A.qcoeff[p][(size_t)k * A.ncoef[1]];
-        }
-        r.u_has_coeff = r.eob[1] != 0, r.v_has_coeff = r.eob[2] != 0;
+        const MdFullPlaneSums cb = md_full_plane_sums<MAX_TU>(A, k, 1, lambda, tu_out->eob[1]);
+        const MdFullPlaneSums cr = md_full_plane_sums<MAX_TU>(A, k, 2, lambda, tu_out->eob[2]);
+        r.cb_distortion[0] = cb.dist0, r.cb_distortion[1] = cb.dist1, r.cr_distortion[0] = cr.dist0, r.cr_distortion[1] = cr.dist1;
+        r.coeff_bits[1] = cb.bits, r.coeff_bits[2] = cr.bits, r.eob[1] = cb.eob, r.eob[2] = cr.eob;
+        uv0 = cb.dist0 + cr.dist0, uv1 = cb.dist1 + cr.dist1;
+        r.quantized_dc[1] = cb.quantized_dc, r.quantized_dc[2] = cr.quantized_dc, r.u_has_coeff = cb.has_coeff, r.v_has_coeff = cr.has_coeff;
     }
-    r.block_has_coeff = r.y_has_coeff | r.u_has_coeff | r.v_has_coeff;
+    r.block_has_coeff = (r.y_has_coeff | r.u_has_coeff | r.v_has_coeff) != 0;
 
     const uint64_t coeff_rate = r.coeff_bits[0] + r.coeff_bits[1] + r.coeff_bits[2];
     const uint64_t rate = (uint64_t)d->luma_rate + d->chroma_rate + coeff_rate;
-    const uint64_t distortion = y0 + r.cb_distortion[0] + r.cr_distortion[0];
-    if (d->skip_mode_rate == 0xffffffffu) {   // Av1FullCost
-        r.full_cost = md_full_rdcost(lambda, rate, distortion);
-        r.full_lambda_rate = r.full_cost - distortion;
-        r.full_cost_luma = md_full_rdcost(lambda, (uint64_t)d->luma_rate + y_bits, y0);
-    } else {                                  // Av1MergeSkipFullCost
-        const uint64_t skip_distortion = y1 + r.cb_distortion[1] + r.cr_distortion[1];
-        r.merge_cost = md_full_rdcost(lambda, rate, distortion);
-        r.skip_cost = md_full_rdcost(lambda, d->skip_mode_rate, skip_distortion);
-        r.skip_flag = r.skip_cost <= r.merge_cost;
-        r.full_cost = r.skip_flag ? r.skip_cost : r.merge_cost;
-        r.full_lambda_rate = r.full_cost - (r.skip_flag ? skip_distortion : distortion);
-    }
+    const uint64_t distortion = y0 + uv0;
+    // the numbers of the two arms as scalars, stored once: stores into r from inside the arms keep part of r in scratch
+    const bool merge = d->skip_mode_rate != 0xffffffffu;
+    const uint64_t skip_distortion = y1 + uv1;
+    const uint64_t full = md_full_rdcost(lambda, rate, distortion);                                   // Av1FullCost, and the merge arm's merge cost
+    const uint64_t skip = md_full_rdcost(lambda, merge ? d->skip_mode_rate : 0u, skip_distortion);   // Av1MergeSkipFullCost
+    const bool skip_flag = merge && skip <= full;
+    r.merge_cost = merge ? full : 0, r.skip_cost = merge ? skip : 0, r.skip_flag = skip_flag;
+    r.full_cost = skip_flag ? skip : full;
+    r.full_lambda_rate = skip_flag ? skip - skip_distortion : full - distortion;
+    r.full_cost_luma = merge ? 0 : md_full_rdcost(lambda, (uint64_t)d->luma_rate + y_bits, y0);
     return r;
+}
+
+// the row alone, for any TU count
+__device__ __forceinline__ svthip_md_full_result md_full_cost(const MdFullArgs& A, uint32_t k)
+{
+    svthip_md_full128_tu unused;
+    return md_full_cost<4>(A, k, &unused);
 }
 
 // ------------------------------------------------------------------------------------------------ decision
@@ -355,7 +405,7 @@ __device__ __forceinline__ svthip_md_full_decision md_full_decide(const MdFullAr
 
 // ------------------------------------------------------------------------------------------------ copy
 
-// quads of a group's blocks: Y, then Cb, then Cr
+// quads of a group's blocks of bw x bh (Cb, Cr: cw x ch): Y, then Cb, then Cr
 __host__ __device__ __forceinline__ uint32_t md_full_copy_quads(uint32_t bw, uint32_t bh, uint32_t cw, uint32_t ch) { return bw / 4u * bh + 2u * (cw / 4u * ch); }
 
 __device__ __forceinline__ void md_full_store_quad(uint8_t* p, uint32_t v)
@@ -376,12 +426,13 @@ __device__ __forceinline__ void md_full_copy_quad(const MdFullArgs& A, uint32_t 
 {
     const svthip_md_full_decision dec = A.decision[g];
     if (dec.winner_row == MD_FULL_NONE) return;
-    const uint32_t luma_quads = A.bw / 4u * A.bh, chroma_quads = A.cw / 4u * A.ch;
+    const uint32_t yw = A.bw << A.tu_log2_cols, yh = A.bh << A.tu_log2_rows, uvw = A.cw << A.tu_log2_cols, uvh = A.ch << A.tu_log2_rows;   // the block
+    const uint32_t luma_quads = yw / 4u * yh, chroma_quads = uvw / 4u * uvh;
     int plane = 0;
-    uint32_t qw = A.bw / 4u;
+    uint32_t qw = yw / 4u;
     if (q >= luma_quads) {
         if (!A.fast[dec.winner_row].has_uv) return;
-        q -= luma_quads, plane = 1, qw = A.cw / 4u;
+        q -= luma_quads, plane = 1, qw = uvw / 4u;
         if (q >= chroma_quads) q -= chroma_quads, plane = 2;
     }
     const int c = plane ? 1 : 0;
@@ -418,6 +469,7 @@ __global__ void __launch_bounds__(MD_FULL_THREADS) md_full_expand_chroma_kernel(
     if (k < A.n_slots) md_full_expand_chroma(A, k);
 }
 
+template <uint32_t MAX_TU>
 __global__ void __launch_bounds__(MD_FULL_THREADS) md_full_cost_kernel(MdFullArgs A)
 {
     const uint32_t k = blockIdx.x * MD_FULL_THREADS + threadIdx.x;
@@ -426,10 +478,18 @@ __global__ void __launch_bounds__(MD_FULL_THREADS) md_full_cost_kernel(MdFullArg
         uint4 q[9];
         svthip_md_full_result r;
     } o;
-    o.r = md_full_cost(A, k);
+    union {
+        uint4 q[2];
+        svthip_md_full128_tu t;
+    } u;
+    o.r = md_full_cost<MAX_TU>(A, k, &u.t);
     uint4* dst = reinterpret_cast<uint4*>(A.result + k);
 #pragma unroll
     for (int w = 0; w < 9; w++) dst[w] = o.q[w];
+    if (A.tu_out) {
+        uint4* tdst = reinterpret_cast<uint4*>(A.tu_out + k);
+        tdst[0] = u.q[0], tdst[1] = u.q[1];
+    }
 }
 
 __global__ void __launch_bounds__(MD_FULL_THREADS) md_full_decide_kernel(MdFullArgs A)
@@ -446,7 +506,7 @@ __global__ void __launch_bounds__(MD_FULL_THREADS) md_full_decide_kernel(MdFullA
 
 __global__ void __launch_bounds__(256) md_full_copy_kernel(MdFullArgs A)
 {
-    const uint32_t per_group = md_full_copy_quads(A.bw, A.bh, A.cw, A.ch);
+    const uint32_t per_group = md_full_copy_quads(A.bw << A.tu_log2_cols, A.bh << A.tu_log2_rows, A.cw << A.tu_log2_cols, A.ch << A.tu_log2_rows);
     const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (t >= (uint64_t)A.n_groups * per_group) return;
     md_full_copy_quad(A, (uint32_t)(t / per_group), (uint32_t)(t % per_group));

@@ -25,14 +25,16 @@ hipError_t launch_md_ifs_search(const svthip_inter_planes& ref0, const svthip_in
                                 int32_t search_mode, int32_t enable_dual_filter, int16_t quantizer, int32_t write_back, svthip_md_ifs_result* result,
                                 bool use_mfma, void* scratch, const MdIfsLayout& L, void* jobs_scratch, uint32_t* refused, hipStream_t s);
 // md_full.hip: mode decision's full loop -- per slot the fused chain and the rate on Y, Cb and Cr with the tx-type search, the full cost,
-// the decision per block, the winner's reconstruction (kernels: md_full_kernels.h)
-struct MdFullLayout {   // byte offsets into the caller's workspace, its size, and the TxTypes a search runs
+// the decision per block, the winner's reconstruction (kernels: md_full_kernels.h).  One core serves two entries: the 19 block sizes with
+// both sides <= 64 (one luma TU a slot) and, `wide`, 128x128, 128x64 and 64x128 (4, 2 and 2 luma TUs of 64x64 a slot, no tx-type search)
+struct MdFullLayout {   // byte offsets into the caller's workspace, its size, the TUs of a slot and the TxTypes a search runs
     size_t slots, tu[3], rate[3], eob[3], dist[3], bits[3], qcoeff[3], energy_y;
     size_t s_tu, s_rate, s_eob, s_energy, s_dist, s_bits, s_qcoeff, s_recon, s_tus, s_bases, s_out, total;
     uint32_t n_slots, n_types;   // n_types 0: no search
     uint8_t types[16];
+    uint32_t tu_w, tu_h, tu_log2_cols, tu_log2_rows;   // the luma TU; 1 << log2 TUs side by side in each direction
 };
-struct MdFullCall {   // the arguments of svthip_md_full_loop_batch_dev
+struct MdFullCall {   // the arguments of svthip_md_full_loop_batch_dev and svthip_md_full_loop128_batch_dev
     svthip_inter_planes src, pred, slot_recon, recon;
     const svthip_md_fast_desc* fast;
     const svthip_md_full_desc* full;
@@ -48,9 +50,10 @@ struct MdFullCall {   // the arguments of svthip_md_full_loop_batch_dev
     svthip_md_full_decision* decision;
     uint32_t* refused;
     uint32_t max_workgroups;         // SVTHIP_OPT_TQ_MAX_WORKGROUPS
+    svthip_md_full128_tu* tu_out;    // null for the entry without one
 };
-bool md_full_size_ok(uint32_t bwidth, uint32_t bheight);
-bool md_full_layout(uint32_t n_groups, uint32_t max_full, uint32_t bw, uint32_t bh, uint32_t mask_inter, uint32_t mask_intra, MdFullLayout* L);
+bool md_full_size_ok(uint32_t bwidth, uint32_t bheight, bool wide);
+bool md_full_layout(uint32_t n_groups, uint32_t max_full, uint32_t bw, uint32_t bh, bool wide, uint32_t mask_inter, uint32_t mask_intra, MdFullLayout* L);
 hipError_t launch_md_full_loop(const MdFullCall& C, const MdFullLayout& L, hipStream_t s);
 
 }  // namespace svthip

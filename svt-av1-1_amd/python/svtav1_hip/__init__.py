@@ -35,7 +35,7 @@ from ._md import (MD_FAST_CHROMA_QUARTER, MD_FAST_INVALID, MD_FAST_LUMA_GIVEN, M
                   md_fast_group_dtype, md_fast_pick_dtype, md_fast_result_dtype, md_ifs_desc_dtype, md_ifs_result_dtype, md_model_rd_desc_dtype,
                   md_model_rd_result_dtype)
 from ._md import (MD_FULL_CHROMA, MD_FULL_DECIDE, MD_FULL_LUMA, MD_FULL_MAX_SLOTS, MD_FULL_NONE, ModeDecisionFull, md_full_decision_dtype,
-                  md_full_desc_dtype, md_full_result_dtype, md_full_workspace_bytes)
+                  md_full_desc_dtype, md_full_result_dtype, md_full_workspace_bytes, md_full128_tu_dtype, md_full128_workspace_bytes)
 from ._host import ME_CU_RESULT_REF_DTYPE, HostForms, HostPicture
 
 

@@ -1,11 +1,11 @@
 """Mode decision's fast loop (svthip_md_fast_cost_batch_dev, svthip_md_fast_pick_batch_dev), its interpolation-filter search
-(svthip_md_model_rd_batch_dev, svthip_md_interp_filter_search_batch_dev) and its full loop (svthip_md_full_loop_batch_dev): pointer
-marshalling only.
+(svthip_md_model_rd_batch_dev, svthip_md_interp_filter_search_batch_dev) and its full loop (svthip_md_full_loop_batch_dev, and svthip_md_full_loop128_batch_dev
+for 128x128, 128x64 and 64x128): pointer marshalling only.
 
 The four structs cross Python as numpy arrays in device memory; md_fast_desc_dtype() / md_fast_result_dtype() / md_fast_group_dtype() /
 md_fast_pick_dtype() give their layouts (svthip_md_fast_desc, _result, _group, _pick of include/svtav1_hip.h); md_model_rd_desc_dtype() /
 md_model_rd_result_dtype() / md_ifs_desc_dtype() / md_ifs_result_dtype() those of the search (svthip_md_model_rd_desc, _result,
-svthip_md_ifs_desc, _result); md_full_desc_dtype() / md_full_result_dtype() / md_full_decision_dtype() those of the full loop."""
+svthip_md_ifs_desc, _result); md_full_desc_dtype() / md_full_result_dtype() / md_full_decision_dtype() / md_full128_tu_dtype() those of the full loop."""
 from __future__ import annotations
 
 import numpy as np
@@ -119,8 +119,18 @@ def md_full_workspace_bytes(n_groups, max_full, bwidth, bheight, type_mask_inter
     return int(lib().svthip_md_full_workspace_bytes(n_groups, max_full, bwidth, bheight, type_mask_inter, type_mask_intra))
 
 
+def md_full128_tu_dtype() -> np.dtype:
+    """svthip_md_full128_tu, 32 bytes: eob[plane][tu] of a slot of md_full_loop128_batch_dev"""
+    return _abi.dtype("svthip_md_full128_tu")
+
+
+def md_full128_workspace_bytes(n_groups, max_full, bwidth, bheight) -> int:
+    """bytes of d_work for a call of md_full_loop128_batch_dev; 0 for arguments the entry refuses"""
+    return int(lib().svthip_md_full128_workspace_bytes(n_groups, max_full, bwidth, bheight))
+
+
 class ModeDecisionFull:
-    """the full-loop entry as a Context method; planes are InterPlanes of 8-bit planes, the arrays device pointers"""
+    """the full-loop entries as Context methods; planes are InterPlanes of 8-bit planes, the arrays device pointers"""
 
     def md_full_loop_batch_dev(self, src, pred, d_fast, d_full, n_cand, d_group, d_pick, n_groups, bwidth, bheight, d_qparams, d_iscan, iscan_offsets,
                                d_tables, reduced_tx_set, type_mask_inter, type_mask_intra, max_full, slot_recon, tiles_per_row, recon, d_work, stages,
@@ -134,3 +144,15 @@ class ModeDecisionFull:
                                                    bheight, d_qparams, d_iscan, None if offsets is None else offsets.ctypes.data, d_tables, reduced_tx_set,
                                                    type_mask_inter, type_mask_intra, max_full, _planes_arg(slot_recon), tiles_per_row, _planes_arg(recon),
                                                    d_work, stages, d_result, d_decision, stream))
+
+    def md_full_loop128_batch_dev(self, src, pred, d_fast, d_full, n_cand, d_group, d_pick, n_groups, bwidth, bheight, d_qparams, d_iscan, iscan_offsets,
+                                  d_tables, reduced_tx_set, max_full, slot_recon, tiles_per_row, recon, d_work, stages, d_result, d_tu, d_decision,
+                                  stream=None):
+        """md_full_loop_batch_dev for n_groups blocks of 128x128, 128x64 or 64x128 (2 or 4 luma TUs of 64x64 a block, no tx-type search):
+        d_work md_full128_workspace_bytes(..) bytes, d_tu n_groups * max_full rows of md_full128_tu_dtype(); in d_result the has_coeff fields
+        are bit masks over the TUs, quantized_dc the last TU's, eob TU 0's"""
+        offsets = None if iscan_offsets is None else np.ascontiguousarray(np.asarray(iscan_offsets, np.uint32).reshape(19 * 16))
+        _check(lib().svthip_md_full_loop128_batch_dev(self._h, _planes_arg(src), _planes_arg(pred), d_fast, d_full, n_cand, d_group, d_pick, n_groups,
+                                                      bwidth, bheight, d_qparams, d_iscan, None if offsets is None else offsets.ctypes.data, d_tables,
+                                                      reduced_tx_set, max_full, _planes_arg(slot_recon), tiles_per_row, _planes_arg(recon), d_work, stages,
+                                                      d_result, d_tu, d_decision, stream))

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Times mode decision's full loop for one 1920 x 1080 picture at three luma sizes, 8x8, 32x32 and 64x64, each with has_uv, four candidates
 a block and all four picked (max_full 4): svthip_md_full_loop_batch_dev, the whole call with every stage, once without a tx-type search
-(both masks 1) and once with the ENC_M1 masks.  Next to it in the same run:
+(both masks 1) and once with the ENC_M1 masks; and at 128x128 (svthip_md_full_loop128_batch_dev: four luma TUs of 64x64 and four chroma TUs
+of 32x32 a plane and slot, no search), whose 120 blocks of the 1920 x 1024 area hold the same 1 920 luma and 3 840 chroma TUs as the 480
+blocks of the 64x64 row, so that the 64x64 row is its yardstick.  Next to it in the same run:
   * the launches the call is built around, alone, on the same TUs through the public entries -- svthip_encode_tu_batch_dev and
     svthip_coeff_rate_batch_dev on Y (every TxType of the search, then the winner's shape once more), Cb and Cr (as DCT_DCT) -- so that the difference
     is what the new kernels (expand, winner, cost, decide, copy) and the tx-type decision add;
   * the download, to pageable host memory, of the picks and of the per-slot eobs, distortion sums, energies and bits: what a host-side
     full loop on the same leaves costs before it adds up its first cost.
 
-    python tools/md_full_probe.py [--iters N] [--out FILE]      device times (needs a GPU)
+    python tools/md_full_probe.py [--iters N] [--out FILE] [--sizes 8,32,64,128] [--tag TEXT]      device times (needs a GPU)
     python tools/md_full_probe.py --resources FILE              registers, LDS and scratch of the kernels from the compiler's remarks
 
 The prediction pool holds candidate c of the block at (x, y) at (x, c * 1080 + y): four pictures stacked; the slot pool has the same
@@ -31,7 +33,8 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.pat
 import svtav1_hip  # noqa: E402
 
 W, H, SLOTS = 1920, 1080, 4
-SIZES = (8, 32, 64)
+SIZES = (8, 32, 64, 128)
+TU_MAX = 64   # a 128-wide block has TUs of 64x64 (chroma 32x32)
 
 
 def build(size, search, rng, fu, mu):
@@ -49,7 +52,8 @@ def build(size, search, rng, fu, mu):
                               for c in range(SLOTS)]) for p in s.src]
     fast, full = np.zeros((n_groups, SLOTS), fu.FAST_DTYPE), np.zeros((n_groups, SLOTS), fu.FULL_DTYPE)
     bx, by = (a.reshape(-1) for a in np.meshgrid(np.arange(nx) * size, np.arange(ny) * size))
-    types_y, types_uv = svtav1_hip.valid_tx_types(size, size), svtav1_hip.valid_tx_types(size // 2, size // 2)
+    tu = min(size, TU_MAX)
+    types_y, types_uv = svtav1_hip.valid_tx_types(tu, tu), svtav1_hip.valid_tx_types(tu // 2, tu // 2)
     for c in range(SLOTS):
         fast["src_x"][:, c], fast["src_y"][:, c], fast["pred_x"][:, c], fast["pred_y"][:, c] = bx, by, bx, by + c * H
         fast["flags"][:, c] = mu.TYPE_INTER if c & 1 else 0
@@ -88,7 +92,7 @@ def sample_of(s, some, fu):
     return t, rows
 
 
-def device_times(lines, iters):
+def device_times(lines, iters, sizes=SIZES, tag=None):
     import torch
 
     import md_fast_util as mu
@@ -104,20 +108,29 @@ def device_times(lines, iters):
     as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
     d_qp, d_iscan, d_tables = as_dev(sh["qparams"]), as_dev(sh["tabs"].iscan_pool), as_dev(sh["tables"])
     tiles_per_row = {size: W // size for size in SIZES}
+    wide = None
+    if 128 in sizes:
+        import md_full128_util as wide
 
     def report(name, us, size, search, n_groups, kind="device events", **more):
         row = {"entry": name, "kind": kind, "width": W, "height": H, "block": f"{size}x{size}", "search": search, "groups": n_groups, "slots": n_groups * SLOTS,
                "us": round(us, 1), **more}
+        if tag:
+            row["tag"] = tag
         lines.append(row)
         print(json.dumps(row), flush=True)
 
-    for size in SIZES:
+    for size in sizes:
         for search in ("none", "m1"):
+            if size > TU_MAX and search != "none":
+                continue   # no search from 128 on
             rng = np.random.default_rng(size)
-            s = build(size, search, rng, fu, mu)
+            s = build(size, "none" if size > TU_MAX else search, rng, fu, mu)
             if search == "m1" and (s.mask_inter | s.mask_intra) == 1:
                 continue   # 64x64 has DCT_DCT alone: the same call
             n, cw = s.n_slots, size // 2
+            tu_w, tu_cw, per_side = min(size, TU_MAX), min(size, TU_MAX) // 2, size // min(size, TU_MAX)
+            n_tu = per_side * per_side                 # TUs a slot and plane
             d = {k: [torch.from_numpy(p).to("cuda:0") for p in planes] for k, planes in (("src", s.src), ("pool", s.pool))}
             d["slot"] = [torch.zeros((H * SLOTS // (2 if p else 1), W // (2 if p else 1)), dtype=torch.uint8, device="cuda:0") for p in range(3)]
             d["recon"] = [torch.zeros_like(t) for t in d["src"]]
@@ -128,12 +141,22 @@ def device_times(lines, iters):
                 a.y_stride, a.c_stride = W, W // 2
                 planes[k] = a
             d_fast, d_full, d_group, d_pick = as_dev(s.fast), as_dev(s.full), as_dev(s.groups), as_dev(s.picks)
-            work = svtav1_hip.md_full_workspace_bytes(s.n_groups, SLOTS, size, size, s.mask_inter, s.mask_intra)
+            is_wide = size > TU_MAX
+            work = svtav1_hip.md_full128_workspace_bytes(s.n_groups, SLOTS, size, size) if is_wide else \
+                svtav1_hip.md_full_workspace_bytes(s.n_groups, SLOTS, size, size, s.mask_inter, s.mask_intra)
             d_work = torch.zeros(work, dtype=torch.uint8, device="cuda:0")
             d_result = torch.zeros(n * 144, dtype=torch.uint8, device="cuda:0")
             d_decision = torch.zeros(s.n_groups * 16, dtype=torch.uint8, device="cuda:0")
 
+            d_tu_out = torch.zeros(n * 32, dtype=torch.uint8, device="cuda:0")
+
             def call(stages=fu.LUMA | fu.CHROMA | fu.DECIDE):
+                if is_wide:
+                    ctx.md_full_loop128_batch_dev(planes["src"], planes["pool"], d_fast.data_ptr(), d_full.data_ptr(), s.n_cand, d_group.data_ptr(),
+                                                  d_pick.data_ptr(), s.n_groups, size, size, d_qp.data_ptr(), d_iscan.data_ptr(), sh["iscan_offsets"],
+                                                  d_tables.data_ptr(), 0, SLOTS, planes["slot"], tiles_per_row[size], planes["recon"], d_work.data_ptr(), stages,
+                                                  d_result.data_ptr(), d_tu_out.data_ptr(), d_decision.data_ptr(), stream=stream)
+                    return
                 ctx.md_full_loop_batch_dev(planes["src"], planes["pool"], d_fast.data_ptr(), d_full.data_ptr(), s.n_cand, d_group.data_ptr(), d_pick.data_ptr(),
                                            s.n_groups, size, size, d_qp.data_ptr(), d_iscan.data_ptr(), sh["iscan_offsets"], d_tables.data_ptr(), 0, s.mask_inter,
                                            s.mask_intra, SLOTS, planes["slot"], tiles_per_row[size], planes["recon"], d_work.data_ptr(), stages,
@@ -146,7 +169,13 @@ def device_times(lines, iters):
             got_r, got_d = d_result.cpu().numpy().view(fu.RESULT_DTYPE), d_decision.cpu().numpy().view(fu.DECISION_DTYPE)
             some = np.arange(0, s.n_groups, max(1, s.n_groups // 24))
             sub, rows = sample_of(s, some, fu)
-            st = fu.full_loop(Oracle(), sub)
+            if is_wide:
+                sub.origins = wide.tu_origins(size, size)
+                sub.slot_shape = [(-(-len(rows) // wide.SLOT_TILES_PER_ROW) * size // (2 if p else 1), wide.SLOT_TILES_PER_ROW * size // (2 if p else 1)) for p in range(3)]
+                st = wide.full_loop(Oracle(), sub)
+                assert np.array_equal(d_tu_out.cpu().numpy().view(wide.TU_DTYPE).reshape(-1, SLOTS)[some].reshape(-1), st["tu"]), "the timed per-TU records differ"
+            else:
+                st = fu.full_loop(Oracle(), sub)
             want_r = st["result"].copy()
             want_r["row"] = rows[want_r["row"]]
             assert np.array_equal(got_r.reshape(-1, SLOTS)[some].reshape(-1), want_r), "the timed result rows differ"
@@ -160,22 +189,24 @@ def device_times(lines, iters):
             assert ctx.inter_pred_refused() == 0
 
             # the launches alone, through the public entries, on the same TUs
-            ts_y, ts_uv = fu.tx_size_of(size, size), fu.tx_size_of(cw, cw)
+            ts_y, ts_uv = fu.tx_size_of(tu_w, tu_w), fu.tx_size_of(tu_cw, tu_cw)
             both = s.mask_inter | s.mask_intra
             types = [t for t in range(16) if both >> t & 1] if both != 1 else []
             k = np.arange(n)
             tile_x, tile_y = (k % tiles_per_row[size]) * size, (k // tiles_per_row[size]) * size
             launches = []
 
-            def add_launch(plane, w_, n_tu, tx, recon_plane, recon_off, recon_stride, want_dist, ts):
+            def add_launch(plane, w_, n_tu, tx, recon_plane, recon_off, recon_stride, want_dist, ts, tu_x=0, tu_y=0):
+                """n_tu TUs of w_ x w_: slot by slot for a search's candidates (n_tu a multiple of the slots), TU by TU of a slot for a 128-wide
+                block (tu_x, tu_y: each TU's luma offset inside its block)"""
                 c = 1 if plane else 0
-                slot = np.tile(np.arange(n), n_tu // n)
+                slot = np.tile(np.arange(n), n_tu // n) if np.ndim(tu_x) == 0 else np.repeat(np.arange(n), n_tu // n)
                 f = s.fast[slot // SLOTS * SLOTS + s.picks["best"][slot // SLOTS, slot % SLOTS]]
                 r8 = (lambda v: v // 2) if plane else (lambda v: v)
                 tu = np.zeros(n_tu, svtav1_hip.TU_DESC_DTYPE)
                 stride = W // 2 if plane else W
-                tu["src_offset"] = r8(f["src_y"].astype(np.int64)) * stride + r8(f["src_x"].astype(np.int64))
-                tu["pred_offset"] = r8(f["pred_y"].astype(np.int64)) * stride + r8(f["pred_x"].astype(np.int64))
+                tu["src_offset"] = r8(f["src_y"].astype(np.int64) + tu_y) * stride + r8(f["src_x"].astype(np.int64) + tu_x)
+                tu["pred_offset"] = r8(f["pred_y"].astype(np.int64) + tu_y) * stride + r8(f["pred_x"].astype(np.int64) + tu_x)
                 tu["recon_offset"], tu["recon_stride"] = recon_off, recon_stride
                 ncoef = min(w_, 32) ** 2
                 tu["coeff_offset"], tu["iscan_offset"], tu["tx_type"] = np.arange(n_tu) * ncoef, sh["iscan_offsets"][ts][tx], tx
@@ -200,14 +231,21 @@ def device_times(lines, iters):
                 launches.append((go, keep))
 
             slot_off = [tile_y * W + tile_x, (tile_y // 2) * (W // 2) + tile_x // 2]
-            if types:
+            if is_wide:   # every TU of a plane in one launch, as the call has them
+                t = np.tile(np.arange(n_tu), n)
+                ox, oy = (t % per_side) * tu_w, (t // per_side) * tu_w
+                off = [(np.repeat(tile_y, n_tu) + oy) * W + np.repeat(tile_x, n_tu) + ox, ((np.repeat(tile_y, n_tu) + oy) // 2) * (W // 2) + (np.repeat(tile_x, n_tu) + ox) // 2]
+                add_launch(0, tu_w, n * n_tu, np.zeros(n * n_tu, np.int64), d["slot"][0], off[0], W, True, ts_y, ox, oy)
+                for p in (1, 2):
+                    add_launch(p, tu_cw, n * n_tu, np.zeros(n * n_tu, np.int64), d["slot"][p], off[1], W // 2, True, ts_uv, ox, oy)
+            elif types:
                 m = n * len(types)
                 scratch = torch.zeros(m * size * size, dtype=torch.uint8, device="cuda:0")
                 add_launch(0, size, m, np.repeat(types, n), scratch, np.arange(m) * size * size, size, True, ts_y)
                 add_launch(0, size, n, np.zeros(n, np.int64), d["slot"][0], slot_off[0], W, False, ts_y)
             else:
                 add_launch(0, size, n, s.full["tx_type_y"][k // SLOTS * SLOTS + s.picks["best"][k // SLOTS, k % SLOTS]], d["slot"][0], slot_off[0], W, True, ts_y)
-            for p in (1, 2):
+            for p in (1, 2) if not is_wide else ():
                 add_launch(p, cw, n, np.zeros(n, np.int64), d["slot"][p], slot_off[1], W // 2, True, ts_uv)
             t_leaves = timed(torch, lambda: [go() for go, _ in launches], iters, 4)
 
@@ -223,8 +261,8 @@ def device_times(lines, iters):
                 torch.cuda.synchronize()
                 ts.append(time.perf_counter() - t0)
             t_down = float(np.median(ts[3:])) * 1e6
-            tus = n * (len(types) + 1 if types else 1) + 2 * n
-            report("md_full_loop (LUMA | CHROMA | DECIDE)", t_call, size, search, s.n_groups, tx_types=len(types) or 1, transform_units=tus, workspace_bytes=work,
+            tus = n * n_tu * 3 if is_wide else n * (len(types) + 1 if types else 1) + 2 * n
+            report("md_full_loop128 (LUMA | CHROMA | DECIDE)" if is_wide else "md_full_loop (LUMA | CHROMA | DECIDE)", t_call, size, search, s.n_groups, tx_types=len(types) or 1, transform_units=tus, workspace_bytes=work,
                    call_over_leaves=round(t_call / t_leaves, 2), added_us=round(t_call - t_leaves, 1))
             for name, t in t_stage.items():
                 report(f"md_full_loop, stage {name} alone", t, size, search, s.n_groups)
@@ -258,11 +296,15 @@ def main():
     ap.add_argument("--iters", type=int, default=7)
     ap.add_argument("--out", default=None)
     ap.add_argument("--resources", default=None)
+    ap.add_argument("--sizes", default=",".join(str(v) for v in SIZES), help="luma sizes to time, of " + ", ".join(str(v) for v in SIZES))
+    ap.add_argument("--tag", default=None, help="a word kept in every row, e.g. which build was timed")
     a = ap.parse_args()
     if a.resources:
         return resources(a.resources)
     lines = []
-    device_times(lines, a.iters)
+    sizes = tuple(int(v) for v in a.sizes.split(","))
+    assert set(sizes) <= set(SIZES), sizes
+    device_times(lines, a.iters, sizes, a.tag)
     if a.out:
         with open(a.out, "a") as f:
             for row in lines:
