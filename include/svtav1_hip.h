@@ -1166,9 +1166,10 @@ int32_t svthip_av1_highbd_pick_filter_level_dev(svthip_ctx *ctx, const svthip_lf
 
 /* ---------------------------------------------------------------------------------------------
  * CDEF, the stage between deblocking and loop restoration (Codec/EbCdef.c, EbCdefProcess.c): the strength search over all filter
- * blocks, the strength pick and the frame filter.  CDEF_M = 1, fast = 0, 4:2:0, 64x64 superblocks, three planes, one tile, 8 and 10 bits.
+ * blocks, the strength pick and the frame filter.  CDEF_M = 1, fast = 0, 4:2:0, 64x64 superblocks (the entries named ..128 also take
+ * grids with 128X128, 128X64 and 64X128 blocks, below), three planes, one tile, 8 and 10 bits.
  * Every result is the reference's C form bit for bit, the double-precision luma distortion included.
- * NOT covered, and staying on the host or unsupported: 128x128 superblocks, the `fast` search, 12 bits, 4:2:2 / 4:4:0, more than one tile.
+ * NOT covered, and staying on the host or unsupported: the `fast` search, 12 bits, 4:2:2 / 4:4:0, more than one tile.
  *
  *   filter block (fb)      64x64 luma samples; nhfb = (width / 4 + 15) / 16, nvfb likewise, nfb = nhfb * nvfb, raster order.
  *   svthip_cdef_picture    device pointers to sample (0, 0) of the deblocked planes (read only), the source planes (search entries) and the
@@ -1193,9 +1194,31 @@ int32_t svthip_av1_highbd_pick_filter_level_dev(svthip_ctx *ctx, const svthip_lf
  * svthip_av1_[highbd_]cdef_search_dev   the two above on one stream with no host synchronisation; d_mse and d_fb_counted are workspace
  *     that keeps the tables.
  * svthip_av1_[highbd_]cdef_frame_dev   av1_cdef_frame[16bit] (EbCdef.c:470-808 and its twin) for planes [plane_start, plane_end), out of
- *     place from the deblocked planes into picture->out: an fb whose pair is (0, 0) for luma and chroma or whose list is empty, and every
- *     unlisted 8x8 block, is copied; every sample of the output planes is written.  Strengths, dampings and per-fb indices are read from
+ *     place from the deblocked planes into picture->out: an fb whose pair is (0, 0) for luma and chroma, whose list is empty or whose
+ *     index is -1 (:565-570; with 64x64 fbs such an fb lists nothing, the twin of a 128-wide fb left out may), and every unlisted 8x8
+ *     block, is copied; every sample of the output planes is written.  Strengths, dampings and per-fb indices are read from
  *     device memory.  The output planes are what svthip_lr_picture.cdef[] takes.
+ * The ..128 entries: pictures coded with 128-wide blocks (the reference's default superblock).  They take what their namesakes take plus
+ *     d_mi / mi_stride, the grid the deblocking entries read (height / 4 rows of mi_stride >= width / 4 cells): only sb_type of the first
+ *     cell of each fb, cell (16 fbr, 16 fbc), is read, with the reference's BlockSize values, values above 21 clamped; the skip flag still
+ *     comes from picture->d_skip (svthip_lf_mi.flags is another predicate).  With T that sb_type (EbCdefProcess.c:160-193, EbCdef.c:1471-1573):
+ *       - an fb is left out as a twin when (fbc & 1) and T is 128X128 or 128X64, or (fbr & 1) and T is 128X128 or 64X128: its own cell is
+ *         asked, not its neighbour's, also on grids whose blocks contradict each other;
+ *       - otherwise its extent is two fbs wide for 128X128 / 128X64 and two fbs high for 128X128 / 64X128, clipped by the picture only;
+ *       - it is left out as all-skipped by sb_all_skip of its first 64x64 whatever the extent;
+ *       - every 8x8 block of the extent that is not all skipped is listed and filtered as in the namesake; the distortions are summed over
+ *         the whole list and shifted once per plane, Cr added to Cb.
+ *     svthip_av1_[highbd_]cdef_search_mse128_dev   d_mse rows of every searched fb at its own raster index, rows of fbs left out 0;
+ *         d_fb_counted 1 for a searched fb, 0 otherwise, twins included.  d_workspace: svthip_cdef_search128_workspace_bytes(width, height)
+ *         bytes, 8-byte aligned: the unshifted sums per 64x64 quadrant and plane, [nfb][3][64] uint64, written by the search kernel with a
+ *         workgroup per quadrant and merged per fb by a second kernel (integer sums: no order, no atomics in global memory).
+ *     svthip_cdef_pick_strengths128_dev   the namesake's searches on the counted fbs; d_fb_strength is -1 everywhere first, then in
+ *         raster order each counted fb's index goes to its own entry and, by T, to the entries at +1 column, +1 row and both (128X128),
+ *         +1 column (128X64) or +1 row (64X128); later writes win; a copy past the last fb column or row is dropped.  sb_count counts the
+ *         searched fbs.  The result feeds svthip_av1_[highbd_]cdef_frame_dev unchanged: av1_cdef_frame walks 64x64 fbs.
+ *     svthip_av1_[highbd_]cdef_search128_dev   the two on one stream with no host synchronisation.
+ *     A grid with no block size of 128 gives byte for byte what the namesakes give.  Refused in addition to the namesakes' refusals: a
+ *     null d_mi, mi_stride < width / 4 (the pick: < 16 (nhfb - 1) + 1), a d_workspace that is null or not 8-byte aligned.
  * svthip_cdef_dist_8x8_batch_dev   dist_8x8_16bit_c (:1321-1347) on n pairs of contiguous 8x8 16-bit blocks with the search kernel's own
  *     device function: d_out[n] uint64.  It exists so that the one floating-point expression can be tested on its own.
  * Refused with svthip_last_error text and without a launch: a null pointer (frame entries: of the deblocked luma plane and of the
@@ -1235,6 +1258,21 @@ int32_t svthip_av1_cdef_search_dev(svthip_ctx *ctx, const svthip_cdef_picture *p
 int32_t svthip_av1_highbd_cdef_search_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint32_t bit_depth,
                                           uint64_t *d_mse, uint8_t *d_fb_counted, svthip_cdef_result *d_result, int8_t *d_fb_strength,
                                           void *stream);
+size_t svthip_cdef_search128_workspace_bytes(uint32_t width, uint32_t height); /* 0 for refused arguments */
+int32_t svthip_av1_cdef_search_mse128_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint64_t *d_mse,
+                                          uint8_t *d_fb_counted, const svthip_lf_mi *d_mi, uint32_t mi_stride, void *d_workspace, void *stream);
+int32_t svthip_av1_highbd_cdef_search_mse128_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint32_t bit_depth,
+                                                 uint64_t *d_mse, uint8_t *d_fb_counted, const svthip_lf_mi *d_mi, uint32_t mi_stride,
+                                                 void *d_workspace, void *stream);
+int32_t svthip_cdef_pick_strengths128_dev(svthip_ctx *ctx, const uint64_t *d_mse, const uint8_t *d_fb_counted, uint32_t nhfb, uint32_t nvfb,
+                                          uint32_t base_qindex, uint32_t bit_depth, svthip_cdef_result *d_result, int8_t *d_fb_strength,
+                                          const svthip_lf_mi *d_mi, uint32_t mi_stride, void *stream);
+int32_t svthip_av1_cdef_search128_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint64_t *d_mse,
+                                      uint8_t *d_fb_counted, svthip_cdef_result *d_result, int8_t *d_fb_strength, const svthip_lf_mi *d_mi,
+                                      uint32_t mi_stride, void *d_workspace, void *stream);
+int32_t svthip_av1_highbd_cdef_search128_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, uint32_t base_qindex, uint32_t bit_depth,
+                                             uint64_t *d_mse, uint8_t *d_fb_counted, svthip_cdef_result *d_result, int8_t *d_fb_strength,
+                                             const svthip_lf_mi *d_mi, uint32_t mi_stride, void *d_workspace, void *stream);
 int32_t svthip_av1_cdef_frame_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, const svthip_cdef_result *d_result,
                                   const int8_t *d_fb_strength, uint32_t plane_start, uint32_t plane_end, void *stream);
 int32_t svthip_av1_highbd_cdef_frame_dev(svthip_ctx *ctx, const svthip_cdef_picture *picture, const svthip_cdef_result *d_result,
@@ -2154,7 +2192,7 @@ int32_t svthip_md_full_loop_batch_dev(svthip_ctx *ctx, const svthip_inter_planes
  * Refused with SVTHIP_ERR_BAD_PARAMETER before any launch: a size other than 128x128, 128x64 and 64x128 (the 19 sizes of the entry above
  * included); everything else as above.
  * Not here: 16-bit planes; predicting the blocks (the prediction entries take all 22 sizes); the fill of cu_ptr / txb_ptr, which is
- * host work on d_result and d_tu; CDEF and in-loop motion estimation for 128x128 superblocks, which stay as documented. */
+ * host work on d_result and d_tu; in-loop motion estimation for 128x128 superblocks, which stays as documented. */
 typedef struct svthip_md_full128_tu {
     uint16_t eob[3][4]; /* [plane][txb_itr] */
     uint8_t reserved[8];

@@ -79,6 +79,49 @@ int32_t cdef_search_entry(svthip_ctx* ctx, const svthip_cdef_picture* pic, uint3
     return SVTHIP_OK;
 }
 
+// The entries for grids with 128-wide blocks: the namesakes' checks, then the grid (the pick reads the first cell of every fb, the search
+// knows the picture) and the workspace.
+int32_t check_cdef_grid(const svthip_lf_mi* d_mi, uint32_t mi_stride, uint32_t min_stride)
+{
+    TRY(check_non_null({d_mi}));
+    if (mi_stride < min_stride) return fail(SVTHIP_ERR_BAD_PARAMETER, "mi_stride %u is smaller than %u", (unsigned)mi_stride, (unsigned)min_stride);
+    return SVTHIP_OK;
+}
+
+int32_t check_cdef_workspace(const void* d_workspace)
+{
+    TRY(check_non_null({d_workspace}));
+    if (!aligned(d_workspace, 8)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_workspace must be 8-byte aligned");
+    return SVTHIP_OK;
+}
+
+int32_t cdef_search_mse128_entry(svthip_ctx* ctx, const svthip_cdef_picture* pic, uint32_t base_qindex, int bd, uint64_t* d_mse, uint8_t* d_fb_counted,
+                                 const svthip_lf_mi* d_mi, uint32_t mi_stride, void* d_workspace, void* stream)
+{
+    TRY(check_cdef_picture(pic, bd, true, 0, 3));
+    TRY(check_cdef_tables(d_mse, d_fb_counted, base_qindex));
+    TRY(check_cdef_grid(d_mi, mi_stride, pic->width / 4));
+    TRY(check_cdef_workspace(d_workspace));
+    HIP_TRY(svthip::launch_cdef_search_mse128(*pic, (int)base_qindex, bd, d_mi, mi_stride, static_cast<uint64_t*>(d_workspace), d_mse, d_fb_counted,
+                                              call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t cdef_search128_entry(svthip_ctx* ctx, const svthip_cdef_picture* pic, uint32_t base_qindex, int bd, uint64_t* d_mse, uint8_t* d_fb_counted,
+                             svthip_cdef_result* d_result, int8_t* d_fb_strength, const svthip_lf_mi* d_mi, uint32_t mi_stride, void* d_workspace,
+                             void* stream)
+{
+    TRY(check_cdef_picture(pic, bd, true, 0, 3));
+    const uint32_t nhfb = (pic->width / 4 + 15) / 16, nvfb = (pic->height / 4 + 15) / 16;
+    TRY(check_cdef_pick(d_mse, d_fb_counted, nhfb, nvfb, base_qindex, bd, d_result, d_fb_strength));
+    TRY(check_cdef_grid(d_mi, mi_stride, pic->width / 4));
+    TRY(check_cdef_workspace(d_workspace));
+    hipStream_t s = call_stream(ctx, stream);
+    HIP_TRY(svthip::launch_cdef_search_mse128(*pic, (int)base_qindex, bd, d_mi, mi_stride, static_cast<uint64_t*>(d_workspace), d_mse, d_fb_counted, s));
+    HIP_TRY(svthip::launch_cdef_pick128(d_mse, d_fb_counted, nhfb, nvfb, (int)base_qindex, bd, d_mi, mi_stride, d_result, d_fb_strength, s));
+    return SVTHIP_OK;
+}
+
 int32_t cdef_frame_entry(svthip_ctx* ctx, const svthip_cdef_picture* pic, const svthip_cdef_result* d_result, const int8_t* d_fb_strength,
                          uint32_t ps, uint32_t pe, int bd, void* stream)
 {
@@ -132,6 +175,57 @@ int32_t svthip_av1_highbd_cdef_search_dev(svthip_ctx* ctx, const svthip_cdef_pic
     TRY(enter(ctx));
     TRY(check_bit_depth_10(bit_depth));
     return cdef_search_entry(ctx, picture, base_qindex, 10, d_mse, d_fb_counted, d_result, d_fb_strength, stream);
+}
+
+size_t svthip_cdef_search128_workspace_bytes(uint32_t width, uint32_t height)
+{
+    if (check_filter_picture_size(width, height) != SVTHIP_OK) return 0;
+    return svthip::cdef_search128_workspace_bytes(width, height);
+}
+
+int32_t svthip_av1_cdef_search_mse128_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, uint32_t base_qindex, uint64_t* d_mse,
+                                          uint8_t* d_fb_counted, const svthip_lf_mi* d_mi, uint32_t mi_stride, void* d_workspace, void* stream)
+{
+    TRY(enter(ctx));
+    return cdef_search_mse128_entry(ctx, picture, base_qindex, 8, d_mse, d_fb_counted, d_mi, mi_stride, d_workspace, stream);
+}
+
+int32_t svthip_av1_highbd_cdef_search_mse128_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, uint32_t base_qindex, uint32_t bit_depth,
+                                                 uint64_t* d_mse, uint8_t* d_fb_counted, const svthip_lf_mi* d_mi, uint32_t mi_stride,
+                                                 void* d_workspace, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return cdef_search_mse128_entry(ctx, picture, base_qindex, 10, d_mse, d_fb_counted, d_mi, mi_stride, d_workspace, stream);
+}
+
+int32_t svthip_cdef_pick_strengths128_dev(svthip_ctx* ctx, const uint64_t* d_mse, const uint8_t* d_fb_counted, uint32_t nhfb, uint32_t nvfb,
+                                          uint32_t base_qindex, uint32_t bit_depth, svthip_cdef_result* d_result, int8_t* d_fb_strength,
+                                          const svthip_lf_mi* d_mi, uint32_t mi_stride, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_cdef_pick(d_mse, d_fb_counted, nhfb, nvfb, base_qindex, (int)bit_depth, d_result, d_fb_strength));
+    TRY(check_cdef_grid(d_mi, mi_stride, 16 * (nhfb - 1) + 1));   // the first cell of the last fb column
+    HIP_TRY(svthip::launch_cdef_pick128(d_mse, d_fb_counted, nhfb, nvfb, (int)base_qindex, (int)bit_depth, d_mi, mi_stride, d_result, d_fb_strength,
+                                        call_stream(ctx, stream)));
+    return SVTHIP_OK;
+}
+
+int32_t svthip_av1_cdef_search128_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, uint32_t base_qindex, uint64_t* d_mse, uint8_t* d_fb_counted,
+                                      svthip_cdef_result* d_result, int8_t* d_fb_strength, const svthip_lf_mi* d_mi, uint32_t mi_stride,
+                                      void* d_workspace, void* stream)
+{
+    TRY(enter(ctx));
+    return cdef_search128_entry(ctx, picture, base_qindex, 8, d_mse, d_fb_counted, d_result, d_fb_strength, d_mi, mi_stride, d_workspace, stream);
+}
+
+int32_t svthip_av1_highbd_cdef_search128_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, uint32_t base_qindex, uint32_t bit_depth,
+                                             uint64_t* d_mse, uint8_t* d_fb_counted, svthip_cdef_result* d_result, int8_t* d_fb_strength,
+                                             const svthip_lf_mi* d_mi, uint32_t mi_stride, void* d_workspace, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return cdef_search128_entry(ctx, picture, base_qindex, 10, d_mse, d_fb_counted, d_result, d_fb_strength, d_mi, mi_stride, d_workspace, stream);
 }
 
 int32_t svthip_av1_cdef_frame_dev(svthip_ctx* ctx, const svthip_cdef_picture* picture, const svthip_cdef_result* d_result,

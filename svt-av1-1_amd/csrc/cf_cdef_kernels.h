@@ -185,7 +185,10 @@ __device__ inline void cdef_load_tile(uint16_t* tile, const T* __restrict__ plan
 // ---------------------------------------------------------------- the strength search of one fb (cdef_seg_search, EbCdefProcess.c:157-246)
 // One workgroup per fb, its planes in turn.  An item of work is (8x8 block, primary strength): sixteen items a block, each lane filtering
 // its block once for the four secondary strengths of its primary strength from one read of the twelve taps.
-template <typename T>
+// RAW (the search for 128-wide blocks): the fb is a 64x64 quadrant of whatever fb the grid's block sizes make; `mse` is the workspace
+// [nfb][3][64] and receives the quadrant's unshifted sums per plane (0 where it lists nothing), `counted` whether it lists anything;
+// cdef_merge128_kernel forms the tables from them.
+template <typename T, bool RAW = false>
 __global__ __launch_bounds__(kThreads) void cdef_search_kernel(CdefPlanes<T> P, int damping, int coeff_shift, unsigned long long* __restrict__ mse,
                                                            uint8_t* __restrict__ counted, int32_t* __restrict__ dir_out, int32_t* __restrict__ var_out)
 {
@@ -250,13 +253,59 @@ __global__ __launch_bounds__(kThreads) void cdef_search_kernel(CdefPlanes<T> P, 
         }
         __syncthreads();
         for (int g = tid, n = 0; g < 64; g += kThreads, n++) {    // compute_cdef_dist's final shift, per plane; Cr is added to Cb's entry
+            if constexpr (RAW) {
+                mse[((size_t)fb * 3 + pli) * 64 + g] = acc[g];
+                continue;
+            }
             const unsigned long long d = acc[g] >> (2 * coeff_shift);
             if (pli == 0) mse[(size_t)fb * 64 + g] = d; else chroma[n] += d;
         }
     }
+    if constexpr (RAW) {
+        for (int g = tid; g < 3 * 64 && !any; g += kThreads) mse[(size_t)fb * 3 * 64 + g] = 0;
+        return;
+    }
     for (int g = tid, n = 0; g < 64; g += kThreads, n++) {
         if (!any) mse[(size_t)fb * 64 + g] = 0;
         mse[((size_t)nfb + fb) * 64 + g] = chroma[n];
+    }
+}
+
+// ---------------------------------------------------------------- the tables of a picture with 128-wide blocks (cdef_seg_search :160-193, :227-237)
+constexpr int kCdefBlock64x128 = 13, kCdefBlock128x64 = 14, kCdefBlock128x128 = 15;   // BlockSize
+constexpr int kCdefMergeThreads = kThreads == 1 ? 1 : 64;
+
+// what the sb_type of an fb's first cell makes of it: bit 0 two fbs wide, bit 1 two fbs high (values above 21 clamped as the deblocking kernels do)
+__device__ inline int cdef_fb_shape(const svthip_lf_mi* __restrict__ mi, uint32_t mi_stride, int fbx, int fby)
+{
+    const int type = min((int)mi[(size_t)fby * 16 * mi_stride + fbx * 16].sb_type, 21);
+    return (type == kCdefBlock128x128 || type == kCdefBlock128x64 ? 1 : 0) | (type == kCdefBlock128x128 || type == kCdefBlock64x128 ? 2 : 0);
+}
+
+// the second column or row of a wide block by the fb's own cell (:171-175, EbCdef.c:1478-1484)
+__device__ inline bool cdef_fb_is_twin(int shape, int fbx, int fby) { return ((fbx & 1) && (shape & 1)) || ((fby & 1) && (shape & 2)); }
+
+// One workgroup per fb, one lane per strength pair.  `counted` holds what the RAW search left: whether the fb's own 64x64 lists anything,
+// which is sb_all_skip of the first 64x64 whatever the extent.  An fb that is no twin and lists something sums the planes' raw sums over the
+// quadrants of its extent (clipped by the picture only), shifts once per plane and adds Cr to Cb; every other fb's rows are 0.  Each fb
+// reads its own flag only and forms its rows from its own extent, so grids whose blocks contradict each other follow the same rules.
+__global__ __launch_bounds__(kCdefMergeThreads) void cdef_merge128_kernel(const unsigned long long* __restrict__ raw, const svthip_lf_mi* __restrict__ mi,
+                                                                          uint32_t mi_stride, int w, int h, int coeff_shift,
+                                                                          unsigned long long* __restrict__ mse, uint8_t* __restrict__ counted)
+{
+    const int tid = threadIdx.x, fb = blockIdx.x, nhfb = cdef_fbs(w), nvfb = cdef_fbs(h), nfb = nhfb * nvfb;
+    const int fbx = fb % nhfb, fby = fb / nhfb;
+    const int shape = cdef_fb_shape(mi, mi_stride, fbx, fby);
+    const bool on = counted[fb] != 0 && !cdef_fb_is_twin(shape, fbx, fby);
+    __syncthreads();   // every lane has read the quadrant's flag
+    if (tid == 0) counted[fb] = on;
+    const int nx = (shape & 1) && fbx + 1 < nhfb ? 2 : 1, ny = (shape & 2) && fby + 1 < nvfb ? 2 : 1;
+    for (int g = tid; g < 64; g += kCdefMergeThreads) {
+        unsigned long long sum[3] = {};
+        for (int q = 0; q < nx * ny && on; q++)
+            for (int pli = 0; pli < 3; pli++) sum[pli] += raw[((size_t)(fb + (q / nx) * nhfb + q % nx) * 3 + pli) * 64 + g];
+        mse[(size_t)fb * 64 + g] = sum[0] >> (2 * coeff_shift);
+        mse[((size_t)nfb + fb) * 64 + g] = (sum[1] >> (2 * coeff_shift)) + (sum[2] >> (2 * coeff_shift));
     }
 }
 
@@ -268,6 +317,7 @@ struct CdefPickShared {
     int red_at[kCdefPickThreads];
     int lev0[16], lev1[16], n;
     unsigned long long best_tot;
+    int8_t pick[kCdefPickMaxFb];                // WIDE: per fb its own index, -1 where it is not counted
 };
 
 // search_one_dual_c (:1196-1242): the pair that lowers the total most, written to position nb of the lists.  Each lane sums its
@@ -308,9 +358,15 @@ __device__ inline void cdef_search_one_dual(CdefPickShared& S, int nb, const uns
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kCdefPickThreads) void cdef_pick_kernel(const unsigned long long* __restrict__ mse, const uint8_t* __restrict__ counted, int nfb,
-                                                                  double lambda, int damping, svthip_cdef_result* __restrict__ result,
-                                                                  int8_t* __restrict__ fb_strength)
+// WIDE (the pick for 128-wide blocks): the reference writes the picks in compacted (raster) order, each followed by its copies to the
+// other first cells of a 128-wide block (:1549-1569), later writes winning; a copy past the last fb column or row is dropped.  What
+// that leaves in an fb is the pick of the last counted fb, in raster order, that writes there: the fb itself, else the one to its left
+// if that is two fbs wide, else the one above if that is two high, else the one above left if that is both.  One lane per fb asks in
+// that order, so grids whose blocks contradict each other come out as under the serial walk.
+template <bool WIDE>
+__device__ inline void cdef_pick_fbs(const unsigned long long* __restrict__ mse, const uint8_t* __restrict__ counted, int nfb, double lambda, int damping,
+                                     svthip_cdef_result* __restrict__ result, int8_t* __restrict__ fb_strength, const svthip_lf_mi* __restrict__ mi,
+                                     uint32_t mi_stride, int nhfb)
 {
     __shared__ CdefPickShared S;
     __shared__ int str0[8], str1[8], bits;
@@ -323,7 +379,10 @@ __global__ __launch_bounds__(kCdefPickThreads) void cdef_pick_kernel(const unsig
             if (counted[fb]) S.fb_of[n++] = (uint16_t)fb;
         S.n = n, bits = 0, best_total = 1ull << 63;
     }
-    for (int fb = tid; fb < nfb; fb += kCdefPickThreads) fb_strength[fb] = -1;
+    for (int fb = tid; fb < nfb; fb += kCdefPickThreads) {
+        fb_strength[fb] = -1;
+        if constexpr (WIDE) S.pick[fb] = -1;
+    }
     __syncthreads();
     for (int i = 0; i <= 3; i++) {
         const int nb = 1 << i;
@@ -354,7 +413,18 @@ __global__ __launch_bounds__(kCdefPickThreads) void cdef_pick_kernel(const unsig
             const unsigned long long cur = m0[(size_t)S.fb_of[i] * 64 + str0[g]] + m1[(size_t)S.fb_of[i] * 64 + str1[g]];
             if (cur < best) best = cur, at = g;
         }
-        fb_strength[S.fb_of[i]] = (int8_t)at;
+        if constexpr (WIDE) S.pick[S.fb_of[i]] = (int8_t)at; else fb_strength[S.fb_of[i]] = (int8_t)at;
+    }
+    if constexpr (WIDE) {
+        __syncthreads();
+        for (int fb = tid; fb < nfb; fb += kCdefPickThreads) {
+            const int fbx = fb % nhfb, fby = fb / nhfb;
+            int v = S.pick[fb];
+            if (v < 0 && fbx > 0 && S.pick[fb - 1] >= 0 && (cdef_fb_shape(mi, mi_stride, fbx - 1, fby) & 1)) v = S.pick[fb - 1];
+            if (v < 0 && fby > 0 && S.pick[fb - nhfb] >= 0 && (cdef_fb_shape(mi, mi_stride, fbx, fby - 1) & 2)) v = S.pick[fb - nhfb];
+            if (v < 0 && fbx > 0 && fby > 0 && S.pick[fb - nhfb - 1] >= 0 && cdef_fb_shape(mi, mi_stride, fbx - 1, fby - 1) == 3) v = S.pick[fb - nhfb - 1];
+            fb_strength[fb] = (int8_t)v;
+        }
     }
     if (tid == 0) {
         result->cdef_bits = bits, result->nb_cdef_strengths = nb;
@@ -362,6 +432,21 @@ __global__ __launch_bounds__(kCdefPickThreads) void cdef_pick_kernel(const unsig
         result->pri_damping = result->sec_damping = damping;
         result->sb_count = S.n;
     }
+}
+
+__global__ __launch_bounds__(kCdefPickThreads) void cdef_pick_kernel(const unsigned long long* __restrict__ mse, const uint8_t* __restrict__ counted, int nfb,
+                                                                  double lambda, int damping, svthip_cdef_result* __restrict__ result,
+                                                                  int8_t* __restrict__ fb_strength)
+{
+    cdef_pick_fbs<false>(mse, counted, nfb, lambda, damping, result, fb_strength, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(kCdefPickThreads) void cdef_pick128_kernel(const unsigned long long* __restrict__ mse, const uint8_t* __restrict__ counted, int nfb,
+                                                                     double lambda, int damping, svthip_cdef_result* __restrict__ result,
+                                                                     int8_t* __restrict__ fb_strength, const svthip_lf_mi* __restrict__ mi, uint32_t mi_stride,
+                                                                     int nhfb)
+{
+    cdef_pick_fbs<true>(mse, counted, nfb, lambda, damping, result, fb_strength, mi, mi_stride, nhfb);
 }
 
 // ---------------------------------------------------------------- the frame filter (av1_cdef_frame, EbCdef.c:470-808), out of place
@@ -385,8 +470,9 @@ __global__ __launch_bounds__(kThreads) void cdef_frame_kernel(CdefPlanes<T> P, i
     const T* in = P.dbk[pli] + (size_t)y0 * P.dbk_stride[pli] + x0;
     T* out = P.out[pli] + (size_t)y0 * P.out_stride[pli] + x0;
     // the fb is passed over (:609-613), or this plane's strengths are both 0 and its filter returns its input (the clamp of x to the min
-    // and max over x and its taps)
-    if ((ys == 0 && uvs == 0) || !any || strength == 0) {
+    // and max over x and its taps).  An index of -1 is passed over as well (:565-570): with 64x64 fbs such an fb lists nothing anyway, a
+    // 128-wide fb left out for its first 64x64 may list blocks in the others.
+    if (fb_strength[fb] < 0 || (ys == 0 && uvs == 0) || !any || strength == 0) {
         for (int i = tid; i < rows * cols; i += kThreads) {
             const int r = i / cols, c = i - r * cols;
             out[(size_t)r * P.out_stride[pli] + c] = in[(size_t)r * P.dbk_stride[pli] + c];

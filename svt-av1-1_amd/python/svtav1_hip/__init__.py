@@ -24,7 +24,7 @@ from ._pred import (AV1_BLOCK_SIZES_WH, BI_PRED, CONVOLVE_COMPOUND_DESC_DTYPE, C
                     Prediction)
 from ._cfl import CFL_DECISION_DTYPE, CFL_DECISION_JOB_DTYPE, CFL_DESC_DTYPE, CFL_LUMA_SIZES_WH, Cfl
 from ._deblock import LF_MI_DTYPE, Deblocking, LfPicture, make_lf_picture
-from ._cdef import CDEF_PICK_MAX_FB, CDEF_RESULT_DTYPE, Cdef, CdefPicture, cdef_filter_blocks, make_cdef_picture
+from ._cdef import CDEF_PICK_MAX_FB, CDEF_RESULT_DTYPE, Cdef, CdefPicture, cdef_filter_blocks, cdef_search128_workspace_bytes, make_cdef_picture
 from ._restoration import (RESTORE_NONE, RESTORE_SGRPROJ, RESTORE_SWITCHABLE, RESTORE_WIENER, SGRPROJ_DETAIL_DTYPE, SGRPROJ_PARAMS,
                            WIENER_WALK_STATE_DTYPE, LrPicture, Restoration, lr_pick_workspace_bytes, lr_unit_geometry, lr_unit_sizes,
                            lr_workspace_bytes, make_lr_picture, rest_finish_rates_dtype, rest_finish_result_dtype, sgrproj_walk_max_trials,

@@ -1,5 +1,5 @@
 """CDEF (svthip_av1_[highbd_]cdef_search_mse_dev, svthip_cdef_pick_strengths_dev, .._cdef_search_dev, .._cdef_frame_dev,
-svthip_cdef_dist_8x8_batch_dev): pointer marshalling only."""
+svthip_cdef_dist_8x8_batch_dev, and the ..128 entries for grids with 128-wide blocks): pointer marshalling only."""
 from __future__ import annotations
 
 from . import _abi
@@ -15,6 +15,11 @@ CdefPicture = _abi.structure("svthip_cdef_picture")
 def cdef_filter_blocks(width, height):
     """(nhfb, nvfb): 64x64 filter blocks each way"""
     return (width // 4 + 15) // 16, (height // 4 + 15) // 16
+
+
+def cdef_search128_workspace_bytes(width, height) -> int:
+    """bytes of d_workspace for the ..search[_mse]128_dev entries; 0 for a size the entries refuse"""
+    return int(lib().svthip_cdef_search128_workspace_bytes(width, height))
 
 
 def make_cdef_picture(width, height, deblocked, deblocked_stride, d_skip, skip_stride, source=(None, None, None), source_stride=(0, 0, 0),
@@ -40,6 +45,20 @@ class Cdef:
     def av1_cdef_search_dev(self, picture, base_qindex, d_mse, d_fb_counted, d_result, d_fb_strength, bit_depth=8, stream=None):
         f, bd = _hbd(bit_depth, "cdef_search_dev")
         _check(f(self._h, _picture_ref(picture), base_qindex, *bd, d_mse, d_fb_counted, d_result, d_fb_strength, stream))
+
+    def av1_cdef_search_mse128_dev(self, picture, base_qindex, d_mse, d_fb_counted, d_mi, mi_stride, d_workspace, bit_depth=8, stream=None):
+        """d_mi: the svthip_lf_mi grid of the deblocking entries (sb_type of each fb's first cell is read)"""
+        f, bd = _hbd(bit_depth, "cdef_search_mse128_dev")
+        _check(f(self._h, _picture_ref(picture), base_qindex, *bd, d_mse, d_fb_counted, d_mi, mi_stride, d_workspace, stream))
+
+    def cdef_pick_strengths128_dev(self, d_mse, d_fb_counted, nhfb, nvfb, base_qindex, bit_depth, d_result, d_fb_strength, d_mi, mi_stride, stream=None):
+        _check(lib().svthip_cdef_pick_strengths128_dev(self._h, d_mse, d_fb_counted, nhfb, nvfb, base_qindex, bit_depth, d_result, d_fb_strength, d_mi,
+                                                       mi_stride, stream))
+
+    def av1_cdef_search128_dev(self, picture, base_qindex, d_mse, d_fb_counted, d_result, d_fb_strength, d_mi, mi_stride, d_workspace, bit_depth=8,
+                               stream=None):
+        f, bd = _hbd(bit_depth, "cdef_search128_dev")
+        _check(f(self._h, _picture_ref(picture), base_qindex, *bd, d_mse, d_fb_counted, d_result, d_fb_strength, d_mi, mi_stride, d_workspace, stream))
 
     def av1_cdef_frame_dev(self, picture, d_result, d_fb_strength, plane_start, plane_end, bit_depth=8, stream=None):
         f, bd = _hbd(bit_depth, "cdef_frame_dev")

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Times the CDEF entries on a synthetic 1920 x 1080 picture (30 x 17 filter blocks), 8 and 10 bits: the strength search of all filter
 blocks, the strength pick, the frame filter of the three planes with the search's own result, and, next to them, the two copies of the
-three planes that a host CDEF between two device stages costs (device to pinned host memory and back, hipMemcpyAsync on the same stream).
+three planes that a host CDEF between two device stages costs (device to pinned host memory and back, hipMemcpyAsync on the same stream);
+then the search and the pick for grids with 128-wide blocks, on a grid of BLOCK_64X64 (the same 510 fbs) and on one of BLOCK_128X128
+(135 wide fbs), with the existing pick on the same tables beside them.
 
     python tools/cdef_probe.py [--iters N] [--out FILE]          device times (needs a GPU)
     python tools/cdef_probe.py --cpu [--out FILE]                the CPU yardstick (build container only, where the reference exists)
@@ -96,6 +98,26 @@ def device_times(lines, iters):
         report("cdef_search (search + pick, one call)", bd,
                lambda: ctx.av1_cdef_search_dev(pic, QINDEX, d_mse.data_ptr(), d_cnt.data_ptr(), d_res.data_ptr(), d_fbs.data_ptr(), bit_depth=bd,
                                                stream=stream), 2)
+
+        # the entries for grids with 128-wide blocks: on a grid of 64X64 blocks (the same 510 fbs) and on one of 128X128 blocks (135 wide fbs)
+        d_work = torch.zeros(svtav1_hip.cdef_search128_workspace_bytes(W, H) // 8, dtype=torch.int64, device="cuda:0")
+        for label, sb_type in (("64X64 grid, 510 fbs", 12), ("128X128 grid, 135 wide fbs", 15)):
+            grid = np.zeros((H // 4, W // 4), svtav1_hip.LF_MI_DTYPE)
+            grid["sb_type"] = sb_type
+            d_mi = dev(grid)
+            torch.cuda.synchronize()
+            report(f"cdef_search_mse128 ({label})", bd,
+                   lambda: ctx.av1_cdef_search_mse128_dev(pic, QINDEX, d_mse.data_ptr(), d_cnt.data_ptr(), d_mi.data_ptr(), W // 4, d_work.data_ptr(), bit_depth=bd,
+                                                          stream=stream), 2, fbs=nfb)
+            report(f"cdef_pick_strengths128 ({label})", bd,
+                   lambda: ctx.cdef_pick_strengths128_dev(d_mse.data_ptr(), d_cnt.data_ptr(), nh, nv, QINDEX, bd, d_res.data_ptr(), d_fbs.data_ptr(), d_mi.data_ptr(),
+                                                          W // 4, stream=stream), 2)
+            torch.cuda.synchronize()
+            res = d_res.cpu().numpy().view(svtav1_hip.CDEF_RESULT_DTYPE)[0]
+            lines[-1].update(sb_count=int(res["sb_count"]), cdef_bits=int(res["cdef_bits"]))
+            report(f"cdef_pick_strengths on the same tables ({label})", bd,
+                   lambda: ctx.cdef_pick_strengths_dev(d_mse.data_ptr(), d_cnt.data_ptr(), nh, nv, QINDEX, bd, d_res.data_ptr(), d_fbs.data_ptr(), stream=stream), 2,
+                   sb_count=int(res["sb_count"]))
 
         def copies():
             for h, d in zip(pinned, d_dbk):
