@@ -2305,6 +2305,105 @@ int32_t svthip_open_loop_intra_search_batch_dev(svthip_ctx *ctx, const uint8_t *
 int32_t svthip_open_loop_intra_search_picture(svthip_ctx *ctx, const svthip_host_picture *cur, const svthip_ois_params *params,
                                               const void *const *me_results, uint32_t n_pu, uint32_t *cand, uint8_t *total);
 
+/* ---------------------------------------------------------------------------------------------
+ * Motion-analysis statistics: what the reference's ME process, initial rate control and source-based operations derive from the ME
+ * results, the OIS candidate words and two more passes over picture samples, so that those tables never have to leave the device.
+ * Five entries; every one takes n_pics pictures of EQUAL dimensions (at most SVTHIP_HME_MAX_JOBS), device pointers for tables and
+ * samples, HOST arrays for what differs between the pictures (descriptors, params), enqueues on `stream` and does not synchronise.
+ * Geometry as svthip_pa_picture: SBs of 64x64 in raster order, n_sb = ceil(width / 64) * ceil(height / 64); a complete SB lies wholly
+ * inside the picture.  Width and height are multiples of 8.  8-bit planes (these stages read the 8-bit planes at every bit depth).
+ * All outputs are bit-identical to the reference.
+ *
+ * Out of scope, host code over the few bytes per SB these entries leave: the stationary-edge functions and everything over
+ * edge_results_ptr (Codec/EbInitialRateControlProcess.c:486-), the sliding-window updates over several pictures of
+ * InitialRateControlKernel, the chroma-mean classifiers and the picture-level derivations of source_based_operations_kernel.
+ * CheckForNonUniformMotionVectorField (:173-250) computes a local count and stores nothing: it has no device form.
+ *
+ * d_me: [n_pics][n_sb][me_pu_stride] svthip_me_cu_result, me_pu_stride 85 or 209, raster PU order; d_ois_cand: [n_pics][n_sb][85][18]
+ * OisCandidate_t words as svthip_open_loop_intra_search_batch_dev leaves them (distortion in bits 0..19).  Of the OIS words these entries
+ * read candidate 0 of the four 32x32 CUs (raster CU 1..4) of COMPLETE SBs only.  OpenLoopIntraSearchLcu writes that distortion on every
+ * one of its branches (Codec/EbMotionEstimation.c:8113, :8264 via SortIntraModesOpenLoop, :7973-8000, :8315, :7525-7745): a 32x32 CU of a
+ * complete SB is always valid and never skipped by cu8x8_mode, so the reference never reads a word here that an earlier picture left
+ * behind, and the zeros that the OIS entry writes into words the reference leaves untouched are never read. */
+typedef struct svthip_ma_picture_params {
+    uint8_t slice_is_intra;              /* slice_type == I_SLICE */
+    uint8_t temporal_layer_index;        /* 0..5 */
+    uint8_t hierarchical_levels;         /* 0..5 */
+    uint8_t is_used_as_reference_flag;
+    uint8_t intensity_transition_flag;
+    uint8_t reserved[3];
+    uint32_t ref_index;                  /* svthip_ma_sb_flags_dev: which of the n_ref_pics reference tables is this picture's list-0 reference */
+} svthip_ma_picture_params;
+
+/* ComputeDecimatedZzSad (Codec/EbMotionEstimationProcess.c:219-348): per complete SB the SAD of the 16x16 window of the CURRENT picture's
+ * 1/16 plane at (sb_x >> 2, sb_y >> 2) against the samples prev[(sb_y + 4 r) * stride + sb_x + 4 c] of the PREVIOUS input picture's
+ * full-resolution plane (Decimation2D with step 4, Codec/EbPictureAnalysisProcess.c:100-125, never materialised).
+ *   d_sad [n_pics][n_sb]               decimatedLcuCollocatedSad (~0 for an incomplete SB)
+ *   d_zz_cost [n_pics][n_sb]           zz_cost_array: the ladder of :307-327, INVALID_ZZ_COST (255) for an incomplete SB
+ *   d_non_moving_index [n_pics][n_sb]  non_moving_index_array: the ladder of :332-343
+ * The reference stores both arrays in the PREVIOUS picture's control set (previous_picture_control_set_wrapper_ptr), not the current one.
+ * cur[j]: only the 1/16 plane is read (svthip_pa_derive_planes_dev must have built it); prev[j]: only the full-resolution plane.  Nothing
+ * outside the two pictures' interiors is read, and nothing at all of an incomplete SB. */
+int32_t svthip_ma_zz_sad_dev(svthip_ctx *ctx, const uint8_t *d_pool, const svthip_pa_picture *cur, const svthip_pa_picture *prev,
+                             uint32_t n_pics, uint32_t *d_sad, uint8_t *d_zz_cost, uint8_t *d_non_moving_index, void *stream);
+
+/* CalculateAcEnergy (Codec/EbSourceBasedOperationsProcess.c:347-408) over ComputeNxMSatdSadLCU (Codec/EbPictureOperators.c:286-367) and
+ * the 8x8 Hadamard leaf Compute8x8Satd_U8_SSE4 (ASM_SSE4_1/EbPictureOperators_Intrinsic_SSE4_1.c:250-): for every complete SB of a picture
+ * with params[j].slice_is_intra, the 64x64 energy and the four 32x32 energies of the source luma, each the sum over its 8x8 blocks of
+ * (sum |coefficient| + 2) >> 2 minus (sum |DC|) >> 2 -- the DC sum is shifted once per block group, so the 64x64 value is not the sum
+ * of the other four.
+ *   d_energy [n_pics][n_sb][5]  sb_y_src_energy_cu_array,  d_mean [n_pics][n_sb][5]  sb_y_src_mean_cu_array (entries 0..4 of d_y_mean)
+ * Every other SB, and every SB of a picture that is not intra, gets the reference's sentinel 100000000 in all ten words.
+ * d_y_mean: the [n_pics][n_sb][85] table of svthip_pa_block_stats_dev.  Only the interior of the full-resolution plane is read. */
+int32_t svthip_ma_ac_energy_dev(svthip_ctx *ctx, const uint8_t *d_pool, const svthip_pa_picture *pics,
+                                const svthip_ma_picture_params *params, uint32_t n_pics, const uint8_t *d_y_mean, uint64_t *d_energy,
+                                uint64_t *d_mean, void *stream);
+
+/* The tail of MotionEstimateLcu (Codec/EbMotionEstimation.c:7150-7158) and the distortion-histogram loop of MotionEstimationKernel
+ * (Codec/EbMotionEstimationProcess.c:607-725, both arms; the reference runs them when rate_control_mode != 0), for whole pictures:
+ *   d_rc_me_distortion [n_pics][n_sb]          sum of distortion[0] of PUs 5..20 (0 on an intra picture, where the reference writes nothing)
+ *   d_inter_sad_interval_index [n_pics][n_sb]  0 for an incomplete SB and on intra pictures
+ *   d_intra_sad_interval_index [n_pics][n_sb]  0 for an incomplete SB
+ *   d_histograms [n_pics][2][128]              me_distortion_histogram (all 0 on an intra picture), then ois_distortion_histogram
+ *   d_full_sb_count [n_pics]                   full_sb_count
+ * The counters are uint32_t (the reference's are uint16_t; they agree below 65536 complete SBs).  The compression above interval 63 and the
+ * clamp at 127 are as written, the uint16_t casts of :629-633 and :657 included.  d_me may be NULL when every picture is intra. */
+int32_t svthip_ma_distortion_stats_dev(svthip_ctx *ctx, const svthip_me_cu_result *d_me, uint32_t me_pu_stride,
+                                       const uint32_t *d_ois_cand, uint32_t width, uint32_t height,
+                                       const svthip_ma_picture_params *params, uint32_t n_pics, uint32_t *d_rc_me_distortion,
+                                       uint32_t *d_inter_sad_interval_index, uint32_t *d_intra_sad_interval_index,
+                                       uint32_t *d_histograms, uint32_t *d_full_sb_count, void *stream);
+
+/* MeBasedGlobalMotionDetection / DetectGlobalMotion (Codec/EbInitialRateControlProcess.c:30-56, 68-154, 253-406, 467-483) from entry 0 of
+ * every complete SB's ME row and its four neighbours' (zero vectors at the picture borders by the reference's own rules, which for right
+ * and bottom test origin + 128 > size), thresholds GLOBAL_MOTION_THRESHOLD[hierarchical_levels][temporal_layer_index]:
+ *   d_global_motion [n_pics][12] int32 = is_pan, is_tilt, panMvx, panMvy, tiltMvx, tiltMvy, totalCheckedLcus, totalPanLcus, totalTiltLcus,
+ *                                        totalPanHighAmpLcus, totalTiltHighAmpLcus, rows without a list-0 candidate
+ * The vector sums are signed 64-bit and divided as C divides (towards zero) before the reference's (int16_t).  On an intra picture all
+ * twelve words are 0 (both flags false; the reference leaves the vectors alone).
+ * GetMv (:30-56) leaves its caller's variables untouched when entry 0 has no UNI_PRED_LIST_0 candidate, so the reference then carries the
+ * vector of whichever SB it looked at before.  The device's own ME always writes such a candidate.  This entry does not emulate the carry:
+ * it takes (0, 0) for such a row, counts them in word 11 over the complete SBs, and promises the reference's result only when that count
+ * is 0.  Width and height must be at least 64: the reference divides by the number of complete SBs. */
+int32_t svthip_ma_global_motion_dev(svthip_ctx *ctx, const svthip_me_cu_result *d_me, uint32_t me_pu_stride, uint32_t width,
+                                    uint32_t height, const svthip_ma_picture_params *params, uint32_t n_pics,
+                                    int32_t *d_global_motion, void *stream);
+
+/* DeriveSimilarCollocatedFlag (Codec/EbInitialRateControlProcess.c:1286-1329), FailingMotionLcu and DetectUncoveredLcu
+ * (Codec/EbSourceBasedOperationsProcess.c:214-341) with the false defaults that source_based_operations_kernel writes before it calls them
+ * (:1062, :1072):
+ *   d_flags [n_pics][n_sb][4] uint8 = similar_colocated_sb_array, similar_colocated_sb_array_ii, failing_motion_sb_flag,
+ *                                     uncovered_area_sb_flag
+ * d_y_mean / d_variance: this launch's [n_pics][n_sb][85] tables of svthip_pa_block_stats_dev (entry 0 read).  d_ref_y_mean /
+ * d_ref_variance: the tables of the list-0 reference pictures, [n_ref_pics][n_sb][ref_row_stride] with the 64x64 entry first -- the tables
+ * of svthip_pa_block_stats_dev with ref_row_stride 85, or packed per-SB arrays as EbPaReferenceObject_t keeps them with ref_row_stride 1;
+ * params[j].ref_index picks picture j's reference among them.  On an intra picture all four flags are 0 and neither the reference
+ * tables nor d_me nor d_ois_cand are read; all of them may be NULL when every picture is intra. */
+int32_t svthip_ma_sb_flags_dev(svthip_ctx *ctx, const uint8_t *d_y_mean, const uint16_t *d_variance, const uint8_t *d_ref_y_mean,
+                               const uint16_t *d_ref_variance, uint32_t ref_row_stride, uint32_t n_ref_pics,
+                               const svthip_me_cu_result *d_me, uint32_t me_pu_stride, const uint32_t *d_ois_cand, uint32_t width,
+                               uint32_t height, const svthip_ma_picture_params *params, uint32_t n_pics, uint8_t *d_flags, void *stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-GPU: superblocks of a picture sharded over the GPUs of one node, RCCL over xGMI for the one real exchange.
