@@ -2192,7 +2192,8 @@ int32_t svthip_md_full_loop_batch_dev(svthip_ctx *ctx, const svthip_inter_planes
  * Refused with SVTHIP_ERR_BAD_PARAMETER before any launch: a size other than 128x128, 128x64 and 64x128 (the 19 sizes of the entry above
  * included); everything else as above.
  * Not here: 16-bit planes; predicting the blocks (the prediction entries take all 22 sizes); the fill of cu_ptr / txb_ptr, which is
- * host work on d_result and d_tu; in-loop motion estimation for 128x128 superblocks, which stays as documented. */
+ * host work on d_result and d_tu; in-loop motion estimation for 128x128 superblocks, which stays as documented.  Turning the block
+ * costs of both full-loop entries into a partition and a picture is svthip_md_partition_batch_dev / _compose_dev below. */
 typedef struct svthip_md_full128_tu {
     uint16_t eob[3][4]; /* [plane][txb_itr] */
     uint8_t reserved[8];
@@ -2208,6 +2209,142 @@ int32_t svthip_md_full_loop128_batch_dev(svthip_ctx *ctx, const svthip_inter_pla
                                          uint32_t tiles_per_row, const svthip_inter_planes *recon, void *d_work, uint32_t stages,
                                          svthip_md_full_result *d_result, svthip_md_full128_tu *d_tu, svthip_md_full_decision *d_decision,
                                          void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mode decision's partition decision: what mode_decision_sb (Codec/EbProductCodingLoop.c:2762-2880) does around md_encode_block with
+ * the block costs -- d1_non_square_block_decision (Codec/EbFullLoop.c:2086-2108), d2_inter_depth_block_decision with
+ * compute_depth_costs (:2113-2256, :2368-2437) and Av1SplitFlagRate (Codec/EbRateDistortionCost.c:2304-2378) -- then the walk by which
+ * EncodePass finds the final blocks (Codec/EbCodingLoop.c:3051-3069, :4111-4114), and the copy of their winner tiles into one picture.
+ * 8-bit 4:2:0, superblocks of 64x64 or 128x128.  One launch decides n_sb superblocks: the partition contexts take part in no decision
+ * the reference makes (every Av1SplitFlagRate call of compute_depth_costs is for a square wholly inside the picture, where the rate is
+ * partitionFacBits[partition_cdf_length(bsize)][type] and the contexts are not read), so superblocks do not depend on each other.
+ *
+ * GEOMETRY.  svthip_md_partition_geometry writes the block table of md_scan_all_blks (Codec/EbUtility.c:702-837) for sb_size 64 (1101
+ * blocks, 341 squares) or 128 (4421 blocks, 1365 squares) in md-scan order and returns the block count; at most `max` records are
+ * written (out may be NULL with max 0); 0 for another sb_size.  Host code, no context.  svthip_md_partition_block (16 bytes): origin_x /
+ * origin_y inside the superblock, bwidth / bheight, shape (PART: 0 N, 1 H, 2 V, 3 HA, 4 HB, 5 VA, 6 VB, 7 H4, 8 V4), depth, nsi, totns,
+ * sqi_mds (the block's square), parent_mds (the square above that square, 0xffff for the root), is_last_quadrant (of the block's
+ * square), has_uv, bwidth_uv / bheight_uv.  The device computes the same records from the index; no table is uploaded.
+ *
+ * THE DECISION.  svthip_md_partition_batch_dev, on the caller's stream, nothing read back:
+ *   d_sb [n_sb]        svthip_md_partition_sb: first_leaf, leaf_count (its leaves in d_leaf), full_lambda, origin_x / origin_y of the
+ *                      superblock in the picture.
+ *   d_leaf [n_leaf]    svthip_md_partition_leaf, in the order of the reference's leaf_data_array: mds_idx, tot_d1_blocks, split_flag,
+ *                      decision_index (the block's cost is d_decision[decision_index].cost; SVTHIP_MD_PART_NONE means MAX_MODE_COST =
+ *                      13616969489728 * 8, what md_encode_block gives a non-square block of an incomplete superblock, :2430-2442,
+ *                      :2683), pool_x / pool_y (where the block's winner tile lies in the tile pool: `recon_x / recon_y` of the
+ *                      full-loop call that made it; chroma at ((p >> 3) << 3) / 2).
+ *   d_decision         ONE array of svthip_md_full_decision; each svthip_md_full_loop*_batch_dev call writes its own sub-range.
+ *   partition_fac_bits md_rate_estimation_ptr->partitionFacBits as [20][11] int32, a HOST array read during the call (rows 0, 4, 8, 10
+ *                      and the columns PARTITION_NONE and PARTITION_SPLIT are what the walk reads).
+ *   slice_is_intra     slice_type == I_SLICE.
+ * The walk is the reference's, what looks odd included:
+ *   start   every square has split_flag 1, part PARTITION_SPLIT, untested (Initialize_cu_data_structure, :663-697); a listed block
+ *           takes split_flag and mdc_split_flag from its leaf, best_d1_blk = its own index, tested.
+ *   d1      at a listed block with nsi + 1 == totns: the costs of the shape's blocks are summed (uint64, wrapping); PART_N assigns the
+ *           square's cost, part and best_d1_blk unconditionally, another shape on strict < against the square's cost.
+ *   d2      at a leaf where the count of d1 blocks (1 at a PART_N leaf, else one more) equals its tot_d1_blocks: nothing unless the
+ *           square's split_flag is 0; then, while the square is a last quadrant: parent cost = its cost + RDCOST of the non-split
+ *           rate if it was tested, else MAX_MODE_COST; children cost = the four costs + RDCOST of the parent's split rate + per child
+ *           with mdc_split_flag 0 the RDCOST of its non-split rate, the latter only when the LEAF is larger than 4x4 (FIX_INTER_DEPTH
+ *           tests context_ptr->blk_geom, :2196); RDCOST(bits) = (bits * full_lambda + 256) >> 9; parent <= children: split_flag = 0,
+ *           cost = parent cost; else cost = children cost, part = PARTITION_SPLIT (split_flag stays).
+ *   intra   with the parent at index 0 of an intra slice compute_depth_costs is skipped (FIX_DEBUG_CRASH, :2410-2412): the parent
+ *           cost is MAX_MODE_COST and the children cost is what the previous level of the same climb left (0 at its first level).
+ *   unlisted  a block that no leaf names has cost MAX_MODE_COST and every field the reference never assigns 0 (mdc_split_flag
+ *           included).  The reference reads whatever an earlier superblock left there; the lists it ships never make it.
+ * Outputs:
+ *   d_result [n_sb][n_blocks]  svthip_md_partition_result per md-scan index: cost, leaf (index into d_leaf, SVTHIP_MD_PART_NONE when
+ *                      not listed), best_d1_blk, part (PartitionType: 0 NONE, 1 HORZ, 2 VERT, 3 SPLIT, 4 HORZ_A, 5 HORZ_B, 6 VERT_A,
+ *                      7 VERT_B, 8 HORZ_4, 9 VERT_4), flags (SVTHIP_MD_PART_SPLIT_FLAG | _TESTED | _MDC_SPLIT_FLAG).
+ *   d_final [n_sb][max_final], d_final_count [n_sb]  the final blocks in coding order: from index 0, a square whose part is not
+ *                      PARTITION_SPLIT gives the ns_blk_num[part] blocks from ns_blk_offset[part] on (by part, not best_d1_blk, as
+ *                      EncodePass does) and its whole subtree is passed over, another square is descended into.  max_final is
+ *                      SVTHIP_MD_PART_MAX_FINAL_64 or _128.  svthip_md_partition_final: leaf, mds_idx, x / y in the picture, bwidth,
+ *                      bheight, has_uv, part (of its square), n_part (the block count of that part).  A final block that no leaf
+ *                      names has leaf = SVTHIP_MD_PART_NONE and is counted.
+ * Refused with SVTHIP_ERR_BAD_PARAMETER and text before any launch: sb_size other than 64 / 128; with n_sb > 0 (n_sb == 0 returns OK) a
+ * null pointer, an array not 16-byte aligned (d_final_count 4).  Refused ON THE DEVICE, counted and reported by
+ * svthip_inter_pred_refused: a superblock whose leaf range passes n_leaf or the block count, and per leaf an mds_idx beyond the table, an
+ * mds_idx not above its predecessor's, a decision_index beyond n_decision -- such a superblock keeps the start state in d_result and
+ * gets no final block --, and every final block without a leaf.
+ *
+ * THE COMPOSITION.  svthip_md_partition_compose_dev copies, for every final block with a leaf, the winner tile from `pool` at the
+ * leaf's pool_x / pool_y to `dst` at x / y: Y bwidth x bheight, and for a block with has_uv Cb and Cr bwidth_uv x bheight_uv at
+ * ((p >> 3) << 3) / 2 in both.  Rows move in the widest unit (16, 8, 4, 2, 1 bytes) that both addresses, both strides and the width
+ * are multiples of; no byte outside a tile is read or written.  width x height (dst) and pool_width x pool_height are luma sizes, chroma
+ * planes hold (w + 1) / 2 x (h + 1) / 2: a block whose tile would pass either is skipped and counted on the device, as is a d_final_count
+ * above max_final.  Host refusals as above, and a null plane, a picture or pool size of 0, a stride below the width of its plane.
+ * Every host refusal is made before the context is looked at.
+ * svthip_md_partition_picture_dev is both steps on one stream with nothing in between.
+ *
+ * Where they go: after the svthip_md_full_loop*_batch_dev calls of a picture, in place of EbProductCodingLoop.c:2823-2873 for all its
+ * superblocks; d_final is what EncodePass's loop visits, d_result[..].part its cu_partition_array.
+ * Not here: the neighbour-array updates of md_update_all_neighbour_arrays* and the contexts of everything except partition (their
+ * inputs are the candidates' rates, host work before the full loop); filling cu_ptr / final_cu_arr (host work on d_final and the
+ * full loop's results); 16-bit planes; writing svthip_lf_mi. */
+#define SVTHIP_MD_PART_NONE 0xffffffffu
+#define SVTHIP_MD_PART_SPLIT_FLAG 1u
+#define SVTHIP_MD_PART_TESTED 2u
+#define SVTHIP_MD_PART_MDC_SPLIT_FLAG 4u
+#define SVTHIP_MD_PART_BLOCKS_64 1101
+#define SVTHIP_MD_PART_BLOCKS_128 4421
+#define SVTHIP_MD_PART_MAX_FINAL_64 256
+#define SVTHIP_MD_PART_MAX_FINAL_128 1024
+
+typedef struct svthip_md_partition_block {
+    uint8_t origin_x, origin_y, bwidth, bheight;
+    uint8_t shape, depth, nsi, totns;
+    uint16_t sqi_mds, parent_mds;
+    uint8_t is_last_quadrant, has_uv;
+    uint8_t bwidth_uv, bheight_uv;
+} svthip_md_partition_block;
+
+typedef struct svthip_md_partition_sb {
+    uint32_t first_leaf, leaf_count;
+    uint32_t full_lambda;
+    uint16_t origin_x, origin_y;
+} svthip_md_partition_sb;
+
+typedef struct svthip_md_partition_leaf {
+    uint32_t decision_index;
+    uint16_t mds_idx;
+    uint8_t tot_d1_blocks, split_flag;
+    uint16_t pool_x, pool_y;
+    uint8_t reserved[4];
+} svthip_md_partition_leaf;
+
+typedef struct svthip_md_partition_result {
+    uint64_t cost;
+    uint32_t leaf;
+    uint16_t best_d1_blk;
+    uint8_t part, flags;
+} svthip_md_partition_result;
+
+typedef struct svthip_md_partition_final {
+    uint32_t leaf;
+    uint16_t mds_idx;
+    uint16_t x, y;
+    uint8_t bwidth, bheight;
+    uint8_t has_uv, part, n_part, reserved;
+} svthip_md_partition_final;
+
+uint32_t svthip_md_partition_geometry(uint32_t sb_size, svthip_md_partition_block *out, uint32_t max);
+int32_t svthip_md_partition_batch_dev(svthip_ctx *ctx, const svthip_md_partition_sb *d_sb, uint32_t n_sb,
+                                      const svthip_md_partition_leaf *d_leaf, uint32_t n_leaf, const svthip_md_full_decision *d_decision,
+                                      uint32_t n_decision, uint32_t sb_size, int32_t slice_is_intra, const int32_t partition_fac_bits[20 * 11],
+                                      svthip_md_partition_result *d_result, svthip_md_partition_final *d_final, uint32_t *d_final_count,
+                                      void *stream);
+int32_t svthip_md_partition_compose_dev(svthip_ctx *ctx, uint32_t n_sb, const svthip_md_partition_leaf *d_leaf, uint32_t n_leaf,
+                                        uint32_t sb_size, const svthip_md_partition_final *d_final, const uint32_t *d_final_count,
+                                        const svthip_inter_planes *pool, uint32_t pool_width, uint32_t pool_height,
+                                        const svthip_inter_planes *dst, uint32_t width, uint32_t height, void *stream);
+int32_t svthip_md_partition_picture_dev(svthip_ctx *ctx, const svthip_md_partition_sb *d_sb, uint32_t n_sb,
+                                        const svthip_md_partition_leaf *d_leaf, uint32_t n_leaf, const svthip_md_full_decision *d_decision,
+                                        uint32_t n_decision, uint32_t sb_size, int32_t slice_is_intra, const int32_t partition_fac_bits[20 * 11],
+                                        svthip_md_partition_result *d_result, svthip_md_partition_final *d_final, uint32_t *d_final_count,
+                                        const svthip_inter_planes *pool, uint32_t pool_width, uint32_t pool_height,
+                                        const svthip_inter_planes *dst, uint32_t width, uint32_t height, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Reference-layout results and host-pointer forms (what a C host that owns host memory binds).

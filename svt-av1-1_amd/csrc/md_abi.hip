@@ -71,6 +71,42 @@ int32_t md_full_loop(bool wide, svthip_ctx* ctx, const svthip_inter_planes* src,
     return SVTHIP_OK;
 }
 
+// The three partition entries: `decide` and `compose` say which launches run.  What needs no device is checked before the context is
+// entered, so a refusal does not depend on one.
+int32_t md_partition(bool decide, bool compose, svthip_ctx* ctx, const svthip::MdPartCall& C, const svthip_inter_planes* pool, const svthip_inter_planes* dst,
+                     void* stream)
+{
+    if (C.sb_size != 64u && C.sb_size != 128u) return fail(SVTHIP_ERR_BAD_PARAMETER, "sb_size must be 64 or 128 (got %d)", (int)C.sb_size);
+    if (C.n_sb) {
+        TRY(check_non_null({C.leaf, C.final_, C.final_count}));
+        if (!aligned({C.leaf, C.final_}, 16) || !aligned(C.final_count, 4))
+            return fail(SVTHIP_ERR_BAD_PARAMETER, "leaf and final-block arrays must be 16-byte aligned, the final counts 4-byte");
+        if (decide) {
+            TRY(check_non_null({C.sb, C.decision, C.partition_fac_bits, C.result}));
+            if (!aligned({C.sb, C.decision, C.result}, 16))
+                return fail(SVTHIP_ERR_BAD_PARAMETER, "superblock, decision and result arrays must be 16-byte aligned");
+        }
+        if (compose) {
+            TRY(check_non_null({pool, dst}));
+            TRY(check_non_null({pool->y, pool->cb, pool->cr, dst->y, dst->cb, dst->cr}));
+            if (!C.width || !C.height || !C.pool_width || !C.pool_height)
+                return fail(SVTHIP_ERR_BAD_PARAMETER, "picture and pool sizes must not be 0 (%d x %d, %d x %d)", (int)C.width, (int)C.height, (int)C.pool_width,
+                            (int)C.pool_height);
+            if (pool->y_stride < C.pool_width || pool->c_stride < (C.pool_width + 1u) / 2u || dst->y_stride < C.width || dst->c_stride < (C.width + 1u) / 2u)
+                return fail(SVTHIP_ERR_BAD_PARAMETER, "a plane stride is below the width of its plane");
+        }
+    }
+    TRY(enter(ctx));
+    if (C.n_sb == 0) return SVTHIP_OK;
+    svthip::MdPartCall call = C;
+    if (compose) call.pool = *pool, call.dst = *dst;
+    hipStream_t s;
+    TRY(refused_counter(ctx, stream, &s, &call.refused));
+    if (decide) HIP_TRY(svthip::launch_md_part_decide(call, s));
+    if (compose) HIP_TRY(svthip::launch_md_part_compose(call, s));
+    return SVTHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -189,6 +225,47 @@ int32_t svthip_md_full_loop128_batch_dev(svthip_ctx* ctx, const svthip_inter_pla
 {
     return md_full_loop(true, ctx, src, pred, d_fast, d_full, n_cand, d_group, d_pick, n_groups, bwidth, bheight, d_qparams, d_iscan, iscan_offsets, d_tables,
                         reduced_tx_set, 1, 1, max_full, slot_recon, tiles_per_row, recon, d_work, stages, d_result, d_tu, d_decision, stream);
+}
+
+// ---------------------------------------------------------------- mode decision's partition decision
+
+uint32_t svthip_md_partition_geometry(uint32_t sb_size, svthip_md_partition_block* out, uint32_t max) { return svthip::md_part_geometry(sb_size, out, max); }
+
+int32_t svthip_md_partition_batch_dev(svthip_ctx* ctx, const svthip_md_partition_sb* d_sb, uint32_t n_sb, const svthip_md_partition_leaf* d_leaf,
+                                      uint32_t n_leaf, const svthip_md_full_decision* d_decision, uint32_t n_decision, uint32_t sb_size,
+                                      int32_t slice_is_intra, const int32_t partition_fac_bits[20 * 11], svthip_md_partition_result* d_result,
+                                      svthip_md_partition_final* d_final, uint32_t* d_final_count, void* stream)
+{
+    svthip::MdPartCall C = {};
+    C.sb = d_sb, C.leaf = d_leaf, C.decision = d_decision, C.n_sb = n_sb, C.n_leaf = n_leaf, C.n_decision = n_decision, C.sb_size = sb_size;
+    C.slice_is_intra = slice_is_intra, C.partition_fac_bits = partition_fac_bits, C.result = d_result, C.final_ = d_final, C.final_count = d_final_count;
+    return md_partition(true, false, ctx, C, nullptr, nullptr, stream);
+}
+
+int32_t svthip_md_partition_compose_dev(svthip_ctx* ctx, uint32_t n_sb, const svthip_md_partition_leaf* d_leaf, uint32_t n_leaf, uint32_t sb_size,
+                                        const svthip_md_partition_final* d_final, const uint32_t* d_final_count, const svthip_inter_planes* pool,
+                                        uint32_t pool_width, uint32_t pool_height, const svthip_inter_planes* dst, uint32_t width, uint32_t height,
+                                        void* stream)
+{
+    svthip::MdPartCall C = {};
+    C.leaf = d_leaf, C.n_sb = n_sb, C.n_leaf = n_leaf, C.sb_size = sb_size;
+    C.final_ = const_cast<svthip_md_partition_final*>(d_final), C.final_count = const_cast<uint32_t*>(d_final_count);
+    C.pool_width = pool_width, C.pool_height = pool_height, C.width = width, C.height = height;
+    return md_partition(false, true, ctx, C, pool, dst, stream);
+}
+
+int32_t svthip_md_partition_picture_dev(svthip_ctx* ctx, const svthip_md_partition_sb* d_sb, uint32_t n_sb, const svthip_md_partition_leaf* d_leaf,
+                                        uint32_t n_leaf, const svthip_md_full_decision* d_decision, uint32_t n_decision, uint32_t sb_size,
+                                        int32_t slice_is_intra, const int32_t partition_fac_bits[20 * 11], svthip_md_partition_result* d_result,
+                                        svthip_md_partition_final* d_final, uint32_t* d_final_count, const svthip_inter_planes* pool,
+                                        uint32_t pool_width, uint32_t pool_height, const svthip_inter_planes* dst, uint32_t width, uint32_t height,
+                                        void* stream)
+{
+    svthip::MdPartCall C = {};
+    C.sb = d_sb, C.leaf = d_leaf, C.decision = d_decision, C.n_sb = n_sb, C.n_leaf = n_leaf, C.n_decision = n_decision, C.sb_size = sb_size;
+    C.slice_is_intra = slice_is_intra, C.partition_fac_bits = partition_fac_bits, C.result = d_result, C.final_ = d_final, C.final_count = d_final_count;
+    C.pool_width = pool_width, C.pool_height = pool_height, C.width = width, C.height = height;
+    return md_partition(true, true, ctx, C, pool, dst, stream);
 }
 
 }  // extern "C"

@@ -55,5 +55,24 @@ struct MdFullCall {   // the arguments of svthip_md_full_loop_batch_dev and svth
 bool md_full_size_ok(uint32_t bwidth, uint32_t bheight, bool wide);
 bool md_full_layout(uint32_t n_groups, uint32_t max_full, uint32_t bw, uint32_t bh, bool wide, uint32_t mask_inter, uint32_t mask_intra, MdFullLayout* L);
 hipError_t launch_md_full_loop(const MdFullCall& C, const MdFullLayout& L, hipStream_t s);
+// md_part.hip: mode decision's partition decision -- per superblock d1 and d2 over the block costs the full loop left, the final blocks in
+// coding order, and the picture composed of their winner tiles (kernels: md_part_kernels.h)
+struct MdPartCall {   // the arguments of svthip_md_partition_batch_dev, _compose_dev and _picture_dev; an entry fills what its launch reads
+    const svthip_md_partition_sb* sb;
+    const svthip_md_partition_leaf* leaf;
+    const svthip_md_full_decision* decision;
+    uint32_t n_sb, n_leaf, n_decision, sb_size;
+    int32_t slice_is_intra;
+    const int32_t* partition_fac_bits;   // host, [20 * 11]
+    svthip_md_partition_result* result;
+    svthip_md_partition_final* final_;
+    uint32_t* final_count;
+    svthip_inter_planes pool, dst;
+    uint32_t pool_width, pool_height, width, height;
+    uint32_t* refused;
+};
+uint32_t md_part_geometry(uint32_t sb_size, svthip_md_partition_block* out, uint32_t max);   // 0: not 64 or 128
+hipError_t launch_md_part_decide(const MdPartCall& C, hipStream_t s);
+hipError_t launch_md_part_compose(const MdPartCall& C, hipStream_t s);
 
 }  // namespace svthip

@@ -36,9 +36,12 @@ from ._md import (MD_FAST_CHROMA_QUARTER, MD_FAST_INVALID, MD_FAST_LUMA_GIVEN, M
                   md_model_rd_result_dtype)
 from ._md import (MD_FULL_CHROMA, MD_FULL_DECIDE, MD_FULL_LUMA, MD_FULL_MAX_SLOTS, MD_FULL_NONE, ModeDecisionFull, md_full_decision_dtype,
                   md_full_desc_dtype, md_full_result_dtype, md_full_workspace_bytes, md_full128_tu_dtype, md_full128_workspace_bytes)
+from ._md import (MD_PART_BLOCKS_64, MD_PART_BLOCKS_128, MD_PART_MAX_FINAL_64, MD_PART_MAX_FINAL_128, MD_PART_MDC_SPLIT_FLAG, MD_PART_NONE,
+                  MD_PART_SPLIT_FLAG, MD_PART_TESTED, ModeDecisionPartition, md_partition_block_dtype, md_partition_final_dtype, md_partition_geometry,
+                  md_partition_leaf_dtype, md_partition_result_dtype, md_partition_sb_dtype)
 from ._host import ME_CU_RESULT_REF_DTYPE, HostForms, HostPicture
 from ._ma import MA_PICTURE_PARAMS_DTYPE, MaPictureParams, MotionAnalysis, make_ma_params
 
 
-class Context(ContextCore, MotionEstimation, TransformQuant, PictureAnalysis, Prediction, Cfl, Deblocking, Cdef, Restoration, FilmGrain, ModeDecisionFast, InterpFilterSearch, ModeDecisionFull, HostForms, MotionAnalysis):
+class Context(ContextCore, MotionEstimation, TransformQuant, PictureAnalysis, Prediction, Cfl, Deblocking, Cdef, Restoration, FilmGrain, ModeDecisionFast, InterpFilterSearch, ModeDecisionFull, ModeDecisionPartition, HostForms, MotionAnalysis):
     """One svthip_ctx (stream + scratch), the analogue of one MeContext_t."""

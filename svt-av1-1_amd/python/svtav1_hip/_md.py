@@ -1,11 +1,13 @@
 """Mode decision's fast loop (svthip_md_fast_cost_batch_dev, svthip_md_fast_pick_batch_dev), its interpolation-filter search
 (svthip_md_model_rd_batch_dev, svthip_md_interp_filter_search_batch_dev) and its full loop (svthip_md_full_loop_batch_dev, and svthip_md_full_loop128_batch_dev
-for 128x128, 128x64 and 64x128): pointer marshalling only.
+for 128x128, 128x64 and 64x128), and its partition decision (svthip_md_partition_geometry, svthip_md_partition_batch_dev, _compose_dev, _picture_dev): pointer
+marshalling only.
 
 The four structs cross Python as numpy arrays in device memory; md_fast_desc_dtype() / md_fast_result_dtype() / md_fast_group_dtype() /
 md_fast_pick_dtype() give their layouts (svthip_md_fast_desc, _result, _group, _pick of include/svtav1_hip.h); md_model_rd_desc_dtype() /
 md_model_rd_result_dtype() / md_ifs_desc_dtype() / md_ifs_result_dtype() those of the search (svthip_md_model_rd_desc, _result,
-svthip_md_ifs_desc, _result); md_full_desc_dtype() / md_full_result_dtype() / md_full_decision_dtype() / md_full128_tu_dtype() those of the full loop."""
+svthip_md_ifs_desc, _result); md_full_desc_dtype() / md_full_result_dtype() / md_full_decision_dtype() / md_full128_tu_dtype() those of the full loop;
+md_partition_block_dtype() / _sb_dtype() / _leaf_dtype() / _result_dtype() / _final_dtype() those of the partition decision."""
 from __future__ import annotations
 
 import numpy as np
@@ -156,3 +158,74 @@ class ModeDecisionFull:
                                                       bwidth, bheight, d_qparams, d_iscan, None if offsets is None else offsets.ctypes.data, d_tables,
                                                       reduced_tx_set, max_full, _planes_arg(slot_recon), tiles_per_row, _planes_arg(recon), d_work, stages,
                                                       d_result, d_tu, d_decision, stream))
+
+
+MD_PART_NONE, MD_PART_SPLIT_FLAG, MD_PART_TESTED, MD_PART_MDC_SPLIT_FLAG, MD_PART_BLOCKS_64, MD_PART_BLOCKS_128, MD_PART_MAX_FINAL_64, MD_PART_MAX_FINAL_128 = (
+    _abi.define("SVTHIP_MD_PART_" + t) for t in ("NONE", "SPLIT_FLAG", "TESTED", "MDC_SPLIT_FLAG", "BLOCKS_64", "BLOCKS_128", "MAX_FINAL_64", "MAX_FINAL_128"))
+
+
+def md_partition_block_dtype() -> np.dtype:
+    """svthip_md_partition_block, 16 bytes: a block of the md scan"""
+    return _abi.dtype("svthip_md_partition_block")
+
+
+def md_partition_sb_dtype() -> np.dtype:
+    """svthip_md_partition_sb, 16 bytes"""
+    return _abi.dtype("svthip_md_partition_sb")
+
+
+def md_partition_leaf_dtype() -> np.dtype:
+    """svthip_md_partition_leaf, 16 bytes"""
+    return _abi.dtype("svthip_md_partition_leaf")
+
+
+def md_partition_result_dtype() -> np.dtype:
+    """svthip_md_partition_result, 16 bytes"""
+    return _abi.dtype("svthip_md_partition_result")
+
+
+def md_partition_final_dtype() -> np.dtype:
+    """svthip_md_partition_final, 16 bytes"""
+    return _abi.dtype("svthip_md_partition_final")
+
+
+def md_partition_geometry(sb_size) -> np.ndarray:
+    """the blocks of a 64x64 (1101) or 128x128 (4421) superblock in md-scan order, an array of md_partition_block_dtype(); host work, no context"""
+    n = int(lib().svthip_md_partition_geometry(sb_size, None, 0))
+    if not n:
+        raise ValueError(f"sb_size must be 64 or 128, not {sb_size}")
+    out = np.zeros(n, md_partition_block_dtype())
+    assert int(lib().svthip_md_partition_geometry(sb_size, out.ctypes.data, n)) == n
+    return out
+
+
+def _fac_bits(partition_fac_bits):
+    return None if partition_fac_bits is None else np.ascontiguousarray(np.asarray(partition_fac_bits, np.int32).reshape(20 * 11))
+
+
+class ModeDecisionPartition:
+    """the partition entries as Context methods; pool / dst are InterPlanes of 8-bit planes, the arrays device pointers"""
+
+    def md_partition_batch_dev(self, d_sb, n_sb, d_leaf, n_leaf, d_decision, n_decision, sb_size, slice_is_intra, partition_fac_bits, d_result, d_final,
+                               d_final_count, stream=None):
+        """d1 and d2 over the block costs of n_sb superblocks and their final blocks in coding order: d_sb an array of md_partition_sb_dtype(),
+        d_leaf one of md_partition_leaf_dtype(), d_decision the md_full_decision_dtype() rows the full-loop calls wrote, partition_fac_bits
+        [20][11] host integers, d_result n_sb * MD_PART_BLOCKS_* rows of md_partition_result_dtype(), d_final n_sb * MD_PART_MAX_FINAL_* of
+        md_partition_final_dtype(), d_final_count n_sb uint32; a bad leaf list and a final block without a leaf are counted (inter_pred_refused)"""
+        bits = _fac_bits(partition_fac_bits)
+        _check(lib().svthip_md_partition_batch_dev(self._h, d_sb, n_sb, d_leaf, n_leaf, d_decision, n_decision, sb_size, slice_is_intra,
+                                                   None if bits is None else bits.ctypes.data, d_result, d_final, d_final_count, stream))
+
+    def md_partition_compose_dev(self, n_sb, d_leaf, n_leaf, sb_size, d_final, d_final_count, pool, pool_width, pool_height, dst, width, height, stream=None):
+        """the winner tiles of the final blocks, from `pool` at their leaves' pool_x / pool_y to `dst` at their picture positions; a block
+        whose tile would pass a plane is skipped and counted (inter_pred_refused)"""
+        _check(lib().svthip_md_partition_compose_dev(self._h, n_sb, d_leaf, n_leaf, sb_size, d_final, d_final_count, _planes_arg(pool), pool_width,
+                                                     pool_height, _planes_arg(dst), width, height, stream))
+
+    def md_partition_picture_dev(self, d_sb, n_sb, d_leaf, n_leaf, d_decision, n_decision, sb_size, slice_is_intra, partition_fac_bits, d_result, d_final,
+                                 d_final_count, pool, pool_width, pool_height, dst, width, height, stream=None):
+        """md_partition_batch_dev, then md_partition_compose_dev, on one stream"""
+        bits = _fac_bits(partition_fac_bits)
+        _check(lib().svthip_md_partition_picture_dev(self._h, d_sb, n_sb, d_leaf, n_leaf, d_decision, n_decision, sb_size, slice_is_intra,
+                                                     None if bits is None else bits.ctypes.data, d_result, d_final, d_final_count, _planes_arg(pool),
+                                                     pool_width, pool_height, _planes_arg(dst), width, height, stream))
