@@ -10,22 +10,18 @@ then the search and the pick for grids with 128-wide blocks, on a grid of BLOCK_
     python tools/cdef_probe.py --resources FILE                  registers, LDS and scratch of the kernels from the code object's notes
 
 Device times are microseconds: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as
-tools/inter_pred_probe.py takes them.  The pictures are the synthetic ones of tests/golden/make_golden_cdef.py with 30 % of the cells skipped.
+tools/probe_common.py: timed takes them.  One JSON line per row, appended to --out.  The pictures are the synthetic ones of tests/golden/make_golden_cdef.py with 30 % of the cells skipped.
 --cpu times the reference's own cdef_seg_search, finish_cdef_search and av1_cdef_frame over the same pictures, one thread, through the
 fixture driver (tests/golden/ref_cdef_driver.c; leaf functions as the encoder dispatches them, AVX2, but the C mse_4x4_16bit): seconds per
 picture, best of two.
 For a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/cdef_probe.py --iters 2"""
 import argparse
-import json
-import os
-import subprocess
-import sys
+import functools
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, open_stream, resources, timed, write_rows  # sets the import path
 
 import make_golden_cdef as gen  # noqa: E402
 
@@ -48,30 +44,22 @@ def cpu_yardstick(lines):
             total, parts = min((R.time(QINDEX) for _ in range(2)), key=lambda t: t[0])
             R.close()
             for name, t in zip(("cdef_seg_search", "finish_cdef_search", "av1_cdef_frame"), parts):
-                lines.append({"entry": f"reference {name}, 1 thread", "bit_depth": bd, "us": round(float(t) * 1e6, 1)})
-                print(json.dumps(lines[-1]), flush=True)
-            lines.append({"entry": "reference search + finish + frame, 1 thread", "bit_depth": bd, "us": round(total * 1e6, 1)})
-            print(json.dumps(lines[-1]), flush=True)
+                emit(lines, {"entry": f"reference {name}, 1 thread", "bit_depth": bd, "us": round(float(t) * 1e6, 1)})
+            emit(lines, {"entry": "reference search + finish + frame, 1 thread", "bit_depth": bd, "us": round(total * 1e6, 1)})
 
 
 def device_times(lines, iters):
     import torch
 
     import svtav1_hip
-    from inter_pred_probe import timed
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    _, stream = open_stream(torch)
+    dev = functools.partial(as_dev, torch)
     nh, nv = svtav1_hip.cdef_filter_blocks(W, H)
     nfb = nh * nv
 
     def report(name, bd, fn, reps, **more):
-        row = {"entry": name, "bit_depth": bd, "us": round(timed(torch, fn, iters, reps), 1), **more}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, {"entry": name, "bit_depth": bd, "us": round(timed(torch, fn, iters, reps).median, 1), **more})
 
     for bd in (8, 10):
         dbk, src, skip = pictures(bd)
@@ -130,39 +118,18 @@ def device_times(lines, iters):
     ctx.close()
 
 
-def resources(path):
-    """the kernels' notes of the built library: the compiler's own resource remarks for csrc/cf_cdef.hip"""
-    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "cf_cdef.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                            os.path.join(tmp, "cf_cdef.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    keep = ("Function Name", "TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS Size")
-    with open(path, "w") as f:
-        for ln in r.stderr.split("\n"):
-            if "remark:" in ln and any(k in ln for k in keep):
-                t = ln.split("remark:", 1)[1].split("[-Rpass")[0].rstrip()
-                f.write(("Name:" + t.split("Function Name:")[1] if "Function Name" in t else "   " + t.strip()) + "\n")
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--cpu", action="store_true")
-    ap.add_argument("--resources", default=None)
+    add_common_args(ap, 5, cpu=True, resources=True)
     a = ap.parse_args()
     lines = []
     if a.resources:
-        return resources(a.resources)
+        return resources("cf_cdef.hip", a.resources)
     if a.cpu:
         cpu_yardstick(lines)
     else:
         device_times(lines, a.iters)
-    if a.out:
-        with open(a.out, "a") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines)
 
 
 if __name__ == "__main__":

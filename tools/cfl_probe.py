@@ -6,22 +6,17 @@ decision kernel over the pool's 538 560 (distortion, bits) pairs.
     python tools/cfl_probe.py [--iters N] [--out FILE] [--only predict8,predict10,candidates,decision]
 
 Times are device times in microseconds: the median over N samples, each the mean of 10 back-to-back calls queued behind a sleep kernel, as
-tools/inter_pred_probe.py takes them.  "bytes" is what the call must move (luma, DC prediction and descriptor in, prediction out; for the
+tools/probe_common.py: timed takes them.  One JSON line per row; --out is overwritten.  "bytes" is what the call must move (luma, DC prediction and descriptor in, prediction out; for the
 decision every pair and table it may read), "tb_s" that over the time, "hbm_share" that over the 8 TB/s peak DESIGN.md uses.
 For a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/cfl_probe.py --iters 3"""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, emit, open_stream, timed, write_rows  # sets the import path
 
 import cfl_util as cu  # noqa: E402
 import svtav1_hip  # noqa: E402
-from inter_pred_probe import timed  # noqa: E402
 
 W, H, LW, LH = 1920, 1088, 16, 16
 HBM_PEAK = 8e12
@@ -44,28 +39,23 @@ def picture_descs():
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, 20)
     ap.add_argument("--only", default="predict8,predict10,candidates,decision")
     a = ap.parse_args()
     only = set(a.only.split(","))
     rng = np.random.default_rng(1)
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     desc = picture_descs()
     n = len(desc)
     d_desc = cu.to_dev(desc)
     lines = []
 
     def report(name, fn, nbytes, **more):
-        t = timed(torch, fn, a.iters)
+        t = timed(torch, fn, a.iters).median
         row = {"kernel": name, "blocks": n, "us": round(t, 2), "bytes": int(nbytes), "tb_s": round(nbytes / t / 1e6, 3),
                "hbm_share": round(nbytes / (t * 1e-6) / HBM_PEAK, 4), **more}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, row)
 
     for bd in (8, 10):
         if f"predict{bd}" not in only and not (bd == 8 and "candidates" in only):
@@ -101,10 +91,7 @@ def main():
                n * (66 * (16 + 4) + 16 + 32) + ab.nbytes)
     ctx.inter_pred_refused()
     ctx.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in lines:
-                f.write(json.dumps(r) + "\n")
+    write_rows(a.out, lines, append=False)
 
 
 if __name__ == "__main__":

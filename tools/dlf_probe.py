@@ -5,7 +5,7 @@ filter of the three planes, one 64-level SSE table per plane, and the whole leve
     python tools/dlf_probe.py [--iters N] [--out FILE]
 
 Times are device times in microseconds: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as
-tools/inter_pred_probe.py takes them.  "bytes" is what the call must move (frame: every plane read and written once, and the grid; table:
+tools/probe_common.py: timed takes them.  One JSON line per row; --out is overwritten.  "bytes" is what the call must move (frame: every plane read and written once, and the grid; table:
 the plane and its source read once, and the grid; pick: five tables), "tb_s" that over the time, "hbm_share" that over the 8 TB/s peak
 DESIGN.md uses.  "ns_per_sample_level" of a table is its time over samples x 64 levels.  The frame filter works in place and a filtered
 picture takes other branches than an unfiltered one, so every timed call is preceded by a device copy that restores the planes; the
@@ -15,18 +15,14 @@ For a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/dlf_probe.p
 For the table kernel's vector instructions per sample and level: rocprofv3 --pmc SQ_INSTS_VALU -- python tools/dlf_probe.py --iters 1
 --only table, in a run of its own; the counter counts wave instructions, so x 64 lanes / (samples x 64 levels) = the counter / samples."""
 import argparse
-import json
-import os
-import sys
+import functools
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, open_stream, timed, write_rows  # sets the import path
 
 import dlf_util as du  # noqa: E402
 import svtav1_hip  # noqa: E402
-from inter_pred_probe import timed  # noqa: E402
 
 W, H = 1920, 1088
 HBM_PEAK = 8e12
@@ -35,32 +31,27 @@ HBM_PEAK = 8e12
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, 10)
     ap.add_argument("--only", default="frame,table,pick")
     a = ap.parse_args()
     only = set(a.only.split(","))
     rng = np.random.default_rng(1)
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     mi = du.random_mi_grid(rng, W, H, min_size=8)
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    dev = functools.partial(as_dev, torch)
     d_mi = dev(mi)
     d_levels = dev(np.array([24, 20, 16, 16], np.int32))
     d_sse = torch.zeros(5 * 64, dtype=torch.int64, device="cuda:0")
     lines = []
 
     def report(name, bd, fn, nbytes, reps, minus=0.0, **more):
-        t = timed(torch, fn, a.iters, reps) - minus
+        t = timed(torch, fn, a.iters, reps).median - minus
         if "samples" in more:
             more = {"ns_per_sample_level": round(t * 1e3 / (more["samples"] * 64), 5)}
         row = {"entry": name, "bit_depth": bd, "us": round(t, 1), "bytes": int(nbytes), "tb_s": round(nbytes / t / 1e6, 4),
                "hbm_share": round(nbytes / (t * 1e-6) / HBM_PEAK, 5), **more}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, row)
 
     for bd in (8, 10):
         es = 1 if bd == 8 else 2
@@ -79,7 +70,7 @@ def main():
             ctx.av1_loop_filter_frame_dev(pic, d_mi.data_ptr(), mi.shape[1], d_levels.data_ptr(), 0, 0, 3, bit_depth=bd, stream=stream)
 
         if "frame" in only:
-            t_restore = timed(torch, restore, a.iters, 10)
+            t_restore = timed(torch, restore, a.iters, 10).median
             report("loop_filter_frame (3 planes)", bd, frame, 2 * sum(samples) * es + mi.nbytes, 10, minus=t_restore, restore_us=round(t_restore, 1))
             restore()
         for plane in range(3):
@@ -96,10 +87,7 @@ def main():
                    2 * (3 * samples[0] + samples[1] + samples[2]) * es + 5 * mi.nbytes, 2)
     ctx.synchronize()
     ctx.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines, append=False)
 
 
 if __name__ == "__main__":

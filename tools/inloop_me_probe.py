@@ -10,19 +10,20 @@ recorded (tests/golden/inloop_me.npz, ref_seconds_1080p, ref_seconds_1080p_subpe
     python tools/inloop_me_probe.py --resources FILE                  registers, LDS and scratch of the kernels from the compiler's remarks
 
 Device times are microseconds per launch: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as
-tools/inter_pred_probe.py takes them; the entries are sampled in alternation (one sample of each per round), so drift hits all alike.
+tools/probe_common.py: timed takes them; the entries are sampled in alternation (one sample of each per round), so drift hits all alike.
 `of_packed_sad_ceiling`: abs-diffs per second over the measured packed-SAD issue ceiling of DESIGN section 6 (1.56e14 abs-diff/s).  One
-JSON line per row, appended to --out."""
+JSON line per row, printed and appended to --out (default profiles/inloop_me_probe.jsonl) once the run has finished.
+The resource report comes from the hipcc line of tools/probe_common.py: resources (gfx950, -O3, -fPIC, -std=c++17, the compiler's
+resource-usage remarks) on csrc/me_inloop.hip.  Its LDS size of 0 is right: the kernels' LDS is dynamic (inloop_lds_bytes), 24 300 bytes
+for a 64x64 area and 44 776 for 127x127."""
 import argparse
+import functools
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import ROOT, add_common_args, as_dev, open_stream, resources, timed, write_rows  # sets the import path
 
 PACKED_SAD_CEILING = 1.56e14   # abs-diff/s, DESIGN section 6
 W, H, AREA = 1920, 1080, 64
@@ -33,14 +34,10 @@ def device_times(iters, out):
 
     import me_inloop_util as iu
     import svtav1_hip
-    from inter_pred_probe import timed
     from svtav1_hip import synth
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    _, stream = open_stream(torch)
+    dev = functools.partial(as_dev, torch)
     cur, ref = synth.PaPicture(synth.synth_luma(W, H, 1)), synth.PaPicture(synth.synth_luma(W, H, 0))
     sbs = iu.sb_origins(W, H)
     n = len(sbs)
@@ -84,7 +81,7 @@ def device_times(iters, out):
     samples = {name: [] for name, _ in entries}
     for _ in range(iters):            # alternating: one sample of every entry per round
         for name, fn in entries:
-            samples[name].append(timed(torch, fn, 1, 4))
+            samples[name].append(timed(torch, fn, 1, 4).median)
     # correctness of what was timed: the one-call entry ran last on d_sad / d_mv / d_out
     torch.cuda.synchronize()
     desc = d_desc.cpu().numpy().reshape(n, 8)
@@ -122,36 +119,18 @@ def device_times(iters, out):
     sub_s = float(fx["ref_seconds_1080p_subpel"])
     lines.append({"entry": "reference in_loop_motion_estimation_sblock, one host thread, use_subpel_flag = 1 (from the fixture generator)", "kind": "host clock",
                   "width": W, "height": H, "superblocks": n, "area": [AREA, AREA], "us": round(sub_s * 1e6, 0)})
-    with open(out, "a") as f:
-        for row in lines:
-            print(json.dumps(row), flush=True)
-            f.write(json.dumps(row) + "\n")
+    for row in lines:
+        print(json.dumps(row), flush=True)
+    write_rows(out, lines)
     ctx.close()
-
-
-def resources(path):
-    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "me_inloop.hip")
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    keep = []
-    for ln in r.stderr.splitlines():
-        if "remark:" in ln:
-            keep.append(ln.split("remark:", 1)[1].replace("[-Rpass-analysis=kernel-resource-usage]", "").rstrip())
-    with open(path, "w") as f:
-        f.write("hipcc --offload-arch=gfx950 -O3 -std=c++17 -Rpass-analysis=kernel-resource-usage svt-av1-1_amd/csrc/me_inloop.hip\n"
-                "LDS is dynamic (inloop_lds_bytes): 24 300 bytes for a 64x64 area, 44 776 for 127x127.\n" + "\n".join(keep) + "\n")
-    print(open(path).read())
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=9)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "inloop_me_probe.jsonl"))
-    ap.add_argument("--resources", default=None)
+    add_common_args(ap, 9, out_default=os.path.join(ROOT, "profiles", "inloop_me_probe.jsonl"), resources=True)
     a = ap.parse_args()
     if a.resources:
-        resources(a.resources)
+        resources("me_inloop.hip", a.resources, spill=True)
     else:
         device_times(a.iters, a.out)
 

@@ -7,17 +7,13 @@ per plane and direction group, what a caller of those entries launches); only th
     python tools/inter_pred_probe.py [--iters N] [--out FILE]
 
 Times are device times in microseconds: the median over N samples, each the mean of 10 back-to-back calls queued behind a sleep kernel
-(without it the events measure the host's launch rate: about 35 us for the eleven launches of a call from Python, whatever the size).
+(tools/probe_common.py: timed).  One JSON line per row; --out is overwritten.
 --sizes limits the run (e.g. for a kernel-trace pass: rocprofv3 --kernel-trace --stats -- python tools/inter_pred_probe.py --sizes 4x4,8x8)."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, open_stream, timed, write_rows  # sets the import path
 
 import inter_pred_util as ipu  # noqa: E402
 import svtav1_hip  # noqa: E402
@@ -78,42 +74,17 @@ def per_plane_jobs(desc, bw, bh, ys, cs):
     return out
 
 
-def timed(torch, fn, iters, reps=10):
-    """device time of one fn() in microseconds: the stream is held by a sleep kernel while reps calls are queued behind it, so the
-    events bracket the device's back-to-back execution and not the host's launch rate (which is slower than small calls)"""
-    s = torch.cuda.current_stream()
-    for _ in range(3):
-        fn()
-    ts = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda._sleep(20_000_000)
-        a.record(s)
-        for _ in range(reps):
-            fn()
-        b.record(s)
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1000.0 / reps)
-    return float(np.median(ts))
-
-
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, 20)
     ap.add_argument("--per-plane-max-pus", type=int, default=40000, help="skip the per-plane comparison above this many PUs (host build time)")
     ap.add_argument("--sizes", default="", help="comma-separated WxH list (default: all 22)")
     ap.add_argument("--bit-depths", default="8,10")
     a = ap.parse_args()
     rng = np.random.default_rng(1)
     ctx = svtav1_hip.Context(0)
-    # a stream of our own: the default stream's handle is NULL, which the library reads as "the context's stream" -- the events would then
-    # bracket nothing
-    torch_stream = torch.cuda.Stream()
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     lines = []
     only = {tuple(int(v) for v in t.split("x")) for t in a.sizes.split(",") if t}
     for bd in [int(v) for v in a.bit_depths.split(",")]:
@@ -127,18 +98,18 @@ def main():
             if only and (bw, bh) not in only:
                 continue
             desc = descs_1080p(rng, bw, bh, mode)
-            d_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+            d_desc = as_dev(torch, desc)
             n = len(desc)
             if bd == 8:
                 call = lambda: ctx.av1_inter_pred_batch_dev(P0, P1, PP, d_desc.data_ptr(), n, bw, bh, stream=stream)  # noqa: E731
             else:
                 call = lambda: ctx.av1_highbd_inter_pred_batch_dev(P0, P1, PP, d_desc.data_ptr(), n, bw, bh, 10, stream=stream)  # noqa: E731
-            t_pu = timed(torch, call, a.iters)
+            t_pu = timed(torch, call, a.iters).median
             ctx.inter_pred_refused()
             row = {"bd": bd, "size": f"{bw}x{bh}", "mode": mode, "n_pu": n, "whole_pu_us": round(t_pu, 2)}
             if min(bw, bh) >= 8 and mode == "mixed" and n <= a.per_plane_max_pus:
                 jobs = per_plane_jobs(desc, bw, bh, refs[0].y.shape[1], refs[0].cb.shape[1])
-                dj = {k: torch.from_numpy(v.view(np.uint8).reshape(-1).copy()).to("cuda:0") for k, v in jobs.items()}
+                dj = {k: as_dev(torch, v) for k, v in jobs.items()}
                 bwu, bhu = max(4, bw >> 1), max(4, bh >> 1)
                 lib = svtav1_hip.lib()
 
@@ -160,15 +131,11 @@ def main():
                                                                               int(direction == 2), cnt, w, h, 10, stream)
                             assert rc == 0, lib.svthip_last_error().decode()
 
-                t_pp = timed(torch, planes_call, a.iters)
+                t_pp = timed(torch, planes_call, a.iters).median
                 row.update(per_plane_us=round(t_pp, 2), ratio=round(t_pu / t_pp, 3), per_plane_launches=sum(1 if k[0] == "y" else 2 for k in jobs))
-            lines.append(row)
-            print(json.dumps(row), flush=True)
+            emit(lines, row)
     ctx.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in lines:
-                f.write(json.dumps(r) + "\n")
+    write_rows(a.out, lines, append=False)
 
 
 if __name__ == "__main__":

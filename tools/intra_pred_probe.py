@@ -8,19 +8,15 @@ mode mixes "dc" / "all13" / "directional", 8 and 10 bits, with and without d_sad
 
     python tools/intra_pred_probe.py [--iters N] [--out FILE]
 
-Times are device times in microseconds, measured as tools/inter_pred_probe.py measures them.  For a kernel-trace pass:
-rocprofv3 --kernel-trace --stats -- python tools/intra_pred_probe.py --iters 2."""
+Times are device times in microseconds, the median tools/probe_common.py: timed gives.  One JSON line per row; --out is overwritten.
+For a kernel-trace pass: rocprofv3 --kernel-trace --stats -- python tools/intra_pred_probe.py --iters 2."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, open_stream, timed, write_rows  # sets the import path
 
-import inter_pred_probe as ipp  # noqa: E402
+import inter_pred_probe as ipp  # noqa: E402  (the picture's size and the translational descriptors of the copy yardstick)
 import inter_pred_util as ipu  # noqa: E402
 import intra_pred_util as iu  # noqa: E402
 import svtav1_hip  # noqa: E402
@@ -50,15 +46,11 @@ def intra_descs_1080p(rng, n_side, stride, origin, mix):
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, 20)
     a = ap.parse_args()
     rng = np.random.default_rng(1)
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     lines = []
     for bd in (8, 10):
         ref = ipu.random_picture(rng, W, H, BORDER, bd, "smooth")
@@ -75,16 +67,16 @@ def main():
             if n_side >= 8:
                 td = ipp.descs_1080p(rng, n_side, n_side, "uni")
                 td["mv"], td["interp_filters"], td["pred_direction"], td["own_list"], td["has_uv"] = 0, 0, 0, 0, 0
-                d_td = torch.from_numpy(td.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+                d_td = as_dev(torch, td)
                 if bd == 8:
                     trans = lambda: ctx.av1_inter_pred_batch_dev(P0, P0, PP, d_td.data_ptr(), len(td), n_side, n_side, stream=stream)  # noqa: E731
                 else:
                     trans = lambda: ctx.av1_highbd_inter_pred_batch_dev(P0, P0, PP, d_td.data_ptr(), len(td), n_side, n_side, 10, stream=stream)  # noqa: E731
-                copy_us = ipp.timed(torch, trans, a.iters)
+                copy_us = timed(torch, trans, a.iters).median
             for mix in MIXES:
                 desc = intra_descs_1080p(rng, n_side, S, BORDER, mix)
                 n = len(desc)
-                d_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+                d_desc = as_dev(torch, desc)
                 d_sad = torch.zeros(n, dtype=torch.int32, device="cuda:0")
                 for with_sad in ((False, True) if bd == 8 else (False,)):
                     if bd == 8:
@@ -94,21 +86,17 @@ def main():
                     else:
                         fn = lambda: ctx.av1_highbd_intra_pred_batch_dev(d_edge.data_ptr(), d_dst.data_ptr(), d_desc.data_ptr(), n, tx_size, 10,  # noqa: E731
                                                                          stream)
-                    t = ipp.timed(torch, fn, a.iters)
+                    t = timed(torch, fn, a.iters).median
                     nbytes = n * (SB * (4 * n_side + 1 + n_side * n_side * (2 if with_sad else 1)) + 32 + (4 if with_sad else 0))
                     floor_us = nbytes / HBM_BYTES_PER_S * 1e6
                     row = {"bd": bd, "size": f"{n_side}x{n_side}", "mix": mix, "sad": with_sad, "n_blocks": n, "intra_us": round(t, 2),
                            "bytes": nbytes, "hbm_floor_us": round(floor_us, 2), "ratio_vs_hbm_floor": round(t / floor_us, 2),
                            "copy_us": None if copy_us is None else round(copy_us, 2),
                            "ratio_vs_copy": None if copy_us is None else round(t / copy_us, 3)}
-                    lines.append(row)
-                    print(json.dumps(row), flush=True)
+                    emit(lines, row)
         assert ctx.inter_pred_refused() == 0
     ctx.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in lines:
-                f.write(json.dumps(r) + "\n")
+    write_rows(a.out, lines, append=False)
 
 
 if __name__ == "__main__":

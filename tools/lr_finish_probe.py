@@ -7,7 +7,7 @@ four parts, at 1920 x 1080 (32 units a plane) and 3840 x 2160 (120 a plane), 8 b
 
 Per size, the alternatives taken in turn within each sample:
   decision kernel, device        microseconds of svthip_rest_finish_search_dev, the median over N samples, each the mean of back-to-back calls
-                                 queued behind a sleep kernel, as tools/inter_pred_probe.py takes them
+                                 queued behind a sleep kernel, as tools/probe_common.py: timed takes them
   decision, idle stream, host clock      enqueue on an idle stream and wait for it: what a caller that does wait would see
   round trip, host clock         what a host decision needs around it: hipMemcpyAsync of the four tables to pinned host memory, a stream
                                  synchronise, the upload of the unit types enqueued (and, second figure, completed).  No host computation
@@ -17,18 +17,17 @@ The tables the decision reads are the searches' own results on the synthetic pic
 ordinary ones (lr_finish_util.ORDINARY with rdmult 60000).
 --cpu times the reference's rest_finish_search on tables of the same unit counts, one thread, through the fixture driver
 (tests/golden/ref_lr_finish_driver.c): microseconds per picture, the mean of 1000 calls, best of three.
+One JSON line per row; --out is overwritten, its folder made if it is not there.
 For a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/lr_finish_probe.py --iters 2"""
 import argparse
-import json
+import functools
 import os
-import sys
 import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python"), ROOT]
+from probe_common import add_common_args, as_dev, emit, open_stream, timed, write_rows  # sets the import path
 
 import lr_finish_util as fu  # noqa: E402
 
@@ -52,8 +51,7 @@ def cpu_yardstick(lines):
             ra, ub = fu.rates_array(RATES), np.array(base, np.int32)
             t = min(L.drv_finish_time(ra.ctypes.data, ub.ctypes.data, *[a.ctypes.data for a in tables], 1000) for _ in range(3)) / 1000
             L.drv_lr_close()
-            lines.append({"entry": "reference rest_finish_search, 3 planes, 1 thread", "size": f"{w}x{h}", "units": base[3], "us": round(t * 1e6, 2)})
-            print(json.dumps(lines[-1]), flush=True)
+            emit(lines, {"entry": "reference rest_finish_search, 3 planes, 1 thread", "size": f"{w}x{h}", "units": base[3], "us": round(t * 1e6, 2)})
 
 
 def device_times(lines, iters):
@@ -61,18 +59,12 @@ def device_times(lines, iters):
 
     import make_golden_lr as gen
     import svtav1_hip
-    from inter_pred_probe import timed
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    torch_stream, stream = open_stream(torch)
+    dev = functools.partial(as_dev, torch)
 
     def report(name, size, us, **more):
-        row = {"entry": name, "size": size, "us": round(us, 1), **more}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, {"entry": name, "size": size, "us": round(us, 1), **more})
 
     for (w, h) in SIZES:
         size, bd = f"{w}x{h}", 8
@@ -132,7 +124,7 @@ def device_times(lines, iters):
             torch_stream.synchronize()
             h_type.copy_(d_type)              # the unit types the upload then carries, outside the timing
             samples["trip"].append(round_trip())
-        report("decision kernel, device", size, timed(torch, decide, iters, 20), units=n)
+        report("decision kernel, device", size, timed(torch, decide, iters, 20).median, units=n)
         frame_types = d_res.cpu().numpy().view(svtav1_hip.rest_finish_result_dtype())["frame_type"].tolist()
         lines[-1]["frame_types"] = frame_types
         report("decision, idle stream, enqueue to completion, host clock", size, float(np.median([s[0] for s in samples["idle"]])))
@@ -140,10 +132,10 @@ def device_times(lines, iters):
                upload_completed_us=round(float(np.median([s[1] for s in samples["trip"]])), 1))
         parts = {}
         for name, fn, reps in (("search_wiener (bound of trials)", wiener, 1), ("search_sgrproj", sgr, 1), ("decision", decide, 20), ("lr_filter_frame", filt, 5)):
-            parts[name] = timed(torch, fn, iters, reps)
+            parts[name] = timed(torch, fn, iters, reps).median
             report("part: " + name, size, parts[name])
         report("sum of the four parts", size, sum(parts.values()))
-        report("one-call entry", size, timed(torch, one, iters, 1))
+        report("one-call entry", size, timed(torch, one, iters, 1).median)
         torch_stream.synchronize()
         same = all(torch.equal(a, b) for a, b in ((d_taps, d_taps1), (d_sgr, d_sgr1), (d_type, d_type1), (d_res, d_res1)))
         lines[-1]["same_outputs_as_parts"] = bool(same)
@@ -157,9 +149,7 @@ def device_times(lines, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--cpu", action="store_true")
+    add_common_args(ap, 5, cpu=True)
     a = ap.parse_args()
     lines = []
     if a.cpu:
@@ -168,9 +158,7 @@ def main():
         device_times(lines, a.iters)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+        write_rows(a.out, lines, append=False)
 
 
 if __name__ == "__main__":

@@ -7,20 +7,18 @@ unit RESTORE_SGRPROJ.
     python tools/lr_sgr_probe.py --cpu [--out FILE]                the CPU yardstick (build container only, where the reference exists)
 
 Device times are microseconds: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as
-tools/inter_pred_probe.py takes them.  The pictures are the synthetic ones of tests/golden/make_golden_lr.py.
+tools/probe_common.py: timed takes them.  One JSON line per row; --out is overwritten.  The pictures are the synthetic ones of tests/golden/make_golden_lr.py.
 --cpu times the reference's own search_sgrproj_seg over the same pictures, one thread, through the fixture driver
 (tests/golden/ref_lr_sgr_driver.c; leaf functions as the encoder dispatches them, AVX2): seconds per picture, best of two.
 For a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/lr_sgr_probe.py --iters 2"""
 import argparse
+import functools
 import json
-import os
-import sys
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, open_stream, timed, write_rows  # sets the import path
 
 import make_golden_lr as gen  # noqa: E402
 
@@ -37,28 +35,21 @@ def cpu_yardstick(lines):
             R = gen.Reference(L, W, H, bd, cdef, dbk, src)
             t = min(L.drv_sgr_time() for _ in range(2))
             R.close()
-            lines.append({"entry": "reference search_sgrproj_seg, 3 planes, 1 thread", "bit_depth": bd, "us": round(t * 1e6, 1)})
-            print(json.dumps(lines[-1]), flush=True)
+            emit(lines, {"entry": "reference search_sgrproj_seg, 3 planes, 1 thread", "bit_depth": bd, "us": round(t * 1e6, 1)})
 
 
 def device_times(lines, iters):
     import torch
 
     import svtav1_hip
-    from inter_pred_probe import timed
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
-    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    _, stream = open_stream(torch)
+    dev = functools.partial(as_dev, torch)
     base, _ = svtav1_hip.lr_unit_geometry(W, H)
     n = base[3]
 
     def report(name, bd, fn, reps, **more):
-        row = {"entry": name, "bit_depth": bd, "us": round(timed(torch, fn, iters, reps), 1), **more}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, {"entry": name, "bit_depth": bd, "us": round(timed(torch, fn, iters, reps).median, 1), **more})
 
     for bd in (8, 10):
         planes = gen.make_pictures(np.random.default_rng(bd), W, H, bd)
@@ -91,19 +82,14 @@ def device_times(lines, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--cpu", action="store_true")
+    add_common_args(ap, 5, cpu=True)
     a = ap.parse_args()
     lines = []
     if a.cpu:
         cpu_yardstick(lines)
     else:
         device_times(lines, a.iters)
-    if a.out:
-        with open(a.out, "w") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines, append=False)
 
 
 if __name__ == "__main__":

@@ -8,22 +8,19 @@ pictures per launch, and next to them in the same run their yardsticks:
     python tools/ma_stats_probe.py --cpu [--out FILE]                the CPU yardstick (build container only, where the reference exists)
 
 Device times are microseconds per LAUNCH: the median over N samples, each the mean of ten back-to-back calls queued behind a sleep kernel, as
-tools/inter_pred_probe.py takes them; min and max of the N samples are the run-to-run spread.  Bytes are what the algorithm reads and writes,
+tools/probe_common.py: timed takes them; min and max of the N samples are the run-to-run spread.  Bytes are what the algorithm reads and writes,
 computed from the shapes.  The download is timed by the host clock around synchronous copies.  --cpu times the reference's own functions on one
 picture, one thread, through the fixture driver (tests/golden/ref_ma_stats_driver.c, ASM_AVX2): microseconds per picture, best of five runs of 20
 calls; the table group is MeBasedGlobalMotionDetection, DeriveSimilarCollocatedFlag, FailingMotionLcu and DetectUncoveredLcu (the histogram loop
 is inline in the reference's thread body and not part of it).  One JSON line per row, appended to --out."""
 import argparse
+import functools
 import json
-import os
-import sys
 import tempfile
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, host_timed, open_stream, timed, write_rows  # sets the import path
 
 W, H = 1920, 1080
 COUNTS = (1, 12)
@@ -75,8 +72,7 @@ def cpu_yardstick(lines):
         for which, name, call in calls:
             assert call() == 0
             t = min(L.drv_ma_time(which, 20) for _ in range(5)) / 20
-            lines.append({"entry": f"reference {name}, 1 picture, 1 thread", "kind": "cpu, build container, host clock", "us": round(t * 1e6, 1)})
-            print(json.dumps(lines[-1]), flush=True)
+            emit(lines, {"entry": f"reference {name}, 1 picture, 1 thread", "kind": "cpu, build container, host clock", "us": round(t * 1e6, 1)})
         L.drv_ma_close()
 
 
@@ -88,17 +84,14 @@ def device_times(lines, iters):
     from svtav1_hip import synth
 
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    torch_stream, stream = open_stream(torch)
     n_max, n_sb, complete = max(COUNTS), mu.n_sbs(W, H), int(mu.complete_sbs(W, H).sum())
     lumas = [picture(s) for s in range(n_max + 1)]
     pool, descs = svtav1_hip.build_picture_pool([synth.PaPicture(p) for p in lumas])
     d_pool = torch.from_numpy(pool).to("cuda:0")
     rng = np.random.default_rng(3)
     me, cand = zip(*[tables(rng, n_sb) for _ in range(n_max)])
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    dev = functools.partial(as_dev, torch)
     d_me, d_cand = dev(np.stack(me)), dev(np.stack(cand))
     z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda:0")  # noqa: E731
     d_y, d_v = dev(rng.integers(0, 256, (n_max + 1, n_sb, 85)).astype(np.uint8)), dev(rng.integers(0, 16000, (n_max + 1, n_sb, 85)).astype(np.uint16))
@@ -108,28 +101,12 @@ def device_times(lines, iters):
     d_hist, d_full, d_gm, d_flags = z((n_max, 2, 128), torch.int32), z((n_max,), torch.int32), z((n_max, 12), torch.int32), z((n_max, n_sb, 4), torch.uint8)
     torch.cuda.synchronize()
 
-    def timed(fn, reps=10):
-        for _ in range(3):
-            fn()
-        ts = []
-        for _ in range(iters):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda._sleep(20_000_000)
-            a.record(torch_stream)
-            for _ in range(reps):
-                fn()
-            b.record(torch_stream)
-            b.synchronize()
-            ts.append(a.elapsed_time(b) * 1000.0 / reps)
-        return float(np.median(ts)), float(min(ts)), float(max(ts))
-
     def report(name, fn, n, nbytes=None, **more):
-        us, lo, hi = timed(fn)
+        us, lo, hi = timed(torch, fn, iters)
         row = {"entry": name, "kind": "device events", "pictures": n, "us": round(us, 2), "us_min": round(lo, 2), "us_max": round(hi, 2), **more}
         if nbytes:
             row.update(bytes=nbytes, GB_per_s=round(nbytes / us / 1e3, 1))
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, row)
         return us
 
     for n in COUNTS:
@@ -154,19 +131,10 @@ def device_times(lines, iters):
         # what a host-side tail costs today: the ME and OIS tables to pageable host memory, and the synchronise
         nbytes = n * n_sb * 85 * (24 + 18 * 4)
         d_tab, h_tab = torch.zeros(nbytes, dtype=torch.uint8, device="cuda:0"), torch.zeros(nbytes, dtype=torch.uint8)
-        ts = []
-        for _ in range(3 + iters):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            h_tab.copy_(d_tab)
-            torch_stream.synchronize()
-            ts.append(time.perf_counter() - t0)
-        us = float(np.median(ts[3:])) * 1e6
-        row = {"entry": "yardstick: download of the ME and OIS tables to pageable host memory and a stream synchronise", "kind": "host clock around synchronous copies",
-               "pictures": n, "us": round(us, 1), "us_min": round(min(ts[3:]) * 1e6, 1), "us_max": round(max(ts[3:]) * 1e6, 1), "bytes": nbytes,
-               "three_table_entries_us": round(t_tab, 2), "download_over_table_entries": round(us / t_tab, 1)}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        us, lo, hi = host_timed(lambda: (h_tab.copy_(d_tab), torch_stream.synchronize()), iters, torch.cuda.synchronize)
+        emit(lines, {"entry": "yardstick: download of the ME and OIS tables to pageable host memory and a stream synchronise", "kind": "host clock around synchronous copies",
+                     "pictures": n, "us": round(us, 1), "us_min": round(lo, 1), "us_max": round(hi, 1), "bytes": nbytes,
+                     "three_table_entries_us": round(t_tab, 2), "download_over_table_entries": round(us / t_tab, 1)})
     # correctness of what was timed last, on the first and last picture
     torch.cuda.synchronize()
     sad = d_sad.cpu().numpy().view(np.uint32)
@@ -178,19 +146,14 @@ def device_times(lines, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=9)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--cpu", action="store_true")
+    add_common_args(ap, 9, cpu=True)
     a = ap.parse_args()
     lines = []
     if a.cpu:
         cpu_yardstick(lines)
     else:
         device_times(lines, a.iters)
-    if a.out:
-        with open(a.out, "a") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines)
 
 
 if __name__ == "__main__":

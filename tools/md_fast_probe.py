@@ -10,21 +10,14 @@ tiles and the source picture once).
     python tools/md_fast_probe.py --resources FILE              registers, LDS and scratch of the kernels from the compiler's remarks
 
 The prediction pool holds candidate c of the block at (x, y) at (x, c * 1080 + y): six pictures stacked.  Device times are microseconds
-per call: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as tools/inter_pred_probe.py takes
+per call: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as tools/probe_common.py: timed takes
 them; GB/s is the bytes the launch must read over that time.  What was timed is compared with numpy before it is reported.  One JSON line
 per row, appended to --out.  For a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/md_fast_probe.py --iters 2"""
 import argparse
-import json
-import os
-import subprocess
-import sys
-import tempfile
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, host_timed, open_stream, resources, timed, write_rows  # sets the import path
 
 W, H, CANDIDATES = 1920, 1080, 6
 SIZES = (8, 32, 64)
@@ -43,12 +36,8 @@ def device_times(lines, iters):
 
     import md_fast_util as mu
     import svtav1_hip
-    from inter_pred_probe import timed
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     rng = np.random.default_rng(5)
     yy, xx = np.mgrid[0:H, 0:W]
     luma = ((np.sin(xx / 17.0) + np.cos(yy / 11.0)) * 60 + 128 + rng.integers(-6, 7, (H, W))).clip(0, 255).astype(np.uint8)
@@ -68,22 +57,13 @@ def device_times(lines, iters):
         row = {"entry": name, "kind": kind, "width": W, "height": H, "block": size if isinstance(size, str) else f"{size}x{size}", "candidates": n, "us": round(us, 1), "bytes": nbytes, **more}
         if nbytes:
             row["GB_per_s"] = round(nbytes / us / 1e3, 1)
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, row)
 
     # the yardsticks do not depend on the block size
     d_copy = [torch.empty_like(t) for t in d_pool + d_src]
-    t_copy = timed(torch, lambda: [d.copy_(s) for d, s in zip(d_copy, d_pool + d_src)], iters, 10)
+    t_copy = timed(torch, lambda: [d.copy_(s) for d, s in zip(d_copy, d_pool + d_src)], iters, 10).median
     host = [torch.empty(t.shape, dtype=torch.uint8) for t in d_pool]
-    ts = []
-    for _ in range(3 + iters):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for hst, t in zip(host, d_pool):
-            hst.copy_(t)
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    t_down = float(np.median(ts[3:])) * 1e6
+    t_down = host_timed(lambda: ([hst.copy_(t) for hst, t in zip(host, d_pool)], torch.cuda.synchronize()), iters, torch.cuda.synchronize).median
 
     for size in SIZES:
         nx, ny = W // size, H // size
@@ -99,15 +79,14 @@ def device_times(lines, iters):
         desc = desc.reshape(-1)
         groups = np.zeros(n_blocks, mu.GROUP_DTYPE)
         groups["first"], groups["count"], groups["buffer_total_count"], groups["buffer_width"] = np.arange(n_blocks) * CANDIDATES, CANDIDATES, 3, 13
-        as_dev = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
-        d_desc, d_groups = as_dev(desc), as_dev(groups)
+        d_desc, d_groups = as_dev(torch, desc), as_dev(torch, groups)
         d_result = torch.zeros(n * 16, dtype=torch.uint8, device="cuda:0")
         d_pick = torch.zeros(n_blocks * 32, dtype=torch.uint8, device="cuda:0")
         cost = lambda: ctx.md_fast_cost_batch_dev(planes[0], planes[1], d_desc.data_ptr(), n, size, size, d_result.data_ptr(), stream=stream)  # noqa: E731
         pick = lambda: ctx.md_fast_pick_batch_dev(d_result.data_ptr(), d_desc.data_ptr(), n, d_groups.data_ptr(), n_blocks, d_pick.data_ptr(),  # noqa: E731
                                                   stream=stream)
-        t_cost = timed(torch, cost, iters, 10)
-        t_pick = timed(torch, pick, iters, 10)
+        t_cost = timed(torch, cost, iters, 10).median
+        t_pick = timed(torch, pick, iters, 10).median
         # correctness of what was timed
         torch.cuda.synchronize()
         got = d_result.cpu().numpy().view(mu.RESULT_DTYPE)
@@ -130,35 +109,15 @@ def device_times(lines, iters):
     ctx.close()
 
 
-def resources(path):
-    """the compiler's own resource remarks for csrc/md_fast.hip"""
-    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "md_fast.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                            os.path.join(tmp, "md_fast.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    keep = ("Function Name", "TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS Size", "Spill")
-    with open(path, "w") as f:
-        for ln in r.stderr.split("\n"):
-            if "remark:" in ln and any(k in ln for k in keep):
-                t = ln.split("remark:", 1)[1].split("[-Rpass")[0].rstrip()
-                f.write(("Name:" + t.split("Function Name:")[1] if "Function Name" in t else "   " + t.strip()) + "\n")
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--resources", default=None)
+    add_common_args(ap, 7, resources=True)
     a = ap.parse_args()
     if a.resources:
-        return resources(a.resources)
+        return resources("md_fast.hip", a.resources, spill=True)
     lines = []
     device_times(lines, a.iters)
-    if a.out:
-        with open(a.out, "a") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines)
 
 
 if __name__ == "__main__":

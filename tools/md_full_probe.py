@@ -15,20 +15,14 @@ blocks of the 64x64 row, so that the 64x64 row is its yardstick.  Next to it in 
 
 The prediction pool holds candidate c of the block at (x, y) at (x, c * 1080 + y): four pictures stacked; the slot pool has the same
 shape.  Device times are microseconds per call: the median over N samples, each the mean of back-to-back calls queued behind a sleep
-kernel, as tools/inter_pred_probe.py takes them.  What was timed is compared with the restatement (tests/md_full_util.py) on a sample of
+kernel, as tools/probe_common.py: timed takes them.  What was timed is compared with the restatement (tests/md_full_util.py) on a sample of
 the blocks before it is reported.  One JSON line per row, appended to --out.  No threshold is set here."""
 import argparse
-import json
-import os
-import subprocess
-import sys
-import tempfile
-import time
+import functools
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python"), ROOT]
+from probe_common import add_common_args, as_dev, emit, host_timed, open_stream, resources, timed, write_rows  # sets the import path
 
 import svtav1_hip  # noqa: E402
 
@@ -97,16 +91,12 @@ def device_times(lines, iters, sizes=SIZES, tag=None):
 
     import md_fast_util as mu
     import md_full_util as fu
-    from inter_pred_probe import timed
     from oracle.binding import Oracle
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     sh = fu.shared()
-    as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
-    d_qp, d_iscan, d_tables = as_dev(sh["qparams"]), as_dev(sh["tabs"].iscan_pool), as_dev(sh["tables"])
+    upload = functools.partial(as_dev, torch)
+    d_qp, d_iscan, d_tables = upload(sh["qparams"]), upload(sh["tabs"].iscan_pool), upload(sh["tables"])
     tiles_per_row = {size: W // size for size in SIZES}
     wide = None
     if 128 in sizes:
@@ -117,8 +107,7 @@ def device_times(lines, iters, sizes=SIZES, tag=None):
                "us": round(us, 1), **more}
         if tag:
             row["tag"] = tag
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, row)
 
     for size in sizes:
         for search in ("none", "m1"):
@@ -140,7 +129,7 @@ def device_times(lines, iters, sizes=SIZES, tag=None):
                 a.y, a.cb, a.cr = (t.data_ptr() for t in ts_)
                 a.y_stride, a.c_stride = W, W // 2
                 planes[k] = a
-            d_fast, d_full, d_group, d_pick = as_dev(s.fast), as_dev(s.full), as_dev(s.groups), as_dev(s.picks)
+            d_fast, d_full, d_group, d_pick = upload(s.fast), upload(s.full), upload(s.groups), upload(s.picks)
             is_wide = size > TU_MAX
             work = svtav1_hip.md_full128_workspace_bytes(s.n_groups, SLOTS, size, size) if is_wide else \
                 svtav1_hip.md_full_workspace_bytes(s.n_groups, SLOTS, size, size, s.mask_inter, s.mask_intra)
@@ -162,8 +151,8 @@ def device_times(lines, iters, sizes=SIZES, tag=None):
                                            s.mask_intra, SLOTS, planes["slot"], tiles_per_row[size], planes["recon"], d_work.data_ptr(), stages,
                                            d_result.data_ptr(), d_decision.data_ptr(), stream=stream)
 
-            t_call = timed(torch, call, iters, 4)
-            t_stage = {name: timed(torch, lambda st=st: call(st), iters, 4) for name, st in (("luma", fu.LUMA), ("chroma", fu.CHROMA), ("decide", fu.DECIDE))}
+            t_call = timed(torch, call, iters, 4).median
+            t_stage = {name: timed(torch, lambda st=st: call(st), iters, 4).median for name, st in (("luma", fu.LUMA), ("chroma", fu.CHROMA), ("decide", fu.DECIDE))}
             # correctness of what was timed: a sample of the blocks against the restatement
             torch.cuda.synchronize()
             got_r, got_d = d_result.cpu().numpy().view(fu.RESULT_DTYPE), d_decision.cpu().numpy().view(fu.DECISION_DTYPE)
@@ -213,7 +202,7 @@ def device_times(lines, iters, sizes=SIZES, tag=None):
                 tu["src_stride"] = tu["pred_stride"] = stride
                 rd = np.zeros(n_tu, svtav1_hip.COEFF_RATE_DESC_DTYPE)
                 rd["coeff_offset"], rd["iscan_offset"], rd["tx_type"], rd["plane_type"], rd["is_inter"] = tu["coeff_offset"], tu["iscan_offset"], tx, c, 1
-                d_tu, d_rd = as_dev(tu), as_dev(rd)
+                d_tu, d_rd = upload(tu), upload(rd)
                 d_q = torch.zeros(n_tu * ncoef, dtype=torch.int32, device="cuda:0")
                 d_eob = torch.zeros(n_tu, dtype=torch.int16, device="cuda:0")
                 d_energy, d_dist = torch.zeros(n_tu, dtype=torch.int64, device="cuda:0"), torch.zeros(n_tu * 2, dtype=torch.int64, device="cuda:0")
@@ -247,20 +236,12 @@ def device_times(lines, iters, sizes=SIZES, tag=None):
                 add_launch(0, size, n, s.full["tx_type_y"][k // SLOTS * SLOTS + s.picks["best"][k // SLOTS, k % SLOTS]], d["slot"][0], slot_off[0], W, True, ts_y)
             for p in (1, 2) if not is_wide else ():
                 add_launch(p, cw, n, np.zeros(n, np.int64), d["slot"][p], slot_off[1], W // 2, True, ts_uv)
-            t_leaves = timed(torch, lambda: [go() for go, _ in launches], iters, 4)
+            t_leaves = timed(torch, lambda: [go() for go, _ in launches], iters, 4).median
 
             # what a host-side full loop downloads today: the picks and the per-slot eobs, sums, energies and bits
             per_slot = [torch.zeros(n * b, dtype=torch.uint8, device="cuda:0") for b in (3 * 2, 3 * 16, 8, 3 * 4)] + [d_pick]
             host = [torch.empty(t.shape, dtype=torch.uint8) for t in per_slot]
-            ts = []
-            for _ in range(3 + iters):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for hst, t in zip(host, per_slot):
-                    hst.copy_(t)
-                torch.cuda.synchronize()
-                ts.append(time.perf_counter() - t0)
-            t_down = float(np.median(ts[3:])) * 1e6
+            t_down = host_timed(lambda: ([hst.copy_(t) for hst, t in zip(host, per_slot)], torch.cuda.synchronize()), iters, torch.cuda.synchronize).median
             tus = n * n_tu * 3 if is_wide else n * (len(types) + 1 if types else 1) + 2 * n
             report("md_full_loop128 (LUMA | CHROMA | DECIDE)" if is_wide else "md_full_loop (LUMA | CHROMA | DECIDE)", t_call, size, search, s.n_groups, tx_types=len(types) or 1, transform_units=tus, workspace_bytes=work,
                    call_over_leaves=round(t_call / t_leaves, 2), added_us=round(t_call - t_leaves, 1))
@@ -276,39 +257,18 @@ def device_times(lines, iters, sizes=SIZES, tag=None):
     ctx.close()
 
 
-def resources(path):
-    """the compiler's own resource remarks for csrc/md_full.hip"""
-    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "md_full.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                            os.path.join(tmp, "md_full.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    keep = ("Function Name", "TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS Size", "Spill")
-    with open(path, "w") as f:
-        for ln in r.stderr.split("\n"):
-            if "remark:" in ln and any(k in ln for k in keep):
-                t = ln.split("remark:", 1)[1].split("[-Rpass")[0].rstrip()
-                f.write(("Name:" + t.split("Function Name:")[1] if "Function Name" in t else "   " + t.strip()) + "\n")
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--resources", default=None)
+    add_common_args(ap, 7, resources=True, tag=True)
     ap.add_argument("--sizes", default=",".join(str(v) for v in SIZES), help="luma sizes to time, of " + ", ".join(str(v) for v in SIZES))
-    ap.add_argument("--tag", default=None, help="a word kept in every row, e.g. which build was timed")
     a = ap.parse_args()
     if a.resources:
-        return resources(a.resources)
+        return resources("md_full.hip", a.resources, spill=True)
     lines = []
     sizes = tuple(int(v) for v in a.sizes.split(","))
     assert set(sizes) <= set(SIZES), sizes
     device_times(lines, a.iters, sizes, a.tag)
-    if a.out:
-        with open(a.out, "a") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines)
 
 
 if __name__ == "__main__":

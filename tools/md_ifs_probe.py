@@ -15,21 +15,16 @@ bi-predicted mixed -- at three luma sizes, 8x8, 32x32 and 64x64, in the fast mod
     python tools/md_ifs_probe.py --resources FILE                registers, LDS and scratch of the kernels from the compiler's remarks
 
 Device times are microseconds per call: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as
-tools/inter_pred_probe.py takes them.  What was timed is compared with the restatement on a sample of candidates before it is reported.
+tools/probe_common.py: timed takes them.  What was timed is compared with the restatement on a sample of candidates before it is reported.
 One JSON line per row, appended to --out."""
 import argparse
-import json
-import os
-import subprocess
-import sys
+import functools
 import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), ROOT,
-                os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, host_timed, open_stream, resources, timed, write_rows  # sets the import path
 
 W, H, BORDER = 1920, 1080, 80
 SIZES = (8, 32, 64)
@@ -87,31 +82,25 @@ def device_times(lines, iters):
     import inter_pred_util as ipu
     import md_ifs_util as mu
     import svtav1_hip
-    from inter_pred_probe import timed
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     ref0, ref1, src = pictures()
     pics = (ref0, ref1, ipu.Picture(*src, 0))
     dev = [ipu.to_device(p) for p in pics]
     P = [ipu.planes_of(d, p) for d, p in zip(dev, pics)]
-    as_dev = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    upload = functools.partial(as_dev, torch)
 
     def report(name, us, size, n, kind="device events", **more):
-        row = {"entry": name, "kind": kind, "width": W, "height": H, "block": f"{size}x{size}", "candidates": n, "us": round(us, 1), **more}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, {"entry": name, "kind": kind, "width": W, "height": H, "block": f"{size}x{size}", "candidates": n, "us": round(us, 1), **more})
 
     for size in SIZES:
         pu, f = candidates(size)
         n = len(pu)
-        d_pu, d_f = as_dev(pu), as_dev(f)
+        d_pu, d_f = upload(pu), upload(f)
         d_result = torch.zeros(n * 32, dtype=torch.uint8, device="cuda:0")
         search = lambda: ctx.md_interp_filter_search_batch_dev(P[0], P[1], P[2], d_pu.data_ptr(), d_f.data_ptr(), n, size, size, 1, 1, QUANTIZER, 0,  # noqa: E731
                                                                d_result.data_ptr(), stream=stream)
-        t_search = timed(torch, search, iters, 5)
+        t_search = timed(torch, search, iters, 5).median
         torch.cuda.synchronize()
         got = d_result.cpu().numpy().view(mu.IFS_RESULT_DTYPE)
         some = np.arange(0, n, max(1, n // 40))
@@ -132,12 +121,12 @@ def device_times(lines, iters):
         tiles = ipu.Picture(np.zeros((rows * size, k * size), np.uint8), *(np.zeros((rows * size // 2, k * size // 2), np.uint8) for _ in range(2)), 0)
         d_tiles = ipu.to_device(tiles)
         p_tiles = ipu.planes_of(d_tiles, tiles)
-        d_tpu, d_m = as_dev(t_pu), as_dev(m)
+        d_tpu, d_m = upload(t_pu), upload(m)
         d_mres = torch.zeros(n_tiles * 32, dtype=torch.uint8, device="cuda:0")
         predict = lambda: ctx.av1_inter_pred_batch_dev(P[0], P[1], p_tiles, d_tpu.data_ptr(), n_tiles, size, size, stream=stream)  # noqa: E731
         measure = lambda: ctx.md_model_rd_batch_dev(P[2], p_tiles, d_m.data_ptr(), n_tiles, size, size, QUANTIZER, d_mres.data_ptr(), stream=stream)  # noqa: E731
-        t_predict = timed(torch, predict, iters, 5)
-        t_measure = timed(torch, measure, iters, 10)
+        t_predict = timed(torch, predict, iters, 5).median
+        t_measure = timed(torch, measure, iters, 10).median
         torch.cuda.synchronize()
         got_m = d_mres.cpu().numpy().view(mu.MODEL_RESULT_DTYPE)
         for j, c in zip(range(len(some)), some):
@@ -146,18 +135,11 @@ def device_times(lines, iters):
         # yardsticks: a copy of what the measurement reads; the download of five tiles a candidate
         sources = [d_tiles["y"], d_tiles["cb"], d_tiles["cr"], dev[2]["y"], dev[2]["cb"], dev[2]["cr"]]
         copies = [torch.empty_like(s) for s in sources]
-        t_copy = timed(torch, lambda: [d.copy_(s) for d, s in zip(copies, sources)], iters, 10)
+        t_copy = timed(torch, lambda: [d.copy_(s) for d, s in zip(copies, sources)], iters, 10).median
         read = sum(s.numel() for s in sources) + m.nbytes
         five = torch.zeros(n * REFERENCE_PREDICTIONS * size * size * 3 // 2, dtype=torch.uint8, device="cuda:0")
         host = torch.empty(five.shape, dtype=torch.uint8)
-        ts = []
-        for _ in range(3 + iters):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            host.copy_(five)
-            torch.cuda.synchronize()
-            ts.append(time.perf_counter() - t0)
-        t_down = float(np.median(ts[3:])) * 1e6
+        t_down = host_timed(lambda: (host.copy_(five), torch.cuda.synchronize()), iters, torch.cuda.synchronize).median
         report("(i) interpolation-filter search, fast mode, whole call", t_search, size, n, trials_per_candidate=3, search_minus_prediction_over_prediction=round((t_search - t_predict) / t_predict, 2),
                download_over_search=round(t_down / t_search, 1))
         report("(ii) inter prediction alone on the same trial descriptors", t_predict, size, n, pus=n_tiles)
@@ -190,43 +172,22 @@ def reference_times(lines, sample=60, repeat=200):
             row = {"entry": "(v) reference interpolation_filter_search, fast mode, one host thread (C kernels), scaled to the picture",
                    "kind": "host clock, build machine", "width": W, "height": H, "block": f"{size}x{size}", "candidates": n, "us": round(one * n * 1e6, 1),
                    "us_per_candidate": round(one * 1e6, 2), "sampled": int(len(some))}
-            lines.append(row)
-            print(json.dumps(row), flush=True)
-
-
-def resources(path):
-    """the compiler's own resource remarks for csrc/md_ifs.hip"""
-    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "md_ifs.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                            os.path.join(tmp, "md_ifs.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    keep = ("Function Name", "TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS Size", "Spill")
-    with open(path, "w") as f:
-        for ln in r.stderr.split("\n"):
-            if "remark:" in ln and any(k in ln for k in keep):
-                t = ln.split("remark:", 1)[1].split("[-Rpass")[0].rstrip()
-                f.write(("Name:" + t.split("Function Name:")[1] if "Function Name" in t else "   " + t.strip()) + "\n")
+            emit(lines, row)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=7)
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, 7, resources=True)
     ap.add_argument("--reference", action="store_true")
-    ap.add_argument("--resources", default=None)
     a = ap.parse_args()
     if a.resources:
-        return resources(a.resources)
+        return resources("md_ifs.hip", a.resources, spill=True)
     lines = []
     if a.reference:
         reference_times(lines)
     else:
         device_times(lines, a.iters)
-    if a.out:
-        with open(a.out, "a") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines)
 
 
 if __name__ == "__main__":

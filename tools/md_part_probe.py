@@ -12,21 +12,15 @@ all-blocks list (forward_all_blocks_to_md) and the squares-only list (forward_sq
 
 The tile pool holds the winner tile of a block at its picture position in the layer of its shape (nine pictures stacked), so blocks of
 different depths share tiles: the composition reads the same bytes a real pool would give it.  Device times are microseconds per call: the
-median, minimum and maximum over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as tools/inter_pred_probe.py
+median, minimum and maximum over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as tools/probe_common.py: timed
 takes them.  What was timed is compared with the restatement (tests/md_part_util.py) on a sample of the superblocks before it is
 reported.  One JSON line per row, appended to --out.  No threshold is set here."""
 import argparse
-import json
-import os
-import subprocess
-import sys
-import tempfile
-import time
+import functools
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python"), ROOT]
+from probe_common import add_common_args, as_dev, emit, host_timed, open_stream, resources, timed, write_rows  # sets the import path
 
 import svtav1_hip  # noqa: E402
 
@@ -63,57 +57,35 @@ def build(sb_size, kind, rng, pu):
     return origins, lists, sbs, leaves, decisions
 
 
-def timed(torch, fn, iters, reps=10):
-    """(median, min, max) device microseconds of one fn(); see tools/inter_pred_probe.py: timed"""
-    s = torch.cuda.current_stream()
-    for _ in range(3):
-        fn()
-    ts = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda._sleep(20_000_000)
-        a.record(s)
-        for _ in range(reps):
-            fn()
-        b.record(s)
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1000.0 / reps)
-    return float(np.median(ts)), float(min(ts)), float(max(ts))
-
-
 def device_times(lines, iters, tag=None):
     import torch
 
     import md_part_util as pu
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
-    as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda:0")  # noqa: E731
+    torch_stream, stream = open_stream(torch)
+    upload = functools.partial(as_dev, torch)
     rng = np.random.default_rng(3)
     fac = rng.integers(150, 3000, (20, 11)).astype(np.int32)
     pool_h = 9 * LAYER_H
     pool = [rng.integers(0, 256, (pool_h, W), np.uint8), *(rng.integers(0, 256, (pool_h // 2, W // 2), np.uint8) for _ in range(2))]
-    d_pool, d_dst = [as_dev(p) for p in pool], [torch.zeros(n, dtype=torch.uint8, device="cuda:0") for n in (W * H, W * H // 4, W * H // 4)]
+    d_pool, d_dst = [upload(p) for p in pool], [torch.zeros(n, dtype=torch.uint8, device="cuda:0") for n in (W * H, W * H // 4, W * H // 4)]
     d_copy = [torch.zeros_like(t) for t in d_dst]
     planes = lambda ts, ys, cs: svtav1_hip.InterPlanes(ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ys, cs)  # noqa: E731
     pool_arg, dst_arg = planes(d_pool, W, W // 2), planes(d_dst, W, W // 2)
 
     def report(name, t, sb_size, kind, n_sb, n_leaf, how="device events", **more):
         row = {"entry": name, "kind": how, "width": W, "height": H, "sb_size": sb_size, "list": kind, "superblocks": n_sb, "leaves": n_leaf,
-               "us": round(t[0], 1), "us_min": round(t[1], 1), "us_max": round(t[2], 1), **more}
+               "us": round(t.median, 1), "us_min": round(t.min, 1), "us_max": round(t.max, 1), **more}
         if tag:
             row["tag"] = tag
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        emit(lines, row)
 
     for sb_size in (64, 128):
         n, max_final = len(pu.geometry(sb_size)), 1024 if sb_size == 128 else 256
         for kind in ("all", "sq"):
             origins, lists, sbs, leaves, decisions = build(sb_size, kind, rng, pu)
             n_sb, n_leaf = len(sbs), len(leaves)
-            d_sb, d_leaf, d_dec = as_dev(sbs), as_dev(leaves), as_dev(decisions)
+            d_sb, d_leaf, d_dec = upload(sbs), upload(leaves), upload(decisions)
             d_result = torch.zeros(n_sb * n * 16, dtype=torch.uint8, device="cuda:0")
             d_final = torch.zeros(n_sb * max_final * 16, dtype=torch.uint8, device="cuda:0")
             d_count = torch.zeros(n_sb * 4, dtype=torch.uint8, device="cuda:0")
@@ -150,60 +122,36 @@ def device_times(lines, iters, tag=None):
             # the round trip the decision kernel replaces: host clock, pinned memory, no host computation
             h_dec = torch.empty(d_dec.numel(), dtype=torch.uint8).pin_memory()
             h_up = [torch.zeros(t.numel(), dtype=torch.uint8).pin_memory() for t in (d_result, d_final, d_count)]
-            ts = []
-            for _ in range(3 + iters):
-                torch_stream.synchronize()
-                t0 = time.perf_counter()
+
+            def round_trip():
                 h_dec.copy_(d_dec, non_blocking=True)
                 torch_stream.synchronize()
                 for t, hst in zip((d_result, d_final, d_count), h_up):
                     t.copy_(hst, non_blocking=True)
                 torch_stream.synchronize()
-                ts.append((time.perf_counter() - t0) * 1e6)
-            ts = ts[3:]
-            t_trip = (float(np.median(ts)), float(min(ts)), float(max(ts)))
-            report("md_partition_batch_dev", t_decide, sb_size, kind, n_sb, n_leaf, final_blocks=blocks, over_round_trip=round(t_decide[0] / t_trip[0], 2))
+
+            t_trip = host_timed(round_trip, iters, torch_stream.synchronize)
+            report("md_partition_batch_dev", t_decide, sb_size, kind, n_sb, n_leaf, final_blocks=blocks, over_round_trip=round(t_decide.median / t_trip.median, 2))
             report("yardstick: decisions to pinned host memory, synchronise, records and final lists uploaded, synchronise; no host computation", t_trip,
                    sb_size, kind, n_sb, n_leaf, how="host clock", bytes_down=int(d_dec.numel()), bytes_up=int(sum(t.numel() for t in h_up)))
-            report("md_partition_compose_dev", t_compose, sb_size, kind, n_sb, n_leaf, final_blocks=blocks, over_plane_copy=round(t_compose[0] / t_copy[0], 2))
+            report("md_partition_compose_dev", t_compose, sb_size, kind, n_sb, n_leaf, final_blocks=blocks, over_plane_copy=round(t_compose.median / t_copy.median, 2))
             report("yardstick: device-to-device copy of the three planes", t_copy, sb_size, kind, n_sb, n_leaf, bytes=W * H * 3 // 2)
             report("md_partition_picture_dev", t_picture, sb_size, kind, n_sb, n_leaf, final_blocks=blocks,
-                   over_its_parts=round(t_picture[0] / (t_decide[0] + t_compose[0]), 2))
+                   over_its_parts=round(t_picture.median / (t_decide.median + t_compose.median), 2))
             del d_sb, d_leaf, d_dec, d_result, d_final, d_count
     ctx.synchronize()
     ctx.close()
 
 
-def resources(path):
-    """the compiler's own resource remarks for csrc/md_part.hip"""
-    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "md_part.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                            os.path.join(tmp, "md_part.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    keep = ("Function Name", "TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS Size", "Spill")
-    with open(path, "w") as f:
-        for ln in r.stderr.split("\n"):
-            if "remark:" in ln and any(k in ln for k in keep):
-                t = ln.split("remark:", 1)[1].split("[-Rpass")[0].rstrip()
-                f.write(("Name:" + t.split("Function Name:")[1] if "Function Name" in t else "   " + t.strip()) + "\n")
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--resources", default=None)
-    ap.add_argument("--tag", default=None, help="a word kept in every row, e.g. which build was timed")
+    add_common_args(ap, 7, resources=True, tag=True)
     a = ap.parse_args()
     if a.resources:
-        return resources(a.resources)
+        return resources("md_part.hip", a.resources, spill=True)
     lines = []
     device_times(lines, a.iters, a.tag)
-    if a.out:
-        with open(a.out, "a") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -11,20 +11,13 @@ the reconstructed 16-bit planes a host-side PSNR would have to fetch (pageable h
     python tools/pa_bitdepth_probe.py --resources FILE                  registers, LDS and scratch of the kernels from the compiler's remarks
 
 Device times are microseconds per LAUNCH: the median over N samples, each the mean of back-to-back calls queued behind a sleep kernel, as
-tools/inter_pred_probe.py takes them.  Planes are tight (stride = width), so every row starts 16-byte aligned; bytes are what the algorithm
+tools/probe_common.py: timed takes them.  Planes are tight (stride = width), so every row starts 16-byte aligned; bytes are what the algorithm
 reads and writes, computed from the shapes, and GB/s is bytes over the time.  One JSON line per row, appended to --out."""
 import argparse
-import json
-import os
-import subprocess
-import sys
-import tempfile
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, emit, host_timed, open_stream, resources, timed, write_rows  # sets the import path
 
 SHAPES = ((1920, 1080, 12), (3840, 2160, 1))   # width, height, pictures per launch
 
@@ -34,26 +27,13 @@ def device_times(lines, iters):
 
     import bitdepth_util as bu
     import svtav1_hip
-    from inter_pred_probe import timed
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
 
     def host_copy(name, dst, src, n, nbytes, **more):
-        ts = []
-        for _ in range(3 + iters):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            dst.copy_(src)
-            torch.cuda.synchronize()
-            ts.append(time.perf_counter() - t0)
-        us = float(np.median(ts[3:])) * 1e6
-        row = {"entry": name, "kind": "host clock around synchronous copies", "width": w, "height": h, "pictures": n, "us": round(us, 1), "bytes": nbytes,
-               "GB_per_s": round(nbytes / us / 1e3, 1), **more}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        us = host_timed(lambda: (dst.copy_(src), torch.cuda.synchronize()), iters, torch.cuda.synchronize).median
+        emit(lines, {"entry": name, "kind": "host clock around synchronous copies", "width": w, "height": h, "pictures": n, "us": round(us, 1), "bytes": nbytes,
+                     "GB_per_s": round(nbytes / us / 1e3, 1), **more})
 
     for w, h, n in SHAPES:
         rng = np.random.default_rng(w)
@@ -108,18 +88,18 @@ def device_times(lines, iters):
         copies = {}
         for name, per_pic, fn in entries:
             nbytes = n * per_pic
-            us = timed(torch, fn, iters, 10)
+            us = timed(torch, fn, iters, 10).median
             if nbytes not in copies:
                 src = torch.zeros(nbytes, dtype=torch.uint8, device="cuda:0")
                 dst = torch.zeros_like(src)
-                copies[nbytes] = (timed(torch, lambda: dst.copy_(src), iters, 10), timed(torch, lambda: dst[:nbytes // 2].copy_(src[:nbytes // 2]), iters, 10))
+                copies[nbytes] = (timed(torch, lambda: dst.copy_(src), iters, 10).median,
+                                  timed(torch, lambda: dst[:nbytes // 2].copy_(src[:nbytes // 2]), iters, 10).median)
                 del src, dst
             copy_us, half_us = copies[nbytes]
             row = {"entry": name, "kind": "device events", "width": w, "height": h, "pictures": n, "us": round(us, 1), "bytes": nbytes,
                    "GB_per_s": round(nbytes / us / 1e3, 1), "copy_of_as_many_bytes_us": round(copy_us, 1), "ratio_to_that_copy": round(us / copy_us, 2),
                    "copy_of_the_same_traffic_us": round(half_us, 1), "ratio_to_the_same_traffic": round(us / half_us, 2)}
-            lines.append(row)
-            print(json.dumps(row), flush=True)
+            emit(lines, row)
         # correctness of what was timed, on the first and the last picture
         torch.cuda.synchronize()
         out8, outn = d_out8.cpu().numpy(), d_outn.cpu().numpy()
@@ -153,35 +133,15 @@ def device_times(lines, iters):
     ctx.close()
 
 
-def resources(path):
-    """the compiler's own resource remarks for csrc/pa_bitdepth.hip"""
-    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "pa_bitdepth.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                            os.path.join(tmp, "pa_bitdepth.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    keep = ("Function Name", "TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS Size")
-    with open(path, "w") as f:
-        for ln in r.stderr.split("\n"):
-            if "remark:" in ln and any(k in ln for k in keep):
-                t = ln.split("remark:", 1)[1].split("[-Rpass")[0].rstrip()
-                f.write(("Name:" + t.split("Function Name:")[1] if "Function Name" in t else "   " + t.strip()) + "\n")
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--resources", default=None)
+    add_common_args(ap, 7, resources=True)
     a = ap.parse_args()
     lines = []
     if a.resources:
-        return resources(a.resources)
+        return resources("pa_bitdepth.hip", a.resources)
     device_times(lines, a.iters)
-    if a.out:
-        with open(a.out, "a") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -11,22 +11,16 @@ the download of the planes that a host-side detection would cost (profiles/pa_st
     python tools/pa_noise_probe.py --resources FILE                  registers, LDS and scratch of the kernels from the compiler's remarks
 
 Device times are microseconds per LAUNCH of 12 pictures: the median over N samples, each the mean of back-to-back calls queued behind a sleep
-kernel, as tools/inter_pred_probe.py takes them; bytes are what the algorithm reads and writes, computed from the shapes below, and GB/s is
+kernel, as tools/probe_common.py: timed takes them; bytes are what the algorithm reads and writes, computed from the shapes below, and GB/s is
 bytes over that time.  --cpu times the reference's own FullSampleDenoise with denoiseFlag 0 on one picture, one thread, through the fixture
 driver (tests/golden/ref_pa_noise_driver.c, ASM_AVX2): microseconds per picture, best of five runs of 10 calls.  One JSON line per row,
 appended to --out.  For a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/pa_noise_probe.py --iters 2"""
 import argparse
-import json
-import os
-import subprocess
-import sys
 import tempfile
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, emit, host_timed, open_stream, resources, timed, write_rows  # sets the import path
 
 W, H, N_PICS = 1920, 1080, 12
 
@@ -54,9 +48,8 @@ def cpu_yardstick(lines):
         assert L.drv_pa_noise_open(W, H, *[p.ctypes.data for p in keep]) == 510
         for sub in (1, 0):
             t = min(L.drv_pa_noise_time(sub, 10) for _ in range(5)) / 10
-            lines.append({"entry": "reference FullSampleDenoise (denoiseFlag 0), 1 picture, 1 thread", "kind": "cpu, build container, host clock",
-                          "sub_precision": sub, "us": round(t * 1e6, 1)})
-            print(json.dumps(lines[-1]), flush=True)
+            emit(lines, {"entry": "reference FullSampleDenoise (denoiseFlag 0), 1 picture, 1 thread", "kind": "cpu, build container, host clock",
+                         "sub_precision": sub, "us": round(t * 1e6, 1)})
         L.drv_pa_noise_close()
 
 
@@ -66,13 +59,9 @@ def device_times(lines, iters):
     import pa_noise_util as nu
     import pa_stats_util as pu
     import svtav1_hip
-    from inter_pred_probe import timed
     from svtav1_hip import synth
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # the default stream's handle is NULL, which the library reads as "the context's stream"
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     planes = [picture(s) for s in range(N_PICS)]
     luma_pool, descs = svtav1_hip.build_picture_pool([synth.PaPicture(p[0]) for p in planes])
     cstride, cbytes = W // 2, (W // 2) * (H // 2)
@@ -86,10 +75,8 @@ def device_times(lines, iters):
     torch.cuda.synchronize()
 
     def report(name, fn, reps, nbytes, **more):
-        us = timed(torch, fn, iters, reps)
-        row = {"entry": name, "kind": "device events", "pictures": N_PICS, "us": round(us, 1), "bytes": nbytes, "GB_per_s": round(nbytes / us / 1e3, 1), **more}
-        lines.append(row)
-        print(json.dumps(row), flush=True)
+        us = timed(torch, fn, iters, reps).median
+        emit(lines, {"entry": name, "kind": "device events", "pictures": N_PICS, "us": round(us, 1), "bytes": nbytes, "GB_per_s": round(nbytes / us / 1e3, 1), **more})
         return us
 
     detect_us = {}
@@ -119,56 +106,26 @@ def device_times(lines, iters):
     # the download a host-side detector would cost (profiles/pa_stats_probe.jsonl has it for the same planes): pageable host memory, host clock
     dev = torch.zeros(N_PICS * B["planes"], dtype=torch.uint8, device="cuda:0")
     host = torch.zeros(N_PICS * B["planes"], dtype=torch.uint8)
-    ts = []
-    for _ in range(3 + iters):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        host.copy_(dev)
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    us = float(np.median(ts[3:])) * 1e6
-    row = {"entry": f"yardstick: download of the planes of {N_PICS} picture(s) to pageable host memory", "kind": "host clock around synchronous copies",
-           "pictures": N_PICS, "us": round(us, 1), "bytes": N_PICS * B["planes"], "GB_per_s": round(N_PICS * B["planes"] / us / 1e3, 1),
-           "detection_only_sub_us": round(detect_us[(1, False)], 1), "cheaper_than_the_download": detect_us[(1, False)] < us}
-    lines.append(row)
-    print(json.dumps(row), flush=True)
+    us = host_timed(lambda: (host.copy_(dev), torch.cuda.synchronize()), iters, torch.cuda.synchronize).median
+    emit(lines, {"entry": f"yardstick: download of the planes of {N_PICS} picture(s) to pageable host memory", "kind": "host clock around synchronous copies",
+                 "pictures": N_PICS, "us": round(us, 1), "bytes": N_PICS * B["planes"], "GB_per_s": round(N_PICS * B["planes"] / us / 1e3, 1),
+                 "detection_only_sub_us": round(detect_us[(1, False)], 1), "cheaper_than_the_download": detect_us[(1, False)] < us})
     ctx.synchronize()
     ctx.close()
 
 
-def resources(path):
-    """the compiler's own resource remarks for csrc/pa_noise.hip"""
-    src = os.path.join(ROOT, "svt-av1-1_amd", "csrc", "pa_noise.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                            os.path.join(tmp, "pa_noise.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    keep = ("Function Name", "TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS Size")
-    with open(path, "w") as f:
-        for ln in r.stderr.split("\n"):
-            if "remark:" in ln and any(k in ln for k in keep):
-                t = ln.split("remark:", 1)[1].split("[-Rpass")[0].rstrip()
-                f.write(("Name:" + t.split("Function Name:")[1] if "Function Name" in t else "   " + t.strip()) + "\n")
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--cpu", action="store_true")
-    ap.add_argument("--resources", default=None)
+    add_common_args(ap, 7, cpu=True, resources=True)
     a = ap.parse_args()
     lines = []
     if a.resources:
-        return resources(a.resources)
+        return resources("pa_noise.hip", a.resources)
     if a.cpu:
         cpu_yardstick(lines)
     else:
         device_times(lines, a.iters)
-    if a.out:
-        with open(a.out, "a") as f:
-            for row in lines:
-                f.write(json.dumps(row) + "\n")
+    write_rows(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -6,19 +6,16 @@ path (OPT_CONVOLVE_VALU).
 
     python tools/warp_probe.py [--iters N] [--out FILE] [--sizes 16x16,...]
 
-Times are device times in microseconds, measured as tools/inter_pred_probe.py measures them (median over N samples, each the mean of 10
-back-to-back calls queued behind a sleep kernel).  For a kernel-trace pass: rocprofv3 --kernel-trace --stats -- python tools/warp_probe.py."""
+Times are device times in microseconds, measured by tools/probe_common.py: timed (median over N samples, each the mean of 10 back-to-back
+calls queued behind a sleep kernel).  One JSON line per row; --out is overwritten.  For a kernel-trace pass:
+rocprofv3 --kernel-trace --stats -- python tools/warp_probe.py."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "svt-av1-1_amd", "python")]
+from probe_common import add_common_args, as_dev, emit, open_stream, timed, write_rows  # sets the import path
 
-import inter_pred_probe as ipp  # noqa: E402
+import inter_pred_probe as ipp  # noqa: E402  (the picture's size and the translational descriptors of the yardstick)
 import inter_pred_util as ipu  # noqa: E402
 import svtav1_hip  # noqa: E402
 import warp_util as wu  # noqa: E402
@@ -54,17 +51,13 @@ def warp_descs_1080p(rng, bw, bh):
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, 20)
     ap.add_argument("--sizes", default="8x8,16x16,32x32,64x64")
     ap.add_argument("--bit-depths", default="8,10")
     a = ap.parse_args()
     rng = np.random.default_rng(1)
     ctx = svtav1_hip.Context(0)
-    torch_stream = torch.cuda.Stream()   # a stream of our own: a NULL handle would mean the context's stream (see inter_pred_probe)
-    torch.cuda.set_stream(torch_stream)
-    stream = torch_stream.cuda_stream
-    assert stream
+    _, stream = open_stream(torch)
     lines = []
     for bd in [int(v) for v in a.bit_depths.split(",")]:
         ref = ipu.random_picture(rng, W, H, BORDER, bd, "smooth")
@@ -76,31 +69,26 @@ def main():
             wd = warp_descs_1080p(rng, bw, bh)
             td = ipp.descs_1080p(rng, bw, bh, "uni")   # pred_direction 0 / 1: one reference per PU, as the warp reads
             n = len(wd)
-            d_wd = torch.from_numpy(wd.view(np.uint8).reshape(-1).copy()).to("cuda:0")
-            d_td = torch.from_numpy(td.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+            d_wd, d_td = as_dev(torch, wd), as_dev(torch, td)
             if bd == 8:
                 warp = lambda: ctx.av1_warped_pred_batch_dev(P0, PP, W, H, d_wd.data_ptr(), n, bw, bh, stream=stream)  # noqa: E731
                 trans = lambda: ctx.av1_inter_pred_batch_dev(P0, P0, PP, d_td.data_ptr(), n, bw, bh, stream=stream)  # noqa: E731
             else:
                 warp = lambda: ctx.av1_highbd_warped_pred_batch_dev(P0, PP, W, H, d_wd.data_ptr(), n, bw, bh, 10, stream=stream)  # noqa: E731
                 trans = lambda: ctx.av1_highbd_inter_pred_batch_dev(P0, P0, PP, d_td.data_ptr(), n, bw, bh, 10, stream=stream)  # noqa: E731
-            t_warp = ipp.timed(torch, warp, a.iters)
-            t_def = ipp.timed(torch, trans, a.iters)
+            t_warp = timed(torch, warp, a.iters).median
+            t_def = timed(torch, trans, a.iters).median
             ctx.set_option(svtav1_hip.OPT_CONVOLVE_VALU, 1)
             try:
-                t_valu = ipp.timed(torch, trans, a.iters)
+                t_valu = timed(torch, trans, a.iters).median
             finally:
                 ctx.set_option(svtav1_hip.OPT_CONVOLVE_VALU, 0)
             assert ctx.inter_pred_refused() == 0
             row = {"bd": bd, "size": f"{bw}x{bh}", "n_pu": n, "warped_us": round(t_warp, 2), "translational_us": round(t_def, 2),
                    "translational_valu_us": round(t_valu, 2), "ratio_vs_default": round(t_warp / t_def, 3), "ratio_vs_valu": round(t_warp / t_valu, 3)}
-            lines.append(row)
-            print(json.dumps(row), flush=True)
+            emit(lines, row)
     ctx.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in lines:
-                f.write(json.dumps(r) + "\n")
+    write_rows(a.out, lines, append=False)
 
 
 if __name__ == "__main__":
