@@ -1654,6 +1654,102 @@ int32_t svthip_av1_highbd_add_film_grain_dev(svthip_ctx *ctx, const svthip_film_
                                              uint32_t height, uint32_t bit_depth, const int16_t *d_tables, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Film-grain ESTIMATION, the parts of aom_denoise_and_model_run (Codec/noise_model.c:1744-1822; called from
+ * Codec/EbPictureAnalysisProcess.c:3328 when film_grain_denoise_strength is set) whose arithmetic is IEEE double in a fixed order of
+ * operations: the noise model, aom_noise_model_update (:1030-1147), and the sample work of the flat-block finder,
+ * aom_flat_block_finder_run (:580-686).  Every double these entries write equals the reference's bit for bit: a running sum is one
+ * lane's serial sum in the reference's order, no product is fused with an addition, a division is the IEEE division.
+ * What calls libm or sorts stays on the host with the reference's own functions: aom_wiener_denoise_2d (the float FFT filter), the
+ * flatness score 1 / (1 + exp(..)) with its qsort and top-decile union (:666-698), aom_noise_model_save_latest and
+ * aom_noise_model_get_grain_parameters (log2).  The chain is therefore NOT device-resident yet: features and state are downloaded.
+ *
+ * 4:2:0 (chroma_sub_log2 is hard-wired to {1, 1}, :1752), 8 bits and 10 bits; the 10-bit planes are the packed 16-bit picture of
+ * pack_2d_pic, which svthip_pa_pack_10bit_dev produces.  block_size, lag and shape are the values denoise_and_model_ctor and
+ * denoise_and_model_realloc_if_necessary set (DENOISING_BlockSize 32; AOM_NOISE_SHAPE_SQUARE, lag 3, :1631): 24 unknowns for luma, 25
+ * for chroma (the 25th is the correlation with luma), 20 strength bins.  All pointers but ctx and the plane / stride arrays are device
+ * pointers; planes point at sample (0, 0), strides are in samples; the work is enqueued on `stream` (NULL: the context's) and nothing
+ * synchronises with the host.
+ *
+ * svthip_[highbd_]film_grain_noise_model_dev: aom_noise_model_init + aom_noise_model_update of one picture.  d_flat_blocks: one byte
+ * per 32x32 block of the luma plane in raster order, ((width + 31) / 32) * ((height + 31) / 32) of them, any non-zero value is flat.
+ * *d_state receives latest_state[c] and combined_state[c] for c = Y, Cb, Cr; a system of n unknowns has its A packed with a row pitch
+ * of n in the first n * n doubles, as the reference has it, the rest is 0.  status is the aom_noise_status_t; when it is not OK the
+ * struct holds what the reference had written up to its return, on a model fresh from aom_noise_model_init (zeros, ar_gain 1).
+ * Reproduced as written: y_start / x_start by the flat neighbour above / left, the three arms of x_end and its width - lag, y_end
+ * without lag (:843-853); the gate num_samples_w * num_samples_h > block_size of the strength measurements (:914); linsolve's pivot
+ * search, row exchanges and TINY_NEAR_ZERO returns with x partly written (Codec/mathutils.h:26-60); the chroma fallback solution
+ * (:238-247); aom_noise_strength_solver_solve adding mean / 8192 into the solver's own b on EVERY call, so that combined_state, a copy
+ * taken after latest_state's solve and solved again, has it added twice (:314-350, :1134-1141).  If every flat block fails the gate the
+ * reference divides 0 by 0; the NaNs' sign and payload are then not pinned.
+ * Launches: the observations (a lane per entry of A's upper half and of b, all channels at once), the block means and noise variances,
+ * then one workgroup for the solves and the strength walk; the intermediate sums live in context scratch.
+ *
+ * svthip_[highbd_]film_grain_flat_block_features_dev: per 32x32 block of the luma plane aom_flat_block_finder_extract_block (edge
+ * clamp, division by the normalisation, the three multiply_mat products with their 1024-term serial sums), the gradient covariance,
+ * mean and variance over the interior, then trace, ratio, norm and var as the reference has them in :649-657 and the thresholded
+ * is_flat byte (255 / 0, :670) into d_is_flat.  The host finishes with the reference's score, sort and union on the downloaded
+ * features.  d_tables: the block svthip_film_grain_flat_block_tables_dev wrote, or NULL: the entry then builds it
+ * in context scratch on the same stream first.
+ * svthip_film_grain_flat_block_tables_dev: A[1024][3] then AtA_inv[3][3] of aom_flat_block_finder_init (:483-510), built with the
+ * reference's arithmetic; they do not depend on the bit depth.  SVTHIP_FILM_GRAIN_FLAT_TABLES_DOUBLES doubles, 8-byte aligned.
+ *
+ * Refused with SVTHIP_ERR_BAD_PARAMETER before any launch: a NULL context, array, plane, map or output; block_size other than 32, lag
+ * other than 3, a shape other than SVTHIP_FILM_GRAIN_NOISE_SHAPE_SQUARE; odd or zero width or height, or one above 65536; a stride
+ * smaller than the plane width; a bit depth other than 10 (highbd entries); 16-bit planes not 2-byte aligned, d_state, d_features or
+ * d_tables not 8-byte aligned. */
+#define SVTHIP_FILM_GRAIN_NOISE_BLOCK_SIZE 32  /* DENOISING_BlockSize */
+#define SVTHIP_FILM_GRAIN_NOISE_LAG 3
+#define SVTHIP_FILM_GRAIN_NOISE_SHAPE_SQUARE 1 /* AOM_NOISE_SHAPE_SQUARE */
+#define SVTHIP_FILM_GRAIN_NOISE_MAX_COEFFS 25
+#define SVTHIP_FILM_GRAIN_NOISE_BINS 20
+#define SVTHIP_FILM_GRAIN_NOISE_OK 0                       /* aom_noise_status_t */
+#define SVTHIP_FILM_GRAIN_NOISE_INVALID_ARGUMENT 1
+#define SVTHIP_FILM_GRAIN_NOISE_INSUFFICIENT_FLAT_BLOCKS 2
+#define SVTHIP_FILM_GRAIN_NOISE_DIFFERENT_NOISE_TYPE 3
+#define SVTHIP_FILM_GRAIN_NOISE_INTERNAL_ERROR 4
+#define SVTHIP_FILM_GRAIN_FLAT_TABLES_DOUBLES 3081 /* 1024 * 3 + 3 * 3 */
+
+typedef struct svthip_film_grain_noise_channel { /* aom_noise_state_t */
+    double A[625]; /* eqns: n = 24 (Y) or 25 (Cb, Cr) unknowns, row pitch n */
+    double b[SVTHIP_FILM_GRAIN_NOISE_MAX_COEFFS];
+    double x[SVTHIP_FILM_GRAIN_NOISE_MAX_COEFFS];
+    double ar_gain;
+    double strength_A[400]; /* strength_solver.eqns: 20 bins */
+    double strength_b[SVTHIP_FILM_GRAIN_NOISE_BINS];
+    double strength_x[SVTHIP_FILM_GRAIN_NOISE_BINS];
+    double strength_total;
+    int32_t strength_num_equations;
+    int32_t num_observations;
+} svthip_film_grain_noise_channel;
+
+typedef struct svthip_film_grain_noise_state {
+    svthip_film_grain_noise_channel latest[3];
+    svthip_film_grain_noise_channel combined[3];
+    int32_t status;
+    int32_t reserved;
+} svthip_film_grain_noise_state;
+
+typedef struct svthip_film_grain_flat_block_features {
+    double trace, ratio, norm, var;
+} svthip_film_grain_flat_block_features;
+
+int32_t svthip_film_grain_noise_model_dev(svthip_ctx *ctx, const void *const d_data[3], const void *const d_denoised[3],
+                                          const uint32_t stride[3], uint32_t width, uint32_t height, uint32_t block_size, uint32_t lag,
+                                          uint32_t shape, const uint8_t *d_flat_blocks, svthip_film_grain_noise_state *d_state, void *stream);
+int32_t svthip_highbd_film_grain_noise_model_dev(svthip_ctx *ctx, const void *const d_data[3], const void *const d_denoised[3],
+                                                 const uint32_t stride[3], uint32_t width, uint32_t height, uint32_t bit_depth,
+                                                 uint32_t block_size, uint32_t lag, uint32_t shape, const uint8_t *d_flat_blocks,
+                                                 svthip_film_grain_noise_state *d_state, void *stream);
+int32_t svthip_film_grain_flat_block_tables_dev(svthip_ctx *ctx, double *d_tables, void *stream);
+int32_t svthip_film_grain_flat_block_features_dev(svthip_ctx *ctx, const void *d_luma, uint32_t stride, uint32_t width, uint32_t height,
+                                                  uint32_t block_size, const double *d_tables,
+                                                  svthip_film_grain_flat_block_features *d_features, uint8_t *d_is_flat, void *stream);
+int32_t svthip_highbd_film_grain_flat_block_features_dev(svthip_ctx *ctx, const void *d_luma, uint32_t stride, uint32_t width,
+                                                         uint32_t height, uint32_t bit_depth, uint32_t block_size, const double *d_tables,
+                                                         svthip_film_grain_flat_block_features *d_features, uint8_t *d_is_flat,
+                                                         void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mode decision's fast loop: the second loop of ProductPerformFastLoop (Codec/EbProductCodingLoop.c:1282-1459) after the predictions,
  * which the prediction entries above leave in device memory, and PreModeDecision (Codec/EbModeDecision.c:393-471) behind it.  8-bit
  * planes only, as the reference's fast loop (it runs on 8-bit planes for 10-bit input too).  Pure integer arithmetic, bit-identical.

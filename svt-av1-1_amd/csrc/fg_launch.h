@@ -1,4 +1,4 @@
-// svt-av1-1_amd/csrc/fg_launch.h -- launch boundary of the film-grain family (fg_grain.hip): what the C-ABI glue calls.
+// svt-av1-1_amd/csrc/fg_launch.h -- launch boundary of the film-grain family (fg_grain.hip, fg_noise_model.hip): what the C-ABI glue calls.
 #pragma once
 #include "svthip_internal.h"
 
@@ -8,5 +8,17 @@ namespace svthip {
 hipError_t launch_film_grain_tables(const svthip_film_grain_params& params, int bit_depth, int16_t* tables, hipStream_t s);
 hipError_t launch_film_grain_frame(const svthip_film_grain_params& params, int bit_depth, const void* const src[3], const uint32_t src_stride[3],
                                    void* const dst[3], const uint32_t dst_stride[3], uint32_t width, uint32_t height, const int16_t* tables, hipStream_t s);
+
+// fg_noise_model.hip: film-grain estimation -- the noise model and the flat-block features (kernels: fg_noise_model_kernels.h)
+// SLOT_FG_NOISE_MODEL for a w x h picture:  obs[3][352] doubles | block stats[3][blocks] (mean, var) | n_obs[3]
+struct FgNoiseModelLayout {
+    size_t stats, n_obs, total;   // byte offsets of the arrays behind obs, size of the slot
+};
+FgNoiseModelLayout fg_noise_model_layout(uint32_t width, uint32_t height);
+hipError_t launch_film_grain_noise_model(int bit_depth, const void* const data[3], const void* const denoised[3], const uint32_t stride[3], uint32_t width,
+                                         uint32_t height, const uint8_t* flat_blocks, void* scratch, svthip_film_grain_noise_state* state, hipStream_t s);
+hipError_t launch_film_grain_flat_block_tables(double* tables, hipStream_t s);
+hipError_t launch_film_grain_flat_block_features(int bit_depth, const void* luma, uint32_t stride, uint32_t width, uint32_t height, const double* tables,
+                                                 svthip_film_grain_flat_block_features* features, uint8_t* is_flat, hipStream_t s);
 
 }  // namespace svthip

@@ -29,6 +29,8 @@ enum Slot {
     SLOT_PA_SSE_PARTIALS, // workgroup sums of the picture SSE entries on their way to d_sse: svthip::pa_sse_partial_bytes
     SLOT_INLOOP_DESC,     // search areas of svthip_me_inloop_search_dev on their way to its full-pel search: inloop_desc_bytes
     SLOT_INLOOP_PLANES,   // half-pel planes of the in-loop sub-pel refinement, three per (picture, SB): svthip::inloop_planes_bytes
+    SLOT_FG_NOISE_MODEL,  // sums of svthip_[highbd_]film_grain_noise_model_dev on their way to the state: svthip::fg_noise_model_layout
+    SLOT_FG_FLAT_TABLES,  // the table block of the one-call flat-block form: SVTHIP_FILM_GRAIN_FLAT_TABLES_DOUBLES doubles
     SLOT_COUNT
 };
 

@@ -1,4 +1,6 @@
-"""AV1 film-grain synthesis (svthip_film_grain_tables_dev, svthip_av1_[highbd_]add_film_grain_dev): pointer marshalling only.
+"""AV1 film-grain synthesis (svthip_film_grain_tables_dev, svthip_av1_[highbd_]add_film_grain_dev) and estimation
+(svthip_[highbd_]film_grain_noise_model_dev, svthip_film_grain_flat_block_tables_dev, svthip_[highbd_]film_grain_flat_block_features_dev):
+pointer marshalling only.
 
 The parameter block svthip_film_grain_params crosses Python as a packed buffer built by film_grain_params(**fields): the layout of
 aom_film_grain_t, all int32 in declaration order, then the uint16 random_seed and a reserved uint16."""
@@ -19,6 +21,23 @@ _PACKED = "<" + "".join(f"{n}{code}" for _, code, n in _FILM_GRAIN_FIELDS)
 FILM_GRAIN_PARAMS_BYTES = _LAYOUT.itemsize
 assert struct.calcsize(_PACKED) == FILM_GRAIN_PARAMS_BYTES   # the C struct has no implicit padding: the packed words are its layout
 FILM_GRAIN_TABLES_BYTES = _abi.define("SVTHIP_FILM_GRAIN_TABLES_BYTES")
+FILM_GRAIN_NOISE_BLOCK_SIZE = _abi.define("SVTHIP_FILM_GRAIN_NOISE_BLOCK_SIZE")
+FILM_GRAIN_NOISE_LAG = _abi.define("SVTHIP_FILM_GRAIN_NOISE_LAG")
+FILM_GRAIN_NOISE_SHAPE_SQUARE = _abi.define("SVTHIP_FILM_GRAIN_NOISE_SHAPE_SQUARE")
+FILM_GRAIN_NOISE_OK = _abi.define("SVTHIP_FILM_GRAIN_NOISE_OK")
+FILM_GRAIN_NOISE_INSUFFICIENT_FLAT_BLOCKS = _abi.define("SVTHIP_FILM_GRAIN_NOISE_INSUFFICIENT_FLAT_BLOCKS")
+FILM_GRAIN_NOISE_INTERNAL_ERROR = _abi.define("SVTHIP_FILM_GRAIN_NOISE_INTERNAL_ERROR")
+FILM_GRAIN_FLAT_TABLES_DOUBLES = _abi.define("SVTHIP_FILM_GRAIN_FLAT_TABLES_DOUBLES")
+
+
+def film_grain_noise_state_dtype() -> np.dtype:
+    """svthip_film_grain_noise_state: latest[3] and combined[3] of svthip_film_grain_noise_channel, status"""
+    return _abi.dtype("svthip_film_grain_noise_state")
+
+
+def film_grain_flat_block_features_dtype() -> np.dtype:
+    """svthip_film_grain_flat_block_features: trace, ratio, norm, var of one 32x32 block"""
+    return _abi.dtype("svthip_film_grain_flat_block_features")
 
 
 def film_grain_param_offsets() -> dict:
@@ -69,3 +88,33 @@ class FilmGrain:
         src, ss = _planes(d_src, src_stride)
         dst, ds = _planes(d_dst, dst_stride)
         _check(lib().svthip_av1_highbd_add_film_grain_dev(self._h, params, src, ss, dst, ds, width, height, bit_depth, d_tables, stream))
+
+    def film_grain_noise_model_dev(self, d_data, d_denoised, stride, width, height, d_flat_blocks, d_state, block_size=FILM_GRAIN_NOISE_BLOCK_SIZE,
+                                   lag=FILM_GRAIN_NOISE_LAG, shape=FILM_GRAIN_NOISE_SHAPE_SQUARE, stream=None):
+        """aom_noise_model_init + aom_noise_model_update on 8-bit planes with the given flat-block map into *d_state"""
+        data, st = _planes(d_data, stride)
+        den, _ = _planes(d_denoised, None)
+        _check(lib().svthip_film_grain_noise_model_dev(self._h, data, den, st, width, height, block_size, lag, shape, d_flat_blocks, d_state, stream))
+
+    def highbd_film_grain_noise_model_dev(self, d_data, d_denoised, stride, width, height, bit_depth, d_flat_blocks, d_state,
+                                          block_size=FILM_GRAIN_NOISE_BLOCK_SIZE, lag=FILM_GRAIN_NOISE_LAG, shape=FILM_GRAIN_NOISE_SHAPE_SQUARE, stream=None):
+        """the same on 16-bit planes of 10-bit samples"""
+        data, st = _planes(d_data, stride)
+        den, _ = _planes(d_denoised, None)
+        _check(lib().svthip_highbd_film_grain_noise_model_dev(self._h, data, den, st, width, height, bit_depth, block_size, lag, shape, d_flat_blocks,
+                                                              d_state, stream))
+
+    def film_grain_flat_block_tables_dev(self, d_tables, stream=None):
+        """A | AtA_inv of aom_flat_block_finder_init into d_tables (FILM_GRAIN_FLAT_TABLES_DOUBLES doubles)"""
+        _check(lib().svthip_film_grain_flat_block_tables_dev(self._h, d_tables, stream))
+
+    def film_grain_flat_block_features_dev(self, d_luma, stride, width, height, d_features, d_is_flat, d_tables=None,
+                                           block_size=FILM_GRAIN_NOISE_BLOCK_SIZE, stream=None):
+        """the features and thresholded is_flat byte of every 32x32 block of an 8-bit luma plane; d_tables None builds the tables in scratch"""
+        _check(lib().svthip_film_grain_flat_block_features_dev(self._h, d_luma, stride, width, height, block_size, d_tables, d_features, d_is_flat, stream))
+
+    def highbd_film_grain_flat_block_features_dev(self, d_luma, stride, width, height, bit_depth, d_features, d_is_flat, d_tables=None,
+                                                  block_size=FILM_GRAIN_NOISE_BLOCK_SIZE, stream=None):
+        """the same on a 16-bit plane of 10-bit samples"""
+        _check(lib().svthip_highbd_film_grain_flat_block_features_dev(self._h, d_luma, stride, width, height, bit_depth, block_size, d_tables, d_features,
+                                                                     d_is_flat, stream))
