@@ -1659,9 +1659,10 @@ int32_t svthip_av1_highbd_add_film_grain_dev(svthip_ctx *ctx, const svthip_film_
  * operations: the noise model, aom_noise_model_update (:1030-1147), and the sample work of the flat-block finder,
  * aom_flat_block_finder_run (:580-686).  Every double these entries write equals the reference's bit for bit: a running sum is one
  * lane's serial sum in the reference's order, no product is fused with an addition, a division is the IEEE division.
- * What calls libm or sorts stays on the host with the reference's own functions: aom_wiener_denoise_2d (the float FFT filter), the
- * flatness score 1 / (1 + exp(..)) with its qsort and top-decile union (:666-698), aom_noise_model_save_latest and
- * aom_noise_model_get_grain_parameters (log2).  The chain is therefore NOT device-resident yet: features and state are downloaded.
+ * aom_wiener_denoise_2d, the float FFT filter between the two, is on the device too (the Wiener denoising entries below): its only libm
+ * call fills a fixed table.  What is NOT device-resident is what calls libm per picture or sorts, and it stays the reference's own host
+ * code: the flatness score 1 / (1 + exp(..)) with its qsort and top-decile union (:666-698), aom_noise_model_save_latest and
+ * aom_noise_model_get_grain_parameters (log2).  Only the feature table and the state cross to the host; the planes stay.
  *
  * 4:2:0 (chroma_sub_log2 is hard-wired to {1, 1}, :1752), 8 bits and 10 bits; the 10-bit planes are the packed 16-bit picture of
  * pack_2d_pic, which svthip_pa_pack_10bit_dev produces.  block_size, lag and shape are the values denoise_and_model_ctor and
@@ -1748,6 +1749,61 @@ int32_t svthip_highbd_film_grain_flat_block_features_dev(svthip_ctx *ctx, const 
                                                          uint32_t height, uint32_t bit_depth, uint32_t block_size, const double *d_tables,
                                                          svthip_film_grain_flat_block_features *d_features, uint8_t *d_is_flat,
                                                          void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Film-grain Wiener DENOISING: aom_wiener_denoise_2d (Codec/noise_model.c:1363-1500), the third part of aom_denoise_and_model_run, which
+ * makes the denoised planes the noise model reads.  4:2:0, 8 and 10 bits, block_size 32 (chroma blocks 16), as
+ * denoise_and_model_realloc_if_necessary configures it.  Every float equals the reference's bit for bit, and so does every sample:
+ *   - aom_flat_block_finder_extract_block (:522-563) at the offsets of the four half-overlapped passes, bx and by from -1, coordinates
+ *     clamped on both sides; chroma at block size 16 with the tables aom_flat_block_finder_init's arithmetic gives at n = 16; the three
+ *     multiply_mat products keep their serial 1024- / 256-term double sums;
+ *   - the half-cosine window (:1314-1326) as (float)(cos_y * cos_x) of the 32 + 16 doubles of csrc/fg_cos_window.inc
+ *     (tools/gen_fg_cos_window.py): cos is not called at run time;
+ *   - aom_fft_2d_gen (Codec/fft.c:58-72) over the 1-D networks of Codec/fft_common.h, with their six-digit constants and the association
+ *     of every butterfly; aom_noise_tx_filter (Codec/noise_util.c:93-112): p > kBeta * psd in float, p > 1e-6 in double, the IEEE float
+ *     division of the gain; aom_ifft_2d_gen (:114-184) as the reference's run-time dispatch configures it on an AVX2 host (vec_size 8;
+ *     there is no C inverse above 2x2), then the division by n * n of aom_noise_tx_inverse;
+ *   - result += (block + plane * window) * window (:1455-1466): a sample receives up to four contributions, added to +0.0f in the order
+ *     of the passes (0, 0), (0, 1/2), (1/2, 0), (1/2, 1/2), each pass a launch; no float atomics;
+ *   - dither_and_quantize_{lowbd,highbd} (:1328-1361): serial error diffusion, a lane per row on the wavefront x + 2 y, a band of 64
+ *     rows after the other in one workgroup's loop; no workgroup waits on another.
+ * fp32 denormals are kept and nothing is contracted or reassociated.
+ *
+ * svthip_[highbd_]film_grain_wiener_filter_dev: the four passes of all three planes into d_planes, three float planes one behind the
+ * other, each svthip_film_grain_wiener_workspace_bytes(width, height) / 3 bytes, in the reference's `result` geometry: row pitch
+ * ((width + 31) / 32 + 2) * 32 floats for all three, picture sample (x, y) of plane p at (y + (32 >> sub)) * pitch + x + (32 >> sub) with
+ * sub = 0 for Y and 1 for Cb, Cr.  Only the picture area of each plane is defined; the margin keeps what it held.
+ * d_noise_psd[3]: device arrays as the reference takes them, 1024 floats for Y; Cb and Cr read the first 256.
+ * svthip_film_grain_noise_psd_default is aom_noise_psd_get_default_value (Codec/noise_util.c:25) on the host, in float as written: *psd
+ * receives the value for *factor (both host pointers; no context, SVTHIP_ERR_BAD_PARAMETER when one is NULL).
+ * svthip_[highbd_]film_grain_dither_dev: those planes into 8- or 16-bit samples.  The float planes are scratch afterwards (the errors
+ * are diffused into them in the reference; here they are left as they were, which callers must not rely on).
+ * svthip_[highbd_]film_grain_wiener_denoise_dev: both stages in one call with the float planes in context scratch.
+ * All entries enqueue on `stream` (NULL: the context's) and do not synchronise with the host; tables and the dither's hand-over rows live
+ * in context scratch.
+ *
+ * Refused with SVTHIP_ERR_BAD_PARAMETER before any launch: a NULL context, array, plane, psd or output; block_size other than 32; odd or
+ * zero width or height, or one above 65536; a stride smaller than the plane width; a bit depth other than 10 (highbd entries); 16-bit
+ * planes not 2-byte aligned, psd arrays or d_planes not 4-byte aligned. */
+size_t svthip_film_grain_wiener_workspace_bytes(uint32_t width, uint32_t height);
+int32_t svthip_film_grain_noise_psd_default(uint32_t block_size, const float *factor, float *psd);
+int32_t svthip_film_grain_wiener_filter_dev(svthip_ctx *ctx, const void *const d_data[3], const uint32_t stride[3], uint32_t width,
+                                            uint32_t height, uint32_t block_size, const float *const d_noise_psd[3], float *d_planes,
+                                            void *stream);
+int32_t svthip_highbd_film_grain_wiener_filter_dev(svthip_ctx *ctx, const void *const d_data[3], const uint32_t stride[3], uint32_t width,
+                                                   uint32_t height, uint32_t bit_depth, uint32_t block_size,
+                                                   const float *const d_noise_psd[3], float *d_planes, void *stream);
+int32_t svthip_film_grain_dither_dev(svthip_ctx *ctx, float *d_planes, void *const d_denoised[3], const uint32_t stride[3], uint32_t width,
+                                     uint32_t height, uint32_t block_size, void *stream);
+int32_t svthip_highbd_film_grain_dither_dev(svthip_ctx *ctx, float *d_planes, void *const d_denoised[3], const uint32_t stride[3],
+                                            uint32_t width, uint32_t height, uint32_t bit_depth, uint32_t block_size, void *stream);
+int32_t svthip_film_grain_wiener_denoise_dev(svthip_ctx *ctx, const void *const d_data[3], const uint32_t data_stride[3],
+                                             void *const d_denoised[3], const uint32_t denoised_stride[3], uint32_t width, uint32_t height,
+                                             uint32_t block_size, const float *const d_noise_psd[3], void *stream);
+int32_t svthip_highbd_film_grain_wiener_denoise_dev(svthip_ctx *ctx, const void *const d_data[3], const uint32_t data_stride[3],
+                                                    void *const d_denoised[3], const uint32_t denoised_stride[3], uint32_t width,
+                                                    uint32_t height, uint32_t bit_depth, uint32_t block_size,
+                                                    const float *const d_noise_psd[3], void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Mode decision's fast loop: the second loop of ProductPerformFastLoop (Codec/EbProductCodingLoop.c:1282-1459) after the predictions,

@@ -114,6 +114,68 @@ int32_t flat_block_features_entry(svthip_ctx* ctx, const void* d_luma, uint32_t 
     return SVTHIP_OK;
 }
 
+// what the denoising entries share: the picture, the planes of one role per call
+int32_t check_denoise_planes(const void* const planes[3], const uint32_t stride[3], uint32_t width, int bd)
+{
+    for (int p = 0; p < 3; p++) {
+        TRY(check_non_null({planes[p]}));
+        const uint32_t w = p ? width / 2 : width;
+        if (stride[p] < w) return fail(SVTHIP_ERR_BAD_PARAMETER, "the stride of plane %d must be >= its width %u", p, (unsigned)w);
+        if (bd > 8 && !aligned(planes[p], 2)) return fail(SVTHIP_ERR_BAD_PARAMETER, "16-bit planes must be 2-byte aligned (plane %d)", p);
+    }
+    return SVTHIP_OK;
+}
+
+int32_t wiener_filter_entry(svthip_ctx* ctx, const void* const d_data[3], const uint32_t stride[3], uint32_t width, uint32_t height, int bd, uint32_t block_size,
+                            const float* const d_noise_psd[3], float* d_planes, void* stream)
+{
+    TRY(check_non_null({d_data, stride, d_noise_psd, d_planes}));
+    TRY(check_estimation_picture(width, height, block_size));
+    TRY(check_denoise_planes(d_data, stride, width, bd));
+    TRY(check_non_null({d_noise_psd[0], d_noise_psd[1], d_noise_psd[2]}));
+    if (!aligned({d_noise_psd[0], d_noise_psd[1], d_noise_psd[2], d_planes}, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_noise_psd and d_planes must be 4-byte aligned");
+    hipStream_t s = call_stream(ctx, stream);
+    TRY(ensure_scratch(ctx, SLOT_FG_DENOISE, svthip::fg_denoise_layout(width, height).planes));
+    TRY(scratch_on_stream(ctx, s));
+    HIP_TRY(svthip::launch_film_grain_wiener_filter(bd, d_data, stride, width, height, d_noise_psd, d_planes, slot_ptr<double>(ctx, SLOT_FG_DENOISE), s));
+    return SVTHIP_OK;
+}
+
+int32_t dither_entry(svthip_ctx* ctx, float* d_planes, void* const d_denoised[3], const uint32_t stride[3], uint32_t width, uint32_t height, int bd,
+                     uint32_t block_size, void* stream)
+{
+    TRY(check_non_null({d_planes, d_denoised, stride}));
+    TRY(check_estimation_picture(width, height, block_size));
+    TRY(check_denoise_planes(d_denoised, stride, width, bd));
+    if (!aligned(d_planes, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_planes must be 4-byte aligned");
+    hipStream_t s = call_stream(ctx, stream);
+    const svthip::FgDenoiseLayout L = svthip::fg_denoise_layout(width, height);
+    TRY(ensure_scratch(ctx, SLOT_FG_DENOISE, L.planes));
+    TRY(scratch_on_stream(ctx, s));
+    HIP_TRY(svthip::launch_film_grain_dither(bd, d_planes, d_denoised, stride, width, height, slot_ptr<float>(ctx, SLOT_FG_DENOISE, L.err_rows), s));
+    return SVTHIP_OK;
+}
+
+int32_t wiener_denoise_entry(svthip_ctx* ctx, const void* const d_data[3], const uint32_t data_stride[3], void* const d_denoised[3],
+                             const uint32_t denoised_stride[3], uint32_t width, uint32_t height, int bd, uint32_t block_size,
+                             const float* const d_noise_psd[3], void* stream)
+{
+    TRY(check_non_null({d_data, data_stride, d_denoised, denoised_stride, d_noise_psd}));
+    TRY(check_estimation_picture(width, height, block_size));
+    TRY(check_denoise_planes(d_data, data_stride, width, bd));
+    TRY(check_denoise_planes(d_denoised, denoised_stride, width, bd));
+    TRY(check_non_null({d_noise_psd[0], d_noise_psd[1], d_noise_psd[2]}));
+    if (!aligned({d_noise_psd[0], d_noise_psd[1], d_noise_psd[2]}, 4)) return fail(SVTHIP_ERR_BAD_PARAMETER, "d_noise_psd must be 4-byte aligned");
+    hipStream_t s = call_stream(ctx, stream);
+    const svthip::FgDenoiseLayout L = svthip::fg_denoise_layout(width, height);
+    TRY(ensure_scratch(ctx, SLOT_FG_DENOISE, L.total));
+    TRY(scratch_on_stream(ctx, s));
+    float* planes = slot_ptr<float>(ctx, SLOT_FG_DENOISE, L.planes);
+    HIP_TRY(svthip::launch_film_grain_wiener_filter(bd, d_data, data_stride, width, height, d_noise_psd, planes, slot_ptr<double>(ctx, SLOT_FG_DENOISE), s));
+    HIP_TRY(svthip::launch_film_grain_dither(bd, planes, d_denoised, denoised_stride, width, height, slot_ptr<float>(ctx, SLOT_FG_DENOISE, L.err_rows), s));
+    return SVTHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -190,6 +252,69 @@ int32_t svthip_highbd_film_grain_flat_block_features_dev(svthip_ctx* ctx, const 
     TRY(enter(ctx));
     TRY(check_bit_depth_10(bit_depth));
     return flat_block_features_entry(ctx, d_luma, stride, width, height, 10, block_size, d_tables, d_features, d_is_flat, stream);
+}
+
+// ---------------------------------------------------------------- film-grain Wiener denoising
+
+size_t svthip_film_grain_wiener_workspace_bytes(uint32_t width, uint32_t height)
+{
+    return sizeof(float) * 3 * svthip::fg_denoise_layout(width, height).plane_floats;
+}
+
+int32_t svthip_film_grain_noise_psd_default(uint32_t block_size, const float* factor, float* psd)
+{
+#pragma clang fp contract(off)
+    TRY(check_non_null({factor, psd}));
+    const int32_t n = (int32_t)block_size;   // aom_noise_psd_get_default_value (Codec/noise_util.c:25) in float as written
+    *psd = (*factor * *factor / 10000) * n * n / 8;
+    return SVTHIP_OK;
+}
+
+int32_t svthip_film_grain_wiener_filter_dev(svthip_ctx* ctx, const void* const d_data[3], const uint32_t stride[3], uint32_t width, uint32_t height,
+                                            uint32_t block_size, const float* const d_noise_psd[3], float* d_planes, void* stream)
+{
+    TRY(enter(ctx));
+    return wiener_filter_entry(ctx, d_data, stride, width, height, 8, block_size, d_noise_psd, d_planes, stream);
+}
+
+int32_t svthip_highbd_film_grain_wiener_filter_dev(svthip_ctx* ctx, const void* const d_data[3], const uint32_t stride[3], uint32_t width, uint32_t height,
+                                                   uint32_t bit_depth, uint32_t block_size, const float* const d_noise_psd[3], float* d_planes, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return wiener_filter_entry(ctx, d_data, stride, width, height, 10, block_size, d_noise_psd, d_planes, stream);
+}
+
+int32_t svthip_film_grain_dither_dev(svthip_ctx* ctx, float* d_planes, void* const d_denoised[3], const uint32_t stride[3], uint32_t width, uint32_t height,
+                                     uint32_t block_size, void* stream)
+{
+    TRY(enter(ctx));
+    return dither_entry(ctx, d_planes, d_denoised, stride, width, height, 8, block_size, stream);
+}
+
+int32_t svthip_highbd_film_grain_dither_dev(svthip_ctx* ctx, float* d_planes, void* const d_denoised[3], const uint32_t stride[3], uint32_t width,
+                                            uint32_t height, uint32_t bit_depth, uint32_t block_size, void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return dither_entry(ctx, d_planes, d_denoised, stride, width, height, 10, block_size, stream);
+}
+
+int32_t svthip_film_grain_wiener_denoise_dev(svthip_ctx* ctx, const void* const d_data[3], const uint32_t data_stride[3], void* const d_denoised[3],
+                                             const uint32_t denoised_stride[3], uint32_t width, uint32_t height, uint32_t block_size,
+                                             const float* const d_noise_psd[3], void* stream)
+{
+    TRY(enter(ctx));
+    return wiener_denoise_entry(ctx, d_data, data_stride, d_denoised, denoised_stride, width, height, 8, block_size, d_noise_psd, stream);
+}
+
+int32_t svthip_highbd_film_grain_wiener_denoise_dev(svthip_ctx* ctx, const void* const d_data[3], const uint32_t data_stride[3], void* const d_denoised[3],
+                                                    const uint32_t denoised_stride[3], uint32_t width, uint32_t height, uint32_t bit_depth,
+                                                    uint32_t block_size, const float* const d_noise_psd[3], void* stream)
+{
+    TRY(enter(ctx));
+    TRY(check_bit_depth_10(bit_depth));
+    return wiener_denoise_entry(ctx, d_data, data_stride, d_denoised, denoised_stride, width, height, 10, block_size, d_noise_psd, stream);
 }
 
 }  // extern "C"

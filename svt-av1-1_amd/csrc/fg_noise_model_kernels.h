@@ -411,22 +411,24 @@ __host__ __device__ inline void fgm_finish(const FgmPicture& P, const double* ob
 
 // ---------------------------------------------------------------- the flat-block finder
 
-// aom_flat_block_finder_init's tables (:483-510): A[1024][3], then AtA_inv[3][3] by three solves of the running sums of coords coords'
-__host__ __device__ inline void fgf_tables(double* tables, FgmSolveWork& W, double* ata, int lane, int lanes)
+// aom_flat_block_finder_init's tables (:483-510) at block size n: A[n * n][3], then AtA_inv[3][3] by three solves of the running sums
+// of coords coords'.  n is 32 for luma; the Wiener filter's chroma blocks (fg_denoise_kernels.h) use n = 16.
+__host__ __device__ inline void fgf_tables_n(int n, double* tables, FgmSolveWork& W, double* ata, int lane, int lanes)
 {
 #pragma clang fp contract(off)
+    const int nn = n * n;
     double* A = tables;
-    double* inv = tables + FGF_N * FGF_PARAMS;
-    for (int row = lane; row < FGF_N; row += lanes) {
-        const int y = row / FGM_BLOCK, x = row % FGM_BLOCK;
-        A[FGF_PARAMS * row + 0] = ((double)y - FGM_BLOCK / 2.) / (FGM_BLOCK / 2.);
-        A[FGF_PARAMS * row + 1] = ((double)x - FGM_BLOCK / 2.) / (FGM_BLOCK / 2.);
+    double* inv = tables + nn * FGF_PARAMS;
+    for (int row = lane; row < nn; row += lanes) {
+        const int y = row / n, x = row % n;
+        A[FGF_PARAMS * row + 0] = ((double)y - n / 2.) / (n / 2.);
+        A[FGF_PARAMS * row + 1] = ((double)x - n / 2.) / (n / 2.);
         A[FGF_PARAMS * row + 2] = 1;
     }
     __syncthreads();
     for (int e = lane; e < FGF_PARAMS * FGF_PARAMS; e += lanes) {
         double sum = 0;
-        for (int row = 0; row < FGF_N; row++) {
+        for (int row = 0; row < nn; row++) {
             const double p = A[FGF_PARAMS * row + e / FGF_PARAMS] * A[FGF_PARAMS * row + e % FGF_PARAMS];
             sum += p;
         }
@@ -443,23 +445,30 @@ __host__ __device__ inline void fgf_tables(double* tables, FgmSolveWork& W, doub
         __syncthreads();
     }
 }
+__host__ __device__ inline void fgf_tables(double* tables, FgmSolveWork& W, double* ata, int lane, int lanes)
+{
+    fgf_tables_n(FGM_BLOCK, tables, W, ata, lane, lanes);
+}
 
-// aom_flat_block_finder_extract_block (:522-563) into blk (LDS, 1024 doubles), `fit` holding AtA_inv_b then plane_coords
+// aom_flat_block_finder_extract_block (:522-563) at block size n and any offset (coordinates are clamped on both sides) into blk (LDS,
+// n * n doubles), `fit` holding AtA_inv_b; plane_f, where given, receives (float) of the fitted plane of every sample
 template <typename T>
-__host__ __device__ inline void fgf_extract(const T* data, int w, int h, uint32_t stride, int offsx, int offsy, double normalization,
-                                            const double* tables, double* blk, double* fit, int lane, int lanes)
+__host__ __device__ inline void fgf_extract_n(int n, const T* data, int w, int h, uint32_t stride, int offsx, int offsy, double normalization,
+                                              const double* tables, double* blk, double* fit, float* plane_f, int lane, int lanes)
 {
 #pragma clang fp contract(off)
+    const int nn = n * n;
     const double* A = tables;
-    const double* inv = tables + FGF_N * FGF_PARAMS;
-    for (int i = lane; i < FGF_N; i += lanes) {
-        const int y = fgm_min(offsy + i / FGM_BLOCK, h - 1), x = fgm_min(offsx + i % FGM_BLOCK, w - 1);   // offsets are never negative
+    const double* inv = tables + nn * FGF_PARAMS;
+    for (int i = lane; i < nn; i += lanes) {
+        int y = fgm_min(offsy + i / n, h - 1), x = fgm_min(offsx + i % n, w - 1);
+        y = y < 0 ? 0 : y, x = x < 0 ? 0 : x;
         blk[i] = ((double)data[(size_t)y * stride + x]) / normalization;
     }
     __syncthreads();
     for (int c = lane; c < FGF_PARAMS; c += lanes) {
         double sum = 0;
-        for (int i = 0; i < FGF_N; i++) {
+        for (int i = 0; i < nn; i++) {
             const double p = blk[i] * A[i * FGF_PARAMS + c];
             sum += p;
         }
@@ -475,15 +484,22 @@ __host__ __device__ inline void fgf_extract(const T* data, int w, int h, uint32_
         }
         pc[r] = sum;
     }
-    for (int i = lane; i < FGF_N; i += lanes) {
+    for (int i = lane; i < nn; i += lanes) {
         double sum = 0;
         for (int c = 0; c < FGF_PARAMS; c++) {
             const double p = A[i * FGF_PARAMS + c] * pc[c];
             sum += p;
         }
         blk[i] -= sum;
+        if (plane_f) plane_f[i] = (float)sum;
     }
     __syncthreads();
+}
+template <typename T>
+__host__ __device__ inline void fgf_extract(const T* data, int w, int h, uint32_t stride, int offsx, int offsy, double normalization,
+                                            const double* tables, double* blk, double* fit, int lane, int lanes)
+{
+    fgf_extract_n<T>(FGM_BLOCK, data, w, h, stride, offsx, offsy, normalization, tables, blk, fit, nullptr, lane, lanes);
 }
 
 // the five running sums over the interior (:624-639), one per lane: Gxx, Gxy, Gyy, mean, var
@@ -517,7 +533,7 @@ __host__ __device__ inline uint8_t fgf_features(const double sums[5], svthip_fil
     return (trace < kTrace && ratio < kRatio && e1 < kNorm && var > kVar) ? 255 : 0;
 }
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && !defined(SVTHIP_FGM_ARITHMETIC_ONLY)   // fg_denoise_kernels.h shares the arithmetic above, not the kernels
 // ---------------------------------------------------------------- kernels
 
 // grid (FGM_OBS_GROUPS, 3 channels): every lane owns one entry of its channel's A (upper half) or b and walks ALL flat blocks in raster
@@ -595,6 +611,6 @@ __global__ __launch_bounds__(FGM_LANES) void fgf_features_kernel(const T* __rest
     __syncthreads();
     if (threadIdx.x == 0) is_flat[b] = fgf_features(sums, features + b);
 }
-#endif  // __HIPCC__
+#endif  // __HIPCC__ && !SVTHIP_FGM_ARITHMETIC_ONLY
 
 }  // namespace svthip

@@ -318,6 +318,7 @@ int32_t svthip_reserve(svthip_ctx* ctx, uint32_t width, uint32_t height, uint32_
     TRY(ensure_scratch(ctx, SLOT_FILM_GRAIN_TABLES, SVTHIP_FILM_GRAIN_TABLES_BYTES));
     TRY(ensure_scratch(ctx, SLOT_FG_NOISE_MODEL, svthip::fg_noise_model_layout(width, height).total));
     TRY(ensure_scratch(ctx, SLOT_FG_FLAT_TABLES, sizeof(double) * SVTHIP_FILM_GRAIN_FLAT_TABLES_DOUBLES));
+    TRY(ensure_scratch(ctx, SLOT_FG_DENOISE, svthip::fg_denoise_layout(width, height).planes));   // the one-call form's float planes grow it on first use
     TRY(ensure_scratch(ctx, SLOT_PA_SSE_PARTIALS, svthip::pa_sse_partial_bytes(width, height, n_jobs < SVTHIP_HME_MAX_JOBS ? n_jobs : SVTHIP_HME_MAX_JOBS)));
     {   // the interpolation-filter search in its fast mode, one 8x8 candidate per 8x8 block of a picture
         const uint64_t n_cand = (uint64_t)(width / 8) * (height / 8);

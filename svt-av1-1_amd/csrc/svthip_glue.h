@@ -31,6 +31,7 @@ enum Slot {
     SLOT_INLOOP_PLANES,   // half-pel planes of the in-loop sub-pel refinement, three per (picture, SB): svthip::inloop_planes_bytes
     SLOT_FG_NOISE_MODEL,  // sums of svthip_[highbd_]film_grain_noise_model_dev on their way to the state: svthip::fg_noise_model_layout
     SLOT_FG_FLAT_TABLES,  // the table block of the one-call flat-block form: SVTHIP_FILM_GRAIN_FLAT_TABLES_DOUBLES doubles
+    SLOT_FG_DENOISE,      // tables, error rows and (one-call form) float planes of the film-grain Wiener denoising: svthip::fg_denoise_layout
     SLOT_COUNT
 };
 

@@ -31,8 +31,8 @@ from ._restoration import (RESTORE_NONE, RESTORE_SGRPROJ, RESTORE_SWITCHABLE, RE
                            sgrproj_workspace_bytes, wiener_walk_max_trials)
 from ._grain import (FILM_GRAIN_FLAT_TABLES_DOUBLES, FILM_GRAIN_NOISE_BLOCK_SIZE, FILM_GRAIN_NOISE_INSUFFICIENT_FLAT_BLOCKS,
                      FILM_GRAIN_NOISE_INTERNAL_ERROR, FILM_GRAIN_NOISE_LAG, FILM_GRAIN_NOISE_OK, FILM_GRAIN_NOISE_SHAPE_SQUARE, FILM_GRAIN_PARAMS_BYTES,
-                     FILM_GRAIN_TABLES_BYTES, FilmGrain, film_grain_flat_block_features_dtype, film_grain_noise_state_dtype, film_grain_param_offsets,
-                     film_grain_params)
+                     FILM_GRAIN_TABLES_BYTES, FilmGrain, film_grain_flat_block_features_dtype, film_grain_noise_state_dtype, film_grain_noise_psd_default, film_grain_param_offsets,
+                     film_grain_params, film_grain_wiener_workspace_bytes)
 from ._md import (MD_FAST_CHROMA_QUARTER, MD_FAST_INVALID, MD_FAST_LUMA_GIVEN, MD_FAST_MAX_BUFFERS, MD_FAST_MAX_CANDIDATES, MD_FAST_SKIP_DISTORTION,
                   MD_FAST_TYPE_INTER, MD_IFS_REFUSED, MD_IFS_SEARCH_FAST, MD_IFS_SEARCH_FULL, InterpFilterSearch, ModeDecisionFast, md_fast_desc_dtype,
                   md_fast_group_dtype, md_fast_pick_dtype, md_fast_result_dtype, md_ifs_desc_dtype, md_ifs_result_dtype, md_model_rd_desc_dtype,

@@ -1,6 +1,6 @@
 """AV1 film-grain synthesis (svthip_film_grain_tables_dev, svthip_av1_[highbd_]add_film_grain_dev) and estimation
-(svthip_[highbd_]film_grain_noise_model_dev, svthip_film_grain_flat_block_tables_dev, svthip_[highbd_]film_grain_flat_block_features_dev):
-pointer marshalling only.
+(svthip_[highbd_]film_grain_noise_model_dev, svthip_film_grain_flat_block_tables_dev, svthip_[highbd_]film_grain_flat_block_features_dev) and Wiener denoising (svthip_[highbd_]film_grain_wiener_filter_dev, _dither_dev,
+_wiener_denoise_dev): pointer marshalling only.
 
 The parameter block svthip_film_grain_params crosses Python as a packed buffer built by film_grain_params(**fields): the layout of
 aom_film_grain_t, all int32 in declaration order, then the uint16 random_seed and a reserved uint16."""
@@ -28,6 +28,18 @@ FILM_GRAIN_NOISE_OK = _abi.define("SVTHIP_FILM_GRAIN_NOISE_OK")
 FILM_GRAIN_NOISE_INSUFFICIENT_FLAT_BLOCKS = _abi.define("SVTHIP_FILM_GRAIN_NOISE_INSUFFICIENT_FLAT_BLOCKS")
 FILM_GRAIN_NOISE_INTERNAL_ERROR = _abi.define("SVTHIP_FILM_GRAIN_NOISE_INTERNAL_ERROR")
 FILM_GRAIN_FLAT_TABLES_DOUBLES = _abi.define("SVTHIP_FILM_GRAIN_FLAT_TABLES_DOUBLES")
+
+
+def film_grain_wiener_workspace_bytes(width: int, height: int) -> int:
+    """bytes of the three float planes svthip_film_grain_wiener_filter_dev writes and svthip_film_grain_dither_dev reads"""
+    return int(lib().svthip_film_grain_wiener_workspace_bytes(width, height))
+
+
+def film_grain_noise_psd_default(block_size: int, factor: float) -> float:
+    """aom_noise_psd_get_default_value in float"""
+    f, out = C.c_float(factor), C.c_float()
+    _check(lib().svthip_film_grain_noise_psd_default(block_size, C.byref(f), C.byref(out)))
+    return out.value
 
 
 def film_grain_noise_state_dtype() -> np.dtype:
@@ -118,3 +130,42 @@ class FilmGrain:
         """the same on a 16-bit plane of 10-bit samples"""
         _check(lib().svthip_highbd_film_grain_flat_block_features_dev(self._h, d_luma, stride, width, height, bit_depth, block_size, d_tables, d_features,
                                                                      d_is_flat, stream))
+
+    def film_grain_wiener_filter_dev(self, d_data, stride, width, height, d_noise_psd, d_planes, block_size=FILM_GRAIN_NOISE_BLOCK_SIZE, stream=None):
+        """the FFT filter stage of aom_wiener_denoise_2d on 8-bit planes into the three float planes at d_planes"""
+        data, st = _planes(d_data, stride)
+        psd, _ = _planes(d_noise_psd, None)
+        _check(lib().svthip_film_grain_wiener_filter_dev(self._h, data, st, width, height, block_size, psd, d_planes, stream))
+
+    def highbd_film_grain_wiener_filter_dev(self, d_data, stride, width, height, bit_depth, d_noise_psd, d_planes, block_size=FILM_GRAIN_NOISE_BLOCK_SIZE,
+                                            stream=None):
+        """the same on 16-bit planes of 10-bit samples"""
+        data, st = _planes(d_data, stride)
+        psd, _ = _planes(d_noise_psd, None)
+        _check(lib().svthip_highbd_film_grain_wiener_filter_dev(self._h, data, st, width, height, bit_depth, block_size, psd, d_planes, stream))
+
+    def film_grain_dither_dev(self, d_planes, d_denoised, stride, width, height, block_size=FILM_GRAIN_NOISE_BLOCK_SIZE, stream=None):
+        """dither_and_quantize_lowbd of the three float planes into 8-bit planes"""
+        den, st = _planes(d_denoised, stride)
+        _check(lib().svthip_film_grain_dither_dev(self._h, d_planes, den, st, width, height, block_size, stream))
+
+    def highbd_film_grain_dither_dev(self, d_planes, d_denoised, stride, width, height, bit_depth, block_size=FILM_GRAIN_NOISE_BLOCK_SIZE, stream=None):
+        """dither_and_quantize_highbd into 16-bit planes of 10-bit samples"""
+        den, st = _planes(d_denoised, stride)
+        _check(lib().svthip_highbd_film_grain_dither_dev(self._h, d_planes, den, st, width, height, bit_depth, block_size, stream))
+
+    def film_grain_wiener_denoise_dev(self, d_data, data_stride, d_denoised, denoised_stride, width, height, d_noise_psd,
+                                      block_size=FILM_GRAIN_NOISE_BLOCK_SIZE, stream=None):
+        """aom_wiener_denoise_2d on 8-bit planes, the float planes in context scratch"""
+        data, ds = _planes(d_data, data_stride)
+        den, ns = _planes(d_denoised, denoised_stride)
+        psd, _ = _planes(d_noise_psd, None)
+        _check(lib().svthip_film_grain_wiener_denoise_dev(self._h, data, ds, den, ns, width, height, block_size, psd, stream))
+
+    def highbd_film_grain_wiener_denoise_dev(self, d_data, data_stride, d_denoised, denoised_stride, width, height, bit_depth, d_noise_psd,
+                                             block_size=FILM_GRAIN_NOISE_BLOCK_SIZE, stream=None):
+        """the same on 16-bit planes of 10-bit samples"""
+        data, ds = _planes(d_data, data_stride)
+        den, ns = _planes(d_denoised, denoised_stride)
+        psd, _ = _planes(d_noise_psd, None)
+        _check(lib().svthip_highbd_film_grain_wiener_denoise_dev(self._h, data, ds, den, ns, width, height, bit_depth, block_size, psd, stream))
